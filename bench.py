@@ -26,6 +26,11 @@ Rank 0 prints ONE JSON line.  Besides the driver's fields it carries
   cpu_baseline : the AVX2 + threads CPU port of the reference's kernel
                  (oracle/, kind "port") timed on this box's host cores on a
                  bounded sample of the same workload (rank 0, N = 1 only).
+
+--dump-outputs DIR writes what the last timed step computed, the arrays a caller of the timed path receives, as
+DIR/<name>.npy in float64, one row per sample, with the indices of those samples in DIR/sample_index.npy and the place
+and kind of every NaN / inf in DIR/nonfinite.npy (see write_dump; read_dump restores the arrays as computed); the inputs
+are seeded, so two builds run with the same arguments can be compared output for output.
 """
 
 import argparse
@@ -50,6 +55,10 @@ N_SIMD = 256 * 4
 FP64_OP_NS = 2.29
 MFMA_NS = 16.0
 UBENCH_FILE = os.path.join(ROOT, "profiles", "ubench_constants.json")   # parsed from the raw tools/ubench_* logs next to it
+DUMP_BYTES = 60_000_000       # --dump-outputs: what the outputs and sample_index may take; room for nonfinite.npy under 64 MB
+DUMP_LIMIT = 64_000_000       # ... and what the whole dump may take
+DUMP_SEED = 20261015           # ... and the seed of the sample of samples it keeps when the outputs are larger
+OUTPUT_NAMES = ("h1", "h2", "prob", "matching", "dosage", "postprob")    # what the predict entries return, in their order
 
 
 def issue_constants():
@@ -113,7 +122,14 @@ def main():
                     help="--gpus N > 1: one process per GPU under torch.distributed (default; RCCL rendezvous), or ONE process "
                          "with one host thread per GPU through the C ABI (hibag_hip_model_replicate + the device entry), "
                          "the way an R / C++ host would drive a node (INTEGRATION.md section B)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the outputs of the last one (h1, h2, prob, matching, dosage and, with "
+                         "--prob, postprob: one row per sample) as DIR/<name>.npy in float64, the samples they hold as "
+                         "DIR/sample_index.npy (all of them, or, above 64 MB in all, a fixed, seeded sample) and every NaN / "
+                         "inf among them as a row of DIR/nonfinite.npy (sample row, output, column, kind), 0 in its place")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.launcher == "threads" and "WORLD_SIZE" not in os.environ:
         return main_threads(args)
@@ -240,12 +256,13 @@ def main():
             dist.barrier()
         torch.cuda.synchronize(dev)
 
-    def timed(fn, warmup, steps, mdl):
+    def timed(fn, warmup, steps, mdl, after=None):
         """W untimed warm-up steps, then exactly K timed steps between fences.  Inside the timed region HIP events bracket
         the DOMINANT kernel only (the roofline's `avg_launch_ms` is measured live there, as the contract asks): an event
         record is a packet of its own on the queue, and five of them per step cost 2 % of it.  Which kernel dominates is
         found in two untimed steps before the warm-up; the other kernels' times come from up to ten more steps with every
-        kernel class bracketed, AFTER the timed region."""
+        kernel class bracketed, AFTER the timed region.  `after` is called between the two, when the output buffers still
+        hold what the last timed step wrote."""
         mdl.set_timing(True); mdl.reset_timing()
         for _ in range(2):
             fn()
@@ -265,6 +282,8 @@ def main():
         dt_ = time.perf_counter() - t0
         timed.local_dt = dt_                   # (this rank's own clock; the line's figure is the max over ranks)
         tm_dom = mdl.get_timing()
+        if after is not None:
+            after()
         extra = max(1, min(steps, 10))
         mdl.set_timing(True); mdl.reset_timing()
         for _ in range(extra):
@@ -283,9 +302,27 @@ def main():
             dt_ = float(t.item())
         return dt_, tm
 
-    dt, timing = timed(step, args.warmup, args.steps, model)
+    last = {}
+
+    def keep_last_step():
+        outs = zip(OUTPUT_NAMES, (d_h1, d_h2, d_prob, d_match, d_dos, d_pp))
+        last.update({k: t.cpu().numpy() for k, t in outs if t is not None})
+
+    dt, timing = timed(step, args.warmup, args.steps, model, after=keep_last_step if args.dump_outputs else None)
     dt_local = timed.local_dt
     faults = {"timed_model": int(model.handover_faults())}
+
+    if args.dump_outputs:
+        # the rows of the whole step: this rank's samples are rows first .. first + n of it (the classifier-sharded route
+        # merges onto every rank, so rank 0 holds them all)
+        first = lo if strong else (0 if by_classifier else rank * n)
+        part = dump_part(last, dump_rows(n_total, last), first)
+        parts = [part]
+        if world > 1 and not by_classifier:
+            parts = [None] * world
+            dist.all_gather_object(parts, part)
+        if rank == 0:
+            write_dump(args.dump_outputs, parts)
 
     # sanity on the timed outputs: calls of samples drawn from the model
     h1 = d_h1.cpu().numpy(); h2 = d_h2.cpu().numpy()
@@ -547,6 +584,68 @@ def issue_floor(obj, avg_ms, n, K, dev_model):
     floor = 2 * K["fp64_op_ns"] + mfma_ns / max(w, 1)
     achieved = N_SIMD * avg_ms * 1e6 / (w * n / 64.0)
     return floor, achieved
+
+
+def dump_rows(n, outs):
+    """The samples --dump-outputs keeps of a step over n samples whose outputs are `outs` (arrays with one row per sample,
+    for any one slice of them): None for all of them, or, when their float64 copies and sample_index.npy would exceed
+    DUMP_BYTES, the sorted indices of a fixed, seeded sample."""
+    import numpy as np
+    row_bytes = 8 * (1 + sum(int(np.prod(v.shape[1:])) for v in outs.values()))
+    if n * row_bytes <= DUMP_BYTES:
+        return None
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=DUMP_BYTES // row_bytes, replace=False))
+
+
+def dump_part(outs, rows, first):
+    """One process's share of a dump: of the step's samples first .. first + len(its outputs) `outs`, those in `rows`
+    (dump_rows of the whole step; None: all), with their indices in the step as sample_index."""
+    import numpy as np
+    n = len(next(iter(outs.values())))
+    sel = np.arange(n) if rows is None else rows[(rows >= first) & (rows < first + n)] - first
+    return dict({k: v[sel] for k, v in outs.items()}, sample_index=first + sel)
+
+
+def write_dump(path, parts):
+    """The dump of the shares `parts` (dump_part, in sample order) as DIR/<name>.npy in float64 (the int32 calls exactly).
+    Every value is written as computed but the NaN and inf a sample gets where its posterior sums underflow (as in the
+    reference: tests/test_hip_parity.py, test_underflow_gives_nan_like_the_reference): each is a row (sample row,
+    OUTPUT_NAMES index, column of the row-major [row, ...] array, 0 = NaN / 1 = +inf / 2 = -inf) of DIR/nonfinite.npy and
+    0 in its array, so that every file holds finite numbers and no sample or value is lost."""
+    import numpy as np
+    outs = {k: np.concatenate([p[k] for p in parts]).astype(np.float64) for k in parts[0]}
+    nonfinite = [np.zeros((0, 4))]
+    for j, k in enumerate(OUTPUT_NAMES):
+        if k not in outs or not outs[k].size:
+            continue
+        v = outs[k].reshape(len(outs[k]), -1)              # (a view: the copy astype made)
+        r, c = np.nonzero(~np.isfinite(v))
+        x = v[r, c]
+        nonfinite.append(np.stack([r, np.full(len(r), j), c, np.where(np.isnan(x), 0, np.where(x > 0, 1, 2))], axis=1))
+        v[r, c] = 0.0
+    outs["nonfinite"] = np.concatenate(nonfinite).astype(np.float64)
+    size = sum(v.nbytes + 128 for v in outs.values())
+    if size > DUMP_LIMIT:
+        raise RuntimeError(f"--dump-outputs: {len(outs['nonfinite'])} NaN / inf outputs take the dump to {size} bytes, "
+                           f"past {DUMP_LIMIT}")
+    os.makedirs(path, exist_ok=True)
+    for k, v in outs.items():
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(v))
+
+
+def read_dump(path):
+    """The arrays of a dump as the timed step computed them (float64, NaN and inf back in place), and sample_index."""
+    import numpy as np
+    d = {f[:-4]: np.load(os.path.join(path, f)) for f in os.listdir(path) if f.endswith(".npy")}
+    for r, j, c, kind in d.pop("nonfinite").astype(np.int64):
+        v = d[OUTPUT_NAMES[j]]
+        v.reshape(len(v), -1)[r, c] = (np.nan, np.inf, -np.inf)[kind]
+    return d
+
+
+def dump_outputs(path, outs):
+    """--dump-outputs for a process that holds the outputs of all the samples of the step."""
+    write_dump(path, [dump_part(outs, dump_rows(len(next(iter(outs.values()))), outs), 0)])
 
 
 def median_ms(fn, reps=12, warm=2):
@@ -1121,11 +1220,13 @@ def main_threads(args):
         grp = ShardGroup(first, devices)
         for _ in range(max(1, min(args.warmup, 2))):
             got = grp.predict_raw(geno, want_dosage=True)
-        steps = max(1, min(args.steps, 10))
+        steps = args.steps
         t0 = time.perf_counter()
         for _ in range(steps):
             got = grp.predict_raw(geno, want_dosage=True)
         dt = time.perf_counter() - t0
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {k: got[k] for k in OUTPUT_NAMES if got.get(k) is not None})
         ref = first.predict_raw(geno[:10_000], 1, want_dosage=False, want_prob=False)
         out = {
             "metric": "hlaPredict() samples/sec, 10k samples x 100-classifier HLA-B",
@@ -1160,7 +1261,7 @@ def main_threads(args):
     if strong:
         geno_all, truth_all = synth.make_samples(founders, afreq, n_total, seed=synth.DEFAULT_SEED + 1)
     bar = threading.Barrier(N)
-    times, accs, errs, sizes = [0.0] * N, [0.0] * N, [], [0] * N
+    times, accs, errs, sizes, lasts = [0.0] * N, [0.0] * N, [], [0] * N, [None] * N
 
     def worker(r):
         try:
@@ -1191,6 +1292,8 @@ def main_threads(args):
                 step()
             st.synchronize(); bar.wait(); st.synchronize()
             times[r] = time.perf_counter() - t0
+            if args.dump_outputs:
+                lasts[r] = {k: t.cpu().numpy() for k, t in zip(OUTPUT_NAMES, (h1, h2, pr, mt, ds))}
             if m.status() != 0:
                 raise RuntimeError("a launch reported a failed hand-over")
             accs[r] = float(np.mean((h1.cpu().numpy() == truth[:, 0]) & (h2.cpu().numpy() == truth[:, 1])))
@@ -1204,6 +1307,8 @@ def main_threads(args):
         t.join()
     if errs:
         sys.exit("bench.py --launcher threads: " + "; ".join(errs))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {k: np.concatenate([p[k] for p in lasts]) for k in lasts[0]})
     dt = max(times)
     total = sum(sizes)
     out = {

@@ -117,18 +117,21 @@ def test_a_failed_handover_on_one_shard_is_repaired_not_returned(hib):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("extra", [["--no-cpu-baseline"], ["--shard", "classifiers"]])
-def test_bench_two_rank_rehearsal_on_one_device(extra):
+def test_bench_two_rank_rehearsal_on_one_device(extra, tmp_path, oracle):
     """`python bench.py --gpus 2` end to end on a one-GPU box: bench.py starts its own two ranks (torch.distributed.run), both
     ranks share device 0 and the collectives go over gloo (HIBAG_BENCH_DRY_RANKS=1 -- RCCL refuses two ranks on one device).
     What is checked is the orchestration the driver's 8-GPU run goes through: slice bounds, the classifier-sharded merge
-    against the unsharded posterior, the one JSON line."""
+    against the unsharded posterior, the one JSON line -- and --dump-outputs: rank 0 writes every rank's share of the
+    100,000 samples, which must be the oracle's outputs across the boundary between the ranks' slices."""
     import json
     import os
     import subprocess
     import sys
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, HIBAG_BENCH_DRY_RANKS="1")
-    p = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1"] + extra,
+    dump = str(tmp_path / "dump")
+    p = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
+                        "--dump-outputs", dump] + extra,
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600, stdin=subprocess.DEVNULL)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -141,3 +144,19 @@ def test_bench_two_rank_rehearsal_on_one_device(extra):
     assert chk["calls_identical_to_unsharded"] and chk["nan_pattern_identical"]
     assert chk["max_rel_dev_posterior_vs_unsharded"] < chk["tolerance"]
     assert all(v == 0 for v in d["handover_faults"].values())
+    import bench
+    from hibag_amd import synth
+    got = bench.read_dump(dump)
+    assert np.array_equal(got.pop("sample_index"), np.arange(100_000))
+    model, founders, af = synth.make_model(bench.SHAPE)
+    geno, _ = synth.make_samples(founders, af, 100_000, seed=synth.DEFAULT_SEED + 1)
+    rows = np.r_[0:500, 49_000:51_000, 99_500:100_000]
+    want = oracle.predict(oracle.flatten(model), geno[rows], vote_method=1, avx2=True, n_threads=8)
+    for k, v in got.items():
+        w = np.asarray(want[k], np.float64)
+        if "--shard" in extra and k not in ("h1", "h2"):      # (the merged partial sums: rounding-level differences)
+            assert np.array_equal(np.isnan(v[rows]), np.isnan(w)), k
+            fin = np.isfinite(w) & (np.abs(w) > 1e-200)
+            np.testing.assert_allclose(v[rows][fin], w[fin], rtol=chk["tolerance"], atol=0, err_msg=k)
+        else:
+            assert np.array_equal(v[rows], w, equal_nan=True), k
