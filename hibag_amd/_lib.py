@@ -39,7 +39,7 @@ EXPORTS = [
     "hibag_hip_shard_bounds", "hibag_hip_model_shard", "hibag_hip_model_batch_limit", "hibag_hip_shard_group_new",
     "hibag_hip_shard_group_free", "hibag_hip_shard_group_ranks", "hibag_hip_shard_group_allreduces", "hibag_hip_rccl_version",
     "hibag_hip_shard_group_predict", "hibag_hip_predict_multi_sharded", "hibag_hip_measure_issue_costs",
-    "hibag_hip_test_time_avg_prob", "hibag_hip_test_read_diag", "hibag_hip_plugin_degraded_calls",
+    "hibag_hip_test_time_avg_prob", "hibag_hip_test_read_diag", "hibag_hip_plugin_degraded_calls", "hibag_hip_predict_oob",
 ]
 
 
@@ -94,6 +94,7 @@ def lib() -> C.CDLL:
     L.hibag_hip_model_second_pass_pairs.restype = i64
     L.hibag_hip_model_mutation_table.argtypes = [vp, vp]
     L.hibag_hip_predict.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp]
+    L.hibag_hip_predict_oob.argtypes = [vp, vp, i32, vp, vp, vp, vp]
     L.hibag_hip_predict_device.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]
     L.hibag_hip_predict_partial_device.argtypes = [vp, vp, i32, vp, vp]
     L.hibag_hip_finish_device.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]

@@ -205,6 +205,11 @@ struct hibag_hip_model {
 	bool staged_ready = false;
 	// PLINK BED payload + SNP map of hibag_hip_predict_bed
 	DevBuf ws_bed, ws_bedidx;
+	// hibag_hip_predict_oob: the plain haplotype table its rescan reads (built at the first call) -- bits, frequencies,
+	// per-classifier offsets and allele starts, at the byte offsets below
+	DevBuf oob_hap;
+	size_t oob_freq_at = 0, oob_off_at = 0, oob_start_at = 0;
+	bool oob_hap_ready = false;
 	DevBuf ws_thrash;                      // HIBAG_DEBUG_THRASH_MB (hibag_predict.hip run_core): scratch a measurement overwrites between the passes
 
 	KernelTimer timer;
@@ -224,7 +229,7 @@ struct hibag_hip_model {
 		if (side.join) (void)hipEventDestroy(side.join);
 		if (side.stream) (void)hipStreamDestroy(side.stream);
 		for (DevBuf *b : {&d_int, &d_stream, &d_tile, &d_tab, &d_blk, &d_pfac, &d_phdr, &d_parow, &ws_bt, &ws_bias, &ws_cells, &ws_sync, &ws_err, &ws_planes, &ws_cw, &ws_tot, &ws_inv, &ws_winv,
-		                  &ws_part, &ws_best, &ws_vrec, &ws_geno, &ws_out, &ws_codes, &ws_bed, &ws_bedidx, &ws_thrash})
+		                  &ws_part, &ws_best, &ws_vrec, &ws_geno, &ws_out, &ws_codes, &ws_bed, &ws_bedidx, &ws_thrash, &oob_hap})
 			b->release();
 	}
 };

@@ -33,5 +33,21 @@ void hibag_launch_scalars(const HibagModelView &M, const HibagBatchView &B, cons
 void hibag_launch_finish(const HibagModelView &M, const HibagBatchView &B, double *d_part,
 	int32_t *d_H1, int32_t *d_H2, double *d_max_prob, double *d_matching,
 	double *d_dosage, double *d_postprob, hipStream_t st);
+// hlaOutOfBag (hibag_k_oob.h): each classifier predicts its own out-of-bag samples.  The per-classifier arrays are
+// [C][ld] with the batch's sample 0 at column 0 (the caller offsets the pointers); the plain haplotype table (grouped by
+// allele, hla_start[c][n_hla + 1] relative to hap_off[c]) serves the rare lane whose record log cannot settle its call.
+struct HibagOobOut {
+	const int32_t *samp_num;           // bootstrap counts: 0 = out of bag
+	int32_t *h1, *h2;                  // 0-based alleles or NA_integer_
+	double *prob;
+	size_t ld;
+	const uint64_t *hap_bits;          // [H][2]
+	const double *hap_freq;            // [H]
+	const int *hap_off;                // [C]
+	const int *hla_start;              // [C][n_hla + 1]
+};
+// after a pack of the batch: the one-classifier weights, pass 1 with its record log, the picks -- no second pass, no finish
+void hibag_launch_oob(const HibagModelView &M, const HibagBatchView &B, const uint8_t *d_codes, const HibagOobOut &O,
+	int force_rescan, const HibagSideStream &side, hipStream_t st);
 
 #endif

@@ -89,6 +89,7 @@ static_assert(2 * HIBAG_FP4_MAX_SNPS + 1 <= ACCUM_TAB_N, "pass 2's table must co
 #include "hibag_k_pass2.h"
 #include "hibag_k_vote.h"
 #include "hibag_k_finish.h"
+#include "hibag_k_oob.h"
 
 // ---------------------------------------------------------------------------
 // launchers (host side, no synchronisation, no allocation)
@@ -313,4 +314,18 @@ void hibag_launch_finish(const HibagModelView &M, const HibagBatchView &B, doubl
 	if (d_postprob)
 		hipLaunchKernelGGL(k_finish_prob, dim3(B.n_pad / 64, (M.n_cell + 63) / 64), dim3(256), 0, st,
 			M, B, (const double *)d_part, d_postprob);
+}
+
+void hibag_launch_oob(const HibagModelView &M, const HibagBatchView &B, const uint8_t *d_codes, const HibagOobOut &O,
+	int force_rescan, const HibagSideStream &side, hipStream_t st)
+{
+	if (M.n_classifier == 0) return;
+	hipLaunchKernelGGL(k_oob_weight, dim3(B.n_pad / 64, M.n_classifier), dim3(64), 0, st, M, B, d_codes, O);
+	hibag_launch_total(M, B, st, side, true);
+	hipLaunchKernelGGL(k_oob_pick, dim3(B.n_pad / 64, M.n_classifier), dim3(64), 0, st, M, B, d_codes, O, force_rescan);
+	if (M.n_wide > 0) hipLaunchKernelGGL(k_oob_scan, dim3(B.n_pad / 64, M.n_wide), dim3(64), 0, st, M, B, O);
+	if (M.n_valu > 0) {
+		const unsigned gx = (unsigned)((B.n_pad / HIBAG_WAVE + BLOCK_WAVES - 1) / BLOCK_WAVES);
+		hipLaunchKernelGGL(k_oob_best_valu, dim3(gx, M.n_classifier), dim3(BLOCK_THREADS), 0, st, M, B, O);
+	}
 }

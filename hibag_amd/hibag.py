@@ -208,6 +208,24 @@ class HlaAttrBagClass:
             _as_ptr(out["prob"]), _as_ptr(out["matching"]), _as_ptr(out.get("dosage")), _as_ptr(out.get("postprob"))))
         return out
 
+    def predict_oob(self, genomat: np.ndarray, samp_num) -> dict:
+        """``hlaOutOfBag``'s per-classifier predictions (``R/HIBAG.R:1320-1334``) in one batched call
+        (``hibag_hip_predict_oob``): classifier c, as a one-classifier model of its own, predicts every sample s with
+        ``samp_num[c, s] == 0``.  ``genomat`` int32 [n_samp, n_snp] holds the model's training samples in
+        ``sample_id`` order, ``samp_num`` [n_classifier, n_samp] their bootstrap counts.  Returns ``h1``, ``h2``
+        (0-based, NA = INT_MIN where not predicted) and ``prob`` (0 there), each [n_classifier, n_samp]."""
+        g = np.ascontiguousarray(genomat, np.int32)
+        if g.ndim != 2 or g.shape[1] != self.obj.n_snp:
+            raise ValueError("genomat must be [n_samp, n.snp] int32")
+        n, nc = g.shape[0], len(self.obj.classifiers)
+        sn = np.ascontiguousarray(samp_num, np.int32)
+        if sn.shape != (nc, n):
+            raise ValueError(f"samp_num must be [n_classifier, n_samp] = [{nc}, {n}]")
+        out = {"h1": np.empty((nc, n), np.int32), "h2": np.empty((nc, n), np.int32), "prob": np.empty((nc, n), np.float64)}
+        _lib.check(_lib.lib().hibag_hip_predict_oob(self.handle, _as_ptr(g), n, _as_ptr(sn), _as_ptr(out["h1"]),
+                                                    _as_ptr(out["h2"]), _as_ptr(out["prob"])))
+        return out
+
     def predict_bed(self, bed_fn: str, n_samp: int, n_snp: int, snp_col: np.ndarray, flip: Optional[np.ndarray] = None,
                     vote_method: int = 1, want_dosage: bool = True, want_prob: bool = False) -> dict:
         """``PredictHLA`` on every sample of a PLINK BED file (``hibag_hip_predict_bed``):

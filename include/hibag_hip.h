@@ -23,7 +23,8 @@ extern "C" {
 
 #define HIBAG_HIP_ABI_VERSION 7   /* 2: + PLINK BED entries, training driver; 3: + hibag_hip_predict_mapped[_device]; 4: + hibag_hip_model_stored_cells;
                                      5: + hibag_hip_model_status / _clear_status, hibag_hip_predict_multi, hibag_hip_model_replicate, hibag_hip_model_engine;
-                                     7: + hibag_hip_predict_snp_major[_device], hibag_hip_trainer_set_shared, hibag_hip_train_set_thread_budget */
+                                     7: + hibag_hip_predict_snp_major[_device], hibag_hip_trainer_set_shared, hibag_hip_train_set_thread_budget;
+                                        later, additive (no bump): + hibag_hip_predict_oob */
 
 /* error codes */
 #define HIBAG_HIP_OK          0
@@ -131,6 +132,17 @@ int hibag_hip_model_mutation_table(const hibag_hip_model *m, double *out);
 int hibag_hip_predict(hibag_hip_model *m, const int32_t *geno, int n_samp,
 	int vote_method, int32_t *H1, int32_t *H2, double *max_prob,
 	double *matching, double *dosage, double *postprob);
+
+/* hlaOutOfBag's per-classifier predictions (R/HIBAG.R:1320-1334): classifier c of the model, taken as a
+ * one-classifier model of its own, predicts every sample s with samp_num[c][s] == 0 -- bit-identical to
+ * hlaPredict(vote = "prob") of that one-classifier model (src/LibHLA.cpp:2317-2482): SNP weights all 1, the
+ * call the first strict maximum of (0 + p * w) * (1 / w) in pair order, that value the probability.
+ *   geno      int32 [n_samp][n_snp], the model's training samples in model$sample.id order
+ *   samp_num  int32 [n_classifier][n_samp], the bootstrap counts of each classifier
+ * Outputs [n_classifier][n_samp]: H1, H2 (0-based, NA_integer_ where not predicted), prob (0 there).
+ * All pointers are host memory and required when n_samp > 0; one batched launch sequence, no second pass. */
+int hibag_hip_predict_oob(hibag_hip_model *m, const int32_t *geno, int n_samp, const int32_t *samp_num,
+	int32_t *H1, int32_t *H2, double *prob);
 
 /* Device-pointer form of the same call: every pointer is device memory on the
  * model's device, work is enqueued on `stream` (a hipStream_t, NULL = default
