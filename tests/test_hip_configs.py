@@ -13,6 +13,7 @@ cfg5  "hlaAttrBagging() training, 1k samples x 300 SNPs": the device-scored driv
 import numpy as np
 import pytest
 
+import oracle_full as OF
 from test_oracle_train import assert_same_classifier
 
 pytestmark = pytest.mark.gpu
@@ -41,12 +42,8 @@ def test_cfg3_100k_samples_eight_classifier_shards(hib, oracle):
     assert np.mean((full["h1"][ok] == truth[ok, 0]) & (full["h2"][ok] == truth[ok, 1])) > 0.9
     assert full["h1"][7] == hib.NA_INTEGER and full["prob"][7] == 0.0
 
-    # a 200-sample subset against the CPU oracle: every output bit-identical
-    rng = np.random.default_rng(3)
-    sub = np.sort(np.concatenate([[0, 7, n - 1], rng.choice(n, 197, replace=False)]))
-    want = oracle.predict(oracle.flatten(model), G[sub], vote_method=1)
-    for k in ("h1", "h2", "prob", "matching", "dosage", "postprob"):
-        assert np.array_equal(full[k][sub], want[k], equal_nan=True), k
+    # every sample against the CPU oracle, 25,000 at a time: every output bit-identical
+    OF.assert_same_sliced(full, model, G, vote=1)
 
     # eight classifier shards (13,13,13,13,12,12,12,12 classifiers) on the same samples; the partial entry
     # takes one batch at a time, so the cohort goes through in slices
@@ -126,29 +123,21 @@ def test_device_entry_on_a_stream_of_the_callers(hib, oracle):
     assert m.status() == 0 and m.handover_faults() == 0
     flat = oracle.flatten(model)
     for G, (dg, h1, h2, pr, mt, ds) in zip(genos, outs):
-        sub = np.arange(0, n, 25)
-        want = oracle.predict(flat, G[sub], vote_method=1, want_prob=False, avx2=True, n_threads=8)
-        assert np.array_equal(h1.cpu().numpy()[sub], want["h1"]) and np.array_equal(h2.cpu().numpy()[sub], want["h2"])
-        assert np.array_equal(pr.cpu().numpy()[sub], want["prob"], equal_nan=True)
-        assert np.array_equal(mt.cpu().numpy()[sub], want["matching"], equal_nan=True)
-        assert np.array_equal(ds.cpu().numpy()[sub], want["dosage"], equal_nan=True)
+        want = oracle.predict(flat, G, vote_method=1, want_prob=False, avx2=True, n_threads=OF.THREADS)
+        got = dict(h1=h1.cpu().numpy(), h2=h2.cpu().numpy(), prob=pr.cpu().numpy(), matching=mt.cpu().numpy(), dosage=ds.cpu().numpy())
+        OF.assert_same(got, want, ("h1", "h2", "prob", "matching", "dosage"))
     m.close()
 
 
 def test_cfg4_hla_drb1_full_model_against_oracle(hib, oracle):
     """The DRB1 shape at full size: 100 classifiers x 500 haplotypes (12.5 M haplotype pairs per sample)."""
-    from hibag_amd import synth
-    model, founders, af = synth.make_model("hla-drb1")
-    G, truth = synth.make_samples(founders, af, 2048)
+    model, G, truth = OF.cohort("hla-drb1", 2048)
     m = hib.hlaModelFromObj(model)
     assert m.stored_cells() > 0 and m.second_pass_pairs() == 0   # 73 pairs per cell: pass 1 stores every cell sum, pass 2 reads them back
     got = m.predict_raw(G, 1, want_dosage=True, want_prob=True)
     m.close()
     assert np.mean((got["h1"] == truth[:, 0]) & (got["h2"] == truth[:, 1])) > 0.9
-    sub = np.arange(0, 2048, 86)[:24]                      # the oracle needs ~0.1 s per sample at this size
-    want = oracle.predict(oracle.flatten(model), G[sub], vote_method=1, avx2=True, n_threads=8)
-    for k in ("h1", "h2", "prob", "matching", "dosage", "postprob"):
-        assert np.array_equal(got[k][sub], want[k], equal_nan=True), k
+    OF.assert_same(got, OF.want("hla-drb1", 2048, vote=1))
 
 
 def test_cfg5_training_1k_samples_300_snps(hib, oracle):
@@ -184,30 +173,41 @@ def test_large_model_1500_haplotypes_per_classifier(hib, oracle):
     got = m.predict_raw(G, 1, want_dosage=True, want_prob=True)
     m.close()
     assert np.mean((got["h1"] == truth[:, 0]) & (got["h2"] == truth[:, 1])) > 0.9
-    sub = np.array([0, 1, 63, 64, 100, 191])
-    want = oracle.predict(oracle.flatten(model), G[sub], vote_method=1, avx2=True, n_threads=8)
-    for k in ("h1", "h2", "prob", "matching", "dosage", "postprob"):
-        assert np.array_equal(got[k][sub], want[k], equal_nan=True), k
+    OF.assert_same(got, oracle.predict(oracle.flatten(model), G, vote_method=1, avx2=True, n_threads=OF.THREADS))
+
+
+def _cfg4_at_4096_against_oracle(hib, recipe):
+    """Every sample of cohort("hla-drb1", 4096, recipe) against the oracle, both votes."""
+    n = 4096
+    model, G, truth = OF.cohort("hla-drb1", n, recipe=recipe)
+    m = hib.hlaModelFromObj(model)
+    assert m.stored_cells() > 0 and m.second_pass_pairs() == 0
+    if recipe:
+        assert all(m.engine(c)[1] == 1 and m.engine(c)[0] != "valu" for c in OF._tail_one_step(model))
+    for vote in (1, 2):
+        got = m.predict_raw(G, vote, want_dosage=True, want_prob=True)
+        assert m.handover_faults() == 0
+        if not recipe:
+            assert np.mean((got["h1"] == truth[:, 0]) & (got["h2"] == truth[:, 1])) > 0.9
+        else:
+            assert got["h1"][n - 1] == hib.NA_INTEGER
+        OF.assert_same(got, OF.want("hla-drb1", n, vote=vote, recipe=recipe), what=f"vote {vote}")
+    m.close()
 
 
 def test_cfg4_at_the_benchmarks_size_chunked_items_against_oracle(hib, oracle):
     """The DRB1 shape at the 4,096 samples bench.py times: 1,600 pass-1 items on 1,280 resident workgroups, so the last
     rounds run as chunks (12 per item) that resume at HibagModelView::blk_close rows with every cell stored -- the split of
-    the loop at src/LibHLA.cpp:1776-1829.  (The 2,048-sample test above has 800 items: no chunks.)"""
-    from hibag_amd import synth
-    model, founders, af = synth.make_model("hla-drb1")
-    n = 4096
-    G, truth = synth.make_samples(founders, af, n)
-    m = hib.hlaModelFromObj(model)
-    assert m.stored_cells() > 0 and m.second_pass_pairs() == 0
-    got = m.predict_raw(G, 1, want_dosage=True, want_prob=True)
-    assert m.handover_faults() == 0
-    m.close()
-    assert np.mean((got["h1"] == truth[:, 0]) & (got["h2"] == truth[:, 1])) > 0.9
-    sub = np.concatenate([np.arange(0, n, 171)[:22], [n - 65, n - 1]])     # 24 samples, the last sample groups included
-    want = oracle.predict(oracle.flatten(model), G[sub], vote_method=1, avx2=True, n_threads=8)
-    for k in ("h1", "h2", "prob", "matching", "dosage", "postprob"):
-        assert np.array_equal(got[k][sub], want[k], equal_nan=True), k
+    the loop at src/LibHLA.cpp:1776-1829.  (The 2,048-sample test above has 800 items: no chunks.)  Every sample, both
+    votes."""
+    _cfg4_at_4096_against_oracle(hib, "")
+
+
+def test_cfg4_at_the_benchmarks_size_structured_missingness_against_oracle(hib, oracle):
+    """The cohort above with structured missingness (oracle_full._structured): a 64-sample group near the end without any
+    SNP of the ten classifiers whose items run last, chunked; groups with weights that are not powers of two; an all-NA
+    last sample.  Every sample, both votes."""
+    _cfg4_at_4096_against_oracle(hib, "structured")
 
 
 @pytest.mark.parametrize("n", [700, 10_000])
@@ -216,24 +216,18 @@ def test_generated_rows_and_prebuilt_rows_give_the_same_bits(hib, oracle, monkey
     small enough, the default for every shape of the suite) and generated from the O(H) haplotype table (larger models,
     HIBAG_PREBUILT_MB=0 here).  Both vote methods (the vote has builds of its own) at a batch of one round -- the general
     build, five workgroups per CU -- and of several -- the FP4-only builds at six, with chunked items: bit-equal to each
-    other and, on a subset, to the oracle."""
-    from hibag_amd import synth
-    model, founders, af = synth.make_model("hla-b")
-    G, _ = synth.make_samples(founders, af, n, seed=77)
-    G[5, :] = hib.NA_INTEGER
+    other and, on every sample, to the oracle."""
+    model, G, _ = OF.cohort("hla-b", n, seed=77, recipe="na5")
     pre = hib.hlaModelFromObj(model)
     monkeypatch.setenv("HIBAG_PREBUILT_MB", "0")
     gen = hib.hlaModelFromObj(model)
     monkeypatch.delenv("HIBAG_PREBUILT_MB")
-    sub = np.arange(0, n, max(1, n // 30))[:30]
     for vote in (1, 2):
         a = pre.predict_raw(G, vote, want_dosage=True, want_prob=True)
         b = gen.predict_raw(G, vote, want_dosage=True, want_prob=True)
         for k in ("h1", "h2", "prob", "matching", "dosage", "postprob"):
             assert np.array_equal(a[k], b[k], equal_nan=True), (vote, k)
-        want = oracle.predict(oracle.flatten(model), G[sub], vote_method=vote, avx2=True, n_threads=8)
-        for k in ("h1", "h2", "prob", "matching", "dosage", "postprob"):
-            assert np.array_equal(b[k][sub], want[k], equal_nan=True), (vote, k)
+        OF.assert_same(b, OF.want("hla-b", n, vote=vote, seed=77, recipe="na5"), what=f"vote {vote}")
     assert pre.handover_faults() == 0 and gen.handover_faults() == 0
     pre.close(); gen.close()
 
@@ -244,20 +238,16 @@ import numpy as np
 sys.path.insert(0, os.environ["HIBAG_REPO"])
 import hibag_amd as hib
 from hibag_amd import synth
-from oracle import oracle as O
-O.build()
 hib.hlaSetKernelTarget("hip")
-shape, n = sys.argv[1], int(sys.argv[2])
+shape, n, out = sys.argv[1], int(sys.argv[2]), sys.argv[3]
 model, founders, af = synth.make_model(shape)
 G, _ = synth.make_samples(founders, af, n)
 m = hib.hlaModelFromObj(model)
 got = m.predict_raw(G, 1, want_dosage=True, want_prob=True)
 faults = m.handover_faults()
 m.close()
-sub = np.arange(0, n, max(1, n // 40))[:40]
-want = O.predict(O.flatten(model), G[sub], vote_method=1, avx2=True, n_threads=8)
-bad = [k for k in ("h1", "h2", "prob", "matching", "dosage", "postprob") if not np.array_equal(got[k][sub], want[k], equal_nan=True)]
-print(json.dumps({"bad": bad, "faults": int(faults)}))
+np.savez(out, **got)
+print(json.dumps({"faults": int(faults)}))
 """
 
 
@@ -265,17 +255,20 @@ print(json.dumps({"bad": bad, "faults": int(faults)}))
 def test_cfg2_every_number_of_chunks_per_item_equals_the_oracle(tail_k, tmp_path):
     """HIBAG_TAIL_K = chunks per work item of the last rounds of both passes (read once per process, hence a child
     process per value): 1 = undivided items, 2 / 8 / 12 around the default of 4.  The benchmark configuration
-    (10,000 samples, HLA-B shape), 40 samples against the oracle, every output bit for bit."""
+    (10,000 samples, HLA-B shape): the child writes its outputs, every sample is compared with one cached oracle result,
+    every output bit for bit."""
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     script = tmp_path / "tail_k.py"
     script.write_text(_TAIL_K_SCRIPT)
     env = dict(os.environ, HIBAG_TAIL_K=str(tail_k), HIBAG_REPO=root)
-    p = subprocess.run([sys.executable, str(script), "hla-b", "10000"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
-                       text=True, timeout=900)
+    out = tmp_path / "out.npz"
+    p = subprocess.run([sys.executable, str(script), "hla-b", "10000", str(out)], env=env, stdout=subprocess.PIPE,
+                       stderr=subprocess.PIPE, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
-    res = json.loads(p.stdout.strip().splitlines()[-1])
-    assert res == {"bad": [], "faults": 0}
+    assert json.loads(p.stdout.strip().splitlines()[-1]) == {"faults": 0}
+    with np.load(out) as got:
+        OF.assert_same(dict(got), OF.want("hla-b", 10_000, vote=1), what=f"HIBAG_TAIL_K={tail_k}")
 
 
 def test_predict_multi_two_replicas_on_one_device_equal_the_single_call(hib, oracle):
@@ -338,12 +331,9 @@ def test_haplotype_count_at_the_matrix_engines_index_limit(hib, oracle, n_haplo)
     m = hib.hlaModelFromObj(model)
     kind = m.engine(1)
     assert (kind[0] == "valu") == (n_haplo >= 16384), kind
-    sub = np.array([0, 1, 2, 63, 64, 69])
     flat = oracle.flatten(model)
     for vote in (1, 2):
         got = m.predict_raw(G, vote, want_dosage=True, want_prob=True)
-        want = oracle.predict(flat, G[sub], vote_method=vote, avx2=True, n_threads=8)
-        for key in ("h1", "h2", "prob", "matching", "dosage", "postprob"):
-            assert np.array_equal(got[key][sub], want[key], equal_nan=True), (vote, key)
+        OF.assert_same(got, oracle.predict(flat, G, vote_method=vote, avx2=True, n_threads=OF.THREADS), what=f"vote {vote}")
     assert m.handover_faults() == 0
     m.close()

@@ -279,9 +279,22 @@ def test_entry_points_campaign(monkeypatch, tmp_path):
             grp.close()
             # identical calls -- except where the two best cells of a sample tie to within rounding: the shards add the
             # classifiers' terms in another order, and a call is the FIRST strict maximum (seed 950299: two cells one ulp apart
-            # in the one-model sums, equal in the shards'; tools/fuzz_repro_shards.py).  There the calls' probabilities must agree.
-            differ = (got["h1"] != want1["h1"]) | (got["h2"] != want1["h2"])
-            ok = bool(np.all(np.abs(got["prob"][differ] - want1["prob"][differ]) <= 1e-12 * np.abs(want1["prob"][differ])))
+            # in the one-model sums, equal in the shards'; tools/fuzz_repro_shards.py).  There both calls' cells lie within
+            # 4 ulps of each other in the one-model posterior, the shards' call is the first maximum of the shards' posterior,
+            # and such samples are rare: at most one per 10,000 (at least one allowed).
+            differ = np.flatnonzero((got["h1"] != want1["h1"]) | (got["h2"] != want1["h2"]))
+            ok = len(differ) <= max(1, n // 10_000)
+            for i in differ:
+                g1, g2, w1, w2 = (int(x) for x in (got["h1"][i], got["h2"][i], want1["h1"][i], want1["h2"][i]))
+                if min(g1, g2, w1, w2) < 0:                   # one side made no call (NA_integer_): not a near-tie
+                    ok = False
+                    break
+                nh = model.n_hla
+                pg, pw = g1 * nh - g1 * (g1 - 1) // 2 + g2 - g1, w1 * nh - w1 * (w1 - 1) // 2 + w2 - w1
+                a, b = want1["postprob"][i, [pg, pw]]
+                ok = ok and bool(np.isfinite(a) and np.isfinite(b) and a > 0 and b > 0)
+                ok = ok and abs(int(np.float64(a).view(np.int64)) - int(np.float64(b).view(np.int64))) <= 4
+                ok = ok and int(np.argmax(got["postprob"][i])) == pg
             with np.errstate(invalid="ignore", divide="ignore"):
                 fin = np.isfinite(want1["postprob"]) & (want1["postprob"] > 1e-200)
                 rel = np.abs(got["postprob"] - want1["postprob"])[fin] / want1["postprob"][fin]

@@ -9,7 +9,8 @@ import pytest
 import hibag_amd as hb
 from conftest import align_geno
 from hibag_amd import NA_INTEGER, synth
-from test_oob_host import oracle_oob
+from oracle_full import cohort, want_oob
+from test_oob_host import TIE_RING_START, TIE_VARIANTS, oracle_oob, tie_calls, tie_case
 
 pytestmark = pytest.mark.gpu
 
@@ -30,6 +31,13 @@ def _gpu_loop(model, G):
         for k in ("h1", "h2", "prob"):
             out[k][c, oob] = r[k]
     return out
+
+
+def _differ(a, b):
+    """[(classifier, sample)] where a and b differ (NaN == NaN)."""
+    a, b = np.asarray(a), np.asarray(b)
+    same = (a == b) | (np.isnan(a) & np.isnan(b)) if a.dtype.kind == "f" else a == b
+    return np.argwhere(~same)
 
 
 def _samp_num(model):
@@ -85,6 +93,54 @@ def test_predict_oob_matches_the_oracle_loop(which, oracle, model_oob, model_a, 
     monkeypatch.setenv("HIBAG_OOB_RESCAN", "1")
     assert _same(dev.predict_oob(G, _samp_num(model)), want)
     dev.close()
+
+
+@pytest.mark.parametrize("shape,n,env", [("hla-b", 10_000, {}), ("hla-b", 10_000, {"HIBAG_OOB_BATCH": "4032"}),
+                                         ("hla-b", 10_000, {"HIBAG_OOB_RESCAN": "1"}), ("hla-drb1", 4096, {})])
+def test_predict_oob_at_size_equals_the_oracle_loop(shape, n, env, monkeypatch):
+    """The benchmark's cohorts with seeded bootstrap counts: every (classifier, sample) bit-equal to the oracle's loop.
+    HIBAG_OOB_BATCH=4032: three batches (4,032 + 4,032 + 1,936 samples), the last ending inside a 64-sample group;
+    HIBAG_OOB_RESCAN=1: every lane by the full walk.  At the DRB1 shape pass 1 stores every cell sum and runs its last rounds as chunks."""
+    model, G, _ = cohort(shape, n)
+    samp_num, want = want_oob(shape, n, boot_seed=n + 1)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    dev = hb.hlaModelFromObj(model)
+    if shape == "hla-drb1":
+        assert dev.stored_cells() > 0
+    got = dev.predict_oob(G, samp_num)
+    assert dev.handover_faults() == 0 and dev.status() == 0
+    dev.close()
+    assert np.count_nonzero(got["h1"] != NA_INTEGER) > 0.3 * samp_num.size
+    for k in ("h1", "h2", "prob"):
+        bad = _differ(got[k], want[k])
+        assert len(bad) == 0, (k, len(bad), "(classifier, sample, group):", [(int(c), int(s), int(s) // 64) for c, s in bad[:8]])
+
+
+@pytest.mark.parametrize("snp_counts,seed,engine", [((10, 20, 27), 1, "fp4-1"), ((40, 84), 2, "fp4-k"), ((113, 120), 3, "valu")])
+def test_t_ties(snp_counts, seed, engine, oracle):
+    """Calls decided by a T-tie (tests/test_oob_host.py: the earlier of two cells that T merges wins) on each engine's
+    pick: k_oob_pick from the record log (one-step FP4; ties in slot 1, in the ring after more than seven records, and
+    between ring entries), k_oob_scan (several K steps), k_oob_best_valu.  predict_oob and hlaPredict of the
+    one-classifier models equal the oracle."""
+    model, G, samp_num, kind = tie_case(snp_counts, seed)
+    dev = hb.hlaModelFromObj(model)
+    for c in range(len(model.classifiers)):
+        e, k = dev.engine(c)
+        assert {"fp4-1": e == "fp4" and k == 1, "fp4-k": e == "fp4" and k > 1, "valu": e == "valu"}[engine], (c, e, k)
+    want = oracle_oob(oracle, model, G)
+    tie, called = tie_calls(oracle, model, G, want)       # the cases are ties: the oracle's call is not the raw first maximum
+    kind = np.array(kind)
+    for v in TIE_VARIANTS:
+        assert tie[kind == v].sum() >= 5, v
+    assert (tie[kind == "ring"] & (called[kind == "ring"] >= TIE_RING_START)).sum() >= 5
+    assert (tie[kind == "first"] & (called[kind == "first"] == 0)).sum() >= 5
+    got = dev.predict_oob(G, samp_num)
+    dev.close()
+    for k in ("h1", "h2", "prob"):
+        bad = _differ(got[k], want[k])
+        assert len(bad) == 0, (k, len(bad), [(int(c), int(s), kind[c], bool(tie[c, s])) for c, s in bad[:8]])
+    assert _same(_gpu_loop(model, G), want)
 
 
 def _average(model, hla, G, thr):

@@ -296,10 +296,9 @@ def test_plugin_table_per_sample_path(hib, oracle, hapmap_geno, model_a):
 # --- BASELINE config 2 at full size: properties that do not need the oracle ------------
 
 def test_full_size_hla_b_properties(hib, oracle):
-    from hibag_amd import synth
-    model, founders, af = synth.make_model("hla-b")
+    import oracle_full as OF
     N = 10_000
-    G, truth = synth.make_samples(founders, af, N)
+    model, G, truth = OF.cohort("hla-b", N)
     dev = hib.hlaModelFromObj(model)
     out = dev.predict_raw(G, 1, want_dosage=True, want_prob=True)
     # (a classifier whose total underflows turns cells into inf/NaN like the reference; keep finite rows)
@@ -324,10 +323,8 @@ def test_full_size_hla_b_properties(hib, oracle):
     assert np.array_equal(part["postprob"], out["postprob"][1234:1301], equal_nan=True)
     # samples drawn from the model are called correctly almost always
     assert np.mean((out["h1"] == truth[:, 0]) & (out["h2"] == truth[:, 1])) > 0.97
-    # and a random subset agrees with the oracle to the last bit
-    sub = np.sort(np.random.default_rng(5).choice(N, 160, replace=False))
-    want = oracle.predict(oracle.flatten(model), G[sub], avx2=True, n_threads=8)
-    assert_same({k: v[sub] for k, v in out.items()}, want)
+    # and every sample agrees with the oracle to the last bit
+    OF.assert_same(out, OF.want("hla-b", N, vote=1))
 
 
 def test_both_engines_give_the_same_bits(hib, oracle, monkeypatch):
@@ -389,20 +386,18 @@ def test_all_forms_of_pass_two(hib, oracle, monkeypatch, mode):
 def test_more_samples_than_one_batch(hib, oracle):
     """The driver cuts the cohort into batches (<= 131,072 samples); results must not depend on
     where the cuts fall."""
+    import oracle_full as OF
     from hibag_amd import synth
     model, founders, af = synth.make_model("hla-a-small", n_classifier=8)
     N = 140_000
     G, _ = synth.make_samples(founders, af, N)
     dev = hib.hlaModelFromObj(model)
-    out = dev.predict_raw(G, 1, want_dosage=True, want_prob=False)
+    out = dev.predict_raw(G, 1, want_dosage=True, want_prob=True)
     lo, hi = 131_072 - 100, 131_072 + 100            # straddles the batch boundary
     part = dev.predict_raw(G[lo:hi], 1, want_dosage=True, want_prob=False)
     for k in part:
         assert np.array_equal(part[k], out[k][lo:hi], equal_nan=True), k
-    sub = np.sort(np.random.default_rng(11).choice(N, 200, replace=False))
-    want = oracle.predict(oracle.flatten(model), G[sub], want_prob=False, avx2=True, n_threads=8)
-    for k in want:
-        assert np.array_equal(out[k][sub], want[k], equal_nan=True), k
+    OF.assert_same_sliced(out, model, G, vote=1)                # every sample, 25,000 at a time
 
 
 @pytest.mark.parametrize("seed", range(24))

@@ -95,8 +95,9 @@ def test_full_false_is_the_overall_of_full_true(thr):
 
 # ---- the reference's loop (R/HIBAG.R:1320-1334) on the oracle ---------------------------------------------------------
 
-def oracle_oob(oracle, model, G):
-    """Classifier by classifier: a one-classifier model predicts its OOB samples (vote "prob").  [C, n] arrays."""
+def oracle_oob(oracle, model, G, avx2=False, n_threads=1):
+    """Classifier by classifier: a one-classifier model predicts its OOB samples (vote "prob").  [C, n] arrays.
+    `avx2` / `n_threads`: the oracle's AVX2 port (pinned equal to the scalar restatement), for cohorts at size."""
     C, n = len(model.classifiers), G.shape[0]
     h1 = np.full((C, n), NA_INTEGER, np.int32)
     h2 = np.full((C, n), NA_INTEGER, np.int32)
@@ -104,7 +105,7 @@ def oracle_oob(oracle, model, G):
     for c, cls in enumerate(model.classifiers):
         oob = np.flatnonzero(np.asarray(cls.samp_num) == 0)
         fm = oracle.flatten(dataclasses.replace(model, classifiers=[cls]))
-        r = oracle.predict(fm, G[oob], 1, want_dosage=False, want_prob=False)
+        r = oracle.predict(fm, G[oob], 1, want_dosage=False, want_prob=False, avx2=avx2, n_threads=n_threads)
         h1[c, oob], h2[c, oob], prob[c, oob] = r["h1"], r["h2"], r["prob"]
     return {"h1": h1, "h2": h2, "prob": prob}
 
@@ -131,3 +132,100 @@ def test_oracle_loop_reproduces_the_stored_oob_accuracy(oracle, model_oob, hapma
     # classifier 98: two of its OOB samples miss every one of its SNPs -- hlaPredict calls nothing there
     oob98 = np.flatnonzero(np.asarray(model_oob.classifiers[98].samp_num) == 0)
     assert int(np.sum(got["h1"][98, oob98] == NA_INTEGER)) == 2
+
+
+# ---- T-ties: cells that the one-classifier transform merges -----------------------------------------------------------
+# A one-classifier model's call is the first strict maximum of T(p) = (0 + p * w) * (1 / w), p = cell * (1 / total),
+# w = typed SNPs / SNPs (src/LibHLA.cpp:1497-1518, 1549-1566, 2418-2431).  T can map cells an ulp apart to one value,
+# and then the EARLIER cell wins.  With one haplotype "00...0" per allele every pair is at distance 0, so the cells are
+# products of frequencies alone, and near-equal frequencies put the largest cells (0, j) a few ulps apart.
+
+TIE_SNPS = 120
+TIE_VARIANTS = ("basic", "ring", "first")
+TIE_RING_START = 11          # "ring": cells 0 .. 10 are eleven rising records before the near-equal ones
+_EPS = 2.0 ** -52
+
+
+def _tie_freqs(rng, variant):
+    """basic: f0 and seven near-equal f_j (records: (0,0), (0,1) and the (0,j) that still rise).
+    ring: ten clearly rising f_j first -- eleven records precede the near-equal cells, so the earliest tied record has
+    left slot 1 (the first record) and sits in the ring of the six latest.
+    first: f_j near f0 / 2, so 2 f0 f_j lies an ulp or two from f0^2: the first record, cell (0,0), ties with the maximum."""
+    if variant == "basic":
+        return np.concatenate([[0.15], 0.11 * (1 + rng.integers(0, 6, 7) * _EPS)])
+    if variant == "ring":
+        return np.concatenate([[0.15], 0.05 + 0.004 * np.arange(1, TIE_RING_START), 0.11 * (1 + rng.integers(0, 6, 7) * _EPS)])
+    f0 = rng.uniform(0.1, 0.3)
+    return np.concatenate([[f0], f0 / 2 * (1 + rng.integers(0, 2, 7) * _EPS)])
+
+
+def tie_case(snp_counts, seed, per=6):
+    """A model of `per` classifiers per (variant, SNP count) -- classifier i has variant TIE_VARIANTS[i // per %
+    3] -- 256 samples typed 0 at growing prefixes and at random subsets of the SNPs (NA elsewhere: weights typed / k),
+    and bootstrap counts that leave four samples in five out of bag.  Returns (model, G, samp_num, variant per classifier)."""
+    from hibag_amd.model import Classifier, HlaAttrBagObj
+    rng = np.random.default_rng(seed)
+    cls, kind = [], []
+    for k in snp_counts:
+        for v in TIE_VARIANTS:
+            for _ in range(per):
+                f = _tie_freqs(rng, v)
+                cls.append(Classifier(snpidx=np.sort(rng.choice(TIE_SNPS, k, replace=False)), freq=f,
+                                      hla=np.arange(len(f)), haplo=["0" * k] * len(f)))
+                kind.append(v)
+    n_hla = max(len(c.freq) for c in cls)
+    n = 256
+    G = np.full((n, TIE_SNPS), NA_INTEGER, np.int32)
+    for t in range(1, TIE_SNPS + 1):
+        G[t - 1, :t] = 0
+    for s in range(TIE_SNPS, n):
+        G[s, rng.random(TIE_SNPS) < rng.uniform(0.05, 0.95)] = 0
+    samp_num = np.zeros((len(cls), n), np.int32)
+    for c in range(len(cls)):
+        samp_num[c, (np.arange(n) + c) % 5 == 0] = 1
+        cls[c].samp_num = samp_num[c]
+    model = HlaAttrBagObj(n_samp=n, n_snp=TIE_SNPS, hla_allele=[f"{a:02d}" for a in range(n_hla)], classifiers=cls,
+                          sample_id=[f"s{i}" for i in range(n)])
+    return model, G, samp_num, kind
+
+
+def _cell(h1, h2, n_hla):
+    return h1 * n_hla - h1 * (h1 - 1) // 2 + (h2 - h1)
+
+
+def tie_calls(oracle, model, G, want):
+    """[C, n] bool: the oracle's out-of-bag call (`want`, from oracle_oob) is NOT the first maximum of the raw cells
+    p (oracle.post_prob2) -- a T-tie decided it -- and [C, n] int: the cell it called (-1: none).  Checks on the way that
+    the call is the first strict maximum of T restated here, and that `prob` is its value."""
+    C, n = want["h1"].shape
+    tie = np.zeros((C, n), bool)
+    called = np.full((C, n), -1)
+    for c, cls in enumerate(model.classifiers):
+        fm = oracle.flatten(dataclasses.replace(model, classifiers=[cls]))
+        idx = np.asarray(cls.snpidx)
+        for s in np.flatnonzero(want["h1"][c] != NA_INTEGER):
+            cells, _ = oracle.post_prob2(fm, 0, *oracle.int_to_snp(G[s], idx))       # (p = cell * (1 / total))
+            w = np.count_nonzero((G[s, idx] >= 0) & (G[s, idx] <= 2)) / len(idx)
+            T = (0.0 + cells * w) * (1 / w)
+            p = _cell(int(want["h1"][c, s]), int(want["h2"][c, s]), model.n_hla)
+            assert p == int(np.argmax(T)) and T[p] == want["prob"][c, s], (c, s)
+            called[c, s] = p
+            tie[c, s] = p != int(np.argmax(cells))
+    return tie, called
+
+
+@pytest.mark.parametrize("snp_counts,seed", [((10, 20, 27), 1), ((40, 84), 2), ((113, 120), 3)])
+def test_t_ties_are_reached_on_the_oracle(oracle, snp_counts, seed):
+    """The crafted cases of tests/test_hip_oob.py::test_t_ties really are T-ties in each variant: calls that are not
+    the raw first maximum, in the ring after more than seven records, and at the first record."""
+    model, G, samp_num, kind = tie_case(snp_counts, seed)
+    want = oracle_oob(oracle, model, G)
+    tie, called = tie_calls(oracle, model, G, want)
+    kind = np.array(kind)
+    for v in TIE_VARIANTS:
+        assert tie[kind == v].sum() >= 5, (v, int(tie[kind == v].sum()))
+    ring = tie[kind == "ring"] & (called[kind == "ring"] >= TIE_RING_START)
+    assert ring.sum() >= 5
+    first = tie[kind == "first"] & (called[kind == "first"] == 0)
+    assert first.sum() >= 5
+    assert np.array_equal(oracle_oob(oracle, model, G, avx2=True, n_threads=8)["prob"], want["prob"])
