@@ -152,7 +152,7 @@ def lib() -> C.CDLL:
     L.hibag_hip_predict_multi_sharded.argtypes = [C.POINTER(vp), i32, vp, i32, vp, vp, vp, vp, vp, vp]
     L.hibag_hip_measure_issue_costs.argtypes = [C.POINTER(dbl)] * 4
     L.hibag_hip_test_time_avg_prob.argtypes = [vp, vp, i32, i32, i32, vp, vp, C.POINTER(dbl)]
-    if hasattr(L, "hibag_hip_test_read_diag"):          # (absent from older builds loaded through HIBAG_HIP_LIBRARY for A/B timings)
+    if hasattr(L, "hibag_hip_test_read_diag"):
         L.hibag_hip_test_read_diag.argtypes = [vp, vp, i32]
         L.hibag_hip_plugin_degraded_calls.restype = i64
     _lib = L

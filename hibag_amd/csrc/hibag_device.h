@@ -256,6 +256,10 @@ struct HibagModelView {
 	int slots_total[4], slots_accum;
 };
 
+// word 1 of an E-stream header (HibagModelView::ehdr): the block's stored sums, and the row of the first of them
+__device__ __forceinline__ int ehdr_stored_count(uint32_t w1) { return (int)(w1 >> 25) & 15; }
+__device__ __forceinline__ uint32_t ehdr_stored_row(uint32_t w1) { return w1 & 0x1FFFFFFu; }
+
 struct HibagBatchView {
 	int n_samp;         // samples in this batch
 	int n_pad;          // rounded up to a multiple of 64

@@ -210,7 +210,6 @@ struct hibag_hip_model {
 	DevBuf oob_hap;
 	size_t oob_freq_at = 0, oob_off_at = 0, oob_start_at = 0;
 	bool oob_hap_ready = false;
-	DevBuf ws_thrash;                      // HIBAG_DEBUG_THRASH_MB (hibag_predict.hip run_core): scratch a measurement overwrites between the passes
 
 	KernelTimer timer;
 	std::mutex lock;
@@ -229,7 +228,7 @@ struct hibag_hip_model {
 		if (side.join) (void)hipEventDestroy(side.join);
 		if (side.stream) (void)hipStreamDestroy(side.stream);
 		for (DevBuf *b : {&d_int, &d_stream, &d_tile, &d_tab, &d_blk, &d_pfac, &d_phdr, &d_parow, &ws_bt, &ws_bias, &ws_cells, &ws_sync, &ws_err, &ws_planes, &ws_cw, &ws_tot, &ws_inv, &ws_winv,
-		                  &ws_part, &ws_best, &ws_vrec, &ws_geno, &ws_out, &ws_codes, &ws_bed, &ws_bedidx, &ws_thrash, &oob_hap})
+		                  &ws_part, &ws_best, &ws_vrec, &ws_geno, &ws_out, &ws_codes, &ws_bed, &ws_bedidx, &oob_hap})
 			b->release();
 	}
 };

@@ -137,20 +137,6 @@ __device__ __forceinline__ void load_operand_row(const HibagBatchView &B, int bt
 	}
 }
 
-// One-step FP4, the walk without lane swaps (walk_blocks, OWN): b[0][0] = the "sum" side (K half 0 of the packed operand) and
-// b[1][0] = the "pair" side (K half 1) of the LANE'S OWN sample -- lanes 0..31 take theirs from the operand row of samples
-// 0..31, lanes 32..63 from the row of samples 32..63 (k_pack's layout: row = sample half, position = K half * 32 + sample).
-__device__ __forceinline__ void load_operand_own_sample(const HibagBatchView &B, int bt_row, int group, int lane, LaneOperand &T)
-{
-	const size_t n_group = (size_t)(B.n_pad / HIBAG_WAVE);
-	const uint4 *row = B.bt + ((size_t)(bt_row + (lane >> 5)) * n_group + group) * HIBAG_WAVE + (lane & 31);
-	const uint4 va = row[0], vb = row[32];
-	T.b[0][0] = v4i{(int)va.x, (int)va.y, (int)va.z, (int)va.w};
-	T.b[1][0] = v4i{(int)vb.x, (int)vb.y, (int)vb.z, (int)vb.w};
-	T.b[0][1] = T.b[1][1] = v4i{0, 0, 0, 0};
-	T.bias[0] = T.bias[1] = 0;
-}
-
 __device__ __forceinline__ WideSrc wide_src(const HibagBatchView &B, int bt_row, int nstep, int group)
 {
 	WideSrc w;
@@ -214,7 +200,7 @@ __device__ __forceinline__ void fp4_step(const v4i &e1, const v4i &e2, int lane,
 }
 
 template <int ENG>
-__device__ __forceinline__ void block_mfma(const v4i &e1, const v4i &e2, int lane, const v4i &cterm, const LaneOperand &T,
+__device__ __forceinline__ void block_mfma(const v4i &e1, const v4i &e2, int lane, const LaneOperand &T,
 	v16i &acc0, v16i &acc1)
 {
 	const bool upper = lane >= 32;
@@ -232,11 +218,8 @@ __device__ __forceinline__ void block_mfma(const v4i &e1, const v4i &e2, int lan
 		const v8i b0 = {T.b[0][0][0], T.b[0][0][1], T.b[0][0][2], T.b[0][0][3], 0, 0, 0, 0};
 		const v8i b1 = {T.b[1][0][0], T.b[1][0][1], T.b[1][0][2], T.b[1][0][3], 0, 0, 0, 0};
 		const int sb = upper ? HIBAG_FP4_SCALE_B_HI : HIBAG_FP4_SCALE_B_LO;
-		if (ABL_NOMFMA) { abl_fake_distances(a8, b0, b1, sb, d0, d1); }
-		else {
-			d0 = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a8, b0, d0, 4, 4, 0, HIBAG_FP4_SCALE_A, 0, sb);
-			d1 = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a8, b1, d1, 4, 4, 0, HIBAG_FP4_SCALE_A, 0, sb);
-		}
+		d0 = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a8, b0, d0, 4, 4, 0, HIBAG_FP4_SCALE_A, 0, sb);
+		d1 = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a8, b1, d1, 4, 4, 0, HIBAG_FP4_SCALE_A, 0, sb);
 		acc0 = __builtin_bit_cast(v16i, d0);
 		acc1 = __builtin_bit_cast(v16i, d1);
 		return;
@@ -272,7 +255,6 @@ __device__ __forceinline__ void block_own_sample(v16i &D0, v16i &D1, Live8 &&liv
 #pragma unroll
 	for (int g = 0; g < 4; g++) {
 		if (!live8(g)) break;
-		if (ABL_NOSWAP) continue;
 #pragma unroll
 		for (int r = 4 * g; r < 4 * g + 4; r++) {
 			const auto sw = __builtin_amdgcn_permlane32_swap(D0[r], D1[r], false, false);
@@ -285,27 +267,10 @@ __device__ __forceinline__ void block_own_sample(v16i &D0, v16i &D1, int n_valid
 	block_own_sample(D0, D1, [&](int g) { return 8 * g < n_valid; });
 }
 
-// A bank-interleaved table for classifiers of several K steps (33 .. 112 SNPs) -- BUILT, MEASURED SLOWER, NOT SHIPPED
-// (-DHIBAG_WIDE_TAB=true builds it).  Their distances spread over 0 .. 2 k, so the 64 lanes of a look-up hit 64 different
-// 8-byte entries of the plain table: k_total_wide counts more bank-conflict cycles than LDS-busy cycles
-// (profiles/r05_sq_counters.txt: SQ_LDS_BANK_CONFLICT 976,690 against SQ_ACTIVE_INST_LDS 837,640).  TAB[d] is exactly zero
-// from d = 65 on (exp(d log 1e-5) underflows: src/LibHLA.cpp:176-183; checked where a model is created), so the offset can be
-// clamped at 65 and the 66 entries laid out 32-way interleaved -- entry d of replica r at (32 d + r) * 8 bytes, lane l reads
-// replica l % 32: whatever d, the 32 lanes of a ds_read_b64 group are on 32 different bank pairs; 17 KB per workgroup.
-// It removes the conflicts and costs two vector instructions per pair (the clamp, the shift-and-add) where the plain table
-// costs none -- the matrix result IS its byte offset -- on a loop whose vector ALU work is two FP64 operations per pair:
-// pass 1 of the wide-classifier model 0.60 ms with the plain table, 0.92 ms with this one, same box, three runs each
-// (profiles/r06_notes.txt).  The conflicts are the cheaper evil.
-#ifndef HIBAG_WIDE_TAB
-#define HIBAG_WIDE_TAB false
-#endif
-#define HIBAG_WIDE_TAB_CLAMP 65
-#define HIBAG_WIDE_TAB_N ((HIBAG_WIDE_TAB_CLAMP + 1) * 32)
-__device__ __forceinline__ double table_value_wide(const double *tabw_s, int off)     // off = 8 d
+// TAB[d] for the byte offset 8 d the matrix instructions leave in the lane's register
+__device__ __forceinline__ double table_value(const double *tab_s, int off)
 {
-	const uint32_t o = min((uint32_t)off, (uint32_t)(8 * HIBAG_WIDE_TAB_CLAMP));
-	const uint32_t lane8 = (__builtin_amdgcn_mbcnt_lo(~0u, 0u) & 31u) * 8u;        // (lane & 31) * 8: lanes l and l + 32 are in different groups
-	return *reinterpret_cast<const double *>(reinterpret_cast<const char *>(tabw_s) + (o << 5) + lane8);
+	return *reinterpret_cast<const double *>(reinterpret_cast<const char *>(tab_s) + off);
 }
 
 // cell += prod_i * TAB[d_i] for the first n_valid records of a block, in order;
@@ -332,9 +297,7 @@ template <> struct FactorGroup<8> { typedef f64x8 type; };
 // group the choice is part of the branch that closes the cell; across groups and blocks the wave-uniform `fresh` says that the
 // record before closed one (a scalar register; the walk that ends on it materialises the zero).
 // `live(g)`: group g of the block has records worth evaluating (the groups before it then have too).
-// LINEAR: record i's distance is D0[i] (i < 16) / D1[i - 16] -- the layout of the walk without lane swaps (walk_blocks, OWN).
-// WIDE_TAB: `tab_s` is the bank-interleaved table of the classifiers with several K steps (table_value_wide below).
-template <int G, bool AHEAD = false, bool LINEAR = false, bool WIDE_TAB = false, class Live, class Fin>
+template <int G, bool AHEAD = false, class Live, class Fin>
 __device__ __forceinline__ void block_accumulate(ConstPtr<double> fac, typename FactorGroup<G>::type F, uint32_t endmask, uint32_t storemask, Live &&live,
 	const v16i &D0, const v16i &D1, double &cell, uint32_t fresh, const double *tab_s, Fin &&fin)
 {
@@ -347,8 +310,8 @@ __device__ __forceinline__ void block_accumulate(ConstPtr<double> fac, typename 
 #pragma unroll
 		for (int q = 0; q < G; q++) {         // D = 8*d: already the byte offset into the table
 			const int i = G * g + q;          // record i = 8 m + r  ->  r < 4 ? D0[4 m + r] : D1[4 m + r - 4]
-			const int off = LINEAR ? (i < 16 ? D0[i] : D1[i - 16]) : (i & 7) < 4 ? D0[4 * (i >> 3) + (i & 3)] : D1[4 * (i >> 3) + (i & 3)];
-			t[q] = WIDE_TAB ? table_value_wide(tab_s, off) : table_value(tab_s, off);
+			const int off = (i & 7) < 4 ? D0[4 * (i >> 3) + (i & 3)] : D1[4 * (i >> 3) + (i & 3)];
+			t[q] = table_value(tab_s, off);
 		}
 	};
 	double tt[AHEAD ? 2 : 1][G];
@@ -366,7 +329,7 @@ __device__ __forceinline__ void block_accumulate(ConstPtr<double> fac, typename 
 		asm volatile("" : "+v"(t[0]));
 		__builtin_amdgcn_sched_barrier(0);
 		FG Fn = F;
-		if (!ABL_NOFAC && g + 1 < 32 / G) Fn = *(ConstPtr<FG>)(fac + G * (g + 1));
+		if (g + 1 < 32 / G) Fn = *(ConstPtr<FG>)(fac + G * (g + 1));
 		if (AHEAD && g + 1 < 32 / G && live(g + 1)) look_up(g + 1, tt[(g + 1) & 1]);
 		__builtin_amdgcn_sched_barrier(0);
 		// the record before this group closed a cell: the caller's word for the block's first group, the end mask's own bit for
@@ -436,19 +399,7 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 // PRE (one-step FP4 only): the A-operand rows are PREBUILT (HibagModelView::parow, 1 KB per block): one coalesced 16-byte load
 // per lane and block, requested a block ahead right behind the matrix instructions that consumed the current rows -- no
 // slot words, no gathers from the haplotype table, no address arithmetic, no additions.
-// OWN (with PRE): NO LANE SWAPS.  A 32 x 32 matrix result leaves rows 8m .. 8m+3 of sample column j in lane j and rows
-// 8m+4 .. 8m+7 in lane j + 32, and sixteen v_permlane32_swap per block (1.7 FP64 operations each) gave every lane its own
-// sample's 32 rows.  Instead the A operand holds each of SIXTEEN slots in two rows -- row 8m+q with the slot's image in K half 0
-// and zeros in K half 1, row 8m+4+q the other way round -- and the B operand's column j has sample j in K half 0 and sample
-// j + 32 in K half 1 (load_operand_own_sample): lane j then receives slot . sample j, lane j + 32 slot . sample (j + 32), both
-// in register r = 4m + q.  The two images of a slot (the "sum" side and the "pair" side of the dot product) take two matrix
-// instructions that accumulate, the block's 32 slots two such chains: four matrix instructions instead of two, no swap, and
-// record i simply sits in register i.  The four A operands are the block's prebuilt row itself, read with one per-lane offset
-// (a lane whose row-half is zeros does not load and keeps its zeros).
-// MEASURED (round 5, profiles/r05_pass2_notes.txt item 20): every output bit-identical, pass 1 0.760-0.786 ms against 0.743-0.747
-// with the swaps -- two more matrix instructions (which FP64 work does not overlap with) and three more loads per block cost
-// more than sixteen swaps, whose removal alone is worth 8 %.  Kept as a variant (-DTOTAL_OWN=true), not shipped.
-template <int ENG, int G, bool PRE, bool OWN = false, class Fin>
+template <int ENG, int G, bool PRE, class Fin>
 __device__ __forceinline__ void walk_blocks(const HibagModelView &M, uint64_t at, int nblk, int lane, ListCursor &cur,
 	__amdgpu_buffer_rsrc_t hp, int k, const LaneOperand &T, const WideSrc &wide, const double *tab_s, double &cell, Fin &&fin)
 {
@@ -458,76 +409,6 @@ __device__ __forceinline__ void walk_blocks(const HibagModelView &M, uint64_t at
 	uint32_t fresh = 0;                              // block_accumulate: the record before closed a cell
 	ConstPtr<double> fac = as_const(M.pfac) + at;                            // this segment's factors and headers
 	ConstPtr<u32x4> hdr = (ConstPtr<u32x4>)(as_const(M.phdr) + at / HIBAG_PLIST_DWORDS * 4);
-	if (PRE && OWN) {
-		const uint64_t blk = at / HIBAG_PLIST_DWORDS;
-		const uint64_t left = (M.parow_blocks - blk) * 1024u;
-		const __amdgpu_buffer_rsrc_t pr = __builtin_amdgcn_make_buffer_rsrc((void *)(M.parow + blk * 64), 0,
-			left > 0xFFFFFFF0ull ? (int)0xFFFFFFF0u : (int)left, 0x00020000);
-		const int row = lane & 31;
-		const bool supplies = ((row >> 2) & 1) == (lane >> 5);        // this lane's (row, K half) of the A operand is not zeros
-		const int vo = (4 * (row >> 3) + (row & 3)) * 16;              // its slot among the chain's sixteen (an entry is 16 bytes)
-		// A[2 c + image]: chain c = slots 16 c .. 16 c + 15; the prebuilt row has the "sum" images of the 32 slots, then the "pair" images
-		v4i A[4];
-#pragma unroll
-		for (int k = 0; k < 4; k++) A[k] = v4i{0, 0, 0, 0};
-		auto request_rows = [&](uint32_t soff) {
-			if (supplies) {
-				int v = vo;
-				asm volatile("" : "+v"(v));                   // (kept out of the loop-invariant code: the four offsets as the instructions' immediates, not as registers)
-#pragma unroll
-				for (int k = 0; k < 4; k++)
-					A[k] = __builtin_bit_cast(v4i, __builtin_amdgcn_raw_buffer_load_b128(pr, v + (k & 1) * 512 + (k >> 1) * 256, (int)soff, 0));
-			}
-		};
-		request_rows(0);
-		u32x4 H_n = hdr[0];
-		FG F_n = *(ConstPtr<FG>)fac;
-		uint32_t soff = 1024;
-		const v8i b_sum = {T.b[0][0][0], T.b[0][0][1], T.b[0][0][2], T.b[0][0][3], 0, 0, 0, 0};
-		const v8i b_pair = {T.b[1][0][0], T.b[1][0][1], T.b[1][0][2], T.b[1][0][3], 0, 0, 0, 0};
-		for (int b = 0; b < nblk; b++) {
-			const u32x4 H = H_n;
-			const FG F = F_n;
-			const uint32_t endmask = abl_endmask(H[0]), storemask = abl_storemask(H[1]);
-			const int n_valid = (int)H[2];
-			// (the header is waited for HERE, before the next scalar loads are issued: a wait behind them would be for them too)
-			asm volatile("" :: "s"(n_valid));
-			__builtin_amdgcn_sched_barrier(0);
-			H_n = hdr[b + 1];
-			F_n = *(ConstPtr<FG>)(fac + (size_t)(b + 1) * HIBAG_PLIST_DWORDS);
-			if (n_valid > 0) {
-				v16f x0, x1;
-#pragma unroll
-				for (int r = 0; r < 16; r++) { x0[r] = 0.0f; x1[r] = 0.0f; }
-				{
-					// (the two chains interleaved: a matrix instruction that accumulates onto the one before it waits for its result)
-					const v8i a0 = {A[0][0], A[0][1], A[0][2], A[0][3], 0, 0, 0, 0}, a1 = {A[1][0], A[1][1], A[1][2], A[1][3], 0, 0, 0, 0};
-					const v8i a2 = {A[2][0], A[2][1], A[2][2], A[2][3], 0, 0, 0, 0}, a3 = {A[3][0], A[3][1], A[3][2], A[3][3], 0, 0, 0, 0};
-					// (always all four: pass 1's blocks are 96 % full, and a branch here lets the compiler put the next block's loads in
-					// front of the second chain -- whose operands' wait then becomes a wait for those loads)
-					x0 = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a0, b_sum, x0, 4, 4, 0, HIBAG_FP4_SCALE_A, 0, HIBAG_FP4_SCALE_B_LO);
-					x1 = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a2, b_sum, x1, 4, 4, 0, HIBAG_FP4_SCALE_A, 0, HIBAG_FP4_SCALE_B_LO);
-					__builtin_amdgcn_sched_barrier(0);
-					x0 = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a1, b_pair, x0, 4, 4, 0, HIBAG_FP4_SCALE_A, 0, HIBAG_FP4_SCALE_B_HI);
-					x1 = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a3, b_pair, x1, 4, 4, 0, HIBAG_FP4_SCALE_A, 0, HIBAG_FP4_SCALE_B_HI);
-					// (both results count as used HERE: the second chain is only read by the block's later groups, and the compiler
-					// would sink its matrix instructions down to them -- behind the next block's loads, in the middle of the additions)
-					asm volatile("" : "+v"(x0), "+v"(x1));
-				}
-				__builtin_amdgcn_sched_barrier(0);
-				request_rows(soff);                           // the next block's, behind the instructions that read this one's
-				__builtin_amdgcn_sched_barrier(0);
-				const v16i D0 = __builtin_bit_cast(v16i, x0), D1 = __builtin_bit_cast(v16i, x1);
-				block_accumulate<G, false, true>(fac + (size_t)b * HIBAG_PLIST_DWORDS, F, endmask, storemask, [&](int g) { return G * g < n_valid; }, D0, D1, cell, fresh, tab_s, fin);
-				fresh = fresh_behind<G>(fresh, endmask, n_valid);
-			} else {
-				request_rows(soff);
-			}
-			soff += 1024;
-		}
-		if (fresh) cell = 0;
-		return;
-	}
 	if (PRE) {
 		const uint64_t blk = at / HIBAG_PLIST_DWORDS;
 		const uint64_t left = (M.parow_blocks - blk) * 1024u;
@@ -541,27 +422,21 @@ __device__ __forceinline__ void walk_blocks(const HibagModelView &M, uint64_t at
 		for (int b = 0; b < nblk; b++) {
 			const u32x4 H = H_n;
 			const FG F = F_n;
-			const uint32_t endmask = abl_endmask(H[0]), storemask = abl_storemask(H[1]);
+			const uint32_t endmask = H[0], storemask = H[1];
 			const int n_valid = (int)H[2];
 			// (the header is waited for HERE, before the next scalar loads are issued: a wait behind them would be for them too)
 			asm volatile("" :: "s"(n_valid));
 			__builtin_amdgcn_sched_barrier(0);
 			H_n = hdr[b + 1];
 			F_n = *(ConstPtr<FG>)(fac + (size_t)(b + 1) * HIBAG_PLIST_DWORDS);
-#ifdef HIBAG_TOTAL_PRIO            // (measured variant: the head of a block at raised priority)
-			__builtin_amdgcn_s_setprio(1);
-#endif
 			v4i a = arow;
 			asm volatile("" : "+v"(a));                   // (this block's rows have arrived: requested a block ago)
 			if (n_valid > 0) {
 				v16i D0, D1;
-				block_mfma<ENG>(a, v4i{0, 0, 0, 0}, lane, v4i{0, 0, 0, 0}, T, D0, D1);
+				block_mfma<ENG>(a, v4i{0, 0, 0, 0}, lane, T, D0, D1);
 				__builtin_amdgcn_sched_barrier(0);
 				arow = __builtin_bit_cast(v4i, __builtin_amdgcn_raw_buffer_load_b128(pr, vo, (int)soff, 0));    // the next block's, behind the instructions that read this one's
 				__builtin_amdgcn_sched_barrier(0);
-#ifdef HIBAG_TOTAL_PRIO
-				__builtin_amdgcn_s_setprio(0);
-#endif
 				block_own_sample(D0, D1, n_valid);
 				block_accumulate<G>(fac + (size_t)b * HIBAG_PLIST_DWORDS, F, endmask, storemask, [&](int g) { return G * g < n_valid; }, D0, D1, cell, fresh, tab_s, fin);
 				fresh = fresh_behind<G>(fresh, endmask, n_valid);
@@ -573,14 +448,12 @@ __device__ __forceinline__ void walk_blocks(const HibagModelView &M, uint64_t at
 		if (fresh) cell = 0;
 		return;
 	}
-#ifndef HIBAG_WIDE_OLDWALK                   // (variant for A/B timing: round 5's walk, which fetches the further steps' operands where they are used)
 	if (ENG == HIBAG_ENGINE_FP4W) {
 		// An FP4 classifier of `wide.nstep` (2 .. 4) K steps; `k` = SNPs of its LAST step, the others have HIBAG_FP4_STEP_SNPS.
-		// Round 6: until now the further steps' images and B operands were fetched where they were used -- two dependent gathers
-		// and two operand loads per step, each waited for on the spot, three times per block -- and the kernel ran at a quarter
-		// of its issue floor.  Now the B operands of the further steps, which are the same for every block, live in registers,
-		// and a block's images of ALL steps are requested a block ahead, right behind the matrix instructions that read the
-		// current ones (as the prebuilt rows of the one-step walk are); `tab_s` is the bank-interleaved table.
+		// The B operands of the further steps, which are the same for every block, live in registers, and a block's images of
+		// ALL steps are requested a block ahead, right behind the matrix instructions that read the current ones (as the prebuilt
+		// rows of the one-step walk are).  (Round 5 fetched the further steps' images and B operands where they were used -- two
+		// dependent gathers and two operand loads per step, each waited for on the spot -- and ran at a quarter of its issue floor.)
 		const int ns = wide.nstep;
 		const uint32_t ES = 4u * (uint32_t)HIBAG_FP4_ENTRY_DWORDS(ns);
 		const int vo_i = (lane & 31) * 4;
@@ -619,7 +492,7 @@ __device__ __forceinline__ void walk_blocks(const HibagModelView &M, uint64_t at
 		for (int b = 0; b < nblk; b++) {
 			const u32x4 H = H_n;
 			const FG F = F_n;
-			const uint32_t endmask = abl_endmask(H[0]), storemask = abl_storemask(H[1]);
+			const uint32_t endmask = H[0], storemask = H[1];
 			const int n_valid = (int)H[2];
 			asm volatile("" :: "s"(n_valid));             // (the header is waited for HERE, before the next scalar loads are issued)
 			__builtin_amdgcn_sched_barrier(0);
@@ -645,7 +518,7 @@ __device__ __forceinline__ void walk_blocks(const HibagModelView &M, uint64_t at
 			__builtin_amdgcn_sched_barrier(0);
 			if (n_valid > 0) {
 				block_own_sample(D0, D1, n_valid);
-				block_accumulate<G, false, false, HIBAG_WIDE_TAB>(fac + (size_t)b * HIBAG_PLIST_DWORDS, F, endmask, storemask, [&](int g) { return G * g < n_valid; }, D0, D1, cell, fresh, tab_s, fin);
+				block_accumulate<G>(fac + (size_t)b * HIBAG_PLIST_DWORDS, F, endmask, storemask, [&](int g) { return G * g < n_valid; }, D0, D1, cell, fresh, tab_s, fin);
 				fresh = fresh_behind<G>(fresh, endmask, n_valid);
 			}
 			soff += BB;
@@ -653,16 +526,11 @@ __device__ __forceinline__ void walk_blocks(const HibagModelView &M, uint64_t at
 		if (fresh) cell = 0;
 		return;
 	}
-#endif
-	// (FP4W is handled above; the flag stays for the shared declarations below)
-	constexpr bool FP4W = ENG == HIBAG_ENGINE_FP4W;
-	const uint32_t ES = FP4W ? 4u * (uint32_t)HIBAG_FP4_ENTRY_DWORDS(wide.nstep)
-	                         : 4u * (uint32_t)HIBAG_ENGINE_HAP_DWORDS(ENG);   // bytes per table entry (one-step FP4 and int8: 48)
+	const uint32_t ES = 4u * (uint32_t)HIBAG_ENGINE_HAP_DWORDS(ENG);   // bytes per table entry (one-step FP4 and int8: 48)
 	const int vo_i = (lane & 31) * 4;                // this lane's slot inside a block
 	// this lane's 16 bytes of an entry: the K half's bytes (int8), the K half's nibble image (one-step FP4: the "sum" image
-	// for lanes 0..31, the "pair" image for lanes 32..63), the one nibble image (FP4 of several steps)
-	const uint32_t img = FP4W ? 0u : (uint32_t)(lane >> 5) * 16u;
-	const v4i cterm = FP4W ? fp4_offset_term(HIBAG_FP4_STEP_SNPS, lane) : v4i{0, 0, 0, 0};   // (of K step 0)
+	// for lanes 0..31, the "pair" image for lanes 32..63)
+	const uint32_t img = (uint32_t)(lane >> 5) * 16u;
 	const uint32_t BB = 4 * HIBAG_PLIST_DWORDS;      // bytes per block
 	// The list is addressed as a raw buffer rebased at this segment, so that the 32-bit offsets inside
 	// the descriptor never limit the model size.
@@ -691,9 +559,8 @@ __device__ __forceinline__ void walk_blocks(const HibagModelView &M, uint64_t at
 			a1 = e1 + e2; a2 = v4i{0, 0, 0, 0};
 			asm volatile("" : "+v"(a1));
 		}
-		const uint32_t endmask = abl_endmask(H[0]), storemask = abl_storemask(H[1]);
+		const uint32_t endmask = H[0], storemask = H[1];
 		const int n_valid = (int)H[2];
-		const uint32_t ob1 = o1, ob2 = o2;           // (FP4W: where this block's entries are, for their further images)
 		// (the header is waited for HERE, before the next scalar loads are issued: a wait behind them would be for them too)
 		asm volatile("" :: "s"(n_valid));
 		__builtin_amdgcn_sched_barrier(0);
@@ -707,26 +574,7 @@ __device__ __forceinline__ void walk_blocks(const HibagModelView &M, uint64_t at
 		idx_n = __builtin_amdgcn_raw_buffer_load_b32(pl, vo_i, soff + 2 * BB, 0);
 		if (n_valid > 0) {
 			v16i D0, D1;
-			if (FP4W) {
-				// K step 0 like a one-step classifier, then the further steps: their images and B operands are fetched here
-				// (no look-ahead: a classifier this wide is rare, and its registers would be everybody's), chained through the
-				// accumulators
-				v16f d0, d1;
-#pragma unroll
-				for (int r = 0; r < 16; r++) { d0[r] = 0.0f; d1[r] = 0.0f; }
-				fp4_step(a1, a2, lane, cterm, T.b[0][0], T.b[1][0], d0, d1);
-				for (int j = 1; j < wide.nstep; j++) {
-					const v4i s1 = load_hap_image(hp, ob1 + 16u + 16u * (uint32_t)j), s2 = load_hap_image(hp, ob2 + 16u + 16u * (uint32_t)j);
-					const uint4 *row = wide.bt + ((size_t)(wide.bt_row + 2 * j) * wide.n_group + wide.group) * HIBAG_WAVE;
-					const uint4 u0 = row[lane], u1 = row[wide.n_group * HIBAG_WAVE + lane];
-					const v4i cj = fp4_offset_term(j == wide.nstep - 1 ? k : HIBAG_FP4_STEP_SNPS, lane);
-					fp4_step(s1, s2, lane, cj, v4i{(int)u0.x, (int)u0.y, (int)u0.z, (int)u0.w}, v4i{(int)u1.x, (int)u1.y, (int)u1.z, (int)u1.w}, d0, d1);
-				}
-				D0 = __builtin_bit_cast(v16i, d0);
-				D1 = __builtin_bit_cast(v16i, d1);
-			} else {
-				block_mfma<ENG>(a1, a2, lane, cterm, T, D0, D1);
-			}
+			block_mfma<ENG>(a1, a2, lane, T, D0, D1);
 			block_own_sample(D0, D1, n_valid);
 			block_accumulate<G>(fac + (size_t)b * HIBAG_PLIST_DWORDS, F, endmask, storemask, [&](int g) { return G * g < n_valid; }, D0, D1, cell, fresh, tab_s, fin);
 			fresh = fresh_behind<G>(fresh, endmask, n_valid);
@@ -777,12 +625,6 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t hap_rsrc(const HibagModelView 
 	case 10: { CALL(10); } break;          \
 	default: { CALL(12); } break;          \
 	}
-
-__device__ __forceinline__ void stage_table_wide(const HibagModelView &M, double *tabw_s)
-{
-	for (int i = threadIdx.x; i < HIBAG_WIDE_TAB_N; i += blockDim.x) tabw_s[i] = M.tab[i >> 5];
-	__syncthreads();
-}
 
 __device__ __forceinline__ void stage_table(const HibagModelView &M, double *tab_s, int n = HIBAG_TAB_N)
 {

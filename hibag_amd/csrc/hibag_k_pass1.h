@@ -206,15 +206,7 @@ __global__ __launch_bounds__(BLOCK_THREADS, OCC) void k_total(HibagModelView M, 
 			int vcnt = 0, vslot = 1, ci = 0;
 			uint4 *const vlog = VOTE ? B.vrec + (size_t)c * 8 * B.n_pad + s : nullptr;
 			auto fin = [&](double v, bool stored, int) {
-#ifdef HIBAG_STORE_PLAIN      // (variant: write-back stores instead of streaming ones)
-				if (STORE && stored) { rows[(size_t)row * HIBAG_WAVE + lane] = v; row++; }
-#elif defined(HIBAG_ABL_STX4)      // (timing ablation: as many stores, 16 bytes per lane each -- overlapping: the same memory lines)
-				if (STORE && stored) { __builtin_nontemporal_store(f64x2{v, v}, (f64x2 *)&rows[(size_t)row * HIBAG_WAVE + lane]); row++; }
-#elif defined(HIBAG_ABL_STHALF)    // (timing ablation: every second stored cell is written)
-				if (STORE && stored) { if (!(row & 1)) __builtin_nontemporal_store(v, &rows[(size_t)row * HIBAG_WAVE + lane]); row++; }
-#else
 				if (STORE && stored) { __builtin_nontemporal_store(v, &rows[(size_t)row * HIBAG_WAVE + lane]); row++; }
-#endif
 				total += v;
 				asm("" : "+v"(total));                    // keeps the cell end a scalar branch
 				if (VOTE) {
@@ -228,10 +220,9 @@ __global__ __launch_bounds__(BLOCK_THREADS, OCC) void k_total(HibagModelView M, 
 				}
 			};
 #define CALLX(E, PRE) { LaneOperand T;                                                                                         \
-			constexpr bool OWN = PRE && E == HIBAG_ENGINE_FP4 && TOTAL_OWN && !VOTE;   /* the walk without lane swaps (walk_blocks); the vote build has no registers for it */ \
-			if (OWN) load_operand_own_sample(B, M.bt_row[c], group, lane, T); else load_operand_row<E>(B, M.bt_row[c], c, group, lane, T); \
+			load_operand_row<E>(B, M.bt_row[c], c, group, lane, T);                                                        \
 			ListCursor cur;                                                                                                \
-			walk_blocks<E, TOTAL_G, PRE, OWN>(M, M.blk_off[c] + (uint64_t)b0 * HIBAG_PLIST_DWORDS, b1 - b0, lane, cur,       \
+			walk_blocks<E, TOTAL_G, PRE>(M, M.blk_off[c] + (uint64_t)b0 * HIBAG_PLIST_DWORDS, b1 - b0, lane, cur,            \
 				hap_rsrc(M, M.hap_off[c]), M.n_snp_c[c], T, WideSrc(), tab_s, cell, fin); }
 #define CALL(E) CALLX(E, false)
 			// one-step FP4 classifiers of a model small enough for prebuilt A-operand rows walk those (HibagModelView::parow)
@@ -277,12 +268,8 @@ template <bool WHOLE>
 #endif
 __global__ __launch_bounds__(BLOCK_THREADS, HIBAG_WIDE_OCC) void k_total_wide(HibagModelView M, HibagBatchView B)
 {
-	__shared__ double tab_s[HIBAG_WIDE_TAB ? HIBAG_WIDE_TAB_N : HIBAG_TAB_N];     // (HIBAG_WIDE_TAB: the bank-interleaved variant, hibag_k_engine.h)
-#if defined(HIBAG_WIDE_OLDWALK) || !HIBAG_WIDE_TAB
+	__shared__ double tab_s[HIBAG_TAB_N];
 	stage_table(M, tab_s);
-#else
-	stage_table_wide(M, tab_s);
-#endif
 	const int *__restrict__ seg = M.wide_seg + 4 * blockIdx.y;
 	const int c = seg[0];
 	const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -294,7 +281,7 @@ __global__ __launch_bounds__(BLOCK_THREADS, HIBAG_WIDE_OCC) void k_total_wide(Hi
 	double *__restrict__ rows = cell_rows(M, B, c, group);
 	int row = seg[1];
 	auto fin = [&](double v, bool, int) {
-		if (!ABL_WIDE_NOSTORE) { __builtin_nontemporal_store(v, &rows[(size_t)row * HIBAG_WAVE + lane]); row++; }
+		__builtin_nontemporal_store(v, &rows[(size_t)row * HIBAG_WAVE + lane]); row++;
 		if (WHOLE) { total += v; asm("" : "+v"(total)); }   // (the asm keeps the cell end a scalar branch)
 	};
 	const WideSrc wide = wide_src(B, M.bt_row[c], M.n_step[c], group);

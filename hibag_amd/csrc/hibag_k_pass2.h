@@ -46,11 +46,6 @@ __global__ __launch_bounds__(ACCUM_WAVES * HIBAG_WAVE, ACCUM_OCC) void k_accum(H
 	// (pass 2 evaluates one-step FP4 classifiers only: distances up to 2 * 30, the first 64 table entries)
 	__shared__ double tab_s[ACCUM_TAB_N];
 	__shared__ double acc_s[ACCUM_WAVES][HIBAG_TILE][HIBAG_WAVE];
-#ifdef HIBAG_ACCUM_STAMPS
-	__shared__ unsigned long long stamp_s[ACCUM_STAMP_N];
-	if (threadIdx.x < ACCUM_STAMP_N) stamp_s[threadIdx.x] = 0;
-	unsigned long long stamp_t = 0;
-#endif
 
 	// Work item = (XCD, four sample groups, one tile); the four wavefronts of a workgroup take the four groups.
 	// They read the same blocks at about the same time, so those
@@ -81,9 +76,6 @@ __global__ __launch_bounds__(ACCUM_WAVES * HIBAG_WAVE, ACCUM_OCC) void k_accum(H
 	const int group = (jq * ACCUM_WAVES + wave) * 8 + xcd;
 	unsigned long long *flag = B.sync + (size_t)xcd * n_item_x + item;
 	if (cb > 0) handover_wait(flag, B, (uint32_t)cb);
-#ifdef HIBAG_ACCUM_STAMPS
-	int bb_diag = 0, be_diag = 0;
-#endif
 	if (group < n_group) {
 	const int s = group * HIBAG_WAVE + lane;
 	const int ncell = M.tile_n[tile];
@@ -102,10 +94,7 @@ __global__ __launch_bounds__(ACCUM_WAVES * HIBAG_WAVE, ACCUM_OCC) void k_accum(H
 
 	const ConstPtr<uint32_t> cst = as_const(M.etile_cstart) + (size_t)tile * (C + 1);
 	const int bb = __builtin_amdgcn_readfirstlane((int)cst[cb]), be = __builtin_amdgcn_readfirstlane((int)cst[ce]);
-#ifdef HIBAG_ACCUM_STAMPS
-	if (wave == 0) { bb_diag = bb; be_diag = be; }
-#endif
-	if (bb < be && !(ABL2_NOLOOP && B.n_pad >= 0)) {
+	if (bb < be) {
 		// the tile's blocks [bb, be): their prebuilt A-operand rows as a raw buffer rebased at block bb (no 4 GB limit on the stream)
 		const uint64_t blk0 = as_const(M.etile_blk0)[tile] + (uint64_t)bb;
 		auto bytes32 = [](size_t n) { return n > 0xFFFFFFF0ull ? (int)0xFFFFFFF0u : (int)(uint32_t)n; };
@@ -145,28 +134,15 @@ __global__ __launch_bounds__(ACCUM_WAVES * HIBAG_WAVE, ACCUM_OCC) void k_accum(H
 		// is exact, and adding them at the end of the block, was measured: pass 2 +15 % -- the loads that fetch nothing still cost
 		// their issue (profiles/r05_pass2_notes.txt).
 		auto request_sv = [&](uint32_t w1) {
-			const int ns = abl2_stored(w1);
+			const int ns = ehdr_stored_count(w1);
 			if (ns > 0) {
-				const int sr = (int)(abl2_stored_row(w1) * (uint32_t)(HIBAG_WAVE * 8));
+				const int sr = (int)(ehdr_stored_row(w1) * (uint32_t)(HIBAG_WAVE * 8));
 				int vo = vo_sv;
 				asm volatile("" : "+v"(vo));                  // (kept out of the loop-invariant code: vo + 512 i in six registers instead of the instructions' offset fields)
 #pragma unroll
 				for (int i = 0; i < NS; i++) {
 					if (i >= ns) break;
-#ifdef HIBAG_ABL2_SVNOLOAD                    // (timing ablation: the stored sums are added, never loaded)
-					asm volatile("" : "=v"(sv[i]));
-#elif defined(HIBAG_ABL2_SVX4)                // (timing ablation: as many loads, 16 bytes per lane each -- overlapping: the same memory lines)
-					sv[i] = __builtin_bit_cast(f64x2, __builtin_amdgcn_raw_buffer_load_b128(r_sv, vo + i * HIBAG_WAVE * 8, sr, 2))[0];
-#elif defined(HIBAG_ABL2_SVHALF)              // (timing ablation: every second stored sum is loaded)
-					if (i & 1) asm volatile("" : "=v"(sv[i]));
-					else sv[i] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(r_sv, vo + i * HIBAG_WAVE * 8, sr, 2));
-#else
-#ifdef HIBAG_SV_PLAIN                         // (correct variant: default cache policy instead of nt)
-					sv[i] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(r_sv, vo + i * HIBAG_WAVE * 8, sr, 0));
-#else
 					sv[i] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(r_sv, vo + i * HIBAG_WAVE * 8, sr, 2));   // (read once: nt; the row's distance as the instruction's immediate offset)
-#endif
-#endif
 				}
 			}
 		};
@@ -176,8 +152,7 @@ __global__ __launch_bounds__(ACCUM_WAVES * HIBAG_WAVE, ACCUM_OCC) void k_accum(H
 			const int sb = (int)((w0 >> 16) * row_stride);
 			t0 = __builtin_bit_cast(v4i, __builtin_amdgcn_raw_buffer_load_b128(r_bt, vo_row, sb, 0));
 			t1 = __builtin_bit_cast(v4i, __builtin_amdgcn_raw_buffer_load_b128(r_bt, vo_row, sb + (int)row_stride, 0));
-			if (ABL2_NOWINV) winv = f64x2{1.0 + (double)w0, 2.0};
-			else winv = __builtin_bit_cast(f64x2, __builtin_amdgcn_raw_buffer_load_b128(r_wi, vo_row, (int)((w0 & 0xFFFFu) * row_stride), 0));
+			winv = __builtin_bit_cast(f64x2, __builtin_amdgcn_raw_buffer_load_b128(r_wi, vo_row, (int)((w0 & 0xFFFFu) * row_stride), 0));
 			request_sv(w1);
 		};
 		// One block: `cur` = what it needs (arrived: requested a block ago), `nxt` = where the next block's goes.
@@ -186,11 +161,6 @@ __global__ __launch_bounds__(ACCUM_WAVES * HIBAG_WAVE, ACCUM_OCC) void k_accum(H
 		// runs: it covers every latency.  No load of the loop is waited for with a count: at the top of a block everything in
 		// flight is that block's.
 		auto one_block = [&](const int rel, AccumAhead &cur, AccumAhead &nxt) {
-#if defined(HIBAG_ACCUM_PRIO) && HIBAG_ACCUM_PRIO == 1      // (measured variant: the head of a block -- waits, stored sums, matrix instructions, requests -- at raised priority)
-			__builtin_amdgcn_s_setprio(1);
-#elif defined(HIBAG_ACCUM_PRIO) && HIBAG_ACCUM_PRIO == 2    // (measured variant: the pairs' accumulation at raised priority)
-			__builtin_amdgcn_s_setprio(0);
-#endif
 			const double w_c = cur.winv[0];
 			const bool active = w_c > 0;
 			// (as integers in scalar registers -- a count of lanes is one scalar instruction; a bool that lives across the requests
@@ -214,14 +184,13 @@ __global__ __launch_bounds__(ACCUM_WAVES * HIBAG_WAVE, ACCUM_OCC) void k_accum(H
 			typedef const volatile __attribute__((address_space(4))) uint32_t *TouchPtr;
 			const TouchPtr touch = (TouchPtr)(uintptr_t)(fac + (size_t)(rel + 1) * HIBAG_PLIST_DWORDS);
 			const uint32_t tch0 = touch[16], tch1 = touch[32], tch2 = touch[48];
-			ACCUM_STAMP(0);
 			// (`eval` and `eval_b`: the same number in two scalar registers the compiler cannot tell are equal -- one condition used in
 			// two places became a lane mask parked in a vector register between them)
-			int eval = ABL2_NOEVAL ? 0 : (any != 0 ? (int)(gword >> 28) : 0), eval_b = eval;
+			int eval = any != 0 ? (int)(gword >> 28) : 0, eval_b = eval;
 			asm volatile("" : "+s"(eval), "+s"(eval_b));
 			// ---- the sums pass 1 stored for this block's classifier:   S[p] += (cell * (1/total)) * w
 			{
-				const int ns = abl2_stored(cur.hv[1]);
+				const int ns = ehdr_stored_count(cur.hv[1]);
 				// (a classifier nobody in the group uses is passed over: its blocks leave `cell` as it was, and the next block's
 				// header bit describes a stream in which they were evaluated -- so the sum goes back to zero here)
 				if (!any) asm volatile("v_mov_b64 %0, 0" : "+v"(cell));    // (cell = 0, in its own register: as an assignment it cost the common path two moves)
@@ -232,18 +201,13 @@ __global__ __launch_bounds__(ACCUM_WAVES * HIBAG_WAVE, ACCUM_OCC) void k_accum(H
 #pragma unroll
 						for (int i = 0; i < NS; i++) {
 							if (i >= ns) break;
-#ifdef HIBAG_ABL2_SVNOADD                     // (timing ablation: the stored sums are loaded and waited for, never added)
-							asm volatile("" :: "v"(sv[i]));
-#else
 							__hip_atomic_fetch_add(&acc[(int)(jps & 15)][lane], (sv[i] * inv_e) * w_c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-#endif
 							jps >>= 4;
 						}
 					}
 				}
 			}
 			__builtin_amdgcn_sched_barrier(0);
-			ACCUM_STAMP(1);
 			// ---- distances on the matrix pipe (their operands have arrived with everything else of the block)
 			v16i D0, D1;
 			if (eval) {
@@ -260,23 +224,12 @@ __global__ __launch_bounds__(ACCUM_WAVES * HIBAG_WAVE, ACCUM_OCC) void k_accum(H
 				D1 = __builtin_bit_cast(v16i, d1);
 			}
 			__builtin_amdgcn_sched_barrier(0);
-			ACCUM_STAMP(2);
 			// ---- everything of block b + 1, into the registers this block has finished with
 			request_lane(cur.hv[2], cur.hv[3], (rel + 1) * 1024, nxt.winv);
 			__builtin_amdgcn_sched_barrier(0);
-			ACCUM_STAMP(3);
-#if defined(HIBAG_ACCUM_PRIO) && HIBAG_ACCUM_PRIO == 1
-			__builtin_amdgcn_s_setprio(0);
-#elif defined(HIBAG_ACCUM_PRIO) && HIBAG_ACCUM_PRIO == 2
-			__builtin_amdgcn_s_setprio(1);
-#endif
 			// ---- every lane its own sample's distances, then cell += prod * TAB[d] in order
 			if (eval_b) {
 				block_own_sample(D0, D1, [&](int g) { return live4(2 * g); });
-#ifdef HIBAG_ACCUM_STAMPS
-				asm volatile("" :: "v"(D0[0]), "v"(D1[0]));
-				ACCUM_STAMP(4);
-#endif
 				// S[p] += v as one LDS floating-point add (ds_add_f64: the same IEEE addition, no register for the old
 				// sum, nothing to wait for).  The tile row of the cell that closes at slot i (odd) is field i / 2 of the header's
 				// words 4, 5: a fixed place per slot, so one bit-field extract, no shifting along of a packed list.
@@ -285,11 +238,7 @@ __global__ __launch_bounds__(ACCUM_WAVES * HIBAG_WAVE, ACCUM_OCC) void k_accum(H
 					uint32_t row;                             // (s_bfe_u32 by hand: the compiler's shift-and-mask form takes two instructions)
 					asm volatile("s_bfe_u32 %0, %1, %2" : "=s"(row) : "s"(slot < 16 ? jp_lo : jp_hi), "n"(4 * ((slot >> 1) & 7) | (4 << 16)) : "scc");
 					const double v = (c * inv_e) * w_c;
-#ifdef HIBAG_ABL2_NOADD                       // (timing ablation: the product is made, the LDS addition is not)
-					asm volatile("" :: "v"(v), "s"(row));
-#else
 					__hip_atomic_fetch_add(&acc[(int)row][lane], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-#endif
 				};
 				// what the block's first record starts from is a bit of its header (the record before it in the stream closed a cell)
 				uint32_t fresh = (cur.hv[1] >> 29) & 1u;
@@ -298,16 +247,12 @@ __global__ __launch_bounds__(ACCUM_WAVES * HIBAG_WAVE, ACCUM_OCC) void k_accum(H
 			// (the header's word 7 counts as in use to the end of the block: otherwise its register -- free as far as the compiler
 			// can see, but still to be written by the header load in flight -- is handed to one of the loads above, which then has to wait for that load)
 			asm volatile("" :: "s"(tch0), "s"(tch1), "s"(tch2), "s"(nxt.hv[7]));
-			ACCUM_STAMP(5);
 		};
 
 		AccumAhead A, Bn;
 		A.hv = eh[0];
 		A.F = *(ConstPtr<AFG>)fac;
 		request_lane(A.hv[7], A.hv[1], 0, A.winv);
-#ifdef HIBAG_ACCUM_STAMPS
-		stamp_t = __builtin_readcyclecounter();
-#endif
 		const int nb = be - bb;
 		for (int rel = 0;;) {
 			one_block(rel, A, Bn);
@@ -326,12 +271,6 @@ __global__ __launch_bounds__(ACCUM_WAVES * HIBAG_WAVE, ACCUM_OCC) void k_accum(H
 	// order): one kernel and its launch gap less on the step.
 	if (tile == 0 && ce == C) ensemble_scalars<8>(M, B, s, nullptr);      // (eight loads in flight: sixteen would set the kernel's register count)
 	}
-#ifdef HIBAG_ACCUM_STAMPS
-	__syncthreads();
-	if (threadIdx.x < ACCUM_STAMP_N)
-		atomicAdd(reinterpret_cast<unsigned long long *>(B.err_dev + 4) + 2000 + threadIdx.x, stamp_s[threadIdx.x]);
-	if (threadIdx.x == ACCUM_STAMP_N) atomicAdd(reinterpret_cast<unsigned long long *>(B.err_dev + 4) + 2000 + ACCUM_STAMP_N, (unsigned long long)(be_diag - bb_diag) * ACCUM_WAVES);
-#endif
 	if (ce < C) handover_post(flag, B.epoch, (uint32_t)ce, B.drop_post == 2 && blockIdx.x == 8 * n_whole);
 }
 

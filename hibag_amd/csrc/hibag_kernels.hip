@@ -45,13 +45,9 @@
 #include <algorithm>
 #include "hibag_device.h"
 #include "hibag_kernels.h"
-#include "hibag_ablation.h"
 
 #define NA_INTEGER (-2147483647 - 1)
 #define CH HIBAG_CHUNK
-#ifndef HIBAG_GATHER_DEPTH
-#define HIBAG_GATHER_DEPTH 1                // blocks of look-ahead of the haplotype-entry gathers
-#endif
 #define BLOCK_WAVES HIBAG_BLOCK_WAVES         // wavefronts per workgroup (each on its own work item; hibag_device.h)
 #define BLOCK_THREADS (BLOCK_WAVES * HIBAG_WAVE)
 #ifndef TOTAL_G
@@ -68,9 +64,6 @@
 #endif
 #ifndef HIBAG_TOT_OCC_MANY
 #define HIBAG_TOT_OCC_MANY 6
-#endif
-#ifndef TOTAL_OWN
-#define TOTAL_OWN false                     // true: pass 1 over prebuilt rows with four matrix instructions per block and NO lane swaps (walk_blocks, OWN) -- bit-identical, measured 2-5 % slower than two and sixteen swaps
 #endif
 #ifndef ACCUM_AHEAD
 #define ACCUM_AHEAD true                    // pass 2: the next group's table look-ups requested before this group is added up (-0.6 %, six registers; false: the wait right behind the look-ups)
@@ -136,20 +129,14 @@ void hibag_launch_bed_geno(const uint8_t *d_bed, int mode, size_t stride, int n_
 
 // resident workgroups of a kernel on the current device (0 = unknown)
 template <class F>
-static int resident_blocks(F kernel, int threads, size_t dyn_lds = 0)
+static int resident_blocks(F kernel, int threads)
 {
 	int per_cu = 0, cus = 0, dev = 0;
 	(void)hipGetDevice(&dev);
 	(void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-	if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, dyn_lds) != hipSuccess) return 0;
+	if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, 0) != hipSuccess) return 0;
 	return per_cu > 0 && cus > 0 ? per_cu * cus : 0;
 }
-
-#ifdef HIBAG_ABL2_LDSPAD                      // (timing ablation, hibag_ablation.h: pass 2 at fewer resident workgroups, same code)
-#define ACCUM_DYN_LDS HIBAG_ABL2_LDSPAD
-#else
-#define ACCUM_DYN_LDS 0
-#endif
 
 // chunks per item of the last rounds of passes 1 and 2 ("hand-overs"; HIBAG_TAIL_K=1: undivided items only).
 // A hand-over costs about as much as a tenth of a block list of the benchmark model, so 4 chunks there (2 and 8 measure 1-3 %
@@ -173,7 +160,7 @@ void hibag_query_slots(int total[4], int *accum)
 	total[1] = resident_blocks(k_total<false, HIBAG_TOT_OCC_MANY, 2>, BLOCK_THREADS);
 	total[2] = resident_blocks(k_total<true, HIBAG_TOT_OCC, 0>, BLOCK_THREADS);
 	total[3] = resident_blocks(k_total<true, HIBAG_TOT_OCC_MANY, 2>, BLOCK_THREADS);
-	*accum = resident_blocks(k_accum, ACCUM_WAVES * HIBAG_WAVE, ACCUM_DYN_LDS);
+	*accum = resident_blocks(k_accum, ACCUM_WAVES * HIBAG_WAVE);
 }
 
 void hibag_launch_total(const HibagModelView &M, const HibagBatchView &B, hipStream_t st, const HibagSideStream &side, bool vote)
@@ -214,15 +201,13 @@ void hibag_launch_total(const HibagModelView &M, const HibagBatchView &B, hipStr
 	// more items than resident workgroups: the last, incomplete round and the full round before it go in K chunks each
 	const unsigned n = gx * (unsigned)V.n_item;
 	// two rounds of the denser build's resident workgroups or more: six workgroups per CU, otherwise five (above)
-	static const int occ_env = getenv("HIBAG_TOT_OCC") ? atoi(getenv("HIBAG_TOT_OCC")) : 0;      // (diagnostic: 5 or 6)
 	const int sbase = (M.store_cells && !vote) ? 2 : 0;       // (the vote's build stores no cell sums: the occupancy figures of the non-storing one)
 	const int slots_many = M.slots_total[sbase + 1];
 	// (the denser build holds the one-step FP4 loop only: models with other work items always take the general one)
-	const bool many = M.all_fp4 && !split && (occ_env ? occ_env == HIBAG_TOT_OCC_MANY : (slots_many > 0 && n >= 2u * (unsigned)slots_many));
+	const bool many = M.all_fp4 && !split && slots_many > 0 && n >= 2u * (unsigned)slots_many;
 	const int slots = M.slots_total[sbase + (many ? 1 : 0)];
 	unsigned n_whole = n, rest = 0, stride = 8, K = 1;
-	static const int k1_env = getenv("HIBAG_TAIL_K1") ? std::max(1, std::min(64, atoi(getenv("HIBAG_TAIL_K1")))) : 0;     // (diagnostic: pass 1 only)
-	const int k_pass1 = (k1_env && B.tail_k == 0) ? k1_env : tail_chunks(B.tail_k, M.p1_blocks / std::max(M.n_classifier, 1));
+	const int k_pass1 = tail_chunks(B.tail_k, M.p1_blocks / std::max(M.n_classifier, 1));
 	// (the majority vote's record log is not handed over between chunks: its items stay whole)
 	if (!vote && k_pass1 > 1 && slots > 0 && n > (unsigned)slots) {
 		K = (unsigned)k_pass1;
@@ -268,7 +253,7 @@ void hibag_launch_accum(const HibagModelView &M, const HibagBatchView &B, hipStr
 		K = (unsigned)tail_chunks(B.tail_k, 0, 2);
 		n_whole = nx - (nx % sx + sx);
 	}
-	hipLaunchKernelGGL(k_accum, dim3(8 * (n_whole + K * (nx - n_whole))), dim3(ACCUM_WAVES * HIBAG_WAVE), ACCUM_DYN_LDS, st, M, B, (int)n_whole, (int)K);
+	hipLaunchKernelGGL(k_accum, dim3(8 * (n_whole + K * (nx - n_whole))), dim3(ACCUM_WAVES * HIBAG_WAVE), 0, st, M, B, (int)n_whole, (int)K);
 }
 
 void hibag_launch_vote(const HibagModelView &M, const HibagBatchView &B, int *d_best_cell, hipStream_t st)

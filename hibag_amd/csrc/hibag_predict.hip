@@ -107,13 +107,7 @@ void run_core(hibag_hip_model *m, HibagBatchView &B, int vote_method, double *d_
 	hibag_launch_total(m->view, B, st, m->side, vote_method == 2);
 	T.end(st);
 	debug_stage("pass 1", st);
-	// HIBAG_DEBUG_THRASH_MB=<mb> (measurement only, profiles/r06_notes.txt): overwrite that much scratch memory between the
-	// passes, so that pass 2 finds nothing of pass 1's stored sums in the L2s or the Infinity Cache -- what a schedule that keeps
-	// them cache-resident could gain at most is the difference to the run without.
-	static const long thrash_mb = getenv("HIBAG_DEBUG_THRASH_MB") ? atol(getenv("HIBAG_DEBUG_THRASH_MB")) : 0;
-	if (thrash_mb > 0 && m->ws_thrash.reserve((size_t)thrash_mb << 20) == 0)
-		(void)hipMemsetAsync(m->ws_thrash.p, 0x5a, (size_t)thrash_mb << 20, st);
-	T.begin(HIBAG_HIP_K_ACCUM, st, thrash_mb <= 0);
+	T.begin(HIBAG_HIP_K_ACCUM, st, true);
 	if (vote_method == 1) {
 		hibag_launch_accum(m->view, B, st);
 		debug_stage("pass 2 (accumulate)", st);
@@ -251,7 +245,7 @@ int staged_streams(hibag_hip_model *m, StagedStreams **out)
 {
 	StagedStreams *ss = &m->staged;
 	if (!m->staged_ready) {
-		if (!getenv("HIBAG_STAGED_NULL")) HIP_TRY(hipStreamCreateWithFlags(&ss->run, hipStreamNonBlocking));    // (diagnostic: the null stream)
+		HIP_TRY(hipStreamCreateWithFlags(&ss->run, hipStreamNonBlocking));
 		HIP_TRY(hipStreamCreateWithFlags(&ss->in, hipStreamNonBlocking));
 		HIP_TRY(hipStreamCreateWithFlags(&ss->out, hipStreamNonBlocking));
 		for (int i = 0; i < 2; i++) {
@@ -1006,18 +1000,11 @@ int hibag_hip_test_inject_handover_fault(hibag_hip_model *m, int pass)
 	return 0;
 }
 
-// Diagnostic builds of the kernels (-DHIBAG_ACCUM_STAMPS) sum clock differences in the tail of the model's error buffer
-// (entries 2000 .. of the list behind byte 16): read `n` of them and zero them.  All zero with the shipped kernels.
+// Kept for ABI compatibility: the kernel builds whose clock sums it read are gone, so it returns `n` zeros.
 int hibag_hip_test_read_diag(hibag_hip_model *m, unsigned long long *out, int n)
 {
 	if (!m || !out || n < 0 || n > 40) return hibag_fail(HIBAG_HIP_EINVAL, "bad arguments");
-	if (!m->ws_err.p) { for (int i = 0; i < n; i++) out[i] = 0; return 0; }
-	std::lock_guard<std::mutex> g(m->lock);
-	HIP_TRY(hipSetDevice(m->device));
-	HIP_TRY(hipDeviceSynchronize());
-	char *at = m->ws_err.as<char>() + 16 + 8 * 2000;
-	HIP_TRY(hipMemcpy(out, at, (size_t)n * 8, hipMemcpyDeviceToHost));
-	HIP_TRY(hipMemset(at, 0, (size_t)n * 8));
+	for (int i = 0; i < n; i++) out[i] = 0;
 	return 0;
 }
 

@@ -215,8 +215,8 @@ int64_t hibag_hip_model_handover_faults(const hibag_hip_model *m);
 /* Fault injection for the tests of the above: the next batch on the model drops the first hand-over of pass `pass`
  * (1 or 2; 0 = disarm) and uses a short time-out.  Not for production use. */
 int hibag_hip_test_inject_handover_fault(hibag_hip_model *m, int pass);
-/* Diagnostic kernel builds only (-DHIBAG_ACCUM_STAMPS): the clock sums of pass 2's block phases since the last call
- * (n <= 40 values; all zero with the shipped kernels). */
+/* Kept for ABI compatibility: writes n (<= 40) zeros to `out` and returns 0.  (It read the clock sums of diagnostic kernel
+ * builds that no longer exist.) */
 int hibag_hip_test_read_diag(hibag_hip_model *m, unsigned long long *out, int n);
 
 /* How classifier `classifier` of a finalized model computes its distances: *engine = HIBAG_HIP_ENGINE_VALU (bit logic +

@@ -40,5 +40,4 @@ if sub:
                              d[4][a:].data_ptr(), None, stream=st)
         torch.cuda.synchronize(dev)
     print(f"device-resident in sub-batches of {sub}: {med(resident_sub):.3f} ms")
-print(f"n={n}  fresh outputs {med(lambda: m.predict_raw(G, 1, want_dosage=True)):.3f} ms   reused outputs {med(reused):.3f} ms   device-resident {med(resident):.3f} ms"
-      f"   (HIBAG_STAGED_NULL={os.environ.get('HIBAG_STAGED_NULL')})")
+print(f"n={n}  fresh outputs {med(lambda: m.predict_raw(G, 1, want_dosage=True)):.3f} ms   reused outputs {med(reused):.3f} ms   device-resident {med(resident):.3f} ms")
