@@ -24,7 +24,7 @@ extern "C" {
 #define HIBAG_HIP_ABI_VERSION 7   /* 2: + PLINK BED entries, training driver; 3: + hibag_hip_predict_mapped[_device]; 4: + hibag_hip_model_stored_cells;
                                      5: + hibag_hip_model_status / _clear_status, hibag_hip_predict_multi, hibag_hip_model_replicate, hibag_hip_model_engine;
                                      7: + hibag_hip_predict_snp_major[_device], hibag_hip_trainer_set_shared, hibag_hip_train_set_thread_budget;
-                                        later, additive (no bump): + hibag_hip_predict_oob */
+                                        later, additive (no bump): + hibag_hip_predict_oob; + the LD entries (hibag_hip_ld_*) */
 
 /* error codes */
 #define HIBAG_HIP_OK          0
@@ -143,6 +143,39 @@ int hibag_hip_predict(hibag_hip_model *m, const int32_t *geno, int n_samp,
  * All pointers are host memory and required when n_samp > 0; one batched launch sequence, no second pass. */
 int hibag_hip_predict_oob(hibag_hip_model *m, const int32_t *geno, int n_samp, const int32_t *samp_num,
 	int32_t *H1, int32_t *H2, double *prob);
+
+/* ---- linkage disequilibrium: hlaGenoLD / hlaLDMatrix ----------------------
+ * r^2 = num^2 / (dx dy) from exact integer sums over the samples used (n, Sx, Sxx, Sy, Syy, Sxy; num = n Sxy - Sx Sy,
+ * dx = n Sxx - Sx^2, dy = n Syy - Sy^2, all int64, then one double rounding per operation); NaN where dx or dy is 0.
+ * The sums are int8 Gram matrices on the matrix cores (DESIGN.md "LD"). */
+typedef struct hibag_hip_ld_geno hibag_hip_ld_geno;      /* genotypes resident on the calling thread's device */
+
+/* Copies genotypes to the device selected by the calling thread and packs them there.
+ *   geno  int32 [n_snp][n_samp] (snp_major != 0) or [n_samp][n_snp] (snp_major == 0); 0/1/2, anything else is missing
+ * n_samp is at most 2^24 (EINVAL beyond: the formula above is exact in double up to there).  NULL on failure
+ * (hibag_hip_last_error says why).  Replaces the host matrix that R/HIBAG.R:1431-1443 and :1507 hand to cor(). */
+hibag_hip_ld_geno *hibag_hip_ld_geno_new(const int32_t *geno, int n_snp, int n_samp, int snp_major);
+void hibag_hip_ld_geno_free(hibag_hip_ld_geno *g);
+
+/* Per SNP the number of called genotypes and their sum: hlaLDMatrix's MAF filter (R/HIBAG.R:1468-1472, rowMeans). */
+int hibag_hip_ld_snp_counts(hibag_hip_ld_geno *g, int32_t *n_valid, int64_t *sum);
+
+/* hlaLDMatrix's cor(t(genotype), use = "na.or.complete")^2 (R/HIBAG.R:1507) over the SNPs snp_idx[0 .. n_idx):
+ * the samples used are those called at every one of them (*n_complete of them).  r2 is float64 [n_idx][n_idx],
+ * host memory; its diagonal is 1, and every entry is NaN when fewer than two samples are complete.  The result is
+ * made in row panels (HIBAG_LD_PANEL_ROWS rows if that is set, else about 64 MB each) copied through pinned buffers
+ * while the next panel is computed, so device memory does not grow with n_idx^2. */
+int hibag_hip_ld_matrix(hibag_hip_ld_geno *g, const int32_t *snp_idx, int n_idx, double *r2, int *n_complete);
+
+/* Event time in milliseconds of the Gram kernels of the handle's last hibag_hip_ld_matrix call (for measurements). */
+int hibag_hip_ld_gram_ms(hibag_hip_ld_geno *g, double *ms);
+
+/* hlaGenoLD (R/HIBAG.R:1425-1445): for every SNP j, ld[j] = the mean of the non-NaN r^2(j, a) over the alleles, summed in
+ * allele order (NaN if there is none), each r^2 over the samples with a genotype at j and both alleles known.
+ *   allele1 / allele2  int32 [n_samp]: 0-based indices into the caller's sorted allele list, HIBAG_HIP_NA_INTEGER = NA
+ *   r2_or_null         float64 [n_snp][n_allele], the single r^2 values (may be NULL) */
+int hibag_hip_ld_hla(hibag_hip_ld_geno *g, const int32_t *allele1, const int32_t *allele2, int n_allele,
+	double *ld, double *r2_or_null);
 
 /* Device-pointer form of the same call: every pointer is device memory on the
  * model's device, work is enqueued on `stream` (a hipStream_t, NULL = default
