@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the hlaPredict() hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
 
 Metric (BASELINE.json): hlaPredict() samples/sec (+ achieved HBM GB/s) on the
 10k-sample x 100-classifier HLA-B configuration.  A *step* is one pass of the
@@ -17,15 +17,20 @@ is device-resident (the PCIe-inclusive rate of the host-pointer entry is
           CLASSIFIERS on all the samples, merged by one RCCL all-reduce of the partial posterior sums per 25,000 samples.
           `--samples n` instead gives every rank its own n samples (weak scaling).
 
-Rank 0 prints ONE JSON line.  Besides the driver's fields it carries
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line:
+the driver's fields, the configuration, and per rank its samples, time and hand-over faults.  With --full it also carries
   roofline     : the dominant kernel against the HBM roof the metric names,
                  from HIP events recorded on the launch stream inside the timed
                  region (and, under "issue", the SIMD time per wavefront-pair
                  against the FP64 + matrix-core issue floor measured in this process, the ceiling
-                 that actually binds this path -- DESIGN.md section 5);
+                 that actually binds this path -- DESIGN.md section 5); the
+                 other kernels' times come from up to ten further steps;
   cpu_baseline : the AVX2 + threads CPU port of the reference's kernel
                  (oracle/, kind "port") timed on this box's host cores on a
-                 bounded sample of the same workload (rank 0, N = 1 only).
+                 bounded sample of the same workload (rank 0, N = 1 only);
+and the calls' accuracy against the synthetic truth, the protocol / host- and API-inclusive rates and the other
+configurations (N = 1), the classifier-sharded leg (N > 1) and the check of a classifier-sharded run against the unsharded
+one.  --no-cpu-baseline and --no-extras leave parts of that out.  The timed steps are the same with or without --full.
 
 --dump-outputs DIR writes what the last timed step computed, the arrays a caller of the timed path receives, as
 DIR/<name>.npy in float64, one row per sample, with the indices of those samples in DIR/sample_index.npy and the place
@@ -111,13 +116,18 @@ def main():
     ap.add_argument("--shape", default=SHAPE)
     ap.add_argument("--prob", action="store_true", help="also return the full posterior matrix (type='response+prob')")
     ap.add_argument("--vote", choices=("prob", "majority"), default="prob", help="hlaPredict(vote=): averaged posteriors (default) or majority vote")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline line, measure and check everything else: roofline and per-kernel times, call "
+                         "accuracy, the protocol / host- and API-inclusive rates, other configurations, the CPU baseline, the "
+                         "classifier-sharded leg and check (takes a minute or more)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-wide", action="store_true", help="diagnostic: drop the one 100-SNP classifier of the synthetic model")
     ap.add_argument("--shard", choices=("samples", "classifiers"), default="samples",
                     help="multi-GPU decomposition: every rank its own samples (default, no collective), or every rank a "
                          "slice of the classifiers on the SAME samples, merged by one RCCL all-reduce of the partial "
                          "posterior sums per step (BASELINE config 3's 'RCCL posterior merge'; strong scaling)")
-    ap.add_argument("--no-extras", action="store_true", help="skip host_inclusive / other_configs (profiling runs)")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: skip host_inclusive / other_configs and the classifier-sharded leg (profiling runs)")
     ap.add_argument("--launcher", choices=("ranks", "threads"), default="ranks",
                     help="--gpus N > 1: one process per GPU under torch.distributed (default; RCCL rendezvous), or ONE process "
                          "with one host thread per GPU through the C ABI (hibag_hip_model_replicate + the device entry), "
@@ -256,13 +266,13 @@ def main():
             dist.barrier()
         torch.cuda.synchronize(dev)
 
-    def timed(fn, warmup, steps, mdl, after=None):
+    def timed(fn, warmup, steps, mdl, after=None, kernels=True):
         """W untimed warm-up steps, then exactly K timed steps between fences.  Inside the timed region HIP events bracket
         the DOMINANT kernel only (the roofline's `avg_launch_ms` is measured live there, as the contract asks): an event
         record is a packet of its own on the queue, and five of them per step cost 2 % of it.  Which kernel dominates is
-        found in two untimed steps before the warm-up; the other kernels' times come from up to ten more steps with every
-        kernel class bracketed, AFTER the timed region.  `after` is called between the two, when the output buffers still
-        hold what the last timed step wrote."""
+        found in two untimed steps before the warm-up; with `kernels` the other kernels' times come from up to ten more
+        steps with every kernel class bracketed, AFTER the timed region (without, only the dominant kernel's is returned).
+        `after` is called between the two, when the output buffers still hold what the last timed step wrote."""
         mdl.set_timing(True); mdl.reset_timing()
         for _ in range(2):
             fn()
@@ -284,18 +294,20 @@ def main():
         tm_dom = mdl.get_timing()
         if after is not None:
             after()
-        extra = max(1, min(steps, 10))
-        mdl.set_timing(True); mdl.reset_timing()
-        for _ in range(extra):
-            fn()
-        fence()
-        tm_all = mdl.get_timing()
+        tm = {dom_k: tm_dom[dom_k]}
+        if kernels:
+            extra = max(1, min(steps, 10))
+            mdl.set_timing(True); mdl.reset_timing()
+            for _ in range(extra):
+                fn()
+            fence()
+            tm_all = mdl.get_timing()
+            # per kernel (summed ms over `steps` launches, launches): the dominant one as measured in the timed region, the
+            # others scaled from the steps behind it
+            tm = {k: (v[0] / max(v[1], 1) * steps, steps) for k, v in tm_all.items()}
+            tm[dom_k] = tm_dom[dom_k]
+            timed.events = f"timed region: HIP events around k_{dom_k} only; other kernels from {extra} further steps"
         mdl.set_timing(False)
-        # per kernel (summed ms over `steps` launches, launches): the dominant one as measured in the timed region, the others
-        # scaled from the steps behind it
-        tm = {k: (v[0] / max(v[1], 1) * steps, steps) for k, v in tm_all.items()}
-        tm[dom_k] = tm_dom[dom_k]
-        timed.events = f"timed region: HIP events around k_{dom_k} only; other kernels from {extra} further steps"
         if world > 1:
             t = torch.tensor([dt_], dtype=torch.float64, device=dev)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -308,7 +320,8 @@ def main():
         outs = zip(OUTPUT_NAMES, (d_h1, d_h2, d_prob, d_match, d_dos, d_pp))
         last.update({k: t.cpu().numpy() for k, t in outs if t is not None})
 
-    dt, timing = timed(step, args.warmup, args.steps, model, after=keep_last_step if args.dump_outputs else None)
+    dt, timing = timed(step, args.warmup, args.steps, model, after=keep_last_step if args.dump_outputs else None,
+                       kernels=args.full)
     dt_local = timed.local_dt
     faults = {"timed_model": int(model.handover_faults())}
 
@@ -324,12 +337,59 @@ def main():
         if rank == 0:
             write_dump(args.dump_outputs, parts)
 
+    value = n_total * args.steps / dt
+    pair_evals = model_obj.pair_evals_per_sample()
+    out = {
+        "metric": "hlaPredict() samples/sec, 10k samples x 100-classifier HLA-B",
+        "value": value, "unit": "samples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": scaling,
+        "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+        "config": {"workload": workload_text(args, model_obj, n, n_total, world, strong or by_classifier),
+                   "samples_per_gpu": n, "samples_per_step": n_total,
+                   "parallelism": (f"classifier-sharded x{world} ({len(sub.classifiers)} of {len(model_obj.classifiers)} classifiers on this rank; "
+                                   f"one RCCL all-reduce of {allreduce_bytes} bytes per {CFG3_SLICE} samples)"
+                                   if by_classifier else f"sample-sharded x{world} (contiguous slices, no collective)"),
+                   "kernel_target": target,
+                   "engine": os.environ.get("HIBAG_ENGINE", "mfma") + " (FP4 / int8 MFMA distances + FP64 VALU accumulation in reference order)"},
+        "pair_evals_per_s": value * pair_evals,
+        "rccl_ranks": rccl_ranks,
+    }
+    if dry:
+        out["dry_run"] = (f"{world} ranks sharing {torch.cuda.device_count()} device(s), collectives over gloo through host "
+                          "staging: a rehearsal of the orchestration, not a measurement")
+        out["rccl_ranks"] = None
+
+    def ranks_seen(**kernels_ms):
+        """What every rank saw: the first real multi-GPU run has to diagnose itself from its one line."""
+        mine = dict({"rank": rank, "local_rank": local_rank, "device": int(model.device()),
+                     "devices_visible": int(hibag_amd._lib.lib().hibag_hip_device_count()),
+                     "samples": int(n), "ms_per_step": round(dt_local / args.steps * 1e3, 4)},
+                    **kernels_ms, handover_faults=int(model.handover_faults()))
+        if world == 1:
+            return [mine]
+        seen = [None] * world
+        dist.all_gather_object(seen, mine)
+        return seen
+
+    def emit():
+        # hand-overs that failed (and were repaired or reported) in any model this run timed: a fault costs a repeated batch,
+        # so a non-zero count explains a slow line -- it must be 0
+        out["handover_faults"] = faults
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+
+    if not args.full:
+        out["ranks"] = ranks_seen()
+        emit()
+        return
+
+    # ---- --full: everything else the line carries ----
     # sanity on the timed outputs: calls of samples drawn from the model
     h1 = d_h1.cpu().numpy(); h2 = d_h2.cpu().numpy()
     call_acc = float(np.mean((h1 == truth[:, 0]) & (h2 == truth[:, 1])))
-
-    value = n_total * args.steps / dt
-    pair_evals = model_obj.pair_evals_per_sample()
     pe_rank = sub.pair_evals_per_sample() if by_classifier else pair_evals      # what one rank's kernels evaluate
 
     # ---- roofline of the dominant kernel (HIP events on the launch stream) ----
@@ -482,37 +542,8 @@ def main():
             pass
         g2 = o2 = None
 
-    # what every rank saw: the first real multi-GPU run has to diagnose itself from its one line
-    mine = {"rank": rank, "local_rank": local_rank, "device": int(model.device()), "devices_visible": int(hibag_amd._lib.lib().hibag_hip_device_count()),
-            "samples": int(n), "ms_per_step": round(dt_local / args.steps * 1e3, 4),
-            "k_total_ms": round(ms1, 4), "k_accum_ms": round(ms2, 4), "handover_faults": int(model.handover_faults())}
-    ranks_seen = [mine]
-    if world > 1:
-        ranks_seen = [None] * world
-        dist.all_gather_object(ranks_seen, mine)
-
-    out = {
-        "metric": "hlaPredict() samples/sec, 10k samples x 100-classifier HLA-B",
-        "value": value, "unit": "samples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": scaling,
-        "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-        "config": {"workload": workload_text(args, model_obj, n, n_total, world, strong or by_classifier),
-                   "samples_per_gpu": n, "samples_per_step": n_total,
-                   "parallelism": (f"classifier-sharded x{world} ({len(sub.classifiers)} of {len(model_obj.classifiers)} classifiers on this rank; "
-                                   f"one RCCL all-reduce of {allreduce_bytes} bytes per {CFG3_SLICE} samples)"
-                                   if by_classifier else f"sample-sharded x{world} (contiguous slices, no collective)"),
-                   "kernel_target": target,
-                   "engine": os.environ.get("HIBAG_ENGINE", "mfma") + " (FP4 / int8 MFMA distances + FP64 VALU accumulation in reference order)"},
-        "pair_evals_per_s": value * pair_evals,
-        "call_accuracy_vs_truth": call_acc,
-        "rccl_ranks": rccl_ranks,
-        "ranks": ranks_seen,
-        "roofline": roofline,
-    }
-    if dry:
-        out["dry_run"] = (f"{world} ranks sharing {torch.cuda.device_count()} device(s), collectives over gloo through host "
-                          "staging: a rehearsal of the orchestration, not a measurement")
-        out["rccl_ranks"] = None
+    out["ranks"] = ranks_seen(k_total_ms=round(ms1, 4), k_accum_ms=round(ms2, 4))
+    out.update({"call_accuracy_vs_truth": call_acc, "roofline": roofline})
     if shard_check is not None:
         out["classifier_shard_check"] = shard_check
     if sharded_line is not None:
@@ -548,16 +579,7 @@ def main():
         out["cpu_baseline"] = cpu_baseline(model_obj, geno, h1, h2)
         out["speedup_vs_cpu_baseline"] = value / out["cpu_baseline"]["value"]
         out["speedup_vs_one_cpu_thread"] = value / out["cpu_baseline"]["one_thread"]["value"]
-
-    # hand-overs that failed (and were repaired or reported) in any model this run timed: a fault costs a repeated batch,
-    # so a non-zero count explains a slow line -- it must be 0
-    out["handover_faults"] = faults
-
-    if rank == 0:
-        print(json.dumps(out), flush=True)
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
+    emit()
 
 
 def workload_text(args, model_obj, n, n_total, world, shared):
@@ -1227,7 +1249,6 @@ def main_threads(args):
         dt = time.perf_counter() - t0
         if args.dump_outputs:
             dump_outputs(args.dump_outputs, {k: got[k] for k in OUTPUT_NAMES if got.get(k) is not None})
-        ref = first.predict_raw(geno[:10_000], 1, want_dosage=False, want_prob=False)
         out = {
             "metric": "hlaPredict() samples/sec, 10k samples x 100-classifier HLA-B",
             "value": n * steps / dt, "unit": "samples/s", "n_gpus": N, "steps": steps, "warmup": args.warmup,
@@ -1242,16 +1263,19 @@ def main_threads(args):
                        "kernel_target": target,
                        "launcher": "threads: one process, the calling thread drives every device (hibag_hip_shard_group_predict)"},
             "pair_evals_per_s": n * steps / dt * pair_evals,
-            "call_accuracy_vs_truth": float(np.mean((got["h1"] == truth[:, 0]) & (got["h2"] == truth[:, 1]))),
             "rccl_ranks": grp.ranks, "rccl_allreduces": grp.allreduces,
             "rccl_version_code": int(hibag_amd._lib.lib().hibag_hip_rccl_version()),
-            "classifier_shard_check": {"calls_identical_to_unsharded": bool(np.array_equal(ref["h1"], got["h1"][:10_000]) and
-                                                                            np.array_equal(ref["h2"], got["h2"][:10_000])),
-                                       "max_rel_dev_prob_vs_unsharded": float(np.nanmax(np.abs(got["prob"][:10_000] - ref["prob"]) /
-                                                                                        np.maximum(np.abs(ref["prob"]), 1e-300))),
-                                       "tolerance": 1e-10},
             "handover_faults": {"shards": int(sum(m.handover_faults() for m in grp.shards))},
         }
+        if args.full:
+            ref = first.predict_raw(geno[:10_000], 1, want_dosage=False, want_prob=False)
+            out["call_accuracy_vs_truth"] = float(np.mean((got["h1"] == truth[:, 0]) & (got["h2"] == truth[:, 1])))
+            out["classifier_shard_check"] = {
+                "calls_identical_to_unsharded": bool(np.array_equal(ref["h1"], got["h1"][:10_000]) and
+                                                     np.array_equal(ref["h2"], got["h2"][:10_000])),
+                "max_rel_dev_prob_vs_unsharded": float(np.nanmax(np.abs(got["prob"][:10_000] - ref["prob"]) /
+                                                                 np.maximum(np.abs(ref["prob"]), 1e-300))),
+                "tolerance": 1e-10}
         print(json.dumps(out), flush=True)
         grp.close(); first.close()
         return
@@ -1296,7 +1320,8 @@ def main_threads(args):
                 lasts[r] = {k: t.cpu().numpy() for k, t in zip(OUTPUT_NAMES, (h1, h2, pr, mt, ds))}
             if m.status() != 0:
                 raise RuntimeError("a launch reported a failed hand-over")
-            accs[r] = float(np.mean((h1.cpu().numpy() == truth[:, 0]) & (h2.cpu().numpy() == truth[:, 1])))
+            if args.full:
+                accs[r] = float(np.mean((h1.cpu().numpy() == truth[:, 0]) & (h2.cpu().numpy() == truth[:, 1])))
         except Exception as e:                        # noqa: BLE001
             errs.append(repr(e))
             bar.abort()
@@ -1322,9 +1347,11 @@ def main_threads(args):
                    "launcher": f"threads: one process, one host thread and one model replica per GPU through the C ABI "
                                f"(devices {devices})"},
         "pair_evals_per_s": total * args.steps / dt * pair_evals,
-        "call_accuracy_vs_truth": float(np.mean(accs)), "rccl_ranks": None,
+        "rccl_ranks": None,
         "handover_faults": {"replicas": int(sum(m.handover_faults() for m in models))},
     }
+    if args.full:
+        out["call_accuracy_vs_truth"] = float(np.mean(accs))
     print(json.dumps(out), flush=True)
     for m in models[1:]:
         m.close()

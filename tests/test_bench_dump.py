@@ -1,7 +1,8 @@
 """bench.py --dump-outputs: what the last timed step computed, as DIR/<name>.npy in float64 with the samples they hold in
 DIR/sample_index.npy -- every sample, or, above 64 MB in all, a fixed, seeded sample of them (the same rows from every
 output) -- and every NaN / inf recorded in DIR/nonfinite.npy; the shares of several ranks merge into the same dump; and,
-on the GPU, the very outputs the oracle computes for the benchmark's seeded inputs."""
+on the GPU, the very outputs the oracle computes for the benchmark's seeded inputs, and what a plain line holds against one
+with --full."""
 
 import os
 import subprocess
@@ -123,3 +124,30 @@ def test_bench_dump_equals_the_oracle(tmp_path, oracle):
     assert np.array_equal(got.pop("sample_index"), np.arange(len(geno)))
     for k, v in got.items():                                  # every sample, the underflowing ones included
         assert np.array_equal(v, np.asarray(want[k], np.float64), equal_nan=True), k
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("extra", [[], ["--full", "--no-extras", "--no-cpu-baseline"]])
+def test_bench_line_plain_and_full(extra):
+    """A plain run's line is the headline figure and its configuration; --full adds the roofline of the same timed steps
+    and the calls' accuracy (--no-extras / --no-cpu-baseline keep the other legs out)."""
+    import json
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1"] + extra,
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600, stdin=subprocess.DEVNULL)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["metric"] == "hlaPredict() samples/sec, 10k samples x 100-classifier HLA-B"
+    assert (d["unit"], d["higher_is_better"], d["dtype"], d["steps"], d["warmup"]) == ("samples/s", True, "f64", 3, 1)
+    assert d["value"] > 0 and d["value"] * d["ms_per_step"] * 1e-3 == pytest.approx(bench.SAMPLES_PER_GPU, rel=1e-9)
+    assert all(v == 0 for v in d["handover_faults"].values())
+    moved = {"roofline", "call_accuracy_vs_truth", "protocol", "host_inclusive", "api_inclusive", "host_inclusive_100k",
+             "other_configs", "cpu_baseline", "classifier_shard_check", "classifier_sharded"}
+    if not extra:
+        assert not moved & set(d)
+        assert "k_total_ms" not in d["ranks"][0]
+    else:
+        assert moved & set(d) == {"roofline", "call_accuracy_vs_truth"}
+        assert d["call_accuracy_vs_truth"] > 0.99
+        assert d["roofline"]["bound"] == "simd-issue" and set(d["roofline"]["kernels_ms_per_step"]) >= {"total", "accum"}

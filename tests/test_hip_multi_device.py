@@ -118,7 +118,7 @@ def test_bench_over_two_real_ranks(extra):
     collectives over RCCL -- `rccl_ranks` counts them with a real all-reduce."""
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k != "HIBAG_BENCH_DRY_RANKS"}
-    p = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"] + extra,
+    p = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline"] + extra,
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900, stdin=subprocess.DEVNULL)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]

@@ -131,7 +131,7 @@ def test_bench_two_rank_rehearsal_on_one_device(extra, tmp_path, oracle):
     env = dict(os.environ, HIBAG_BENCH_DRY_RANKS="1")
     dump = str(tmp_path / "dump")
     p = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                        "--dump-outputs", dump] + extra,
+                        "--full", "--dump-outputs", dump] + extra,
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600, stdin=subprocess.DEVNULL)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]

@@ -25,7 +25,7 @@ run cfg2_vote2 --vote majority
 run cfg4 --shape hla-drb1 --samples 4096 --steps 10 --warmup 2
 fi
 cd $R
-timeout 1200 python3 bench.py > $out/bench.json 2> $out/bench.log
+timeout 1200 python3 bench.py --full > $out/bench.json 2> $out/bench.log
 tail -c 1200 $out/bench.json
 if [ -z "${PROFILES_ONLY_CFG2:-}" ]; then
 cd /tmp
