@@ -214,7 +214,7 @@ struct HibagModelView {
 	int p1_prebuilt;             // 1: the pass-1 lists (k_total's FP4 walk) have rows too
 	const uint32_t *ctile;       // [C][n_tile][8]: everything pass 2 needs per (classifier, tile) in one s_load_dwordx8:
 	                             // {engine | k << 2 | #listed cells << 8 | (K steps - 1) << 13 | bt_row << 16    (k: SNPs of the LAST K step), dword offset of the first haplotype-table entry,
-	                             //  pair list dword offset lo/hi, #blocks, first stored row | #stored cells << 27, row list lo/hi}
+	                             //  0, 0, 0, first stored row | #stored cells << 27, row list lo/hi}  (words 1-4: read by no kernel)
 	                             // row list: 4 bits per cell -- the listed (evaluated) cells in closing order, then the stored ones
 
 	// stored cells: rows of HibagBatchView::cells.  Evaluating a haplotype pair again in pass 2 costs ~0.25 ps per sample,

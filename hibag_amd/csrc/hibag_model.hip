@@ -8,8 +8,6 @@
 
 namespace hibag_detail {
 
-
-
 // The mutation/error weights exp(d*log(1e-5)), TAB[0]=1, non-finite -> 0:
 // the same expression, evaluated by the host libm like the reference does in
 // its static initialiser (src/LibHLA.cpp:166-183).
@@ -190,7 +188,7 @@ int append_pair_blocks(const int *st, int n_hla, int h1, int h2, int p0, int n_c
 // `cap`: cells per tile at most (<= HIBAG_TILE, what a wavefront of pass 2 has LDS rows for).  Pass 2's parallelism is
 // (groups of 64 samples) x (tiles): a model of few alleles cut into tiles of fifteen leaves most of the device idle -- the
 // reference's bundled HLA-A model, 14 alleles = 105 cells = 7 tiles, made 1,100 wavefronts of a 10,000-sample batch for
-// 1,024 SIMDs that hold five each, and pass 2 took 1.7 x pass 1 -- so such a model gets smaller tiles (tile_cap below).
+// 1,024 SIMDs that hold five each, and pass 2 took 1.7 x pass 1 -- so such a model gets smaller tiles (plan_tiles).
 void build_tiles(int P, const std::vector<uint64_t> &cell_work, std::vector<int> &tile_p0, std::vector<int> &tile_n, int cap)
 {
 	uint64_t total = 0;
@@ -219,368 +217,394 @@ void build_tiles(int P, const std::vector<uint64_t> &cell_work, std::vector<int>
 	}
 }
 
-int finalize_model(hibag_hip_model *m)
-{
-	if (m->finalized) return hibag_fail(HIBAG_HIP_ESTATE, "model already finalized");
-	HIP_TRY(hipSetDevice(m->device));
-	const int C = (int)m->cls.size(), nh = m->n_hla, S = m->n_snp;
-	const int P = nh * (nh + 1) / 2;
+// The overrides finalize_model honours, read from the environment at every finalize (the tests change them between models).
+struct FinalizeOptions {
+	enum Pass2 { AUTO, STREAM, HYBRID, RECOMPUTE } pass2 = AUTO;   // HIBAG_PASS2: which cell sums pass 1 stores (plan_store)
+	uint64_t store_above = 12;       // HIBAG_STORE_PAIRS: cells of more haplotype pairs are stored (plan_store)
+	double prebuilt_mb = 128;        // HIBAG_PREBUILT_MB: prebuilt rows for the pass-1 lists below this size (plan_parow)
+	FinalizeOptions()
+	{
+		if (const char *e = getenv("HIBAG_PASS2"))
+			pass2 = !strcmp(e, "stream") ? STREAM : !strcmp(e, "hybrid") ? HYBRID : !strcmp(e, "recompute") ? RECOMPUTE : AUTO;
+		if (const char *e = getenv("HIBAG_STORE_PAIRS")) store_above = (uint64_t)std::max(0, atoi(e));
+		if (const char *e = getenv("HIBAG_PREBUILT_MB")) prebuilt_mb = atof(e);
+	}
+};
 
-	std::vector<int> n_snp_c(C), nwp(C), snp_off(C), mask_row(C), c_order(C), snp_index,
-		snp_weight(std::max(S, 1), 0);
-	std::vector<uint64_t> stream_off(std::max(C, 1), 0), cell_work(P, 0);
-	std::vector<uint32_t> stream;
-	// per classifier: records (haplotype pairs) of every cell, and 4-record chunks of every cell
-	std::vector<std::vector<uint32_t>> cell_chunks(C), cell_pairs(C);
-	std::vector<std::vector<int>> starts(C);
-	std::vector<int> engine(std::max(C, 1), 0), bt_row(std::max(C, 1), 0), cls_nblk(std::max(C, 1), 0), n_step(std::max(C, 1), 1);
-	std::vector<int> &mfma_nkb = engine;                 // (non-zero = a matrix engine)
-	std::vector<uint32_t> hap, hap_off(std::max(C, 1), 0);
-	std::vector<int64_t> pairs(C);
-	int bt_rows = 0;
-	int rows = 0;
-	m->pair_evals = 0;
-	int64_t valu_pairs = 0;
-	const bool allow_wide = !(getenv("HIBAG_PASS2") && !strcmp(getenv("HIBAG_PASS2"), "recompute"));
-	for (int c = 0; c < C; c++) {
+// The kernels' tables and scalars, built without a HIP call by the plan_* stages (trailing comments: which), then uploaded.
+struct ModelLayout {
+	struct ClassifierPlan {                 // what the stages keep per classifier besides the kernels' arrays
+		std::vector<int> st;                    // [n_hla + 1] first haplotype of every allele
+		std::vector<uint32_t> chunks, npairs;   // [P] 4-record chunks and haplotype pairs (matrix engines only) of every cell
+		std::vector<uint8_t> stored;            // [P] pass 1 stores the cell's sum
+		int64_t pairs = 0;                      // haplotype pairs of the classifier
+	};
+	struct SlotRange { size_t first, n; int c; };   // which classifier's haplotype table the slots of plist[first, first + n) index
+	int C, nh, S, P;
+	std::vector<ClassifierPlan> cp;
+	std::vector<int> n_snp_c, nwp, snp_off, mask_row, c_order, snp_index, snp_weight, engine, bt_row, cls_nblk, n_step;   // plan_classifiers
+	std::vector<uint64_t> stream_off, cell_work;
+	std::vector<uint32_t> stream, hap, hap_off;
+	int rows = 0, bt_rows = 0;
+	int64_t pair_evals = 0;
+	std::vector<int> tile_p0, tile_n, tile_h1, tile_h2;      // plan_tiles; tile_h1, tile_h2: (h1, h2) of every tile's first cell
+	int n_tile = 0, store_mode = 0;                          // store_mode: plan_store
+	std::vector<uint32_t> cls_cnt, cls_cell, tile_meta, tile_k0, tile_nlist, tile_nstored;   // plan_cell_lists
+	std::vector<uint64_t> tile_jpack;
+	std::vector<int> cls_off, cls_n, n_stored_c;             // n_stored_c: cells of the classifier pass 1 stores in mode 2
+	int64_t second_pass_pairs = 0;
+	std::vector<int> item, item_whole, split_row, split_cls, wide_cls;   // plan_work_items
+	double split_heavy_ns = 0, split_rest_ns = 0;
+	std::vector<uint32_t> plist, ehdr, etile_cstart, blk_close;          // plan_pair_lists
+	std::vector<uint64_t> etile_blk0, blk_off, wseg_off;
+	std::vector<SlotRange> slot_ranges;
+	std::vector<int> cell_row, wseg, wide_scan;             // wide_scan: the classifiers of several K steps whose total k_total_scan forms
+	uint64_t estream_blocks = 0, p1_base = 0;
+	long long p1_blocks = 0;
+	std::vector<double> pfac;                                // plan_factors, plan_parow, plan_ctile
+	std::vector<uint32_t> phdr, parow, ctile;
+	size_t parow_blocks = 0;
+	bool p1_prebuilt = false;
+	explicit ModelLayout(const hibag_hip_model *m)
+		: C((int)m->cls.size()), nh(m->n_hla), S(m->n_snp), P(nh * (nh + 1) / 2), cp(C), n_snp_c(C), nwp(C), snp_off(C), mask_row(C),
+		  c_order(C), snp_weight(std::max(S, 1), 0), engine(std::max(C, 1), 0), bt_row(std::max(C, 1), 0), cls_nblk(std::max(C, 1), 0),
+		  n_step(std::max(C, 1), 1), stream_off(std::max(C, 1), 0), cell_work(P, 0), hap_off(std::max(C, 1), 0) {}
+	// Pass 2 evaluates the pairs of one-step FP4 classifiers only (k_accum's block stream); a classifier on any other engine
+	// -- int8 (29..32 SNPs), FP4 in several K steps, VALU -- has all its cells stored by pass 1 and read back.
+	bool evaluates(int c) const { return engine[c] == HIBAG_ENGINE_FP4 && n_step[c] == 1; }
+	bool stored_big(int c, int p) const { return store_mode == 2 && cp[c].stored[p] != 0; }   // mode 2: pass 2 reads the cell's sum
+};
+
+// Appends the table entry {ff, f} of haplotype i (-1: the all-zero padding entry) of a matrix-engine classifier to `hap`.
+void append_hap_entry(const HostClassifier &k, int engine, int steps, double ff, int i, double f, std::vector<uint32_t> &hap)
+{
+	const bool fp4 = engine == HIBAG_ENGINE_FP4;
+	// bits of a haplotype: SNPs [lo, lo + 32) of its 128-bit string
+	auto window = [&](int i, int lo) -> uint32_t {
+		if (i < 0) return 0u;
+		const unsigned __int128 v = ((unsigned __int128)k.bits[2 * (size_t)i + 1] << 64) | k.bits[2 * (size_t)i];
+		return (uint32_t)(v >> lo);
+	};
+	uint32_t w[12 + 4 * (HIBAG_FP4_MAX_STEPS - 1)] = {0};
+	int n = 0;
+	if (fp4 && steps == 1) {       // two nibble images, both ADDED by the kernel (K layout in hibag_device.h):
+		// the "sum" image has nibble s = 2 (the e2m1 code of 1.0) where bit s is set, the "pair" image the code 3 (1.5) --
+		// two of them make the code 6 (4.0), so the sum of two pair images is w = 0 / 1.5 / 4 for 0 / 1 / 2 set bits
+		const uint32_t bits = window(i, 0);
+		for (int sb = 0; sb < 32; sb++) {
+			w[sb >> 3] |= ((bits >> sb) & 1u) << (4 * (sb & 7) + 1);
+			w[4 + (sb >> 3)] |= (((bits >> sb) & 1u) * 3u) << (4 * (sb & 7));
+		}
+		if (i >= 0) {
+			// ... plus the A-row constants of the offset digits at nibbles k, k + 1: each image carries half of each (sum
+			// image: codes 1 and 3, 0.5 + 0.5 = 1 and 3 + 3 = code 6 = 4; pair image: 3 and 3 -> 4, 4).  (Not the padding
+			// entry: its rows must stay zero.)
+			const int ks = k.n_snp;
+			for (int q = 0; q < 2; q++) {
+				const int nib = ks + q;
+				w[nib >> 3] |= (q == 0 ? 1u : 3u) << (4 * (nib & 7));
+				w[4 + (nib >> 3)] |= 3u << (4 * (nib & 7));
+			}
+		}
+		n = 8;
+	} else if (fp4) {              // nibble s = 2 (the e2m1 code of 1.0) where bit s is set
+		const uint32_t bits = window(i, 0) & ((1u << HIBAG_FP4_STEP_SNPS) - 1);
+		for (int sb = 0; sb < 32; sb++) w[sb >> 3] |= ((bits >> sb) & 1u) << (4 * (sb & 7) + 1);
+		n = 4;
+	} else {                       // byte s = 1 where bit s is set
+		const uint32_t bits = window(i, 0);
+		for (int sb = 0; sb < 32; sb++) w[sb >> 2] |= ((bits >> sb) & 1u) << (8 * (sb & 3));
+		n = 8;
+	}
+	memcpy(&w[n], &ff, sizeof(double)); memcpy(&w[n + 2], &f, sizeof(double));
+	n += 4;
+	for (int j = 1; j < steps; j++, n += 4) {      // further K steps: the next 28 SNPs each
+		const uint32_t bits = window(i, HIBAG_FP4_STEP_SNPS * j) & ((1u << HIBAG_FP4_STEP_SNPS) - 1);
+		for (int sb = 0; sb < 32; sb++) w[n + (sb >> 3)] |= ((bits >> sb) & 1u) << (4 * (sb & 7) + 1);
+	}
+	hap.insert(hap.end(), w, w + n);
+}
+
+// Stage 1, per classifier: engine, rows, allele starts, the cells' pairs and chunks, its table entries or pair records.
+int plan_classifiers(const hibag_hip_model *m, const FinalizeOptions &opt, ModelLayout &L)
+{
+	const int nh = L.nh, P = L.P;
+	for (int c = 0; c < L.C; c++) {
 		const HostClassifier &k = m->cls[c];
+		ModelLayout::ClassifierPlan &cp = L.cp[c];
 		const int H = (int)k.freq.size();
-		n_snp_c[c] = k.n_snp;
-		nwp[c] = round_nwp((3 * k.n_snp + 31) / 32);
-		snp_off[c] = (int)snp_index.size();
-		for (int v : k.snpidx) { snp_index.push_back(v); snp_weight[v]++; }
-		if (k.snpidx.empty()) snp_index.insert(snp_index.end(), (size_t)k.n_snp, 0);
-		mask_row[c] = rows;
-		rows += 2 * nwp[c];
-		std::vector<int> &st = starts[c];
-		st.assign(nh + 1, 0);
-		for (int i = 0; i < H; i++) st[k.hla[i] + 1]++;
-		for (int h = 0; h < nh; h++) st[h + 1] += st[h];
+		L.n_snp_c[c] = k.n_snp;
+		L.nwp[c] = round_nwp((3 * k.n_snp + 31) / 32);
+		L.snp_off[c] = (int)L.snp_index.size();
+		for (int v : k.snpidx) { L.snp_index.push_back(v); L.snp_weight[v]++; }
+		if (k.snpidx.empty()) L.snp_index.insert(L.snp_index.end(), (size_t)k.n_snp, 0);
+		L.mask_row[c] = L.rows;
+		L.rows += 2 * L.nwp[c];
+		cp.st.assign(nh + 1, 0);
+		for (int i = 0; i < H; i++) cp.st[k.hla[i] + 1]++;
+		for (int h = 0; h < nh; h++) cp.st[h + 1] += cp.st[h];
 		// matrix-core engines: at most 112 SNPs; table indices: first haplotype < 2H + 1 in 16 bits, second < H + 1 in 14
-		engine[c] = (m->use_mfma && H < 16384) ? HIBAG_ENGINE_OF(k.n_snp, m->use_fp4) : HIBAG_ENGINE_VALU;
+		L.engine[c] = (m->use_mfma && H < 16384) ? HIBAG_ENGINE_OF(k.n_snp, m->use_fp4) : HIBAG_ENGINE_VALU;
 		// (several K steps need their cells stored: not with pass 2 forced to evaluate every pair)
-		if (engine[c] == HIBAG_ENGINE_FP4 && k.n_snp > HIBAG_FP4_MAX_SNPS && !allow_wide) engine[c] = HIBAG_ENGINE_VALU;
-		n_step[c] = HIBAG_ENGINE_STEPS(engine[c], k.n_snp);
-		bt_row[c] = bt_rows;
-		bt_rows += HIBAG_ENGINE_ROWS(engine[c], k.n_snp);
-		cell_chunks[c].assign(P, 0);
-		cell_pairs[c].assign(P, 0);
-		if (mfma_nkb[c]) {
+		if (L.engine[c] == HIBAG_ENGINE_FP4 && k.n_snp > HIBAG_FP4_MAX_SNPS && opt.pass2 == FinalizeOptions::RECOMPUTE) L.engine[c] = HIBAG_ENGINE_VALU;
+		L.n_step[c] = HIBAG_ENGINE_STEPS(L.engine[c], k.n_snp);
+		L.bt_row[c] = L.bt_rows;
+		L.bt_rows += HIBAG_ENGINE_ROWS(L.engine[c], k.n_snp);
+		cp.chunks.assign(P, 0);
+		cp.npairs.assign(P, 0);
+		if (L.engine[c] != HIBAG_ENGINE_VALU) {
 			// no record stream: the kernels generate the records from the haplotype table
-			hap_off[c] = (uint32_t)hap.size();
-			const bool fp4 = engine[c] == HIBAG_ENGINE_FP4;
-			const int steps = n_step[c];
-			// bits of a haplotype: SNPs [lo, lo + 32) of its 128-bit string
-			auto window = [&](int i, int lo) -> uint32_t {
-				if (i < 0) return 0u;
-				const unsigned __int128 v = ((unsigned __int128)k.bits[2 * (size_t)i + 1] << 64) | k.bits[2 * (size_t)i];
-				return (uint32_t)(v >> lo);
-			};
-			auto entry = [&](double ff, int i, double f) {
-				uint32_t w[12 + 4 * (HIBAG_FP4_MAX_STEPS - 1)] = {0};
-				int n = 0;
-				if (fp4 && steps == 1) {       // two nibble images, both ADDED by the kernel (K layout in hibag_device.h):
-					// the "sum" image has nibble s = 2 (the e2m1 code of 1.0) where bit s is set, the "pair" image the code 3 (1.5) --
-					// two of them make the code 6 (4.0), so the sum of two pair images is w = 0 / 1.5 / 4 for 0 / 1 / 2 set bits
-					const uint32_t bits = window(i, 0);
-					for (int sb = 0; sb < 32; sb++) {
-						w[sb >> 3] |= ((bits >> sb) & 1u) << (4 * (sb & 7) + 1);
-						w[4 + (sb >> 3)] |= (((bits >> sb) & 1u) * 3u) << (4 * (sb & 7));
-					}
-					if (i >= 0) {
-						// ... plus the A-row constants of the offset digits at nibbles k, k + 1: each image carries half of each (sum
-						// image: codes 1 and 3, 0.5 + 0.5 = 1 and 3 + 3 = code 6 = 4; pair image: 3 and 3 -> 4, 4).  (Not the padding
-						// entry: its rows must stay zero.)
-						const int ks = k.n_snp;
-						for (int q = 0; q < 2; q++) {
-							const int nib = ks + q;
-							w[nib >> 3] |= (q == 0 ? 1u : 3u) << (4 * (nib & 7));
-							w[4 + (nib >> 3)] |= 3u << (4 * (nib & 7));
-						}
-					}
-					n = 8;
-				} else if (fp4) {              // nibble s = 2 (the e2m1 code of 1.0) where bit s is set
-					const uint32_t bits = window(i, 0) & ((1u << HIBAG_FP4_STEP_SNPS) - 1);
-					for (int sb = 0; sb < 32; sb++) w[sb >> 3] |= ((bits >> sb) & 1u) << (4 * (sb & 7) + 1);
-					n = 4;
-				} else {                       // byte s = 1 where bit s is set
-					const uint32_t bits = window(i, 0);
-					for (int sb = 0; sb < 32; sb++) w[sb >> 2] |= ((bits >> sb) & 1u) << (8 * (sb & 3));
-					n = 8;
-				}
-				memcpy(&w[n], &ff, sizeof(double)); memcpy(&w[n + 2], &f, sizeof(double));
-				n += 4;
-				for (int j = 1; j < steps; j++, n += 4) {      // further K steps: the next 28 SNPs each
-					const uint32_t bits = window(i, HIBAG_FP4_STEP_SNPS * j) & ((1u << HIBAG_FP4_STEP_SNPS) - 1);
-					for (int sb = 0; sb < 32; sb++) w[n + (sb >> 3)] |= ((bits >> sb) & 1u) << (4 * (sb & 7) + 1);
-				}
-				hap.insert(hap.end(), w, w + n);
-			};
-			for (int i = 0; i < H; i++) entry(2 * k.freq[i], i, k.freq[i]);
-			entry(0.0, -1, 0.0);                                   // H: the padding entry (frequency +0.0)
-			for (int i = 0; i < H; i++) entry(k.freq[i], i, k.freq[i]);   // H+1+i: first of a diagonal pair
+			L.hap_off[c] = (uint32_t)L.hap.size();
+			for (int i = 0; i < H; i++) append_hap_entry(k, L.engine[c], L.n_step[c], 2 * k.freq[i], i, k.freq[i], L.hap);
+			append_hap_entry(k, L.engine[c], L.n_step[c], 0.0, -1, 0.0, L.hap);                   // H: the padding entry (frequency +0.0)
+			for (int i = 0; i < H; i++) append_hap_entry(k, L.engine[c], L.n_step[c], k.freq[i], i, k.freq[i], L.hap);   // H+1+i: first of a diagonal pair
 			size_t p = 0;
 			for (int h1 = 0; h1 < nh; h1++)
 				for (int h2 = h1; h2 < nh; h2++) {
-					const uint64_t n1 = (uint64_t)(st[h1 + 1] - st[h1]), n2 = (uint64_t)(st[h2 + 1] - st[h2]);
+					const uint64_t n1 = (uint64_t)(cp.st[h1 + 1] - cp.st[h1]), n2 = (uint64_t)(cp.st[h2 + 1] - cp.st[h2]);
 					const uint64_t n = h1 == h2 ? n1 * (n1 + 1) / 2 : n1 * n2;
 					if (n > 0xFFFFFFull * HIBAG_CHUNK) return hibag_fail(HIBAG_HIP_EINVAL, "an allele pair of classifier %d has too many haplotype pairs", c);
-					cell_pairs[c][p] = (uint32_t)n;
-					cell_chunks[c][p++] = (uint32_t)((n + HIBAG_CHUNK - 1) / HIBAG_CHUNK);
+					cp.npairs[p] = (uint32_t)n;
+					cp.chunks[p++] = (uint32_t)((n + HIBAG_CHUNK - 1) / HIBAG_CHUNK);
 				}
 		} else {
-			if (stream.size() & 1) stream.push_back(0);          // 8-byte alignment of the doubles inside
-			stream_off[c] = stream.size();
-			build_pair_stream(k, nh, nwp[c], st.data(), stream, cell_chunks[c]);
+			if (L.stream.size() & 1) L.stream.push_back(0);          // 8-byte alignment of the doubles inside
+			L.stream_off[c] = L.stream.size();
+			build_pair_stream(k, nh, L.nwp[c], cp.st.data(), L.stream, cp.chunks);
 		}
-		for (int p = 0; p < P; p++) cell_work[p] += (uint64_t)cell_chunks[c][p] * (nwp[c] + 2);
-		pairs[c] = (int64_t)H * (H + 1) / 2;
-		m->pair_evals += pairs[c];
-		if (!mfma_nkb[c]) valu_pairs += pairs[c];
-		c_order[c] = c;
+		for (int p = 0; p < P; p++) L.cell_work[p] += (uint64_t)cp.chunks[p] * (L.nwp[c] + 2);
+		cp.pairs = (int64_t)H * (H + 1) / 2;
+		L.pair_evals += cp.pairs;
+		L.c_order[c] = c;
 	}
-	if (!m->snp_weight_override.empty()) snp_weight = m->snp_weight_override;
-	std::stable_sort(c_order.begin(), c_order.end(), [&](int a, int b) { return pairs[a] * nwp[a] > pairs[b] * nwp[b]; });
+	if (!m->snp_weight_override.empty()) L.snp_weight = m->snp_weight_override;
+	std::stable_sort(L.c_order.begin(), L.c_order.end(), [&](int a, int b) { return L.cp[a].pairs * L.nwp[a] > L.cp[b].pairs * L.nwp[b]; });
 	// the walker fetches one chunk ahead: keep a widest-record chunk of slack behind the last record
-	stream.insert(stream.end(), HIBAG_CHUNK_DWORDS(HIBAG_MAX_NWP), 0);
-	if (snp_index.empty()) snp_index.push_back(0);
-	if (hap.empty()) hap.insert(hap.end(), 12, 0u);
-	if (hap.size() * sizeof(uint32_t) > 0x7FFFFF00ull) return hibag_fail(HIBAG_HIP_EINVAL, "the model's haplotype tables exceed 2 GB");
+	L.stream.insert(L.stream.end(), HIBAG_CHUNK_DWORDS(HIBAG_MAX_NWP), 0);
+	if (L.snp_index.empty()) L.snp_index.push_back(0);
+	if (L.hap.empty()) L.hap.insert(L.hap.end(), 12, 0u);
+	if (L.hap.size() * sizeof(uint32_t) > 0x7FFFFF00ull) return hibag_fail(HIBAG_HIP_EINVAL, "the model's haplotype tables exceed 2 GB");
+	// (an all-zero FP4 entry behind the tables: reads of the haplotype table through a slot of a padding block land here)
+	L.hap.insert(L.hap.end(), HIBAG_ENGINE_HAP_DWORDS(HIBAG_ENGINE_FP4), 0u);
+	while (L.hap.size() % 4) L.hap.push_back(0u);
+	return 0;
+}
 
-	std::vector<int> tile_p0, tile_n;
+// Stage 2: the tiles of pass 2 (build_tiles) and the (h1, h2) of every tile's first cell.
+void plan_tiles(ModelLayout &L)
+{
 	// cells per tile: fifteen where that still makes ~48 tiles or more (50 alleles: 85), fewer for models of few alleles, down
-	// to four (a visit of fewer cells is mostly block overhead).  HIBAG_TILE_CAP overrides (diagnostic).
-	int tile_cap = std::max(4, std::min(HIBAG_TILE, (P + 47) / 48));
-	if (const char *e = getenv("HIBAG_TILE_CAP")) tile_cap = std::max(1, std::min(HIBAG_TILE, atoi(e)));
-	build_tiles(P, cell_work, tile_p0, tile_n, tile_cap);
-	const int n_tile = (int)tile_p0.size();
-	std::vector<int> tile_h1(n_tile, 0), tile_h2(n_tile, 0);      // (h1, h2) of every tile's first cell
-	{
-		int t = 0, p = 0;
-		for (int h1 = 0; h1 < nh && t < n_tile; h1++)
-			for (int h2 = h1; h2 < nh && t < n_tile; h2++, p++)
-				if (p == tile_p0[t]) { tile_h1[t] = h1; tile_h2[t] = h2; t++; }
-	}
-	// Which cell sums pass 1 stores for pass 2 (HibagModelView::store_cells).  Measured on MI355X: evaluating a haplotype
-	// pair again costs ~0.25 ps per sample, a stored cell ~2.2 ps (written in pass 1, read in pass 2, both at HBM speed).
-	// A model with many pairs per non-empty cell (the DRB1 shape: 73) stores every cell and pass 2 only reads; otherwise
-	// (the HLA-B benchmark model: 8.5) the cells with more than `store_above` pairs of the matrix-engine classifiers are
-	// stored -- 15 % of its cells hold 62 % of its pairs -- and pass 2 evaluates the rest (thresholds 8 .. 16 measure the same;
-	// below, the stores slow pass 1 down more than pass 2 gains).  HIBAG_PASS2 = stream |
-	// hybrid | recompute and HIBAG_STORE_PAIRS override.
-	uint64_t store_above = 12;
-	if (const char *e = getenv("HIBAG_STORE_PAIRS")) store_above = (uint64_t)std::max(0, atoi(e));
-	uint32_t fit_min = 5;
-	if (const char *e = getenv("HIBAG_STORE_FIT")) fit_min = atoi(e) > 0 ? (uint32_t)atoi(e) : ~0u;
-	if (getenv("HIBAG_PASS2") && !strcmp(getenv("HIBAG_PASS2"), "recompute")) { store_above = ~(uint64_t)0; fit_min = ~0u; }   // (no cell of theirs is stored)
-	// Pass 2 evaluates the pairs of one-step FP4 classifiers only (k_accum's block stream); a classifier on any other engine
-	// -- int8 (29..32 SNPs), FP4 in several K steps, VALU -- has all its cells stored by pass 1 and read back.
-	auto pass2_evaluates = [&](int c) { return engine[c] == HIBAG_ENGINE_FP4 && n_step[c] == 1; };
-	{
-		long long n_cells = 0, n_big = 0;
-		double cost = 0;                                   // pairs, a VALU-engine pair counted five times (what it costs)
-		for (int c = 0; c < C; c++) {
-			cost += (double)pairs[c] * (mfma_nkb[c] ? 1.0 : 5.0);
-			for (int p = 0; p < P; p++) {
-				n_cells += cell_chunks[c][p] != 0;
-				n_big += pass2_evaluates(c) ? cell_pairs[c][p] > store_above : cell_chunks[c][p] != 0;
-			}
-		}
-		m->store_mode = C == 0 ? 0 : cost >= 14.0 * (double)std::max<long long>(n_cells, 1) ? 1 : n_big ? 2 : 0;
-		if (const char *e = getenv("HIBAG_PASS2")) {
-			if (!strcmp(e, "stream")) m->store_mode = C > 0;
-			else if (!strcmp(e, "recompute")) m->store_mode = n_big ? 2 : 0;       // (only what pass 2 cannot evaluate is stored)
-			else if (!strcmp(e, "hybrid")) m->store_mode = n_big ? 2 : 0;
+	// to four (a visit of fewer cells is mostly block overhead)
+	const int tile_cap = std::max(4, std::min(HIBAG_TILE, (L.P + 47) / 48));
+	build_tiles(L.P, L.cell_work, L.tile_p0, L.tile_n, tile_cap);
+	L.n_tile = (int)L.tile_p0.size();
+	L.tile_h1.assign(L.n_tile, 0); L.tile_h2.assign(L.n_tile, 0);
+	for (int h1 = 0, t = 0, p = 0; h1 < L.nh && t < L.n_tile; h1++)
+		for (int h2 = h1; h2 < L.nh && t < L.n_tile; h2++, p++)
+			if (p == L.tile_p0[t]) { L.tile_h1[t] = h1; L.tile_h2[t] = h2; t++; }
+}
+
+// Stage 3: which cell sums pass 1 stores for pass 2 (HibagModelView::store_cells, and `stored` of every classifier).  Measured
+// on MI355X: evaluating a haplotype pair again costs ~0.25 ps per sample, a stored cell ~2.2 ps (written in pass 1, read in
+// pass 2, both at HBM speed).  A model with many pairs per non-empty cell (the DRB1 shape: 73) stores every cell and pass 2
+// only reads; otherwise (the HLA-B benchmark model: 8.5) the cells with more than `store_above` pairs of the matrix-engine
+// classifiers are stored -- 15 % of its cells hold 62 % of its pairs -- and pass 2 evaluates the rest (thresholds 8 .. 16
+// measure the same; below, the stores slow pass 1 down more than pass 2 gains).  HIBAG_PASS2 = stream | hybrid | recompute
+// and HIBAG_STORE_PAIRS override.
+void plan_store(const FinalizeOptions &opt, ModelLayout &L)
+{
+	const int C = L.C, P = L.P;
+	const bool recompute = opt.pass2 == FinalizeOptions::RECOMPUTE;       // (no cell of theirs is stored)
+	const uint64_t store_above = recompute ? ~(uint64_t)0 : opt.store_above;
+	const uint32_t fit_min = recompute ? ~0u : 5u;           // the fit rule below (swept 0 .. 5: flat around 5, 4 % slower without it)
+	long long n_cells = 0, n_big = 0;
+	double cost = 0;                                   // pairs, a VALU-engine pair counted five times (what it costs)
+	bool any_eval = false;                             // (none: e.g. HIBAG_ENGINE=valu)
+	for (int c = 0; c < C; c++) {
+		cost += (double)L.cp[c].pairs * (L.engine[c] ? 1.0 : 5.0);
+		any_eval |= L.evaluates(c);
+		for (int p = 0; p < P; p++) {
+			n_cells += L.cp[c].chunks[p] != 0;
+			n_big += L.evaluates(c) ? L.cp[c].npairs[p] > store_above : L.cp[c].chunks[p] != 0;
 		}
 	}
-	{
-		// nothing pass 2 could evaluate (no one-step FP4 classifier, e.g. HIBAG_ENGINE=valu): read everything back
-		bool any_eval = false;
-		for (int c = 0; c < C; c++) any_eval |= pass2_evaluates(c);
-		if (m->store_mode == 2 && !any_eval) m->store_mode = 1;
-	}
-	const int store_mode = m->store_mode;
-	// stored[c][p]: pass 1 stores the sum of cell p of classifier c.  Mode 2: the cells of a matrix-engine classifier with
+	L.store_mode = C == 0 ? 0 : cost >= 14.0 * (double)std::max<long long>(n_cells, 1) ? 1 : n_big ? 2 : 0;
+	if (opt.pass2 == FinalizeOptions::STREAM) L.store_mode = C > 0;
+	else if (opt.pass2 != FinalizeOptions::AUTO) L.store_mode = n_big ? 2 : 0;     // (recompute: only what pass 2 cannot evaluate is stored)
+	if (L.store_mode == 2 && !any_eval) L.store_mode = 1;       // nothing pass 2 could evaluate: read everything back
+	// stored[p]: pass 1 stores the sum of cell p of the classifier.  Mode 2: the cells of a matrix-engine classifier with
 	// more than `store_above` pairs, at most HIBAG_STORED_PER_VISIT per (classifier, tile) -- the ones with the most pairs --
 	// which is what pass 2 keeps in registers for a visit, and every cell of a VALU-engine classifier; mode 1: every non-empty cell.
-	std::vector<std::vector<uint8_t>> stored(C);
 	for (int c = 0; c < C; c++) {
-		stored[c].assign(P, 0);
-		if (store_mode == 1) { for (int p = 0; p < P; p++) stored[c][p] = cell_chunks[c][p] != 0; }
-		else if (store_mode == 2 && !pass2_evaluates(c)) {
-			// pass 2 evaluates one-step FP4 classifiers only: all the cells of the others
-			for (int p = 0; p < P; p++) stored[c][p] = cell_chunks[c][p] != 0;
-		} else if (store_mode == 2)
-			for (int t = 0; t < n_tile; t++) {
+		std::vector<uint8_t> &stored = L.cp[c].stored;
+		stored.assign(P, 0);
+		if (L.store_mode == 1 || (L.store_mode == 2 && !L.evaluates(c)))    // (mode 2: all the cells of a classifier pass 2 cannot evaluate)
+			for (int p = 0; p < P; p++) stored[p] = L.cp[c].chunks[p] != 0;
+		else if (L.store_mode == 2)
+			for (int t = 0; t < L.n_tile; t++) {
 				// Largest cells first: a cell with more than `store_above` pairs is stored; so is -- while the visit's
 				// remaining pair slots would not fit ONE 32-slot block -- any cell of at least `fit_min` pairs: a second,
-				// mostly empty block costs pass 2 more than a stored sum (HIBAG_STORE_FIT=0 switches that off).
+				// mostly empty block costs pass 2 more than a stored sum.
 				std::vector<std::pair<uint32_t, int>> cells;
 				uint32_t slots = 0;                            // pair slots of the visit (cells padded to an even count)
-				for (int j = 0; j < tile_n[t]; j++) {
-					const uint32_t n = cell_pairs[c][tile_p0[t] + j];
-					if (n) { cells.push_back({n, tile_p0[t] + j}); slots += n + (n & 1u); }
+				for (int j = 0; j < L.tile_n[t]; j++) {
+					const uint32_t n = L.cp[c].npairs[L.tile_p0[t] + j];
+					if (n) { cells.push_back({n, L.tile_p0[t] + j}); slots += n + (n & 1u); }
 				}
 				std::stable_sort(cells.begin(), cells.end(), [](const auto &a, const auto &b) { return a.first > b.first; });
 				for (size_t i = 0; i < cells.size() && i < HIBAG_STORED_PER_VISIT; i++) {
 					const uint32_t n = cells[i].first;
 					if (!(n > store_above || (slots > HIBAG_PLIST_DWORDS && n >= fit_min))) break;
-					stored[c][cells[i].second] = 1;
+					stored[cells[i].second] = 1;
 					slots -= n + (n & 1u);
 				}
 			}
 	}
-	// a cell of a matrix-engine classifier whose sum pass 2 reads instead of evaluating its pairs (mode 2)
-	auto stored_big = [&](int c, int p) { return store_mode == 2 && stored[c][p] != 0; };
+}
 
-	// pass 1 lists (non-empty cells per classifier) and pass 2 tile entries
-	std::vector<uint32_t> cls_cnt, cls_cell, tile_meta((size_t)std::max(C, 1) * n_tile * HIBAG_TILE_META + 1, 0);
-	std::vector<int> cls_off(std::max(C, 1), 0), cls_n(std::max(C, 1), 0);
-	std::vector<uint32_t> tile_k0((size_t)std::max(C, 1) * n_tile, 0), tile_nlist((size_t)std::max(C, 1) * n_tile, 0),
-		tile_nstored((size_t)std::max(C, 1) * n_tile, 0);
-	std::vector<uint64_t> tile_jpack((size_t)std::max(C, 1) * n_tile, 0);
-	std::vector<int> n_stored_c(std::max(C, 1), 0);        // cells of the classifier pass 1 stores in mode 2
-	m->second_pass_pairs = 0;
-	for (int c = 0; c < C; c++) {
-		cls_off[c] = (int)cls_cnt.size();
-		for (int p = 0; p < P; p++)
-			if (cell_chunks[c][p]) { cls_cnt.push_back(cell_chunks[c][p]); cls_cell.push_back((uint32_t)p); }
-		cls_n[c] = (int)cls_cnt.size() - cls_off[c];
-		cls_cnt.push_back(0); cls_cell.push_back(0);        // the walker reads one count ahead
+// Stage 4: pass 1 lists (non-empty cells per classifier) and pass 2 tile entries.
+int plan_cell_lists(ModelLayout &L)
+{
+	const size_t CT = (size_t)std::max(L.C, 1) * L.n_tile;
+	L.tile_meta.assign(CT * HIBAG_TILE_META + 1, 0);
+	L.tile_k0.assign(CT, 0); L.tile_nlist.assign(CT, 0); L.tile_nstored.assign(CT, 0); L.tile_jpack.assign(CT, 0);
+	L.cls_off.assign(std::max(L.C, 1), 0); L.cls_n.assign(std::max(L.C, 1), 0); L.n_stored_c.assign(std::max(L.C, 1), 0);
+	for (int c = 0; c < L.C; c++) {
+		const std::vector<uint32_t> &chunks = L.cp[c].chunks;
+		L.cls_off[c] = (int)L.cls_cnt.size();
+		for (int p = 0; p < L.P; p++)
+			if (chunks[p]) { L.cls_cnt.push_back(chunks[p]); L.cls_cell.push_back((uint32_t)p); }
+		L.cls_n[c] = (int)L.cls_cnt.size() - L.cls_off[c];
+		L.cls_cnt.push_back(0); L.cls_cell.push_back(0);        // the walker reads one count ahead
 		uint64_t off = 0;
 		int k_first = 0;                                    // non-empty cells of the classifier in earlier tiles
-		for (int t = 0; t < n_tile; t++) {
-			uint32_t *me = &tile_meta[((size_t)c * n_tile + t) * HIBAG_TILE_META];
-			tile_k0[(size_t)c * n_tile + t] = (uint32_t)k_first;
+		for (int t = 0; t < L.n_tile; t++) {
+			const size_t ct = (size_t)c * L.n_tile + t;
+			const int p0 = L.tile_p0[t];
+			uint32_t *me = &L.tile_meta[ct * HIBAG_TILE_META];
 			if (off > 0xFFFFFFFFull) return hibag_fail(HIBAG_HIP_EINVAL, "classifier %d has too many haplotype pairs", c);
 			me[1] = (uint32_t)off;
 			int k = 0;
 			uint64_t jpack = 0;
-			for (int j = 0; j < tile_n[t]; j++) {
-				const uint32_t n = cell_chunks[c][tile_p0[t] + j];
+			for (int j = 0; j < L.tile_n[t]; j++) {
+				const uint32_t n = chunks[p0 + j];
 				if (n > 0xFFFFFFu) return hibag_fail(HIBAG_HIP_EINVAL, "an allele pair of classifier %d has too many haplotype pairs", c);
 				if (n) { jpack |= (uint64_t)j << (4 * k); me[4 + k++] = ((uint32_t)j << 24) | n; off += n; }
 			}
 			me[0] = (uint32_t)k;
 			me[2] = (uint32_t)jpack; me[3] = (uint32_t)(jpack >> 32);
-			{
-				// what pass 2 gets per (classifier, tile): the cells it evaluates (in closing order), then those it reads
-				uint64_t jp = 0;
-				int nl = 0, ns = 0;
-				for (int j = 0; j < tile_n[t]; j++)
-					if (cell_chunks[c][tile_p0[t] + j] && !stored_big(c, tile_p0[t] + j)) {
-						jp |= (uint64_t)j << (4 * nl++);
-						if (store_mode != 1) m->second_pass_pairs += pass2_evaluates(c) ? cell_pairs[c][tile_p0[t] + j] : 0;
-					}
-				for (int j = 0; j < tile_n[t]; j++)
-					if (stored_big(c, tile_p0[t] + j)) jp |= (uint64_t)j << (4 * (nl + ns++));
-				tile_jpack[(size_t)c * n_tile + t] = jp;
-				tile_nlist[(size_t)c * n_tile + t] = (uint32_t)nl;
-				tile_nstored[(size_t)c * n_tile + t] = (uint32_t)ns;
-				if (store_mode == 2) tile_k0[(size_t)c * n_tile + t] = (uint32_t)n_stored_c[c];   // first stored row of the tile
-				n_stored_c[c] += ns;
-			}
-			k_first += k;
-			for (int j = 0; j < tile_n[t]; j++)
-				if (!cell_chunks[c][tile_p0[t] + j]) me[4 + k++] = (uint32_t)j << 24;
-		}
-	}
-	if (cls_cnt.empty()) { cls_cnt.push_back(0); cls_cell.push_back(0); }
-
-	// pass-1 work items.  One per classifier, except VALU-engine classifiers (more than 112 SNPs)
-	// whose work dwarfs the typical one: a single wavefront per sample group would walk them for
-	// many times the duration of the rest of the pass, so they are cut into items of typical size
-	// that store per-cell sums, added in order afterwards (k_total_scan).
-	std::vector<int> item, item_whole, split_row(std::max(C, 1), -1), split_cls, wide_cls;
-	double split_heavy_ns = 0, split_rest_ns = 0;
-	{
-		// rough wavefront-time per record: matrix engine 50 ns at full occupancy, VALU engine 18 ns per
-		// 32-bit word while other wavefronts share its SIMD (measured), 48 ns at full occupancy
-		std::vector<double> work(C, 0.0);
-		double typical = 0;
-		int n_typ = 0;
-		for (int c = 0; c < C; c++) {
-			work[c] = (double)pairs[c] * (mfma_nkb[c] ? 50.0 * (0.5 + 0.5 * n_step[c]) : 48.0 * nwp[c]);
-			if (mfma_nkb[c]) { typical += work[c]; n_typ++; }
-			split_rest_ns += work[c];
-		}
-		typical = n_typ ? typical / n_typ : 0;
-		std::vector<std::pair<double, std::vector<int>>> items, whole;
-		for (int c = 0; c < C; c++) {
-			if (n_step[c] > 1) { wide_cls.push_back(c); continue; }        // pass 1 in k_total_wide
-			whole.push_back({work[c], {c, 0, cls_n[c], 0}});
-			int nseg = 1;
-			if (!mfma_nkb[c] && typical > 0 && work[c] > 3 * typical)
-				nseg = (int)std::min<double>(64, std::max(2.0, std::floor(work[c] / typical)));
-			if (nseg == 1 || cls_n[c] < 2) {
-				items.push_back({work[c], {c, 0, cls_n[c], 0}});
-				continue;
-			}
-			split_heavy_ns = std::max(split_heavy_ns, (double)pairs[c] * 18.0 * nwp[c]);       // measured: 1.1 ms for 5,050 pairs x 12 words
-			split_row[c] = 1;                              // (>= 0: split; its cells have rows in HibagBatchView::cells)
-			split_cls.push_back(c);
-			uint64_t total = 0, acc = 0, chunk0 = 0;
-			for (int i = 0; i < cls_n[c]; i++) total += cls_cnt[cls_off[c] + i] + 1;
-			int i0 = 0, k = 1;
-			for (int i = 0; i < cls_n[c]; i++) {
-				acc += cls_cnt[cls_off[c] + i] + 1;
-				const bool last = i + 1 == cls_n[c];
-				if (last || acc * nseg >= total * k) {
-					uint64_t chunks = 0;
-					for (int j = i0; j <= i; j++) chunks += cls_cnt[cls_off[c] + j];
-					items.push_back({work[c] * (double)(chunks + 1) / (double)total, {c, i0, i + 1, (int)chunk0}});
-					chunk0 += chunks;
-					i0 = i + 1;
-					while (k < nseg && acc * nseg >= total * k) k++;
+			// what pass 2 gets per (classifier, tile): the cells it evaluates (in closing order), then those it reads
+			uint64_t jp = 0;
+			int nl = 0, ns = 0;
+			for (int j = 0; j < L.tile_n[t]; j++)
+				if (chunks[p0 + j] && !L.stored_big(c, p0 + j)) {
+					jp |= (uint64_t)j << (4 * nl++);
+					if (L.store_mode != 1) L.second_pass_pairs += L.evaluates(c) ? L.cp[c].npairs[p0 + j] : 0;
 				}
+			for (int j = 0; j < L.tile_n[t]; j++)
+				if (L.stored_big(c, p0 + j)) jp |= (uint64_t)j << (4 * (nl + ns++));
+			L.tile_jpack[ct] = jp;
+			L.tile_nlist[ct] = (uint32_t)nl;
+			L.tile_nstored[ct] = (uint32_t)ns;
+			L.tile_k0[ct] = (uint32_t)(L.store_mode == 2 ? L.n_stored_c[c] : k_first);   // mode 2: first stored row of the tile
+			L.n_stored_c[c] += ns;
+			k_first += k;
+			for (int j = 0; j < L.tile_n[t]; j++)
+				if (!chunks[p0 + j]) me[4 + k++] = (uint32_t)j << 24;
+		}
+	}
+	if (L.cls_cnt.empty()) { L.cls_cnt.push_back(0); L.cls_cell.push_back(0); }
+	return 0;
+}
+
+// Stage 5: the pass-1 work items.  One per classifier, except VALU-engine classifiers (more than 112 SNPs) whose work
+// dwarfs the typical one: a single wavefront per sample group would walk them for many times the duration of the rest of
+// the pass, so they are cut into items of typical size that store per-cell sums, added in order afterwards (k_total_scan).
+void plan_work_items(ModelLayout &L)
+{
+	L.split_row.assign(std::max(L.C, 1), -1);
+	// rough wavefront-time per record: matrix engine 50 ns at full occupancy, VALU engine 18 ns per
+	// 32-bit word while other wavefronts share its SIMD (measured), 48 ns at full occupancy
+	std::vector<double> work(L.C, 0.0);
+	double typical = 0;
+	int n_typ = 0;
+	for (int c = 0; c < L.C; c++) {
+		work[c] = (double)L.cp[c].pairs * (L.engine[c] ? 50.0 * (0.5 + 0.5 * L.n_step[c]) : 48.0 * L.nwp[c]);
+		if (L.engine[c]) { typical += work[c]; n_typ++; }
+		L.split_rest_ns += work[c];
+	}
+	typical = n_typ ? typical / n_typ : 0;
+	std::vector<std::pair<double, std::vector<int>>> items, whole;
+	for (int c = 0; c < L.C; c++) {
+		if (L.n_step[c] > 1) { L.wide_cls.push_back(c); continue; }        // pass 1 in k_total_wide
+		const int n = L.cls_n[c];
+		const uint32_t *cnt = &L.cls_cnt[L.cls_off[c]];
+		whole.push_back({work[c], {c, 0, n, 0}});
+		int nseg = 1;
+		if (!L.engine[c] && typical > 0 && work[c] > 3 * typical)
+			nseg = (int)std::min<double>(64, std::max(2.0, std::floor(work[c] / typical)));
+		if (nseg == 1 || n < 2) {
+			items.push_back({work[c], {c, 0, n, 0}});
+			continue;
+		}
+		L.split_heavy_ns = std::max(L.split_heavy_ns, (double)L.cp[c].pairs * 18.0 * L.nwp[c]);       // measured: 1.1 ms for 5,050 pairs x 12 words
+		L.split_row[c] = 1;                              // (>= 0: split; its cells have rows in HibagBatchView::cells)
+		L.split_cls.push_back(c);
+		uint64_t total = 0, acc = 0, chunk0 = 0;
+		for (int i = 0; i < n; i++) total += cnt[i] + 1;
+		int i0 = 0, k = 1;
+		for (int i = 0; i < n; i++) {
+			acc += cnt[i] + 1;
+			if (i + 1 == n || acc * nseg >= total * k) {
+				uint64_t chunks = 0;
+				for (int j = i0; j <= i; j++) chunks += cnt[j];
+				items.push_back({work[c] * (double)(chunks + 1) / (double)total, {c, i0, i + 1, (int)chunk0}});
+				chunk0 += chunks;
+				i0 = i + 1;
+				while (k < nseg && acc * nseg >= total * k) k++;
 			}
 		}
-		std::stable_sort(whole.begin(), whole.end(), [](const auto &a, const auto &b) { return a.first > b.first; });
-		for (const auto &it : whole) item_whole.insert(item_whole.end(), it.second.begin(), it.second.end());
-		std::stable_sort(items.begin(), items.end(), [](const auto &a, const auto &b) { return a.first > b.first; });
-		for (const auto &it : items) item.insert(item.end(), it.second.begin(), it.second.end());
 	}
+	std::stable_sort(whole.begin(), whole.end(), [](const auto &a, const auto &b) { return a.first > b.first; });
+	for (const auto &it : whole) L.item_whole.insert(L.item_whole.end(), it.second.begin(), it.second.end());
+	std::stable_sort(items.begin(), items.end(), [](const auto &a, const auto &b) { return a.first > b.first; });
+	for (const auto &it : items) L.item.insert(L.item.end(), it.second.begin(), it.second.end());
+}
 
-	// pair lists of the matrix-core engine.  Pass 2 first, tile-major: the segments (tile t, classifier 0),
-	// (t, 1), ... follow each other, which is the order a pass-2 wavefront reads them in; then, per
-	// classifier, all cells back to back for pass 1 (no block left half empty at a tile boundary).
-	std::vector<uint32_t> plist;
-	struct SlotRange { size_t first, n; int c; };
-	std::vector<SlotRange> slot_ranges;          // which classifier's haplotype table the slots of plist[first, first + n) index
-	std::vector<uint64_t> blk_off(std::max(C, 1), 0), seg_off((size_t)std::max(C, 1) * n_tile, 0);
-	std::vector<uint32_t> seg_nblk((size_t)std::max(C, 1) * n_tile, 0);
-	long long dbg_b1 = 0, dbg_b2 = 0, dbg_seg = 0;
-	std::vector<int> cell_row((size_t)C + 1, 0);
+// Stage 6: the stored rows of every classifier and the pair lists of the matrix-core engine.  Pass 2 first, tile-major: the
+// segments (tile t, classifier 0), (t, 1), ... follow each other, which is the order a pass-2 wavefront reads them in; then, per
+// classifier, all cells back to back for pass 1 (no block left half empty at a tile boundary).
+int plan_pair_lists(const hibag_hip_model *m, ModelLayout &L)
+{
+	const int C = L.C, n_tile = L.n_tile;
+	L.cell_row.assign((size_t)C + 1, 0);
 	for (int c = 0; c < C; c++)
-		cell_row[c + 1] = cell_row[c] + (store_mode == 1 || split_row[c] >= 0 ? cls_n[c] : store_mode == 2 ? n_stored_c[c] : 0);
+		L.cell_row[c + 1] = L.cell_row[c] + (L.store_mode == 1 || L.split_row[c] >= 0 ? L.cls_n[c] : L.store_mode == 2 ? L.n_stored_c[c] : 0);
 	// The E-stream of pass 2: per tile the blocks of classifier 0, 1, 2 ... (hibag_device.h).  A (classifier, tile) visit is
 	// the blocks of its evaluated cells' pair slots -- one-step FP4 classifiers only -- with the visit's stored sums attached
 	// four per block; a visit with more stored sums than its slot blocks carry (any classifier of another engine) gets
 	// blocks of padding slots for the rest.
-	std::vector<uint32_t> ehdr, etile_cstart((size_t)n_tile * (C + 1), 0);
-	std::vector<uint64_t> etile_blk0(std::max(n_tile, 1), 0);
-	// (an all-zero FP4 entry behind the tables: reads of the haplotype table through a slot of a padding block land here)
-	hap.insert(hap.end(), HIBAG_ENGINE_HAP_DWORDS(HIBAG_ENGINE_FP4), 0u);
-	while (hap.size() % 4) hap.push_back(0u);
-	for (int t = 0; t < n_tile && store_mode != 1; t++) {
-		etile_blk0[t] = plist.size() / HIBAG_PLIST_DWORDS;
+	L.etile_cstart.assign((size_t)n_tile * (C + 1), 0);
+	L.etile_blk0.assign(std::max(n_tile, 1), 0);
+	std::vector<uint32_t> &plist = L.plist, &ehdr = L.ehdr;
+	for (int t = 0; t < n_tile && L.store_mode != 1; t++) {
+		L.etile_blk0[t] = plist.size() / HIBAG_PLIST_DWORDS;
 		for (int c = 0; c < C; c++) {
 			const size_t ct = (size_t)c * n_tile + t;
-			etile_cstart[(size_t)t * (C + 1) + c] = (uint32_t)(plist.size() / HIBAG_PLIST_DWORDS - etile_blk0[t]);
+			L.etile_cstart[(size_t)t * (C + 1) + c] = (uint32_t)(plist.size() / HIBAG_PLIST_DWORDS - L.etile_blk0[t]);
 			const size_t first = plist.size();
 			int nb = 0;
-			if (pass2_evaluates(c) && tile_nlist[ct] > 0)
-				nb = append_pair_blocks(starts[c].data(), nh, tile_h1[t], tile_h2[t], tile_p0[t], tile_n[t],
-					(uint32_t)m->cls[c].freq.size(), plist, nullptr, store_mode == 2 ? stored[c].data() : nullptr);
-			if (nb > 0) slot_ranges.push_back({first, plist.size() - first, c});
-			const int ns = (int)tile_nstored[ct];
+			if (L.evaluates(c) && L.tile_nlist[ct] > 0)
+				nb = append_pair_blocks(L.cp[c].st.data(), L.nh, L.tile_h1[t], L.tile_h2[t], L.tile_p0[t], L.tile_n[t],
+					(uint32_t)m->cls[c].freq.size(), plist, nullptr, L.store_mode == 2 ? L.cp[c].stored.data() : nullptr);
+			if (nb > 0) L.slot_ranges.push_back({first, plist.size() - first, c});
+			const int ns = (int)L.tile_nstored[ct];
 			const int nvb = std::max(nb, (ns + HIBAG_STORED_PER_VISIT - 1) / HIBAG_STORED_PER_VISIT);
 			for (int b = nb; b < nvb; b++) plist.insert(plist.end(), HIBAG_PLIST_DWORDS, 0u);     // padding slots: entry 0 of the zero entry's "table"
-			dbg_b2 += nvb; dbg_seg += nvb > 0;
 			// the visit's cells in closing order, then its stored ones (tile_jpack)
-			uint64_t jp = tile_jpack[ct];
-			uint64_t jps = jp >> (4 * tile_nlist[ct]);
-			uint32_t srow = (uint32_t)cell_row[c] + tile_k0[ct];
+			uint64_t jp = L.tile_jpack[ct];
+			uint64_t jps = jp >> (4 * L.tile_nlist[ct]);
+			uint32_t srow = (uint32_t)L.cell_row[c] + L.tile_k0[ct];
 			for (int b = 0; b < nvb; b++) {
 				// the tile rows of the cells that close in this block, each at the place of its closing slot: slot i (odd: cells
 				// are padded to an even number of slots) -> field i / 2
@@ -597,11 +621,11 @@ int finalize_model(hibag_hip_model *m)
 				// (pass 2 requests the operand rows of every block it passes, also of blocks that only carry stored sums: a
 				// classifier of the vector engine has no rows -- bt_row[c] is then the NEXT classifier's first row, or one past
 				// the last row of the batch's array for the model's last classifiers: rows 0 and 1 instead)
-				const uint32_t bt = (uint32_t)(HIBAG_ENGINE_ROWS(engine[c], n_snp_c[c]) > 0 ? bt_row[c] : 0);
+				const uint32_t bt = (uint32_t)(HIBAG_ENGINE_ROWS(L.engine[c], L.n_snp_c[c]) > 0 ? L.bt_row[c] : 0);
 				if (bt > 0xFFFFu) return hibag_fail(HIBAG_HIP_EINVAL, "too many classifiers for the matrix engine's operand rows");
 				const uint32_t h[8] = {
 					(uint32_t)c | (bt << 16), srow | ((uint32_t)nsb << 25),
-					0u, 0u,                                   // (the next block's first two words: filled in below)
+					0u, 0u,                                   // (the next block's first two words: plan_factors)
 					(uint32_t)jq, (uint32_t)(jq >> 32),
 					(uint32_t)jps, 0u};
 				ehdr.insert(ehdr.end(), h, h + 8);
@@ -609,22 +633,19 @@ int finalize_model(hibag_hip_model *m)
 				srow += (uint32_t)nsb;
 			}
 		}
-		etile_cstart[(size_t)t * (C + 1) + C] = (uint32_t)(plist.size() / HIBAG_PLIST_DWORDS - etile_blk0[t]);
+		L.etile_cstart[(size_t)t * (C + 1) + C] = (uint32_t)(plist.size() / HIBAG_PLIST_DWORDS - L.etile_blk0[t]);
 	}
 	// look-ahead slack: the loop requests block b + 1 whole and the slots / header of block b + 2
-	const uint64_t estream_blocks = plist.size() / HIBAG_PLIST_DWORDS + 4;
+	L.estream_blocks = plist.size() / HIBAG_PLIST_DWORDS + 4;
 	plist.insert(plist.end(), 4 * HIBAG_PLIST_DWORDS, 0u);
-	ehdr.resize(estream_blocks * 8, 0u);
-	for (uint64_t b = 0; b + 1 < estream_blocks; b++) { ehdr[b * 8 + 2] = ehdr[(b + 1) * 8]; ehdr[b * 8 + 3] = ehdr[(b + 1) * 8 + 1]; }
-	const uint64_t p1_base = plist.size();
-	std::vector<uint32_t> blk_close;
-	// segments of the classifiers with several K steps (k_total_wide): {classifier, first stored row, blocks} + list offset
-	std::vector<int> wseg, wide_scan;                   // wide_scan: the classifiers of several K steps whose total k_total_scan forms
-	std::vector<uint64_t> wseg_off;
+	ehdr.resize(L.estream_blocks * 8, 0u);
+	L.p1_base = plist.size();
+	L.blk_off.assign(std::max(C, 1), 0);
 	for (int c = 0; c < C; c++) {
-		if (!mfma_nkb[c]) continue;
-		blk_off[c] = plist.size();
-		if (n_step[c] > 1) {
+		if (!L.engine[c]) continue;
+		const uint32_t pad = (uint32_t)m->cls[c].freq.size();
+		L.blk_off[c] = plist.size();
+		if (L.n_step[c] > 1) {
 			// A classifier of several K steps: its list in segments of whole cells, each starting a block of its own, so
 			// that different workgroups can walk them (their cell sums are stored, k_total_scan adds them in order);
 			// walked as one list (majority vote) the padding between the segments adds nothing.
@@ -632,77 +653,70 @@ int finalize_model(hibag_hip_model *m)
 			// A model with many such classifiers has parallelism enough: then a classifier is ONE segment, its walk forms the
 			// in-order total itself (wide_seg[3] = 1) and k_total_scan -- a second pass over every stored sum, HBM-bound --
 			// is not needed for it.
-			const bool whole = (int)wide_cls.size() >= 8;
-			const long long seg_pairs = whole ? (1ll << 62) : std::max<long long>(512, 6000 / n_step[c]);
+			const bool whole = (int)L.wide_cls.size() >= 8;
+			const long long seg_pairs = whole ? (1ll << 62) : std::max<long long>(512, 6000 / L.n_step[c]);
 			bool any_seg = false;
 			int p_lo = 0, h1_lo = 0, h2_lo = 0, row = 0, h1 = 0, h2 = 0;
 			long long acc_pairs = 0;
 			int rows_in_seg = 0;
-			for (int p = 0; p < P; p++) {
-				acc_pairs += cell_pairs[c][p];
-				rows_in_seg += cell_pairs[c][p] != 0;
+			for (int p = 0; p < L.P; p++) {
+				acc_pairs += L.cp[c].npairs[p];
+				rows_in_seg += L.cp[c].npairs[p] != 0;
 				int nh1 = h1, nh2 = h2 + 1;
-				if (nh2 == nh) { nh1++; nh2 = nh1; }
-				if (acc_pairs >= seg_pairs || p + 1 == P) {
+				if (nh2 == L.nh) { nh1++; nh2 = nh1; }
+				if (acc_pairs >= seg_pairs || p + 1 == L.P) {
 					const size_t off = plist.size();
-					const int nb = append_pair_blocks(starts[c].data(), nh, h1_lo, h2_lo, p_lo, p + 1 - p_lo, (uint32_t)m->cls[c].freq.size(),
-						plist, stored[c].data(), nullptr);
-					if (nb > 0) { wseg.insert(wseg.end(), {c, row, nb, whole ? 1 : 0}); wseg_off.push_back(off); any_seg = true; }
+					const int nb = append_pair_blocks(L.cp[c].st.data(), L.nh, h1_lo, h2_lo, p_lo, p + 1 - p_lo, pad, plist, L.cp[c].stored.data(), nullptr);
+					if (nb > 0) { L.wseg.insert(L.wseg.end(), {c, row, nb, whole ? 1 : 0}); L.wseg_off.push_back(off); any_seg = true; }
 					row += rows_in_seg; rows_in_seg = 0; acc_pairs = 0;
 					p_lo = p + 1; h1_lo = nh1; h2_lo = nh2;
 				}
 				h1 = nh1; h2 = nh2;
 			}
-			if (!whole || !any_seg) wide_scan.push_back(c);          // (a classifier without haplotypes has no segment: the scan writes its zero total)
-			cls_nblk[c] = (int)((plist.size() - blk_off[c]) / HIBAG_PLIST_DWORDS);
-			slot_ranges.push_back({(size_t)blk_off[c], plist.size() - (size_t)blk_off[c], c});
-			dbg_b1 += cls_nblk[c];
-			for (int b = 0; b < cls_nblk[c] && store_mode; b++) blk_close.push_back(0);     // (keeps the block numbering; not used for these)
-			continue;
-		}
-		cls_nblk[c] = append_pair_blocks(starts[c].data(), nh, 0, 0, 0, P, (uint32_t)m->cls[c].freq.size(), plist,
-			store_mode ? stored[c].data() : nullptr, nullptr);
-		slot_ranges.push_back({(size_t)blk_off[c], plist.size() - (size_t)blk_off[c], c});
-		dbg_b1 += cls_nblk[c];
+			if (!whole || !any_seg) L.wide_scan.push_back(c);          // (a classifier without haplotypes has no segment: the scan writes its zero total)
+		} else
+			append_pair_blocks(L.cp[c].st.data(), L.nh, 0, 0, 0, L.P, pad, plist, L.store_mode ? L.cp[c].stored.data() : nullptr, nullptr);
+		L.cls_nblk[c] = (int)((plist.size() - L.blk_off[c]) / HIBAG_PLIST_DWORDS);
+		L.slot_ranges.push_back({(size_t)L.blk_off[c], plist.size() - (size_t)L.blk_off[c], c});
+		L.p1_blocks += L.cls_nblk[c];
 		uint32_t closed = 0;
-		for (int b = 0; b < cls_nblk[c] && store_mode; b++) {      // stored cells closed before block b
-			blk_close.push_back(closed);
-			for (int i = 0; i < HIBAG_PLIST_DWORDS; i++) closed += (plist[blk_off[c] + (size_t)b * HIBAG_PLIST_DWORDS + i] >> 30) & 1u;
+		for (int b = 0; b < L.cls_nblk[c] && L.store_mode; b++) {      // stored cells closed before block b (0 for the segmented lists: not used)
+			L.blk_close.push_back(L.n_step[c] > 1 ? 0u : closed);
+			for (int i = 0; i < HIBAG_PLIST_DWORDS; i++) closed += (plist[L.blk_off[c] + (size_t)b * HIBAG_PLIST_DWORDS + i] >> 30) & 1u;
 		}
 	}
-	if (blk_close.empty()) blk_close.push_back(0);
-	(void)valu_pairs;
-	if (getenv("HIBAG_DEBUG_MODEL"))
-		fprintf(stderr, "[hibag model] %d classifiers, %d tiles, pairs %lld; blocks of 32: pass 1 %lld, pass 2 %lld in %lld (classifier, tile) segments; "
-			"pair lists %.1f MB + factors %.1f MB + block headers %.1f MB, haplotype table %.1f KB, VALU-engine stream %.1f MB\n",
-			C, n_tile, (long long)m->pair_evals, dbg_b1, dbg_b2, dbg_seg, plist.size() * 4e-6, plist.size() * 8e-6, plist.size() / 32 * 16e-6,
-			hap.size() * 4e-3, stream.size() * 4e-6);
+	if (L.blk_close.empty()) L.blk_close.push_back(0);
 	plist.insert(plist.end(), 4 * HIBAG_PLIST_DWORDS, 0u);   // look-ahead slack of the block walker
-	// What the kernels take from a block through the SCALAR cache (hibag_device.h): the frequency factor of every slot --
-	// ff[i1] * f[i2], the one rounded multiplication of src/LibHLA.cpp:1786-1813, made here once instead of by every wavefront
-	// that walks the list -- and a header {cell ends, stored cell ends, slots worth evaluating}.
-	std::vector<double> pfac(plist.size(), 0.0);
-	for (const SlotRange &r : slot_ranges) {
+	return 0;
+}
+
+// Stage 7: what the kernels take from a block through the SCALAR cache (hibag_device.h): the frequency factor of every slot --
+// ff[i1] * f[i2], the one rounded multiplication of src/LibHLA.cpp:1786-1813, made here once instead of by every wavefront
+// that walks the list -- and a header {cell ends, stored cell ends, slots worth evaluating}; then the E-stream's headers.
+void plan_factors(const hibag_hip_model *m, ModelLayout &L)
+{
+	L.pfac.assign(L.plist.size(), 0.0);
+	for (const auto &r : L.slot_ranges) {
 		const std::vector<double> &freq = m->cls[r.c].freq;
 		const uint32_t H = (uint32_t)freq.size();
-		// table entries (above): [0, H) = {2 f, f}, H = the padding entry {0, 0}, H + 1 + i = {f, f} (first of a diagonal pair)
+		// table entries (plan_classifiers): [0, H) = {2 f, f}, H = the padding entry {0, 0}, H + 1 + i = {f, f} (first of a diagonal pair)
 		auto ff_of = [&](uint32_t e) { return e < H ? 2 * freq[e] : e == H ? 0.0 : freq[e - H - 1]; };
 		auto f_of = [&](uint32_t e) { return e < H ? freq[e] : e == H ? 0.0 : freq[e - H - 1]; };
-		for (size_t i = r.first; i < r.first + r.n; i++) pfac[i] = ff_of(plist[i] & 0xFFFFu) * f_of((plist[i] >> 16) & 0x3FFFu);
+		for (size_t i = r.first; i < r.first + r.n; i++) L.pfac[i] = ff_of(L.plist[i] & 0xFFFFu) * f_of((L.plist[i] >> 16) & 0x3FFFu);
 	}
-	std::vector<uint32_t> phdr(plist.size() / HIBAG_PLIST_DWORDS * 4, 0u);
-	for (size_t b = 0; b < plist.size() / HIBAG_PLIST_DWORDS; b++) {
+	L.phdr.assign(L.plist.size() / HIBAG_PLIST_DWORDS * 4, 0u);
+	for (size_t b = 0; b < L.plist.size() / HIBAG_PLIST_DWORDS; b++) {
 		uint32_t ends = 0, stores = 0, live = 0;
 		for (int i = 0; i < HIBAG_PLIST_DWORDS; i++) {
-			const uint32_t w = plist[b * HIBAG_PLIST_DWORDS + i];
+			const uint32_t w = L.plist[b * HIBAG_PLIST_DWORDS + i];
 			if (w & HIBAG_PLIST_END) ends |= 1u << i;
 			if (w >= (HIBAG_PLIST_END | HIBAG_PLIST_STORE)) stores |= 1u << i;
-			if (pfac[b * HIBAG_PLIST_DWORDS + i] != 0.0) live |= 1u << i;      // (a zero factor adds +0.0: skipping it is exact)
+			if (L.pfac[b * HIBAG_PLIST_DWORDS + i] != 0.0) live |= 1u << i;      // (a zero factor adds +0.0: skipping it is exact)
 		}
 		live |= ends;
 		int n_valid = 0;
 		while (n_valid < 32 && (live >> n_valid)) n_valid++;
-		phdr[4 * b] = ends; phdr[4 * b + 1] = stores; phdr[4 * b + 2] = (uint32_t)n_valid;
+		L.phdr[4 * b] = ends; L.phdr[4 * b + 1] = stores; L.phdr[4 * b + 2] = (uint32_t)n_valid;
 	}
 	// Pass 2 takes everything of a block from its E-stream header alone (hibag_device.h): the end mask goes where the block's
 	// own request words were (word 0; they move to word 7 -- a walk needs them for its first block only, every other block
@@ -712,191 +726,177 @@ int finalize_model(hibag_hip_model *m)
 	// (nobody uses its classifier) resets the sum instead, and a walk that begins at the block begins at zero: the bit is
 	// right whichever blocks came before.
 	uint32_t closed_before = 0;
-	for (uint64_t b = 0; b < estream_blocks; b++) {
-		const uint32_t groups = (phdr[4 * b + 2] + 3) / 4;
-		ehdr[b * 8 + 7] = ehdr[b * 8];
-		ehdr[b * 8] = phdr[4 * b];
-		ehdr[b * 8 + 1] |= closed_before << 29;
-		ehdr[b * 8 + 6] = (ehdr[b * 8 + 6] & 0x0FFFFFFFu) | (groups << 28);
-		if (groups > 0) closed_before = (phdr[4 * b] >> (4 * groups - 1)) & 1u;
+	for (uint64_t b = 0; b < L.estream_blocks; b++) {
+		const uint32_t groups = (L.phdr[4 * b + 2] + 3) / 4;
+		L.ehdr[b * 8 + 7] = L.ehdr[b * 8];
+		L.ehdr[b * 8] = L.phdr[4 * b];
+		L.ehdr[b * 8 + 1] |= closed_before << 29;
+		L.ehdr[b * 8 + 6] = (L.ehdr[b * 8 + 6] & 0x0FFFFFFFu) | (groups << 28);
+		if (groups > 0) closed_before = (L.phdr[4 * b] >> (4 * groups - 1)) & 1u;
 	}
-	for (uint64_t b = 0; b + 1 < estream_blocks; b++) ehdr[b * 8 + 3] = ehdr[(b + 1) * 8 + 1];
-	// Prebuilt A-operand rows (HibagModelView::parow): for every slot of a one-step FP4 classifier the element-wise sum of its
-	// two haplotypes' images -- the "sum" images for the lower K half (lanes 0..31), the "pair" images for the upper one
-	// (lanes 32..63); nibble sums never carry (codes 0..3 + 0..3).  Blocks outside a slot range (padding blocks) stay zero.
-	const size_t n_blocks_all = plist.size() / HIBAG_PLIST_DWORDS;
-	double pre_mb = 128;
-	if (const char *e = getenv("HIBAG_PREBUILT_MB")) pre_mb = atof(e);
-	bool p1_prebuilt = false;
-	{
-		size_t fp4_p1_blocks = 0;
-		for (int c = 0; c < C; c++) if (pass2_evaluates(c)) fp4_p1_blocks += (size_t)cls_nblk[c];
-		p1_prebuilt = fp4_p1_blocks > 0 && (double)(n_blocks_all) * 1024.0 <= pre_mb * 1e6;
-	}
-	const size_t parow_blocks = p1_prebuilt ? n_blocks_all : (size_t)estream_blocks;
-	std::vector<uint32_t> parow(parow_blocks * 256, 0u);
-	for (const SlotRange &r : slot_ranges) {
-		if (!pass2_evaluates(r.c)) continue;
-		const uint32_t *tab_c = hap.data() + hap_off[r.c];
+	for (uint64_t b = 0; b + 1 < L.estream_blocks; b++) { L.ehdr[b * 8 + 2] = L.ehdr[(b + 1) * 8 + 7]; L.ehdr[b * 8 + 3] = L.ehdr[(b + 1) * 8 + 1]; }
+}
+
+// Stage 8: prebuilt A-operand rows (HibagModelView::parow): for every slot of a one-step FP4 classifier the element-wise sum of
+// its two haplotypes' images -- the "sum" images for the lower K half (lanes 0..31), the "pair" images for the upper one
+// (lanes 32..63); nibble sums never carry (codes 0..3 + 0..3).  Blocks outside a slot range (padding blocks) stay zero.
+void plan_parow(const FinalizeOptions &opt, ModelLayout &L)
+{
+	const size_t n_blocks_all = L.plist.size() / HIBAG_PLIST_DWORDS;
+	size_t fp4_p1_blocks = 0;
+	for (int c = 0; c < L.C; c++) if (L.evaluates(c)) fp4_p1_blocks += (size_t)L.cls_nblk[c];
+	L.p1_prebuilt = fp4_p1_blocks > 0 && (double)(n_blocks_all) * 1024.0 <= opt.prebuilt_mb * 1e6;
+	L.parow_blocks = L.p1_prebuilt ? n_blocks_all : (size_t)L.estream_blocks;
+	L.parow.assign(L.parow_blocks * 256, 0u);
+	for (const auto &r : L.slot_ranges) {
+		if (!L.evaluates(r.c)) continue;
+		const uint32_t *tab_c = L.hap.data() + L.hap_off[r.c];
 		for (size_t i = r.first; i < r.first + r.n; i++) {
 			const size_t b = i / HIBAG_PLIST_DWORDS, sl = i % HIBAG_PLIST_DWORDS;
-			if (b >= parow_blocks) break;
-			const uint32_t *e1 = tab_c + (size_t)(plist[i] & 0xFFFFu) * 12, *e2 = tab_c + (size_t)((plist[i] >> 16) & 0x3FFFu) * 12;
+			if (b >= L.parow_blocks) break;
+			const uint32_t *e1 = tab_c + (size_t)(L.plist[i] & 0xFFFFu) * 12, *e2 = tab_c + (size_t)((L.plist[i] >> 16) & 0x3FFFu) * 12;
 			for (int h = 0; h < 2; h++)
-				for (int d = 0; d < 4; d++) parow[(b * 64 + (size_t)h * 32 + sl) * 4 + d] = e1[4 * h + d] + e2[4 * h + d];
+				for (int d = 0; d < 4; d++) L.parow[(b * 64 + (size_t)h * 32 + sl) * 4 + d] = e1[4 * h + d] + e2[4 * h + d];
 		}
 	}
-	// per (classifier, tile) record of pass 2 (one s_load_dwordx8)
-	std::vector<uint32_t> ctile((size_t)std::max(C, 1) * n_tile * 8 + 8, 0);
-	for (int c = 0; c < C; c++)
-		for (int t = 0; t < n_tile; t++) {
-			uint32_t *r = &ctile[((size_t)c * n_tile + t) * 8];
-			const uint32_t *me = &tile_meta[((size_t)c * n_tile + t) * HIBAG_TILE_META];
-			const uint64_t off = seg_off[(size_t)c * n_tile + t];
-			if (bt_row[c] > 0xFFFF) return hibag_fail(HIBAG_HIP_EINVAL, "too many classifiers for the matrix engine's operand rows");
-			(void)me;
-			const int k_last = n_snp_c[c] - HIBAG_FP4_STEP_SNPS * (n_step[c] - 1);        // SNPs of the last K step (all of them for one step)
-			r[0] = (uint32_t)mfma_nkb[c] | ((uint32_t)k_last << 2 & 0xFCu) | (tile_nlist[(size_t)c * n_tile + t] << 8) |
-			       ((uint32_t)(n_step[c] - 1) << 13) | ((uint32_t)bt_row[c] << 16);
-			r[1] = hap_off[c];
-			r[2] = (uint32_t)off; r[3] = (uint32_t)(off >> 32);
-			r[4] = seg_nblk[(size_t)c * n_tile + t];
+}
+
+// Stage 9: the per (classifier, tile) record of pass 2 (one s_load_dwordx8), and the bounds of the stored rows.
+int plan_ctile(ModelLayout &L)
+{
+	L.ctile.assign((size_t)std::max(L.C, 1) * L.n_tile * 8 + 8, 0);
+	for (int c = 0; c < L.C; c++)
+		for (int t = 0; t < L.n_tile; t++) {
+			const size_t ct = (size_t)c * L.n_tile + t;
+			uint32_t *r = &L.ctile[ct * 8];
+			if (L.bt_row[c] > 0xFFFF) return hibag_fail(HIBAG_HIP_EINVAL, "too many classifiers for the matrix engine's operand rows");
+			const int k_last = L.n_snp_c[c] - HIBAG_FP4_STEP_SNPS * (L.n_step[c] - 1);        // SNPs of the last K step (all of them for one step)
+			r[0] = (uint32_t)L.engine[c] | ((uint32_t)k_last << 2 & 0xFCu) | (L.tile_nlist[ct] << 8) |
+			       ((uint32_t)(L.n_step[c] - 1) << 13) | ((uint32_t)L.bt_row[c] << 16);
+			r[1] = L.hap_off[c];
+			r[2] = 0u; r[3] = 0u; r[4] = 0u;                 // (read by no kernel)
 			// first stored row of the (classifier, tile) among all stored cells of the model
-			const uint64_t row = (uint64_t)cell_row[c] + tile_k0[(size_t)c * n_tile + t];
+			const uint64_t row = (uint64_t)L.cell_row[c] + L.tile_k0[ct];
 			if (row >> 27) return hibag_fail(HIBAG_HIP_EINVAL, "the model has too many allele pairs to store their sums");
-			r[5] = (uint32_t)row | (tile_nstored[(size_t)c * n_tile + t] << 27);
-			r[6] = (uint32_t)tile_jpack[(size_t)c * n_tile + t]; r[7] = (uint32_t)(tile_jpack[(size_t)c * n_tile + t] >> 32);
+			r[5] = (uint32_t)row | (L.tile_nstored[ct] << 27);
+			r[6] = (uint32_t)L.tile_jpack[ct]; r[7] = (uint32_t)(L.tile_jpack[ct] >> 32);
 		}
+	if (L.store_mode != 1 && (uint64_t)L.cell_row[L.C] >= (1ull << 23))      // (k_accum: a stored row's byte offset within a sample group in 32 bits)
+		return hibag_fail(HIBAG_HIP_EINVAL, "the model stores too many cell sums per sample (%d) for the second pass", L.cell_row[L.C]);
+	return 0;
+}
 
-	// one int arena
-	std::vector<int> arena;
-	auto put = [&](const std::vector<int> &v) {
-		size_t off = arena.size();
-		arena.insert(arena.end(), v.begin(), v.end());
-		if (v.empty()) arena.push_back(0);
-		return off;
-	};
-	std::vector<int> hap_off_i(hap_off.begin(), hap_off.end());
-	const size_t o_nsnp = put(n_snp_c), o_nwp = put(nwp), o_snpoff = put(snp_off), o_snpidx = put(snp_index),
-		o_snpw = put(snp_weight), o_mrow = put(mask_row), o_order = put(c_order), o_tp0 = put(tile_p0), o_tn = put(tile_n),
-		o_coff = put(cls_off), o_cn = put(cls_n), o_nkb = put(mfma_nkb), o_nstep = put(n_step), o_btrow = put(bt_row), o_nblk = put(cls_nblk), o_hapoff = put(hap_off_i),
-		o_item = put(item), o_srow = put(split_row), o_scls = put(split_cls), o_itemw = put(item_whole), o_crow = put(cell_row),
-		o_wide = put(wide_cls), o_wseg = put(wseg), o_wscan = put(wide_scan);
+// One array of a device buffer: `bytes` from `src` in `room` (>= bytes) at an `align`-byte boundary, pointed at by `field`.
+struct Part { const void *src; size_t bytes, room, align; void *field; };
+template <class F, class T> Part part(const F *&field, const std::vector<T> &v, size_t align, size_t min_n = 0)
+{
+	return {v.data(), v.size() * sizeof(T), std::max(v.size(), min_n) * sizeof(T), align, &field};
+}
 
-	if (int rc = m->d_int.reserve(arena.size() * sizeof(int))) return rc;
-	if (int rc = m->d_stream.reserve(stream.size() * sizeof(uint32_t))) return rc;
-	const size_t tb_off = 0, tb_meta = stream_off.size() * sizeof(uint64_t), tb_cnt = tb_meta + tile_meta.size() * sizeof(uint32_t),
-		tb_cell = tb_cnt + cls_cnt.size() * sizeof(uint32_t),
-		tb_boff = (tb_cell + cls_cell.size() * sizeof(uint32_t) + 7) & ~(size_t)7,
-		tb_ctile = (tb_boff + blk_off.size() * sizeof(uint64_t) + 31) & ~(size_t)31,
-		tb_hap = (tb_ctile + ctile.size() * sizeof(uint32_t) + 15) & ~(size_t)15,
-		tb_ehdr = (tb_hap + hap.size() * sizeof(uint32_t) + 31) & ~(size_t)31,
-		tb_ecst = tb_ehdr + ehdr.size() * sizeof(uint32_t),
-		tb_eblk = (tb_ecst + std::max<size_t>(etile_cstart.size(), 1) * sizeof(uint32_t) + 7) & ~(size_t)7,
-		tb_close = tb_eblk + etile_blk0.size() * sizeof(uint64_t),
-		tb_wsoff = (tb_close + blk_close.size() * sizeof(uint32_t) + 7) & ~(size_t)7,
-		tb_end = tb_wsoff + std::max<size_t>(wseg_off.size(), 1) * sizeof(uint64_t);
-	if (int rc = m->d_tile.reserve(tb_end)) return rc;
-	if (int rc = m->d_tab.reserve(sizeof(m->tab))) return rc;
-	HIP_TRY(hipMemcpy(m->d_int.p, arena.data(), arena.size() * sizeof(int), hipMemcpyHostToDevice));
-	HIP_TRY(hipMemcpy(m->d_stream.p, stream.data(), stream.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-	char *tbase = m->d_tile.as<char>();
-	HIP_TRY(hipMemcpy(tbase + tb_off, stream_off.data(), stream_off.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
-	HIP_TRY(hipMemcpy(tbase + tb_meta, tile_meta.data(), tile_meta.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-	HIP_TRY(hipMemcpy(tbase + tb_cnt, cls_cnt.data(), cls_cnt.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-	HIP_TRY(hipMemcpy(tbase + tb_cell, cls_cell.data(), cls_cell.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-	HIP_TRY(hipMemcpy(tbase + tb_boff, blk_off.data(), blk_off.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
-	HIP_TRY(hipMemcpy(tbase + tb_ctile, ctile.data(), ctile.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-	HIP_TRY(hipMemcpy(tbase + tb_hap, hap.data(), hap.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-	HIP_TRY(hipMemcpy(tbase + tb_ehdr, ehdr.data(), ehdr.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-	if (!etile_cstart.empty())
-		HIP_TRY(hipMemcpy(tbase + tb_ecst, etile_cstart.data(), etile_cstart.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-	HIP_TRY(hipMemcpy(tbase + tb_eblk, etile_blk0.data(), etile_blk0.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
-	HIP_TRY(hipMemcpy(tbase + tb_close, blk_close.data(), blk_close.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-	if (!wseg_off.empty())
-		HIP_TRY(hipMemcpy(tbase + tb_wsoff, wseg_off.data(), wseg_off.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
-	if (int rc = m->d_blk.reserve(plist.size() * sizeof(uint32_t))) return rc;
-	HIP_TRY(hipMemcpy(m->d_blk.p, plist.data(), plist.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-	if (int rc = m->d_pfac.reserve(pfac.size() * sizeof(double))) return rc;
-	HIP_TRY(hipMemcpy(m->d_pfac.p, pfac.data(), pfac.size() * sizeof(double), hipMemcpyHostToDevice));
-	if (int rc = m->d_phdr.reserve(phdr.size() * sizeof(uint32_t))) return rc;
-	HIP_TRY(hipMemcpy(m->d_phdr.p, phdr.data(), phdr.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-	if (int rc = m->d_parow.reserve(std::max<size_t>(parow.size(), 256) * sizeof(uint32_t))) return rc;
-	if (!parow.empty()) HIP_TRY(hipMemcpy(m->d_parow.p, parow.data(), parow.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-	HIP_TRY(hipMemcpy(m->d_tab.p, m->tab, sizeof(m->tab), hipMemcpyHostToDevice));
+// Lays `parts` out back to back in `buf` at their alignments, copies them (several: in one host image) and points their fields.
+int upload_parts(DevBuf &buf, std::initializer_list<Part> parts)
+{
+	std::vector<size_t> at;
+	size_t end = 0;
+	for (const Part &p : parts) { at.push_back((end + p.align - 1) / p.align * p.align); end = at.back() + p.room; }
+	if (int rc = buf.reserve(end)) return rc;
+	const Part *p = parts.begin();
+	if (parts.size() == 1 && p->bytes) HIP_TRY(hipMemcpy(buf.p, p->src, p->bytes, hipMemcpyHostToDevice));     // (big arrays: no staging)
+	else if (parts.size() > 1) {
+		std::vector<char> img(end, 0);
+		for (size_t i = 0; i < parts.size(); i++) if (p[i].bytes) memcpy(&img[at[i]], p[i].src, p[i].bytes);
+		HIP_TRY(hipMemcpy(buf.p, img.data(), end, hipMemcpyHostToDevice));
+	}
+	for (size_t i = 0; i < parts.size(); i++) { const char *d = buf.as<char>() + at[i]; memcpy(p[i].field, &d, sizeof d); }
+	return 0;
+}
 
+// Reserves the device buffers, uploads the layout, points m->view at it and sets the model's scalars (and its side stream).
+int upload_layout(hibag_hip_model *m, const ModelLayout &L)
+{
+	HIP_TRY(hipSetDevice(m->device));
 	HibagModelView &V = m->view;
-	const int *base = m->d_int.as<int>();
-	V.n_hla = nh; V.n_classifier = C; V.n_snp = S; V.n_cell = P; V.mask_rows = rows; V.n_tile = n_tile;
-	V.n_snp_c = base + o_nsnp; V.nwp = base + o_nwp; V.snp_off = base + o_snpoff;
-	V.snp_index = base + o_snpidx; V.snp_weight = base + o_snpw; V.mask_row = base + o_mrow;
-	V.c_order = base + o_order; V.tile_p0 = base + o_tp0; V.tile_n = base + o_tn;
-	V.stream_off = (const uint64_t *)(tbase + tb_off);
-	V.tile_meta = (const uint32_t *)(tbase + tb_meta);
-	V.cls_cnt = (const uint32_t *)(tbase + tb_cnt);
-	V.cls_cell = (const uint32_t *)(tbase + tb_cell);
-	V.cls_off = base + o_coff; V.cls_n = base + o_cn;
-	V.engine = base + o_nkb; V.n_step = base + o_nstep; V.bt_row = base + o_btrow; V.cls_nblk = base + o_nblk;
-	V.hap_off = (const uint32_t *)(base + o_hapoff);
-	V.n_item_split = (int)item.size() / 4; V.n_item_whole = (int)item_whole.size() / 4; V.n_split = (int)split_cls.size();
-	V.item_split = base + o_item; V.item_whole = base + o_itemw; V.item = V.item_whole; V.n_item = V.n_item_whole;
-	V.split_row = base + o_srow; V.split_cls = base + o_scls;
-	V.all_fp4 = 1;
-	for (int c = 0; c < C; c++)
-		if (n_step[c] == 1 && !(engine[c] == HIBAG_ENGINE_FP4)) V.all_fp4 = 0;      // (classifiers of several K steps are not work items of k_total)
-	V.n_wide = (int)wide_cls.size(); V.wide_cls = base + o_wide;
-	V.n_valu = 0;
-	for (int c = 0; c < C; c++) V.n_valu += engine[c] == HIBAG_ENGINE_VALU;
-	V.n_wide_scan = (int)wide_scan.size(); V.wide_scan = base + o_wscan;
-	V.n_wide_seg = (int)wseg.size() / 4; V.wide_seg = base + o_wseg; V.wide_seg_off = (const uint64_t *)(tbase + tb_wsoff);
+	if (int rc = upload_parts(m->d_int, {      // the int arrays back to back (an empty one as a single 0)
+		part(V.n_snp_c, L.n_snp_c, 4, 1), part(V.nwp, L.nwp, 4, 1), part(V.snp_off, L.snp_off, 4, 1),
+		part(V.snp_index, L.snp_index, 4, 1), part(V.snp_weight, L.snp_weight, 4, 1), part(V.mask_row, L.mask_row, 4, 1),
+		part(V.c_order, L.c_order, 4, 1), part(V.tile_p0, L.tile_p0, 4, 1), part(V.tile_n, L.tile_n, 4, 1), part(V.cls_off, L.cls_off, 4, 1),
+		part(V.cls_n, L.cls_n, 4, 1), part(V.engine, L.engine, 4, 1), part(V.n_step, L.n_step, 4, 1), part(V.bt_row, L.bt_row, 4, 1),
+		part(V.cls_nblk, L.cls_nblk, 4, 1), part(V.hap_off, L.hap_off, 4, 1), part(V.item_split, L.item, 4, 1), part(V.split_row, L.split_row, 4, 1),
+		part(V.split_cls, L.split_cls, 4, 1), part(V.item_whole, L.item_whole, 4, 1), part(V.cell_row, L.cell_row, 4, 1),
+		part(V.wide_cls, L.wide_cls, 4, 1), part(V.wide_seg, L.wseg, 4, 1), part(V.wide_scan, L.wide_scan, 4, 1)})) return rc;
+	if (int rc = upload_parts(m->d_tile, {     // the tables of the pass-1 walkers and of pass 2, at the alignment of their loads
+		part(V.stream_off, L.stream_off, 8), part(V.tile_meta, L.tile_meta, 4), part(V.cls_cnt, L.cls_cnt, 4),
+		part(V.cls_cell, L.cls_cell, 4), part(V.blk_off, L.blk_off, 8), part(V.ctile, L.ctile, 32), part(V.hap, L.hap, 16),
+		part(V.ehdr, L.ehdr, 32), part(V.etile_cstart, L.etile_cstart, 4, 1), part(V.etile_blk0, L.etile_blk0, 8),
+		part(V.blk_close, L.blk_close, 4), part(V.wide_seg_off, L.wseg_off, 8, 1)})) return rc;
+	if (int rc = upload_parts(m->d_stream, {part(V.stream, L.stream, 4)})) return rc;
+	if (int rc = upload_parts(m->d_blk, {part(V.plist, L.plist, 4)})) return rc;
+	if (int rc = upload_parts(m->d_pfac, {part(V.pfac, L.pfac, 8)})) return rc;
+	if (int rc = upload_parts(m->d_phdr, {part(V.phdr, L.phdr, 4)})) return rc;
+	if (int rc = upload_parts(m->d_parow, {{L.parow.data(), L.parow.size() * 4, std::max<size_t>(L.parow.size(), 256) * 4, 16, &V.parow}})) return rc;
+	if (int rc = upload_parts(m->d_tab, {{m->tab, sizeof(m->tab), sizeof(m->tab), 8, &V.tab}})) return rc;
+	V.n_hla = L.nh; V.n_classifier = L.C; V.n_snp = L.S; V.n_cell = L.P; V.mask_rows = L.rows; V.n_tile = L.n_tile;
+	V.n_item_split = (int)L.item.size() / 4; V.n_item_whole = (int)L.item_whole.size() / 4; V.n_split = (int)L.split_cls.size();
+	V.item = V.item_whole; V.n_item = V.n_item_whole;
+	V.all_fp4 = 1; V.n_valu = 0;
+	for (int c = 0; c < L.C; c++) {
+		if (L.n_step[c] == 1 && !(L.engine[c] == HIBAG_ENGINE_FP4)) V.all_fp4 = 0;      // (classifiers of several K steps are not work items of k_total)
+		V.n_valu += L.engine[c] == HIBAG_ENGINE_VALU;
+	}
+	V.n_wide = (int)L.wide_cls.size();
+	V.n_wide_scan = (int)L.wide_scan.size();
+	V.n_wide_seg = (int)L.wseg.size() / 4;
 	if (V.n_wide > 0 && !m->side.stream) {
 		HIP_TRY(hipStreamCreateWithFlags(&m->side.stream, hipStreamNonBlocking));
 		HIP_TRY(hipEventCreateWithFlags(&m->side.fork, hipEventDisableTiming));
 		HIP_TRY(hipEventCreateWithFlags(&m->side.join, hipEventDisableTiming));
 	}
-	V.split_heavy_ns = split_heavy_ns; V.split_rest_ns = split_rest_ns;
-	V.blk_off = (const uint64_t *)(tbase + tb_boff);
-	V.ctile = (const uint32_t *)(tbase + tb_ctile);
-	V.hap = (const uint32_t *)(tbase + tb_hap);
-	V.hap_dwords = (uint32_t)hap.size();
-	V.ehdr = (const uint32_t *)(tbase + tb_ehdr);
-	V.estream_blocks = estream_blocks;
-	V.etile_cstart = (const uint32_t *)(tbase + tb_ecst);
-	V.etile_blk0 = (const uint64_t *)(tbase + tb_eblk);
-	V.blk_close = (const uint32_t *)(tbase + tb_close);
-	V.p1_base = p1_base;
-	V.p1_blocks = dbg_b1;
-	V.cell_row = base + o_crow;
-	V.store_cells = store_mode;
+	V.split_heavy_ns = L.split_heavy_ns; V.split_rest_ns = L.split_rest_ns;
+	V.hap_dwords = (uint32_t)L.hap.size();
+	V.estream_blocks = L.estream_blocks;
+	V.p1_base = L.p1_base;
+	V.p1_blocks = L.p1_blocks;
+	V.store_cells = L.store_mode;
 	hibag_query_slots(V.slots_total, &V.slots_accum);
-	{
-		// A chunk waits for the chunk before it, which was dispatched a whole round earlier; in the worst case the chunks of
-		// an item run one after the other, so the wait is bounded by the item's own length.  One poll lasts ~1 us (s_sleep +
-		// an L2 round trip), a 32-slot block ~1.5 us of elapsed time at full occupancy: 16 polls per block of the longest
-		// item is an order of magnitude of slack on top of the fixed 2^19 (~0.5 s).
-		long long longest = 0;
-		for (int c = 0; c < C; c++) longest = std::max<long long>(longest, mfma_nkb[c] ? cls_nblk[c] : pairs[c] / 8);
-		m->spin_limit = (uint32_t)std::min<long long>(0xFFFFFFF0ll, (1ll << 19) + 16 * longest);
-	}
-	m->cell_rows = cell_row[C];
-	if (store_mode != 1 && (uint64_t)cell_row[C] >= (1ull << 23))      // (k_accum: a stored row's byte offset within a sample group in 32 bits)
-		return hibag_fail(HIBAG_HIP_EINVAL, "the model stores too many cell sums per sample (%d) for the second pass", cell_row[C]);
-	V.plist = m->d_blk.as<uint32_t>();
-	V.pfac = m->d_pfac.as<double>();
-	V.phdr = m->d_phdr.as<uint32_t>();
-	V.plist_dwords = plist.size();
-	V.parow = m->d_parow.as<uint4>();
-	V.parow_blocks = parow_blocks;
-	V.p1_prebuilt = p1_prebuilt ? 1 : 0;
-	m->bt_rows = bt_rows;
-	V.stream = m->d_stream.as<uint32_t>();
-	V.tab = m->d_tab.as<double>();
-	m->mask_rows = rows;
-	m->stream_bytes = stream.size() * sizeof(uint32_t);
-	m->engine_of.assign(engine.begin(), engine.begin() + C);
-	m->steps_of.assign(n_step.begin(), n_step.begin() + C);
+	V.plist_dwords = L.plist.size();
+	V.parow_blocks = L.parow_blocks;
+	V.p1_prebuilt = L.p1_prebuilt ? 1 : 0;
+	// A chunk waits for the chunk before it, which was dispatched a whole round earlier; in the worst case the chunks of
+	// an item run one after the other, so the wait is bounded by the item's own length.  One poll lasts ~1 us (s_sleep +
+	// an L2 round trip), a 32-slot block ~1.5 us of elapsed time at full occupancy: 16 polls per block of the longest
+	// item is an order of magnitude of slack on top of the fixed 2^19 (~0.5 s).
+	long long longest = 0;
+	for (int c = 0; c < L.C; c++) longest = std::max<long long>(longest, L.engine[c] ? L.cls_nblk[c] : L.cp[c].pairs / 8);
+	m->spin_limit = (uint32_t)std::min<long long>(0xFFFFFFF0ll, (1ll << 19) + 16 * longest);
+	m->pair_evals = L.pair_evals;
+	m->store_mode = L.store_mode;
+	m->second_pass_pairs = L.second_pass_pairs;
+	m->cell_rows = L.cell_row[L.C];
+	m->bt_rows = L.bt_rows;
+	m->mask_rows = L.rows;
+	m->stream_bytes = L.stream.size() * sizeof(uint32_t);
+	m->engine_of.assign(L.engine.begin(), L.engine.begin() + L.C);
+	m->steps_of.assign(L.n_step.begin(), L.n_step.begin() + L.C);
 	m->finalized = true;
 	return 0;
+}
+
+// The planning stages in order (any of them may reject the model, before anything is allocated), then the upload.
+int finalize_model(hibag_hip_model *m)
+{
+	if (m->finalized) return hibag_fail(HIBAG_HIP_ESTATE, "model already finalized");
+	const FinalizeOptions opt;
+	ModelLayout L(m);
+	if (int rc = plan_classifiers(m, opt, L)) return rc;
+	plan_tiles(L);
+	plan_store(opt, L);
+	if (int rc = plan_cell_lists(L)) return rc;
+	plan_work_items(L);
+	if (int rc = plan_pair_lists(m, L)) return rc;
+	plan_factors(m, L);
+	plan_parow(opt, L);
+	if (int rc = plan_ctile(L)) return rc;
+	return upload_layout(m, L);
 }
 
 } // namespace hibag_detail

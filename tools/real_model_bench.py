@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """other_configs.cfg1_real_model of bench.py by itself: the reference's bundled HLA-A model on 10,000 samples resampled from its 60
-HapMap genotypes (HIBAG_TILE_CAP=<cells per tile> to see what the tile size does to pass 2 of a model of few alleles)."""
+HapMap genotypes (a model of few alleles: pass 2 runs on small tiles, hibag_model.hip plan_tiles)."""
 import json
 import os
 import sys
