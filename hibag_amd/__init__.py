@@ -19,11 +19,12 @@ from .evaluate import (hlaAlleleSubset, hlaCompareAllele, hlaFlankingSNP, hlaGen
                        r_sample)
 from .oob import hlaOutOfBag  # noqa: F401
 from .ld import hlaGenoLD, hlaLDMatrix  # noqa: F401
+from .distance import hlaDistance  # noqa: F401
 from ._lib import HibagHipError  # noqa: F401
 
 __all__ = ["engine_kind", "engine_nkb", "engine_steps", "NA_INTEGER", "Classifier", "HlaAttrBagObj", "HlaSNPGeno", "load_geno", "load_model", "model_to_robj", "save_model",
            "HlaAlleleClass", "HlaAttrBagClass", "hlaClose", "hlaModelFromObj", "hlaModelToObj",
            "hlaPredict", "hlaSetKernelTarget", "hlaGenoSwitchStrand", "hlaSNPID", "HibagHipError",
            "HlaBEDGeno", "hlaBED2Geno", "hlaLociInfo", "RRandom", "hlaAllele", "hlaAttrBagging", "hlaConcurrentAttrBagging", "hlaParallelAttrBagging", "hlaUniqueAllele", "hlaAlleleDigit", "hlaPredMerge", "hlaAlleleSubset", "hlaCompareAllele", "hlaFlankingSNP", "hlaGenoSubset",
-           "hlaSplitAllele", "r_sample", "hlaOutOfBag", "hlaGenoLD", "hlaLDMatrix",
+           "hlaSplitAllele", "r_sample", "hlaOutOfBag", "hlaGenoLD", "hlaLDMatrix", "hlaDistance",
            "set_seed"]

@@ -41,7 +41,7 @@ EXPORTS = [
     "hibag_hip_shard_group_predict", "hibag_hip_predict_multi_sharded", "hibag_hip_measure_issue_costs",
     "hibag_hip_test_time_avg_prob", "hibag_hip_test_read_diag", "hibag_hip_plugin_degraded_calls", "hibag_hip_predict_oob",
     "hibag_hip_ld_geno_new", "hibag_hip_ld_geno_free", "hibag_hip_ld_snp_counts", "hibag_hip_ld_matrix", "hibag_hip_ld_gram_ms",
-    "hibag_hip_ld_hla",
+    "hibag_hip_ld_hla", "hibag_hip_model_distance", "hibag_hip_model_distance_ms",
 ]
 
 
@@ -105,6 +105,8 @@ def lib() -> C.CDLL:
     L.hibag_hip_ld_matrix.argtypes = [vp, vp, i32, vp, C.POINTER(i32)]
     L.hibag_hip_ld_gram_ms.argtypes = [vp, C.POINTER(dbl)]
     L.hibag_hip_ld_hla.argtypes = [vp, vp, vp, i32, vp, vp]
+    L.hibag_hip_model_distance.argtypes = [vp, vp, vp]
+    L.hibag_hip_model_distance_ms.argtypes = [vp, C.POINTER(dbl)]
     L.hibag_hip_predict_device.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]
     L.hibag_hip_predict_partial_device.argtypes = [vp, vp, i32, vp, vp]
     L.hibag_hip_finish_device.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]

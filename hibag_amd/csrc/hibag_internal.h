@@ -210,6 +210,12 @@ struct hibag_hip_model {
 	DevBuf oob_hap;
 	size_t oob_freq_at = 0, oob_off_at = 0, oob_start_at = 0;
 	bool oob_hap_ready = false;
+	// hibag_hip_model_distance (hibag_dist.hip): its own stream, workspace and timing events; it reads oob_hap, which it
+	// builds itself on a model that was never finalized (adding a classifier drops the table again)
+	hipStream_t dist_st = nullptr;
+	hipEvent_t dist_ev[2] = {nullptr, nullptr};
+	DevBuf dist_cells, dist_tri, dist_acc, dist_num, dist_out;
+	double dist_ms = 0;
 
 	KernelTimer timer;
 	std::mutex lock;
@@ -227,8 +233,11 @@ struct hibag_hip_model {
 		if (side.fork) (void)hipEventDestroy(side.fork);
 		if (side.join) (void)hipEventDestroy(side.join);
 		if (side.stream) (void)hipStreamDestroy(side.stream);
+		if (dist_st) (void)hipStreamDestroy(dist_st);
+		for (hipEvent_t e : dist_ev) if (e) (void)hipEventDestroy(e);
 		for (DevBuf *b : {&d_int, &d_stream, &d_tile, &d_tab, &d_blk, &d_pfac, &d_phdr, &d_parow, &ws_bt, &ws_bias, &ws_cells, &ws_sync, &ws_err, &ws_planes, &ws_cw, &ws_tot, &ws_inv, &ws_winv,
-		                  &ws_part, &ws_best, &ws_vrec, &ws_geno, &ws_out, &ws_codes, &ws_bed, &ws_bedidx, &oob_hap})
+		                  &ws_part, &ws_best, &ws_vrec, &ws_geno, &ws_out, &ws_codes, &ws_bed, &ws_bedidx, &oob_hap,
+		                  &dist_cells, &dist_tri, &dist_acc, &dist_num, &dist_out})
 			b->release();
 	}
 };
@@ -238,6 +247,7 @@ namespace hibag_detail {
 void build_table(double *tab);                               // hibag_model.hip: exp(d * log(1e-5)), the host libm's
 int finalize_model(hibag_hip_model *m);                      // hibag_model.hip
 int batch_limit(const hibag_hip_model *m);                   // hibag_predict.hip: samples per batch (workspace bound)
+int oob_hap_table(hibag_hip_model *m);                       // hibag_predict.hip: m->oob_hap from m->cls (once)
 
 } // namespace hibag_detail
 

@@ -24,7 +24,8 @@ extern "C" {
 #define HIBAG_HIP_ABI_VERSION 7   /* 2: + PLINK BED entries, training driver; 3: + hibag_hip_predict_mapped[_device]; 4: + hibag_hip_model_stored_cells;
                                      5: + hibag_hip_model_status / _clear_status, hibag_hip_predict_multi, hibag_hip_model_replicate, hibag_hip_model_engine;
                                      7: + hibag_hip_predict_snp_major[_device], hibag_hip_trainer_set_shared, hibag_hip_train_set_thread_budget;
-                                        later, additive (no bump): + hibag_hip_predict_oob; + the LD entries (hibag_hip_ld_*) */
+                                        later, additive (no bump): + hibag_hip_predict_oob; + the LD entries (hibag_hip_ld_*);
+                                        + hibag_hip_model_distance[_ms] */
 
 /* error codes */
 #define HIBAG_HIP_OK          0
@@ -143,6 +144,21 @@ int hibag_hip_predict(hibag_hip_model *m, const int32_t *geno, int n_samp,
  * All pointers are host memory and required when n_samp > 0; one batched launch sequence, no second pass. */
 int hibag_hip_predict_oob(hibag_hip_model *m, const int32_t *geno, int n_samp, const int32_t *samp_num,
 	int32_t *H1, int32_t *H2, double *prob);
+
+/* ---- allele distances: hlaDistance ------------------------------------------
+ * hlaDistance(model) (R/HIBAG.R:1545-1570) in one call: for each classifier HIBAG_Distance (src/HIBAG.cpp:1284-1332),
+ * m_c[a][b] = m_c[b][a] = the sum over its haplotype pairs i <= j with alleles (a, b) of f * d divided by the sum of f,
+ * f = freq[i] * freq[j], d = the number of SNPs where the two differ, both sums taken in the reference's order (NaN where
+ * the cell has no pair); then R's fold: out[a][b] = (m_1 + m_2 + ... with NaN read as 0) / (the number of classifiers
+ * whose m_c[a][b] is not NaN), NaN where that number is 0.  Bit-identical to the reference (DESIGN.md "hlaDistance").
+ *   out       float64 [n_hla][n_hla], host memory
+ *   out_each  NULL, or float64 [n_classifier][n_hla][n_hla]: each classifier's m_c, NaN kept (R's `lst` before NaN -> 0)
+ * Works on finalized models and on models that were never finalized (the prediction layout is not needed).  Runs on the
+ * model's device after any work outstanding on the model and returns when the results are on the host.  EINVAL for a
+ * NULL model or one without classifiers; ENOMEM, with the size, when n_hla is too large for the device. */
+int hibag_hip_model_distance(hibag_hip_model *m, double *out, double *out_each);
+/* Event time in milliseconds of the kernels of the model's last hibag_hip_model_distance call (for measurements). */
+int hibag_hip_model_distance_ms(const hibag_hip_model *m, double *ms);
 
 /* ---- linkage disequilibrium: hlaGenoLD / hlaLDMatrix ----------------------
  * r^2 = num^2 / (dx dy) from exact integer sums over the samples used (n, Sx, Sxx, Sy, Syy, Sxy; num = n Sxy - Sx Sy,
