@@ -15,6 +15,7 @@ from .bed import HlaBEDGeno, hlaBED2Geno, hlaLociInfo  # noqa: F401
 from .train import (RRandom, hlaAllele, hlaAttrBagging, hlaConcurrentAttrBagging, hlaParallelAttrBagging,  # noqa: F401
                     hlaUniqueAllele, set_seed)
 from .merge import hlaAlleleDigit, hlaPredMerge  # noqa: F401
+from .predmerge import hlaPredictMerge  # noqa: F401
 from .evaluate import (hlaAlleleSubset, hlaCompareAllele, hlaFlankingSNP, hlaGenoSubset, hlaSplitAllele,  # noqa: F401
                        r_sample)
 from .oob import hlaOutOfBag  # noqa: F401
@@ -25,6 +26,6 @@ from ._lib import HibagHipError  # noqa: F401
 __all__ = ["engine_kind", "engine_nkb", "engine_steps", "NA_INTEGER", "Classifier", "HlaAttrBagObj", "HlaSNPGeno", "load_geno", "load_model", "model_to_robj", "save_model",
            "HlaAlleleClass", "HlaAttrBagClass", "hlaClose", "hlaModelFromObj", "hlaModelToObj",
            "hlaPredict", "hlaSetKernelTarget", "hlaGenoSwitchStrand", "hlaSNPID", "HibagHipError",
-           "HlaBEDGeno", "hlaBED2Geno", "hlaLociInfo", "RRandom", "hlaAllele", "hlaAttrBagging", "hlaConcurrentAttrBagging", "hlaParallelAttrBagging", "hlaUniqueAllele", "hlaAlleleDigit", "hlaPredMerge", "hlaAlleleSubset", "hlaCompareAllele", "hlaFlankingSNP", "hlaGenoSubset",
+           "HlaBEDGeno", "hlaBED2Geno", "hlaLociInfo", "RRandom", "hlaAllele", "hlaAttrBagging", "hlaConcurrentAttrBagging", "hlaParallelAttrBagging", "hlaUniqueAllele", "hlaAlleleDigit", "hlaPredMerge", "hlaPredictMerge", "hlaAlleleSubset", "hlaCompareAllele", "hlaFlankingSNP", "hlaGenoSubset",
            "hlaSplitAllele", "r_sample", "hlaOutOfBag", "hlaGenoLD", "hlaLDMatrix", "hlaDistance",
            "set_seed"]

@@ -42,6 +42,8 @@ EXPORTS = [
     "hibag_hip_test_time_avg_prob", "hibag_hip_test_read_diag", "hibag_hip_plugin_degraded_calls", "hibag_hip_predict_oob",
     "hibag_hip_ld_geno_new", "hibag_hip_ld_geno_free", "hibag_hip_ld_snp_counts", "hibag_hip_ld_matrix", "hibag_hip_ld_gram_ms",
     "hibag_hip_ld_hla", "hibag_hip_model_distance", "hibag_hip_model_distance_ms",
+    "hibag_hip_merge_plan_new", "hibag_hip_merge_plan_free", "hibag_hip_merge_device", "hibag_hip_predict_merge",
+    "hibag_hip_predict_merge_bed",
 ]
 
 
@@ -107,6 +109,15 @@ def lib() -> C.CDLL:
     L.hibag_hip_ld_hla.argtypes = [vp, vp, vp, i32, vp, vp]
     L.hibag_hip_model_distance.argtypes = [vp, vp, vp]
     L.hibag_hip_model_distance_ms.argtypes = [vp, C.POINTER(dbl)]
+    L.hibag_hip_merge_plan_new.argtypes = [i32, vp, C.POINTER(vp), i32, i32]
+    L.hibag_hip_merge_plan_new.restype = vp
+    L.hibag_hip_merge_plan_free.argtypes = [vp]
+    L.hibag_hip_merge_plan_free.restype = None
+    L.hibag_hip_merge_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), vp, i32, i32, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
+    L.hibag_hip_predict_merge.argtypes = [vp, C.POINTER(vp), vp, i32, C.c_size_t, i32, i32, C.POINTER(vp), C.POINTER(vp), i32,
+                                          vp, i32, vp, vp, vp, vp, vp, vp]
+    L.hibag_hip_predict_merge_bed.argtypes = [vp, C.POINTER(vp), C.c_char_p, i32, i32, C.POINTER(vp), C.POINTER(vp), i32,
+                                              vp, i32, vp, vp, vp, vp, vp, vp]
     L.hibag_hip_predict_device.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]
     L.hibag_hip_predict_partial_device.argtypes = [vp, vp, i32, vp, vp]
     L.hibag_hip_finish_device.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]

@@ -249,6 +249,39 @@ int finalize_model(hibag_hip_model *m);                      // hibag_model.hip
 int batch_limit(const hibag_hip_model *m);                   // hibag_predict.hip: samples per batch (workspace bound)
 int oob_hap_table(hibag_hip_model *m);                       // hibag_predict.hip: m->oob_hap from m->cls (once)
 
+// ---- hibag_predict.hip's batch driver, as far as hibag_merge.hip drives it too ----
+// Where a batch's genotypes come from: the int32 matrix, or a PLINK BED payload.
+struct PackSource {
+	const int32_t *d_geno = nullptr;       // [n_samp][row_len]
+	int row_len = 0;                       // SNPs per sample in d_geno (0: the model's n_snp, model order)
+	size_t ld = 0;                         // != 0: d_geno is SNP-MAJOR, [rows][ld] with one row of genotypes per SNP (k_codes_rows); d_col = row of each model SNP
+	const int32_t *d_col = nullptr;        // [n_snp] column of each model SNP in d_geno (-1 = absent), nullptr = identity
+	const uint8_t *d_bed = nullptr;        // payload rows (see k_bed_codes)
+	int mode = 0;
+	size_t stride = 0;
+	int samp0 = 0;                         // BED sample index of the call's sample 0
+	const int32_t *d_row = nullptr, *d_flip = nullptr;
+};
+
+// Host image of the part of a BED file a call needs.  SNP-major files keep only
+// the rows of the wanted SNPs (a cohort file holds the whole genome, a model
+// ~10^2-10^3 SNPs); individual-major files are kept whole.
+struct BedImage {
+	int mode = 0;
+	size_t stride = 0;                 // bytes per row
+	std::vector<uint8_t> rows;         // payload
+	std::vector<int32_t> index;        // per wanted SNP: row (SNP-major) / column (individual-major) in `rows`, -1 = absent
+};
+
+int make_batch(hibag_hip_model *m, int n_samp, bool need_best, HibagBatchView &B);      // the model's workspace for one batch
+void run_core(hibag_hip_model *m, HibagBatchView &B, int vote_method, double *d_part, hipStream_t st);   // passes 1 and 2 behind a pack
+int check_predict_args(hibag_hip_model *m, const void *geno, int n_samp, int vote_method, const void *H1, const void *H2);
+bool take_fault(hibag_hip_model *m);                         // a hand-over failed since the last look: counted, hand-overs off
+int sticky_fault(hibag_hip_model *m);
+int workspace_enter(hibag_hip_model *m, hipStream_t st);
+int workspace_leave(hibag_hip_model *m, hipStream_t st);
+int load_bed(const char *fn, int n_samp, int n_snp, const int32_t *want, int n_want, BedImage &img);
+
 } // namespace hibag_detail
 
 #endif

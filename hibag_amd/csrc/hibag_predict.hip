@@ -183,18 +183,7 @@ struct WorkspaceGuard {
 	~WorkspaceGuard() { if (enqueued && !left && m->ws_done) { (void)hipEventRecord(m->ws_done, st); m->ws_pending = true; } }
 };
 
-// Where a batch's genotypes come from: the int32 matrix, or a PLINK BED payload.
-struct PackSource {
-	const int32_t *d_geno = nullptr;       // [n_samp][row_len]
-	int row_len = 0;                       // SNPs per sample in d_geno (0: the model's n_snp, model order)
-	size_t ld = 0;                         // != 0: d_geno is SNP-MAJOR, [rows][ld] with one row of genotypes per SNP (k_codes_rows); d_col = row of each model SNP
-	const int32_t *d_col = nullptr;        // [n_snp] column of each model SNP in d_geno (-1 = absent), nullptr = identity
-	const uint8_t *d_bed = nullptr;        // payload rows (see k_bed_codes)
-	int mode = 0;
-	size_t stride = 0;
-	int samp0 = 0;                         // BED sample index of the call's sample 0
-	const int32_t *d_row = nullptr, *d_flip = nullptr;
-};
+// (struct PackSource: hibag_internal.h)
 
 int predict_device_locked(hibag_hip_model *m, const PackSource &src, int n_samp, int vote_method,
 	int32_t *d_H1, int32_t *d_H2, double *d_max_prob, double *d_matching, double *d_dosage,
@@ -463,15 +452,7 @@ int predict_staged_locked(hibag_hip_model *m, const int32_t *geno, const PackSou
 // ---------------------------------------------------------------------------
 // PLINK BED files (HIBAG_BEDFlag / HIBAG_ConvBED, src/HIBAG.cpp:1068-1191)
 
-// Host image of the part of a BED file a call needs.  SNP-major files keep only
-// the rows of the wanted SNPs (a cohort file holds the whole genome, a model
-// ~10^2-10^3 SNPs); individual-major files are kept whole.
-struct BedImage {
-	int mode = 0;
-	size_t stride = 0;                 // bytes per row
-	std::vector<uint8_t> rows;         // payload
-	std::vector<int32_t> index;        // per wanted SNP: row (SNP-major) / column (individual-major) in `rows`, -1 = absent
-};
+// (struct BedImage: hibag_internal.h)
 
 int read_bed_prefix(FILE *f, int *mode)
 {

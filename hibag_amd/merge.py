@@ -1,12 +1,15 @@
 """``hlaPredMerge`` (``R/HIBAG.R:825-1023``): combine the posterior matrices of several
 ``hlaPredict(..., type="response+prob")`` results (e.g. models trained for different SNP
-arrays or ancestries) into one call per sample.  Host-side post-processing behind the hot
-path: O(#pairs x #samples) adds, done with the reference's operation order
+arrays or ancestries) into one call per sample, on the host, for results that already are
+there: O(#pairs x #samples) adds, done with the reference's operation order
 (``HIBAG_SumList`` / ``HIBAG_UpdateAddProbW`` / ``HIBAG_NormalizeProb``,
-``src/HIBAG.cpp:1455-1547``)."""
+``src/HIBAG.cpp:1455-1547``).  ``hlaPredictMerge`` (``predmerge.py``) predicts with the k models
+and merges on the device, bit-identical to this function; :func:`merge_plan` restates the
+name work below as one function for it (tests/test_predmerge_host.py holds the two together)."""
 
 from __future__ import annotations
 
+from dataclasses import dataclass
 from typing import Dict, List, Optional, Sequence
 
 import numpy as np
@@ -35,6 +38,71 @@ def hlaAlleleDigit(alleles: Sequence[Optional[str]], max_resolution: str = "", r
             f[-1] = f[-1].rstrip("".join(c for c in set(f[-1]) if not c.isdigit()))
         out.append(":".join(f))
     return out
+
+
+@dataclass
+class MergePlan:
+    """What the names decide in a merge of k models' posteriors (:func:`merge_plan`); everything else is arithmetic.
+
+    Merged rows are the pairs of ``hla_allele`` in the posterior vector's order (:func:`hibag_amd.hibag._pair_names`).
+    The two gather structures are CSR: ``x_off[r] : x_off[r + 1]`` delimits the entries of row / allele ``r``."""
+    hla_allele: List[str]            # the merged allele list, n alleles
+    pair_names: List[str]            # the P = n (n + 1) / 2 merged rows
+    row_of_cell: List[np.ndarray]    # per model: int32 [n_cell_i], source cell -> merged row (many-to-one after a replacement)
+    gather_off: np.ndarray           # int64 [P + 1]; per merged row its source cells ...
+    gather_model: np.ndarray         # int32 ... (model, source cell) in model order, then ascending source cell
+    gather_cell: np.ndarray          # int32
+    first_off: np.ndarray            # int64 [n + 1]; per merged allele the ascending rows whose FIRST name it is
+    first_rows: np.ndarray           # int32 [P]
+    second_off: np.ndarray           # int64 [n + 1]; ... and the ascending rows whose SECOND name it is
+    second_rows: np.ndarray          # int32 [P]
+
+    @property
+    def n_row(self) -> int:
+        return len(self.pair_names)
+
+
+def merge_plan(allele_lists: Sequence[Sequence[str]], equivalence: Optional[Dict[str, str]] = None, max_resolution: str = "",
+               rm_suffix: bool = False) -> MergePlan:
+    """The name work of ``hlaPredMerge`` (``R/HIBAG.R:905-957``) for models with the allele lists ``allele_lists``
+    (``model.hla_allele`` each): every allele is replaced through ``equivalence`` (old name -> new name), then
+    ``hlaAlleleDigit``; the merged list is ``hlaUniqueAllele`` of the union; a model's pair ``a/b`` goes to the merged row
+    named ``a'/b'`` or, failing that, ``b'/a'``."""
+    if not allele_lists:
+        raise ValueError("no allele list given")
+    use_resolution = max_resolution != "" or rm_suffix
+
+    def replace(alleles: List[str]) -> List[str]:
+        if equivalence:
+            alleles = [equivalence.get(a, a) for a in alleles]
+        if use_resolution:
+            alleles = hlaAlleleDigit(alleles, max_resolution, rm_suffix)
+        return alleles
+
+    replaced = [replace(list(a)) for a in allele_lists]
+    hla_allele = hlaUniqueAllele([a for r in replaced for a in r])
+    n = len(hla_allele)
+    lut = {a: i for i, a in enumerate(hla_allele)}
+    row_of_cell = []
+    for r in replaced:
+        idx = np.array([lut[a] for a in r], np.int64)
+        i, j = np.triu_indices(len(r))                   # source cell (i, j), i <= j, is named a[j]/a[i]: the posterior's order
+        lo, hi = np.minimum(idx[i], idx[j]), np.maximum(idx[i], idx[j])
+        row_of_cell.append((hi + lo * (2 * n - lo - 1) // 2).astype(np.int32))     # the row named hi/lo, whichever way round
+    P = n * (n + 1) // 2
+    model = np.concatenate([np.full(len(r), m, np.int32) for m, r in enumerate(row_of_cell)])
+    cell = np.concatenate([np.arange(len(r), dtype=np.int32) for r in row_of_cell])
+    rows = np.concatenate(row_of_cell)
+    order = np.argsort(rows, kind="stable")              # (model, cell) ascending inside every row
+    gather_off = np.concatenate([[0], np.cumsum(np.bincount(rows, minlength=P))]).astype(np.int64)
+    i, j = np.triu_indices(n)                            # merged row (i, j) is named allele[j]/allele[i]
+    all_rows = np.arange(P, dtype=np.int32)
+    by_first = np.argsort(j, kind="stable")
+    off = np.concatenate([[0], np.cumsum(np.bincount(j, minlength=n))]).astype(np.int64)
+    off2 = np.concatenate([[0], np.cumsum(np.bincount(i, minlength=n))]).astype(np.int64)
+    return MergePlan(hla_allele=hla_allele, pair_names=_pair_names(hla_allele), row_of_cell=row_of_cell,
+                     gather_off=gather_off, gather_model=model[order], gather_cell=cell[order],
+                     first_off=off, first_rows=all_rows[by_first], second_off=off2, second_rows=all_rows)
 
 
 def hlaPredMerge(*pdlist: HlaAlleleClass, weight: Optional[Sequence[float]] = None,

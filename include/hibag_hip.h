@@ -25,7 +25,7 @@ extern "C" {
                                      5: + hibag_hip_model_status / _clear_status, hibag_hip_predict_multi, hibag_hip_model_replicate, hibag_hip_model_engine;
                                      7: + hibag_hip_predict_snp_major[_device], hibag_hip_trainer_set_shared, hibag_hip_train_set_thread_budget;
                                         later, additive (no bump): + hibag_hip_predict_oob; + the LD entries (hibag_hip_ld_*);
-                                        + hibag_hip_model_distance[_ms] */
+                                        + hibag_hip_model_distance[_ms]; + the merge entries (hibag_hip_merge_*, hibag_hip_predict_merge[_bed]) */
 
 /* error codes */
 #define HIBAG_HIP_OK          0
@@ -192,6 +192,59 @@ int hibag_hip_ld_gram_ms(hibag_hip_ld_geno *g, double *ms);
  *   r2_or_null         float64 [n_snp][n_allele], the single r^2 values (may be NULL) */
 int hibag_hip_ld_hla(hibag_hip_ld_geno *g, const int32_t *allele1, const int32_t *allele2, int n_allele,
 	double *ld, double *r2_or_null);
+
+/* ---- several models of one locus, merged: hlaPredMerge on the device ----------
+ * hlaPredMerge(hlaPredict(m1, type = "response+prob"), hlaPredict(m2, ...), ...) (R/HIBAG.R:825-1023 around HIBAG_SumList,
+ * HIBAG_UpdateAddProbW, HIBAG_NormalizeProb, src/HIBAG.cpp:1455-1547) without the k posterior matrices leaving the device,
+ * bit-identical to the merge of the k host results.  The NAMES (allele replacement, the merged allele list, which merged
+ * pair a model's pair becomes) are the host's business; the plan takes their outcome:
+ *   n_src_cell[i]      allele pairs of model i, n_hla_i (n_hla_i + 1) / 2, in hibag_hip_predict's postprob order
+ *   row_of_cell[i][j]  merged row of model i's pair j; merged rows are the pairs of the n_merged_hla merged alleles in the
+ *                      same order (row (a, b), a <= b, at b + a (2 n - a - 1) / 2 is named allele[b] "/" allele[a]); a map
+ *                      may send several pairs to one row, and a row may have none
+ * With weights w (given normalised, sum 1) and per sample s:
+ *   matching[s] = 0 + w[0] matching_0[s] + w[1] matching_1[s] + ...          (in model order)
+ *   acc[r][s]   = 0 + the terms p_i[j][s] * w2_i[s] of row r, in model order, then ascending j;
+ *                 w2_i[s] = w[i] * matching_i[s] if use_matching, else w[i]; product rounded, then the sum
+ *   postprob[r][s] = acc[r][s] / (0 + acc[0][s] + acc[1][s] + ...)           (rows ascending; an IEEE division)
+ *   the call    = the first maximum of postprob[.][s] in row order, NaN read as -infinity: H2 = b (the row's first name),
+ *                 H1 = a, max_prob = that row's value (NaN where the whole column is)
+ *   dosage[a][s] = (the sum of postprob over the rows whose first name is a, ascending) + (the same for the second name)
+ * Output MATRICES are row-major with the sample fastest -- dosage [n_merged_hla][ld], postprob [rows][ld] -- the memory of
+ * hlaPredMerge's own matrices, not the sample-major form of hibag_hip_predict.  At most 16 models.
+ * Device memory: the merged matrix is made for one chunk of samples at a time, chunks sized so that it stays within
+ * HIBAG_HIP_MERGE_BUDGET_BYTES (and a chunk is one batch of every model); the k posterior matrices are never materialised
+ * by hibag_hip_predict_merge, which reads each model's un-normalised ensemble sums.  The environment variable
+ * HIBAG_MERGE_CHUNK (samples) asks for smaller chunks; results do not depend on the chunking. */
+#define HIBAG_HIP_MERGE_BUDGET_BYTES ((size_t)1 << 30)
+typedef struct hibag_hip_merge_plan hibag_hip_merge_plan;
+/* NULL on failure (hibag_hip_last_error says why).  The plan lives on `device`, where its models must be. */
+hibag_hip_merge_plan *hibag_hip_merge_plan_new(int n_models, const int32_t *n_src_cell, const int32_t *const *row_of_cell,
+	int n_merged_hla, int device);
+void hibag_hip_merge_plan_free(hibag_hip_merge_plan *plan);
+/* The merge alone, on device buffers: d_postprob[i] [n_samp][n_src_cell[i]] and d_matching[i] [n_samp] as
+ * hibag_hip_predict_device wrote them.  Enqueued on `stream`, no synchronisation; any output may be NULL (H1 and H2 only
+ * together); ld_out >= n_samp is the row stride of d_dosage and d_postprob_out.  The plan owns the scratch of the merge:
+ * calls on one plan go to one stream, or are ordered by the caller. */
+int hibag_hip_merge_device(hibag_hip_merge_plan *plan, const double *const *d_postprob, const double *const *d_matching,
+	const double *weight, int use_matching, int n_samp, int32_t *d_H1, int32_t *d_H2, double *d_max_prob,
+	double *d_matching_out, double *d_dosage, double *d_postprob_out, size_t ld_out, void *stream);
+/* Host-pointer form, predictions included: uploads the cohort once, then per chunk of samples runs the k predictions
+ * (vote_method as in hibag_hip_predict) and the merge behind them on one stream and copies down the outputs that are not
+ * NULL (dosage [n_merged_hla][n_samp], postprob [rows][n_samp]).  models[i] are distinct finalized models on the plan's
+ * device; the call holds their locks and repairs a failed hand-over like the other host-pointer entries.
+ *   geno     the cohort's matrix: int32 [n_samp][n_geno_snp] (snp_major == 0, ld ignored) or [n_geno_snp][ld] (snp_major != 0)
+ *   snp_col[i][model i's n_snp]  column / row of each SNP of model i in geno, -1 = absent; snp_col or snp_col[i] NULL =
+ *            the model's SNPs are the first n_snp of the cohort, in order
+ *   flip[i]  NULL, or != 0 where the allele count is reversed (as hibag_hip_predict_mapped)
+ * The _bed form reads a PLINK BED file like hibag_hip_predict_bed (snp_col[i][.] = BED SNP index, required). */
+int hibag_hip_predict_merge(hibag_hip_merge_plan *plan, hibag_hip_model *const *models, const int32_t *geno, int snp_major,
+	size_t ld, int n_samp, int n_geno_snp, const int32_t *const *snp_col, const int32_t *const *flip, int vote_method,
+	const double *weight, int use_matching, int32_t *H1, int32_t *H2, double *max_prob, double *matching, double *dosage,
+	double *postprob);
+int hibag_hip_predict_merge_bed(hibag_hip_merge_plan *plan, hibag_hip_model *const *models, const char *bed_fn, int n_samp,
+	int n_snp, const int32_t *const *snp_col, const int32_t *const *flip, int vote_method, const double *weight,
+	int use_matching, int32_t *H1, int32_t *H2, double *max_prob, double *matching, double *dosage, double *postprob);
 
 /* Device-pointer form of the same call: every pointer is device memory on the
  * model's device, work is enqueued on `stream` (a hipStream_t, NULL = default
