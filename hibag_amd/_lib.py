@@ -43,7 +43,7 @@ EXPORTS = [
     "hibag_hip_ld_geno_new", "hibag_hip_ld_geno_free", "hibag_hip_ld_snp_counts", "hibag_hip_ld_matrix", "hibag_hip_ld_gram_ms",
     "hibag_hip_ld_hla", "hibag_hip_model_distance", "hibag_hip_model_distance_ms",
     "hibag_hip_merge_plan_new", "hibag_hip_merge_plan_free", "hibag_hip_merge_device", "hibag_hip_predict_merge",
-    "hibag_hip_predict_merge_bed",
+    "hibag_hip_predict_merge_bed", "hibag_hip_predict_prefix", "hibag_hip_predict_prefix_ms",
 ]
 
 
@@ -99,6 +99,8 @@ def lib() -> C.CDLL:
     L.hibag_hip_model_mutation_table.argtypes = [vp, vp]
     L.hibag_hip_predict.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp]
     L.hibag_hip_predict_oob.argtypes = [vp, vp, i32, vp, vp, vp, vp]
+    L.hibag_hip_predict_prefix.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp, vp]
+    L.hibag_hip_predict_prefix_ms.argtypes = [vp, C.POINTER(dbl)]
     L.hibag_hip_ld_geno_new.argtypes = [vp, i32, i32, i32]
     L.hibag_hip_ld_geno_new.restype = vp
     L.hibag_hip_ld_geno_free.argtypes = [vp]

@@ -3,6 +3,7 @@
 // cross the files:
 //   hibag_api.hip      error state, device selection, kernel target, the plugin table
 //   hibag_model.hip    the model: classifiers in, the device layout out (hibag_hip_model_new ... _finalize, replicas, shards)
+//   hibag_prefix.hip   hibag_hip_predict_prefix: every sub-model "first k classifiers" from one pass 1
 //   hibag_predict.hip  the batch driver that replaces CAttrBag_Model::PredictHLA: workspace, kernel sequence, host-pointer
 //                      pipeline, BED input, partial sums, launch status, timing
 #ifndef HIBAG_INTERNAL_H_
@@ -216,6 +217,12 @@ struct hibag_hip_model {
 	hipEvent_t dist_ev[2] = {nullptr, nullptr};
 	DevBuf dist_cells, dist_tri, dist_acc, dist_num, dist_out;
 	double dist_ms = 0;
+	// hibag_hip_predict_prefix (hibag_prefix.hip): the second layout of this model, finalized with every cell sum stored
+	// (built at the first call on a model whose own layout is not store mode 1, never touched by the other entries), and
+	// the entry's workspace: the sub-models' SNP counts, their classifier weights, the tiles' maxima
+	hibag_hip_model *prefix_layout = nullptr;
+	DevBuf pfx_tab, pfx_cw, pfx_best, pfx_cell;
+	double pfx_accum_ms = 0;
 
 	KernelTimer timer;
 	std::mutex lock;
@@ -237,8 +244,9 @@ struct hibag_hip_model {
 		for (hipEvent_t e : dist_ev) if (e) (void)hipEventDestroy(e);
 		for (DevBuf *b : {&d_int, &d_stream, &d_tile, &d_tab, &d_blk, &d_pfac, &d_phdr, &d_parow, &ws_bt, &ws_bias, &ws_cells, &ws_sync, &ws_err, &ws_planes, &ws_cw, &ws_tot, &ws_inv, &ws_winv,
 		                  &ws_part, &ws_best, &ws_vrec, &ws_geno, &ws_out, &ws_codes, &ws_bed, &ws_bedidx, &oob_hap,
-		                  &dist_cells, &dist_tri, &dist_acc, &dist_num, &dist_out})
+		                  &dist_cells, &dist_tri, &dist_acc, &dist_num, &dist_out, &pfx_tab, &pfx_cw, &pfx_best, &pfx_cell})
 			b->release();
+		delete prefix_layout;
 	}
 };
 
@@ -246,6 +254,7 @@ namespace hibag_detail {
 
 void build_table(double *tab);                               // hibag_model.hip: exp(d * log(1e-5)), the host libm's
 int finalize_model(hibag_hip_model *m);                      // hibag_model.hip
+int finalize_model_stream(hibag_hip_model *m);               // hibag_model.hip: the same with FinalizeOptions::STREAM (every cell sum stored), whatever the environment says
 int batch_limit(const hibag_hip_model *m);                   // hibag_predict.hip: samples per batch (workspace bound)
 int oob_hap_table(hibag_hip_model *m);                       // hibag_predict.hip: m->oob_hap from m->cls (once)
 
@@ -280,6 +289,7 @@ bool take_fault(hibag_hip_model *m);                         // a hand-over fail
 int sticky_fault(hibag_hip_model *m);
 int workspace_enter(hibag_hip_model *m, hipStream_t st);
 int workspace_leave(hibag_hip_model *m, hipStream_t st);
+int staged_streams(hibag_hip_model *m, StagedStreams **out);  // the model's streams of the host-pointer entries (created on first use)
 int load_bed(const char *fn, int n_samp, int n_snp, const int32_t *want, int n_want, BedImage &img);
 
 } // namespace hibag_detail

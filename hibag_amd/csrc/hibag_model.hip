@@ -883,10 +883,9 @@ int upload_layout(hibag_hip_model *m, const ModelLayout &L)
 }
 
 // The planning stages in order (any of them may reject the model, before anything is allocated), then the upload.
-int finalize_model(hibag_hip_model *m)
+static int finalize_with(hibag_hip_model *m, const FinalizeOptions &opt)
 {
 	if (m->finalized) return hibag_fail(HIBAG_HIP_ESTATE, "model already finalized");
-	const FinalizeOptions opt;
 	ModelLayout L(m);
 	if (int rc = plan_classifiers(m, opt, L)) return rc;
 	plan_tiles(L);
@@ -898,6 +897,15 @@ int finalize_model(hibag_hip_model *m)
 	plan_parow(opt, L);
 	if (int rc = plan_ctile(L)) return rc;
 	return upload_layout(m, L);
+}
+
+int finalize_model(hibag_hip_model *m) { return finalize_with(m, FinalizeOptions()); }
+
+int finalize_model_stream(hibag_hip_model *m)
+{
+	FinalizeOptions opt;
+	opt.pass2 = FinalizeOptions::STREAM;
+	return finalize_with(m, opt);
 }
 
 } // namespace hibag_detail

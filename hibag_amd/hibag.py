@@ -226,6 +226,30 @@ class HlaAttrBagClass:
                                                     _as_ptr(out["h2"]), _as_ptr(out["prob"])))
         return out
 
+    def predict_prefix(self, genomat: np.ndarray, sizes) -> dict:
+        """``hibag_hip_predict_prefix``: for every ``sizes[i]`` (strictly ascending, 1 .. n_classifier) what
+        ``predict_raw`` (vote by probability) returns for the model of the first ``sizes[i]`` classifiers
+        (``hlaSubModelObj``) -- ``h1``, ``h2``, ``prob``, ``matching``, each [n_sizes, n_samp] -- from one pass 1.
+        ``genomat`` int32 [n_samp, n_snp]."""
+        g = np.ascontiguousarray(genomat, np.int32)
+        if g.ndim != 2 or g.shape[1] != self.obj.n_snp:
+            raise ValueError("genomat must be [n_samp, n.snp] int32")
+        sz = np.ascontiguousarray(sizes, np.int32)
+        if sz.ndim != 1:
+            raise ValueError("sizes must be a vector")
+        n, k = g.shape[0], len(sz)
+        out = {"h1": np.empty((k, n), np.int32), "h2": np.empty((k, n), np.int32), "prob": np.empty((k, n), np.float64),
+               "matching": np.empty((k, n), np.float64)}
+        _lib.check(_lib.lib().hibag_hip_predict_prefix(self.handle, _as_ptr(g), n, _as_ptr(sz), k, _as_ptr(out["h1"]),
+                                                       _as_ptr(out["h2"]), _as_ptr(out["prob"]), _as_ptr(out["matching"])))
+        return out
+
+    def prefix_accum_ms(self) -> float:
+        """Event time (ms) of ``k_prefix_accum`` in the model's last ``predict_prefix`` call."""
+        ms = C.c_double()
+        _lib.check(_lib.lib().hibag_hip_predict_prefix_ms(self.handle, C.byref(ms)))
+        return ms.value
+
     def predict_bed(self, bed_fn: str, n_samp: int, n_snp: int, snp_col: np.ndarray, flip: Optional[np.ndarray] = None,
                     vote_method: int = 1, want_dosage: bool = True, want_prob: bool = False) -> dict:
         """``PredictHLA`` on every sample of a PLINK BED file (``hibag_hip_predict_bed``):

@@ -25,7 +25,8 @@ extern "C" {
                                      5: + hibag_hip_model_status / _clear_status, hibag_hip_predict_multi, hibag_hip_model_replicate, hibag_hip_model_engine;
                                      7: + hibag_hip_predict_snp_major[_device], hibag_hip_trainer_set_shared, hibag_hip_train_set_thread_budget;
                                         later, additive (no bump): + hibag_hip_predict_oob; + the LD entries (hibag_hip_ld_*);
-                                        + hibag_hip_model_distance[_ms]; + the merge entries (hibag_hip_merge_*, hibag_hip_predict_merge[_bed]) */
+                                        + hibag_hip_model_distance[_ms]; + the merge entries (hibag_hip_merge_*, hibag_hip_predict_merge[_bed]);
+                                        + hibag_hip_predict_prefix[_ms] */
 
 /* error codes */
 #define HIBAG_HIP_OK          0
@@ -159,6 +160,29 @@ int hibag_hip_predict_oob(hibag_hip_model *m, const int32_t *geno, int n_samp, c
 int hibag_hip_model_distance(hibag_hip_model *m, double *out, double *out_each);
 /* Event time in milliseconds of the kernels of the model's last hibag_hip_model_distance call (for measurements). */
 int hibag_hip_model_distance_ms(const hibag_hip_model *m, double *ms);
+
+/* ---- every ensemble size at once: hlaPredictCurve ------------------------
+ * For every sizes[i]: what hibag_hip_predict(vote_method = 1) returns for the model made of the first sizes[i] classifiers
+ * of `m` (hlaSubModelObj, R/HIBAG.R:1121-1129 -- the SNP weights are that sub-model's own, src/LibHLA.cpp:2484-2496) --
+ * the best-guess pair, its posterior probability and the matching proportion -- from ONE pack and ONE pass 1 over all
+ * classifiers plus a read-back fold per size.  Every output is bit-identical to the sub-model's own prediction, NA calls
+ * and NaN included.
+ *   geno      int32 [n_samp][n_snp], host memory, the model's SNPs in model order (as hibag_hip_predict)
+ *   sizes     int32 [n_sizes], strictly ascending, 1 <= sizes[i] <= n_classifier; EINVAL otherwise
+ *   H1, H2    int32 [n_sizes][n_samp], 0-based alleles or NA_integer_
+ *   prob, matching   float64 [n_sizes][n_samp]
+ * All four outputs are required.  The dosage and the posterior matrix are not produced (they would be n_sizes matrices),
+ * and there is no majority-vote variant.  The entry needs every cell sum kept by pass 1: on a model whose own layout keeps
+ * fewer it builds, at its first call, a second layout of the same classifiers that does, owned by the handle (device
+ * memory: a second copy of the model's tables and a second workspace); the model's other entries never see it.  Samples go
+ * in batches of at most hibag_hip_model_batch_limit(), fewer where the sub-models' weights (8 bytes per sample for every
+ * classifier of every size) would exceed 8 GB; HIBAG_PREFIX_BATCH (diagnostic) lowers the batch further.  A failed
+ * hand-over is repaired by one run without hand-overs; HIBAG_HIP_EHANDOVER if that fails too.  EINVAL for a classifier
+ * shard (hibag_hip_model_shard: its SNP weights are another model's). */
+int hibag_hip_predict_prefix(hibag_hip_model *m, const int32_t *geno, int n_samp, const int32_t *sizes, int n_sizes,
+	int32_t *H1, int32_t *H2, double *prob, double *matching);
+/* Event time in milliseconds of k_prefix_accum (all batches) in the model's last hibag_hip_predict_prefix call. */
+int hibag_hip_predict_prefix_ms(const hibag_hip_model *m, double *accum_ms);
 
 /* ---- linkage disequilibrium: hlaGenoLD / hlaLDMatrix ----------------------
  * r^2 = num^2 / (dx dy) from exact integer sums over the samples used (n, Sx, Sxx, Sy, Syy, Sxy; num = n Sxy - Sx Sy,
