@@ -23,6 +23,7 @@ from .ld import hlaGenoLD, hlaLDMatrix  # noqa: F401
 from .distance import hlaDistance  # noqa: F401
 from .submodel import hlaCombineModelObj, hlaSubModelObj  # noqa: F401
 from .curve import HlaPredictCurve, hlaPredictCurve  # noqa: F401
+from .topk import HlaTopCalls, hlaPredictTopK  # noqa: F401
 from ._lib import HibagHipError  # noqa: F401
 
 __all__ = ["engine_kind", "engine_nkb", "engine_steps", "NA_INTEGER", "Classifier", "HlaAttrBagObj", "HlaSNPGeno", "load_geno", "load_model", "model_to_robj", "save_model",
@@ -30,5 +31,5 @@ __all__ = ["engine_kind", "engine_nkb", "engine_steps", "NA_INTEGER", "Classifie
            "hlaPredict", "hlaSetKernelTarget", "hlaGenoSwitchStrand", "hlaSNPID", "HibagHipError",
            "HlaBEDGeno", "hlaBED2Geno", "hlaLociInfo", "RRandom", "hlaAllele", "hlaAttrBagging", "hlaConcurrentAttrBagging", "hlaParallelAttrBagging", "hlaUniqueAllele", "hlaAlleleDigit", "hlaPredMerge", "hlaPredictMerge", "hlaAlleleSubset", "hlaCompareAllele", "hlaFlankingSNP", "hlaGenoSubset",
            "hlaSplitAllele", "r_sample", "hlaOutOfBag", "hlaGenoLD", "hlaLDMatrix", "hlaDistance",
-           "hlaSubModelObj", "hlaCombineModelObj", "hlaPredictCurve", "HlaPredictCurve",
+           "hlaSubModelObj", "hlaCombineModelObj", "hlaPredictCurve", "HlaPredictCurve", "hlaPredictTopK", "HlaTopCalls",
            "set_seed"]

@@ -44,7 +44,10 @@ EXPORTS = [
     "hibag_hip_ld_hla", "hibag_hip_model_distance", "hibag_hip_model_distance_ms",
     "hibag_hip_merge_plan_new", "hibag_hip_merge_plan_free", "hibag_hip_merge_device", "hibag_hip_predict_merge",
     "hibag_hip_predict_merge_bed", "hibag_hip_predict_prefix", "hibag_hip_predict_prefix_ms",
+    "hibag_hip_predict_topk", "hibag_hip_predict_topk_device", "hibag_hip_predict_topk_mapped",
+    "hibag_hip_predict_topk_snp_major", "hibag_hip_predict_topk_bed",
 ]
+TOPK_MAX = 16      # HIBAG_HIP_TOPK_MAX of include/hibag_hip.h
 
 
 class HibagHipError(RuntimeError):
@@ -101,6 +104,11 @@ def lib() -> C.CDLL:
     L.hibag_hip_predict_oob.argtypes = [vp, vp, i32, vp, vp, vp, vp]
     L.hibag_hip_predict_prefix.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp, vp]
     L.hibag_hip_predict_prefix_ms.argtypes = [vp, C.POINTER(dbl)]
+    L.hibag_hip_predict_topk.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp]
+    L.hibag_hip_predict_topk_device.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]
+    L.hibag_hip_predict_topk_mapped.argtypes = [vp, vp, i32, i32, vp, vp, i32, i32, vp, vp, vp, vp]
+    L.hibag_hip_predict_topk_snp_major.argtypes = [vp, vp, C.c_size_t, i32, i32, vp, vp, i32, i32, vp, vp, vp, vp]
+    L.hibag_hip_predict_topk_bed.argtypes = [vp, C.c_char_p, i32, i32, vp, vp, i32, i32, vp, vp, vp, vp]
     L.hibag_hip_ld_geno_new.argtypes = [vp, i32, i32, i32]
     L.hibag_hip_ld_geno_new.restype = vp
     L.hibag_hip_ld_geno_free.argtypes = [vp]

@@ -272,6 +272,16 @@ struct PackSource {
 	const int32_t *d_row = nullptr, *d_flip = nullptr;
 };
 
+// The output set of the top-k entries (hibag_hip_predict_topk*), next to d_postprob in the two drivers of hibag_predict.hip:
+// per sample the k best pairs and their probabilities, [n_samp][k] each -- device pointers for predict_device_locked,
+// the caller's host arrays for predict_staged_locked.  With it the finish is k_finish_topk instead of the call / dosage /
+// posterior kernels (those outputs are not asked for by the entries that pass it).
+struct TopKOut {
+	int k = 0;
+	int32_t *h1 = nullptr, *h2 = nullptr;
+	double *prob = nullptr;
+};
+
 // Host image of the part of a BED file a call needs.  SNP-major files keep only
 // the rows of the wanted SNPs (a cohort file holds the whole genome, a model
 // ~10^2-10^3 SNPs); individual-major files are kept whole.

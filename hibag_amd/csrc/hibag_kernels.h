@@ -33,6 +33,12 @@ void hibag_launch_scalars(const HibagModelView &M, const HibagBatchView &B, cons
 void hibag_launch_finish(const HibagModelView &M, const HibagBatchView &B, double *d_part,
 	int32_t *d_H1, int32_t *d_H2, double *d_max_prob, double *d_matching,
 	double *d_dosage, double *d_postprob, hipStream_t st);
+// The finish of the top-k entries (hibag_k_topk.h), launched INSTEAD of hibag_launch_finish: per sample the k largest
+// cells of the normalised ensemble matrix as pairs d_H1 / d_H2 [n_samp][k] with d_prob [n_samp][k], and d_matching [n_samp]
+// (may be nullptr); 1 <= k <= HIBAG_TOPK_MAX (= HIBAG_HIP_TOPK_MAX of the public header).
+#define HIBAG_TOPK_MAX 16
+void hibag_launch_finish_topk(const HibagModelView &M, const HibagBatchView &B, double *d_part, int k,
+	int32_t *d_H1, int32_t *d_H2, double *d_prob, double *d_matching, hipStream_t st);
 // hlaOutOfBag (hibag_k_oob.h): each classifier predicts its own out-of-bag samples.  The per-classifier arrays are
 // [C][ld] with the batch's sample 0 at column 0 (the caller offsets the pointers); the plain haplotype table (grouped by
 // allele, hla_start[c][n_hla + 1] relative to hap_off[c]) serves the rare lane whose record log cannot settle its call.

@@ -82,6 +82,7 @@ static_assert(2 * HIBAG_FP4_MAX_SNPS + 1 <= ACCUM_TAB_N, "pass 2's table must co
 #include "hibag_k_pass2.h"
 #include "hibag_k_vote.h"
 #include "hibag_k_finish.h"
+#include "hibag_k_topk.h"
 #include "hibag_k_oob.h"
 
 // ---------------------------------------------------------------------------
@@ -299,6 +300,20 @@ void hibag_launch_finish(const HibagModelView &M, const HibagBatchView &B, doubl
 	if (d_postprob)
 		hipLaunchKernelGGL(k_finish_prob, dim3(B.n_pad / 64, (M.n_cell + 63) / 64), dim3(256), 0, st,
 			M, B, (const double *)d_part, d_postprob);
+}
+
+// the finish of the top-k entries, in place of hibag_launch_finish: the smallest list bound that holds k (hibag_k_topk.h)
+void hibag_launch_finish_topk(const HibagModelView &M, const HibagBatchView &B, double *d_part, int k,
+	int32_t *d_H1, int32_t *d_H2, double *d_prob, double *d_matching, hipStream_t st)
+{
+	static_assert(HIBAG_TOPK_MAX == 16, "one instantiation of k_finish_topk per list bound up to HIBAG_TOPK_MAX");
+	if (k < 1 || k > HIBAG_TOPK_MAX) return;            // (the entries have checked k)
+#define LAUNCH_TOPK(KMAX) hipLaunchKernelGGL(k_finish_topk<KMAX>, dim3(B.n_pad / 64), dim3(64 * (64 / KMAX)), 0, st, M, B, \
+		(const double *)d_part, k, d_H1, d_H2, d_prob, d_matching)
+	if (k <= 4) LAUNCH_TOPK(4);
+	else if (k <= 8) LAUNCH_TOPK(8);
+	else LAUNCH_TOPK(16);
+#undef LAUNCH_TOPK
 }
 
 void hibag_launch_oob(const HibagModelView &M, const HibagBatchView &B, const uint8_t *d_codes, const HibagOobOut &O,

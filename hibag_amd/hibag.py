@@ -49,8 +49,23 @@ def hlaSetKernelTarget(cpu: str = "hip") -> List[str]:
     return [_kernel_info]
 
 
+def _kernel_info_text() -> str:
+    """What the last :func:`hlaSetKernelTarget` reported (the line ``hlaPredict`` prints)."""
+    return _kernel_info
+
+
 def _as_ptr(a: Optional[np.ndarray]):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def topk_k(k) -> int:
+    """The ``k`` of the top-k entries as an int within 1 .. ``HIBAG_HIP_TOPK_MAX``; ``ValueError`` otherwise."""
+    ok = isinstance(k, (int, np.integer)) and not isinstance(k, (bool, np.bool_))
+    if not ok and isinstance(k, (float, np.floating)) and float(k).is_integer():
+        ok = True
+    if not ok or not (1 <= int(k) <= _lib.TOPK_MAX):
+        raise ValueError(f"'k' must be an integer between 1 and {_lib.TOPK_MAX} (HIBAG_HIP_TOPK_MAX): {k!r}")
+    return int(k)
 
 
 class HlaAttrBagClass:
@@ -249,6 +264,94 @@ class HlaAttrBagClass:
         ms = C.c_double()
         _lib.check(_lib.lib().hibag_hip_predict_prefix_ms(self.handle, C.byref(ms)))
         return ms.value
+
+    # --- the k best pairs of every sample (hibag_hip_predict_topk and its routes; include/hibag_hip.h "top-k") ---
+    @staticmethod
+    def _topk_outputs(n: int, k: int) -> dict:
+        return dict(h1=np.empty((n, k), np.int32), h2=np.empty((n, k), np.int32), prob=np.empty((n, k), np.float64),
+                    matching=np.empty(n, np.float64))
+
+    def predict_topk(self, genomat: np.ndarray, k: int, vote_method: int = 1) -> dict:
+        """``hibag_hip_predict_topk``: per sample the ``k`` largest cells of the normalised posterior matrix (what
+        ``predict_raw(..., want_prob=True)`` returns as ``postprob``) selected on the device -- ``h1``, ``h2`` (0-based,
+        NA = INT_MIN in the ranks no pair qualifies for) and ``prob`` (0 there), each [n_samp, k], descending, equal values
+        in pair order, and ``matching`` [n_samp].  Rank 0 is ``predict_raw``'s call.  ``genomat`` int32 [n_samp, n_snp]."""
+        k = topk_k(k)
+        g = np.ascontiguousarray(genomat, np.int32)
+        if g.ndim != 2 or g.shape[1] != self.obj.n_snp:
+            raise ValueError("genomat must be [n_samp, n.snp] int32")
+        n = g.shape[0]
+        out = self._topk_outputs(n, k)
+        _lib.check(_lib.lib().hibag_hip_predict_topk(
+            self.handle, _as_ptr(g), n, int(vote_method), k, _as_ptr(out["h1"]), _as_ptr(out["h2"]), _as_ptr(out["prob"]),
+            _as_ptr(out["matching"])))
+        return out
+
+    def predict_topk_mapped(self, genomat: np.ndarray, snp_col: np.ndarray, flip: Optional[np.ndarray], k: int,
+                            vote_method: int = 1) -> dict:
+        """:meth:`predict_topk` on the cohort's own matrix [n_samp, n_geno_snp], as :meth:`predict_mapped`."""
+        k = topk_k(k)
+        g = np.ascontiguousarray(genomat, np.int32)
+        if g.ndim != 2:
+            raise ValueError("genomat must be [n_samp, n_geno_snp]")
+        col = np.ascontiguousarray(snp_col, np.int32)
+        if col.shape != (self.obj.n_snp,):
+            raise ValueError("snp_col must have one entry per model SNP")
+        fl = None if flip is None else np.ascontiguousarray(np.asarray(flip) != 0, np.int32)
+        n = g.shape[0]
+        out = self._topk_outputs(n, k)
+        _lib.check(_lib.lib().hibag_hip_predict_topk_mapped(
+            self.handle, _as_ptr(g), n, g.shape[1], _as_ptr(col), _as_ptr(fl), int(vote_method), k,
+            _as_ptr(out["h1"]), _as_ptr(out["h2"]), _as_ptr(out["prob"]), _as_ptr(out["matching"])))
+        return out
+
+    def predict_topk_snp_major(self, genomat: np.ndarray, snp_col: Optional[np.ndarray], flip: Optional[np.ndarray], k: int,
+                               vote_method: int = 1) -> dict:
+        """:meth:`predict_topk` on a SNP-major matrix [n_geno_snp, n_samp] in C order, as :meth:`predict_snp_major`."""
+        k = topk_k(k)
+        g = np.asarray(genomat)
+        if g.ndim != 2 or g.dtype != np.int32 or g.strides[1] != 4 or g.strides[0] % 4 or (g.shape[0] > 1 and g.strides[0] < 4 * g.shape[1]):
+            g = np.ascontiguousarray(g, np.int32)
+            if g.ndim != 2:
+                raise ValueError("genomat must be [n_geno_snp, n_samp]")
+        col = None
+        if snp_col is not None:
+            col = np.ascontiguousarray(snp_col, np.int32)
+            if col.shape != (self.obj.n_snp,):
+                raise ValueError("snp_col must have one entry per model SNP")
+        elif g.shape[0] < self.obj.n_snp:
+            raise ValueError("nrow(snp) == object$n.snp is not TRUE")
+        fl = None if flip is None else np.ascontiguousarray(np.asarray(flip) != 0, np.int32)
+        n = g.shape[1]
+        out = self._topk_outputs(n, k)
+        ld = g.strides[0] // 4 if g.shape[0] > 1 else max(n, 1)
+        _lib.check(_lib.lib().hibag_hip_predict_topk_snp_major(
+            self.handle, _as_ptr(g), ld, n, max(g.shape[0], 1), _as_ptr(col), _as_ptr(fl), int(vote_method), k,
+            _as_ptr(out["h1"]), _as_ptr(out["h2"]), _as_ptr(out["prob"]), _as_ptr(out["matching"])))
+        return out
+
+    def predict_topk_bed(self, bed_fn: str, n_samp: int, n_snp: int, snp_col: np.ndarray, flip: Optional[np.ndarray], k: int,
+                         vote_method: int = 1) -> dict:
+        """:meth:`predict_topk` on every sample of a PLINK BED file, as :meth:`predict_bed`."""
+        k = topk_k(k)
+        col = np.ascontiguousarray(snp_col, np.int32)
+        if col.shape != (self.obj.n_snp,):
+            raise ValueError("snp_col must have one entry per model SNP")
+        fl = None if flip is None else np.ascontiguousarray(np.asarray(flip) != 0, np.int32)
+        n = int(n_samp)
+        out = self._topk_outputs(n, k)
+        _lib.check(_lib.lib().hibag_hip_predict_topk_bed(
+            self.handle, os.fsencode(bed_fn), n, int(n_snp), _as_ptr(col), _as_ptr(fl), int(vote_method), k,
+            _as_ptr(out["h1"]), _as_ptr(out["h2"]), _as_ptr(out["prob"]), _as_ptr(out["matching"])))
+        return out
+
+    def predict_topk_device(self, d_geno, n_samp: int, k: int, d_h1, d_h2, d_prob, d_matching=None, vote_method: int = 1,
+                            stream=None):
+        """Device-pointer form of :meth:`predict_topk`; arguments are ints (``tensor.data_ptr()``) or None."""
+        def p(x):
+            return None if x is None else C.c_void_p(int(x))
+        _lib.check(_lib.lib().hibag_hip_predict_topk_device(
+            self.handle, p(d_geno), int(n_samp), int(vote_method), int(k), p(d_h1), p(d_h2), p(d_prob), p(d_matching), p(stream)))
 
     def predict_bed(self, bed_fn: str, n_samp: int, n_snp: int, snp_col: np.ndarray, flip: Optional[np.ndarray] = None,
                     vote_method: int = 1, want_dosage: bool = True, want_prob: bool = False) -> dict:

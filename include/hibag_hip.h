@@ -26,7 +26,8 @@ extern "C" {
                                      7: + hibag_hip_predict_snp_major[_device], hibag_hip_trainer_set_shared, hibag_hip_train_set_thread_budget;
                                         later, additive (no bump): + hibag_hip_predict_oob; + the LD entries (hibag_hip_ld_*);
                                         + hibag_hip_model_distance[_ms]; + the merge entries (hibag_hip_merge_*, hibag_hip_predict_merge[_bed]);
-                                        + hibag_hip_predict_prefix[_ms] */
+                                        + hibag_hip_predict_prefix[_ms];
+                                       + the top-k entries (hibag_hip_predict_topk[_device, _mapped, _snp_major, _bed]): added within version 7 */
 
 /* error codes */
 #define HIBAG_HIP_OK          0
@@ -454,6 +455,39 @@ int hibag_hip_conv_bed(const char *bed_fn, int n_samp, int n_snp, int n_save_snp
 int hibag_hip_predict_bed(hibag_hip_model *m, const char *bed_fn, int n_samp, int n_snp,
 	const int32_t *snp_col, const int32_t *flip, int vote_method,
 	int32_t *H1, int32_t *H2, double *max_prob, double *matching, double *dosage, double *postprob);
+
+/* ---- top-k: each sample's k best allele pairs: hlaPredictTopK ----------------
+ * Between "one pair" and "the whole posterior matrix": per sample the k largest cells of the NORMALISED ensemble matrix
+ * -- exactly the values the postprob output of hibag_hip_predict holds for that vote_method -- as allele pairs with their
+ * probabilities, selected on the device; k * 20 + 8 bytes per sample come back instead of 8 * n_hla (n_hla + 1) / 2.
+ * The ranking rule:
+ *   rank 0 is the call of hibag_hip_predict (BestGuessEnsemble, src/LibHLA.cpp:1549-1566): the first strict maximum in
+ *   pair order, only values > 0; rank r is the first strict maximum among the pairs not yet listed, again only values > 0
+ *   -- descending probability, equal probabilities in ascending pair order; a pair whose value is 0 or NaN is never listed.
+ * Outputs, sample-major:
+ *   h1, h2 [n_samp][k]   0-based allele indices (h1 <= h2), HIBAG_HIP_NA_INTEGER in the ranks no pair qualifies for
+ *   prob   [n_samp][k]   the pairs' posterior probabilities, 0 in those ranks; h1[s][0], h2[s][0], prob[s][0] are
+ *                        bit for bit the H1, H2, max_prob of hibag_hip_predict
+ *   matching [n_samp]    as hibag_hip_predict; may be NULL
+ * h1, h2 and prob are required; 1 <= k <= HIBAG_HIP_TOPK_MAX, vote_method 1 or 2; HIBAG_HIP_EINVAL otherwise.  No dosage
+ * and no posterior matrix (ask hibag_hip_predict for those).  Everything else -- batches, the host-pointer pipeline, the
+ * repair of a failed hand-over (poisoned outputs are NA pairs and NaN probabilities in every rank), the launch status of
+ * the _device form -- is as for the sibling entry of the same suffix, whose other arguments these take in the same
+ * order.  (Added within ABI version 7) */
+#define HIBAG_HIP_TOPK_MAX 16
+int hibag_hip_predict_topk(hibag_hip_model *m, const int32_t *geno, int n_samp, int vote_method, int k,
+	int32_t *h1, int32_t *h2, double *prob, double *matching);
+int hibag_hip_predict_topk_device(hibag_hip_model *m, const int32_t *d_geno, int n_samp, int vote_method, int k,
+	int32_t *d_h1, int32_t *d_h2, double *d_prob, double *d_matching, void *stream);
+int hibag_hip_predict_topk_mapped(hibag_hip_model *m, const int32_t *geno, int n_samp, int n_geno_snp,
+	const int32_t *snp_col, const int32_t *flip, int vote_method, int k,
+	int32_t *h1, int32_t *h2, double *prob, double *matching);
+int hibag_hip_predict_topk_snp_major(hibag_hip_model *m, const int32_t *geno, size_t ld, int n_samp, int n_geno_snp,
+	const int32_t *snp_col, const int32_t *flip, int vote_method, int k,
+	int32_t *h1, int32_t *h2, double *prob, double *matching);
+int hibag_hip_predict_topk_bed(hibag_hip_model *m, const char *bed_fn, int n_samp, int n_snp,
+	const int32_t *snp_col, const int32_t *flip, int vote_method, int k,
+	int32_t *h1, int32_t *h2, double *prob, double *matching);
 
 /* ---- training: replaces HIBAG_Training + HIBAG_NewClassifiers ---------------- */
 
