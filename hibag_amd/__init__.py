@@ -6,7 +6,7 @@ The compute lives in ``csrc/libhibag_hip.so`` (hand-written HIP for gfx950,
 C ABI in ``include/hibag_hip.h``); there is no CPU fallback in this package.
 """
 
-from .model import (NA_INTEGER, Classifier, HlaAttrBagObj, HlaSNPGeno, engine_kind, engine_nkb, engine_steps, load_geno, load_model,  # noqa: F401
+from .model import (NA_INTEGER, Classifier, HlaAttrBagObj, HlaSNPGeno, engine_kind, engine_nkb, engine_steps, load_geno, load_model, load_model_list,  # noqa: F401
                     model_to_robj, save_model)
 from .hibag import (HlaAlleleClass, HlaAttrBagClass, hlaClose, hlaModelFromObj, hlaModelToObj,   # noqa: F401
                     hlaPredict, hlaSetKernelTarget)
@@ -24,6 +24,7 @@ from .distance import hlaDistance  # noqa: F401
 from .submodel import hlaCombineModelObj, hlaSubModelObj  # noqa: F401
 from .curve import HlaPredictCurve, hlaPredictCurve  # noqa: F401
 from .topk import HlaTopCalls, hlaPredictTopK  # noqa: F401
+from .cohort import HlaDeviceCohort, hlaPredictLoci  # noqa: F401
 from ._lib import HibagHipError  # noqa: F401
 
 __all__ = ["engine_kind", "engine_nkb", "engine_steps", "NA_INTEGER", "Classifier", "HlaAttrBagObj", "HlaSNPGeno", "load_geno", "load_model", "model_to_robj", "save_model",
@@ -32,4 +33,5 @@ __all__ = ["engine_kind", "engine_nkb", "engine_steps", "NA_INTEGER", "Classifie
            "HlaBEDGeno", "hlaBED2Geno", "hlaLociInfo", "RRandom", "hlaAllele", "hlaAttrBagging", "hlaConcurrentAttrBagging", "hlaParallelAttrBagging", "hlaUniqueAllele", "hlaAlleleDigit", "hlaPredMerge", "hlaPredictMerge", "hlaAlleleSubset", "hlaCompareAllele", "hlaFlankingSNP", "hlaGenoSubset",
            "hlaSplitAllele", "r_sample", "hlaOutOfBag", "hlaGenoLD", "hlaLDMatrix", "hlaDistance",
            "hlaSubModelObj", "hlaCombineModelObj", "hlaPredictCurve", "HlaPredictCurve", "hlaPredictTopK", "HlaTopCalls",
+           "HlaDeviceCohort", "hlaPredictLoci", "load_model_list",
            "set_seed"]

@@ -46,6 +46,9 @@ EXPORTS = [
     "hibag_hip_predict_merge_bed", "hibag_hip_predict_prefix", "hibag_hip_predict_prefix_ms",
     "hibag_hip_predict_topk", "hibag_hip_predict_topk_device", "hibag_hip_predict_topk_mapped",
     "hibag_hip_predict_topk_snp_major", "hibag_hip_predict_topk_bed",
+    "hibag_hip_cohort_new", "hibag_hip_cohort_from_bed", "hibag_hip_cohort_free", "hibag_hip_cohort_device",
+    "hibag_hip_cohort_n_samp", "hibag_hip_cohort_n_snp", "hibag_hip_cohort_bytes", "hibag_hip_cohort_snp_counts",
+    "hibag_hip_predict_cohort", "hibag_hip_predict_topk_cohort",
 ]
 TOPK_MAX = 16      # HIBAG_HIP_TOPK_MAX of include/hibag_hip.h
 
@@ -109,6 +112,23 @@ def lib() -> C.CDLL:
     L.hibag_hip_predict_topk_mapped.argtypes = [vp, vp, i32, i32, vp, vp, i32, i32, vp, vp, vp, vp]
     L.hibag_hip_predict_topk_snp_major.argtypes = [vp, vp, C.c_size_t, i32, i32, vp, vp, i32, i32, vp, vp, vp, vp]
     L.hibag_hip_predict_topk_bed.argtypes = [vp, C.c_char_p, i32, i32, vp, vp, i32, i32, vp, vp, vp, vp]
+    if hasattr(L, "hibag_hip_cohort_new"):
+        # (an older build selected with HIBAG_HIP_LIBRARY, e.g. the parent commit's for a baseline timing, lacks the cohort
+        # entries: everything else still binds, and a call that needs them fails with AttributeError)
+        L.hibag_hip_cohort_new.argtypes = [vp, i32, C.c_size_t, i32, i32, vp, i32]
+        L.hibag_hip_cohort_new.restype = vp
+        L.hibag_hip_cohort_from_bed.argtypes = [C.c_char_p, i32, i32, vp, i32]
+        L.hibag_hip_cohort_from_bed.restype = vp
+        L.hibag_hip_cohort_free.argtypes = [vp]
+        L.hibag_hip_cohort_free.restype = None
+        for f in (L.hibag_hip_cohort_device, L.hibag_hip_cohort_n_samp, L.hibag_hip_cohort_n_snp):
+            f.argtypes = [vp]
+            f.restype = i32
+        L.hibag_hip_cohort_bytes.argtypes = [vp]
+        L.hibag_hip_cohort_bytes.restype = i64
+        L.hibag_hip_cohort_snp_counts.argtypes = [vp, vp, vp]
+        L.hibag_hip_predict_cohort.argtypes = [vp, vp, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp]
+        L.hibag_hip_predict_topk_cohort.argtypes = [vp, vp, i32, i32, vp, vp, i32, i32, vp, vp, vp, vp]
     L.hibag_hip_ld_geno_new.argtypes = [vp, i32, i32, i32]
     L.hibag_hip_ld_geno_new.restype = vp
     L.hibag_hip_ld_geno_free.argtypes = [vp]

@@ -6,6 +6,7 @@
 //   hibag_prefix.hip   hibag_hip_predict_prefix: every sub-model "first k classifiers" from one pass 1
 //   hibag_predict.hip  the batch driver that replaces CAttrBag_Model::PredictHLA: workspace, kernel sequence, host-pointer
 //                      pipeline, BED input, partial sums, launch status, timing
+//   hibag_cohort.hip   a cohort's genotypes resident on a device in 2-bit form, and the prediction entries that read them
 #ifndef HIBAG_INTERNAL_H_
 #define HIBAG_INTERNAL_H_
 
@@ -300,6 +301,10 @@ int sticky_fault(hibag_hip_model *m);
 int workspace_enter(hibag_hip_model *m, hipStream_t st);
 int workspace_leave(hibag_hip_model *m, hipStream_t st);
 int staged_streams(hibag_hip_model *m, StagedStreams **out);  // the model's streams of the host-pointer entries (created on first use)
+int check_topk_args(int n_samp, int k, const void *h1, const void *h2, const void *prob);
+// the host-pointer driver (slices, download pipeline, repair of a failed hand-over) on a 2-bit payload resident on the model's device
+int predict_payload_locked(hibag_hip_model *m, const PackSource &src, int n_samp, int vote_method,
+	int32_t *H1, int32_t *H2, double *max_prob, double *matching, double *dosage, double *postprob, const TopKOut *topk);
 int load_bed(const char *fn, int n_samp, int n_snp, const int32_t *want, int n_want, BedImage &img);
 
 } // namespace hibag_detail

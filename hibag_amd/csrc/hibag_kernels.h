@@ -18,6 +18,12 @@ void hibag_launch_pack_bed(const HibagModelView &M, const HibagBatchView &B, con
 	size_t stride, int samp0, const int32_t *d_snp_row, const int32_t *d_flip, uint8_t *d_codes, hipStream_t st);
 void hibag_launch_bed_geno(const uint8_t *d_bed, int mode, size_t stride, int n_samp, int n_save,
 	const int32_t *d_sel, int32_t *d_geno, hipStream_t st);
+// The resident cohort (hibag_k_cohort.h).  _pack: a slab of the host's int32 matrix -- [n_snp][ld] (snp_major, ld a multiple
+// of 4, at most 65,535 rows) or [n_samp][ld] with the SNP fastest (at most 65,535 x 64 SNPs) -- into the 2-bit rows that start
+// at d_out, `stride` bytes apart, from byte `byte0` of each row on.  _counts: called genotypes and their sum per row.
+void hibag_launch_cohort_pack(const int32_t *d_slab, int snp_major, size_t ld, int n_snp, int n_samp, uint8_t *d_out,
+	size_t stride, size_t byte0, hipStream_t st);
+void hibag_launch_cohort_counts(const uint8_t *d_rows, size_t stride, int n_snp, int32_t *d_n_valid, int64_t *d_sum, hipStream_t st);
 // `side`: a second stream and two events of the caller's, for the kernel that runs beside pass 1 where the model has
 // FP4 classifiers of several K steps (fork behind what is already on `st`, join before anything that follows)
 struct HibagSideStream { hipStream_t stream = nullptr; hipEvent_t fork = nullptr, join = nullptr; };

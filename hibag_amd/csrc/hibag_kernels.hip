@@ -84,6 +84,7 @@ static_assert(2 * HIBAG_FP4_MAX_SNPS + 1 <= ACCUM_TAB_N, "pass 2's table must co
 #include "hibag_k_finish.h"
 #include "hibag_k_topk.h"
 #include "hibag_k_oob.h"
+#include "hibag_k_cohort.h"
 
 // ---------------------------------------------------------------------------
 // launchers (host side, no synchronisation, no allocation)
@@ -126,6 +127,25 @@ void hibag_launch_bed_geno(const uint8_t *d_bed, int mode, size_t stride, int n_
 	if (n_samp <= 0 || n_save <= 0) return;
 	hipLaunchKernelGGL(k_bed_geno, dim3((n_samp + 63) / 64, (n_save + 63) / 64), dim3(256), 0, st, d_bed, mode, stride,
 		n_samp, n_save, d_sel, d_geno);
+}
+
+// the resident cohort (hibag_k_cohort.h): one slab of the host matrix into the 2-bit rows; the per-row counts
+void hibag_launch_cohort_pack(const int32_t *d_slab, int snp_major, size_t ld, int n_snp, int n_samp, uint8_t *d_out,
+	size_t stride, size_t byte0, hipStream_t st)
+{
+	if (n_snp <= 0 || n_samp <= 0) return;
+	if (snp_major)
+		hipLaunchKernelGGL(k_cohort_pack<true>, dim3(((n_samp + 3) / 4 + 255) / 256, n_snp), dim3(256), 0, st, d_slab, ld, n_snp,
+			n_samp, d_out, stride, byte0);
+	else
+		hipLaunchKernelGGL(k_cohort_pack<false>, dim3((n_samp + COHORT_TILE_SAMP - 1) / COHORT_TILE_SAMP,
+			(n_snp + COHORT_TILE_SNP - 1) / COHORT_TILE_SNP), dim3(256), 0, st, d_slab, ld, n_snp, n_samp, d_out, stride, byte0);
+}
+
+void hibag_launch_cohort_counts(const uint8_t *d_rows, size_t stride, int n_snp, int32_t *d_n_valid, int64_t *d_sum, hipStream_t st)
+{
+	if (n_snp <= 0) return;
+	hipLaunchKernelGGL(k_cohort_counts, dim3((n_snp + 3) / 4), dim3(256), 0, st, d_rows, stride, n_snp, d_n_valid, d_sum);
 }
 
 // resident workgroups of a kernel on the current device (0 = unknown)

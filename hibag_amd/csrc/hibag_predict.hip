@@ -476,6 +476,15 @@ int predict_staged_locked(hibag_hip_model *m, const int32_t *geno, const PackSou
 	return 0;
 }
 
+// The host-pointer driver on a 2-bit payload that is already on the model's device (what the BED entries upload per call;
+// the rows of a resident cohort, hibag_cohort.hip): `src` as for hibag_launch_pack_bed, samples src.samp0 .. + n_samp.
+int predict_payload_locked(hibag_hip_model *m, const PackSource &src, int n_samp, int vote_method,
+	int32_t *H1, int32_t *H2, double *max_prob, double *matching, double *dosage, double *postprob, const TopKOut *topk)
+{
+	return predict_staged_locked(m, nullptr, &src, n_samp, vote_method, H1, H2, max_prob, matching, dosage, postprob, nullptr, false,
+		nullptr, topk);
+}
+
 // ---------------------------------------------------------------------------
 // PLINK BED files (HIBAG_BEDFlag / HIBAG_ConvBED, src/HIBAG.cpp:1068-1191)
 

@@ -23,6 +23,7 @@ import numpy as np
 from . import _lib
 from ._lib import HibagHipError
 from .bed import HlaBEDGeno
+from .cohort import HlaDeviceCohort
 from .model import (NA_INTEGER, Classifier, HlaAttrBagObj, HlaSNPGeno)
 
 _TARGETS_CPU = ("max", "auto.avx2", "base", "sse2", "sse4", "avx", "avx2", "avx512f", "avx512bw",
@@ -370,6 +371,41 @@ class HlaAttrBagClass:
             _as_ptr(out.get("dosage")), _as_ptr(out.get("postprob"))))
         return out
 
+    def _cohort_args(self, cohort, snp_col, flip, first: int, count: Optional[int]):
+        col = np.ascontiguousarray(snp_col, np.int32)
+        if col.shape != (self.obj.n_snp,):
+            raise ValueError("snp_col must have one entry per model SNP")
+        fl = None if flip is None else np.ascontiguousarray(np.asarray(flip) != 0, np.int32)
+        first = int(first)
+        n = cohort.n_samp - first if count is None else int(count)
+        return col, fl, first, n
+
+    def predict_cohort(self, cohort, snp_col: np.ndarray, flip: Optional[np.ndarray] = None, vote_method: int = 1,
+                       want_dosage: bool = True, want_prob: bool = False, first: int = 0, count: Optional[int] = None) -> dict:
+        """``PredictHLA`` on samples ``[first, first + count)`` of a resident cohort (``hibag_hip_predict_cohort``;
+        ``cohort``: an ``HlaDeviceCohort``): ``snp_col[k]`` = resident row of model SNP k (-1 = absent), ``flip[k]`` =
+        reverse its allele count.  Nothing but the row map goes up."""
+        h = cohort.handle
+        col, fl, first, n = self._cohort_args(cohort, snp_col, flip, first, count)
+        out = self._outputs(max(n, 0), want_dosage, want_prob)
+        _lib.check(_lib.lib().hibag_hip_predict_cohort(
+            self.handle, h, first, n, _as_ptr(col), _as_ptr(fl), int(vote_method),
+            _as_ptr(out["h1"]), _as_ptr(out["h2"]), _as_ptr(out["prob"]), _as_ptr(out["matching"]),
+            _as_ptr(out.get("dosage")), _as_ptr(out.get("postprob"))))
+        return out
+
+    def predict_topk_cohort(self, cohort, snp_col: np.ndarray, flip: Optional[np.ndarray], k: int, vote_method: int = 1,
+                            first: int = 0, count: Optional[int] = None) -> dict:
+        """:meth:`predict_topk` on samples ``[first, first + count)`` of a resident cohort, as :meth:`predict_cohort`."""
+        k = topk_k(k)
+        h = cohort.handle
+        col, fl, first, n = self._cohort_args(cohort, snp_col, flip, first, count)
+        out = self._topk_outputs(max(n, 0), k)
+        _lib.check(_lib.lib().hibag_hip_predict_topk_cohort(
+            self.handle, h, first, n, _as_ptr(col), _as_ptr(fl), int(vote_method), k,
+            _as_ptr(out["h1"]), _as_ptr(out["h2"]), _as_ptr(out["prob"]), _as_ptr(out["matching"])))
+        return out
+
     def predict_mapped(self, genomat: np.ndarray, snp_col: np.ndarray, flip: Optional[np.ndarray] = None,
                        vote_method: int = 1, want_dosage: bool = True, want_prob: bool = False) -> dict:
         """``PredictHLA`` on the COHORT's own matrix ``genomat`` [n_samp, n_geno_snp] (``hibag_hip_predict_mapped``):
@@ -699,7 +735,8 @@ def hlaPredict(object: HlaAttrBagClass, snp: Union[HlaSNPGeno, HlaBEDGeno, np.nd
     """``hlaPredict`` (``R/HIBAG.R:481-818``).
 
     ``snp`` is an :class:`HlaSNPGeno` or a numeric matrix [n.snp, n.samp] (or a
-    vector of length n.snp) laid out like the R argument.  ``cl``: the reference takes a
+    vector of length n.snp) laid out like the R argument; also a lazily opened BED file (:class:`HlaBEDGeno`) or a cohort
+    resident on the model's device (:class:`HlaDeviceCohort`).  ``cl``: the reference takes a
     ``parallel`` cluster and spreads contiguous sample slices over its workers
     (``R/HIBAG.R:764-808``); here a list of device indices does the same over the GPUs of
     the node (``hibag_hip_predict_multi``: one replica and one host thread per device, no
@@ -734,8 +771,15 @@ def hlaPredict(object: HlaAttrBagClass, snp: Union[HlaSNPGeno, HlaBEDGeno, np.nd
         print("Prediction:\n    " + ("based on the averaged posterior probabilities" if vote_method == 1
                                       else "by voting from all individual classifiers"), file=out)
 
-    bed_plan = map_plan = None
-    if isinstance(snp, HlaBEDGeno):
+    bed_plan = map_plan = coh_plan = None
+    if isinstance(snp, HlaDeviceCohort):
+        # extension: the genotypes are resident on the device (hibag_amd/cohort.py); the SNP matching / strand check runs on
+        # the cohort's annotation, with allele frequencies from counts made on the device
+        coh_plan = snp.plan_for(obj, match_type, allele_check, same_strand, verbose, verbose_match)
+        assembly = coh_plan.assembly
+        geno_sampid = list(snp.sample_id)
+        mat = None
+    elif isinstance(snp, HlaBEDGeno):
         # extension: the genotypes stay in the PLINK BED file; the SNP matching / strand check
         # (R/HIBAG.R:550-686) runs on the annotation and the device decodes the file directly
         from .snpmatch import plan_snps_for_predict
@@ -789,6 +833,9 @@ def hlaPredict(object: HlaAttrBagClass, snp: Union[HlaSNPGeno, HlaBEDGeno, np.nd
         bad = [d for d in devices if not isinstance(d, (int, np.integer)) or isinstance(d, bool) or not (0 <= int(d) < n_dev)]
         if not devices or bad:
             raise ValueError(f"'cl' must be a non-empty list of HIP device indices below {n_dev}: {cl!r}")
+        if coh_plan is not None:
+            raise ValueError("hlaPredict(cl = [devices]) takes a genotype matrix or an hlaSNPGenoClass; a resident cohort "
+                             "(HlaDeviceCohort) lives on one device: predict there, with cl = False")
         if bed_plan is not None:
             # the BED route decodes on ONE device (hibag_hip_predict_bed); silently ignoring the list would not be what
             # the caller asked for
@@ -817,6 +864,9 @@ def hlaPredict(object: HlaAttrBagClass, snp: Union[HlaSNPGeno, HlaBEDGeno, np.nd
                 cache[key] = object.replicate(int(d))
             reps.append((int(d), cache[key]))
         rv = predict_multi([r for _, r in reps], genomat, vote_method, want_dosage=want_dosage, want_prob=want_prob)
+    elif coh_plan is not None:
+        rv = object.predict_cohort(snp, snp.rows_of(coh_plan.sel), coh_plan.flip, vote_method,
+                                   want_dosage=want_dosage, want_prob=want_prob)
     elif bed_plan is not None:
         col = np.where(bed_plan.sel >= 0, snp.bed_index[np.maximum(bed_plan.sel, 0)], -1)
         rv = object.predict_bed(snp.bed_fn, snp.n_bed_samp, snp.n_bed_snp, col, bed_plan.flip, vote_method,

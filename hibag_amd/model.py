@@ -17,7 +17,7 @@ from __future__ import annotations
 import os
 
 from dataclasses import dataclass, field
-from typing import Any, List, Optional, Sequence
+from typing import Any, Dict, List, Optional, Sequence
 
 import numpy as np
 
@@ -199,6 +199,20 @@ def load_model(path: str, name: Optional[str] = None, gene: Optional[str] = None
     if gene is not None:
         obj = obj[gene]
     return model_from_robj(obj)
+
+
+def load_model_list(path: str, name: Optional[str] = None) -> Dict[str, HlaAttrBagObj]:
+    """Load a list of models, one per locus -- the form published models ship in (``modellist$A``, ``$B``, ...) -- from
+    an R workspace: ``{locus: HlaAttrBagObj}`` in the list's order, keyed by the list's names.  ``name`` picks the
+    object; every element is what ``load_model(path, name, gene=locus)`` returns."""
+    ws = rdata.load_rdata(path)
+    lst = ws[name] if name else next(iter(ws.values()))
+    names = list(getattr(lst, "names", None) or [])
+    if not names or any(n is None or n == "" for n in names) or len(set(names)) != len(names):
+        raise ValueError("the object is not a list of models with one unique name per locus")
+    if any("hlaAttrBagObj" not in (getattr(lst[n], "attrs", {}).get("class") or []) for n in names):
+        raise ValueError("the object is not a list of models with one unique name per locus")
+    return {str(n): model_from_robj(lst[n]) for n in names}
 
 
 def load_geno(path: str, name: Optional[str] = None) -> HlaSNPGeno:

@@ -15,6 +15,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from .bed import HlaBEDGeno
+from .cohort import HlaDeviceCohort
 from .hibag import HlaAlleleClass, HlaAttrBagClass, _as_integer, _kernel_info_text, topk_k
 from .model import NA_INTEGER, HlaSNPGeno
 
@@ -113,7 +114,7 @@ def hlaPredictTopK(model: HlaAttrBagClass, snp, k: int = 3, vote: str = "prob", 
 
     ``snp``: what ``hlaPredict`` takes on one device -- an :class:`HlaSNPGeno` (SNP matching, strand flips and missing
     model SNPs as ``hlaPredict`` decides them, applied on the device), a numeric matrix [n.snp, n.samp] in either memory
-    order, a vector of length n.snp, or a lazily opened :class:`HlaBEDGeno`.  The list is descending; equal probabilities
+    order, a vector of length n.snp, a lazily opened :class:`HlaBEDGeno`, or a resident :class:`HlaDeviceCohort`.  The list is descending; equal probabilities
     come in pair order; a pair with probability 0 (or NaN) is never listed, so a sample may have fewer than ``k`` ranks
     filled (``NA_INTEGER`` / 0.0 in the others).  ``best()`` is ``hlaPredict(..., type="response")`` bit for bit."""
     if not isinstance(model, HlaAttrBagClass):
@@ -136,8 +137,13 @@ def hlaPredictTopK(model: HlaAttrBagClass, snp, k: int = 3, vote: str = "prob", 
               ("based on the averaged posterior probabilities" if vote_method == 1
                else "by voting from all individual classifiers"), file=out)
 
-    bed_plan = map_plan = None
-    if isinstance(snp, HlaBEDGeno):
+    bed_plan = map_plan = coh_plan = None
+    if isinstance(snp, HlaDeviceCohort):
+        coh_plan = snp.plan_for(obj, match_type, allele_check, same_strand, verbose, verbose_match)
+        assembly = coh_plan.assembly
+        geno_sampid = list(snp.sample_id)
+        mat = None
+    elif isinstance(snp, HlaBEDGeno):
         from .snpmatch import plan_snps_for_predict
         bed_plan = plan_snps_for_predict(obj, snp, snp.allele_freq, match_type, allele_check, same_strand,
                                          verbose, verbose_match)
@@ -174,7 +180,9 @@ def hlaPredictTopK(model: HlaAttrBagClass, snp, k: int = 3, vote: str = "prob", 
         print(f"# of samples: {n_samp}", file=out)
         print(f"Kernel target: {_kernel_info_text() or 'hip'}", file=out)
 
-    if bed_plan is not None:
+    if coh_plan is not None:
+        rv = model.predict_topk_cohort(snp, snp.rows_of(coh_plan.sel), coh_plan.flip, k, vote_method)
+    elif bed_plan is not None:
         col = np.where(bed_plan.sel >= 0, snp.bed_index[np.maximum(bed_plan.sel, 0)], -1)
         rv = model.predict_topk_bed(snp.bed_fn, snp.n_bed_samp, snp.n_bed_snp, col, bed_plan.flip, k, vote_method)
     else:

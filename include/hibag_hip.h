@@ -27,7 +27,8 @@ extern "C" {
                                         later, additive (no bump): + hibag_hip_predict_oob; + the LD entries (hibag_hip_ld_*);
                                         + hibag_hip_model_distance[_ms]; + the merge entries (hibag_hip_merge_*, hibag_hip_predict_merge[_bed]);
                                         + hibag_hip_predict_prefix[_ms];
-                                       + the top-k entries (hibag_hip_predict_topk[_device, _mapped, _snp_major, _bed]): added within version 7 */
+                                       + the top-k entries (hibag_hip_predict_topk[_device, _mapped, _snp_major, _bed]): added within version 7;
+                                       + the resident cohort (hibag_hip_cohort_*, hibag_hip_predict_cohort, hibag_hip_predict_topk_cohort): likewise */
 
 /* error codes */
 #define HIBAG_HIP_OK          0
@@ -488,6 +489,47 @@ int hibag_hip_predict_topk_snp_major(hibag_hip_model *m, const int32_t *geno, si
 int hibag_hip_predict_topk_bed(hibag_hip_model *m, const char *bed_fn, int n_samp, int n_snp,
 	const int32_t *snp_col, const int32_t *flip, int vote_method, int k,
 	int32_t *h1, int32_t *h2, double *prob, double *matching);
+
+/* ---- resident cohort: one cohort's genotypes kept on a device for many calls -------
+ * A run types one cohort at every locus, and then asks again (the k best pairs, both vote methods, a second ancestry's
+ * model).  Every entry above takes the raw genotypes again on each call -- 4 bytes per genotype up the bus and a decode per
+ * model.  A cohort keeps them on ONE device at 2 bits per genotype: SNP-major rows in PLINK's own codes (00 = 2, 01 = missing,
+ * 10 = 1, 11 = 0; four samples per byte, lowest bits first), rows a multiple of 16 bytes apart, the slots behind the last
+ * sample missing -- the payload of a SNP-major BED file, so a matrix and a file share the decode of hibag_hip_predict_bed
+ * and everything behind it.  A cohort is immutable once built; calls on different models may share it from different threads.
+ *   hibag_hip_cohort_new       from an int32 matrix: geno[snp * ld + sample] (snp_major != 0, ld >= n_samp) or
+ *                              geno[sample * ld + snp] (snp_major == 0, the memory of R's SNP x sample matrix, ld >= n_snp);
+ *                              anything outside 0..2 is missing (as hibag_hip_predict).  snp_rows[n_rows] selects the SNPs
+ *                              that become rows 0 .. n_rows - 1 of the cohort, in that order (NULL: all n_snp, n_rows ignored).
+ *                              The matrix goes up in slabs through pinned staging and is packed on the device: it is never
+ *                              resident whole.  On the calling thread's device (hibag_hip_set_device).  At most 2^30 samples.
+ *   hibag_hip_cohort_from_bed  the same from a PLINK BED file of n_samp x n_snp genotypes, either storage mode; checked like
+ *                              hibag_hip_predict_bed (same messages; a short file is an error).  snp_rows: BED SNP indices.
+ * Both return NULL on failure (hibag_hip_last_error says why).
+ *   hibag_hip_cohort_snp_counts  per row the number of called genotypes (int32) and their sum (int64), exact; what the
+ *                              allele frequencies of hlaPredict's strand check are made of
+ *   hibag_hip_predict_cohort   hibag_hip_predict_mapped for samples [first, first + count) of the cohort, host-pointer
+ *                              outputs: snp_col[model n_snp] = cohort row of each model SNP (-1 = absent), flip as there.
+ *                              Batches, the download pipeline and the repair of a failed hand-over are those of the other
+ *                              host-pointer entries; the call takes the model's lock.  Bit-identical to hibag_hip_predict_mapped
+ *                              on the matrix the cohort was made from.  HIBAG_HIP_EINVAL (with a message) when cohort and
+ *                              model are on different devices, the window leaves the cohort, or a snp_col entry is >= n_snp.
+ *   hibag_hip_predict_topk_cohort  the same with the top-k output set (see "top-k" above). */
+typedef struct hibag_hip_cohort hibag_hip_cohort;
+hibag_hip_cohort *hibag_hip_cohort_new(const int32_t *geno, int snp_major, size_t ld, int n_samp, int n_snp,
+	const int32_t *snp_rows, int n_rows);
+hibag_hip_cohort *hibag_hip_cohort_from_bed(const char *bed_fn, int n_samp, int n_snp, const int32_t *snp_rows, int n_rows);
+void hibag_hip_cohort_free(hibag_hip_cohort *c);
+int hibag_hip_cohort_device(const hibag_hip_cohort *c);     /* -1 for NULL */
+int hibag_hip_cohort_n_samp(const hibag_hip_cohort *c);
+int hibag_hip_cohort_n_snp(const hibag_hip_cohort *c);      /* rows held */
+int64_t hibag_hip_cohort_bytes(const hibag_hip_cohort *c);  /* device memory of the rows */
+int hibag_hip_cohort_snp_counts(const hibag_hip_cohort *c, int32_t *n_valid, int64_t *sum);
+int hibag_hip_predict_cohort(hibag_hip_model *m, const hibag_hip_cohort *c, int first, int count, const int32_t *snp_col,
+	const int32_t *flip, int vote_method, int32_t *H1, int32_t *H2, double *max_prob, double *matching, double *dosage,
+	double *postprob);
+int hibag_hip_predict_topk_cohort(hibag_hip_model *m, const hibag_hip_cohort *c, int first, int count, const int32_t *snp_col,
+	const int32_t *flip, int vote_method, int k, int32_t *h1, int32_t *h2, double *prob, double *matching);
 
 /* ---- training: replaces HIBAG_Training + HIBAG_NewClassifiers ---------------- */
 
