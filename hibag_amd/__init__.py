@@ -19,6 +19,7 @@ from .predmerge import hlaPredictMerge  # noqa: F401
 from .evaluate import (hlaAlleleSubset, hlaCompareAllele, hlaFlankingSNP, hlaGenoSubset, hlaSplitAllele,  # noqa: F401
                        r_sample)
 from .oob import hlaOutOfBag  # noqa: F401
+from .oobens import hlaOutOfBagEnsemble, out_of_bag_mask  # noqa: F401
 from .ld import hlaGenoLD, hlaLDMatrix  # noqa: F401
 from .distance import hlaDistance  # noqa: F401
 from .submodel import hlaCombineModelObj, hlaSubModelObj  # noqa: F401
@@ -31,7 +32,7 @@ __all__ = ["engine_kind", "engine_nkb", "engine_steps", "NA_INTEGER", "Classifie
            "HlaAlleleClass", "HlaAttrBagClass", "hlaClose", "hlaModelFromObj", "hlaModelToObj",
            "hlaPredict", "hlaSetKernelTarget", "hlaGenoSwitchStrand", "hlaSNPID", "HibagHipError",
            "HlaBEDGeno", "hlaBED2Geno", "hlaLociInfo", "RRandom", "hlaAllele", "hlaAttrBagging", "hlaConcurrentAttrBagging", "hlaParallelAttrBagging", "hlaUniqueAllele", "hlaAlleleDigit", "hlaPredMerge", "hlaPredictMerge", "hlaAlleleSubset", "hlaCompareAllele", "hlaFlankingSNP", "hlaGenoSubset",
-           "hlaSplitAllele", "r_sample", "hlaOutOfBag", "hlaGenoLD", "hlaLDMatrix", "hlaDistance",
+           "hlaSplitAllele", "r_sample", "hlaOutOfBag", "hlaOutOfBagEnsemble", "out_of_bag_mask", "hlaGenoLD", "hlaLDMatrix", "hlaDistance",
            "hlaSubModelObj", "hlaCombineModelObj", "hlaPredictCurve", "HlaPredictCurve", "hlaPredictTopK", "HlaTopCalls",
            "HlaDeviceCohort", "hlaPredictLoci", "load_model_list",
            "set_seed"]

@@ -48,7 +48,7 @@ EXPORTS = [
     "hibag_hip_predict_topk_snp_major", "hibag_hip_predict_topk_bed",
     "hibag_hip_cohort_new", "hibag_hip_cohort_from_bed", "hibag_hip_cohort_free", "hibag_hip_cohort_device",
     "hibag_hip_cohort_n_samp", "hibag_hip_cohort_n_snp", "hibag_hip_cohort_bytes", "hibag_hip_cohort_snp_counts",
-    "hibag_hip_predict_cohort", "hibag_hip_predict_topk_cohort",
+    "hibag_hip_predict_cohort", "hibag_hip_predict_topk_cohort", "hibag_hip_predict_masked",
 ]
 TOPK_MAX = 16      # HIBAG_HIP_TOPK_MAX of include/hibag_hip.h
 
@@ -105,6 +105,8 @@ def lib() -> C.CDLL:
     L.hibag_hip_model_mutation_table.argtypes = [vp, vp]
     L.hibag_hip_predict.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp]
     L.hibag_hip_predict_oob.argtypes = [vp, vp, i32, vp, vp, vp, vp]
+    if hasattr(L, "hibag_hip_predict_masked"):        # (absent from an older build selected with HIBAG_HIP_LIBRARY, as below)
+        L.hibag_hip_predict_masked.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp]
     L.hibag_hip_predict_prefix.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp, vp]
     L.hibag_hip_predict_prefix_ms.argtypes = [vp, C.POINTER(dbl)]
     L.hibag_hip_predict_topk.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp]

@@ -224,6 +224,10 @@ struct hibag_hip_model {
 	hibag_hip_model *prefix_layout = nullptr;
 	DevBuf pfx_tab, pfx_cw, pfx_best, pfx_cell;
 	double pfx_accum_ms = 0;
+	// hibag_hip_predict_masked: the inverted index SNP -> classifiers (CSR: n_snp + 1 offsets, then the classifiers; built at
+	// the first call), the call's mask [C][n_samp] and the batch's per-sample SNP counts [n_snp][n_pad]
+	DevBuf mask_idx, mask_use, mask_cnt;
+	bool mask_idx_ready = false;
 
 	KernelTimer timer;
 	std::mutex lock;
@@ -245,7 +249,8 @@ struct hibag_hip_model {
 		for (hipEvent_t e : dist_ev) if (e) (void)hipEventDestroy(e);
 		for (DevBuf *b : {&d_int, &d_stream, &d_tile, &d_tab, &d_blk, &d_pfac, &d_phdr, &d_parow, &ws_bt, &ws_bias, &ws_cells, &ws_sync, &ws_err, &ws_planes, &ws_cw, &ws_tot, &ws_inv, &ws_winv,
 		                  &ws_part, &ws_best, &ws_vrec, &ws_geno, &ws_out, &ws_codes, &ws_bed, &ws_bedidx, &oob_hap,
-		                  &dist_cells, &dist_tri, &dist_acc, &dist_num, &dist_out, &pfx_tab, &pfx_cw, &pfx_best, &pfx_cell})
+		                  &dist_cells, &dist_tri, &dist_acc, &dist_num, &dist_out, &pfx_tab, &pfx_cw, &pfx_best, &pfx_cell,
+		                  &mask_idx, &mask_use, &mask_cnt})
 			b->release();
 		delete prefix_layout;
 	}

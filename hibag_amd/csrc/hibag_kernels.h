@@ -61,5 +61,17 @@ struct HibagOobOut {
 // after a pack of the batch: the one-classifier weights, pass 1 with its record log, the picks -- no second pass, no finish
 void hibag_launch_oob(const HibagModelView &M, const HibagBatchView &B, const uint8_t *d_codes, const HibagOobOut &O,
 	int force_rescan, const HibagSideStream &side, hipStream_t st);
+// The per-sample classifier mask of hibag_hip_predict_masked (hibag_k_mask.h).  `use` is [C][ld] bytes with the batch's
+// sample 0 at column 0 (the caller offsets the pointer); the users of a SNP are the classifiers that hold it, in model order.
+struct HibagMaskView {
+	const uint8_t *use;                // != 0: the classifier takes part for the sample
+	size_t ld;
+	const int *user_off;               // [n_snp + 1]
+	const int *user_cls;               // [user_off[n_snp]]
+	int32_t *cnt;                      // [n_snp][n_pad] workspace: the sample's sub-model's classifiers per SNP
+};
+// after a pack of the batch, before pass 1: the sub-models' SNP counts, then their classifier weights into B.cw / B.winv
+void hibag_launch_mask_weights(const HibagModelView &M, const HibagBatchView &B, const uint8_t *d_codes, const HibagMaskView &K,
+	hipStream_t st);
 
 #endif

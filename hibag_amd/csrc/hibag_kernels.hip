@@ -84,6 +84,7 @@ static_assert(2 * HIBAG_FP4_MAX_SNPS + 1 <= ACCUM_TAB_N, "pass 2's table must co
 #include "hibag_k_finish.h"
 #include "hibag_k_topk.h"
 #include "hibag_k_oob.h"
+#include "hibag_k_mask.h"
 #include "hibag_k_cohort.h"
 
 // ---------------------------------------------------------------------------
@@ -348,4 +349,12 @@ void hibag_launch_oob(const HibagModelView &M, const HibagBatchView &B, const ui
 		const unsigned gx = (unsigned)((B.n_pad / HIBAG_WAVE + BLOCK_WAVES - 1) / BLOCK_WAVES);
 		hipLaunchKernelGGL(k_oob_best_valu, dim3(gx, M.n_classifier), dim3(BLOCK_THREADS), 0, st, M, B, O);
 	}
+}
+
+void hibag_launch_mask_weights(const HibagModelView &M, const HibagBatchView &B, const uint8_t *d_codes, const HibagMaskView &K,
+	hipStream_t st)
+{
+	if (M.n_classifier == 0 || M.n_snp == 0) return;
+	hipLaunchKernelGGL(k_mask_counts, dim3(B.n_pad / 64, M.n_snp), dim3(64), 0, st, M, B, K);
+	hipLaunchKernelGGL(k_mask_weight, dim3(B.n_pad / 64, M.n_classifier), dim3(64), 0, st, M, B, d_codes, K);
 }

@@ -639,6 +639,98 @@ int predict_oob_locked(hibag_hip_model *m, const int32_t *geno, int n_samp, cons
 	return 0;
 }
 
+// ---------------------------------------------------------------------------
+// A per-sample classifier mask (hibag_hip_predict_masked)
+
+// The inverted index SNP -> classifiers of the model on the device (HibagMaskView::user_off / user_cls): what
+// k_mask_counts walks.  Users are listed in model order.
+int mask_user_index(hibag_hip_model *m)
+{
+	if (m->mask_idx_ready) return 0;
+	const int S = std::max(m->n_snp, 0);
+	std::vector<int> tab((size_t)S + 1, 0);
+	for (const HostClassifier &k : m->cls) for (int v : k.snpidx) tab[(size_t)v + 1]++;
+	for (int v = 0; v < S; v++) tab[(size_t)v + 1] += tab[v];
+	const size_t n_user = (size_t)tab[S];
+	std::vector<int> at(tab.begin(), tab.end() - 1);
+	tab.resize((size_t)S + 1 + std::max<size_t>(n_user, 1), 0);
+	for (size_t c = 0; c < m->cls.size(); c++) for (int v : m->cls[c].snpidx) tab[(size_t)S + 1 + at[v]++] = (int)c;
+	if (int rc = m->mask_idx.reserve(tab.size() * sizeof(int))) return rc;
+	HIP_TRY(hipMemcpy(m->mask_idx.p, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice));
+	m->mask_idx_ready = true;
+	return 0;
+}
+
+// The whole call on the device, in the manner of predict_oob_locked (training cohorts are small): genotypes and mask up
+// once, batches of at most batch_limit samples (pack, the sub-models' weights, passes 1 and 2 or the vote, finish), the
+// outputs down once.  A failed hand-over is repaired as there: once more without hand-overs, before anything is returned.
+int predict_masked_locked(hibag_hip_model *m, const int32_t *geno, int n_samp, const uint8_t *use, int vote_method,
+	int32_t *H1, int32_t *H2, double *max_prob, double *matching, double *dosage, double *postprob, bool is_retry = false)
+{
+	if (m->ws_pending && m->ws_done && !is_retry) HIP_TRY(hipEventSynchronize(m->ws_done));
+	if (int rc = sticky_fault(m)) return rc;
+	if (int rc = mask_user_index(m)) return rc;
+	StagedStreams *ss;
+	if (int rc = staged_streams(m, &ss)) return rc;
+	const hipStream_t st = ss->run;
+	const size_t C = (size_t)m->view.n_classifier, n = (size_t)n_samp, S = (size_t)m->n_snp, P = (size_t)m->view.n_cell,
+		nh = (size_t)m->n_hla;
+	const size_t o_h1 = 0, o_h2 = o_h1 + n * 4, o_mp = (o_h2 + n * 4 + 7) / 8 * 8, o_mt = o_mp + n * 8, o_ds = o_mt + n * 8,
+		o_pp = o_ds + (dosage ? n * nh * 8 : 0), out_bytes = o_pp + (postprob ? n * P * 8 : 0);
+	int lim = batch_limit(m);
+	if (const char *e = getenv("HIBAG_MASK_BATCH")) lim = std::min(lim, std::max(64, atoi(e)) / 64 * 64);     // (diagnostic: smaller batches)
+	const size_t pad_max = (size_t)round_up(std::min(lim, n_samp), HIBAG_WAVE);
+	if (int rc = m->ws_geno.reserve(std::max<size_t>(n * S * sizeof(int32_t), 4))) return rc;
+	if (int rc = m->ws_out.reserve(out_bytes)) return rc;
+	if (int rc = m->mask_use.reserve(std::max<size_t>(C * n, 1))) return rc;
+	if (int rc = m->mask_cnt.reserve(std::max<size_t>(S, 1) * pad_max * sizeof(int32_t))) return rc;
+	char *o = m->ws_out.as<char>();
+	const int32_t *d_geno = m->ws_geno.as<int32_t>();
+	if (int rc = workspace_enter(m, st)) return rc;
+	WorkspaceGuard guard{m, st};
+	guard.enqueued = true;
+	HIP_TRY(hipMemcpyAsync(m->ws_geno.p, geno, n * S * sizeof(int32_t), hipMemcpyHostToDevice, st));
+	HIP_TRY(hipMemcpyAsync(m->mask_use.p, use, C * n, hipMemcpyHostToDevice, st));
+	for (int s0 = 0; s0 < n_samp; s0 += lim) {
+		const int nb = std::min(lim, n_samp - s0);
+		HibagBatchView B;
+		if (int rc = make_batch(m, nb, vote_method == 2, B)) return rc;
+		HibagMaskView K;
+		K.use = m->mask_use.as<uint8_t>() + s0; K.ld = n;
+		K.user_off = m->mask_idx.as<int>(); K.user_cls = K.user_off + S + 1;
+		K.cnt = m->mask_cnt.as<int32_t>();
+		m->timer.begin(HIBAG_HIP_K_PACK, st);
+		hibag_launch_pack(m->view, B, d_geno + (size_t)s0 * S, 0, nullptr, nullptr, m->ws_codes.as<uint8_t>(), st);
+		hibag_launch_mask_weights(m->view, B, m->ws_codes.as<uint8_t>(), K, st);
+		m->timer.end(st);
+		run_core(m, B, vote_method, m->ws_part.as<double>(), st);
+		m->timer.begin(HIBAG_HIP_K_FINISH, st, true);
+		hibag_launch_finish(m->view, B, B.part,
+			H1 ? (int32_t *)(o + o_h1) + s0 : nullptr, H2 ? (int32_t *)(o + o_h2) + s0 : nullptr,
+			max_prob ? (double *)(o + o_mp) + s0 : nullptr, matching ? (double *)(o + o_mt) + s0 : nullptr,
+			dosage ? (double *)(o + o_ds) + (size_t)s0 * nh : nullptr,
+			postprob ? (double *)(o + o_pp) + (size_t)s0 * P : nullptr, st);
+		m->timer.end(st);
+		debug_stage("masked batch", st);
+	}
+	HIP_TRY(hipGetLastError());
+	if (H1) {
+		HIP_TRY(hipMemcpyAsync(H1, o + o_h1, n * 4, hipMemcpyDeviceToHost, st));
+		HIP_TRY(hipMemcpyAsync(H2, o + o_h2, n * 4, hipMemcpyDeviceToHost, st));
+	}
+	if (max_prob) HIP_TRY(hipMemcpyAsync(max_prob, o + o_mp, n * 8, hipMemcpyDeviceToHost, st));
+	if (matching) HIP_TRY(hipMemcpyAsync(matching, o + o_mt, n * 8, hipMemcpyDeviceToHost, st));
+	if (dosage) HIP_TRY(hipMemcpyAsync(dosage, o + o_ds, n * nh * 8, hipMemcpyDeviceToHost, st));
+	if (postprob) HIP_TRY(hipMemcpyAsync(postprob, o + o_pp, n * P * 8, hipMemcpyDeviceToHost, st));
+	if (int rc = guard.leave()) return rc;
+	HIP_TRY(hipStreamSynchronize(st));
+	if (take_fault(m)) {
+		if (is_retry) return hibag_fail(HIBAG_HIP_EHANDOVER, "a hand-over between workgroups failed in a launch without hand-overs");
+		return predict_masked_locked(m, geno, n_samp, use, vote_method, H1, H2, max_prob, matching, dosage, postprob, true);
+	}
+	return 0;
+}
+
 } // namespace hibag_detail
 
 // ===========================================================================
@@ -684,6 +776,17 @@ int hibag_hip_predict_oob(hibag_hip_model *m, const int32_t *geno, int n_samp, c
 	std::lock_guard<std::mutex> g(m->lock);
 	HIP_TRY(hipSetDevice(m->device));
 	return predict_oob_locked(m, geno, n_samp, samp_num, H1, H2, prob);
+}
+
+int hibag_hip_predict_masked(hibag_hip_model *m, const int32_t *geno, int n_samp, const uint8_t *use, int vote_method,
+	int32_t *H1, int32_t *H2, double *max_prob, double *matching, double *dosage, double *postprob)
+{
+	if (int rc = check_predict_args(m, geno, n_samp, vote_method, H1, H2)) return rc;
+	if (n_samp > 0 && !use) return hibag_fail(HIBAG_HIP_EINVAL, "use is NULL");
+	if (n_samp == 0) return 0;
+	std::lock_guard<std::mutex> g(m->lock);
+	HIP_TRY(hipSetDevice(m->device));
+	return predict_masked_locked(m, geno, n_samp, use, vote_method, H1, H2, max_prob, matching, dosage, postprob);
 }
 
 // samples per batch of the device-pointer entries that take ONE batch (hibag_hip_predict_partial_device); 0 = not finalized

@@ -242,6 +242,31 @@ class HlaAttrBagClass:
                                                     _as_ptr(out["h2"]), _as_ptr(out["prob"])))
         return out
 
+    def predict_masked(self, geno: np.ndarray, use, vote_method: int = 1, want_dosage: bool = True,
+                       want_prob: bool = False) -> dict:
+        """``hibag_hip_predict_masked``: a per-sample classifier mask.  Sample s gets what ``predict_raw`` returns for it
+        from the model of the classifiers c with ``use[c, s] != 0`` (in model order, with that sub-model's own SNP weights),
+        bit for bit; a sample no classifier is used for gets call NA, ``prob`` 0, ``matching`` NaN.  ``geno`` int32
+        [n_samp, n_snp], ``use`` [n_classifier, n_samp] (bool or integer; nonzero = takes part).  Returns a dict like
+        :meth:`predict_raw`'s."""
+        g = np.ascontiguousarray(geno, np.int32)
+        if g.ndim != 2 or g.shape[1] != self.obj.n_snp:
+            raise ValueError("genomat must be [n_samp, n.snp] int32")
+        n, nc = g.shape[0], len(self.obj.classifiers)
+        u = np.asarray(use)
+        if u.dtype.kind not in "biu":
+            raise TypeError("use must be a boolean or integer array")
+        if u.shape != (nc, n):
+            raise ValueError(f"use must be [n_classifier, n_samp] = [{nc}, {n}]")
+        if int(vote_method) not in (1, 2):
+            raise ValueError("Invalid 'vote_method'.")
+        u = np.ascontiguousarray(u != 0, np.uint8)
+        out = self._outputs(n, want_dosage, want_prob)
+        _lib.check(_lib.lib().hibag_hip_predict_masked(
+            self.handle, _as_ptr(g), n, _as_ptr(u), int(vote_method), _as_ptr(out["h1"]), _as_ptr(out["h2"]),
+            _as_ptr(out["prob"]), _as_ptr(out["matching"]), _as_ptr(out.get("dosage")), _as_ptr(out.get("postprob"))))
+        return out
+
     def predict_prefix(self, genomat: np.ndarray, sizes) -> dict:
         """``hibag_hip_predict_prefix``: for every ``sizes[i]`` (strictly ascending, 1 .. n_classifier) what
         ``predict_raw`` (vote by probability) returns for the model of the first ``sizes[i]`` classifiers

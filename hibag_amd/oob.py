@@ -23,22 +23,11 @@ from .model import HlaAttrBagObj, HlaSNPGeno
 _DETAIL_AVG = ("call.rate", "accuracy", "sensitivity", "specificity", "ppv", "npv")
 
 
-def hlaOutOfBag(model: Union[HlaAttrBagObj, HlaAttrBagClass], hla: HlaAlleleClass, snp: HlaSNPGeno,
-                call_threshold: float = float("nan"), verbose: bool = True) -> Dict:
-    """Out-of-bag accuracy of ``model``: R's ``list(overall, confusion, detail)`` averaged over the classifiers.
-    ``confusion`` comes with ``confusion_rows`` / ``confusion_cols``, ``detail`` is a dict of columns."""
-    if not isinstance(model, (HlaAttrBagObj, HlaAttrBagClass)):
-        raise TypeError('inherits(model, "hlaAttrBagObj") | inherits(model, "hlaAttrBagClass") is not TRUE')
-    if not isinstance(hla, HlaAlleleClass):
-        raise TypeError('inherits(hla, "hlaAlleleClass") is not TRUE')
-    if not isinstance(snp, HlaSNPGeno):
-        raise TypeError('inherits(snp, "hlaSNPGenoClass") is not TRUE')
-    obj = model.obj if isinstance(model, HlaAttrBagClass) else model
-    if verbose and isinstance(model, HlaAttrBagClass):
-        print(f"HIBAG model for {obj.hla_locus}: {len(obj.classifiers)} individual classifiers, "
-              f"{obj.n_snp} SNPs, {obj.n_hla} unique HLA alleles")
-
-    # map samples and SNPs (R/HIBAG.R:1297-1313)
+def training_cohort(obj: HlaAttrBagObj, hla: HlaAlleleClass, snp: HlaSNPGeno, every_classifier: bool):
+    """The model's training samples and SNPs found in ``hla`` and ``snp`` (``R/HIBAG.R:1297-1313``, its errors), and the
+    bootstrap counts: ``geno`` int32 [n_samp, n_snp] in ``sample_id`` / ``snp_id`` order of the model and ``samp_num`` int32
+    [n_classifier, n_samp].  ``every_classifier``: a classifier without an out-of-bag sample raises (what ``hlaOutOfBag``,
+    which evaluates classifier by classifier, cannot do without)."""
     if not obj.sample_id:
         raise ValueError("There is no sample ID in the model.")
     spos = {s: i for i, s in enumerate(snp.sample_id)}
@@ -63,9 +52,29 @@ def hlaOutOfBag(model: Union[HlaAttrBagObj, HlaAttrBagClass], hla: HlaAlleleClas
         sn = np.asarray(c.samp_num)
         if sn.shape != (n,):
             raise ValueError(f"classifier {i + 1}: samp.num has {sn.size} entries, the model {n} samples")
-        if not np.any(sn == 0):
+        if every_classifier and not np.any(sn == 0):
             raise ValueError(f"classifier {i + 1} has no out-of-bag sample: it cannot be evaluated")
         samp_num[i] = sn
+    return geno, samp_num
+
+
+def hlaOutOfBag(model: Union[HlaAttrBagObj, HlaAttrBagClass], hla: HlaAlleleClass, snp: HlaSNPGeno,
+                call_threshold: float = float("nan"), verbose: bool = True) -> Dict:
+    """Out-of-bag accuracy of ``model``: R's ``list(overall, confusion, detail)`` averaged over the classifiers.
+    ``confusion`` comes with ``confusion_rows`` / ``confusion_cols``, ``detail`` is a dict of columns."""
+    if not isinstance(model, (HlaAttrBagObj, HlaAttrBagClass)):
+        raise TypeError('inherits(model, "hlaAttrBagObj") | inherits(model, "hlaAttrBagClass") is not TRUE')
+    if not isinstance(hla, HlaAlleleClass):
+        raise TypeError('inherits(hla, "hlaAlleleClass") is not TRUE')
+    if not isinstance(snp, HlaSNPGeno):
+        raise TypeError('inherits(snp, "hlaSNPGenoClass") is not TRUE')
+    obj = model.obj if isinstance(model, HlaAttrBagClass) else model
+    if verbose and isinstance(model, HlaAttrBagClass):
+        print(f"HIBAG model for {obj.hla_locus}: {len(obj.classifiers)} individual classifiers, "
+              f"{obj.n_snp} SNPs, {obj.n_hla} unique HLA alleles")
+
+    geno, samp_num = training_cohort(obj, hla, snp, every_classifier=True)
+    nclass = len(obj.classifiers)
 
     dev = model if isinstance(model, HlaAttrBagClass) else hlaModelFromObj(obj)
     try:

@@ -28,7 +28,8 @@ extern "C" {
                                         + hibag_hip_model_distance[_ms]; + the merge entries (hibag_hip_merge_*, hibag_hip_predict_merge[_bed]);
                                         + hibag_hip_predict_prefix[_ms];
                                        + the top-k entries (hibag_hip_predict_topk[_device, _mapped, _snp_major, _bed]): added within version 7;
-                                       + the resident cohort (hibag_hip_cohort_*, hibag_hip_predict_cohort, hibag_hip_predict_topk_cohort): likewise */
+                                       + the resident cohort (hibag_hip_cohort_*, hibag_hip_predict_cohort, hibag_hip_predict_topk_cohort): likewise;
+                                       + hibag_hip_predict_masked: likewise */
 
 /* error codes */
 #define HIBAG_HIP_OK          0
@@ -147,6 +148,19 @@ int hibag_hip_predict(hibag_hip_model *m, const int32_t *geno, int n_samp,
  * All pointers are host memory and required when n_samp > 0; one batched launch sequence, no second pass. */
 int hibag_hip_predict_oob(hibag_hip_model *m, const int32_t *geno, int n_samp, const int32_t *samp_num,
 	int32_t *H1, int32_t *H2, double *prob);
+
+/* A per-sample classifier mask (hlaOutOfBagEnsemble: every training sample typed by the classifiers that did not see it).
+ * Sample s gets exactly what hibag_hip_predict returns for it from the model made of the classifiers c with
+ * use[c][s] != 0, in model order (hlaSubModelObj-style; the SNP weights are that sub-model's own,
+ * src/LibHLA.cpp:2484-2496) -- every output bit-identical, both vote methods.  A sample no classifier is used for gets
+ * what a sample with every SNP missing gets: call NA, max_prob 0, matching NaN.
+ *   geno      int32 [n_samp][n_snp], sample-major in model order, as for hibag_hip_predict
+ *   use       uint8 [n_classifier][n_samp], row = classifier; nonzero = the classifier takes part for the sample
+ * Outputs as for hibag_hip_predict (any may be NULL; H1 and H2 only together).  All pointers are host memory; genotypes
+ * and mask go up once, the outputs come down once.  The weights are formed per sample on the device; cell sums, totals
+ * and both passes are the model's own kernels. */
+int hibag_hip_predict_masked(hibag_hip_model *m, const int32_t *geno, int n_samp, const uint8_t *use, int vote_method,
+	int32_t *H1, int32_t *H2, double *max_prob, double *matching, double *dosage, double *postprob);
 
 /* ---- allele distances: hlaDistance ------------------------------------------
  * hlaDistance(model) (R/HIBAG.R:1545-1570) in one call: for each classifier HIBAG_Distance (src/HIBAG.cpp:1284-1332),
