@@ -49,6 +49,7 @@ EXPORTS = [
     "hibag_hip_cohort_new", "hibag_hip_cohort_from_bed", "hibag_hip_cohort_free", "hibag_hip_cohort_device",
     "hibag_hip_cohort_n_samp", "hibag_hip_cohort_n_snp", "hibag_hip_cohort_bytes", "hibag_hip_cohort_snp_counts",
     "hibag_hip_predict_cohort", "hibag_hip_predict_topk_cohort", "hibag_hip_predict_masked",
+    "hibag_hip_test_build_eval_batch",
 ]
 TOPK_MAX = 16      # HIBAG_HIP_TOPK_MAX of include/hibag_hip.h
 
@@ -207,6 +208,8 @@ def lib() -> C.CDLL:
     L.hibag_hip_predict_multi_sharded.argtypes = [C.POINTER(vp), i32, vp, i32, vp, vp, vp, vp, vp, vp]
     L.hibag_hip_measure_issue_costs.argtypes = [C.POINTER(dbl)] * 4
     L.hibag_hip_test_time_avg_prob.argtypes = [vp, vp, i32, i32, i32, vp, vp, C.POINTER(dbl)]
+    if hasattr(L, "hibag_hip_test_build_eval_batch"):     # (absent from an older build selected with HIBAG_HIP_LIBRARY)
+        L.hibag_hip_test_build_eval_batch.argtypes = [i32, i32, vp, vp, i32, i32, vp, vp, vp, vp, i32, vp, i32, vp, vp]
     if hasattr(L, "hibag_hip_test_read_diag"):
         L.hibag_hip_test_read_diag.argtypes = [vp, vp, i32]
         L.hibag_hip_plugin_degraded_calls.restype = i64

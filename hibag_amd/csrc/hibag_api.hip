@@ -128,3 +128,45 @@ extern "C" int hibag_hip_test_time_avg_prob(const void *geno, const double *weig
 	if (seconds) *seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
 	return 0;
 }
+
+// The batched scoring of one growth step (hibag_build_eval_batch, hibag_plugin.h) is C++-only and otherwise reached only from
+// inside the training driver, where a step's width, candidates and route are whatever the greedy search makes them.  This
+// entry runs one such step on the caller's own arrays, between an init and a done of its own: build_init, build_set_bootstrap,
+// the cohort's genotype matrix if one is given (the candidates then travel as rows of it: the device-resident route; without
+// it the host packs each candidate's column: the host-packed route), the scoring, build_done.  It REPLACES the calling
+// thread's build state.  Tests only.
+extern "C" int hibag_hip_test_build_eval_batch(int n_hla, int n_sample, const int *boot, const void *base_geno, int n_snp,
+	int n_cand, const int *n_haplo, const void *haplo, const int32_t *columns, const int32_t *geno_snp_major, int n_matrix_snp,
+	const int *cand_snp, int acc_floor, int *acc_oob, double *loss_ib)
+{
+	if (n_hla <= 0 || n_hla > 32767 || n_sample <= 0 || n_snp < 1 || n_snp > 128 || n_cand <= 0)
+		return hibag_fail(HIBAG_HIP_EINVAL, "test_build_eval_batch: invalid sizes");
+	if (!boot || !base_geno || !n_haplo || !haplo || !acc_oob || !loss_ib)
+		return hibag_fail(HIBAG_HIP_EINVAL, "test_build_eval_batch: a required array is NULL");
+	if (geno_snp_major ? (n_matrix_snp <= 0 || !cand_snp) : !columns)
+		return hibag_fail(HIBAG_HIP_EINVAL, "test_build_eval_batch: a genotype matrix needs cand_snp, no matrix needs columns");
+	try {
+		std::vector<HibagBuildCandidate> cand((size_t)n_cand);
+		const PluginHaplotype *hp = (const PluginHaplotype *)haplo;
+		for (int c = 0; c < n_cand; c++) {
+			if (n_haplo[c] < 0) return hibag_fail(HIBAG_HIP_EINVAL, "test_build_eval_batch: negative haplotype count");
+			if (geno_snp_major && (cand_snp[c] < 0 || cand_snp[c] >= n_matrix_snp))
+				return hibag_fail(HIBAG_HIP_EINVAL, "test_build_eval_batch: cand_snp[%d] = %d is no row of the matrix", c, cand_snp[c]);
+			cand[c].haplo = hp;
+			cand[c].n_haplo = n_haplo[c];
+			cand[c].column = columns ? columns + (size_t)c * n_sample : nullptr;
+			cand[c].snp = geno_snp_major ? cand_snp[c] : -1;
+			hp += n_haplo[c];
+		}
+		struct Scope { ~Scope() { hibag_build_done(); } } scope;       // (also when one of the calls below throws)
+		hibag_build_init(n_hla, n_sample);
+		hibag_build_set_bootstrap(boot);
+		if (geno_snp_major) hibag_build_set_genotypes(geno_snp_major, n_matrix_snp);
+		hibag_build_eval_batch((const PluginGenotype *)base_geno, n_snp, cand.data(), n_cand, acc_floor, acc_oob, loss_ib);
+	} catch (const char *msg) {
+		return hibag_fail(HIBAG_HIP_ENODEV, "%s", msg);
+	} catch (const std::bad_alloc &) {
+		return hibag_fail(HIBAG_HIP_ENOMEM, "out of host memory");
+	}
+	return 0;
+}

@@ -29,7 +29,8 @@ extern "C" {
                                         + hibag_hip_predict_prefix[_ms];
                                        + the top-k entries (hibag_hip_predict_topk[_device, _mapped, _snp_major, _bed]): added within version 7;
                                        + the resident cohort (hibag_hip_cohort_*, hibag_hip_predict_cohort, hibag_hip_predict_topk_cohort): likewise;
-                                       + hibag_hip_predict_masked: likewise */
+                                       + hibag_hip_predict_masked: likewise;
+                                       + hibag_hip_test_build_eval_batch (a test entry): likewise */
 
 /* error codes */
 #define HIBAG_HIP_OK          0
@@ -685,6 +686,28 @@ long long hibag_hip_plugin_degraded_calls(void);
  * (bench.py: what the zero-change route costs a compiled host, no interpreter between the calls) and tests. */
 int hibag_hip_test_time_avg_prob(const void *geno, const double *weight, int n_samp, int n_classifier, int n_cell,
 	int32_t *best_cell, double *matching, double *seconds);
+
+/* One growth step's batched scoring on the caller's own arrays, for tests: what the training driver does per step with its
+ * candidates -- build_init(n_hla, n_sample), build_set_bootstrap(boot), the scoring of n_cand candidate lists that extend
+ * one genotype list by its SNP n_snp - 1 (1 <= n_snp <= 128), build_done -- and what a sequence of build_set_haplo_geno +
+ * build_acc_oob + build_acc_ib calls returns for them (src/LibHLA.cpp:2018-2038).
+ *   boot[n_sample]        bootstrap counts, 0 = out-of-bag
+ *   base_geno             TGenotype [n_sample] (48 bytes each): the committed SNPs and the true alleles, position n_snp - 1 missing
+ *   n_haplo[n_cand], haplo  the candidates' THaplotype lists back to back (32 bytes each), each grouped by ascending
+ *                         allele with aux.hla_allele filled (SetHaploAux_GPU, src/LibHLA.cpp:565-578)
+ *   columns               [n_cand][n_sample] the raw genotype of each candidate's SNP per sample (outside 0..2 = missing)
+ *   geno_snp_major, n_matrix_snp, cand_snp[n_cand]   optional: a SNP-major int32 matrix [n_matrix_snp][n_sample] that is kept
+ *                         on the device, and each candidate's row in it; the candidates then travel as row indices and
+ *                         `columns` is not read (it may be NULL).  With geno_snp_major NULL the host packs `columns`.
+ *   acc_floor             the search's best out-of-bag count so far
+ *   acc_oob[n_cand]       out: correct alleles over the out-of-bag samples
+ *   loss_ib[n_cand]       out: -2 * in-bag log-likelihood where acc_oob reaches the running maximum that starts at
+ *                         acc_floor (:2033-2034), else 0
+ * Replaces the calling thread's training state (like build_init); nothing else of the build entries may run on the thread
+ * in between.  (Added within ABI version 7.) */
+int hibag_hip_test_build_eval_batch(int n_hla, int n_sample, const int *boot, const void *base_geno, int n_snp,
+	int n_cand, const int *n_haplo, const void *haplo, const int32_t *columns, const int32_t *geno_snp_major, int n_matrix_snp,
+	const int *cand_snp, int acc_floor, int *acc_oob, double *loss_ib);
 
 #ifdef __cplusplus
 }

@@ -5,7 +5,10 @@ search drives a plugin (src/LibHLA.cpp:1913-1979, :1002-1073):
 * build_acc_oob against the `outofbag.acc` values the REFERENCE stored in its two
   bundled models (2 x 100 classifiers) -- known answers, not oracle outputs;
 * build_acc_ib and build_haplomatch against the oracle's restatements of
-  _PostProb / _PrepHaploMatch, bit for bit.
+  _PostProb / _PrepHaploMatch, bit for bit;
+* the same three entries on CONSTRUCTED inputs at every SNP word count (tests/training_reference.py; their properties
+  are checked by tests/test_training_inputs_host.py): no fixture classifier has more than 24 SNPs, so the fixtures run
+  build_eval<1> and one turn of match_dist's word loop only.
 """
 
 import ctypes as C
@@ -14,6 +17,7 @@ import math
 import numpy as np
 import pytest
 
+import training_reference as T
 from conftest import align_geno
 from test_hip_parity import _TGenotype, _THaplotype
 
@@ -109,3 +113,59 @@ def test_training_entries(which, oracle, hapmap_geno, hla_type_table, model_oob,
                 assert got.get(kk, []) == want, f"classifier {c}, in-bag sample {kk}"
                 assert len(want) >= 1            # the host insists on a non-empty list (src/LibHLA.cpp:1066-1072)
     tab.build_done()
+
+
+@pytest.mark.parametrize("key", list(T.PLUGIN_CASES))
+def test_training_entries_every_width(key, oracle):
+    """build_set_haplo_geno + build_acc_oob / build_acc_ib / build_haplomatch through the table, as above, on generated
+    inputs: n_snp = 1, 2, 31...33, 63...65, 95...97, 127, 128 at 65 samples (two sample groups, one of them a single lane)
+    and 1, 63, 64, 65, 130 samples at 65 SNPs.  Both packed words and both words of each genotype plane are filled, with
+    the reference's garbage above n_snp in the haplotypes.  First under test because of these cases: build_eval<2>
+    (33...64 SNPs), <3> (65...96), <4> (97...128) -- the [w * n_haplo + a] strides against the NW-strided planes, bits 0
+    and 31 of every word, the mask of the top word -- and match_dist with nw > 1.  In "far" one out-of-bag sample is far
+    from every pair: no best guess, which counts as no correct allele; its NaN posterior stays out of the in-bag sum."""
+    import hibag_amd
+    from hibag_amd import _lib
+    hibag_amd.hlaSetKernelTarget("hip")
+    cs, want = T.plugin_case(key), T.case_score(key)
+    lst = cs.lst
+    n, nh, k, H = len(cs.boot), lst.n_hla, lst.n_snp, len(lst.allele)
+    tab = _FullTable.from_address(_lib.lib().hibag_hip_gpu_ext_proc())
+    libc = C.CDLL(None)
+    libc.free.argtypes = [C.c_void_p]
+    hap_r, geno_r = lst.records(), cs.records()
+    hap = C.cast(hap_r.ctypes.data, C.POINTER(_THaplotype))
+    geno = C.cast(geno_r.ctypes.data, C.POINTER(_TGenotype))
+    boot = (C.c_int * n)(*[int(v) for v in cs.boot])
+
+    tab.build_init(nh, n)
+    try:
+        tab.build_set_bootstrap(boot)
+        tab.build_set_haplo_geno(hap, H, geno, k)
+        got_oob, got_ib = tab.build_acc_oob(), tab.build_acc_ib()
+        n_per = (C.c_size_t * nh)(*[int(v) for v in lst.lens])
+        out_n = C.c_size_t(0)
+        buf = tab.build_haplomatch(hap, n_per, k, geno, C.byref(out_n))
+        cnt = buf[0] // 2
+        pairs = np.ctypeslib.as_array(buf, shape=(1 + 2 * cnt,)).copy()
+        libc.free(buf)
+    finally:
+        tab.build_done()
+    print(f"{key}: acc_oob {got_oob} (want {want.acc_oob}), acc_ib {got_ib!r} (want {want.loss_ib!r}), {cnt} pairs")
+    assert got_oob == want.acc_oob
+    assert got_ib == want.loss_ib
+    assert out_n.value == 1 + 2 * cnt
+    got = {}
+    for q in range(cnt):
+        kk, v = int(pairs[1 + 2 * q]), int(pairs[2 + 2 * q])
+        got.setdefault(kk, []).append((v & 0xFFFF, v >> 16))
+    fm = T.flat_model([lst])
+    st = np.concatenate([[0], np.cumsum(lst.lens)])
+    inbag = np.where(cs.boot > 0)[0]
+    for kk, s in enumerate(inbag):
+        lo, hi = sorted((int(cs.a1[s]), int(cs.a2[s])))
+        ref = oracle.prep_haplo_match(fm, 0, cs.s1[s], cs.s2[s], lo, hi)
+        ref = [(int(i) - int(st[lo]), int(j) - int(st[hi])) for i, j in ref]
+        assert got.get(kk, []) == ref, f"in-bag sample {kk}"
+        assert len(ref) >= 1            # the host insists on a non-empty list (src/LibHLA.cpp:1066-1072)
+    assert set(got) <= set(range(len(inbag)))

@@ -335,6 +335,33 @@ def test_status_entries_reject_bad_arguments_without_a_gpu():
     L.hibag_hip_model_free(m)
 
 
+def test_build_eval_batch_entry_rejects_bad_arguments_without_a_gpu():
+    """hibag_hip_test_build_eval_batch checks what it is given before it touches the device or the build state."""
+    from hibag_amd import _lib
+    L = _lib.lib()
+    i32 = lambda v: np.ascontiguousarray(v, np.int32)
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    boot, geno, nh, hap = i32([1, 0]), np.zeros(2 * 48, np.uint8), i32([1]), np.zeros(32, np.uint8)
+    col, cs, acc, loss = i32([[0, 1]]), i32([0]), i32([0]), np.zeros(1)
+    call = lambda *a: L.hibag_hip_test_build_eval_batch(*a)
+    ok = [3, 2, p(boot), p(geno), 1, 1, p(nh), p(hap), p(col), None, 0, None, 0, p(acc), p(loss)]
+    for at, bad in ((0, 0), (0, 40000), (1, 0), (4, 0), (4, 129), (5, 0), (2, None), (3, None), (6, None), (7, None), (8, None),
+                    (13, None), (14, None)):
+        args = list(ok)
+        args[at] = bad
+        assert call(*args) == -1, (at, bad)
+        assert "test_build_eval_batch" in L.hibag_hip_last_error().decode()
+    with_matrix = list(ok)
+    with_matrix[8:12] = [None, p(col), 1, None]                  # a matrix without cand_snp
+    assert call(*with_matrix) == -1
+    with_matrix[11] = p(i32([1]))                                # a row the matrix does not have
+    assert call(*with_matrix) == -1 and "no row of the matrix" in L.hibag_hip_last_error().decode()
+    with_matrix[10], with_matrix[11] = 0, p(cs)                  # no rows at all
+    assert call(*with_matrix) == -1
+    nh[0] = -1
+    assert call(*ok) == -1
+
+
 def test_classifier_shard_bounds_cover_the_model_in_order():
     """hibag_hip_shard_bounds (host logic of the RCCL-merged route): contiguous, ordered, sizes within one of each other --
     the same split hibag_amd.dist.shard_bounds makes for the one-process-per-GPU route."""
