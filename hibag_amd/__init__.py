@@ -26,6 +26,7 @@ from .submodel import hlaCombineModelObj, hlaSubModelObj  # noqa: F401
 from .curve import HlaPredictCurve, hlaPredictCurve  # noqa: F401
 from .topk import HlaTopCalls, hlaPredictTopK  # noqa: F401
 from .cohort import HlaDeviceCohort, hlaPredictLoci  # noqa: F401
+from .draws import HlaPosteriorDraws, hlaPredictDraws  # noqa: F401
 from ._lib import HibagHipError  # noqa: F401
 
 __all__ = ["engine_kind", "engine_nkb", "engine_steps", "NA_INTEGER", "Classifier", "HlaAttrBagObj", "HlaSNPGeno", "load_geno", "load_model", "model_to_robj", "save_model",
@@ -34,5 +35,5 @@ __all__ = ["engine_kind", "engine_nkb", "engine_steps", "NA_INTEGER", "Classifie
            "HlaBEDGeno", "hlaBED2Geno", "hlaLociInfo", "RRandom", "hlaAllele", "hlaAttrBagging", "hlaConcurrentAttrBagging", "hlaParallelAttrBagging", "hlaUniqueAllele", "hlaAlleleDigit", "hlaPredMerge", "hlaPredictMerge", "hlaAlleleSubset", "hlaCompareAllele", "hlaFlankingSNP", "hlaGenoSubset",
            "hlaSplitAllele", "r_sample", "hlaOutOfBag", "hlaOutOfBagEnsemble", "out_of_bag_mask", "hlaGenoLD", "hlaLDMatrix", "hlaDistance",
            "hlaSubModelObj", "hlaCombineModelObj", "hlaPredictCurve", "HlaPredictCurve", "hlaPredictTopK", "HlaTopCalls",
-           "HlaDeviceCohort", "hlaPredictLoci", "load_model_list",
+           "HlaDeviceCohort", "hlaPredictLoci", "load_model_list", "hlaPredictDraws", "HlaPosteriorDraws",
            "set_seed"]

@@ -50,8 +50,11 @@ EXPORTS = [
     "hibag_hip_cohort_n_samp", "hibag_hip_cohort_n_snp", "hibag_hip_cohort_bytes", "hibag_hip_cohort_snp_counts",
     "hibag_hip_predict_cohort", "hibag_hip_predict_topk_cohort", "hibag_hip_predict_masked",
     "hibag_hip_test_build_eval_batch",
+    "hibag_hip_predict_draw", "hibag_hip_predict_draw_device", "hibag_hip_predict_draw_mapped",
+    "hibag_hip_predict_draw_snp_major", "hibag_hip_predict_draw_bed", "hibag_hip_predict_draw_cohort",
 ]
 TOPK_MAX = 16      # HIBAG_HIP_TOPK_MAX of include/hibag_hip.h
+DRAW_MAX = 64      # HIBAG_HIP_DRAW_MAX
 
 
 class HibagHipError(RuntimeError):
@@ -115,6 +118,14 @@ def lib() -> C.CDLL:
     L.hibag_hip_predict_topk_mapped.argtypes = [vp, vp, i32, i32, vp, vp, i32, i32, vp, vp, vp, vp]
     L.hibag_hip_predict_topk_snp_major.argtypes = [vp, vp, C.c_size_t, i32, i32, vp, vp, i32, i32, vp, vp, vp, vp]
     L.hibag_hip_predict_topk_bed.argtypes = [vp, C.c_char_p, i32, i32, vp, vp, i32, i32, vp, vp, vp, vp]
+    if hasattr(L, "hibag_hip_predict_draw"):          # (absent from an older build selected with HIBAG_HIP_LIBRARY)
+        u64 = C.c_uint64
+        L.hibag_hip_predict_draw.argtypes = [vp, vp, i32, i32, i32, u64, i64, vp, vp, vp, vp]
+        L.hibag_hip_predict_draw_device.argtypes = [vp, vp, i32, i32, i32, u64, i64, vp, vp, vp, vp, vp]
+        L.hibag_hip_predict_draw_mapped.argtypes = [vp, vp, i32, i32, vp, vp, i32, i32, u64, i64, vp, vp, vp, vp]
+        L.hibag_hip_predict_draw_snp_major.argtypes = [vp, vp, C.c_size_t, i32, i32, vp, vp, i32, i32, u64, i64, vp, vp, vp, vp]
+        L.hibag_hip_predict_draw_bed.argtypes = [vp, C.c_char_p, i32, i32, vp, vp, i32, i32, u64, i64, vp, vp, vp, vp]
+        L.hibag_hip_predict_draw_cohort.argtypes = [vp, vp, i32, i32, vp, vp, i32, i32, u64, i64, vp, vp, vp, vp]
     if hasattr(L, "hibag_hip_cohort_new"):
         # (an older build selected with HIBAG_HIP_LIBRARY, e.g. the parent commit's for a baseline timing, lacks the cohort
         # entries: everything else still binds, and a call that needs them fails with AttributeError)

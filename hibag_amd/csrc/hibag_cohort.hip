@@ -11,7 +11,7 @@
 //   hibag_hip_cohort_from_bed   from a BED file: the selected rows as they are in the file (an individual-major file is
 //                               transposed on the host, two bits at a time)
 //   hibag_hip_cohort_snp_counts k_cohort_counts: called genotypes and their sum per row
-//   hibag_hip_predict_cohort / hibag_hip_predict_topk_cohort
+//   hibag_hip_predict_cohort / hibag_hip_predict_topk_cohort / hibag_hip_predict_draw_cohort
 // A cohort is immutable once built: calls on different models may read it from different threads; each takes its model's
 // lock like the other host-pointer entries.
 
@@ -253,7 +253,7 @@ int cohort_from_bed(const char *bed_fn, int n_samp, int n_snp, const int32_t *sn
 
 int predict_cohort_entry(hibag_hip_model *m, const hibag_hip_cohort *c, int first, int count, const int32_t *snp_col,
 	const int32_t *flip, int vote_method, int32_t *H1, int32_t *H2, double *max_prob, double *matching, double *dosage,
-	double *postprob, const TopKOut *topk)
+	double *postprob, const ListOut *list)
 {
 	if (m && !c) return hibag_fail(HIBAG_HIP_EINVAL, "cohort is NULL");
 	if (int rc = check_predict_args(m, c, std::max(count, 0), vote_method, H1, H2)) return rc;
@@ -261,7 +261,7 @@ int predict_cohort_entry(hibag_hip_model *m, const hibag_hip_cohort *c, int firs
 		return hibag_fail(HIBAG_HIP_EINVAL, "the cohort is on device %d, the model on device %d", c->device, m->device);
 	if (first < 0 || count < 0 || (long long)first + count > c->n_samp)
 		return hibag_fail(HIBAG_HIP_EINVAL, "samples [%d, %d + %d) lie outside the cohort's %d samples", first, first, count, c->n_samp);
-	if (topk) if (int rc = check_topk_args(count, topk->k, topk->h1, topk->h2, topk->prob)) return rc;
+	if (list) if (int rc = check_list_args(count, *list)) return rc;
 	if (!snp_col && m->n_snp > 0) return hibag_fail(HIBAG_HIP_EINVAL, "snp_col is NULL");
 	for (int k = 0; k < m->n_snp; k++)
 		if (snp_col[k] >= c->n_snp)
@@ -286,7 +286,7 @@ int predict_cohort_entry(hibag_hip_model *m, const hibag_hip_cohort *c, int firs
 	src.samp0 = first;
 	src.d_row = m->ws_bedidx.as<int32_t>();
 	src.d_flip = m->ws_bedidx.as<int32_t>() + S;
-	return predict_payload_locked(m, src, count, vote_method, H1, H2, max_prob, matching, dosage, postprob, topk);
+	return predict_payload_locked(m, src, count, vote_method, H1, H2, max_prob, matching, dosage, postprob, list);
 }
 
 } // namespace
@@ -341,8 +341,17 @@ int hibag_hip_predict_cohort(hibag_hip_model *m, const hibag_hip_cohort *c, int 
 int hibag_hip_predict_topk_cohort(hibag_hip_model *m, const hibag_hip_cohort *c, int first, int count, const int32_t *snp_col,
 	const int32_t *flip, int vote_method, int k, int32_t *h1, int32_t *h2, double *prob, double *matching)
 {
-	const TopKOut topk{k, h1, h2, prob};
+	const ListOut topk{k, h1, h2, prob};
 	return predict_cohort_entry(m, c, first, count, snp_col, flip, vote_method, nullptr, nullptr, nullptr, matching, nullptr, nullptr, &topk);
+}
+
+// (`sample0` is the caller's index of sample `first`: the entry does not add `first` itself)
+int hibag_hip_predict_draw_cohort(hibag_hip_model *m, const hibag_hip_cohort *c, int first, int count, const int32_t *snp_col,
+	const int32_t *flip, int vote_method, int n_draw, uint64_t seed, int64_t sample0, int32_t *h1, int32_t *h2, double *prob,
+	double *matching)
+{
+	const ListOut draw{n_draw, h1, h2, prob, true, seed, sample0};
+	return predict_cohort_entry(m, c, first, count, snp_col, flip, vote_method, nullptr, nullptr, nullptr, matching, nullptr, nullptr, &draw);
 }
 
 } // extern "C"

@@ -278,14 +278,18 @@ struct PackSource {
 	const int32_t *d_row = nullptr, *d_flip = nullptr;
 };
 
-// The output set of the top-k entries (hibag_hip_predict_topk*), next to d_postprob in the two drivers of hibag_predict.hip:
-// per sample the k best pairs and their probabilities, [n_samp][k] each -- device pointers for predict_device_locked,
-// the caller's host arrays for predict_staged_locked.  With it the finish is k_finish_topk instead of the call / dosage /
-// posterior kernels (those outputs are not asked for by the entries that pass it).
-struct TopKOut {
-	int k = 0;
+// The list output set of the top-k entries (hibag_hip_predict_topk*) and of the draw entries (hibag_hip_predict_draw*), next
+// to d_postprob in the two drivers of hibag_predict.hip: per sample k pairs and their probabilities, [n_samp][k] each --
+// device pointers for predict_device_locked, the caller's host arrays for predict_staged_locked.  With it the finish is
+// k_finish_topk (the k best pairs) or, with `draws` set, k_finish_draw (k = n_draw pairs drawn from the posterior) instead of
+// the call / dosage / posterior kernels (those outputs are not asked for by the entries that pass it).
+struct ListOut {
+	int k = 0;                             // pairs per sample: the k of the top-k entries, the n_draw of the draw entries
 	int32_t *h1 = nullptr, *h2 = nullptr;
 	double *prob = nullptr;
+	bool draws = false;                    // which finish runs
+	uint64_t seed = 0;                     // draws: the generator's key ...
+	int64_t sample0 = 0;                   // ... and the index, in the caller's numbering, of sample 0 of h1 / h2 / prob
 };
 
 // Host image of the part of a BED file a call needs.  SNP-major files keep only
@@ -306,10 +310,10 @@ int sticky_fault(hibag_hip_model *m);
 int workspace_enter(hibag_hip_model *m, hipStream_t st);
 int workspace_leave(hibag_hip_model *m, hipStream_t st);
 int staged_streams(hibag_hip_model *m, StagedStreams **out);  // the model's streams of the host-pointer entries (created on first use)
-int check_topk_args(int n_samp, int k, const void *h1, const void *h2, const void *prob);
+int check_list_args(int n_samp, const ListOut &list);       // the list entries' own arguments, behind check_predict_args
 // the host-pointer driver (slices, download pipeline, repair of a failed hand-over) on a 2-bit payload resident on the model's device
 int predict_payload_locked(hibag_hip_model *m, const PackSource &src, int n_samp, int vote_method,
-	int32_t *H1, int32_t *H2, double *max_prob, double *matching, double *dosage, double *postprob, const TopKOut *topk);
+	int32_t *H1, int32_t *H2, double *max_prob, double *matching, double *dosage, double *postprob, const ListOut *list);
 int load_bed(const char *fn, int n_samp, int n_snp, const int32_t *want, int n_want, BedImage &img);
 
 } // namespace hibag_detail

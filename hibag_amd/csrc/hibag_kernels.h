@@ -45,6 +45,13 @@ void hibag_launch_finish(const HibagModelView &M, const HibagBatchView &B, doubl
 #define HIBAG_TOPK_MAX 16
 void hibag_launch_finish_topk(const HibagModelView &M, const HibagBatchView &B, double *d_part, int k,
 	int32_t *d_H1, int32_t *d_H2, double *d_prob, double *d_matching, hipStream_t st);
+// The finish of the draw entries (hibag_k_draw.h), launched INSTEAD of hibag_launch_finish: per sample n_draw pairs drawn
+// from the normalised ensemble matrix, d_H1 / d_H2 / d_prob [n_samp][n_draw], and d_matching [n_samp] (may be nullptr);
+// 1 <= n_draw <= HIBAG_DRAW_MAX (= HIBAG_HIP_DRAW_MAX of the public header).  Lane 0 of the batch is sample
+// `sample_index_of_first_lane` of the caller's numbering: the index the counter-based generator is keyed with.
+#define HIBAG_DRAW_MAX 64
+void hibag_launch_finish_draw(const HibagModelView &M, const HibagBatchView &B, double *d_part, int n_draw, uint64_t seed,
+	int64_t sample_index_of_first_lane, int32_t *d_H1, int32_t *d_H2, double *d_prob, double *d_matching, hipStream_t st);
 // hlaOutOfBag (hibag_k_oob.h): each classifier predicts its own out-of-bag samples.  The per-classifier arrays are
 // [C][ld] with the batch's sample 0 at column 0 (the caller offsets the pointers); the plain haplotype table (grouped by
 // allele, hla_start[c][n_hla + 1] relative to hap_off[c]) serves the rare lane whose record log cannot settle its call.

@@ -83,6 +83,7 @@ static_assert(2 * HIBAG_FP4_MAX_SNPS + 1 <= ACCUM_TAB_N, "pass 2's table must co
 #include "hibag_k_vote.h"
 #include "hibag_k_finish.h"
 #include "hibag_k_topk.h"
+#include "hibag_k_draw.h"
 #include "hibag_k_oob.h"
 #include "hibag_k_mask.h"
 #include "hibag_k_cohort.h"
@@ -335,6 +336,20 @@ void hibag_launch_finish_topk(const HibagModelView &M, const HibagBatchView &B, 
 	else if (k <= 8) LAUNCH_TOPK(8);
 	else LAUNCH_TOPK(16);
 #undef LAUNCH_TOPK
+}
+
+// the finish of the draw entries, in place of hibag_launch_finish: the fewest wavefronts per workgroup that hold n_draw (hibag_k_draw.h)
+void hibag_launch_finish_draw(const HibagModelView &M, const HibagBatchView &B, double *d_part, int n_draw, uint64_t seed,
+	int64_t sample_index_of_first_lane, int32_t *d_H1, int32_t *d_H2, double *d_prob, double *d_matching, hipStream_t st)
+{
+	static_assert(HIBAG_DRAW_MAX == 4 * DRAW_PER_WAVE, "one instantiation of k_finish_draw per wavefront count up to HIBAG_DRAW_MAX / DRAW_PER_WAVE");
+	if (n_draw < 1 || n_draw > HIBAG_DRAW_MAX) return;  // (the entries have checked n_draw)
+#define LAUNCH_DRAW(NW) hipLaunchKernelGGL(k_finish_draw<NW>, dim3(B.n_pad / 64), dim3(64 * NW), 0, st, M, B, \
+		(const double *)d_part, n_draw, seed, sample_index_of_first_lane, d_H1, d_H2, d_prob, d_matching)
+	if (n_draw <= DRAW_PER_WAVE) LAUNCH_DRAW(1);
+	else if (n_draw <= 2 * DRAW_PER_WAVE) LAUNCH_DRAW(2);
+	else LAUNCH_DRAW(4);
+#undef LAUNCH_DRAW
 }
 
 void hibag_launch_oob(const HibagModelView &M, const HibagBatchView &B, const uint8_t *d_codes, const HibagOobOut &O,

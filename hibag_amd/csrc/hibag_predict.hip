@@ -135,13 +135,17 @@ int check_predict_args(hibag_hip_model *m, const void *geno, int n_samp, int vot
 	return 0;
 }
 
-// the top-k entries' own arguments, behind check_predict_args
-int check_topk_args(int n_samp, int k, const void *h1, const void *h2, const void *prob)
+// the top-k and the draw entries' own arguments, behind check_predict_args
+int check_list_args(int n_samp, const ListOut &list)
 {
-	static_assert(HIBAG_HIP_TOPK_MAX == HIBAG_TOPK_MAX, "the public bound is the kernels' bound");
-	if (k < 1 || k > HIBAG_HIP_TOPK_MAX)
-		return hibag_fail(HIBAG_HIP_EINVAL, "k = %d is outside 1 .. %d (HIBAG_HIP_TOPK_MAX)", k, HIBAG_HIP_TOPK_MAX);
-	if (n_samp > 0 && (!h1 || !h2 || !prob)) return hibag_fail(HIBAG_HIP_EINVAL, "h1, h2 and prob are all required");
+	static_assert(HIBAG_HIP_TOPK_MAX == HIBAG_TOPK_MAX && HIBAG_HIP_DRAW_MAX == HIBAG_DRAW_MAX, "the public bounds are the kernels' bounds");
+	if (list.draws) {
+		if (list.k < 1 || list.k > HIBAG_HIP_DRAW_MAX)
+			return hibag_fail(HIBAG_HIP_EINVAL, "n_draw = %d is outside 1 .. %d (HIBAG_HIP_DRAW_MAX)", list.k, HIBAG_HIP_DRAW_MAX);
+		if (list.sample0 < 0) return hibag_fail(HIBAG_HIP_EINVAL, "sample0 = %lld is negative", (long long)list.sample0);
+	} else if (list.k < 1 || list.k > HIBAG_HIP_TOPK_MAX)
+		return hibag_fail(HIBAG_HIP_EINVAL, "k = %d is outside 1 .. %d (HIBAG_HIP_TOPK_MAX)", list.k, HIBAG_HIP_TOPK_MAX);
+	if (n_samp > 0 && (!list.h1 || !list.h2 || !list.prob)) return hibag_fail(HIBAG_HIP_EINVAL, "h1, h2 and prob are all required");
 	return 0;
 }
 
@@ -197,9 +201,9 @@ struct WorkspaceGuard {
 
 int predict_device_locked(hibag_hip_model *m, const PackSource &src, int n_samp, int vote_method,
 	int32_t *d_H1, int32_t *d_H2, double *d_max_prob, double *d_matching, double *d_dosage,
-	double *d_postprob, hipStream_t st, const TopKOut *topk = nullptr)
+	double *d_postprob, hipStream_t st, const ListOut *list = nullptr)
 {
-	// `topk` (device pointers): the top-k finish in place of the others (d_H1 .. d_postprob other than d_matching are not looked at)
+	// `list` (device pointers): the top-k or the draw finish in place of the others (d_H1 .. d_postprob other than d_matching are not looked at)
 	HIP_TRY(hipSetDevice(m->device));
 	if (int rc = workspace_enter(m, st)) return rc;
 	// Whatever way this call ends, work it has enqueued still uses the shared workspace: the next call on another stream
@@ -224,9 +228,12 @@ int predict_device_locked(hibag_hip_model *m, const PackSource &src, int n_samp,
 		m->timer.end(st);
 		run_core(m, B, vote_method, m->ws_part.as<double>(), st);
 		m->timer.begin(HIBAG_HIP_K_FINISH, st, true);
-		if (topk)
-			hibag_launch_finish_topk(m->view, B, B.part, topk->k, topk->h1 + (size_t)s0 * topk->k, topk->h2 + (size_t)s0 * topk->k,
-				topk->prob + (size_t)s0 * topk->k, d_matching ? d_matching + s0 : nullptr, st);
+		if (list && list->draws)
+			hibag_launch_finish_draw(m->view, B, B.part, list->k, list->seed, list->sample0 + s0, list->h1 + (size_t)s0 * list->k,
+				list->h2 + (size_t)s0 * list->k, list->prob + (size_t)s0 * list->k, d_matching ? d_matching + s0 : nullptr, st);
+		else if (list)
+			hibag_launch_finish_topk(m->view, B, B.part, list->k, list->h1 + (size_t)s0 * list->k, list->h2 + (size_t)s0 * list->k,
+				list->prob + (size_t)s0 * list->k, d_matching ? d_matching + s0 : nullptr, st);
 		else hibag_launch_finish(m->view, B, B.part,
 			d_H1 ? d_H1 + s0 : nullptr, d_H2 ? d_H2 + s0 : nullptr,
 			d_max_prob ? d_max_prob + s0 : nullptr, d_matching ? d_matching + s0 : nullptr,
@@ -287,9 +294,9 @@ struct HostRows {
 
 int predict_staged_locked(hibag_hip_model *m, const int32_t *geno, const PackSource *bed, int n_samp, int vote_method,
 	int32_t *H1, int32_t *H2, double *max_prob, double *matching, double *dosage, double *postprob,
-	const PackSource *map = nullptr, bool is_retry = false, const HostRows *hr = nullptr, const TopKOut *topk = nullptr)
+	const PackSource *map = nullptr, bool is_retry = false, const HostRows *hr = nullptr, const ListOut *list = nullptr)
 {
-	// `topk` (host arrays [n_samp][k]; H1 .. postprob other than `matching` are NULL then): the lists take the place of the
+	// `list` (host arrays [n_samp][k], top-k or draws; H1 .. postprob other than `matching` are NULL then): the lists take the place of the
 	// dosage in a slice's output buffer, right behind the per-sample vectors, so that a slice still comes down in one copy
 	// `map`: geno is the cohort's own matrix (map->row_len SNPs per sample); map->d_col / d_flip sit on the device
 	// `hr` (with `map` for d_col / d_flip): the cohort's matrix is SNP-major, see HostRows
@@ -303,8 +310,8 @@ int predict_staged_locked(hibag_hip_model *m, const int32_t *geno, const PackSou
 	const size_t geno_bytes = ((size_t)slice * std::max<size_t>(S, 1) * sizeof(int32_t) + 255) / 256 * 256;
 	const size_t o_h1 = 0, o_h2 = o_h1 + (size_t)slice * 4, o_mp = (o_h2 + (size_t)slice * 4 + 7) / 8 * 8,
 		o_mt = o_mp + (size_t)slice * 8, o_ds = o_mt + (size_t)slice * 8, o_pp = o_ds + (size_t)slice * nh * 8,
-		tk = topk ? (size_t)topk->k : 0, o_t1 = o_ds, o_t2 = o_t1 + (size_t)slice * tk * 4, o_tp = o_t2 + (size_t)slice * tk * 4,
-		out_bytes = ((topk ? o_tp + (size_t)slice * tk * 8 : o_pp + (postprob ? (size_t)slice * P * 8 : 0)) + 255) / 256 * 256;
+		tk = list ? (size_t)list->k : 0, o_t1 = o_ds, o_t2 = o_t1 + (size_t)slice * tk * 4, o_tp = o_t2 + (size_t)slice * tk * 4,
+		out_bytes = ((list ? o_tp + (size_t)slice * tk * 8 : o_pp + (postprob ? (size_t)slice * P * 8 : 0)) + 255) / 256 * 256;
 	// A pipelined run starts with a shorter slice: what nothing overlaps with is the staging and upload of the FIRST slice,
 	// and a third of a slice costs the kernels less (their last rounds are emptier) than the wait it saves.
 	const bool piped = n_samp > slice;
@@ -368,14 +375,14 @@ int predict_staged_locked(hibag_hip_model *m, const int32_t *geno, const PackSou
 	};
 	bool small_staged = false;
 	if (!piped)
-		if (int rc = m->pin_out.reserve(topk ? out_bytes : o_ds)) return rc;
+		if (int rc = m->pin_out.reserve(list ? out_bytes : o_ds)) return rc;
 	// device -> host of slice i's outputs: straight into the caller's arrays (one slice), or into the pinned staging buffer
 	auto download = [&](int i) -> int {
 		int s0, n; slice_of(i, s0, n);
 		const char *o = m->ws_out.as<char>() + (size_t)(i % nbuf) * out_bytes;
 		if (piped) {
 			HIP_TRY(hipStreamWaitEvent(ss->out, ss->ran[i & 1], 0));
-			const size_t used = topk ? o_tp + (size_t)n * tk * 8 : (postprob ? o_pp + (size_t)n * P * 8 : dosage ? o_ds + (size_t)n * nh * 8 : o_ds);
+			const size_t used = list ? o_tp + (size_t)n * tk * 8 : (postprob ? o_pp + (size_t)n * P * 8 : dosage ? o_ds + (size_t)n * nh * 8 : o_ds);
 			HIP_TRY(hipMemcpyAsync((char *)m->pin_out.p + (size_t)(i & 1) * out_bytes, o, used, hipMemcpyDeviceToHost, ss->out));
 			HIP_TRY(hipEventRecord(ss->down[i & 1], ss->out));
 			return 0;
@@ -385,8 +392,8 @@ int predict_staged_locked(hibag_hip_model *m, const int32_t *geno, const PackSou
 		// come down in ONE copy into pinned staging and are handed out behind the final synchronisation -- a copy into the
 		// caller's pageable memory holds the calling thread for ~12 us whatever its size, and there were four of them; the
 		// large ones (dosage, posterior) go straight to the caller's arrays.
-		if (H1 || max_prob || matching || topk) {
-			HIP_TRY(hipMemcpyAsync(m->pin_out.p, o, topk ? o_tp + (size_t)n * tk * 8 : o_ds, hipMemcpyDeviceToHost, st));     // (the lists ride along)
+		if (H1 || max_prob || matching || list) {
+			HIP_TRY(hipMemcpyAsync(m->pin_out.p, o, list ? o_tp + (size_t)n * tk * 8 : o_ds, hipMemcpyDeviceToHost, st));     // (the lists ride along)
 			small_staged = true;
 		}
 		if (dosage) HIP_TRY(hipMemcpyAsync(dosage + (size_t)s0 * nh, o + o_ds, (size_t)n * nh * 8, hipMemcpyDeviceToHost, st));
@@ -403,9 +410,9 @@ int predict_staged_locked(hibag_hip_model *m, const int32_t *geno, const PackSou
 		if (matching) memcpy(matching + s0, o + o_mt, (size_t)n * 8);
 		if (dosage) memcpy(dosage + (size_t)s0 * nh, o + o_ds, (size_t)n * nh * 8);
 		if (postprob) memcpy(postprob + (size_t)s0 * P, o + o_pp, (size_t)n * P * 8);
-		if (topk) {
-			memcpy(topk->h1 + (size_t)s0 * tk, o + o_t1, (size_t)n * tk * 4); memcpy(topk->h2 + (size_t)s0 * tk, o + o_t2, (size_t)n * tk * 4);
-			memcpy(topk->prob + (size_t)s0 * tk, o + o_tp, (size_t)n * tk * 8);
+		if (list) {
+			memcpy(list->h1 + (size_t)s0 * tk, o + o_t1, (size_t)n * tk * 4); memcpy(list->h2 + (size_t)s0 * tk, o + o_t2, (size_t)n * tk * 4);
+			memcpy(list->prob + (size_t)s0 * tk, o + o_tp, (size_t)n * tk * 8);
 		}
 		return 0;
 	};
@@ -428,12 +435,16 @@ int predict_staged_locked(hibag_hip_model *m, const int32_t *geno, const PackSou
 			if (piped) HIP_TRY(hipStreamWaitEvent(ss->run, ss->up[i & 1], 0));
 		}
 		if (piped && i >= 2) HIP_TRY(hipStreamWaitEvent(ss->run, ss->down[i & 1], 0));    // slice i - 2 has left the device output buffer
-		TopKOut d_topk;
-		if (topk) { d_topk.k = topk->k; d_topk.h1 = (int32_t *)(o + o_t1); d_topk.h2 = (int32_t *)(o + o_t2); d_topk.prob = (double *)(o + o_tp); }
+		ListOut d_list;
+		if (list) {       // (the slice's lists in the device output buffer; a draw is keyed with the sample's index in the caller's numbering)
+			d_list = *list;
+			d_list.h1 = (int32_t *)(o + o_t1); d_list.h2 = (int32_t *)(o + o_t2); d_list.prob = (double *)(o + o_tp);
+			d_list.sample0 = list->sample0 + s0;
+		}
 		if (int rc = predict_device_locked(m, src, n, vote_method,
 				H1 ? (int32_t *)(o + o_h1) : nullptr, H2 ? (int32_t *)(o + o_h2) : nullptr,
 				max_prob ? (double *)(o + o_mp) : nullptr, matching ? (double *)(o + o_mt) : nullptr,
-				dosage ? (double *)(o + o_ds) : nullptr, postprob ? (double *)(o + o_pp) : nullptr, ss->run, topk ? &d_topk : nullptr))
+				dosage ? (double *)(o + o_ds) : nullptr, postprob ? (double *)(o + o_pp) : nullptr, ss->run, list ? &d_list : nullptr))
 			return rc;
 		if (piped) HIP_TRY(hipEventRecord(ss->ran[i & 1], ss->run));
 		if (trace && piped) fprintf(stderr, "[hibag staged] slice %d enqueued at %.3f ms\n", i, now() - tr[0]);
@@ -457,9 +468,9 @@ int predict_staged_locked(hibag_hip_model *m, const int32_t *geno, const PackSou
 		if (H1) { memcpy(H1, o + o_h1, (size_t)n_samp * 4); memcpy(H2, o + o_h2, (size_t)n_samp * 4); }
 		if (max_prob) memcpy(max_prob, o + o_mp, (size_t)n_samp * 8);
 		if (matching) memcpy(matching, o + o_mt, (size_t)n_samp * 8);
-		if (topk) {
-			memcpy(topk->h1, o + o_t1, (size_t)n_samp * tk * 4); memcpy(topk->h2, o + o_t2, (size_t)n_samp * tk * 4);
-			memcpy(topk->prob, o + o_tp, (size_t)n_samp * tk * 8);
+		if (list) {
+			memcpy(list->h1, o + o_t1, (size_t)n_samp * tk * 4); memcpy(list->h2, o + o_t2, (size_t)n_samp * tk * 4);
+			memcpy(list->prob, o + o_tp, (size_t)n_samp * tk * 8);
 		}
 	}
 	if (trace) {
@@ -471,7 +482,7 @@ int predict_staged_locked(hibag_hip_model *m, const int32_t *geno, const PackSou
 	if (take_fault(m)) {
 		// poisoned outputs: once more, now without hand-overs (take_fault switched them off) -- never returned to the caller
 		if (is_retry) return hibag_fail(HIBAG_HIP_EHANDOVER, "a hand-over between workgroups failed in a launch without hand-overs");
-		return predict_staged_locked(m, geno, bed, n_samp, vote_method, H1, H2, max_prob, matching, dosage, postprob, map, true, hr, topk);
+		return predict_staged_locked(m, geno, bed, n_samp, vote_method, H1, H2, max_prob, matching, dosage, postprob, map, true, hr, list);
 	}
 	return 0;
 }
@@ -479,10 +490,10 @@ int predict_staged_locked(hibag_hip_model *m, const int32_t *geno, const PackSou
 // The host-pointer driver on a 2-bit payload that is already on the model's device (what the BED entries upload per call;
 // the rows of a resident cohort, hibag_cohort.hip): `src` as for hibag_launch_pack_bed, samples src.samp0 .. + n_samp.
 int predict_payload_locked(hibag_hip_model *m, const PackSource &src, int n_samp, int vote_method,
-	int32_t *H1, int32_t *H2, double *max_prob, double *matching, double *dosage, double *postprob, const TopKOut *topk)
+	int32_t *H1, int32_t *H2, double *max_prob, double *matching, double *dosage, double *postprob, const ListOut *list)
 {
 	return predict_staged_locked(m, nullptr, &src, n_samp, vote_method, H1, H2, max_prob, matching, dosage, postprob, nullptr, false,
-		nullptr, topk);
+		nullptr, list);
 }
 
 // ---------------------------------------------------------------------------
@@ -853,13 +864,13 @@ int hibag_hip_predict_multi(hibag_hip_model *const *models, int n_models, const 
 	return 0;
 }
 
-// (the bodies of the _mapped, _snp_major and _bed entries: the top-k entries are the same calls with `topk` set)
+// (the bodies of the _mapped, _snp_major and _bed entries: the top-k and the draw entries are the same calls with `list` set)
 static int predict_mapped_entry(hibag_hip_model *m, const int32_t *geno, int n_samp, int n_geno_snp,
 	const int32_t *snp_col, const int32_t *flip, int vote_method,
-	int32_t *H1, int32_t *H2, double *max_prob, double *matching, double *dosage, double *postprob, const TopKOut *topk)
+	int32_t *H1, int32_t *H2, double *max_prob, double *matching, double *dosage, double *postprob, const ListOut *list)
 {
 	if (int rc = check_predict_args(m, geno, n_samp, vote_method, H1, H2)) return rc;
-	if (topk) if (int rc = check_topk_args(n_samp, topk->k, topk->h1, topk->h2, topk->prob)) return rc;
+	if (list) if (int rc = check_list_args(n_samp, *list)) return rc;
 	if (n_geno_snp <= 0) return hibag_fail(HIBAG_HIP_EINVAL, "n_geno_snp must be positive");
 	if (!snp_col && m->n_snp > 0) return hibag_fail(HIBAG_HIP_EINVAL, "snp_col is NULL");
 	for (int k = 0; k < m->n_snp; k++)
@@ -880,7 +891,7 @@ static int predict_mapped_entry(hibag_hip_model *m, const int32_t *geno, int n_s
 	map.row_len = n_geno_snp;
 	map.d_col = m->ws_bedidx.as<int32_t>();
 	map.d_flip = m->ws_bedidx.as<int32_t>() + S;
-	return predict_staged_locked(m, geno, nullptr, n_samp, vote_method, H1, H2, max_prob, matching, dosage, postprob, &map, false, nullptr, topk);
+	return predict_staged_locked(m, geno, nullptr, n_samp, vote_method, H1, H2, max_prob, matching, dosage, postprob, &map, false, nullptr, list);
 }
 
 int hibag_hip_predict_mapped(hibag_hip_model *m, const int32_t *geno, int n_samp, int n_geno_snp,
@@ -908,10 +919,10 @@ int hibag_hip_predict_mapped_device(hibag_hip_model *m, const int32_t *d_geno, i
 // The cohort's matrix SNP-major: geno[row][sample] with `ld` elements between rows.  Only the model's rows are uploaded.
 static int predict_snp_major_entry(hibag_hip_model *m, const int32_t *geno, size_t ld, int n_samp, int n_geno_snp,
 	const int32_t *snp_col, const int32_t *flip, int vote_method,
-	int32_t *H1, int32_t *H2, double *max_prob, double *matching, double *dosage, double *postprob, const TopKOut *topk)
+	int32_t *H1, int32_t *H2, double *max_prob, double *matching, double *dosage, double *postprob, const ListOut *list)
 {
 	if (int rc = check_predict_args(m, geno, n_samp, vote_method, H1, H2)) return rc;
-	if (topk) if (int rc = check_topk_args(n_samp, topk->k, topk->h1, topk->h2, topk->prob)) return rc;
+	if (list) if (int rc = check_list_args(n_samp, *list)) return rc;
 	if (n_geno_snp <= 0) return hibag_fail(HIBAG_HIP_EINVAL, "n_geno_snp must be positive");
 	if (ld < (size_t)n_samp) return hibag_fail(HIBAG_HIP_EINVAL, "ld = %zu is smaller than n_samp = %d", ld, n_samp);
 	if (!snp_col && m->n_snp > n_geno_snp)
@@ -943,7 +954,7 @@ static int predict_snp_major_entry(hibag_hip_model *m, const int32_t *geno, size
 	PackSource map;
 	map.d_col = m->ws_bedidx.as<int32_t>();
 	map.d_flip = flip ? m->ws_bedidx.as<int32_t>() + S : nullptr;
-	return predict_staged_locked(m, geno, nullptr, n_samp, vote_method, H1, H2, max_prob, matching, dosage, postprob, &map, false, &hr, topk);
+	return predict_staged_locked(m, geno, nullptr, n_samp, vote_method, H1, H2, max_prob, matching, dosage, postprob, &map, false, &hr, list);
 }
 
 int hibag_hip_predict_snp_major(hibag_hip_model *m, const int32_t *geno, size_t ld, int n_samp, int n_geno_snp,
@@ -1014,10 +1025,10 @@ int hibag_hip_conv_bed(const char *bed_fn, int n_samp, int n_snp, int n_save_snp
 
 static int predict_bed_entry(hibag_hip_model *m, const char *bed_fn, int n_samp, int n_snp,
 	const int32_t *snp_col, const int32_t *flip, int vote_method,
-	int32_t *H1, int32_t *H2, double *max_prob, double *matching, double *dosage, double *postprob, const TopKOut *topk)
+	int32_t *H1, int32_t *H2, double *max_prob, double *matching, double *dosage, double *postprob, const ListOut *list)
 {
 	if (int rc = check_predict_args(m, bed_fn, n_samp, vote_method, H1, H2)) return rc;
-	if (topk) if (int rc = check_topk_args(n_samp, topk->k, topk->h1, topk->h2, topk->prob)) return rc;
+	if (list) if (int rc = check_list_args(n_samp, *list)) return rc;
 	if (!snp_col && m->n_snp > 0) return hibag_fail(HIBAG_HIP_EINVAL, "snp_col is NULL");
 	BedImage img;
 	if (int rc = load_bed(bed_fn, n_samp, n_snp, snp_col, m->n_snp, img)) return rc;
@@ -1041,7 +1052,7 @@ static int predict_bed_entry(hibag_hip_model *m, const char *bed_fn, int n_samp,
 	src.stride = img.stride;
 	src.d_row = m->ws_bedidx.as<int32_t>();
 	src.d_flip = m->ws_bedidx.as<int32_t>() + S;
-	return predict_staged_locked(m, nullptr, &src, n_samp, vote_method, H1, H2, max_prob, matching, dosage, postprob, nullptr, false, nullptr, topk);
+	return predict_staged_locked(m, nullptr, &src, n_samp, vote_method, H1, H2, max_prob, matching, dosage, postprob, nullptr, false, nullptr, list);
 }
 
 int hibag_hip_predict_bed(hibag_hip_model *m, const char *bed_fn, int n_samp, int n_snp,
@@ -1059,9 +1070,9 @@ int hibag_hip_predict_topk(hibag_hip_model *m, const int32_t *geno, int n_samp, 
 	int32_t *h1, int32_t *h2, double *prob, double *matching)
 {
 	if (int rc = check_predict_args(m, geno, n_samp, vote_method, nullptr, nullptr)) return rc;
-	if (int rc = check_topk_args(n_samp, k, h1, h2, prob)) return rc;
+	const ListOut topk{k, h1, h2, prob};
+	if (int rc = check_list_args(n_samp, topk)) return rc;
 	if (n_samp == 0) return 0;
-	const TopKOut topk{k, h1, h2, prob};
 	std::lock_guard<std::mutex> g(m->lock);
 	HIP_TRY(hipSetDevice(m->device));
 	return predict_staged_locked(m, geno, nullptr, n_samp, vote_method, nullptr, nullptr, nullptr, matching, nullptr, nullptr,
@@ -1072,8 +1083,8 @@ int hibag_hip_predict_topk_device(hibag_hip_model *m, const int32_t *d_geno, int
 	int32_t *d_h1, int32_t *d_h2, double *d_prob, double *d_matching, void *stream)
 {
 	if (int rc = check_predict_args(m, d_geno, n_samp, vote_method, nullptr, nullptr)) return rc;
-	if (int rc = check_topk_args(n_samp, k, d_h1, d_h2, d_prob)) return rc;
-	const TopKOut topk{k, d_h1, d_h2, d_prob};
+	const ListOut topk{k, d_h1, d_h2, d_prob};
+	if (int rc = check_list_args(n_samp, topk)) return rc;
 	std::lock_guard<std::mutex> g(m->lock);
 	if (int rc = sticky_fault(m)) return rc;
 	PackSource src;
@@ -1086,7 +1097,7 @@ int hibag_hip_predict_topk_mapped(hibag_hip_model *m, const int32_t *geno, int n
 	const int32_t *snp_col, const int32_t *flip, int vote_method, int k,
 	int32_t *h1, int32_t *h2, double *prob, double *matching)
 {
-	const TopKOut topk{k, h1, h2, prob};
+	const ListOut topk{k, h1, h2, prob};
 	return predict_mapped_entry(m, geno, n_samp, n_geno_snp, snp_col, flip, vote_method, nullptr, nullptr, nullptr, matching,
 		nullptr, nullptr, &topk);
 }
@@ -1095,7 +1106,7 @@ int hibag_hip_predict_topk_snp_major(hibag_hip_model *m, const int32_t *geno, si
 	const int32_t *snp_col, const int32_t *flip, int vote_method, int k,
 	int32_t *h1, int32_t *h2, double *prob, double *matching)
 {
-	const TopKOut topk{k, h1, h2, prob};
+	const ListOut topk{k, h1, h2, prob};
 	return predict_snp_major_entry(m, geno, ld, n_samp, n_geno_snp, snp_col, flip, vote_method, nullptr, nullptr, nullptr, matching,
 		nullptr, nullptr, &topk);
 }
@@ -1104,9 +1115,67 @@ int hibag_hip_predict_topk_bed(hibag_hip_model *m, const char *bed_fn, int n_sam
 	const int32_t *snp_col, const int32_t *flip, int vote_method, int k,
 	int32_t *h1, int32_t *h2, double *prob, double *matching)
 {
-	const TopKOut topk{k, h1, h2, prob};
+	const ListOut topk{k, h1, h2, prob};
 	return predict_bed_entry(m, bed_fn, n_samp, n_snp, snp_col, flip, vote_method, nullptr, nullptr, nullptr, matching,
 		nullptr, nullptr, &topk);
+}
+
+// ---- pairs drawn from every sample's posterior (include/hibag_hip.h "posterior draws") --------------------------
+// The same fronts with the draw output set: k_finish_draw in place of k_finish_topk, every batch keyed with the index of its
+// first sample in the caller's numbering (sample0 + the batch's offset in the call).
+
+int hibag_hip_predict_draw(hibag_hip_model *m, const int32_t *geno, int n_samp, int vote_method, int n_draw, uint64_t seed,
+	int64_t sample0, int32_t *h1, int32_t *h2, double *prob, double *matching)
+{
+	if (int rc = check_predict_args(m, geno, n_samp, vote_method, nullptr, nullptr)) return rc;
+	const ListOut draw{n_draw, h1, h2, prob, true, seed, sample0};
+	if (int rc = check_list_args(n_samp, draw)) return rc;
+	if (n_samp == 0) return 0;
+	std::lock_guard<std::mutex> g(m->lock);
+	HIP_TRY(hipSetDevice(m->device));
+	return predict_staged_locked(m, geno, nullptr, n_samp, vote_method, nullptr, nullptr, nullptr, matching, nullptr, nullptr,
+		nullptr, false, nullptr, &draw);
+}
+
+int hibag_hip_predict_draw_device(hibag_hip_model *m, const int32_t *d_geno, int n_samp, int vote_method, int n_draw,
+	uint64_t seed, int64_t sample0, int32_t *d_h1, int32_t *d_h2, double *d_prob, double *d_matching, void *stream)
+{
+	if (int rc = check_predict_args(m, d_geno, n_samp, vote_method, nullptr, nullptr)) return rc;
+	const ListOut draw{n_draw, d_h1, d_h2, d_prob, true, seed, sample0};
+	if (int rc = check_list_args(n_samp, draw)) return rc;
+	std::lock_guard<std::mutex> g(m->lock);
+	if (int rc = sticky_fault(m)) return rc;
+	PackSource src;
+	src.d_geno = d_geno;
+	return predict_device_locked(m, src, n_samp, vote_method, nullptr, nullptr, nullptr, d_matching, nullptr, nullptr,
+		(hipStream_t)stream, &draw);
+}
+
+int hibag_hip_predict_draw_mapped(hibag_hip_model *m, const int32_t *geno, int n_samp, int n_geno_snp,
+	const int32_t *snp_col, const int32_t *flip, int vote_method, int n_draw, uint64_t seed, int64_t sample0,
+	int32_t *h1, int32_t *h2, double *prob, double *matching)
+{
+	const ListOut draw{n_draw, h1, h2, prob, true, seed, sample0};
+	return predict_mapped_entry(m, geno, n_samp, n_geno_snp, snp_col, flip, vote_method, nullptr, nullptr, nullptr, matching,
+		nullptr, nullptr, &draw);
+}
+
+int hibag_hip_predict_draw_snp_major(hibag_hip_model *m, const int32_t *geno, size_t ld, int n_samp, int n_geno_snp,
+	const int32_t *snp_col, const int32_t *flip, int vote_method, int n_draw, uint64_t seed, int64_t sample0,
+	int32_t *h1, int32_t *h2, double *prob, double *matching)
+{
+	const ListOut draw{n_draw, h1, h2, prob, true, seed, sample0};
+	return predict_snp_major_entry(m, geno, ld, n_samp, n_geno_snp, snp_col, flip, vote_method, nullptr, nullptr, nullptr, matching,
+		nullptr, nullptr, &draw);
+}
+
+int hibag_hip_predict_draw_bed(hibag_hip_model *m, const char *bed_fn, int n_samp, int n_snp,
+	const int32_t *snp_col, const int32_t *flip, int vote_method, int n_draw, uint64_t seed, int64_t sample0,
+	int32_t *h1, int32_t *h2, double *prob, double *matching)
+{
+	const ListOut draw{n_draw, h1, h2, prob, true, seed, sample0};
+	return predict_bed_entry(m, bed_fn, n_samp, n_snp, snp_col, flip, vote_method, nullptr, nullptr, nullptr, matching,
+		nullptr, nullptr, &draw);
 }
 
 int hibag_hip_predict_partial_device(hibag_hip_model *m, const int32_t *d_geno, int n_samp,

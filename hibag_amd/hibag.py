@@ -69,6 +69,26 @@ def topk_k(k) -> int:
     return int(k)
 
 
+def draw_n(n) -> int:
+    """The ``n_draw`` of the draw entries as an int within 1 .. ``HIBAG_HIP_DRAW_MAX``; ``ValueError`` otherwise."""
+    ok = isinstance(n, (int, np.integer)) and not isinstance(n, (bool, np.bool_))
+    if not ok and isinstance(n, (float, np.floating)) and float(n).is_integer():
+        ok = True
+    if not ok or not (1 <= int(n) <= _lib.DRAW_MAX):
+        raise ValueError(f"'n' must be an integer between 1 and {_lib.DRAW_MAX} (HIBAG_HIP_DRAW_MAX): {n!r}")
+    return int(n)
+
+
+def _draw_key(seed, sample0) -> tuple:
+    """``seed`` (any integer, taken modulo 2^64) and ``sample0`` (>= 0) of the draw entries."""
+    for v, what in ((seed, "seed"), (sample0, "sample0")):
+        if not isinstance(v, (int, np.integer)) or isinstance(v, (bool, np.bool_)):
+            raise ValueError(f"'{what}' must be an integer: {v!r}")
+    if int(sample0) < 0:
+        raise ValueError(f"'sample0' must not be negative: {sample0!r}")
+    return int(seed) & 0xFFFFFFFFFFFFFFFF, int(sample0)
+
+
 class HlaAttrBagClass:
     """``hlaAttrBagClass``: an ``hlaAttrBagObj`` plus the native model handle
     (the reference keeps an index into a handle table and frees it from a
@@ -291,50 +311,46 @@ class HlaAttrBagClass:
         _lib.check(_lib.lib().hibag_hip_predict_prefix_ms(self.handle, C.byref(ms)))
         return ms.value
 
-    # --- the k best pairs of every sample (hibag_hip_predict_topk and its routes; include/hibag_hip.h "top-k") ---
+    # --- the list entries: the k best pairs of every sample (hibag_hip_predict_topk and its routes; include/hibag_hip.h
+    # "top-k") and pairs drawn from its posterior (hibag_hip_predict_draw and its routes; "posterior draws").  The two
+    # families take the same arguments on every route but for their own -- `extra`: (k,) or (n_draw, seed, sample0), which
+    # the C entries take between vote_method and h1 -- so each route is written once (`entry`: the C entry's name, `width`:
+    # pairs per sample).
     @staticmethod
     def _topk_outputs(n: int, k: int) -> dict:
         return dict(h1=np.empty((n, k), np.int32), h2=np.empty((n, k), np.int32), prob=np.empty((n, k), np.float64),
                     matching=np.empty(n, np.float64))
 
-    def predict_topk(self, genomat: np.ndarray, k: int, vote_method: int = 1) -> dict:
-        """``hibag_hip_predict_topk``: per sample the ``k`` largest cells of the normalised posterior matrix (what
-        ``predict_raw(..., want_prob=True)`` returns as ``postprob``) selected on the device -- ``h1``, ``h2`` (0-based,
-        NA = INT_MIN in the ranks no pair qualifies for) and ``prob`` (0 there), each [n_samp, k], descending, equal values
-        in pair order, and ``matching`` [n_samp].  Rank 0 is ``predict_raw``'s call.  ``genomat`` int32 [n_samp, n_snp]."""
-        k = topk_k(k)
+    def _model_col_flip(self, snp_col, flip):
+        col = np.ascontiguousarray(snp_col, np.int32)
+        if col.shape != (self.obj.n_snp,):
+            raise ValueError("snp_col must have one entry per model SNP")
+        return col, (None if flip is None else np.ascontiguousarray(np.asarray(flip) != 0, np.int32))
+
+    def _lists(self, entry: str, extra: tuple, width: int, genomat: np.ndarray, vote_method: int) -> dict:
         g = np.ascontiguousarray(genomat, np.int32)
         if g.ndim != 2 or g.shape[1] != self.obj.n_snp:
             raise ValueError("genomat must be [n_samp, n.snp] int32")
         n = g.shape[0]
-        out = self._topk_outputs(n, k)
-        _lib.check(_lib.lib().hibag_hip_predict_topk(
-            self.handle, _as_ptr(g), n, int(vote_method), k, _as_ptr(out["h1"]), _as_ptr(out["h2"]), _as_ptr(out["prob"]),
+        out = self._topk_outputs(n, width)
+        _lib.check(getattr(_lib.lib(), entry)(
+            self.handle, _as_ptr(g), n, int(vote_method), *extra, _as_ptr(out["h1"]), _as_ptr(out["h2"]), _as_ptr(out["prob"]),
             _as_ptr(out["matching"])))
         return out
 
-    def predict_topk_mapped(self, genomat: np.ndarray, snp_col: np.ndarray, flip: Optional[np.ndarray], k: int,
-                            vote_method: int = 1) -> dict:
-        """:meth:`predict_topk` on the cohort's own matrix [n_samp, n_geno_snp], as :meth:`predict_mapped`."""
-        k = topk_k(k)
+    def _lists_mapped(self, entry: str, extra: tuple, width: int, genomat: np.ndarray, snp_col, flip, vote_method: int) -> dict:
         g = np.ascontiguousarray(genomat, np.int32)
         if g.ndim != 2:
             raise ValueError("genomat must be [n_samp, n_geno_snp]")
-        col = np.ascontiguousarray(snp_col, np.int32)
-        if col.shape != (self.obj.n_snp,):
-            raise ValueError("snp_col must have one entry per model SNP")
-        fl = None if flip is None else np.ascontiguousarray(np.asarray(flip) != 0, np.int32)
+        col, fl = self._model_col_flip(snp_col, flip)
         n = g.shape[0]
-        out = self._topk_outputs(n, k)
-        _lib.check(_lib.lib().hibag_hip_predict_topk_mapped(
-            self.handle, _as_ptr(g), n, g.shape[1], _as_ptr(col), _as_ptr(fl), int(vote_method), k,
+        out = self._topk_outputs(n, width)
+        _lib.check(getattr(_lib.lib(), entry)(
+            self.handle, _as_ptr(g), n, g.shape[1], _as_ptr(col), _as_ptr(fl), int(vote_method), *extra,
             _as_ptr(out["h1"]), _as_ptr(out["h2"]), _as_ptr(out["prob"]), _as_ptr(out["matching"])))
         return out
 
-    def predict_topk_snp_major(self, genomat: np.ndarray, snp_col: Optional[np.ndarray], flip: Optional[np.ndarray], k: int,
-                               vote_method: int = 1) -> dict:
-        """:meth:`predict_topk` on a SNP-major matrix [n_geno_snp, n_samp] in C order, as :meth:`predict_snp_major`."""
-        k = topk_k(k)
+    def _lists_snp_major(self, entry: str, extra: tuple, width: int, genomat: np.ndarray, snp_col, flip, vote_method: int) -> dict:
         g = np.asarray(genomat)
         if g.ndim != 2 or g.dtype != np.int32 or g.strides[1] != 4 or g.strides[0] % 4 or (g.shape[0] > 1 and g.strides[0] < 4 * g.shape[1]):
             g = np.ascontiguousarray(g, np.int32)
@@ -342,34 +358,63 @@ class HlaAttrBagClass:
                 raise ValueError("genomat must be [n_geno_snp, n_samp]")
         col = None
         if snp_col is not None:
-            col = np.ascontiguousarray(snp_col, np.int32)
-            if col.shape != (self.obj.n_snp,):
-                raise ValueError("snp_col must have one entry per model SNP")
+            col, _ = self._model_col_flip(snp_col, None)
         elif g.shape[0] < self.obj.n_snp:
             raise ValueError("nrow(snp) == object$n.snp is not TRUE")
         fl = None if flip is None else np.ascontiguousarray(np.asarray(flip) != 0, np.int32)
         n = g.shape[1]
-        out = self._topk_outputs(n, k)
+        out = self._topk_outputs(n, width)
         ld = g.strides[0] // 4 if g.shape[0] > 1 else max(n, 1)
-        _lib.check(_lib.lib().hibag_hip_predict_topk_snp_major(
-            self.handle, _as_ptr(g), ld, n, max(g.shape[0], 1), _as_ptr(col), _as_ptr(fl), int(vote_method), k,
+        _lib.check(getattr(_lib.lib(), entry)(
+            self.handle, _as_ptr(g), ld, n, max(g.shape[0], 1), _as_ptr(col), _as_ptr(fl), int(vote_method), *extra,
             _as_ptr(out["h1"]), _as_ptr(out["h2"]), _as_ptr(out["prob"]), _as_ptr(out["matching"])))
         return out
+
+    def _lists_bed(self, entry: str, extra: tuple, width: int, bed_fn: str, n_samp: int, n_snp: int, snp_col, flip,
+                   vote_method: int) -> dict:
+        col, fl = self._model_col_flip(snp_col, flip)
+        n = int(n_samp)
+        out = self._topk_outputs(n, width)
+        _lib.check(getattr(_lib.lib(), entry)(
+            self.handle, os.fsencode(bed_fn), n, int(n_snp), _as_ptr(col), _as_ptr(fl), int(vote_method), *extra,
+            _as_ptr(out["h1"]), _as_ptr(out["h2"]), _as_ptr(out["prob"]), _as_ptr(out["matching"])))
+        return out
+
+    def _lists_cohort(self, entry: str, extra: tuple, width: int, cohort, snp_col, flip, vote_method: int, first: int,
+                      count: Optional[int]) -> dict:
+        h = cohort.handle
+        col, fl, first, n = self._cohort_args(cohort, snp_col, flip, first, count)
+        out = self._topk_outputs(max(n, 0), width)
+        _lib.check(getattr(_lib.lib(), entry)(
+            self.handle, h, first, n, _as_ptr(col), _as_ptr(fl), int(vote_method), *extra,
+            _as_ptr(out["h1"]), _as_ptr(out["h2"]), _as_ptr(out["prob"]), _as_ptr(out["matching"])))
+        return out
+
+    def predict_topk(self, genomat: np.ndarray, k: int, vote_method: int = 1) -> dict:
+        """``hibag_hip_predict_topk``: per sample the ``k`` largest cells of the normalised posterior matrix (what
+        ``predict_raw(..., want_prob=True)`` returns as ``postprob``) selected on the device -- ``h1``, ``h2`` (0-based,
+        NA = INT_MIN in the ranks no pair qualifies for) and ``prob`` (0 there), each [n_samp, k], descending, equal values
+        in pair order, and ``matching`` [n_samp].  Rank 0 is ``predict_raw``'s call.  ``genomat`` int32 [n_samp, n_snp]."""
+        k = topk_k(k)
+        return self._lists("hibag_hip_predict_topk", (k,), k, genomat, vote_method)
+
+    def predict_topk_mapped(self, genomat: np.ndarray, snp_col: np.ndarray, flip: Optional[np.ndarray], k: int,
+                            vote_method: int = 1) -> dict:
+        """:meth:`predict_topk` on the cohort's own matrix [n_samp, n_geno_snp], as :meth:`predict_mapped`."""
+        k = topk_k(k)
+        return self._lists_mapped("hibag_hip_predict_topk_mapped", (k,), k, genomat, snp_col, flip, vote_method)
+
+    def predict_topk_snp_major(self, genomat: np.ndarray, snp_col: Optional[np.ndarray], flip: Optional[np.ndarray], k: int,
+                               vote_method: int = 1) -> dict:
+        """:meth:`predict_topk` on a SNP-major matrix [n_geno_snp, n_samp] in C order, as :meth:`predict_snp_major`."""
+        k = topk_k(k)
+        return self._lists_snp_major("hibag_hip_predict_topk_snp_major", (k,), k, genomat, snp_col, flip, vote_method)
 
     def predict_topk_bed(self, bed_fn: str, n_samp: int, n_snp: int, snp_col: np.ndarray, flip: Optional[np.ndarray], k: int,
                          vote_method: int = 1) -> dict:
         """:meth:`predict_topk` on every sample of a PLINK BED file, as :meth:`predict_bed`."""
         k = topk_k(k)
-        col = np.ascontiguousarray(snp_col, np.int32)
-        if col.shape != (self.obj.n_snp,):
-            raise ValueError("snp_col must have one entry per model SNP")
-        fl = None if flip is None else np.ascontiguousarray(np.asarray(flip) != 0, np.int32)
-        n = int(n_samp)
-        out = self._topk_outputs(n, k)
-        _lib.check(_lib.lib().hibag_hip_predict_topk_bed(
-            self.handle, os.fsencode(bed_fn), n, int(n_snp), _as_ptr(col), _as_ptr(fl), int(vote_method), k,
-            _as_ptr(out["h1"]), _as_ptr(out["h2"]), _as_ptr(out["prob"]), _as_ptr(out["matching"])))
-        return out
+        return self._lists_bed("hibag_hip_predict_topk_bed", (k,), k, bed_fn, n_samp, n_snp, snp_col, flip, vote_method)
 
     def predict_topk_device(self, d_geno, n_samp: int, k: int, d_h1, d_h2, d_prob, d_matching=None, vote_method: int = 1,
                             stream=None):
@@ -378,6 +423,55 @@ class HlaAttrBagClass:
             return None if x is None else C.c_void_p(int(x))
         _lib.check(_lib.lib().hibag_hip_predict_topk_device(
             self.handle, p(d_geno), int(n_samp), int(vote_method), int(k), p(d_h1), p(d_h2), p(d_prob), p(d_matching), p(stream)))
+
+    def predict_draw(self, genomat: np.ndarray, n: int, seed: int, vote_method: int = 1, sample0: int = 0) -> dict:
+        """``hibag_hip_predict_draw``: per sample ``n`` allele pairs drawn on the device from the normalised posterior
+        matrix (what ``predict_raw(..., want_prob=True)`` returns as ``postprob``) -- ``h1``, ``h2`` (0-based, NA = INT_MIN
+        for a sample without a positive cell) and ``prob`` (the drawn pair's posterior), each [n_samp, n], and
+        ``matching`` [n_samp].  Draw t of sample s is a function of (``seed``, ``sample0 + s``, t) and the sample's posterior
+        alone.  ``genomat`` int32 [n_samp, n_snp]."""
+        n = draw_n(n)
+        return self._lists("hibag_hip_predict_draw", (n,) + _draw_key(seed, sample0), n, genomat, vote_method)
+
+    def predict_draw_mapped(self, genomat: np.ndarray, snp_col: np.ndarray, flip: Optional[np.ndarray], n: int, seed: int,
+                            vote_method: int = 1, sample0: int = 0) -> dict:
+        """:meth:`predict_draw` on the cohort's own matrix [n_samp, n_geno_snp], as :meth:`predict_mapped`."""
+        n = draw_n(n)
+        return self._lists_mapped("hibag_hip_predict_draw_mapped", (n,) + _draw_key(seed, sample0), n, genomat, snp_col, flip,
+                                  vote_method)
+
+    def predict_draw_snp_major(self, genomat: np.ndarray, snp_col: Optional[np.ndarray], flip: Optional[np.ndarray], n: int,
+                               seed: int, vote_method: int = 1, sample0: int = 0) -> dict:
+        """:meth:`predict_draw` on a SNP-major matrix [n_geno_snp, n_samp] in C order, as :meth:`predict_snp_major`."""
+        n = draw_n(n)
+        return self._lists_snp_major("hibag_hip_predict_draw_snp_major", (n,) + _draw_key(seed, sample0), n, genomat, snp_col,
+                                     flip, vote_method)
+
+    def predict_draw_bed(self, bed_fn: str, n_samp: int, n_snp: int, snp_col: np.ndarray, flip: Optional[np.ndarray], n: int,
+                         seed: int, vote_method: int = 1, sample0: int = 0) -> dict:
+        """:meth:`predict_draw` on every sample of a PLINK BED file, as :meth:`predict_bed`."""
+        n = draw_n(n)
+        return self._lists_bed("hibag_hip_predict_draw_bed", (n,) + _draw_key(seed, sample0), n, bed_fn, n_samp, n_snp, snp_col,
+                               flip, vote_method)
+
+    def predict_draw_device(self, d_geno, n_samp: int, n: int, seed: int, d_h1, d_h2, d_prob, d_matching=None,
+                            vote_method: int = 1, sample0: int = 0, stream=None):
+        """Device-pointer form of :meth:`predict_draw`; pointer arguments are ints (``tensor.data_ptr()``) or None."""
+        def p(x):
+            return None if x is None else C.c_void_p(int(x))
+        seed, sample0 = _draw_key(seed, sample0)
+        _lib.check(_lib.lib().hibag_hip_predict_draw_device(
+            self.handle, p(d_geno), int(n_samp), int(vote_method), int(n), seed, sample0, p(d_h1), p(d_h2), p(d_prob),
+            p(d_matching), p(stream)))
+
+    def predict_draw_cohort(self, cohort, snp_col: np.ndarray, flip: Optional[np.ndarray], n: int, seed: int,
+                            vote_method: int = 1, first: int = 0, count: Optional[int] = None, sample0: int = 0) -> dict:
+        """:meth:`predict_draw` on samples ``[first, first + count)`` of a resident cohort, as :meth:`predict_cohort`.
+        ``sample0`` is the caller's index of sample ``first`` (``first`` is not added to it): ``sample0=first`` draws what
+        a call over the whole cohort draws for these samples."""
+        n = draw_n(n)
+        return self._lists_cohort("hibag_hip_predict_draw_cohort", (n,) + _draw_key(seed, sample0), n, cohort, snp_col, flip,
+                                  vote_method, first, count)
 
     def predict_bed(self, bed_fn: str, n_samp: int, n_snp: int, snp_col: np.ndarray, flip: Optional[np.ndarray] = None,
                     vote_method: int = 1, want_dosage: bool = True, want_prob: bool = False) -> dict:
@@ -423,13 +517,7 @@ class HlaAttrBagClass:
                             first: int = 0, count: Optional[int] = None) -> dict:
         """:meth:`predict_topk` on samples ``[first, first + count)`` of a resident cohort, as :meth:`predict_cohort`."""
         k = topk_k(k)
-        h = cohort.handle
-        col, fl, first, n = self._cohort_args(cohort, snp_col, flip, first, count)
-        out = self._topk_outputs(max(n, 0), k)
-        _lib.check(_lib.lib().hibag_hip_predict_topk_cohort(
-            self.handle, h, first, n, _as_ptr(col), _as_ptr(fl), int(vote_method), k,
-            _as_ptr(out["h1"]), _as_ptr(out["h2"]), _as_ptr(out["prob"]), _as_ptr(out["matching"])))
-        return out
+        return self._lists_cohort("hibag_hip_predict_topk_cohort", (k,), k, cohort, snp_col, flip, vote_method, first, count)
 
     def predict_mapped(self, genomat: np.ndarray, snp_col: np.ndarray, flip: Optional[np.ndarray] = None,
                        vote_method: int = 1, want_dosage: bool = True, want_prob: bool = False) -> dict:

@@ -87,9 +87,10 @@ class HlaTopCalls:
         return f"HlaTopCalls(locus={self.locus!r}, {len(self.sample_id)} samples, k={self.k}, assembly={self.assembly!r})"
 
 
-def _topk_matrix(model: HlaAttrBagClass, g: np.ndarray, sel: Optional[np.ndarray], flip: Optional[np.ndarray], k: int,
-                 vote_method: int) -> dict:
-    """``hibag._predict_matrix``'s routing for the top-k entries: the entry follows the array's memory order, SNP
+def _list_matrix(model: HlaAttrBagClass, family: str, g: np.ndarray, sel: Optional[np.ndarray], flip: Optional[np.ndarray],
+                 args: tuple, vote_method: int) -> dict:
+    """``hibag._predict_matrix``'s routing for the list entries (``family`` "topk" or "draw": the ``predict_<family>*``
+    methods, ``args`` their own arguments -- ``(k,)`` or ``(n, seed)``): the entry follows the array's memory order, SNP
     selection and allele flips happen on the device, no second matrix is built on the host."""
     g = _as_integer(g)
     if flip is not None and not np.any(flip):
@@ -97,32 +98,21 @@ def _topk_matrix(model: HlaAttrBagClass, g: np.ndarray, sel: Optional[np.ndarray
     if g.flags.f_contiguous:
         cohort = g.T                          # a view: [n_samp, cohort SNPs], C-contiguous
         if sel is None and flip is None:
-            return model.predict_topk(cohort, k, vote_method)
+            return getattr(model, f"predict_{family}")(cohort, *args, vote_method)
         if sel is None:
             sel = np.arange(model.obj.n_snp, dtype=np.int32)
-        return model.predict_topk_mapped(cohort, sel, flip, k, vote_method)
+        return getattr(model, f"predict_{family}_mapped")(cohort, sel, flip, *args, vote_method)
     if not g.flags.c_contiguous:
         g = np.ascontiguousarray(g)
-    return model.predict_topk_snp_major(g, sel, flip, k, vote_method)
+    return getattr(model, f"predict_{family}_snp_major")(g, sel, flip, *args, vote_method)
 
 
-def hlaPredictTopK(model: HlaAttrBagClass, snp, k: int = 3, vote: str = "prob", allele_check: bool = True,
-                   match_type: str = "Position", same_strand: bool = False, verbose: bool = True,
-                   verbose_match: bool = True) -> HlaTopCalls:
-    """Per sample the ``k`` most probable allele pairs of ``hlaPredict(model, snp, vote=vote)``'s posterior matrix with
-    their probabilities, selected on the device (1 <= k <= ``HIBAG_HIP_TOPK_MAX``).
-
-    ``snp``: what ``hlaPredict`` takes on one device -- an :class:`HlaSNPGeno` (SNP matching, strand flips and missing
-    model SNPs as ``hlaPredict`` decides them, applied on the device), a numeric matrix [n.snp, n.samp] in either memory
-    order, a vector of length n.snp, a lazily opened :class:`HlaBEDGeno`, or a resident :class:`HlaDeviceCohort`.  The list is descending; equal probabilities
-    come in pair order; a pair with probability 0 (or NaN) is never listed, so a sample may have fewer than ``k`` ranks
-    filled (``NA_INTEGER`` / 0.0 in the others).  ``best()`` is ``hlaPredict(..., type="response")`` bit for bit."""
-    if not isinstance(model, HlaAttrBagClass):
-        raise TypeError("inherits(object, \"hlaAttrBagClass\") is not TRUE")
-    if vote not in _VOTES:
-        raise ValueError("'arg' should be one of \"prob\", \"majority\"")
-    k = topk_k(k)
-    vote_method = _VOTES.index(vote) + 1
+def _predict_lists(model: HlaAttrBagClass, snp, family: str, args: tuple, what: str, vote_method: int, allele_check: bool,
+                   match_type: str, same_strand: bool, verbose: bool, verbose_match: bool):
+    """What ``hlaPredictTopK`` and ``hlaPredictDraws`` share: the verbose header (``what``: the line that says what is
+    reported per sample), ``snp`` resolved to a route -- a resident cohort, a lazily opened BED file, a numeric matrix or
+    vector, an :class:`HlaSNPGeno` with SNP matching -- the call of that route's ``predict_<family>*`` entry, and the
+    "No prediction output" warning.  Returns ``(outputs, sample ids, assembly)``."""
     obj = model.obj
     out = sys.stdout
 
@@ -133,9 +123,7 @@ def hlaPredictTopK(model: HlaAttrBagClass, snp, k: int = 3, vote: str = "prob", 
         n_c = len(obj.classifiers)
         print(f"HIBAG model for HLA-{obj.hla_locus}:\n    {n_c} individual classifier{'s' if n_c > 1 else ''}\n"
               f"    {len(obj.snp_id)} SNPs\n    {obj.n_hla} unique HLA alleles: {', '.join(s)}", file=out)
-        print("Prediction:\n    the " + str(k) + " best allele pair" + ("s" if k > 1 else "") + " per sample, " +
-              ("based on the averaged posterior probabilities" if vote_method == 1
-               else "by voting from all individual classifiers"), file=out)
+        print("Prediction:\n    " + what, file=out)
 
     bed_plan = map_plan = coh_plan = None
     if isinstance(snp, HlaDeviceCohort):
@@ -181,22 +169,47 @@ def hlaPredictTopK(model: HlaAttrBagClass, snp, k: int = 3, vote: str = "prob", 
         print(f"Kernel target: {_kernel_info_text() or 'hip'}", file=out)
 
     if coh_plan is not None:
-        rv = model.predict_topk_cohort(snp, snp.rows_of(coh_plan.sel), coh_plan.flip, k, vote_method)
+        rv = getattr(model, f"predict_{family}_cohort")(snp, snp.rows_of(coh_plan.sel), coh_plan.flip, *args, vote_method)
     elif bed_plan is not None:
         col = np.where(bed_plan.sel >= 0, snp.bed_index[np.maximum(bed_plan.sel, 0)], -1)
-        rv = model.predict_topk_bed(snp.bed_fn, snp.n_bed_samp, snp.n_bed_snp, col, bed_plan.flip, k, vote_method)
+        rv = getattr(model, f"predict_{family}_bed")(snp.bed_fn, snp.n_bed_samp, snp.n_bed_snp, col, bed_plan.flip, *args,
+                                                     vote_method)
     else:
         sel = flip = None
         if map_plan is not None:
             sel = None if map_plan.identity else map_plan.sel
             flip = map_plan.flip if (map_plan.flip is not None and np.any(map_plan.flip)) else None
-        rv = _topk_matrix(model, mat, sel, flip, k, vote_method)
+        rv = _list_matrix(model, family, mat, sel, flip, args, vote_method)
 
-    res = HlaTopCalls(locus=obj.hla_locus, sample_id=list(geno_sampid), k=k, h1=rv["h1"], h2=rv["h2"], prob=rv["prob"],
-                      matching=rv["matching"], assembly=assembly, levels=obj.hla_allele)
     na_cnt = int(np.count_nonzero((rv["h1"][:, 0] == NA_INTEGER) | (rv["h2"][:, 0] == NA_INTEGER)))
     if na_cnt > 0:   # R/HIBAG.R:811-815
         import warnings
         warnings.warn(f"No prediction output{'s' if na_cnt > 1 else ''} for {na_cnt} individual"
                       f"{'s' if na_cnt > 1 else ''} (possibly due to missing SNPs).")
-    return res
+    return rv, list(geno_sampid), assembly
+
+
+def hlaPredictTopK(model: HlaAttrBagClass, snp, k: int = 3, vote: str = "prob", allele_check: bool = True,
+                   match_type: str = "Position", same_strand: bool = False, verbose: bool = True,
+                   verbose_match: bool = True) -> HlaTopCalls:
+    """Per sample the ``k`` most probable allele pairs of ``hlaPredict(model, snp, vote=vote)``'s posterior matrix with
+    their probabilities, selected on the device (1 <= k <= ``HIBAG_HIP_TOPK_MAX``).
+
+    ``snp``: what ``hlaPredict`` takes on one device -- an :class:`HlaSNPGeno` (SNP matching, strand flips and missing
+    model SNPs as ``hlaPredict`` decides them, applied on the device), a numeric matrix [n.snp, n.samp] in either memory
+    order, a vector of length n.snp, a lazily opened :class:`HlaBEDGeno`, or a resident :class:`HlaDeviceCohort`.  The list is descending; equal probabilities
+    come in pair order; a pair with probability 0 (or NaN) is never listed, so a sample may have fewer than ``k`` ranks
+    filled (``NA_INTEGER`` / 0.0 in the others).  ``best()`` is ``hlaPredict(..., type="response")`` bit for bit."""
+    if not isinstance(model, HlaAttrBagClass):
+        raise TypeError("inherits(object, \"hlaAttrBagClass\") is not TRUE")
+    if vote not in _VOTES:
+        raise ValueError("'arg' should be one of \"prob\", \"majority\"")
+    k = topk_k(k)
+    vote_method = _VOTES.index(vote) + 1
+    what = ("the " + str(k) + " best allele pair" + ("s" if k > 1 else "") + " per sample, " +
+            ("based on the averaged posterior probabilities" if vote_method == 1
+             else "by voting from all individual classifiers"))
+    rv, sample_id, assembly = _predict_lists(model, snp, "topk", (k,), what, vote_method, allele_check, match_type,
+                                             same_strand, verbose, verbose_match)
+    return HlaTopCalls(locus=model.obj.hla_locus, sample_id=sample_id, k=k, h1=rv["h1"], h2=rv["h2"], prob=rv["prob"],
+                       matching=rv["matching"], assembly=assembly, levels=model.obj.hla_allele)

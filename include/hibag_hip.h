@@ -30,6 +30,7 @@ extern "C" {
                                        + the top-k entries (hibag_hip_predict_topk[_device, _mapped, _snp_major, _bed]): added within version 7;
                                        + the resident cohort (hibag_hip_cohort_*, hibag_hip_predict_cohort, hibag_hip_predict_topk_cohort): likewise;
                                        + hibag_hip_predict_masked: likewise;
+                                       + the draw entries (hibag_hip_predict_draw[_device, _mapped, _snp_major, _bed, _cohort]): likewise;
                                        + hibag_hip_test_build_eval_batch (a test entry): likewise */
 
 /* error codes */
@@ -505,6 +506,44 @@ int hibag_hip_predict_topk_bed(hibag_hip_model *m, const char *bed_fn, int n_sam
 	const int32_t *snp_col, const int32_t *flip, int vote_method, int k,
 	int32_t *h1, int32_t *h2, double *prob, double *matching);
 
+/* ---- posterior draws: allele pairs sampled from each sample's posterior: hlaPredictDraws ----------------
+ * For analyses that carry the imputation's uncertainty (multiple imputation, haplotype or amino-acid models): per sample
+ * n_draw allele pairs drawn from the NORMALISED ensemble matrix -- exactly the values the postprob output of
+ * hibag_hip_predict holds for that vote_method -- sampled on the device; n_draw * 20 + 8 bytes per sample come back
+ * instead of 8 * n_hla (n_hla + 1) / 2.  The rule, p[c] the sample's posterior in pair order:
+ *   cum[c] = cum[c - 1] + p[c] in plain double additions in pair order (no FMA), S = the last cum;
+ *   draw t of sample i uses u = ((w0 >> 5) * 2^26 + (w1 >> 6)) * 2^-53, where (w0, w1, ., .) =
+ *   Philox4x32-10(counter = (i & 0xffffffff, i >> 32, t, 0), key = (seed & 0xffffffff, seed >> 32));
+ *   the drawn pair is the first c with cum[c] > u * S (one double multiply); a pair of probability 0 is never drawn.
+ * i = sample0 + the sample's index in the call: sample0 >= 0 is the index of the call's first sample in the caller's own
+ * numbering, so that a cohort cut into several calls (or a window of a resident cohort: the _cohort entry does NOT add
+ * `first` itself) draws what one call over the whole cohort draws.  A sample's draws depend on (seed, i, t) and its
+ * posterior alone -- not on batches, routes, a repaired hand-over or n_draw: the first n draws of a call with more are
+ * the draws of a call with n.  (R's sample(prob =) stream is deliberately not mirrored: DESIGN.md section 16.)
+ * Outputs, sample-major:
+ *   h1, h2 [n_samp][n_draw]   0-based allele indices (h1 <= h2); HIBAG_HIP_NA_INTEGER in every draw of a sample whose
+ *                             S > 0 is false (nothing positive, or NaN)
+ *   prob   [n_samp][n_draw]   the drawn pairs' posterior probabilities; for such a sample NaN if S is NaN (an underflow
+ *                             poisoned it), 0 otherwise
+ *   matching [n_samp]         as hibag_hip_predict; may be NULL
+ * h1, h2 and prob are required; 1 <= n_draw <= HIBAG_HIP_DRAW_MAX, sample0 >= 0, vote_method 1 or 2; HIBAG_HIP_EINVAL
+ * otherwise.  Everything else is as for the top-k entry of the same suffix, whose other arguments these take in the same
+ * order.  (Added within ABI version 7) */
+#define HIBAG_HIP_DRAW_MAX 64
+int hibag_hip_predict_draw(hibag_hip_model *m, const int32_t *geno, int n_samp, int vote_method, int n_draw, uint64_t seed,
+	int64_t sample0, int32_t *h1, int32_t *h2, double *prob, double *matching);
+int hibag_hip_predict_draw_device(hibag_hip_model *m, const int32_t *d_geno, int n_samp, int vote_method, int n_draw,
+	uint64_t seed, int64_t sample0, int32_t *d_h1, int32_t *d_h2, double *d_prob, double *d_matching, void *stream);
+int hibag_hip_predict_draw_mapped(hibag_hip_model *m, const int32_t *geno, int n_samp, int n_geno_snp,
+	const int32_t *snp_col, const int32_t *flip, int vote_method, int n_draw, uint64_t seed, int64_t sample0,
+	int32_t *h1, int32_t *h2, double *prob, double *matching);
+int hibag_hip_predict_draw_snp_major(hibag_hip_model *m, const int32_t *geno, size_t ld, int n_samp, int n_geno_snp,
+	const int32_t *snp_col, const int32_t *flip, int vote_method, int n_draw, uint64_t seed, int64_t sample0,
+	int32_t *h1, int32_t *h2, double *prob, double *matching);
+int hibag_hip_predict_draw_bed(hibag_hip_model *m, const char *bed_fn, int n_samp, int n_snp,
+	const int32_t *snp_col, const int32_t *flip, int vote_method, int n_draw, uint64_t seed, int64_t sample0,
+	int32_t *h1, int32_t *h2, double *prob, double *matching);
+
 /* ---- resident cohort: one cohort's genotypes kept on a device for many calls -------
  * A run types one cohort at every locus, and then asks again (the k best pairs, both vote methods, a second ancestry's
  * model).  Every entry above takes the raw genotypes again on each call -- 4 bytes per genotype up the bus and a decode per
@@ -529,7 +568,9 @@ int hibag_hip_predict_topk_bed(hibag_hip_model *m, const char *bed_fn, int n_sam
  *                              host-pointer entries; the call takes the model's lock.  Bit-identical to hibag_hip_predict_mapped
  *                              on the matrix the cohort was made from.  HIBAG_HIP_EINVAL (with a message) when cohort and
  *                              model are on different devices, the window leaves the cohort, or a snp_col entry is >= n_snp.
- *   hibag_hip_predict_topk_cohort  the same with the top-k output set (see "top-k" above). */
+ *   hibag_hip_predict_topk_cohort  the same with the top-k output set (see "top-k" above).
+ *   hibag_hip_predict_draw_cohort  the same with the draw output set (see "posterior draws" above); pass sample0 = first
+ *                              to draw what a call over the whole cohort draws for these samples. */
 typedef struct hibag_hip_cohort hibag_hip_cohort;
 hibag_hip_cohort *hibag_hip_cohort_new(const int32_t *geno, int snp_major, size_t ld, int n_samp, int n_snp,
 	const int32_t *snp_rows, int n_rows);
@@ -545,6 +586,9 @@ int hibag_hip_predict_cohort(hibag_hip_model *m, const hibag_hip_cohort *c, int 
 	double *postprob);
 int hibag_hip_predict_topk_cohort(hibag_hip_model *m, const hibag_hip_cohort *c, int first, int count, const int32_t *snp_col,
 	const int32_t *flip, int vote_method, int k, int32_t *h1, int32_t *h2, double *prob, double *matching);
+int hibag_hip_predict_draw_cohort(hibag_hip_model *m, const hibag_hip_cohort *c, int first, int count, const int32_t *snp_col,
+	const int32_t *flip, int vote_method, int n_draw, uint64_t seed, int64_t sample0, int32_t *h1, int32_t *h2, double *prob,
+	double *matching);
 
 /* ---- training: replaces HIBAG_Training + HIBAG_NewClassifiers ---------------- */
 
