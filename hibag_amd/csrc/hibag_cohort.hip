@@ -252,16 +252,15 @@ int cohort_from_bed(const char *bed_fn, int n_samp, int n_snp, const int32_t *sn
 }
 
 int predict_cohort_entry(hibag_hip_model *m, const hibag_hip_cohort *c, int first, int count, const int32_t *snp_col,
-	const int32_t *flip, int vote_method, int32_t *H1, int32_t *H2, double *max_prob, double *matching, double *dosage,
-	double *postprob, const ListOut *list)
+	const int32_t *flip, int vote_method, const PredictOut &out)
 {
 	if (m && !c) return hibag_fail(HIBAG_HIP_EINVAL, "cohort is NULL");
-	if (int rc = check_predict_args(m, c, std::max(count, 0), vote_method, H1, H2)) return rc;
+	if (int rc = check_predict_args(m, c, std::max(count, 0), vote_method, out.H1, out.H2)) return rc;
 	if (m->device != c->device)
 		return hibag_fail(HIBAG_HIP_EINVAL, "the cohort is on device %d, the model on device %d", c->device, m->device);
 	if (first < 0 || count < 0 || (long long)first + count > c->n_samp)
 		return hibag_fail(HIBAG_HIP_EINVAL, "samples [%d, %d + %d) lie outside the cohort's %d samples", first, first, count, c->n_samp);
-	if (list) if (int rc = check_list_args(count, *list)) return rc;
+	if (out.list.on) if (int rc = check_list_args(count, out.list)) return rc;
 	if (!snp_col && m->n_snp > 0) return hibag_fail(HIBAG_HIP_EINVAL, "snp_col is NULL");
 	for (int k = 0; k < m->n_snp; k++)
 		if (snp_col[k] >= c->n_snp)
@@ -269,24 +268,13 @@ int predict_cohort_entry(hibag_hip_model *m, const hibag_hip_cohort *c, int firs
 	if (count == 0) return 0;
 	std::lock_guard<std::mutex> g(m->lock);
 	HIP_TRY(hipSetDevice(m->device));
-	const size_t S = (size_t)std::max(m->n_snp, 1);
-	std::vector<int32_t> idx;
-	try { idx.assign(2 * S, 0); } catch (...) { return hibag_fail(HIBAG_HIP_ENOMEM, "out of host memory"); }
-	for (int k = 0; k < m->n_snp; k++) {
-		idx[k] = snp_col[k] < 0 ? -1 : snp_col[k];
-		idx[S + k] = flip ? (flip[k] != 0) : 0;
-	}
-	if (int rc = m->ws_bedidx.reserve(idx.size() * sizeof(int32_t))) return rc;
-	HIP_TRY(hipMemcpyAsync(m->ws_bedidx.p, idx.data(), idx.size() * sizeof(int32_t), hipMemcpyHostToDevice, 0));
-	HIP_TRY(hipStreamSynchronize(0));            // `idx` is pageable host memory about to go out of scope
-	PackSource src;
-	src.d_bed = c->rows.as<uint8_t>();
-	src.mode = 1;
-	src.stride = c->stride;
-	src.samp0 = first;
-	src.d_row = m->ws_bedidx.as<int32_t>();
-	src.d_flip = m->ws_bedidx.as<int32_t>() + S;
-	return predict_payload_locked(m, src, count, vote_method, H1, H2, max_prob, matching, dosage, postprob, list);
+	GenoSource src;                              // (a payload on the device: the resident rows)
+	src.pack.d_bed = c->rows.as<uint8_t>();
+	src.pack.mode = 1;
+	src.pack.stride = c->stride;
+	src.pack.samp0 = first;
+	if (int rc = upload_snp_map(m, snp_col, flip, &src.pack.d_row, &src.pack.d_flip)) return rc;
+	return predict_staged_locked(m, src, count, vote_method, out);
 }
 
 } // namespace
@@ -335,14 +323,13 @@ int hibag_hip_predict_cohort(hibag_hip_model *m, const hibag_hip_cohort *c, int 
 	const int32_t *flip, int vote_method, int32_t *H1, int32_t *H2, double *max_prob, double *matching, double *dosage,
 	double *postprob)
 {
-	return predict_cohort_entry(m, c, first, count, snp_col, flip, vote_method, H1, H2, max_prob, matching, dosage, postprob, nullptr);
+	return predict_cohort_entry(m, c, first, count, snp_col, flip, vote_method, {H1, H2, max_prob, matching, dosage, postprob});
 }
 
 int hibag_hip_predict_topk_cohort(hibag_hip_model *m, const hibag_hip_cohort *c, int first, int count, const int32_t *snp_col,
 	const int32_t *flip, int vote_method, int k, int32_t *h1, int32_t *h2, double *prob, double *matching)
 {
-	const ListOut topk{k, h1, h2, prob};
-	return predict_cohort_entry(m, c, first, count, snp_col, flip, vote_method, nullptr, nullptr, nullptr, matching, nullptr, nullptr, &topk);
+	return predict_cohort_entry(m, c, first, count, snp_col, flip, vote_method, PredictOut::topk(k, h1, h2, prob, matching));
 }
 
 // (`sample0` is the caller's index of sample `first`: the entry does not add `first` itself)
@@ -350,8 +337,7 @@ int hibag_hip_predict_draw_cohort(hibag_hip_model *m, const hibag_hip_cohort *c,
 	const int32_t *flip, int vote_method, int n_draw, uint64_t seed, int64_t sample0, int32_t *h1, int32_t *h2, double *prob,
 	double *matching)
 {
-	const ListOut draw{n_draw, h1, h2, prob, true, seed, sample0};
-	return predict_cohort_entry(m, c, first, count, snp_col, flip, vote_method, nullptr, nullptr, nullptr, matching, nullptr, nullptr, &draw);
+	return predict_cohort_entry(m, c, first, count, snp_col, flip, vote_method, PredictOut::draw(n_draw, seed, sample0, h1, h2, prob, matching));
 }
 
 } // extern "C"

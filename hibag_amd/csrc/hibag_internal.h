@@ -1,11 +1,14 @@
 // hibag_internal.h -- what the host-side translation units of libhibag_hip.so share: the model container behind the opaque
-// `hibag_hip_model` of include/hibag_hip.h, its device / pinned buffers, the per-kernel timers, and the few functions that
-// cross the files:
+// `hibag_hip_model` of include/hibag_hip.h, its device / pinned buffers, the per-kernel timers, the types that carry a
+// prediction call through the drivers -- PredictOut (what to return), GenoSource / PackSource (where the genotypes come
+// from), WorkspaceGuard, with_handover_repair (the repair of a failed hand-over) -- and the few functions that cross the files:
 //   hibag_api.hip      error state, device selection, kernel target, the plugin table
 //   hibag_model.hip    the model: classifiers in, the device layout out (hibag_hip_model_new ... _finalize, replicas, shards)
+//   hibag_predict.hip  the batch driver that replaces CAttrBag_Model::PredictHLA: workspace, kernel sequence (enqueue_pack,
+//                      run_core), the host-pointer pipeline (predict_staged_locked), the SNP map upload, BED input, the
+//                      out-of-bag and masked drivers, partial sums, launch status, timing
 //   hibag_prefix.hip   hibag_hip_predict_prefix: every sub-model "first k classifiers" from one pass 1
-//   hibag_predict.hip  the batch driver that replaces CAttrBag_Model::PredictHLA: workspace, kernel sequence, host-pointer
-//                      pipeline, BED input, partial sums, launch status, timing
+//   hibag_merge.hip    hibag_hip_predict_merge: k models' predictions and their merge on one stream
 //   hibag_cohort.hip   a cohort's genotypes resident on a device in 2-bit form, and the prediction entries that read them
 #ifndef HIBAG_INTERNAL_H_
 #define HIBAG_INTERNAL_H_
@@ -278,18 +281,75 @@ struct PackSource {
 	const int32_t *d_row = nullptr, *d_flip = nullptr;
 };
 
-// The list output set of the top-k entries (hibag_hip_predict_topk*) and of the draw entries (hibag_hip_predict_draw*), next
-// to d_postprob in the two drivers of hibag_predict.hip: per sample k pairs and their probabilities, [n_samp][k] each --
-// device pointers for predict_device_locked, the caller's host arrays for predict_staged_locked.  With it the finish is
-// k_finish_topk (the k best pairs) or, with `draws` set, k_finish_draw (k = n_draw pairs drawn from the posterior) instead of
-// the call / dosage / posterior kernels (those outputs are not asked for by the entries that pass it).
+// The list output set of the top-k entries (hibag_hip_predict_topk*) and of the draw entries (hibag_hip_predict_draw*): per
+// sample k pairs and their probabilities, [n_samp][k] each.  With it the finish is k_finish_topk (the k best pairs) or, with
+// `draws` set, k_finish_draw (k = n_draw pairs drawn from the posterior) instead of the call / dosage / posterior kernels.
 struct ListOut {
+	bool on = false;                       // the call is a list entry's
 	int k = 0;                             // pairs per sample: the k of the top-k entries, the n_draw of the draw entries
 	int32_t *h1 = nullptr, *h2 = nullptr;
 	double *prob = nullptr;
 	bool draws = false;                    // which finish runs
 	uint64_t seed = 0;                     // draws: the generator's key ...
 	int64_t sample0 = 0;                   // ... and the index, in the caller's numbering, of sample 0 of h1 / h2 / prob
+};
+
+// What a prediction call returns, the one "outputs" parameter of the drivers: the six per-sample outputs of PredictHLA (any
+// may be null: not asked for) or, for the list entries, `list` and `matching` (the others stay null).  Device pointers for
+// predict_device_locked, the caller's host arrays for the host-pointer drivers.  (The merge drivers of hibag_merge.hip carry
+// their outputs in one too; their matrices are row-major with the samples along a row, so there advanced(s0, 1, 1) applies.)
+struct PredictOut {
+	int32_t *H1 = nullptr, *H2 = nullptr;
+	double *max_prob = nullptr, *matching = nullptr;
+	double *dosage = nullptr;              // [n_samp][n_hla]
+	double *postprob = nullptr;            // [n_samp][n_cell]
+	ListOut list;
+
+	static PredictOut topk(int k, int32_t *h1, int32_t *h2, double *prob, double *matching)
+	{
+		PredictOut o;
+		o.matching = matching;
+		o.list.on = true; o.list.k = k; o.list.h1 = h1; o.list.h2 = h2; o.list.prob = prob;
+		return o;
+	}
+	static PredictOut draw(int n_draw, uint64_t seed, int64_t sample0, int32_t *h1, int32_t *h2, double *prob, double *matching)
+	{
+		PredictOut o = topk(n_draw, h1, h2, prob, matching);
+		o.list.draws = true; o.list.seed = seed; o.list.sample0 = sample0;
+		return o;
+	}
+	// the set `s0` samples further on (null stays null; a draw is keyed with the sample's index in the caller's numbering)
+	PredictOut advanced(size_t s0, size_t n_hla, size_t n_cell) const
+	{
+		PredictOut o = *this;
+		auto adv = [](auto *&p, size_t by) { if (p) p += by; };
+		adv(o.H1, s0); adv(o.H2, s0); adv(o.max_prob, s0); adv(o.matching, s0);
+		adv(o.dosage, s0 * n_hla); adv(o.postprob, s0 * n_cell);
+		adv(o.list.h1, s0 * (size_t)list.k); adv(o.list.h2, s0 * (size_t)list.k); adv(o.list.prob, s0 * (size_t)list.k);
+		o.list.sample0 += (int64_t)s0;
+		return o;
+	}
+};
+
+// A SNP-major host matrix (hibag_hip_predict_snp_major): geno[rows[r] * ld + s] is staged as row r of a slice's
+// [rows.size()][n] device matrix -- only the rows the model uses travel.
+struct HostRows {
+	size_t ld = 0;
+	std::vector<size_t> rows;
+	bool consecutive = false;              // rows[r] = rows[0] + r: a slice is one strided block of the caller's matrix
+};
+
+// Where the genotypes of a host-pointer call come from, the one "source" parameter of predict_staged_locked:
+//   a sample-major host matrix   `geno` [n_samp][pack.row_len] (row_len 0: the model's SNPs in model order), with
+//                                pack.d_col / d_flip (on the device) if it is the cohort's own matrix
+//   SNP-major host rows          `geno` with `rows` (rows.ld != 0), pack.d_col / d_flip as above
+//   a payload on the device      `geno` null: `pack` as for hibag_launch_pack_bed (what the BED entries upload per call; the
+//                                rows of a resident cohort, hibag_cohort.hip), samples pack.samp0 .. + n_samp
+struct GenoSource {
+	const int32_t *geno = nullptr;
+	HostRows rows;
+	PackSource pack;
+	bool snp_major() const { return rows.ld != 0; }
 };
 
 // Host image of the part of a BED file a call needs.  SNP-major files keep only
@@ -303,18 +363,53 @@ struct BedImage {
 };
 
 int make_batch(hibag_hip_model *m, int n_samp, bool need_best, HibagBatchView &B);      // the model's workspace for one batch
+// the pack of batch samples [s0, s0 + B.n_samp) of `src` into m->ws_codes, whichever of the three forms `src` has
+void enqueue_pack(hibag_hip_model *m, HibagBatchView &B, const PackSource &src, int s0, hipStream_t st);
 void run_core(hibag_hip_model *m, HibagBatchView &B, int vote_method, double *d_part, hipStream_t st);   // passes 1 and 2 behind a pack
 int check_predict_args(hibag_hip_model *m, const void *geno, int n_samp, int vote_method, const void *H1, const void *H2);
+int check_list_args(int n_samp, const ListOut &list);       // the list entries' own arguments, behind check_predict_args
 bool take_fault(hibag_hip_model *m);                         // a hand-over failed since the last look: counted, hand-overs off
 int sticky_fault(hibag_hip_model *m);
 int workspace_enter(hibag_hip_model *m, hipStream_t st);
 int workspace_leave(hibag_hip_model *m, hipStream_t st);
 int staged_streams(hibag_hip_model *m, StagedStreams **out);  // the model's streams of the host-pointer entries (created on first use)
-int check_list_args(int n_samp, const ListOut &list);       // the list entries' own arguments, behind check_predict_args
-// the host-pointer driver (slices, download pipeline, repair of a failed hand-over) on a 2-bit payload resident on the model's device
-int predict_payload_locked(hibag_hip_model *m, const PackSource &src, int n_samp, int vote_method,
-	int32_t *H1, int32_t *H2, double *max_prob, double *matching, double *dosage, double *postprob, const ListOut *list);
+// the SNP map of a call on the model's device (m->ws_bedidx): col[k] (null: k; negative: -1, absent) and flip[k] != 0 of every model SNP
+int upload_snp_map(hibag_hip_model *m, const int32_t *col, const int32_t *flip, const int32_t **d_col, const int32_t **d_flip);
+// the host-pointer driver: slices, the three-stream pipeline, repair of a failed hand-over
+int predict_staged_locked(hibag_hip_model *m, const GenoSource &src, int n_samp, int vote_method, const PredictOut &out);
 int load_bed(const char *fn, int n_samp, int n_snp, const int32_t *want, int n_want, BedImage &img);
+
+// Records ws_done when a driver that enqueues on the model's shared workspace returns -- also on its error paths, once
+// anything has been enqueued.
+struct WorkspaceGuard {
+	hibag_hip_model *m = nullptr;
+	hipStream_t st = nullptr;
+	bool enqueued = false, left = false;
+	int leave() { left = true; return workspace_leave(m, st); }
+	~WorkspaceGuard() { if (enqueued && !left && m->ws_done) { (void)hipEventRecord(m->ws_done, st); m->ws_pending = true; } }
+};
+
+// The repair of a failed hand-over, for every driver whose results go to the caller's host arrays.  A device-pointer launch
+// still running on another stream may yet fail a hand-over: it is waited for first, so that its fault becomes the model's
+// sticky status (its caller's to see) instead of being taken for this call's own and repaired away.  Then `body` runs -- the
+// whole call, final synchronisation included.  If a hand-over failed in it the outputs are poisoned: the body runs once
+// more, now without hand-overs (take_fault switched them off), before anything is returned to the caller.
+template <class Body>
+int with_handover_repair(hibag_hip_model *const *models, int n_models, Body body)
+{
+	for (int i = 0; i < n_models; i++) {
+		hibag_hip_model *m = models[i];
+		if (m->ws_pending && m->ws_done) HIP_TRY(hipEventSynchronize(m->ws_done));
+		if (int rc = sticky_fault(m)) return rc;
+	}
+	for (int run = 0; run < 2; run++) {
+		if (int rc = body()) return rc;
+		bool fault = false;
+		for (int i = 0; i < n_models; i++) fault = take_fault(models[i]) || fault;
+		if (!fault) return 0;
+	}
+	return hibag_fail(HIBAG_HIP_EHANDOVER, "a hand-over between workgroups failed in a launch without hand-overs");
+}
 
 } // namespace hibag_detail
 

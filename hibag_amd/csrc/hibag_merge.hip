@@ -43,10 +43,10 @@ static int merge_chunk(const hibag_hip_merge_plan *q, hibag_hip_model *const *mo
 	return (int)std::max<long long>(64, lim / 64 * 64);
 }
 
-// The merge of one chunk: n samples, sources as S says, outputs in device memory (any may be null; dosage / postprob_out
-// are [rows][ld] with this chunk's sample 0 at column 0).
-static int merge_enqueue(hibag_hip_merge_plan *q, const HibagMergeSrc &S, bool part, int n, int32_t *d_H1, int32_t *d_H2,
-	double *d_prob, double *d_matching, double *d_dosage, double *d_postprob, size_t ld, hipStream_t st)
+// The merge of one chunk: n samples, sources as S says, outputs in device memory (any may be null; the matrices of a merge
+// are row-major, dosage [n_hla][ld] and postprob [n_row][ld], here with this chunk's sample 0 at column 0 -- so
+// PredictOut::advanced(s0, 1, 1) is the set s0 samples on).
+static int merge_enqueue(hibag_hip_merge_plan *q, const HibagMergeSrc &S, bool part, int n, const PredictOut &d, size_t ld, hipStream_t st)
 {
 	const int n_pad = round_up(n, 64);
 	if (int rc = q->acc.reserve((size_t)q->n_row * n_pad * sizeof(double))) return rc;
@@ -54,28 +54,28 @@ static int merge_enqueue(hibag_hip_merge_plan *q, const HibagMergeSrc &S, bool p
 	HibagMergePlanView Q{q->d_off.as<int>(), q->d_ent.as<uint32_t>(), q->n_hla, q->n_row};
 	double *acc = q->acc.as<double>(), *total = q->total.as<double>();
 	const dim3 g_rows(n_pad / 64, (q->n_row + MRG_ROWS - 1) / MRG_ROWS);
-	if (part) hipLaunchKernelGGL(k_merge_rows<true>, g_rows, dim3(64 * MRG_ROW_WAVES), 0, st, Q, S, n, n_pad, acc, d_matching);
-	else hipLaunchKernelGGL(k_merge_rows<false>, g_rows, dim3(64 * MRG_ROW_WAVES), 0, st, Q, S, n, n_pad, acc, d_matching);
+	if (part) hipLaunchKernelGGL(k_merge_rows<true>, g_rows, dim3(64 * MRG_ROW_WAVES), 0, st, Q, S, n, n_pad, acc, d.matching);
+	else hipLaunchKernelGGL(k_merge_rows<false>, g_rows, dim3(64 * MRG_ROW_WAVES), 0, st, Q, S, n, n_pad, acc, d.matching);
 	hipLaunchKernelGGL(k_merge_total, dim3(n_pad / 64), dim3(64), 0, st, q->n_row, n_pad, (const double *)acc, total);
 	hipLaunchKernelGGL(k_merge_call, dim3(n_pad / 64), dim3(64 * MRG_SEG), 0, st, q->n_hla, q->n_row, n, n_pad, acc,
-		(const double *)total, d_H1, d_H2, d_prob);
-	if (d_dosage)
+		(const double *)total, d.H1, d.H2, d.max_prob);
+	if (d.dosage)
 		hipLaunchKernelGGL(k_merge_dosage, dim3(n_pad / 64, (q->n_hla + MRG_SEG - 1) / MRG_SEG), dim3(64 * MRG_SEG), 0, st,
-			q->n_hla, n, n_pad, (const double *)acc, d_dosage, ld);
+			q->n_hla, n, n_pad, (const double *)acc, d.dosage, ld);
 	HIP_TRY(hipGetLastError());
-	if (d_postprob)
-		HIP_TRY(hipMemcpy2DAsync(d_postprob, ld * sizeof(double), acc, (size_t)n_pad * sizeof(double), (size_t)n * sizeof(double),
+	if (d.postprob)
+		HIP_TRY(hipMemcpy2DAsync(d.postprob, ld * sizeof(double), acc, (size_t)n_pad * sizeof(double), (size_t)n * sizeof(double),
 			(size_t)q->n_row, hipMemcpyDeviceToDevice, st));
 	return 0;
 }
 
-static int check_plan_call(const hibag_hip_merge_plan *q, const double *weight, const void *H1, const void *H2)
+static int check_plan_call(const hibag_hip_merge_plan *q, const double *weight, const PredictOut &out)
 {
 	if (!q) return hibag_fail(HIBAG_HIP_EINVAL, "merge plan is NULL");
 	if (!weight) return hibag_fail(HIBAG_HIP_EINVAL, "weight is NULL");
 	for (int i = 0; i < q->n_models; i++)
 		if (!(weight[i] >= 0)) return hibag_fail(HIBAG_HIP_EINVAL, "weight[%d] is negative or NaN", i);
-	if ((H1 == nullptr) != (H2 == nullptr)) return hibag_fail(HIBAG_HIP_EINVAL, "H1 and H2 must be given together");
+	if ((out.H1 == nullptr) != (out.H2 == nullptr)) return hibag_fail(HIBAG_HIP_EINVAL, "H1 and H2 must be given together");
 	return 0;
 }
 
@@ -91,16 +91,10 @@ struct MergeCohort {
 
 static int predict_merge_locked(hibag_hip_merge_plan *q, hibag_hip_model *const *models, const MergeCohort &co, int n_samp,
 	const int32_t *const *snp_col, const int32_t *const *flip, int vote_method, const double *weight, int use_matching,
-	int32_t *H1, int32_t *H2, double *prob, double *matching, double *dosage, double *postprob, bool is_retry)
+	const PredictOut &out)
 {
 	const int k = q->n_models;
 	hipStream_t st = q->st;
-	for (int i = 0; i < k; i++) {
-		hibag_hip_model *m = models[i];
-		// (a device-pointer launch still running elsewhere may yet fail a hand-over: its fault is its caller's to see)
-		if (m->ws_pending && m->ws_done && !is_retry) HIP_TRY(hipEventSynchronize(m->ws_done));
-		if (int rc = sticky_fault(m)) return rc;
-	}
 	// per model: column (or BED row) of each of its SNPs in the cohort, and the flips
 	std::vector<size_t> idx_at(k);
 	std::vector<int32_t> idx;
@@ -149,11 +143,27 @@ static int predict_merge_locked(hibag_hip_merge_plan *q, hibag_hip_model *const 
 	const size_t cpad = (size_t)round_up(std::min(chunk, n_samp), 64), nh = (size_t)q->n_hla;
 	// device outputs of a chunk: H1, H2 (int32), prob, matching -- 24 bytes per sample -- and the dosage matrix
 	if (int rc = q->out.reserve(cpad * 24)) return rc;
-	if (dosage) if (int rc = q->dosage.reserve(nh * cpad * sizeof(double))) return rc;
-	int32_t *o_h1 = q->out.as<int32_t>(), *o_h2 = o_h1 + cpad;
-	double *o_pb = (double *)(o_h2 + cpad), *o_mt = o_pb + cpad;
-	for (int i = 0; i < k; i++) if (int rc = workspace_enter(models[i], st)) return rc;
+	if (out.dosage) if (int rc = q->dosage.reserve(nh * cpad * sizeof(double))) return rc;
+	PredictOut d;                              // a chunk's outputs on the device: what is asked for (the posterior is the merge's own q->acc)
+	if (out.H1) { d.H1 = q->out.as<int32_t>(); d.H2 = d.H1 + cpad; }
+	if (out.max_prob) d.max_prob = (double *)(q->out.as<int32_t>() + 2 * cpad);
+	if (out.matching) d.matching = (double *)(q->out.as<int32_t>() + 2 * cpad) + cpad;
+	if (out.dosage) d.dosage = q->dosage.as<double>();
+	// one guard per model: whatever way the call ends, work it has enqueued on a model's shared workspace is chained in front
+	// of that model's next call on another stream
+	WorkspaceGuard guard[HIBAG_MERGE_MAX_MODELS];
+	for (int i = 0; i < k; i++) {
+		if (int rc = workspace_enter(models[i], st)) return rc;
+		guard[i].m = models[i]; guard[i].st = st;
+	}
 
+	PackSource cohort;
+	if (co.bed_fn) { cohort.d_bed = q->bed.as<uint8_t>(); cohort.mode = img.mode; cohort.stride = img.stride; }
+	else {
+		cohort.d_geno = q->geno.as<int32_t>();
+		if (co.snp_major) cohort.ld = (size_t)n_samp;
+		else cohort.row_len = co.n_geno_snp;
+	}
 	for (int s0 = 0; s0 < n_samp; s0 += chunk) {
 		const int n = std::min(chunk, n_samp - s0), n_pad = round_up(n, 64);
 		HibagMergeSrc S{};
@@ -163,58 +173,45 @@ static int predict_merge_locked(hibag_hip_merge_plan *q, hibag_hip_model *const 
 			hibag_hip_model *m = models[i];
 			HibagBatchView B;
 			if (int rc = make_batch(m, n, vote_method == 2, B)) return rc;
-			const int32_t *d_col = q->idx.as<int32_t>() + idx_at[i], *d_flip = d_col + m->n_snp;
-			m->timer.begin(HIBAG_HIP_K_PACK, st);
-			if (co.bed_fn)
-				hibag_launch_pack_bed(m->view, B, q->bed.as<uint8_t>(), img.mode, img.stride, s0, d_col, d_flip, m->ws_codes.as<uint8_t>(), st);
-			else if (co.snp_major)
-				hibag_launch_pack_rows(m->view, B, q->geno.as<int32_t>() + s0, (size_t)n_samp, d_col, d_flip, m->ws_codes.as<uint8_t>(), st);
-			else
-				hibag_launch_pack(m->view, B, q->geno.as<int32_t>() + (size_t)s0 * co.n_geno_snp, co.n_geno_snp, d_col, d_flip,
-					m->ws_codes.as<uint8_t>(), st);
-			m->timer.end(st);
+			guard[i].enqueued = true;
+			PackSource src = cohort;               // the cohort as this model reads it: its own SNP map
+			src.d_col = src.d_row = q->idx.as<int32_t>() + idx_at[i];
+			src.d_flip = src.d_col + m->n_snp;
+			enqueue_pack(m, B, src, s0, st);
 			run_core(m, B, vote_method, m->ws_part.as<double>(), st);
 			S.src[i] = m->ws_part.as<double>();
 			S.n_cell[i] = m->view.n_cell;
 			S.w[i] = weight[i];
 		}
-		if (int rc = merge_enqueue(q, S, true, n, H1 ? o_h1 : nullptr, H1 ? o_h2 : nullptr, prob ? o_pb : nullptr,
-				matching ? o_mt : nullptr, dosage ? q->dosage.as<double>() : nullptr, nullptr, (size_t)n_pad, st))
-			return rc;
+		if (int rc = merge_enqueue(q, S, true, n, d, (size_t)n_pad, st)) return rc;
 		// down: only what was asked for (the matrices are [row][n_samp] on the host, [row][n_pad] here)
-		if (H1) {
-			HIP_TRY(hipMemcpyAsync(H1 + s0, o_h1, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-			HIP_TRY(hipMemcpyAsync(H2 + s0, o_h2, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+		const PredictOut h = out.advanced((size_t)s0, 1, 1);
+		if (h.H1) {
+			HIP_TRY(hipMemcpyAsync(h.H1, d.H1, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+			HIP_TRY(hipMemcpyAsync(h.H2, d.H2, (size_t)n * 4, hipMemcpyDeviceToHost, st));
 		}
-		if (prob) HIP_TRY(hipMemcpyAsync(prob + s0, o_pb, (size_t)n * 8, hipMemcpyDeviceToHost, st));
-		if (matching) HIP_TRY(hipMemcpyAsync(matching + s0, o_mt, (size_t)n * 8, hipMemcpyDeviceToHost, st));
-		if (dosage)
-			HIP_TRY(hipMemcpy2DAsync(dosage + s0, (size_t)n_samp * 8, q->dosage.p, (size_t)n_pad * 8, (size_t)n * 8, nh, hipMemcpyDeviceToHost, st));
-		if (postprob)
-			HIP_TRY(hipMemcpy2DAsync(postprob + s0, (size_t)n_samp * 8, q->acc.p, (size_t)n_pad * 8, (size_t)n * 8, (size_t)q->n_row,
+		if (h.max_prob) HIP_TRY(hipMemcpyAsync(h.max_prob, d.max_prob, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+		if (h.matching) HIP_TRY(hipMemcpyAsync(h.matching, d.matching, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+		if (h.dosage)
+			HIP_TRY(hipMemcpy2DAsync(h.dosage, (size_t)n_samp * 8, d.dosage, (size_t)n_pad * 8, (size_t)n * 8, nh, hipMemcpyDeviceToHost, st));
+		if (h.postprob)
+			HIP_TRY(hipMemcpy2DAsync(h.postprob, (size_t)n_samp * 8, q->acc.p, (size_t)n_pad * 8, (size_t)n * 8, (size_t)q->n_row,
 				hipMemcpyDeviceToHost, st));
 	}
 	HIP_TRY(hipStreamSynchronize(st));
-	bool fault = false;
-	for (int i = 0; i < k; i++) fault = take_fault(models[i]) || fault;
-	if (fault) {
-		// a model's outputs were poisoned: once more, now without hand-overs (take_fault switched them off)
-		if (is_retry) return hibag_fail(HIBAG_HIP_EHANDOVER, "a hand-over between workgroups failed in a launch without hand-overs");
-		return predict_merge_locked(q, models, co, n_samp, snp_col, flip, vote_method, weight, use_matching, H1, H2, prob, matching,
-			dosage, postprob, true);
-	}
+	for (int i = 0; i < k; i++) guard[i].left = true;      // (the stream has run dry: nothing is left to chain behind)
 	return 0;
 }
 
 static int predict_merge(hibag_hip_merge_plan *q, hibag_hip_model *const *models, const MergeCohort &co, int n_samp,
 	const int32_t *const *snp_col, const int32_t *const *flip, int vote_method, const double *weight, int use_matching,
-	int32_t *H1, int32_t *H2, double *prob, double *matching, double *dosage, double *postprob)
+	const PredictOut &out)
 {
-	if (int rc = check_plan_call(q, weight, H1, H2)) return rc;
+	if (int rc = check_plan_call(q, weight, out)) return rc;
 	if (!models) return hibag_fail(HIBAG_HIP_EINVAL, "models is NULL");
 	const void *src = co.bed_fn ? (const void *)co.bed_fn : (const void *)co.geno;
 	for (int i = 0; i < q->n_models; i++) {
-		if (int rc = check_predict_args(models[i], src, n_samp, vote_method, H1, H2)) return rc;
+		if (int rc = check_predict_args(models[i], src, n_samp, vote_method, out.H1, out.H2)) return rc;
 		if (models[i]->view.n_cell != q->n_cell[i])
 			return hibag_fail(HIBAG_HIP_EINVAL, "model %d has %d allele pairs, the merge plan was made for %d", i, models[i]->view.n_cell, q->n_cell[i]);
 		if (models[i]->device != q->device)
@@ -240,8 +237,10 @@ static int predict_merge(hibag_hip_merge_plan *q, hibag_hip_model *const *models
 	struct Unlock { std::vector<hibag_hip_model *> &v; ~Unlock() { for (hibag_hip_model *m : v) m->lock.unlock(); } } unlock{order};
 	HIP_TRY(hipSetDevice(q->device));
 	if (!q->st) HIP_TRY(hipStreamCreateWithFlags(&q->st, hipStreamNonBlocking));
-	return predict_merge_locked(q, models, co, n_samp, snp_col, flip, vote_method, weight, use_matching, H1, H2, prob, matching,
-		dosage, postprob, false);
+	// (a model's outputs poisoned by a failed hand-over: repaired as in predict_staged_locked, for all the models at once)
+	return with_handover_repair(models, q->n_models, [&]() {
+		return predict_merge_locked(q, models, co, n_samp, snp_col, flip, vote_method, weight, use_matching, out);
+	});
 }
 
 } // namespace hibag_detail
@@ -315,7 +314,8 @@ int hibag_hip_merge_device(hibag_hip_merge_plan *q, const double *const *d_postp
 	const double *weight, int use_matching, int n_samp, int32_t *d_H1, int32_t *d_H2, double *d_prob, double *d_matching_out,
 	double *d_dosage, double *d_postprob_out, size_t ld_out, void *stream)
 {
-	if (int rc = check_plan_call(q, weight, d_H1, d_H2)) return rc;
+	const PredictOut out{d_H1, d_H2, d_prob, d_matching_out, d_dosage, d_postprob_out};
+	if (int rc = check_plan_call(q, weight, out)) return rc;
 	if (!d_postprob || !d_matching) return hibag_fail(HIBAG_HIP_EINVAL, "d_postprob / d_matching is NULL");
 	for (int i = 0; i < q->n_models; i++)
 		if (!d_postprob[i] || !d_matching[i]) return hibag_fail(HIBAG_HIP_EINVAL, "d_postprob[%d] / d_matching[%d] is NULL", i, i);
@@ -336,10 +336,7 @@ int hibag_hip_merge_device(hibag_hip_merge_plan *q, const double *const *d_postp
 			S.n_cell[i] = q->n_cell[i];
 			S.w[i] = weight[i];
 		}
-		if (int rc = merge_enqueue(q, S, false, n, d_H1 ? d_H1 + s0 : nullptr, d_H2 ? d_H2 + s0 : nullptr, d_prob ? d_prob + s0 : nullptr,
-				d_matching_out ? d_matching_out + s0 : nullptr, d_dosage ? d_dosage + s0 : nullptr,
-				d_postprob_out ? d_postprob_out + s0 : nullptr, ld_out, (hipStream_t)stream))
-			return rc;
+		if (int rc = merge_enqueue(q, S, false, n, out.advanced((size_t)s0, 1, 1), ld_out, (hipStream_t)stream)) return rc;
 	}
 	return 0;
 }
@@ -351,7 +348,7 @@ int hibag_hip_predict_merge(hibag_hip_merge_plan *q, hibag_hip_model *const *mod
 {
 	MergeCohort co;
 	co.geno = geno; co.snp_major = snp_major; co.ld = ld; co.n_geno_snp = n_geno_snp;
-	return predict_merge(q, models, co, n_samp, snp_col, flip, vote_method, weight, use_matching, H1, H2, prob, matching, dosage, postprob);
+	return predict_merge(q, models, co, n_samp, snp_col, flip, vote_method, weight, use_matching, {H1, H2, prob, matching, dosage, postprob});
 }
 
 int hibag_hip_predict_merge_bed(hibag_hip_merge_plan *q, hibag_hip_model *const *models, const char *bed_fn, int n_samp, int n_snp,
@@ -363,7 +360,7 @@ int hibag_hip_predict_merge_bed(hibag_hip_merge_plan *q, hibag_hip_model *const 
 	for (int i = 0; q && i < q->n_models; i++) if (!snp_col[i]) return hibag_fail(HIBAG_HIP_EINVAL, "snp_col[%d] is NULL", i);
 	MergeCohort co;
 	co.bed_fn = bed_fn; co.n_bed_snp = n_snp;
-	return predict_merge(q, models, co, n_samp, snp_col, flip, vote_method, weight, use_matching, H1, H2, prob, matching, dosage, postprob);
+	return predict_merge(q, models, co, n_samp, snp_col, flip, vote_method, weight, use_matching, {H1, H2, prob, matching, dosage, postprob});
 }
 
 } // extern "C"

@@ -188,69 +188,54 @@ int workspace_leave(hibag_hip_model *m, hipStream_t st)
 	return 0;
 }
 
-// Records ws_done when a device-pointer entry returns -- also on its error paths, once anything has been enqueued.
-struct WorkspaceGuard {
-	hibag_hip_model *m;
-	hipStream_t st;
-	bool enqueued = false, left = false;
-	int leave() { left = true; return workspace_leave(m, st); }
-	~WorkspaceGuard() { if (enqueued && !left && m->ws_done) { (void)hipEventRecord(m->ws_done, st); m->ws_pending = true; } }
-};
+// (structs PackSource, PredictOut, GenoSource, WorkspaceGuard: hibag_internal.h)
 
-// (struct PackSource: hibag_internal.h)
-
-int predict_device_locked(hibag_hip_model *m, const PackSource &src, int n_samp, int vote_method,
-	int32_t *d_H1, int32_t *d_H2, double *d_max_prob, double *d_matching, double *d_dosage,
-	double *d_postprob, hipStream_t st, const ListOut *list = nullptr)
+void enqueue_pack(hibag_hip_model *m, HibagBatchView &B, const PackSource &src, int s0, hipStream_t st)
 {
-	// `list` (device pointers): the top-k or the draw finish in place of the others (d_H1 .. d_postprob other than d_matching are not looked at)
+	uint8_t *codes = m->ws_codes.as<uint8_t>();
+	m->timer.begin(HIBAG_HIP_K_PACK, st);
+	if (src.d_bed)
+		hibag_launch_pack_bed(m->view, B, src.d_bed, src.mode, src.stride, src.samp0 + s0, src.d_row, src.d_flip, codes, st);
+	else if (src.ld)
+		hibag_launch_pack_rows(m->view, B, src.d_geno + s0, src.ld, src.d_col, src.d_flip, codes, st);
+	else
+		hibag_launch_pack(m->view, B, src.d_geno + (size_t)s0 * (src.d_col ? src.row_len : m->n_snp), src.row_len,
+			src.d_col, src.d_flip, codes, st);
+	m->timer.end(st);
+}
+
+// `out`: device pointers.  With out.list the top-k or the draw finish runs in place of the others (of H1 .. postprob only
+// `matching` is looked at then).
+static int predict_device_locked(hibag_hip_model *m, const PackSource &src, int n_samp, int vote_method, const PredictOut &out,
+	hipStream_t st)
+{
 	HIP_TRY(hipSetDevice(m->device));
 	if (int rc = workspace_enter(m, st)) return rc;
 	// Whatever way this call ends, work it has enqueued still uses the shared workspace: the next call on another stream
 	// must be chained behind it (an error in a later batch used to skip the record).
 	WorkspaceGuard guard{m, st};
 	const int lim = batch_limit(m);
-	const size_t P = (size_t)m->view.n_cell;
 	for (int s0 = 0; s0 < n_samp; s0 += lim) {
 		const int n = std::min(lim, n_samp - s0);
 		HibagBatchView B;
 		if (int rc = make_batch(m, n, vote_method == 2, B)) return rc;
 		guard.enqueued = true;
-		m->timer.begin(HIBAG_HIP_K_PACK, st);
-		if (src.d_bed)
-			hibag_launch_pack_bed(m->view, B, src.d_bed, src.mode, src.stride, src.samp0 + s0, src.d_row, src.d_flip,
-				m->ws_codes.as<uint8_t>(), st);
-		else if (src.ld)
-			hibag_launch_pack_rows(m->view, B, src.d_geno + s0, src.ld, src.d_col, src.d_flip, m->ws_codes.as<uint8_t>(), st);
-		else
-			hibag_launch_pack(m->view, B, src.d_geno + (size_t)s0 * (src.d_col ? src.row_len : m->n_snp), src.row_len,
-				src.d_col, src.d_flip, m->ws_codes.as<uint8_t>(), st);
-		m->timer.end(st);
+		enqueue_pack(m, B, src, s0, st);
 		run_core(m, B, vote_method, m->ws_part.as<double>(), st);
+		const PredictOut o = out.advanced((size_t)s0, (size_t)m->n_hla, (size_t)m->view.n_cell);
 		m->timer.begin(HIBAG_HIP_K_FINISH, st, true);
-		if (list && list->draws)
-			hibag_launch_finish_draw(m->view, B, B.part, list->k, list->seed, list->sample0 + s0, list->h1 + (size_t)s0 * list->k,
-				list->h2 + (size_t)s0 * list->k, list->prob + (size_t)s0 * list->k, d_matching ? d_matching + s0 : nullptr, st);
-		else if (list)
-			hibag_launch_finish_topk(m->view, B, B.part, list->k, list->h1 + (size_t)s0 * list->k, list->h2 + (size_t)s0 * list->k,
-				list->prob + (size_t)s0 * list->k, d_matching ? d_matching + s0 : nullptr, st);
-		else hibag_launch_finish(m->view, B, B.part,
-			d_H1 ? d_H1 + s0 : nullptr, d_H2 ? d_H2 + s0 : nullptr,
-			d_max_prob ? d_max_prob + s0 : nullptr, d_matching ? d_matching + s0 : nullptr,
-			d_dosage ? d_dosage + (size_t)s0 * m->n_hla : nullptr,
-			d_postprob ? d_postprob + (size_t)s0 * P : nullptr, st);
+		if (o.list.on && o.list.draws)
+			hibag_launch_finish_draw(m->view, B, B.part, o.list.k, o.list.seed, o.list.sample0, o.list.h1, o.list.h2, o.list.prob,
+				o.matching, st);
+		else if (o.list.on)
+			hibag_launch_finish_topk(m->view, B, B.part, o.list.k, o.list.h1, o.list.h2, o.list.prob, o.matching, st);
+		else hibag_launch_finish(m->view, B, B.part, o.H1, o.H2, o.max_prob, o.matching, o.dosage, o.postprob, st);
 		m->timer.end(st);
 	}
 	HIP_TRY(hipGetLastError());
 	return guard.leave();
 }
 
-// Host-pointer driver.  The cohort is cut into slices (bounded workspace, bounded genotype staging); consecutive slices
-// are pipelined over three streams of the model's -- upload of slice i+1 and download of slice i-1 beside the kernels of
-// slice i, genotype and output buffers doubled -- so that for cohorts of several slices only the first upload and the last
-// download are exposed (SURVEY.md section 8d's protocol counts both).  Genotypes come from the host int32 matrix or from a
-// BED payload already on the device.  A failed hand-over (poisoned outputs) is repaired here: the call is run again
-// with undivided work items, in this process, before anything is returned.
 int staged_streams(hibag_hip_model *m, StagedStreams **out)
 {
 	StagedStreams *ss = &m->staged;
@@ -284,138 +269,203 @@ int staged_slice(const hibag_hip_model *m, int n_samp, size_t row_len)
 	return (int)std::max<long long>(64, (slice + 63) / 64 * 64);
 }
 
-// A SNP-major host matrix (hibag_hip_predict_snp_major): geno[rows[r] * ld + s] is staged as row r of a slice's
-// [rows.size()][n] device matrix -- only the rows the model uses travel.
-struct HostRows {
-	size_t ld = 0;
-	std::vector<size_t> rows;
-	bool consecutive = false;              // rows[r] = rows[0] + r: a slice is one strided block of the caller's matrix
+// Where a slice's outputs lie in the device output buffer (and in its pinned host twin), computed once per call from the
+// slice length and the outputs asked for: the per-sample vectors (calls, probability, matching: 24 bytes per sample), then
+// the dosage and the posterior matrix -- or, for the list entries, the lists where the dosage would be, right behind the
+// vectors, so that a slice still comes down in one copy.
+struct SliceLayout {
+	PredictOut want;                       // the caller's set: which outputs are asked for, and where they go in the end
+	size_t nh = 0, P = 0, tk = 0;
+	size_t o_h1 = 0, o_h2 = 0, o_mp = 0, o_mt = 0, o_ds = 0, o_pp = 0, o_t1 = 0, o_t2 = 0, o_tp = 0;
+	size_t bytes = 0;                      // of the buffer of one slice
+
+	SliceLayout() = default;
+	SliceLayout(size_t slice, size_t n_hla, size_t n_cell, const PredictOut &out)
+		: want(out), nh(n_hla), P(n_cell), tk(out.list.on ? (size_t)out.list.k : 0)
+	{
+		o_h2 = o_h1 + slice * 4; o_mp = (o_h2 + slice * 4 + 7) / 8 * 8; o_mt = o_mp + slice * 8; o_ds = o_mt + slice * 8;
+		o_pp = o_ds + slice * nh * 8;
+		o_t1 = o_ds; o_t2 = o_t1 + slice * tk * 4; o_tp = o_t2 + slice * tk * 4;
+		bytes = ((want.list.on ? o_tp + slice * tk * 8 : o_pp + (want.postprob ? slice * P * 8 : 0)) + 255) / 256 * 256;
+	}
+	// bytes from the start of the buffer that a slice of n samples uses: of the vectors (the lists ride along), of everything asked for
+	size_t vectors(size_t n) const { return want.list.on ? o_tp + n * tk * 8 : o_ds; }
+	size_t used(size_t n) const { return want.list.on ? vectors(n) : want.postprob ? o_pp + n * P * 8 : want.dosage ? o_ds + n * nh * 8 : o_ds; }
+	// the output set of a slice in the buffer at `base`: what is asked for, null for the rest
+	PredictOut bind(char *base) const
+	{
+		PredictOut d = want;
+		if (want.H1) d.H1 = (int32_t *)(base + o_h1);
+		if (want.H2) d.H2 = (int32_t *)(base + o_h2);
+		if (want.max_prob) d.max_prob = (double *)(base + o_mp);
+		if (want.matching) d.matching = (double *)(base + o_mt);
+		if (want.dosage) d.dosage = (double *)(base + o_ds);
+		if (want.postprob) d.postprob = (double *)(base + o_pp);
+		if (want.list.on) { d.list.h1 = (int32_t *)(base + o_t1); d.list.h2 = (int32_t *)(base + o_t2); d.list.prob = (double *)(base + o_tp); }
+		return d;
+	}
+	// a host copy of a slice's buffer -> samples [s0, s0 + n) of the caller's arrays; `matrices`: the dosage and the posterior too
+	void copy_out(const char *staged, size_t s0, size_t n, bool matrices) const
+	{
+		const PredictOut s = bind(const_cast<char *>(staged)), d = want.advanced(s0, nh, P);
+		if (d.H1) { memcpy(d.H1, s.H1, n * 4); memcpy(d.H2, s.H2, n * 4); }
+		if (d.max_prob) memcpy(d.max_prob, s.max_prob, n * 8);
+		if (d.matching) memcpy(d.matching, s.matching, n * 8);
+		if (matrices && d.dosage) memcpy(d.dosage, s.dosage, n * nh * 8);
+		if (matrices && d.postprob) memcpy(d.postprob, s.postprob, n * P * 8);
+		if (d.list.on) {
+			memcpy(d.list.h1, s.list.h1, n * tk * 4); memcpy(d.list.h2, s.list.h2, n * tk * 4);
+			memcpy(d.list.prob, s.list.prob, n * tk * 8);
+		}
+	}
 };
 
-int predict_staged_locked(hibag_hip_model *m, const int32_t *geno, const PackSource *bed, int n_samp, int vote_method,
-	int32_t *H1, int32_t *H2, double *max_prob, double *matching, double *dosage, double *postprob,
-	const PackSource *map = nullptr, bool is_retry = false, const HostRows *hr = nullptr, const ListOut *list = nullptr)
+// Host-pointer driver.  The cohort is cut into slices (bounded workspace, bounded genotype staging); consecutive slices
+// are pipelined over three streams of the model's -- upload of slice i+1 and download of slice i-1 beside the kernels of
+// slice i, genotype and output buffers doubled -- so that for cohorts of several slices only the first upload and the last
+// download are exposed (SURVEY.md section 8d's protocol counts both).  Genotypes come from a host int32 matrix in either
+// memory order or from a 2-bit payload already on the device (GenoSource).  One run of it: plan(), then run() with its
+// upload / download / drain of a slice.
+struct StagedRun {
+	hibag_hip_model *m;
+	const GenoSource &src;
+	int n_samp, vote_method;
+	const PredictOut &out;                 // the caller's host arrays
+
+	StagedStreams *ss = nullptr;
+	size_t S = 0;                          // int32 genotypes per sample that travel
+	int slice = 0, first = 0, n_slice = 0, nbuf = 0;
+	bool piped = false;
+	size_t geno_bytes = 0;                 // of the genotype buffer of one slice
+	SliceLayout L;
+	bool small_staged = false;             // one slice: the vectors wait in pinned staging for the final synchronisation
+
+	void slice_of(int i, int &s0, int &n) const
+	{
+		if (i == 0) { s0 = 0; n = std::min(first, n_samp); }
+		else { s0 = first + (i - 1) * slice; n = std::min(slice, n_samp - s0); }
+	}
+	char *dev_geno(int i) const { return m->ws_geno.as<char>() + (size_t)(i % nbuf) * geno_bytes; }
+	char *dev_out(int i) const { return m->ws_out.as<char>() + (size_t)(i % nbuf) * L.bytes; }
+	char *pin_out(int i) const { return (char *)m->pin_out.p + (size_t)(i & 1) * L.bytes; }
+	int plan();
+	int upload(int i);
+	int download(int i);
+	int drain(int i);
+	int run();
+};
+
+// slice sizes and buffers
+int StagedRun::plan()
 {
-	// `list` (host arrays [n_samp][k], top-k or draws; H1 .. postprob other than `matching` are NULL then): the lists take the place of the
-	// dosage in a slice's output buffer, right behind the per-sample vectors, so that a slice still comes down in one copy
-	// `map`: geno is the cohort's own matrix (map->row_len SNPs per sample); map->d_col / d_flip sit on the device
-	// `hr` (with `map` for d_col / d_flip): the cohort's matrix is SNP-major, see HostRows
-	// A device-pointer launch still running on another stream may yet fail a hand-over: wait for it, so that its fault
-	// becomes the model's sticky status (its caller's to see) instead of being taken for this call's own and repaired away.
-	if (m->ws_pending && m->ws_done && !is_retry) HIP_TRY(hipEventSynchronize(m->ws_done));
-	if (int rc = sticky_fault(m)) return rc;
-	const size_t P = (size_t)m->view.n_cell, nh = (size_t)m->n_hla,
-		S = hr ? std::max<size_t>(hr->rows.size(), 1) : map ? (size_t)map->row_len : (size_t)m->n_snp;
-	const int slice = staged_slice(m, n_samp, bed ? 1 : S);
-	const size_t geno_bytes = ((size_t)slice * std::max<size_t>(S, 1) * sizeof(int32_t) + 255) / 256 * 256;
-	const size_t o_h1 = 0, o_h2 = o_h1 + (size_t)slice * 4, o_mp = (o_h2 + (size_t)slice * 4 + 7) / 8 * 8,
-		o_mt = o_mp + (size_t)slice * 8, o_ds = o_mt + (size_t)slice * 8, o_pp = o_ds + (size_t)slice * nh * 8,
-		tk = list ? (size_t)list->k : 0, o_t1 = o_ds, o_t2 = o_t1 + (size_t)slice * tk * 4, o_tp = o_t2 + (size_t)slice * tk * 4,
-		out_bytes = ((list ? o_tp + (size_t)slice * tk * 8 : o_pp + (postprob ? (size_t)slice * P * 8 : 0)) + 255) / 256 * 256;
+	const bool host = src.geno != nullptr;
+	S = src.snp_major() ? std::max<size_t>(src.rows.rows.size(), 1) : src.pack.row_len ? (size_t)src.pack.row_len : (size_t)m->n_snp;
+	slice = staged_slice(m, n_samp, host ? S : 1);
+	geno_bytes = ((size_t)slice * std::max<size_t>(S, 1) * sizeof(int32_t) + 255) / 256 * 256;
+	L = SliceLayout((size_t)slice, (size_t)m->n_hla, (size_t)m->view.n_cell, out);
 	// A pipelined run starts with a shorter slice: what nothing overlaps with is the staging and upload of the FIRST slice,
 	// and a third of a slice costs the kernels less (their last rounds are emptier) than the wait it saves.
-	const bool piped = n_samp > slice;
+	piped = n_samp > slice;
 	static const int first_env = getenv("HIBAG_STAGED_FIRST") ? atoi(getenv("HIBAG_STAGED_FIRST")) : 0;     // (diagnostic)
-	const int first = piped ? std::max(64, std::min(slice, (first_env > 0 ? first_env : slice / 3) / 64 * 64)) : slice;
-	const int n_slice = piped ? 1 + (n_samp - first + slice - 1) / slice : 1;
-	const int nbuf = piped ? 2 : 1;
-	if (!bed)
+	first = piped ? std::max(64, std::min(slice, (first_env > 0 ? first_env : slice / 3) / 64 * 64)) : slice;
+	n_slice = piped ? 1 + (n_samp - first + slice - 1) / slice : 1;
+	nbuf = piped ? 2 : 1;
+	if (host)
 		if (int rc = m->ws_geno.reserve(geno_bytes * nbuf)) return rc;
-	if (int rc = m->ws_out.reserve(out_bytes * nbuf)) return rc;
-	StagedStreams *ss;
+	if (int rc = m->ws_out.reserve(L.bytes * nbuf)) return rc;
 	if (int rc = staged_streams(m, &ss)) return rc;
 	if (piped) {
 		// pinned staging on the host side, so that every copy call returns at once and the host thread's own work -- filling
 		// and draining the staging buffers, ~50 GB/s -- runs beside the kernels too (transfers from / to the caller's pageable
 		// memory are as fast on this platform, but the calls block: tools/copy_probe, profiles/r03_copy_probe.txt)
-		if (!bed) if (int rc = m->pin_geno.reserve(geno_bytes * 2)) return rc;
-		if (int rc = m->pin_out.reserve(out_bytes * 2)) return rc;
-	} else if (hr && !hr->consecutive) {
-		if (int rc = m->pin_geno.reserve(geno_bytes)) return rc;          // (scattered rows are gathered on the host side)
+		if (host) if (int rc = m->pin_geno.reserve(geno_bytes * 2)) return rc;
+		if (int rc = m->pin_out.reserve(L.bytes * 2)) return rc;
+	} else {
+		if (src.snp_major() && !src.rows.consecutive)
+			if (int rc = m->pin_geno.reserve(geno_bytes)) return rc;          // (scattered rows are gathered on the host side)
+		if (int rc = m->pin_out.reserve(L.vectors((size_t)slice))) return rc;
 	}
-	auto slice_of = [&](int i, int &s0, int &n) {
-		if (i == 0) { s0 = 0; n = std::min(first, n_samp); }
-		else { s0 = first + (i - 1) * slice; n = std::min(slice, n_samp - s0); }
-	};
-	auto upload = [&](int i) -> int {
-		if (bed) return 0;
-		int s0, n; slice_of(i, s0, n);
-		const size_t bytes = (size_t)n * S * sizeof(int32_t);
-		char *dst = m->ws_geno.as<char>() + (size_t)(i % nbuf) * geno_bytes;
-		if (hr) {
-			// SNP-major source: row r of the slice's device matrix [rows][n] = n genotypes of the caller's row rows[r] from sample s0
-			const size_t nr = hr->rows.size(), w = (size_t)n * sizeof(int32_t);
-			if (nr == 0) return 0;
-			const int32_t *first = geno + hr->rows[0] * hr->ld + (size_t)s0;
-			if (!piped && hr->consecutive) {
-				// one block of the caller's matrix (the whole of it when the cohort's SNPs are the model's): no host copy
-				if (hr->ld == (size_t)n) HIP_TRY(hipMemcpyAsync(dst, first, nr * w, hipMemcpyHostToDevice, ss->run));
-				else HIP_TRY(hipMemcpy2DAsync(dst, w, first, hr->ld * sizeof(int32_t), w, nr, hipMemcpyHostToDevice, ss->run));
-				return 0;
-			}
-			char *pin = (char *)m->pin_geno.p + (piped ? (size_t)(i & 1) * geno_bytes : 0);
-			if (piped && i >= 2) HIP_TRY(hipEventSynchronize(ss->up[i & 1]));
-			for (size_t r = 0; r < nr; r++) memcpy(pin + r * w, geno + hr->rows[r] * hr->ld + (size_t)s0, w);
-			if (piped && i >= 2) HIP_TRY(hipStreamWaitEvent(ss->in, ss->ran[i & 1], 0));
-			HIP_TRY(hipMemcpyAsync(dst, pin, nr * w, hipMemcpyHostToDevice, piped ? ss->in : ss->run));
-			if (piped) HIP_TRY(hipEventRecord(ss->up[i & 1], ss->in));
+	return 0;
+}
+
+// host -> device of slice i's genotypes (nothing to do for a payload on the device)
+int StagedRun::upload(int i)
+{
+	if (!src.geno) return 0;
+	int s0, n; slice_of(i, s0, n);
+	const int32_t *geno = src.geno;
+	const size_t bytes = (size_t)n * S * sizeof(int32_t);
+	char *dst = dev_geno(i);
+	if (src.snp_major()) {
+		// SNP-major source: row r of the slice's device matrix [rows][n] = n genotypes of the caller's row rows[r] from sample s0
+		const HostRows &hr = src.rows;
+		const size_t nr = hr.rows.size(), w = (size_t)n * sizeof(int32_t);
+		if (nr == 0) return 0;
+		const int32_t *row0 = geno + hr.rows[0] * hr.ld + (size_t)s0;
+		if (!piped && hr.consecutive) {
+			// one block of the caller's matrix (the whole of it when the cohort's SNPs are the model's): no host copy
+			if (hr.ld == (size_t)n) HIP_TRY(hipMemcpyAsync(dst, row0, nr * w, hipMemcpyHostToDevice, ss->run));
+			else HIP_TRY(hipMemcpy2DAsync(dst, w, row0, hr.ld * sizeof(int32_t), w, nr, hipMemcpyHostToDevice, ss->run));
 			return 0;
 		}
-		if (!piped) {
-			HIP_TRY(hipMemcpyAsync(dst, geno + (size_t)s0 * S, bytes, hipMemcpyHostToDevice, ss->run));
-			return 0;
-		}
-		char *pin = (char *)m->pin_geno.p + (size_t)(i & 1) * geno_bytes;
-		if (i >= 2) HIP_TRY(hipEventSynchronize(ss->up[i & 1]));              // the transfer of slice i - 2 has left the staging buffer
-		memcpy(pin, geno + (size_t)s0 * S, bytes);
-		if (i >= 2) HIP_TRY(hipStreamWaitEvent(ss->in, ss->ran[i & 1], 0));   // ... and its kernels have read the device buffer
-		HIP_TRY(hipMemcpyAsync(dst, pin, bytes, hipMemcpyHostToDevice, ss->in));
-		HIP_TRY(hipEventRecord(ss->up[i & 1], ss->in));
+		char *pin = (char *)m->pin_geno.p + (piped ? (size_t)(i & 1) * geno_bytes : 0);
+		if (piped && i >= 2) HIP_TRY(hipEventSynchronize(ss->up[i & 1]));
+		for (size_t r = 0; r < nr; r++) memcpy(pin + r * w, geno + hr.rows[r] * hr.ld + (size_t)s0, w);
+		if (piped && i >= 2) HIP_TRY(hipStreamWaitEvent(ss->in, ss->ran[i & 1], 0));
+		HIP_TRY(hipMemcpyAsync(dst, pin, nr * w, hipMemcpyHostToDevice, piped ? ss->in : ss->run));
+		if (piped) HIP_TRY(hipEventRecord(ss->up[i & 1], ss->in));
 		return 0;
-	};
-	bool small_staged = false;
-	if (!piped)
-		if (int rc = m->pin_out.reserve(list ? out_bytes : o_ds)) return rc;
-	// device -> host of slice i's outputs: straight into the caller's arrays (one slice), or into the pinned staging buffer
-	auto download = [&](int i) -> int {
-		int s0, n; slice_of(i, s0, n);
-		const char *o = m->ws_out.as<char>() + (size_t)(i % nbuf) * out_bytes;
-		if (piped) {
-			HIP_TRY(hipStreamWaitEvent(ss->out, ss->ran[i & 1], 0));
-			const size_t used = list ? o_tp + (size_t)n * tk * 8 : (postprob ? o_pp + (size_t)n * P * 8 : dosage ? o_ds + (size_t)n * nh * 8 : o_ds);
-			HIP_TRY(hipMemcpyAsync((char *)m->pin_out.p + (size_t)(i & 1) * out_bytes, o, used, hipMemcpyDeviceToHost, ss->out));
-			HIP_TRY(hipEventRecord(ss->down[i & 1], ss->out));
-			return 0;
-		}
-		hipStream_t st = ss->run;
-		// One slice: the four per-sample vectors (calls, probability, matching: 24 bytes per sample, contiguous on the device)
-		// come down in ONE copy into pinned staging and are handed out behind the final synchronisation -- a copy into the
-		// caller's pageable memory holds the calling thread for ~12 us whatever its size, and there were four of them; the
-		// large ones (dosage, posterior) go straight to the caller's arrays.
-		if (H1 || max_prob || matching || list) {
-			HIP_TRY(hipMemcpyAsync(m->pin_out.p, o, list ? o_tp + (size_t)n * tk * 8 : o_ds, hipMemcpyDeviceToHost, st));     // (the lists ride along)
-			small_staged = true;
-		}
-		if (dosage) HIP_TRY(hipMemcpyAsync(dosage + (size_t)s0 * nh, o + o_ds, (size_t)n * nh * 8, hipMemcpyDeviceToHost, st));
-		if (postprob) HIP_TRY(hipMemcpyAsync(postprob + (size_t)s0 * P, o + o_pp, (size_t)n * P * 8, hipMemcpyDeviceToHost, st));
+	}
+	if (!piped) {
+		HIP_TRY(hipMemcpyAsync(dst, geno + (size_t)s0 * S, bytes, hipMemcpyHostToDevice, ss->run));
 		return 0;
-	};
-	// staging buffer -> the caller's arrays (pipelined runs)
-	auto drain = [&](int i) -> int {
-		int s0, n; slice_of(i, s0, n);
-		HIP_TRY(hipEventSynchronize(ss->down[i & 1]));
-		const char *o = (const char *)m->pin_out.p + (size_t)(i & 1) * out_bytes;
-		if (H1) { memcpy(H1 + s0, o + o_h1, (size_t)n * 4); memcpy(H2 + s0, o + o_h2, (size_t)n * 4); }
-		if (max_prob) memcpy(max_prob + s0, o + o_mp, (size_t)n * 8);
-		if (matching) memcpy(matching + s0, o + o_mt, (size_t)n * 8);
-		if (dosage) memcpy(dosage + (size_t)s0 * nh, o + o_ds, (size_t)n * nh * 8);
-		if (postprob) memcpy(postprob + (size_t)s0 * P, o + o_pp, (size_t)n * P * 8);
-		if (list) {
-			memcpy(list->h1 + (size_t)s0 * tk, o + o_t1, (size_t)n * tk * 4); memcpy(list->h2 + (size_t)s0 * tk, o + o_t2, (size_t)n * tk * 4);
-			memcpy(list->prob + (size_t)s0 * tk, o + o_tp, (size_t)n * tk * 8);
-		}
+	}
+	char *pin = (char *)m->pin_geno.p + (size_t)(i & 1) * geno_bytes;
+	if (i >= 2) HIP_TRY(hipEventSynchronize(ss->up[i & 1]));              // the transfer of slice i - 2 has left the staging buffer
+	memcpy(pin, geno + (size_t)s0 * S, bytes);
+	if (i >= 2) HIP_TRY(hipStreamWaitEvent(ss->in, ss->ran[i & 1], 0));   // ... and its kernels have read the device buffer
+	HIP_TRY(hipMemcpyAsync(dst, pin, bytes, hipMemcpyHostToDevice, ss->in));
+	HIP_TRY(hipEventRecord(ss->up[i & 1], ss->in));
+	return 0;
+}
+
+// device -> host of slice i's outputs: straight into the caller's arrays (one slice), or into the pinned staging buffer
+int StagedRun::download(int i)
+{
+	int s0, n; slice_of(i, s0, n);
+	if (piped) {
+		HIP_TRY(hipStreamWaitEvent(ss->out, ss->ran[i & 1], 0));
+		HIP_TRY(hipMemcpyAsync(pin_out(i), dev_out(i), L.used((size_t)n), hipMemcpyDeviceToHost, ss->out));
+		HIP_TRY(hipEventRecord(ss->down[i & 1], ss->out));
 		return 0;
-	};
+	}
+	hipStream_t st = ss->run;
+	// One slice: the four per-sample vectors (calls, probability, matching: 24 bytes per sample, contiguous on the device)
+	// come down in ONE copy into pinned staging and are handed out behind the final synchronisation -- a copy into the
+	// caller's pageable memory holds the calling thread for ~12 us whatever its size, and there were four of them; the
+	// large ones (dosage, posterior) go straight to the caller's arrays.
+	if (out.H1 || out.max_prob || out.matching || out.list.on) {
+		HIP_TRY(hipMemcpyAsync(m->pin_out.p, dev_out(i), L.vectors((size_t)n), hipMemcpyDeviceToHost, st));     // (the lists ride along)
+		small_staged = true;
+	}
+	const PredictOut d = L.bind(dev_out(i)), h = out.advanced((size_t)s0, L.nh, L.P);
+	if (h.dosage) HIP_TRY(hipMemcpyAsync(h.dosage, d.dosage, (size_t)n * L.nh * 8, hipMemcpyDeviceToHost, st));
+	if (h.postprob) HIP_TRY(hipMemcpyAsync(h.postprob, d.postprob, (size_t)n * L.P * 8, hipMemcpyDeviceToHost, st));
+	return 0;
+}
+
+// staging buffer -> the caller's arrays (pipelined runs)
+int StagedRun::drain(int i)
+{
+	int s0, n; slice_of(i, s0, n);
+	HIP_TRY(hipEventSynchronize(ss->down[i & 1]));
+	L.copy_out(pin_out(i), (size_t)s0, (size_t)n, true);
+	return 0;
+}
+
+int StagedRun::run()
+{
+	if (int rc = plan()) return rc;
 	static const bool trace = getenv("HIBAG_STAGED_TRACE") != nullptr;     // diagnostic: host time of each phase on stderr
 	auto now = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
 	double tr[6] = {now(), 0, 0, 0, 0, 0};
@@ -423,29 +473,17 @@ int predict_staged_locked(hibag_hip_model *m, const int32_t *geno, const PackSou
 	if (trace) { if (!piped) (void)hipStreamSynchronize(ss->run); tr[1] = now(); }
 	for (int i = 0; i < n_slice; i++) {
 		int s0, n; slice_of(i, s0, n);
-		char *o = m->ws_out.as<char>() + (size_t)(i % nbuf) * out_bytes;
-		PackSource src;
-		if (bed) {
-			src = *bed;
-			src.samp0 = bed->samp0 + s0;
-		} else {
-			if (map) src = *map;
-			src.d_geno = (const int32_t *)(m->ws_geno.as<char>() + (size_t)(i % nbuf) * geno_bytes);
-			if (hr) src.ld = (size_t)n;
+		PackSource p = src.pack;
+		if (!src.geno) p.samp0 += s0;
+		else {
+			p.d_geno = (const int32_t *)dev_geno(i);
+			if (src.snp_major()) p.ld = (size_t)n;
 			if (piped) HIP_TRY(hipStreamWaitEvent(ss->run, ss->up[i & 1], 0));
 		}
 		if (piped && i >= 2) HIP_TRY(hipStreamWaitEvent(ss->run, ss->down[i & 1], 0));    // slice i - 2 has left the device output buffer
-		ListOut d_list;
-		if (list) {       // (the slice's lists in the device output buffer; a draw is keyed with the sample's index in the caller's numbering)
-			d_list = *list;
-			d_list.h1 = (int32_t *)(o + o_t1); d_list.h2 = (int32_t *)(o + o_t2); d_list.prob = (double *)(o + o_tp);
-			d_list.sample0 = list->sample0 + s0;
-		}
-		if (int rc = predict_device_locked(m, src, n, vote_method,
-				H1 ? (int32_t *)(o + o_h1) : nullptr, H2 ? (int32_t *)(o + o_h2) : nullptr,
-				max_prob ? (double *)(o + o_mp) : nullptr, matching ? (double *)(o + o_mt) : nullptr,
-				dosage ? (double *)(o + o_ds) : nullptr, postprob ? (double *)(o + o_pp) : nullptr, ss->run, list ? &d_list : nullptr))
-			return rc;
+		PredictOut d = L.bind(dev_out(i));
+		d.list.sample0 += s0;              // (a draw is keyed with the sample's index in the caller's numbering)
+		if (int rc = predict_device_locked(m, p, n, vote_method, d, ss->run)) return rc;
 		if (piped) HIP_TRY(hipEventRecord(ss->ran[i & 1], ss->run));
 		if (trace && piped) fprintf(stderr, "[hibag staged] slice %d enqueued at %.3f ms\n", i, now() - tr[0]);
 		if (trace && !piped) { tr[2] = now(); (void)hipStreamSynchronize(ss->run); tr[3] = now(); }
@@ -463,37 +501,39 @@ int predict_staged_locked(hibag_hip_model *m, const int32_t *geno, const PackSou
 	}
 	if (trace) tr[4] = now();
 	HIP_TRY(hipStreamSynchronize(ss->run));
-	if (small_staged) {                                  // (one slice: s0 = 0, n = n_samp)
-		const char *o = (const char *)m->pin_out.p;
-		if (H1) { memcpy(H1, o + o_h1, (size_t)n_samp * 4); memcpy(H2, o + o_h2, (size_t)n_samp * 4); }
-		if (max_prob) memcpy(max_prob, o + o_mp, (size_t)n_samp * 8);
-		if (matching) memcpy(matching, o + o_mt, (size_t)n_samp * 8);
-		if (list) {
-			memcpy(list->h1, o + o_t1, (size_t)n_samp * tk * 4); memcpy(list->h2, o + o_t2, (size_t)n_samp * tk * 4);
-			memcpy(list->prob, o + o_tp, (size_t)n_samp * tk * 8);
-		}
-	}
+	if (small_staged) L.copy_out((const char *)m->pin_out.p, 0, (size_t)n_samp, false);      // (one slice: s0 = 0, n = n_samp)
 	if (trace) {
 		tr[5] = now();
 		if (!piped) fprintf(stderr, "[hibag staged] n=%d upload %.3f  enqueue %.3f  kernels %.3f  download calls %.3f  final sync %.3f ms\n", n_samp,
 			tr[1] - tr[0], tr[2] - tr[1], tr[3] - tr[2], tr[4] - tr[3], tr[5] - tr[4]);
 		else fprintf(stderr, "[hibag staged] n=%d in %d slices of %d: %.3f ms\n", n_samp, n_slice, slice, tr[5] - tr[0]);
 	}
-	if (take_fault(m)) {
-		// poisoned outputs: once more, now without hand-overs (take_fault switched them off) -- never returned to the caller
-		if (is_retry) return hibag_fail(HIBAG_HIP_EHANDOVER, "a hand-over between workgroups failed in a launch without hand-overs");
-		return predict_staged_locked(m, geno, bed, n_samp, vote_method, H1, H2, max_prob, matching, dosage, postprob, map, true, hr, list);
-	}
 	return 0;
 }
 
-// The host-pointer driver on a 2-bit payload that is already on the model's device (what the BED entries upload per call;
-// the rows of a resident cohort, hibag_cohort.hip): `src` as for hibag_launch_pack_bed, samples src.samp0 .. + n_samp.
-int predict_payload_locked(hibag_hip_model *m, const PackSource &src, int n_samp, int vote_method,
-	int32_t *H1, int32_t *H2, double *max_prob, double *matching, double *dosage, double *postprob, const ListOut *list)
+// A failed hand-over (poisoned outputs) is repaired here: the run is made again with undivided work items, in this process,
+// before anything is returned.
+int predict_staged_locked(hibag_hip_model *m, const GenoSource &src, int n_samp, int vote_method, const PredictOut &out)
 {
-	return predict_staged_locked(m, nullptr, &src, n_samp, vote_method, H1, H2, max_prob, matching, dosage, postprob, nullptr, false,
-		nullptr, list);
+	return with_handover_repair(&m, 1, [&]() { return StagedRun{m, src, n_samp, vote_method, out}.run(); });
+}
+
+int upload_snp_map(hibag_hip_model *m, const int32_t *col, const int32_t *flip, const int32_t **d_col, const int32_t **d_flip)
+{
+	const size_t S = (size_t)std::max(m->n_snp, 1);
+	std::vector<int32_t> idx;
+	try { idx.assign(2 * S, 0); } catch (...) { return hibag_fail(HIBAG_HIP_ENOMEM, "out of host memory"); }
+	for (int k = 0; k < m->n_snp; k++) {
+		const int32_t c = col ? col[k] : k;
+		idx[k] = c < 0 ? -1 : c;
+		idx[S + k] = flip ? (flip[k] != 0) : 0;
+	}
+	if (int rc = m->ws_bedidx.reserve(idx.size() * sizeof(int32_t))) return rc;
+	HIP_TRY(hipMemcpyAsync(m->ws_bedidx.p, idx.data(), idx.size() * sizeof(int32_t), hipMemcpyHostToDevice, 0));
+	HIP_TRY(hipStreamSynchronize(0));            // `idx` (and whatever the caller queued before it) is pageable host memory about to go out of scope
+	*d_col = m->ws_bedidx.as<int32_t>();
+	*d_flip = m->ws_bedidx.as<int32_t>() + S;
+	return 0;
 }
 
 // ---------------------------------------------------------------------------
@@ -592,13 +632,11 @@ int oob_hap_table(hibag_hip_model *m)
 }
 
 // The whole call on the device: genotypes and bootstrap counts up once, batches of at most batch_limit samples (pack,
-// one-classifier weights, pass 1 with its record log, the picks), the [C][n_samp] results down once.  A failed hand-over
-// is repaired as in predict_staged_locked: once more without hand-overs, before anything is returned.
-int predict_oob_locked(hibag_hip_model *m, const int32_t *geno, int n_samp, const int32_t *samp_num,
-	int32_t *H1, int32_t *H2, double *prob, bool is_retry = false)
+// one-classifier weights, pass 1 with its record log, the picks), the [C][n_samp] results down once.  The entry runs it
+// under with_handover_repair, like predict_staged_locked.
+static int predict_oob_locked(hibag_hip_model *m, const int32_t *geno, int n_samp, const int32_t *samp_num,
+	int32_t *H1, int32_t *H2, double *prob)
 {
-	if (m->ws_pending && m->ws_done && !is_retry) HIP_TRY(hipEventSynchronize(m->ws_done));
-	if (int rc = sticky_fault(m)) return rc;
 	if (int rc = oob_hap_table(m)) return rc;
 	StagedStreams *ss;
 	if (int rc = staged_streams(m, &ss)) return rc;
@@ -643,10 +681,6 @@ int predict_oob_locked(hibag_hip_model *m, const int32_t *geno, int n_samp, cons
 	HIP_TRY(hipMemcpyAsync(prob, o + o_prob, C * n * 8, hipMemcpyDeviceToHost, st));
 	if (int rc = guard.leave()) return rc;
 	HIP_TRY(hipStreamSynchronize(st));
-	if (take_fault(m)) {
-		if (is_retry) return hibag_fail(HIBAG_HIP_EHANDOVER, "a hand-over between workgroups failed in a launch without hand-overs");
-		return predict_oob_locked(m, geno, n_samp, samp_num, H1, H2, prob, true);
-	}
 	return 0;
 }
 
@@ -674,12 +708,10 @@ int mask_user_index(hibag_hip_model *m)
 
 // The whole call on the device, in the manner of predict_oob_locked (training cohorts are small): genotypes and mask up
 // once, batches of at most batch_limit samples (pack, the sub-models' weights, passes 1 and 2 or the vote, finish), the
-// outputs down once.  A failed hand-over is repaired as there: once more without hand-overs, before anything is returned.
-int predict_masked_locked(hibag_hip_model *m, const int32_t *geno, int n_samp, const uint8_t *use, int vote_method,
-	int32_t *H1, int32_t *H2, double *max_prob, double *matching, double *dosage, double *postprob, bool is_retry = false)
+// outputs down once.  The entry runs it under with_handover_repair, as there.
+static int predict_masked_locked(hibag_hip_model *m, const int32_t *geno, int n_samp, const uint8_t *use, int vote_method,
+	const PredictOut &out)
 {
-	if (m->ws_pending && m->ws_done && !is_retry) HIP_TRY(hipEventSynchronize(m->ws_done));
-	if (int rc = sticky_fault(m)) return rc;
 	if (int rc = mask_user_index(m)) return rc;
 	StagedStreams *ss;
 	if (int rc = staged_streams(m, &ss)) return rc;
@@ -687,7 +719,7 @@ int predict_masked_locked(hibag_hip_model *m, const int32_t *geno, int n_samp, c
 	const size_t C = (size_t)m->view.n_classifier, n = (size_t)n_samp, S = (size_t)m->n_snp, P = (size_t)m->view.n_cell,
 		nh = (size_t)m->n_hla;
 	const size_t o_h1 = 0, o_h2 = o_h1 + n * 4, o_mp = (o_h2 + n * 4 + 7) / 8 * 8, o_mt = o_mp + n * 8, o_ds = o_mt + n * 8,
-		o_pp = o_ds + (dosage ? n * nh * 8 : 0), out_bytes = o_pp + (postprob ? n * P * 8 : 0);
+		o_pp = o_ds + (out.dosage ? n * nh * 8 : 0), out_bytes = o_pp + (out.postprob ? n * P * 8 : 0);
 	int lim = batch_limit(m);
 	if (const char *e = getenv("HIBAG_MASK_BATCH")) lim = std::min(lim, std::max(64, atoi(e)) / 64 * 64);     // (diagnostic: smaller batches)
 	const size_t pad_max = (size_t)round_up(std::min(lim, n_samp), HIBAG_WAVE);
@@ -696,6 +728,12 @@ int predict_masked_locked(hibag_hip_model *m, const int32_t *geno, int n_samp, c
 	if (int rc = m->mask_use.reserve(std::max<size_t>(C * n, 1))) return rc;
 	if (int rc = m->mask_cnt.reserve(std::max<size_t>(S, 1) * pad_max * sizeof(int32_t))) return rc;
 	char *o = m->ws_out.as<char>();
+	PredictOut d;                              // the outputs asked for, on the device
+	if (out.H1) { d.H1 = (int32_t *)(o + o_h1); d.H2 = (int32_t *)(o + o_h2); }
+	if (out.max_prob) d.max_prob = (double *)(o + o_mp);
+	if (out.matching) d.matching = (double *)(o + o_mt);
+	if (out.dosage) d.dosage = (double *)(o + o_ds);
+	if (out.postprob) d.postprob = (double *)(o + o_pp);
 	const int32_t *d_geno = m->ws_geno.as<int32_t>();
 	if (int rc = workspace_enter(m, st)) return rc;
 	WorkspaceGuard guard{m, st};
@@ -716,29 +754,22 @@ int predict_masked_locked(hibag_hip_model *m, const int32_t *geno, int n_samp, c
 		m->timer.end(st);
 		run_core(m, B, vote_method, m->ws_part.as<double>(), st);
 		m->timer.begin(HIBAG_HIP_K_FINISH, st, true);
-		hibag_launch_finish(m->view, B, B.part,
-			H1 ? (int32_t *)(o + o_h1) + s0 : nullptr, H2 ? (int32_t *)(o + o_h2) + s0 : nullptr,
-			max_prob ? (double *)(o + o_mp) + s0 : nullptr, matching ? (double *)(o + o_mt) + s0 : nullptr,
-			dosage ? (double *)(o + o_ds) + (size_t)s0 * nh : nullptr,
-			postprob ? (double *)(o + o_pp) + (size_t)s0 * P : nullptr, st);
+		const PredictOut b = d.advanced((size_t)s0, nh, P);
+		hibag_launch_finish(m->view, B, B.part, b.H1, b.H2, b.max_prob, b.matching, b.dosage, b.postprob, st);
 		m->timer.end(st);
 		debug_stage("masked batch", st);
 	}
 	HIP_TRY(hipGetLastError());
-	if (H1) {
-		HIP_TRY(hipMemcpyAsync(H1, o + o_h1, n * 4, hipMemcpyDeviceToHost, st));
-		HIP_TRY(hipMemcpyAsync(H2, o + o_h2, n * 4, hipMemcpyDeviceToHost, st));
+	if (out.H1) {
+		HIP_TRY(hipMemcpyAsync(out.H1, d.H1, n * 4, hipMemcpyDeviceToHost, st));
+		HIP_TRY(hipMemcpyAsync(out.H2, d.H2, n * 4, hipMemcpyDeviceToHost, st));
 	}
-	if (max_prob) HIP_TRY(hipMemcpyAsync(max_prob, o + o_mp, n * 8, hipMemcpyDeviceToHost, st));
-	if (matching) HIP_TRY(hipMemcpyAsync(matching, o + o_mt, n * 8, hipMemcpyDeviceToHost, st));
-	if (dosage) HIP_TRY(hipMemcpyAsync(dosage, o + o_ds, n * nh * 8, hipMemcpyDeviceToHost, st));
-	if (postprob) HIP_TRY(hipMemcpyAsync(postprob, o + o_pp, n * P * 8, hipMemcpyDeviceToHost, st));
+	if (out.max_prob) HIP_TRY(hipMemcpyAsync(out.max_prob, d.max_prob, n * 8, hipMemcpyDeviceToHost, st));
+	if (out.matching) HIP_TRY(hipMemcpyAsync(out.matching, d.matching, n * 8, hipMemcpyDeviceToHost, st));
+	if (out.dosage) HIP_TRY(hipMemcpyAsync(out.dosage, d.dosage, n * nh * 8, hipMemcpyDeviceToHost, st));
+	if (out.postprob) HIP_TRY(hipMemcpyAsync(out.postprob, d.postprob, n * P * 8, hipMemcpyDeviceToHost, st));
 	if (int rc = guard.leave()) return rc;
 	HIP_TRY(hipStreamSynchronize(st));
-	if (take_fault(m)) {
-		if (is_retry) return hibag_fail(HIBAG_HIP_EHANDOVER, "a hand-over between workgroups failed in a launch without hand-overs");
-		return predict_masked_locked(m, geno, n_samp, use, vote_method, H1, H2, max_prob, matching, dosage, postprob, true);
-	}
 	return 0;
 }
 
@@ -749,27 +780,43 @@ int predict_masked_locked(hibag_hip_model *m, const int32_t *geno, int n_samp, c
 
 extern "C" {
 
+// (the bodies of the device-pointer and host-pointer entries of each route: the plain, the top-k and the draw entries are
+// the same calls with their own output set)
+static int predict_device_entry(hibag_hip_model *m, const PackSource &src, int n_samp, int vote_method, const PredictOut &out,
+	void *stream)
+{
+	if (int rc = check_predict_args(m, src.d_geno, n_samp, vote_method, out.H1, out.H2)) return rc;
+	if (out.list.on) if (int rc = check_list_args(n_samp, out.list)) return rc;
+	std::lock_guard<std::mutex> g(m->lock);
+	if (int rc = sticky_fault(m)) return rc;
+	return predict_device_locked(m, src, n_samp, vote_method, out, (hipStream_t)stream);
+}
+
+static int predict_entry(hibag_hip_model *m, const int32_t *geno, int n_samp, int vote_method, const PredictOut &out)
+{
+	if (int rc = check_predict_args(m, geno, n_samp, vote_method, out.H1, out.H2)) return rc;
+	if (out.list.on) if (int rc = check_list_args(n_samp, out.list)) return rc;
+	if (n_samp == 0) return 0;
+	std::lock_guard<std::mutex> g(m->lock);
+	HIP_TRY(hipSetDevice(m->device));
+	GenoSource src;
+	src.geno = geno;
+	return predict_staged_locked(m, src, n_samp, vote_method, out);
+}
+
 int hibag_hip_predict_device(hibag_hip_model *m, const int32_t *d_geno, int n_samp, int vote_method,
 	int32_t *d_H1, int32_t *d_H2, double *d_max_prob, double *d_matching, double *d_dosage,
 	double *d_postprob, void *stream)
 {
-	if (int rc = check_predict_args(m, d_geno, n_samp, vote_method, d_H1, d_H2)) return rc;
-	std::lock_guard<std::mutex> g(m->lock);
-	if (int rc = sticky_fault(m)) return rc;
 	PackSource src;
 	src.d_geno = d_geno;
-	return predict_device_locked(m, src, n_samp, vote_method, d_H1, d_H2, d_max_prob, d_matching,
-		d_dosage, d_postprob, (hipStream_t)stream);
+	return predict_device_entry(m, src, n_samp, vote_method, {d_H1, d_H2, d_max_prob, d_matching, d_dosage, d_postprob}, stream);
 }
 
 int hibag_hip_predict(hibag_hip_model *m, const int32_t *geno, int n_samp, int vote_method,
 	int32_t *H1, int32_t *H2, double *max_prob, double *matching, double *dosage, double *postprob)
 {
-	if (int rc = check_predict_args(m, geno, n_samp, vote_method, H1, H2)) return rc;
-	if (n_samp == 0) return 0;
-	std::lock_guard<std::mutex> g(m->lock);
-	HIP_TRY(hipSetDevice(m->device));
-	return predict_staged_locked(m, geno, nullptr, n_samp, vote_method, H1, H2, max_prob, matching, dosage, postprob);
+	return predict_entry(m, geno, n_samp, vote_method, {H1, H2, max_prob, matching, dosage, postprob});
 }
 
 int hibag_hip_predict_oob(hibag_hip_model *m, const int32_t *geno, int n_samp, const int32_t *samp_num,
@@ -786,7 +833,7 @@ int hibag_hip_predict_oob(hibag_hip_model *m, const int32_t *geno, int n_samp, c
 	if (n_samp == 0 || m->view.n_classifier == 0) return 0;
 	std::lock_guard<std::mutex> g(m->lock);
 	HIP_TRY(hipSetDevice(m->device));
-	return predict_oob_locked(m, geno, n_samp, samp_num, H1, H2, prob);
+	return with_handover_repair(&m, 1, [&]() { return predict_oob_locked(m, geno, n_samp, samp_num, H1, H2, prob); });
 }
 
 int hibag_hip_predict_masked(hibag_hip_model *m, const int32_t *geno, int n_samp, const uint8_t *use, int vote_method,
@@ -797,7 +844,8 @@ int hibag_hip_predict_masked(hibag_hip_model *m, const int32_t *geno, int n_samp
 	if (n_samp == 0) return 0;
 	std::lock_guard<std::mutex> g(m->lock);
 	HIP_TRY(hipSetDevice(m->device));
-	return predict_masked_locked(m, geno, n_samp, use, vote_method, H1, H2, max_prob, matching, dosage, postprob);
+	const PredictOut out{H1, H2, max_prob, matching, dosage, postprob};
+	return with_handover_repair(&m, 1, [&]() { return predict_masked_locked(m, geno, n_samp, use, vote_method, out); });
 }
 
 // samples per batch of the device-pointer entries that take ONE batch (hibag_hip_predict_partial_device); 0 = not finalized
@@ -825,6 +873,7 @@ int hibag_hip_predict_multi(hibag_hip_model *const *models, int n_models, const 
 	}
 	if (n_samp == 0) return 0;
 	const size_t S = (size_t)models[0]->n_snp, nh = (size_t)models[0]->n_hla, P = nh * (nh + 1) / 2;
+	const PredictOut out{H1, H2, max_prob, matching, dosage, postprob};
 	// One host thread per replica: each drives its own device through the ordinary host-pointer entry on its slice of the
 	// cohort and writes its slice of every output in place -- samples are independent (src/LibHLA.cpp:2362-2411), nothing is
 	// merged.  The first non-empty slice runs on the calling thread.  No C++ exception leaves this function (thread
@@ -836,10 +885,7 @@ int hibag_hip_predict_multi(hibag_hip_model *const *models, int n_models, const 
 		std::vector<int> rc(n_models, 0);
 		std::vector<std::string> msg(n_models);
 		auto run = [&](int i, int first, int count) {
-			rc[i] = hibag_hip_predict(models[i], geno + (size_t)first * S, count, vote_method,
-				H1 ? H1 + first : nullptr, H2 ? H2 + first : nullptr, max_prob ? max_prob + first : nullptr,
-				matching ? matching + first : nullptr, dosage ? dosage + (size_t)first * nh : nullptr,
-				postprob ? postprob + (size_t)first * P : nullptr);
+			rc[i] = predict_entry(models[i], geno + (size_t)first * S, count, vote_method, out.advanced((size_t)first, nh, P));
 			if (rc[i]) { try { msg[i] = hibag_hip_last_error(); } catch (...) {} }
 		};
 		int mine = -1, mine_first = 0, mine_count = 0;
@@ -864,13 +910,11 @@ int hibag_hip_predict_multi(hibag_hip_model *const *models, int n_models, const 
 	return 0;
 }
 
-// (the bodies of the _mapped, _snp_major and _bed entries: the top-k and the draw entries are the same calls with `list` set)
 static int predict_mapped_entry(hibag_hip_model *m, const int32_t *geno, int n_samp, int n_geno_snp,
-	const int32_t *snp_col, const int32_t *flip, int vote_method,
-	int32_t *H1, int32_t *H2, double *max_prob, double *matching, double *dosage, double *postprob, const ListOut *list)
+	const int32_t *snp_col, const int32_t *flip, int vote_method, const PredictOut &out)
 {
-	if (int rc = check_predict_args(m, geno, n_samp, vote_method, H1, H2)) return rc;
-	if (list) if (int rc = check_list_args(n_samp, *list)) return rc;
+	if (int rc = check_predict_args(m, geno, n_samp, vote_method, out.H1, out.H2)) return rc;
+	if (out.list.on) if (int rc = check_list_args(n_samp, out.list)) return rc;
 	if (n_geno_snp <= 0) return hibag_fail(HIBAG_HIP_EINVAL, "n_geno_snp must be positive");
 	if (!snp_col && m->n_snp > 0) return hibag_fail(HIBAG_HIP_EINVAL, "snp_col is NULL");
 	for (int k = 0; k < m->n_snp; k++)
@@ -878,27 +922,18 @@ static int predict_mapped_entry(hibag_hip_model *m, const int32_t *geno, int n_s
 	if (n_samp == 0) return 0;
 	std::lock_guard<std::mutex> g(m->lock);
 	HIP_TRY(hipSetDevice(m->device));
-	const size_t S = (size_t)std::max(m->n_snp, 1);
-	std::vector<int32_t> idx(2 * S, 0);
-	for (int k = 0; k < m->n_snp; k++) {
-		idx[k] = snp_col[k] < 0 ? -1 : snp_col[k];
-		idx[S + k] = flip ? (flip[k] != 0) : 0;
-	}
-	if (int rc = m->ws_bedidx.reserve(idx.size() * sizeof(int32_t))) return rc;
-	HIP_TRY(hipMemcpyAsync(m->ws_bedidx.p, idx.data(), idx.size() * sizeof(int32_t), hipMemcpyHostToDevice, 0));
-	HIP_TRY(hipStreamSynchronize(0));            // `idx` is pageable host memory about to go out of scope
-	PackSource map;
-	map.row_len = n_geno_snp;
-	map.d_col = m->ws_bedidx.as<int32_t>();
-	map.d_flip = m->ws_bedidx.as<int32_t>() + S;
-	return predict_staged_locked(m, geno, nullptr, n_samp, vote_method, H1, H2, max_prob, matching, dosage, postprob, &map, false, nullptr, list);
+	GenoSource src;
+	src.geno = geno;
+	src.pack.row_len = n_geno_snp;
+	if (int rc = upload_snp_map(m, snp_col, flip, &src.pack.d_col, &src.pack.d_flip)) return rc;
+	return predict_staged_locked(m, src, n_samp, vote_method, out);
 }
 
 int hibag_hip_predict_mapped(hibag_hip_model *m, const int32_t *geno, int n_samp, int n_geno_snp,
 	const int32_t *snp_col, const int32_t *flip, int vote_method,
 	int32_t *H1, int32_t *H2, double *max_prob, double *matching, double *dosage, double *postprob)
 {
-	return predict_mapped_entry(m, geno, n_samp, n_geno_snp, snp_col, flip, vote_method, H1, H2, max_prob, matching, dosage, postprob, nullptr);
+	return predict_mapped_entry(m, geno, n_samp, n_geno_snp, snp_col, flip, vote_method, {H1, H2, max_prob, matching, dosage, postprob});
 }
 
 int hibag_hip_predict_mapped_device(hibag_hip_model *m, const int32_t *d_geno, int n_samp, int n_geno_snp,
@@ -912,17 +947,16 @@ int hibag_hip_predict_mapped_device(hibag_hip_model *m, const int32_t *d_geno, i
 	if (int rc = sticky_fault(m)) return rc;
 	PackSource src;
 	src.d_geno = d_geno; src.row_len = n_geno_snp; src.d_col = d_snp_col; src.d_flip = d_flip;
-	return predict_device_locked(m, src, n_samp, vote_method, d_H1, d_H2, d_max_prob, d_matching,
-		d_dosage, d_postprob, (hipStream_t)stream);
+	return predict_device_locked(m, src, n_samp, vote_method, {d_H1, d_H2, d_max_prob, d_matching, d_dosage, d_postprob},
+		(hipStream_t)stream);
 }
 
 // The cohort's matrix SNP-major: geno[row][sample] with `ld` elements between rows.  Only the model's rows are uploaded.
 static int predict_snp_major_entry(hibag_hip_model *m, const int32_t *geno, size_t ld, int n_samp, int n_geno_snp,
-	const int32_t *snp_col, const int32_t *flip, int vote_method,
-	int32_t *H1, int32_t *H2, double *max_prob, double *matching, double *dosage, double *postprob, const ListOut *list)
+	const int32_t *snp_col, const int32_t *flip, int vote_method, const PredictOut &out)
 {
-	if (int rc = check_predict_args(m, geno, n_samp, vote_method, H1, H2)) return rc;
-	if (list) if (int rc = check_list_args(n_samp, *list)) return rc;
+	if (int rc = check_predict_args(m, geno, n_samp, vote_method, out.H1, out.H2)) return rc;
+	if (out.list.on) if (int rc = check_list_args(n_samp, out.list)) return rc;
 	if (n_geno_snp <= 0) return hibag_fail(HIBAG_HIP_EINVAL, "n_geno_snp must be positive");
 	if (ld < (size_t)n_samp) return hibag_fail(HIBAG_HIP_EINVAL, "ld = %zu is smaller than n_samp = %d", ld, n_samp);
 	if (!snp_col && m->n_snp > n_geno_snp)
@@ -932,36 +966,33 @@ static int predict_snp_major_entry(hibag_hip_model *m, const int32_t *geno, size
 	if (n_samp == 0) return 0;
 	std::lock_guard<std::mutex> g(m->lock);
 	HIP_TRY(hipSetDevice(m->device));
-	const size_t S = (size_t)std::max(m->n_snp, 1);
-	HostRows hr;
-	std::vector<int32_t> idx;
+	GenoSource src;
+	src.geno = geno;
+	HostRows &hr = src.rows;
+	std::vector<int32_t> col;
 	try {
-		idx.assign(2 * S, 0);
+		col.assign((size_t)std::max(m->n_snp, 1), -1);
 		hr.ld = ld;
-		hr.rows.reserve(S);
+		hr.rows.reserve(col.size());
 		for (int k = 0; k < m->n_snp; k++) {
 			const int c = snp_col ? snp_col[k] : k;
-			idx[k] = c < 0 ? -1 : (int32_t)hr.rows.size();           // (the staged matrix holds the model's rows only, in model order)
-			if (c >= 0) hr.rows.push_back((size_t)c);
-			idx[S + k] = flip ? (flip[k] != 0) : 0;
+			if (c < 0) continue;
+			col[k] = (int32_t)hr.rows.size();                         // (the staged matrix holds the model's rows only, in model order)
+			hr.rows.push_back((size_t)c);
 		}
 	} catch (...) { return hibag_fail(HIBAG_HIP_ENOMEM, "out of host memory"); }
 	hr.consecutive = true;
 	for (size_t r = 1; r < hr.rows.size(); r++) if (hr.rows[r] != hr.rows[0] + r) { hr.consecutive = false; break; }
-	if (int rc = m->ws_bedidx.reserve(idx.size() * sizeof(int32_t))) return rc;
-	HIP_TRY(hipMemcpyAsync(m->ws_bedidx.p, idx.data(), idx.size() * sizeof(int32_t), hipMemcpyHostToDevice, 0));
-	HIP_TRY(hipStreamSynchronize(0));            // `idx` is pageable host memory about to go out of scope
-	PackSource map;
-	map.d_col = m->ws_bedidx.as<int32_t>();
-	map.d_flip = flip ? m->ws_bedidx.as<int32_t>() + S : nullptr;
-	return predict_staged_locked(m, geno, nullptr, n_samp, vote_method, H1, H2, max_prob, matching, dosage, postprob, &map, false, &hr, list);
+	if (int rc = upload_snp_map(m, col.data(), flip, &src.pack.d_col, &src.pack.d_flip)) return rc;
+	if (!flip) src.pack.d_flip = nullptr;
+	return predict_staged_locked(m, src, n_samp, vote_method, out);
 }
 
 int hibag_hip_predict_snp_major(hibag_hip_model *m, const int32_t *geno, size_t ld, int n_samp, int n_geno_snp,
 	const int32_t *snp_col, const int32_t *flip, int vote_method,
 	int32_t *H1, int32_t *H2, double *max_prob, double *matching, double *dosage, double *postprob)
 {
-	return predict_snp_major_entry(m, geno, ld, n_samp, n_geno_snp, snp_col, flip, vote_method, H1, H2, max_prob, matching, dosage, postprob, nullptr);
+	return predict_snp_major_entry(m, geno, ld, n_samp, n_geno_snp, snp_col, flip, vote_method, {H1, H2, max_prob, matching, dosage, postprob});
 }
 
 int hibag_hip_predict_snp_major_device(hibag_hip_model *m, const int32_t *d_geno, size_t ld, int n_samp, int n_geno_snp,
@@ -976,8 +1007,8 @@ int hibag_hip_predict_snp_major_device(hibag_hip_model *m, const int32_t *d_geno
 	if (int rc = sticky_fault(m)) return rc;
 	PackSource src;
 	src.d_geno = d_geno; src.ld = std::max<size_t>(ld, 1); src.d_col = d_snp_col; src.d_flip = d_flip;
-	return predict_device_locked(m, src, n_samp, vote_method, d_H1, d_H2, d_max_prob, d_matching,
-		d_dosage, d_postprob, (hipStream_t)stream);
+	return predict_device_locked(m, src, n_samp, vote_method, {d_H1, d_H2, d_max_prob, d_matching, d_dosage, d_postprob},
+		(hipStream_t)stream);
 }
 
 // ---- PLINK BED ------------------------------------------------------------
@@ -1024,42 +1055,32 @@ int hibag_hip_conv_bed(const char *bed_fn, int n_samp, int n_snp, int n_save_snp
 }
 
 static int predict_bed_entry(hibag_hip_model *m, const char *bed_fn, int n_samp, int n_snp,
-	const int32_t *snp_col, const int32_t *flip, int vote_method,
-	int32_t *H1, int32_t *H2, double *max_prob, double *matching, double *dosage, double *postprob, const ListOut *list)
+	const int32_t *snp_col, const int32_t *flip, int vote_method, const PredictOut &out)
 {
-	if (int rc = check_predict_args(m, bed_fn, n_samp, vote_method, H1, H2)) return rc;
-	if (list) if (int rc = check_list_args(n_samp, *list)) return rc;
+	if (int rc = check_predict_args(m, bed_fn, n_samp, vote_method, out.H1, out.H2)) return rc;
+	if (out.list.on) if (int rc = check_list_args(n_samp, out.list)) return rc;
 	if (!snp_col && m->n_snp > 0) return hibag_fail(HIBAG_HIP_EINVAL, "snp_col is NULL");
 	BedImage img;
 	if (int rc = load_bed(bed_fn, n_samp, n_snp, snp_col, m->n_snp, img)) return rc;
 	if (n_samp == 0) return 0;
 	std::lock_guard<std::mutex> g(m->lock);
 	HIP_TRY(hipSetDevice(m->device));
-	const size_t S = (size_t)std::max(m->n_snp, 1);
-	std::vector<int32_t> idx(2 * S, 0);
-	for (int k = 0; k < m->n_snp; k++) {
-		idx[k] = img.index[k];
-		idx[S + k] = flip ? (flip[k] != 0) : 0;
-	}
 	if (int rc = m->ws_bed.reserve(std::max<size_t>(img.rows.size(), 1))) return rc;
-	if (int rc = m->ws_bedidx.reserve(idx.size() * sizeof(int32_t))) return rc;
 	HIP_TRY(hipMemcpyAsync(m->ws_bed.p, img.rows.data(), img.rows.size(), hipMemcpyHostToDevice, 0));
-	HIP_TRY(hipMemcpyAsync(m->ws_bedidx.p, idx.data(), idx.size() * sizeof(int32_t), hipMemcpyHostToDevice, 0));
-	HIP_TRY(hipStreamSynchronize(0));            // `img` and `idx` are pageable host memory about to go out of scope
-	PackSource src;
-	src.d_bed = m->ws_bed.as<uint8_t>();
-	src.mode = img.mode;
-	src.stride = img.stride;
-	src.d_row = m->ws_bedidx.as<int32_t>();
-	src.d_flip = m->ws_bedidx.as<int32_t>() + S;
-	return predict_staged_locked(m, nullptr, &src, n_samp, vote_method, H1, H2, max_prob, matching, dosage, postprob, nullptr, false, nullptr, list);
+	GenoSource src;                              // (a payload on the device)
+	src.pack.d_bed = m->ws_bed.as<uint8_t>();
+	src.pack.mode = img.mode;
+	src.pack.stride = img.stride;
+	// (waits for the null stream: `img` too is pageable host memory about to go out of scope)
+	if (int rc = upload_snp_map(m, img.index.data(), flip, &src.pack.d_row, &src.pack.d_flip)) return rc;
+	return predict_staged_locked(m, src, n_samp, vote_method, out);
 }
 
 int hibag_hip_predict_bed(hibag_hip_model *m, const char *bed_fn, int n_samp, int n_snp,
 	const int32_t *snp_col, const int32_t *flip, int vote_method,
 	int32_t *H1, int32_t *H2, double *max_prob, double *matching, double *dosage, double *postprob)
 {
-	return predict_bed_entry(m, bed_fn, n_samp, n_snp, snp_col, flip, vote_method, H1, H2, max_prob, matching, dosage, postprob, nullptr);
+	return predict_bed_entry(m, bed_fn, n_samp, n_snp, snp_col, flip, vote_method, {H1, H2, max_prob, matching, dosage, postprob});
 }
 
 // ---- the k best pairs of every sample (include/hibag_hip.h "top-k") ---------------------------------------
@@ -1069,55 +1090,36 @@ int hibag_hip_predict_bed(hibag_hip_model *m, const char *bed_fn, int n_samp, in
 int hibag_hip_predict_topk(hibag_hip_model *m, const int32_t *geno, int n_samp, int vote_method, int k,
 	int32_t *h1, int32_t *h2, double *prob, double *matching)
 {
-	if (int rc = check_predict_args(m, geno, n_samp, vote_method, nullptr, nullptr)) return rc;
-	const ListOut topk{k, h1, h2, prob};
-	if (int rc = check_list_args(n_samp, topk)) return rc;
-	if (n_samp == 0) return 0;
-	std::lock_guard<std::mutex> g(m->lock);
-	HIP_TRY(hipSetDevice(m->device));
-	return predict_staged_locked(m, geno, nullptr, n_samp, vote_method, nullptr, nullptr, nullptr, matching, nullptr, nullptr,
-		nullptr, false, nullptr, &topk);
+	return predict_entry(m, geno, n_samp, vote_method, PredictOut::topk(k, h1, h2, prob, matching));
 }
 
 int hibag_hip_predict_topk_device(hibag_hip_model *m, const int32_t *d_geno, int n_samp, int vote_method, int k,
 	int32_t *d_h1, int32_t *d_h2, double *d_prob, double *d_matching, void *stream)
 {
-	if (int rc = check_predict_args(m, d_geno, n_samp, vote_method, nullptr, nullptr)) return rc;
-	const ListOut topk{k, d_h1, d_h2, d_prob};
-	if (int rc = check_list_args(n_samp, topk)) return rc;
-	std::lock_guard<std::mutex> g(m->lock);
-	if (int rc = sticky_fault(m)) return rc;
 	PackSource src;
 	src.d_geno = d_geno;
-	return predict_device_locked(m, src, n_samp, vote_method, nullptr, nullptr, nullptr, d_matching, nullptr, nullptr,
-		(hipStream_t)stream, &topk);
+	return predict_device_entry(m, src, n_samp, vote_method, PredictOut::topk(k, d_h1, d_h2, d_prob, d_matching), stream);
 }
 
 int hibag_hip_predict_topk_mapped(hibag_hip_model *m, const int32_t *geno, int n_samp, int n_geno_snp,
 	const int32_t *snp_col, const int32_t *flip, int vote_method, int k,
 	int32_t *h1, int32_t *h2, double *prob, double *matching)
 {
-	const ListOut topk{k, h1, h2, prob};
-	return predict_mapped_entry(m, geno, n_samp, n_geno_snp, snp_col, flip, vote_method, nullptr, nullptr, nullptr, matching,
-		nullptr, nullptr, &topk);
+	return predict_mapped_entry(m, geno, n_samp, n_geno_snp, snp_col, flip, vote_method, PredictOut::topk(k, h1, h2, prob, matching));
 }
 
 int hibag_hip_predict_topk_snp_major(hibag_hip_model *m, const int32_t *geno, size_t ld, int n_samp, int n_geno_snp,
 	const int32_t *snp_col, const int32_t *flip, int vote_method, int k,
 	int32_t *h1, int32_t *h2, double *prob, double *matching)
 {
-	const ListOut topk{k, h1, h2, prob};
-	return predict_snp_major_entry(m, geno, ld, n_samp, n_geno_snp, snp_col, flip, vote_method, nullptr, nullptr, nullptr, matching,
-		nullptr, nullptr, &topk);
+	return predict_snp_major_entry(m, geno, ld, n_samp, n_geno_snp, snp_col, flip, vote_method, PredictOut::topk(k, h1, h2, prob, matching));
 }
 
 int hibag_hip_predict_topk_bed(hibag_hip_model *m, const char *bed_fn, int n_samp, int n_snp,
 	const int32_t *snp_col, const int32_t *flip, int vote_method, int k,
 	int32_t *h1, int32_t *h2, double *prob, double *matching)
 {
-	const ListOut topk{k, h1, h2, prob};
-	return predict_bed_entry(m, bed_fn, n_samp, n_snp, snp_col, flip, vote_method, nullptr, nullptr, nullptr, matching,
-		nullptr, nullptr, &topk);
+	return predict_bed_entry(m, bed_fn, n_samp, n_snp, snp_col, flip, vote_method, PredictOut::topk(k, h1, h2, prob, matching));
 }
 
 // ---- pairs drawn from every sample's posterior (include/hibag_hip.h "posterior draws") --------------------------
@@ -1127,55 +1129,39 @@ int hibag_hip_predict_topk_bed(hibag_hip_model *m, const char *bed_fn, int n_sam
 int hibag_hip_predict_draw(hibag_hip_model *m, const int32_t *geno, int n_samp, int vote_method, int n_draw, uint64_t seed,
 	int64_t sample0, int32_t *h1, int32_t *h2, double *prob, double *matching)
 {
-	if (int rc = check_predict_args(m, geno, n_samp, vote_method, nullptr, nullptr)) return rc;
-	const ListOut draw{n_draw, h1, h2, prob, true, seed, sample0};
-	if (int rc = check_list_args(n_samp, draw)) return rc;
-	if (n_samp == 0) return 0;
-	std::lock_guard<std::mutex> g(m->lock);
-	HIP_TRY(hipSetDevice(m->device));
-	return predict_staged_locked(m, geno, nullptr, n_samp, vote_method, nullptr, nullptr, nullptr, matching, nullptr, nullptr,
-		nullptr, false, nullptr, &draw);
+	return predict_entry(m, geno, n_samp, vote_method, PredictOut::draw(n_draw, seed, sample0, h1, h2, prob, matching));
 }
 
 int hibag_hip_predict_draw_device(hibag_hip_model *m, const int32_t *d_geno, int n_samp, int vote_method, int n_draw,
 	uint64_t seed, int64_t sample0, int32_t *d_h1, int32_t *d_h2, double *d_prob, double *d_matching, void *stream)
 {
-	if (int rc = check_predict_args(m, d_geno, n_samp, vote_method, nullptr, nullptr)) return rc;
-	const ListOut draw{n_draw, d_h1, d_h2, d_prob, true, seed, sample0};
-	if (int rc = check_list_args(n_samp, draw)) return rc;
-	std::lock_guard<std::mutex> g(m->lock);
-	if (int rc = sticky_fault(m)) return rc;
 	PackSource src;
 	src.d_geno = d_geno;
-	return predict_device_locked(m, src, n_samp, vote_method, nullptr, nullptr, nullptr, d_matching, nullptr, nullptr,
-		(hipStream_t)stream, &draw);
+	return predict_device_entry(m, src, n_samp, vote_method, PredictOut::draw(n_draw, seed, sample0, d_h1, d_h2, d_prob, d_matching), stream);
 }
 
 int hibag_hip_predict_draw_mapped(hibag_hip_model *m, const int32_t *geno, int n_samp, int n_geno_snp,
 	const int32_t *snp_col, const int32_t *flip, int vote_method, int n_draw, uint64_t seed, int64_t sample0,
 	int32_t *h1, int32_t *h2, double *prob, double *matching)
 {
-	const ListOut draw{n_draw, h1, h2, prob, true, seed, sample0};
-	return predict_mapped_entry(m, geno, n_samp, n_geno_snp, snp_col, flip, vote_method, nullptr, nullptr, nullptr, matching,
-		nullptr, nullptr, &draw);
+	return predict_mapped_entry(m, geno, n_samp, n_geno_snp, snp_col, flip, vote_method,
+		PredictOut::draw(n_draw, seed, sample0, h1, h2, prob, matching));
 }
 
 int hibag_hip_predict_draw_snp_major(hibag_hip_model *m, const int32_t *geno, size_t ld, int n_samp, int n_geno_snp,
 	const int32_t *snp_col, const int32_t *flip, int vote_method, int n_draw, uint64_t seed, int64_t sample0,
 	int32_t *h1, int32_t *h2, double *prob, double *matching)
 {
-	const ListOut draw{n_draw, h1, h2, prob, true, seed, sample0};
-	return predict_snp_major_entry(m, geno, ld, n_samp, n_geno_snp, snp_col, flip, vote_method, nullptr, nullptr, nullptr, matching,
-		nullptr, nullptr, &draw);
+	return predict_snp_major_entry(m, geno, ld, n_samp, n_geno_snp, snp_col, flip, vote_method,
+		PredictOut::draw(n_draw, seed, sample0, h1, h2, prob, matching));
 }
 
 int hibag_hip_predict_draw_bed(hibag_hip_model *m, const char *bed_fn, int n_samp, int n_snp,
 	const int32_t *snp_col, const int32_t *flip, int vote_method, int n_draw, uint64_t seed, int64_t sample0,
 	int32_t *h1, int32_t *h2, double *prob, double *matching)
 {
-	const ListOut draw{n_draw, h1, h2, prob, true, seed, sample0};
-	return predict_bed_entry(m, bed_fn, n_samp, n_snp, snp_col, flip, vote_method, nullptr, nullptr, nullptr, matching,
-		nullptr, nullptr, &draw);
+	return predict_bed_entry(m, bed_fn, n_samp, n_snp, snp_col, flip, vote_method,
+		PredictOut::draw(n_draw, seed, sample0, h1, h2, prob, matching));
 }
 
 int hibag_hip_predict_partial_device(hibag_hip_model *m, const int32_t *d_geno, int n_samp,

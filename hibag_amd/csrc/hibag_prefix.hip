@@ -50,10 +50,8 @@ static int prefix_batch(const hibag_hip_model *L, int64_t sum_sizes, int n_sizes
 }
 
 static int predict_prefix_locked(hibag_hip_model *m, hibag_hip_model *L, const int32_t *geno, int n_samp, const int32_t *sizes, int n_sizes,
-	int32_t *H1, int32_t *H2, double *prob, double *matching, bool is_retry = false)
+	int32_t *H1, int32_t *H2, double *prob, double *matching)
 {
-	if (L->ws_pending && L->ws_done && !is_retry) HIP_TRY(hipEventSynchronize(L->ws_done));
-	if (int rc = sticky_fault(L)) return rc;
 	StagedStreams *ss;
 	if (int rc = staged_streams(L, &ss)) return rc;
 	const hipStream_t st = ss->run;
@@ -88,10 +86,7 @@ static int predict_prefix_locked(hibag_hip_model *m, hibag_hip_model *L, const i
 	char *o = L->ws_out.as<char>();
 	const int32_t *d_geno = L->ws_geno.as<int32_t>();
 	if (int rc = workspace_enter(L, st)) return rc;
-	struct Guard {                             // (records ws_done on every way out once something is enqueued)
-		hibag_hip_model *L; hipStream_t st; bool left = false;
-		~Guard() { if (!left && L->ws_done) { (void)hipEventRecord(L->ws_done, st); L->ws_pending = true; } }
-	} guard{L, st};
+	WorkspaceGuard guard{L, st, true};
 	HIP_TRY(hipMemcpyAsync(L->pfx_tab.p, tab.data(), tab.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
 	HIP_TRY(hipMemcpyAsync(L->ws_geno.p, geno, n * S * sizeof(int32_t), hipMemcpyHostToDevice, st));
 
@@ -132,8 +127,7 @@ static int predict_prefix_locked(hibag_hip_model *m, hibag_hip_model *L, const i
 	if (e == hipSuccess) e = hipMemcpyAsync(H2, o + o_h2, K * n * 4, hipMemcpyDeviceToHost, st);
 	if (e == hipSuccess) e = hipMemcpyAsync(prob, o + o_prob, K * n * 8, hipMemcpyDeviceToHost, st);
 	if (e == hipSuccess) e = hipMemcpyAsync(matching, o + o_mt, K * n * 8, hipMemcpyDeviceToHost, st);
-	guard.left = true;
-	const int rc_leave = workspace_leave(L, st);
+	const int rc_leave = guard.leave();
 	if (e == hipSuccess) e = hipStreamSynchronize(st);
 	double ms = 0;
 	for (size_t i = 0; i + 1 < ev.size() && e == hipSuccess; i += 2) {
@@ -143,11 +137,7 @@ static int predict_prefix_locked(hibag_hip_model *m, hibag_hip_model *L, const i
 	drop_events();
 	if (e != hipSuccess) return hibag_fail(HIBAG_HIP_ENODEV, "hibag_hip_predict_prefix failed: %s", hipGetErrorString(e));
 	if (rc_leave) return rc_leave;
-	m->pfx_accum_ms = ms;
-	if (take_fault(L)) {
-		if (is_retry) return hibag_fail(HIBAG_HIP_EHANDOVER, "a hand-over between workgroups failed in a launch without hand-overs");
-		return predict_prefix_locked(m, L, geno, n_samp, sizes, n_sizes, H1, H2, prob, matching, true);
-	}
+	m->pfx_accum_ms = ms;                      // (only a completed run sets it; a repair's second run sets it again)
 	return 0;
 }
 
@@ -180,7 +170,8 @@ int hibag_hip_predict_prefix(hibag_hip_model *m, const int32_t *geno, int n_samp
 	HIP_TRY(hipSetDevice(m->device));
 	hibag_hip_model *L = nullptr;
 	if (int rc = prefix_layout(m, &L)) return rc;
-	return predict_prefix_locked(m, L, geno, n_samp, sizes, n_sizes, H1, H2, prob, matching);
+	// (a failed hand-over is repaired as in predict_staged_locked; the hand-overs are those of the layout the entry runs on)
+	return with_handover_repair(&L, 1, [&]() { return predict_prefix_locked(m, L, geno, n_samp, sizes, n_sizes, H1, H2, prob, matching); });
 }
 
 int hibag_hip_predict_prefix_ms(const hibag_hip_model *m, double *accum_ms)

@@ -16,7 +16,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 import sys
-from typing import List, Optional, Sequence, Union
+from typing import List, NamedTuple, Optional, Sequence, Union
 
 import numpy as np
 
@@ -50,33 +50,32 @@ def hlaSetKernelTarget(cpu: str = "hip") -> List[str]:
     return [_kernel_info]
 
 
-def _kernel_info_text() -> str:
-    """What the last :func:`hlaSetKernelTarget` reported (the line ``hlaPredict`` prints)."""
-    return _kernel_info
-
-
 def _as_ptr(a: Optional[np.ndarray]):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+def _dev_ptr(x):
+    """A device address (``tensor.data_ptr()``) or a stream handle, or None, as a C pointer argument."""
+    return None if x is None else C.c_void_p(int(x))
+
+
+def _list_count(v, name: str, limit: int, macro: str) -> int:
+    ok = isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+    if not ok and isinstance(v, (float, np.floating)) and float(v).is_integer():
+        ok = True
+    if not ok or not (1 <= int(v) <= limit):
+        raise ValueError(f"'{name}' must be an integer between 1 and {limit} ({macro}): {v!r}")
+    return int(v)
+
+
 def topk_k(k) -> int:
     """The ``k`` of the top-k entries as an int within 1 .. ``HIBAG_HIP_TOPK_MAX``; ``ValueError`` otherwise."""
-    ok = isinstance(k, (int, np.integer)) and not isinstance(k, (bool, np.bool_))
-    if not ok and isinstance(k, (float, np.floating)) and float(k).is_integer():
-        ok = True
-    if not ok or not (1 <= int(k) <= _lib.TOPK_MAX):
-        raise ValueError(f"'k' must be an integer between 1 and {_lib.TOPK_MAX} (HIBAG_HIP_TOPK_MAX): {k!r}")
-    return int(k)
+    return _list_count(k, "k", _lib.TOPK_MAX, "HIBAG_HIP_TOPK_MAX")
 
 
 def draw_n(n) -> int:
     """The ``n_draw`` of the draw entries as an int within 1 .. ``HIBAG_HIP_DRAW_MAX``; ``ValueError`` otherwise."""
-    ok = isinstance(n, (int, np.integer)) and not isinstance(n, (bool, np.bool_))
-    if not ok and isinstance(n, (float, np.floating)) and float(n).is_integer():
-        ok = True
-    if not ok or not (1 <= int(n) <= _lib.DRAW_MAX):
-        raise ValueError(f"'n' must be an integer between 1 and {_lib.DRAW_MAX} (HIBAG_HIP_DRAW_MAX): {n!r}")
-    return int(n)
+    return _list_count(n, "n", _lib.DRAW_MAX, "HIBAG_HIP_DRAW_MAX")
 
 
 def _draw_key(seed, sample0) -> tuple:
@@ -231,18 +230,121 @@ class HlaAttrBagClass:
         return out
 
     # --- raw entry points -------------------------------------------------
-    def predict_raw(self, genomat: np.ndarray, vote_method: int = 1, want_dosage: bool = True,
-                    want_prob: bool = False) -> dict:
-        """``CAttrBag_Model::PredictHLA`` on host arrays: ``genomat`` int32 [n_samp, n_snp]."""
+    # Every host-pointer entry of the C ABI is `hibag_hip_predict[_topk|_draw]<route>(model, <route's arguments>, vote_method,
+    # <family's own arguments>, <outputs>)`.  A route (`_route_*`) validates and marshals its arguments once, for all three
+    # families: it returns (the entry's suffix, the C arguments in front of vote_method, n_samp).  A tail (`_six`, `_list`)
+    # says which family is called: (the entry's stem, its own C arguments, the keys of its outputs in C order, n -> arrays).
+    def _genomat(self, genomat) -> np.ndarray:
         g = np.ascontiguousarray(genomat, np.int32)
         if g.ndim != 2 or g.shape[1] != self.obj.n_snp:
             raise ValueError("genomat must be [n_samp, n.snp] int32")
-        n = g.shape[0]
-        out = self._outputs(n, want_dosage, want_prob)
-        _lib.check(_lib.lib().hibag_hip_predict(
-            self.handle, _as_ptr(g), n, int(vote_method), _as_ptr(out["h1"]), _as_ptr(out["h2"]),
-            _as_ptr(out["prob"]), _as_ptr(out["matching"]), _as_ptr(out.get("dosage")), _as_ptr(out.get("postprob"))))
+        return g
+
+    def _model_col_flip(self, snp_col, flip):
+        col = np.ascontiguousarray(snp_col, np.int32)
+        if col.shape != (self.obj.n_snp,):
+            raise ValueError("snp_col must have one entry per model SNP")
+        return col, (None if flip is None else np.ascontiguousarray(np.asarray(flip) != 0, np.int32))
+
+    def _route_raw(self, genomat):
+        g = self._genomat(genomat)
+        return "", (_as_ptr(g), g.shape[0]), g.shape[0]
+
+    def _route_mapped(self, genomat, snp_col, flip):
+        g = np.ascontiguousarray(genomat, np.int32)
+        if g.ndim != 2:
+            raise ValueError("genomat must be [n_samp, n_geno_snp]")
+        col, fl = self._model_col_flip(snp_col, flip)
+        return "_mapped", (_as_ptr(g), g.shape[0], g.shape[1], _as_ptr(col), _as_ptr(fl)), g.shape[0]
+
+    def _route_snp_major(self, genomat, snp_col, flip):
+        g = np.asarray(genomat)
+        if g.ndim != 2 or g.dtype != np.int32 or g.strides[1] != 4 or g.strides[0] % 4 or (g.shape[0] > 1 and g.strides[0] < 4 * g.shape[1]):
+            g = np.ascontiguousarray(g, np.int32)
+            if g.ndim != 2:
+                raise ValueError("genomat must be [n_geno_snp, n_samp]")
+        col = None
+        if snp_col is not None:
+            col, _ = self._model_col_flip(snp_col, None)
+        elif g.shape[0] < self.obj.n_snp:
+            raise ValueError("nrow(snp) == object$n.snp is not TRUE")
+        fl = None if flip is None else np.ascontiguousarray(np.asarray(flip) != 0, np.int32)
+        n = g.shape[1]
+        ld = g.strides[0] // 4 if g.shape[0] > 1 else max(n, 1)
+        return "_snp_major", (_as_ptr(g), ld, n, max(g.shape[0], 1), _as_ptr(col), _as_ptr(fl)), n
+
+    def _route_bed(self, bed_fn, n_samp, n_snp, snp_col, flip):
+        col, fl = self._model_col_flip(snp_col, flip)
+        return "_bed", (os.fsencode(bed_fn), int(n_samp), int(n_snp), _as_ptr(col), _as_ptr(fl)), int(n_samp)
+
+    def _route_cohort(self, cohort, snp_col, flip, first, count):
+        h = cohort.handle
+        col, fl = self._model_col_flip(snp_col, flip)
+        first = int(first)
+        n = cohort.n_samp - first if count is None else int(count)
+        return "_cohort", (h, first, n, _as_ptr(col), _as_ptr(fl)), n
+
+    def _outputs(self, n: int, want_dosage: bool, want_prob: bool) -> dict:
+        """The output arrays of ``PredictHLA`` for n samples (every element is written by the library)."""
+        out = dict(h1=np.empty(n, np.int32), h2=np.empty(n, np.int32), prob=np.empty(n, np.float64), matching=np.empty(n, np.float64))
+        if want_dosage:
+            out["dosage"] = np.empty((n, self.obj.n_hla), np.float64)
+        if want_prob:
+            out["postprob"] = np.empty((n, self.obj.n_cell), np.float64)
         return out
+
+    def _six(self, want_dosage: bool, want_prob: bool):
+        return ("hibag_hip_predict", (), ("h1", "h2", "prob", "matching", "dosage", "postprob"),
+                lambda n: self._outputs(n, want_dosage, want_prob))
+
+    @staticmethod
+    def _list(family: str, extra: tuple):
+        """The list entries' tail: ``family`` "topk" with ``extra`` (k,), or "draw" with (n_draw, seed, sample0)."""
+        k = extra[0]
+        return ("hibag_hip_predict_" + family, extra, ("h1", "h2", "prob", "matching"),
+                lambda n: dict(h1=np.empty((n, k), np.int32), h2=np.empty((n, k), np.int32), prob=np.empty((n, k), np.float64),
+                               matching=np.empty(n, np.float64)))
+
+    def _call(self, route, vote_method: int, tail) -> dict:
+        suffix, head, n = route
+        stem, extra, keys, make = tail
+        out = make(max(n, 0))
+        _lib.check(getattr(_lib.lib(), stem + suffix)(self.handle, *head, int(vote_method), *extra,
+                                                      *[_as_ptr(out.get(k)) for k in keys]))
+        return out
+
+    def predict_raw(self, genomat: np.ndarray, vote_method: int = 1, want_dosage: bool = True,
+                    want_prob: bool = False) -> dict:
+        """``CAttrBag_Model::PredictHLA`` on host arrays: ``genomat`` int32 [n_samp, n_snp]."""
+        return self._call(self._route_raw(genomat), vote_method, self._six(want_dosage, want_prob))
+
+    def predict_mapped(self, genomat: np.ndarray, snp_col: np.ndarray, flip: Optional[np.ndarray] = None,
+                       vote_method: int = 1, want_dosage: bool = True, want_prob: bool = False) -> dict:
+        """``PredictHLA`` on the COHORT's own matrix ``genomat`` [n_samp, n_geno_snp] (``hibag_hip_predict_mapped``):
+        ``snp_col[k]`` = column of model SNP k (-1 = absent), ``flip[k]`` = reverse its allele count; the
+        selection and the flip happen on the device while the genotypes are packed."""
+        return self._call(self._route_mapped(genomat, snp_col, flip), vote_method, self._six(want_dosage, want_prob))
+
+    def predict_snp_major(self, genomat: np.ndarray, snp_col: Optional[np.ndarray] = None, flip: Optional[np.ndarray] = None,
+                          vote_method: int = 1, want_dosage: bool = True, want_prob: bool = False) -> dict:
+        """``PredictHLA`` on a SNP-MAJOR matrix ``genomat`` [n_geno_snp, n_samp] in C order -- numpy's own layout for the
+        [SNP, sample] matrix of an ``hlaSNPGenoClass`` (``hibag_hip_predict_snp_major``): row ``snp_col[k]`` holds model SNP k
+        (-1 = absent; ``None`` = row k), ``flip[k]`` reverses its allele count.  Nothing is transposed on the host."""
+        return self._call(self._route_snp_major(genomat, snp_col, flip), vote_method, self._six(want_dosage, want_prob))
+
+    def predict_bed(self, bed_fn: str, n_samp: int, n_snp: int, snp_col: np.ndarray, flip: Optional[np.ndarray] = None,
+                    vote_method: int = 1, want_dosage: bool = True, want_prob: bool = False) -> dict:
+        """``PredictHLA`` on every sample of a PLINK BED file (``hibag_hip_predict_bed``):
+        ``snp_col[k]`` = 0-based .bim index of model SNP k (-1 = absent), ``flip[k]`` =
+        reverse the allele count of SNP k."""
+        return self._call(self._route_bed(bed_fn, n_samp, n_snp, snp_col, flip), vote_method, self._six(want_dosage, want_prob))
+
+    def predict_cohort(self, cohort, snp_col: np.ndarray, flip: Optional[np.ndarray] = None, vote_method: int = 1,
+                       want_dosage: bool = True, want_prob: bool = False, first: int = 0, count: Optional[int] = None) -> dict:
+        """``PredictHLA`` on samples ``[first, first + count)`` of a resident cohort (``hibag_hip_predict_cohort``;
+        ``cohort``: an ``HlaDeviceCohort``): ``snp_col[k]`` = resident row of model SNP k (-1 = absent), ``flip[k]`` =
+        reverse its allele count.  Nothing but the row map goes up."""
+        return self._call(self._route_cohort(cohort, snp_col, flip, first, count), vote_method, self._six(want_dosage, want_prob))
 
     def predict_oob(self, genomat: np.ndarray, samp_num) -> dict:
         """``hlaOutOfBag``'s per-classifier predictions (``R/HIBAG.R:1320-1334``) in one batched call
@@ -250,9 +352,7 @@ class HlaAttrBagClass:
         ``samp_num[c, s] == 0``.  ``genomat`` int32 [n_samp, n_snp] holds the model's training samples in
         ``sample_id`` order, ``samp_num`` [n_classifier, n_samp] their bootstrap counts.  Returns ``h1``, ``h2``
         (0-based, NA = INT_MIN where not predicted) and ``prob`` (0 there), each [n_classifier, n_samp]."""
-        g = np.ascontiguousarray(genomat, np.int32)
-        if g.ndim != 2 or g.shape[1] != self.obj.n_snp:
-            raise ValueError("genomat must be [n_samp, n.snp] int32")
+        g = self._genomat(genomat)
         n, nc = g.shape[0], len(self.obj.classifiers)
         sn = np.ascontiguousarray(samp_num, np.int32)
         if sn.shape != (nc, n):
@@ -269,9 +369,7 @@ class HlaAttrBagClass:
         bit for bit; a sample no classifier is used for gets call NA, ``prob`` 0, ``matching`` NaN.  ``geno`` int32
         [n_samp, n_snp], ``use`` [n_classifier, n_samp] (bool or integer; nonzero = takes part).  Returns a dict like
         :meth:`predict_raw`'s."""
-        g = np.ascontiguousarray(geno, np.int32)
-        if g.ndim != 2 or g.shape[1] != self.obj.n_snp:
-            raise ValueError("genomat must be [n_samp, n.snp] int32")
+        g = self._genomat(geno)
         n, nc = g.shape[0], len(self.obj.classifiers)
         u = np.asarray(use)
         if u.dtype.kind not in "biu":
@@ -281,20 +379,14 @@ class HlaAttrBagClass:
         if int(vote_method) not in (1, 2):
             raise ValueError("Invalid 'vote_method'.")
         u = np.ascontiguousarray(u != 0, np.uint8)
-        out = self._outputs(n, want_dosage, want_prob)
-        _lib.check(_lib.lib().hibag_hip_predict_masked(
-            self.handle, _as_ptr(g), n, _as_ptr(u), int(vote_method), _as_ptr(out["h1"]), _as_ptr(out["h2"]),
-            _as_ptr(out["prob"]), _as_ptr(out["matching"]), _as_ptr(out.get("dosage")), _as_ptr(out.get("postprob"))))
-        return out
+        return self._call(("_masked", (_as_ptr(g), n, _as_ptr(u)), n), vote_method, self._six(want_dosage, want_prob))
 
     def predict_prefix(self, genomat: np.ndarray, sizes) -> dict:
         """``hibag_hip_predict_prefix``: for every ``sizes[i]`` (strictly ascending, 1 .. n_classifier) what
         ``predict_raw`` (vote by probability) returns for the model of the first ``sizes[i]`` classifiers
         (``hlaSubModelObj``) -- ``h1``, ``h2``, ``prob``, ``matching``, each [n_sizes, n_samp] -- from one pass 1.
         ``genomat`` int32 [n_samp, n_snp]."""
-        g = np.ascontiguousarray(genomat, np.int32)
-        if g.ndim != 2 or g.shape[1] != self.obj.n_snp:
-            raise ValueError("genomat must be [n_samp, n.snp] int32")
+        g = self._genomat(genomat)
         sz = np.ascontiguousarray(sizes, np.int32)
         if sz.ndim != 1:
             raise ValueError("sizes must be a vector")
@@ -312,115 +404,44 @@ class HlaAttrBagClass:
         return ms.value
 
     # --- the list entries: the k best pairs of every sample (hibag_hip_predict_topk and its routes; include/hibag_hip.h
-    # "top-k") and pairs drawn from its posterior (hibag_hip_predict_draw and its routes; "posterior draws").  The two
-    # families take the same arguments on every route but for their own -- `extra`: (k,) or (n_draw, seed, sample0), which
-    # the C entries take between vote_method and h1 -- so each route is written once (`entry`: the C entry's name, `width`:
-    # pairs per sample).
-    @staticmethod
-    def _topk_outputs(n: int, k: int) -> dict:
-        return dict(h1=np.empty((n, k), np.int32), h2=np.empty((n, k), np.int32), prob=np.empty((n, k), np.float64),
-                    matching=np.empty(n, np.float64))
-
-    def _model_col_flip(self, snp_col, flip):
-        col = np.ascontiguousarray(snp_col, np.int32)
-        if col.shape != (self.obj.n_snp,):
-            raise ValueError("snp_col must have one entry per model SNP")
-        return col, (None if flip is None else np.ascontiguousarray(np.asarray(flip) != 0, np.int32))
-
-    def _lists(self, entry: str, extra: tuple, width: int, genomat: np.ndarray, vote_method: int) -> dict:
-        g = np.ascontiguousarray(genomat, np.int32)
-        if g.ndim != 2 or g.shape[1] != self.obj.n_snp:
-            raise ValueError("genomat must be [n_samp, n.snp] int32")
-        n = g.shape[0]
-        out = self._topk_outputs(n, width)
-        _lib.check(getattr(_lib.lib(), entry)(
-            self.handle, _as_ptr(g), n, int(vote_method), *extra, _as_ptr(out["h1"]), _as_ptr(out["h2"]), _as_ptr(out["prob"]),
-            _as_ptr(out["matching"])))
-        return out
-
-    def _lists_mapped(self, entry: str, extra: tuple, width: int, genomat: np.ndarray, snp_col, flip, vote_method: int) -> dict:
-        g = np.ascontiguousarray(genomat, np.int32)
-        if g.ndim != 2:
-            raise ValueError("genomat must be [n_samp, n_geno_snp]")
-        col, fl = self._model_col_flip(snp_col, flip)
-        n = g.shape[0]
-        out = self._topk_outputs(n, width)
-        _lib.check(getattr(_lib.lib(), entry)(
-            self.handle, _as_ptr(g), n, g.shape[1], _as_ptr(col), _as_ptr(fl), int(vote_method), *extra,
-            _as_ptr(out["h1"]), _as_ptr(out["h2"]), _as_ptr(out["prob"]), _as_ptr(out["matching"])))
-        return out
-
-    def _lists_snp_major(self, entry: str, extra: tuple, width: int, genomat: np.ndarray, snp_col, flip, vote_method: int) -> dict:
-        g = np.asarray(genomat)
-        if g.ndim != 2 or g.dtype != np.int32 or g.strides[1] != 4 or g.strides[0] % 4 or (g.shape[0] > 1 and g.strides[0] < 4 * g.shape[1]):
-            g = np.ascontiguousarray(g, np.int32)
-            if g.ndim != 2:
-                raise ValueError("genomat must be [n_geno_snp, n_samp]")
-        col = None
-        if snp_col is not None:
-            col, _ = self._model_col_flip(snp_col, None)
-        elif g.shape[0] < self.obj.n_snp:
-            raise ValueError("nrow(snp) == object$n.snp is not TRUE")
-        fl = None if flip is None else np.ascontiguousarray(np.asarray(flip) != 0, np.int32)
-        n = g.shape[1]
-        out = self._topk_outputs(n, width)
-        ld = g.strides[0] // 4 if g.shape[0] > 1 else max(n, 1)
-        _lib.check(getattr(_lib.lib(), entry)(
-            self.handle, _as_ptr(g), ld, n, max(g.shape[0], 1), _as_ptr(col), _as_ptr(fl), int(vote_method), *extra,
-            _as_ptr(out["h1"]), _as_ptr(out["h2"]), _as_ptr(out["prob"]), _as_ptr(out["matching"])))
-        return out
-
-    def _lists_bed(self, entry: str, extra: tuple, width: int, bed_fn: str, n_samp: int, n_snp: int, snp_col, flip,
-                   vote_method: int) -> dict:
-        col, fl = self._model_col_flip(snp_col, flip)
-        n = int(n_samp)
-        out = self._topk_outputs(n, width)
-        _lib.check(getattr(_lib.lib(), entry)(
-            self.handle, os.fsencode(bed_fn), n, int(n_snp), _as_ptr(col), _as_ptr(fl), int(vote_method), *extra,
-            _as_ptr(out["h1"]), _as_ptr(out["h2"]), _as_ptr(out["prob"]), _as_ptr(out["matching"])))
-        return out
-
-    def _lists_cohort(self, entry: str, extra: tuple, width: int, cohort, snp_col, flip, vote_method: int, first: int,
-                      count: Optional[int]) -> dict:
-        h = cohort.handle
-        col, fl, first, n = self._cohort_args(cohort, snp_col, flip, first, count)
-        out = self._topk_outputs(max(n, 0), width)
-        _lib.check(getattr(_lib.lib(), entry)(
-            self.handle, h, first, n, _as_ptr(col), _as_ptr(fl), int(vote_method), *extra,
-            _as_ptr(out["h1"]), _as_ptr(out["h2"]), _as_ptr(out["prob"]), _as_ptr(out["matching"])))
-        return out
-
+    # "top-k") and pairs drawn from its posterior (hibag_hip_predict_draw and its routes; "posterior draws"): the routes
+    # above with the list tail.
     def predict_topk(self, genomat: np.ndarray, k: int, vote_method: int = 1) -> dict:
         """``hibag_hip_predict_topk``: per sample the ``k`` largest cells of the normalised posterior matrix (what
         ``predict_raw(..., want_prob=True)`` returns as ``postprob``) selected on the device -- ``h1``, ``h2`` (0-based,
         NA = INT_MIN in the ranks no pair qualifies for) and ``prob`` (0 there), each [n_samp, k], descending, equal values
         in pair order, and ``matching`` [n_samp].  Rank 0 is ``predict_raw``'s call.  ``genomat`` int32 [n_samp, n_snp]."""
-        k = topk_k(k)
-        return self._lists("hibag_hip_predict_topk", (k,), k, genomat, vote_method)
+        tail = self._list("topk", (topk_k(k),))
+        return self._call(self._route_raw(genomat), vote_method, tail)
 
     def predict_topk_mapped(self, genomat: np.ndarray, snp_col: np.ndarray, flip: Optional[np.ndarray], k: int,
                             vote_method: int = 1) -> dict:
         """:meth:`predict_topk` on the cohort's own matrix [n_samp, n_geno_snp], as :meth:`predict_mapped`."""
-        k = topk_k(k)
-        return self._lists_mapped("hibag_hip_predict_topk_mapped", (k,), k, genomat, snp_col, flip, vote_method)
+        tail = self._list("topk", (topk_k(k),))
+        return self._call(self._route_mapped(genomat, snp_col, flip), vote_method, tail)
 
     def predict_topk_snp_major(self, genomat: np.ndarray, snp_col: Optional[np.ndarray], flip: Optional[np.ndarray], k: int,
                                vote_method: int = 1) -> dict:
         """:meth:`predict_topk` on a SNP-major matrix [n_geno_snp, n_samp] in C order, as :meth:`predict_snp_major`."""
-        k = topk_k(k)
-        return self._lists_snp_major("hibag_hip_predict_topk_snp_major", (k,), k, genomat, snp_col, flip, vote_method)
+        tail = self._list("topk", (topk_k(k),))
+        return self._call(self._route_snp_major(genomat, snp_col, flip), vote_method, tail)
 
     def predict_topk_bed(self, bed_fn: str, n_samp: int, n_snp: int, snp_col: np.ndarray, flip: Optional[np.ndarray], k: int,
                          vote_method: int = 1) -> dict:
         """:meth:`predict_topk` on every sample of a PLINK BED file, as :meth:`predict_bed`."""
-        k = topk_k(k)
-        return self._lists_bed("hibag_hip_predict_topk_bed", (k,), k, bed_fn, n_samp, n_snp, snp_col, flip, vote_method)
+        tail = self._list("topk", (topk_k(k),))
+        return self._call(self._route_bed(bed_fn, n_samp, n_snp, snp_col, flip), vote_method, tail)
+
+    def predict_topk_cohort(self, cohort, snp_col: np.ndarray, flip: Optional[np.ndarray], k: int, vote_method: int = 1,
+                            first: int = 0, count: Optional[int] = None) -> dict:
+        """:meth:`predict_topk` on samples ``[first, first + count)`` of a resident cohort, as :meth:`predict_cohort`."""
+        tail = self._list("topk", (topk_k(k),))
+        return self._call(self._route_cohort(cohort, snp_col, flip, first, count), vote_method, tail)
 
     def predict_topk_device(self, d_geno, n_samp: int, k: int, d_h1, d_h2, d_prob, d_matching=None, vote_method: int = 1,
                             stream=None):
         """Device-pointer form of :meth:`predict_topk`; arguments are ints (``tensor.data_ptr()``) or None."""
-        def p(x):
-            return None if x is None else C.c_void_p(int(x))
+        p = _dev_ptr
         _lib.check(_lib.lib().hibag_hip_predict_topk_device(
             self.handle, p(d_geno), int(n_samp), int(vote_method), int(k), p(d_h1), p(d_h2), p(d_prob), p(d_matching), p(stream)))
 
@@ -430,156 +451,48 @@ class HlaAttrBagClass:
         for a sample without a positive cell) and ``prob`` (the drawn pair's posterior), each [n_samp, n], and
         ``matching`` [n_samp].  Draw t of sample s is a function of (``seed``, ``sample0 + s``, t) and the sample's posterior
         alone.  ``genomat`` int32 [n_samp, n_snp]."""
-        n = draw_n(n)
-        return self._lists("hibag_hip_predict_draw", (n,) + _draw_key(seed, sample0), n, genomat, vote_method)
+        tail = self._list("draw", (draw_n(n),) + _draw_key(seed, sample0))
+        return self._call(self._route_raw(genomat), vote_method, tail)
 
     def predict_draw_mapped(self, genomat: np.ndarray, snp_col: np.ndarray, flip: Optional[np.ndarray], n: int, seed: int,
                             vote_method: int = 1, sample0: int = 0) -> dict:
         """:meth:`predict_draw` on the cohort's own matrix [n_samp, n_geno_snp], as :meth:`predict_mapped`."""
-        n = draw_n(n)
-        return self._lists_mapped("hibag_hip_predict_draw_mapped", (n,) + _draw_key(seed, sample0), n, genomat, snp_col, flip,
-                                  vote_method)
+        tail = self._list("draw", (draw_n(n),) + _draw_key(seed, sample0))
+        return self._call(self._route_mapped(genomat, snp_col, flip), vote_method, tail)
 
     def predict_draw_snp_major(self, genomat: np.ndarray, snp_col: Optional[np.ndarray], flip: Optional[np.ndarray], n: int,
                                seed: int, vote_method: int = 1, sample0: int = 0) -> dict:
         """:meth:`predict_draw` on a SNP-major matrix [n_geno_snp, n_samp] in C order, as :meth:`predict_snp_major`."""
-        n = draw_n(n)
-        return self._lists_snp_major("hibag_hip_predict_draw_snp_major", (n,) + _draw_key(seed, sample0), n, genomat, snp_col,
-                                     flip, vote_method)
+        tail = self._list("draw", (draw_n(n),) + _draw_key(seed, sample0))
+        return self._call(self._route_snp_major(genomat, snp_col, flip), vote_method, tail)
 
     def predict_draw_bed(self, bed_fn: str, n_samp: int, n_snp: int, snp_col: np.ndarray, flip: Optional[np.ndarray], n: int,
                          seed: int, vote_method: int = 1, sample0: int = 0) -> dict:
         """:meth:`predict_draw` on every sample of a PLINK BED file, as :meth:`predict_bed`."""
-        n = draw_n(n)
-        return self._lists_bed("hibag_hip_predict_draw_bed", (n,) + _draw_key(seed, sample0), n, bed_fn, n_samp, n_snp, snp_col,
-                               flip, vote_method)
-
-    def predict_draw_device(self, d_geno, n_samp: int, n: int, seed: int, d_h1, d_h2, d_prob, d_matching=None,
-                            vote_method: int = 1, sample0: int = 0, stream=None):
-        """Device-pointer form of :meth:`predict_draw`; pointer arguments are ints (``tensor.data_ptr()``) or None."""
-        def p(x):
-            return None if x is None else C.c_void_p(int(x))
-        seed, sample0 = _draw_key(seed, sample0)
-        _lib.check(_lib.lib().hibag_hip_predict_draw_device(
-            self.handle, p(d_geno), int(n_samp), int(vote_method), int(n), seed, sample0, p(d_h1), p(d_h2), p(d_prob),
-            p(d_matching), p(stream)))
+        tail = self._list("draw", (draw_n(n),) + _draw_key(seed, sample0))
+        return self._call(self._route_bed(bed_fn, n_samp, n_snp, snp_col, flip), vote_method, tail)
 
     def predict_draw_cohort(self, cohort, snp_col: np.ndarray, flip: Optional[np.ndarray], n: int, seed: int,
                             vote_method: int = 1, first: int = 0, count: Optional[int] = None, sample0: int = 0) -> dict:
         """:meth:`predict_draw` on samples ``[first, first + count)`` of a resident cohort, as :meth:`predict_cohort`.
         ``sample0`` is the caller's index of sample ``first`` (``first`` is not added to it): ``sample0=first`` draws what
         a call over the whole cohort draws for these samples."""
-        n = draw_n(n)
-        return self._lists_cohort("hibag_hip_predict_draw_cohort", (n,) + _draw_key(seed, sample0), n, cohort, snp_col, flip,
-                                  vote_method, first, count)
+        tail = self._list("draw", (draw_n(n),) + _draw_key(seed, sample0))
+        return self._call(self._route_cohort(cohort, snp_col, flip, first, count), vote_method, tail)
 
-    def predict_bed(self, bed_fn: str, n_samp: int, n_snp: int, snp_col: np.ndarray, flip: Optional[np.ndarray] = None,
-                    vote_method: int = 1, want_dosage: bool = True, want_prob: bool = False) -> dict:
-        """``PredictHLA`` on every sample of a PLINK BED file (``hibag_hip_predict_bed``):
-        ``snp_col[k]`` = 0-based .bim index of model SNP k (-1 = absent), ``flip[k]`` =
-        reverse the allele count of SNP k."""
-        col = np.ascontiguousarray(snp_col, np.int32)
-        if col.shape != (self.obj.n_snp,):
-            raise ValueError("snp_col must have one entry per model SNP")
-        fl = None if flip is None else np.ascontiguousarray(np.asarray(flip) != 0, np.int32)
-        n = int(n_samp)
-        out = self._outputs(n, want_dosage, want_prob)
-        _lib.check(_lib.lib().hibag_hip_predict_bed(
-            self.handle, os.fsencode(bed_fn), n, int(n_snp), _as_ptr(col), _as_ptr(fl), int(vote_method),
-            _as_ptr(out["h1"]), _as_ptr(out["h2"]), _as_ptr(out["prob"]), _as_ptr(out["matching"]),
-            _as_ptr(out.get("dosage")), _as_ptr(out.get("postprob"))))
-        return out
-
-    def _cohort_args(self, cohort, snp_col, flip, first: int, count: Optional[int]):
-        col = np.ascontiguousarray(snp_col, np.int32)
-        if col.shape != (self.obj.n_snp,):
-            raise ValueError("snp_col must have one entry per model SNP")
-        fl = None if flip is None else np.ascontiguousarray(np.asarray(flip) != 0, np.int32)
-        first = int(first)
-        n = cohort.n_samp - first if count is None else int(count)
-        return col, fl, first, n
-
-    def predict_cohort(self, cohort, snp_col: np.ndarray, flip: Optional[np.ndarray] = None, vote_method: int = 1,
-                       want_dosage: bool = True, want_prob: bool = False, first: int = 0, count: Optional[int] = None) -> dict:
-        """``PredictHLA`` on samples ``[first, first + count)`` of a resident cohort (``hibag_hip_predict_cohort``;
-        ``cohort``: an ``HlaDeviceCohort``): ``snp_col[k]`` = resident row of model SNP k (-1 = absent), ``flip[k]`` =
-        reverse its allele count.  Nothing but the row map goes up."""
-        h = cohort.handle
-        col, fl, first, n = self._cohort_args(cohort, snp_col, flip, first, count)
-        out = self._outputs(max(n, 0), want_dosage, want_prob)
-        _lib.check(_lib.lib().hibag_hip_predict_cohort(
-            self.handle, h, first, n, _as_ptr(col), _as_ptr(fl), int(vote_method),
-            _as_ptr(out["h1"]), _as_ptr(out["h2"]), _as_ptr(out["prob"]), _as_ptr(out["matching"]),
-            _as_ptr(out.get("dosage")), _as_ptr(out.get("postprob"))))
-        return out
-
-    def predict_topk_cohort(self, cohort, snp_col: np.ndarray, flip: Optional[np.ndarray], k: int, vote_method: int = 1,
-                            first: int = 0, count: Optional[int] = None) -> dict:
-        """:meth:`predict_topk` on samples ``[first, first + count)`` of a resident cohort, as :meth:`predict_cohort`."""
-        k = topk_k(k)
-        return self._lists_cohort("hibag_hip_predict_topk_cohort", (k,), k, cohort, snp_col, flip, vote_method, first, count)
-
-    def predict_mapped(self, genomat: np.ndarray, snp_col: np.ndarray, flip: Optional[np.ndarray] = None,
-                       vote_method: int = 1, want_dosage: bool = True, want_prob: bool = False) -> dict:
-        """``PredictHLA`` on the COHORT's own matrix ``genomat`` [n_samp, n_geno_snp] (``hibag_hip_predict_mapped``):
-        ``snp_col[k]`` = column of model SNP k (-1 = absent), ``flip[k]`` = reverse its allele count; the
-        selection and the flip happen on the device while the genotypes are packed."""
-        g = np.ascontiguousarray(genomat, np.int32)
-        if g.ndim != 2:
-            raise ValueError("genomat must be [n_samp, n_geno_snp]")
-        col = np.ascontiguousarray(snp_col, np.int32)
-        if col.shape != (self.obj.n_snp,):
-            raise ValueError("snp_col must have one entry per model SNP")
-        fl = None if flip is None else np.ascontiguousarray(np.asarray(flip) != 0, np.int32)
-        n = g.shape[0]
-        out = self._outputs(n, want_dosage, want_prob)
-        _lib.check(_lib.lib().hibag_hip_predict_mapped(
-            self.handle, _as_ptr(g), n, g.shape[1], _as_ptr(col), _as_ptr(fl), int(vote_method),
-            _as_ptr(out["h1"]), _as_ptr(out["h2"]), _as_ptr(out["prob"]), _as_ptr(out["matching"]),
-            _as_ptr(out.get("dosage")), _as_ptr(out.get("postprob"))))
-        return out
-
-    def predict_snp_major(self, genomat: np.ndarray, snp_col: Optional[np.ndarray] = None, flip: Optional[np.ndarray] = None,
-                          vote_method: int = 1, want_dosage: bool = True, want_prob: bool = False) -> dict:
-        """``PredictHLA`` on a SNP-MAJOR matrix ``genomat`` [n_geno_snp, n_samp] in C order -- numpy's own layout for the
-        [SNP, sample] matrix of an ``hlaSNPGenoClass`` (``hibag_hip_predict_snp_major``): row ``snp_col[k]`` holds model SNP k
-        (-1 = absent; ``None`` = row k), ``flip[k]`` reverses its allele count.  Nothing is transposed on the host."""
-        g = np.asarray(genomat)
-        if g.ndim != 2 or g.dtype != np.int32 or g.strides[1] != 4 or g.strides[0] % 4 or (g.shape[0] > 1 and g.strides[0] < 4 * g.shape[1]):
-            g = np.ascontiguousarray(g, np.int32)
-            if g.ndim != 2:
-                raise ValueError("genomat must be [n_geno_snp, n_samp]")
-        col = None
-        if snp_col is not None:
-            col = np.ascontiguousarray(snp_col, np.int32)
-            if col.shape != (self.obj.n_snp,):
-                raise ValueError("snp_col must have one entry per model SNP")
-        elif g.shape[0] < self.obj.n_snp:
-            raise ValueError("nrow(snp) == object$n.snp is not TRUE")
-        fl = None if flip is None else np.ascontiguousarray(np.asarray(flip) != 0, np.int32)
-        n = g.shape[1]
-        out = self._outputs(n, want_dosage, want_prob)
-        ld = g.strides[0] // 4 if g.shape[0] > 1 else max(n, 1)
-        _lib.check(_lib.lib().hibag_hip_predict_snp_major(
-            self.handle, _as_ptr(g), ld, n, max(g.shape[0], 1), _as_ptr(col), _as_ptr(fl), int(vote_method),
-            _as_ptr(out["h1"]), _as_ptr(out["h2"]), _as_ptr(out["prob"]), _as_ptr(out["matching"]),
-            _as_ptr(out.get("dosage")), _as_ptr(out.get("postprob"))))
-        return out
-
-    def _outputs(self, n: int, want_dosage: bool, want_prob: bool) -> dict:
-        """The output arrays of ``PredictHLA`` for n samples (every element is written by the library)."""
-        out = dict(h1=np.empty(n, np.int32), h2=np.empty(n, np.int32), prob=np.empty(n, np.float64), matching=np.empty(n, np.float64))
-        if want_dosage:
-            out["dosage"] = np.empty((n, self.obj.n_hla), np.float64)
-        if want_prob:
-            out["postprob"] = np.empty((n, self.obj.n_cell), np.float64)
-        return out
+    def predict_draw_device(self, d_geno, n_samp: int, n: int, seed: int, d_h1, d_h2, d_prob, d_matching=None,
+                            vote_method: int = 1, sample0: int = 0, stream=None):
+        """Device-pointer form of :meth:`predict_draw`; pointer arguments are ints (``tensor.data_ptr()``) or None."""
+        p = _dev_ptr
+        seed, sample0 = _draw_key(seed, sample0)
+        _lib.check(_lib.lib().hibag_hip_predict_draw_device(
+            self.handle, p(d_geno), int(n_samp), int(vote_method), int(n), seed, sample0, p(d_h1), p(d_h2), p(d_prob),
+            p(d_matching), p(stream)))
 
     def predict_device(self, d_geno, n_samp: int, vote_method: int = 1, d_h1=None, d_h2=None, d_prob=None,
                        d_matching=None, d_dosage=None, d_postprob=None, stream=None):
         """Device-pointer form; arguments are ints (``tensor.data_ptr()``) or None."""
-        def p(x):
-            return None if x is None else C.c_void_p(int(x))
+        p = _dev_ptr
         _lib.check(_lib.lib().hibag_hip_predict_device(
             self.handle, p(d_geno), int(n_samp), int(vote_method), p(d_h1), p(d_h2), p(d_prob), p(d_matching),
             p(d_dosage), p(d_postprob), p(stream)))
@@ -589,14 +502,12 @@ class HlaAttrBagClass:
         return int(_lib.lib().hibag_hip_model_batch_limit(self.handle))
 
     def predict_partial_device(self, d_geno, n_samp: int, d_partial, stream=None):
-        def p(x):
-            return None if x is None else C.c_void_p(int(x))
+        p = _dev_ptr
         _lib.check(_lib.lib().hibag_hip_predict_partial_device(self.handle, p(d_geno), int(n_samp), p(d_partial), p(stream)))
 
     def finish_device(self, d_partial, n_samp: int, d_h1=None, d_h2=None, d_prob=None, d_matching=None,
                       d_dosage=None, d_postprob=None, stream=None):
-        def p(x):
-            return None if x is None else C.c_void_p(int(x))
+        p = _dev_ptr
         _lib.check(_lib.lib().hibag_hip_finish_device(
             self.handle, p(d_partial), int(n_samp), p(d_h1), p(d_h2), p(d_prob), p(d_matching), p(d_dosage),
             p(d_postprob), p(stream)))
@@ -819,26 +730,127 @@ def _as_integer(g: np.ndarray) -> np.ndarray:
     raise TypeError("is.numeric(snp) is not TRUE")
 
 
-def _predict_matrix(model: "HlaAttrBagClass", g: np.ndarray, sel: Optional[np.ndarray], flip: Optional[np.ndarray],
-                    vote_method: int, want_dosage: bool, want_prob: bool) -> dict:
+def _predict_matrix(model: "HlaAttrBagClass", family: str, g: np.ndarray, sel: Optional[np.ndarray], flip: Optional[np.ndarray],
+                    args: tuple, vote_method: int, **want) -> dict:
     """``PredictHLA`` on the matrix ``g`` [SNP, sample] of an ``hlaSNPGenoClass`` (or the numeric matrix handed to
     ``hlaPredict``) WITHOUT building a second matrix on the host: row ``sel[k]`` holds model SNP k (-1 = absent, ``None`` =
     row k), ``flip[k]`` reverses its allele count -- both applied on the device while the genotypes are packed.  The entry
     follows the array's memory: column-major (R's own order: the transpose view is the C side's sample-major matrix) ->
-    ``hibag_hip_predict`` / ``_mapped``; row-major (numpy's default) -> ``hibag_hip_predict_snp_major``.  Bit-identical."""
+    ``hibag_hip_predict`` / ``_mapped``; row-major (numpy's default) -> ``hibag_hip_predict_snp_major``.  Bit-identical.
+    ``family``: "" for the six outputs of ``PredictHLA`` (``want``: ``want_dosage`` / ``want_prob``), "topk" or "draw" for the
+    list entries (``args``: their own arguments, ``(k,)`` or ``(n, seed)``) -- the ``predict_*`` methods of that family."""
+    stem = "predict_" + family if family else "predict"
     g = _as_integer(g)
     if flip is not None and not np.any(flip):
         flip = None
     if g.flags.f_contiguous:
         cohort = g.T                          # a view: [n_samp, cohort SNPs], C-contiguous
         if sel is None and flip is None:
-            return model.predict_raw(cohort, vote_method, want_dosage=want_dosage, want_prob=want_prob)
+            return getattr(model, stem if family else "predict_raw")(cohort, *args, vote_method, **want)
         if sel is None:
             sel = np.arange(model.obj.n_snp, dtype=np.int32)
-        return model.predict_mapped(cohort, sel, flip, vote_method, want_dosage=want_dosage, want_prob=want_prob)
+        return getattr(model, stem + "_mapped")(cohort, sel, flip, *args, vote_method, **want)
     if not g.flags.c_contiguous:
         g = np.ascontiguousarray(g)
-    return model.predict_snp_major(g, sel, flip, vote_method, want_dosage=want_dosage, want_prob=want_prob)
+    return getattr(model, stem + "_snp_major")(g, sel, flip, *args, vote_method, **want)
+
+
+class _Resolved(NamedTuple):
+    """What ``snp`` resolves to (:func:`_resolve_snp`)."""
+    route: str                       # "cohort", "bed" or "matrix"
+    plan: object                     # the SNP matching's plan (None: a numeric matrix in model order)
+    sample_id: Sequence
+    assembly: str
+    n_samp: int
+    mat: Optional[np.ndarray]        # route "matrix": [SNP, sample] ...
+    sel: Optional[np.ndarray]        # ... the row of each model SNP (None: row k) ...
+    flip: Optional[np.ndarray]       # ... and which allele counts to reverse (None: none)
+
+
+def _resolve_snp(obj: HlaAttrBagObj, snp, what: str, match_type: str, allele_check: bool, same_strand: bool, verbose: bool,
+                 verbose_match: bool) -> _Resolved:
+    """The ``snp`` argument of ``hlaPredict`` / ``hlaPredictTopK`` / ``hlaPredictDraws`` resolved to a route -- a resident
+    cohort, a lazily opened BED file, a numeric matrix or vector, an :class:`HlaSNPGeno` with SNP matching -- around the
+    verbose header (``what``: the line that says what is predicted)."""
+    out = sys.stdout
+    if verbose:
+        s = list(obj.hla_allele)
+        if len(s) > 3:
+            s = s[:3] + ["..."]
+        n_c = len(obj.classifiers)
+        print(f"HIBAG model for HLA-{obj.hla_locus}:\n    {n_c} individual classifier{'s' if n_c > 1 else ''}\n"
+              f"    {len(obj.snp_id)} SNPs\n    {obj.n_hla} unique HLA alleles: {', '.join(s)}", file=out)
+        print("Prediction:\n    " + what, file=out)
+
+    plan = mat = sel = flip = None
+    if isinstance(snp, HlaDeviceCohort):
+        # extension: the genotypes are resident on the device (hibag_amd/cohort.py); the SNP matching / strand check runs on
+        # the cohort's annotation, with allele frequencies from counts made on the device
+        route = "cohort"
+        plan = snp.plan_for(obj, match_type, allele_check, same_strand, verbose, verbose_match)
+        geno_sampid = list(snp.sample_id)
+    elif isinstance(snp, HlaBEDGeno):
+        # extension: the genotypes stay in the PLINK BED file; the SNP matching / strand check
+        # (R/HIBAG.R:550-686) runs on the annotation and the device decodes the file directly
+        from .snpmatch import plan_snps_for_predict
+        route = "bed"
+        plan = plan_snps_for_predict(obj, snp, snp.allele_freq, match_type, allele_check, same_strand,
+                                     verbose, verbose_match)
+        geno_sampid = list(snp.sample_id)
+    elif not isinstance(snp, HlaSNPGeno):
+        route = "matrix"
+        g = np.asarray(snp)
+        if g.dtype.kind not in "iufb":
+            raise TypeError("is.numeric(snp) is not TRUE")
+        if g.ndim == 1:
+            if g.shape[0] != obj.n_snp:
+                raise ValueError("length(snp) == object$n.snp is not TRUE")
+            g = g.reshape(-1, 1)
+        elif g.ndim != 2 or g.shape[0] != obj.n_snp:
+            raise ValueError("nrow(snp) == object$n.snp is not TRUE")
+        geno_sampid = range(1, g.shape[1] + 1)
+        mat = g
+    else:
+        # the SNP matching / strand check (R/HIBAG.R:550-686) decides on the annotation; the rows are
+        # picked and flipped on the device while the genotypes are packed (hibag_hip_predict_mapped / _snp_major)
+        from .snpmatch import _row_afreq, plan_snps_for_predict
+        route = "matrix"
+        mat = np.asarray(snp.genotype)
+        if mat.ndim != 2:
+            raise ValueError("'snp$genotype' must be a matrix [n.snp, n.samp]")
+        plan = plan_snps_for_predict(obj, snp, lambda rows: _row_afreq(_as_integer(mat[rows])), match_type,
+                                     allele_check, same_strand, verbose, verbose_match)
+        geno_sampid = snp.sample_id
+        if len(geno_sampid) != mat.shape[1]:
+            raise ValueError("length(snp$sample.id) == ncol(snp$genotype) is not TRUE")
+        sel = None if plan.identity else plan.sel
+        flip = plan.flip if (plan.flip is not None and np.any(plan.flip)) else None
+
+    n_samp = len(geno_sampid) if mat is None else mat.shape[1]
+    if verbose:
+        print(f"# of samples: {n_samp}", file=out)
+        print(f"Kernel target: {_kernel_info or 'hip'}", file=out)
+    return _Resolved(route, plan, geno_sampid, "auto-silent" if plan is None else plan.assembly, n_samp, mat, sel, flip)
+
+
+def _predict_resolved(model: "HlaAttrBagClass", snp, r: _Resolved, family: str, args: tuple, vote_method: int, **want) -> dict:
+    """The call of the route ``snp`` resolved to, on the model's own device (``family``, ``args``, ``want``:
+    :func:`_predict_matrix`)."""
+    stem = "predict_" + family if family else "predict"
+    if r.route == "cohort":
+        return getattr(model, stem + "_cohort")(snp, snp.rows_of(r.plan.sel), r.plan.flip, *args, vote_method, **want)
+    if r.route == "bed":
+        col = np.where(r.plan.sel >= 0, snp.bed_index[np.maximum(r.plan.sel, 0)], -1)
+        return getattr(model, stem + "_bed")(snp.bed_fn, snp.n_bed_samp, snp.n_bed_snp, col, r.plan.flip, *args, vote_method,
+                                             **want)
+    return _predict_matrix(model, family, r.mat, r.sel, r.flip, args, vote_method, **want)
+
+
+def _warn_no_prediction(na_cnt: int) -> None:
+    if na_cnt > 0:   # R/HIBAG.R:811-815
+        import warnings
+        warnings.warn(f"No prediction output{'s' if na_cnt > 1 else ''} for {na_cnt} individual"
+                      f"{'s' if na_cnt > 1 else ''} (possibly due to missing SNPs).", stacklevel=2)     # (the caller's own warning)
 
 
 def hlaPredict(object: HlaAttrBagClass, snp: Union[HlaSNPGeno, HlaBEDGeno, np.ndarray], cl=False,
@@ -872,73 +884,12 @@ def hlaPredict(object: HlaAttrBagClass, snp: Union[HlaSNPGeno, HlaBEDGeno, np.nd
         raise ValueError("'arg' should be one of \"prob\", \"majority\"")
     vote_method = _VOTES.index(vote) + 1
     obj = object.obj
-    out = sys.stdout
-
-    if verbose:
-        s = list(obj.hla_allele)
-        if len(s) > 3:
-            s = s[:3] + ["..."]
-        n_c = len(obj.classifiers)
-        print(f"HIBAG model for HLA-{obj.hla_locus}:\n    {n_c} individual classifier{'s' if n_c > 1 else ''}\n"
-              f"    {len(obj.snp_id)} SNPs\n    {obj.n_hla} unique HLA alleles: {', '.join(s)}", file=out)
-        print("Prediction:\n    " + ("based on the averaged posterior probabilities" if vote_method == 1
-                                      else "by voting from all individual classifiers"), file=out)
-
-    bed_plan = map_plan = coh_plan = None
-    if isinstance(snp, HlaDeviceCohort):
-        # extension: the genotypes are resident on the device (hibag_amd/cohort.py); the SNP matching / strand check runs on
-        # the cohort's annotation, with allele frequencies from counts made on the device
-        coh_plan = snp.plan_for(obj, match_type, allele_check, same_strand, verbose, verbose_match)
-        assembly = coh_plan.assembly
-        geno_sampid = list(snp.sample_id)
-        mat = None
-    elif isinstance(snp, HlaBEDGeno):
-        # extension: the genotypes stay in the PLINK BED file; the SNP matching / strand check
-        # (R/HIBAG.R:550-686) runs on the annotation and the device decodes the file directly
-        from .snpmatch import plan_snps_for_predict
-        bed_plan = plan_snps_for_predict(obj, snp, snp.allele_freq, match_type, allele_check, same_strand,
-                                         verbose, verbose_match)
-        assembly = bed_plan.assembly
-        geno_sampid = list(snp.sample_id)
-        mat = None
-    elif not isinstance(snp, HlaSNPGeno):
-        g = np.asarray(snp)
-        if g.dtype.kind not in "iufb":
-            raise TypeError("is.numeric(snp) is not TRUE")
-        if g.ndim == 1:
-            if g.shape[0] != obj.n_snp:
-                raise ValueError("length(snp) == object$n.snp is not TRUE")
-            g = g.reshape(-1, 1)
-        elif g.ndim != 2 or g.shape[0] != obj.n_snp:
-            raise ValueError("nrow(snp) == object$n.snp is not TRUE")
-        geno_sampid = range(1, g.shape[1] + 1)
-        assembly = "auto-silent"
-        mat = g
-    else:
-        # the SNP matching / strand check (R/HIBAG.R:550-686) decides on the annotation; the rows are
-        # picked and flipped on the device while the genotypes are packed (hibag_hip_predict_mapped / _snp_major)
-        from .snpmatch import _row_afreq, plan_snps_for_predict
-        mat = np.asarray(snp.genotype)
-        if mat.ndim != 2:
-            raise ValueError("'snp$genotype' must be a matrix [n.snp, n.samp]")
-        map_plan = plan_snps_for_predict(obj, snp, lambda rows: _row_afreq(_as_integer(mat[rows])), match_type,
-                                         allele_check, same_strand, verbose, verbose_match)
-        assembly = map_plan.assembly
-        geno_sampid = snp.sample_id
-        if len(geno_sampid) != mat.shape[1]:
-            raise ValueError("length(snp$sample.id) == ncol(snp$genotype) is not TRUE")
-
-    n_samp = len(geno_sampid) if mat is None else mat.shape[1]
-    if verbose:
-        print(f"# of samples: {n_samp}", file=out)
-        print(f"Kernel target: {_kernel_info or 'hip'}", file=out)
+    r = _resolve_snp(obj, snp, "based on the averaged posterior probabilities" if vote_method == 1
+                     else "by voting from all individual classifiers", match_type, allele_check, same_strand, verbose, verbose_match)
+    geno_sampid, assembly, mat, sel, flip = r.sample_id, r.assembly, r.mat, r.sel, r.flip
 
     want_prob = type in ("prob", "response+prob")
     want_dosage = type != "response"
-    sel = flip = None
-    if map_plan is not None:
-        sel = None if map_plan.identity else map_plan.sel
-        flip = map_plan.flip if (map_plan.flip is not None and np.any(map_plan.flip)) else None
     devices = list(cl) if isinstance(cl, (list, tuple)) else None
     if devices is not None:
         # a device list: validated up front (an index out of range used to surface as ENODEV from deep inside replicate())
@@ -946,10 +897,10 @@ def hlaPredict(object: HlaAttrBagClass, snp: Union[HlaSNPGeno, HlaBEDGeno, np.nd
         bad = [d for d in devices if not isinstance(d, (int, np.integer)) or isinstance(d, bool) or not (0 <= int(d) < n_dev)]
         if not devices or bad:
             raise ValueError(f"'cl' must be a non-empty list of HIP device indices below {n_dev}: {cl!r}")
-        if coh_plan is not None:
+        if r.route == "cohort":
             raise ValueError("hlaPredict(cl = [devices]) takes a genotype matrix or an hlaSNPGenoClass; a resident cohort "
                              "(HlaDeviceCohort) lives on one device: predict there, with cl = False")
-        if bed_plan is not None:
+        if r.route == "bed":
             # the BED route decodes on ONE device (hibag_hip_predict_bed); silently ignoring the list would not be what
             # the caller asked for
             raise ValueError("hlaPredict(cl = [devices]) takes a genotype matrix or an hlaSNPGenoClass; for a lazily opened BED "
@@ -977,15 +928,8 @@ def hlaPredict(object: HlaAttrBagClass, snp: Union[HlaSNPGeno, HlaBEDGeno, np.nd
                 cache[key] = object.replicate(int(d))
             reps.append((int(d), cache[key]))
         rv = predict_multi([r for _, r in reps], genomat, vote_method, want_dosage=want_dosage, want_prob=want_prob)
-    elif coh_plan is not None:
-        rv = object.predict_cohort(snp, snp.rows_of(coh_plan.sel), coh_plan.flip, vote_method,
-                                   want_dosage=want_dosage, want_prob=want_prob)
-    elif bed_plan is not None:
-        col = np.where(bed_plan.sel >= 0, snp.bed_index[np.maximum(bed_plan.sel, 0)], -1)
-        rv = object.predict_bed(snp.bed_fn, snp.n_bed_samp, snp.n_bed_snp, col, bed_plan.flip, vote_method,
-                                want_dosage=want_dosage, want_prob=want_prob)
     else:
-        rv = _predict_matrix(object, mat, sel, flip, vote_method, want_dosage, want_prob)
+        rv = _predict_resolved(object, snp, r, "", (), vote_method, want_dosage=want_dosage, want_prob=want_prob)
 
     if type == "prob":
         res = rv["postprob"].T                # [n_cell, n_samp]: a view of the sample-major output = R's memory order
@@ -1001,8 +945,5 @@ def hlaPredict(object: HlaAttrBagClass, snp: Union[HlaSNPGeno, HlaBEDGeno, np.nd
                              postprob=(rv["postprob"].T if want_prob else None),
                              pair_names=_model_pair_names(object) if want_prob else [])
 
-    if na_cnt > 0:   # R/HIBAG.R:811-815
-        import warnings
-        warnings.warn(f"No prediction output{'s' if na_cnt > 1 else ''} for {na_cnt} individual"
-                      f"{'s' if na_cnt > 1 else ''} (possibly due to missing SNPs).")
+    _warn_no_prediction(na_cnt)
     return res

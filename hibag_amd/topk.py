@@ -9,15 +9,12 @@ call bit for bit."""
 
 from __future__ import annotations
 
-import sys
 from typing import List, Optional, Sequence
 
 import numpy as np
 
-from .bed import HlaBEDGeno
-from .cohort import HlaDeviceCohort
-from .hibag import HlaAlleleClass, HlaAttrBagClass, _as_integer, _kernel_info_text, topk_k
-from .model import NA_INTEGER, HlaSNPGeno
+from .hibag import HlaAlleleClass, HlaAttrBagClass, _predict_resolved, _resolve_snp, _warn_no_prediction, topk_k
+from .model import NA_INTEGER
 
 _VOTES = ("prob", "majority")
 
@@ -87,106 +84,15 @@ class HlaTopCalls:
         return f"HlaTopCalls(locus={self.locus!r}, {len(self.sample_id)} samples, k={self.k}, assembly={self.assembly!r})"
 
 
-def _list_matrix(model: HlaAttrBagClass, family: str, g: np.ndarray, sel: Optional[np.ndarray], flip: Optional[np.ndarray],
-                 args: tuple, vote_method: int) -> dict:
-    """``hibag._predict_matrix``'s routing for the list entries (``family`` "topk" or "draw": the ``predict_<family>*``
-    methods, ``args`` their own arguments -- ``(k,)`` or ``(n, seed)``): the entry follows the array's memory order, SNP
-    selection and allele flips happen on the device, no second matrix is built on the host."""
-    g = _as_integer(g)
-    if flip is not None and not np.any(flip):
-        flip = None
-    if g.flags.f_contiguous:
-        cohort = g.T                          # a view: [n_samp, cohort SNPs], C-contiguous
-        if sel is None and flip is None:
-            return getattr(model, f"predict_{family}")(cohort, *args, vote_method)
-        if sel is None:
-            sel = np.arange(model.obj.n_snp, dtype=np.int32)
-        return getattr(model, f"predict_{family}_mapped")(cohort, sel, flip, *args, vote_method)
-    if not g.flags.c_contiguous:
-        g = np.ascontiguousarray(g)
-    return getattr(model, f"predict_{family}_snp_major")(g, sel, flip, *args, vote_method)
-
-
 def _predict_lists(model: HlaAttrBagClass, snp, family: str, args: tuple, what: str, vote_method: int, allele_check: bool,
                    match_type: str, same_strand: bool, verbose: bool, verbose_match: bool):
-    """What ``hlaPredictTopK`` and ``hlaPredictDraws`` share: the verbose header (``what``: the line that says what is
-    reported per sample), ``snp`` resolved to a route -- a resident cohort, a lazily opened BED file, a numeric matrix or
-    vector, an :class:`HlaSNPGeno` with SNP matching -- the call of that route's ``predict_<family>*`` entry, and the
-    "No prediction output" warning.  Returns ``(outputs, sample ids, assembly)``."""
-    obj = model.obj
-    out = sys.stdout
-
-    if verbose:
-        s = list(obj.hla_allele)
-        if len(s) > 3:
-            s = s[:3] + ["..."]
-        n_c = len(obj.classifiers)
-        print(f"HIBAG model for HLA-{obj.hla_locus}:\n    {n_c} individual classifier{'s' if n_c > 1 else ''}\n"
-              f"    {len(obj.snp_id)} SNPs\n    {obj.n_hla} unique HLA alleles: {', '.join(s)}", file=out)
-        print("Prediction:\n    " + what, file=out)
-
-    bed_plan = map_plan = coh_plan = None
-    if isinstance(snp, HlaDeviceCohort):
-        coh_plan = snp.plan_for(obj, match_type, allele_check, same_strand, verbose, verbose_match)
-        assembly = coh_plan.assembly
-        geno_sampid = list(snp.sample_id)
-        mat = None
-    elif isinstance(snp, HlaBEDGeno):
-        from .snpmatch import plan_snps_for_predict
-        bed_plan = plan_snps_for_predict(obj, snp, snp.allele_freq, match_type, allele_check, same_strand,
-                                         verbose, verbose_match)
-        assembly = bed_plan.assembly
-        geno_sampid = list(snp.sample_id)
-        mat = None
-    elif not isinstance(snp, HlaSNPGeno):
-        g = np.asarray(snp)
-        if g.dtype.kind not in "iufb":
-            raise TypeError("is.numeric(snp) is not TRUE")
-        if g.ndim == 1:
-            if g.shape[0] != obj.n_snp:
-                raise ValueError("length(snp) == object$n.snp is not TRUE")
-            g = g.reshape(-1, 1)
-        elif g.ndim != 2 or g.shape[0] != obj.n_snp:
-            raise ValueError("nrow(snp) == object$n.snp is not TRUE")
-        geno_sampid = range(1, g.shape[1] + 1)
-        assembly = "auto-silent"
-        mat = g
-    else:
-        from .snpmatch import _row_afreq, plan_snps_for_predict
-        mat = np.asarray(snp.genotype)
-        if mat.ndim != 2:
-            raise ValueError("'snp$genotype' must be a matrix [n.snp, n.samp]")
-        map_plan = plan_snps_for_predict(obj, snp, lambda rows: _row_afreq(_as_integer(mat[rows])), match_type,
-                                         allele_check, same_strand, verbose, verbose_match)
-        assembly = map_plan.assembly
-        geno_sampid = snp.sample_id
-        if len(geno_sampid) != mat.shape[1]:
-            raise ValueError("length(snp$sample.id) == ncol(snp$genotype) is not TRUE")
-
-    n_samp = len(geno_sampid) if mat is None else mat.shape[1]
-    if verbose:
-        print(f"# of samples: {n_samp}", file=out)
-        print(f"Kernel target: {_kernel_info_text() or 'hip'}", file=out)
-
-    if coh_plan is not None:
-        rv = getattr(model, f"predict_{family}_cohort")(snp, snp.rows_of(coh_plan.sel), coh_plan.flip, *args, vote_method)
-    elif bed_plan is not None:
-        col = np.where(bed_plan.sel >= 0, snp.bed_index[np.maximum(bed_plan.sel, 0)], -1)
-        rv = getattr(model, f"predict_{family}_bed")(snp.bed_fn, snp.n_bed_samp, snp.n_bed_snp, col, bed_plan.flip, *args,
-                                                     vote_method)
-    else:
-        sel = flip = None
-        if map_plan is not None:
-            sel = None if map_plan.identity else map_plan.sel
-            flip = map_plan.flip if (map_plan.flip is not None and np.any(map_plan.flip)) else None
-        rv = _list_matrix(model, family, mat, sel, flip, args, vote_method)
-
-    na_cnt = int(np.count_nonzero((rv["h1"][:, 0] == NA_INTEGER) | (rv["h2"][:, 0] == NA_INTEGER)))
-    if na_cnt > 0:   # R/HIBAG.R:811-815
-        import warnings
-        warnings.warn(f"No prediction output{'s' if na_cnt > 1 else ''} for {na_cnt} individual"
-                      f"{'s' if na_cnt > 1 else ''} (possibly due to missing SNPs).")
-    return rv, list(geno_sampid), assembly
+    """What ``hlaPredictTopK`` and ``hlaPredictDraws`` share: ``hlaPredict``'s resolution of ``snp`` to a route (with its verbose
+    header; ``what``: the line that says what is reported per sample), the call of that route's ``predict_<family>*`` entry,
+    and the "No prediction output" warning.  Returns ``(outputs, sample ids, assembly)``."""
+    r = _resolve_snp(model.obj, snp, what, match_type, allele_check, same_strand, verbose, verbose_match)
+    rv = _predict_resolved(model, snp, r, family, args, vote_method)
+    _warn_no_prediction(int(np.count_nonzero((rv["h1"][:, 0] == NA_INTEGER) | (rv["h2"][:, 0] == NA_INTEGER))))
+    return rv, list(r.sample_id), r.assembly
 
 
 def hlaPredictTopK(model: HlaAttrBagClass, snp, k: int = 3, vote: str = "prob", allele_check: bool = True,

@@ -175,3 +175,105 @@ def test_hlaPredict_takes_either_memory_order_without_copies(hib, oracle, hapmap
     with pytest.warns(UserWarning, match="No prediction outputs for 3 individuals"):
         r = hib.hlaPredict(dev, none, type="response", verbose=False)
     assert r.allele1 == [None] * 3 and r.allele2 == [None] * 3
+
+
+@pytest.fixture(scope="module")
+def crossing_case(oracle, tmp_path_factory):
+    """One cohort of 200 samples in every form a route takes, and the oracle's outputs for it (computed once).  The cohort
+    has its own SNPs in its own order, lacks a tenth of the model's and has a third of the rest on the other strand, so the
+    effective model-order matrix is ``Gm``; the sample-major route takes ``Gm`` itself."""
+    from conftest import write_bed
+    from draws_reference import draws_from_postprob
+    from hibag_amd import synth
+    from topk_reference import select
+    model, founders, af = synth.make_model("hla-a-small", seed=51)
+    n, S, lead = 200, model.n_snp, 24
+    G, _ = synth.make_samples(founders, af, n, seed=52)
+    G[[0, 77, n - 1]] = NA
+    rng = np.random.default_rng(53)
+    have = rng.random(S) < 0.9
+    flip = ((rng.random(S) < 0.3) & have).astype(np.int32)
+    Gm = G.copy()
+    Gm[:, ~have] = NA
+    n_geno = 2 * S
+    cols, cohorts = {}, {}
+    for case in ("scattered", "consecutive"):
+        col = np.full(S, -1, np.int32)
+        col[have] = rng.choice(n_geno, int(have.sum()), replace=False) if case == "scattered" else 11 + np.arange(int(have.sum()))
+        cohort = rng.integers(0, 3, (n_geno, n)).astype(np.int32)
+        for k in np.where(have)[0]:
+            g = G[:, k]
+            cohort[col[k]] = np.where((g >= 0) & (g <= 2) & (flip[k] != 0), 2 - g, g)
+        cols[case], cohorts[case] = col, cohort
+    tmp = tmp_path_factory.mktemp("crossing")
+    beds = {mode: str(write_bed(str(tmp / f"mode{mode}.bed"), cohorts["scattered"], mode)) for mode in (0, 1)}
+    # the resident cohort holds `lead` samples in front of the 200: the calls window it with first = lead
+    resident = np.concatenate([rng.integers(0, 3, (n_geno, lead)).astype(np.int32), cohorts["scattered"]], axis=1)
+    want = oracle.predict(oracle.flatten(model), Gm, vote_method=1)
+    k, n_draw, seed, sample0 = 3, 5, 20261018, 1000
+    return dict(model=model, n=n, lead=lead, n_geno=n_geno, Gm=Gm, flip=flip, cols=cols, cohorts=cohorts, beds=beds,
+                resident=resident, want=want, k=k, n_draw=n_draw, seed=seed, sample0=sample0,
+                topk=select(want["postprob"], k, model.n_hla),
+                draws=draws_from_postprob(want["postprob"], n_draw, seed, sample0, model.n_hla))
+
+
+@pytest.mark.parametrize("slice_env", [None, "64"])
+def test_every_route_with_every_output_set(hib, crossing_case, monkeypatch, slice_env):
+    """Routes crossed with output sets, unsliced and on the pipelined path: with ``HIBAG_STAGED_SLICE=64`` the 200 samples
+    go down as slices of 64, 64, 64 and 8, so both double buffers are used twice, slices 0 and 1 are drained while 2 and 3
+    run, and the last slice ends inside a wavefront.  Every plain output equals the oracle's on the effective model-order
+    matrix exactly; the lists equal the reference selection / the reference draws from the oracle's posterior; an array that
+    is not asked for is not touched."""
+    import ctypes as C
+    import os
+    import hibag_amd as hb
+    from draws_reference import assert_draws_equal
+    from hibag_amd import _lib
+    from topk_reference import assert_topk_equal
+    if slice_env:
+        monkeypatch.setenv("HIBAG_STAGED_SLICE", slice_env)
+    c = crossing_case
+    model, n, want, flip = c["model"], c["n"], c["want"], c["flip"]
+    L = _lib.lib()
+    q = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+    m = hb.hlaModelFromObj(model)
+    n_res = c["lead"] + n
+    snp = hb.HlaSNPGeno(genotype=c["resident"], sample_id=[str(i) for i in range(n_res)], snp_id=[f"r{i}" for i in range(c["n_geno"])],
+                        snp_position=np.arange(c["n_geno"], dtype=np.float64), snp_allele=["A/G"] * c["n_geno"], assembly="hg19")
+    sm = np.ascontiguousarray(c["cohorts"]["scattered"].T)                   # the cohort's own matrix, sample-major
+    with hb.HlaDeviceCohort(snp) as coh:
+        window = dict(first=c["lead"], count=n)
+        # route: (the wrapper's method suffix, its arguments, its keywords, the C entry's suffix, the C arguments before vote_method)
+        routes = {
+            "sample-major": ("", (c["Gm"],), {}, "", (q(c["Gm"]), n)),
+            "mapped": ("_mapped", (sm, c["cols"]["scattered"], flip), {}, "_mapped",
+                       (q(sm), n, c["n_geno"], q(c["cols"]["scattered"]), q(flip))),
+            "resident cohort": ("_cohort", (coh, c["cols"]["scattered"], flip), window, "_cohort",
+                                (coh.handle, c["lead"], n, q(c["cols"]["scattered"]), q(flip))),
+        }
+        for case in ("consecutive", "scattered"):
+            g, col = c["cohorts"][case], c["cols"][case]
+            routes["SNP-major, " + case] = ("_snp_major", (g, col, flip), {}, "_snp_major", (q(g), n, n, c["n_geno"], q(col), q(flip)))
+        for mode, fn in c["beds"].items():
+            routes[f"BED mode {mode}"] = ("_bed", (fn, n, c["n_geno"], c["cols"]["scattered"], flip), {}, "_bed",
+                                          (os.fsencode(fn), n, c["n_geno"], q(c["cols"]["scattered"]), q(flip)))
+        assert len(routes) == 7
+        P, pad, sentinel = model.n_cell, 64, -7.5
+        for name, (suffix, args, kw, c_suffix, head) in routes.items():
+            plain = getattr(m, "predict" + (suffix or "_raw"))
+            for want_dosage, want_prob in ((False, False), (True, False), (True, True)):
+                got = plain(*args, 1, want_dosage=want_dosage, want_prob=want_prob, **kw)
+                keys = KEYS[:4] + (("dosage",) if want_dosage else ()) + (("postprob",) if want_prob else ())
+                assert tuple(got) == keys, name                              # (what is not asked for does not exist)
+                same(got, want, keys)
+            # the posterior matrix alone, through the C entry: NULL for the others, the memory around the matrix stays as it was
+            buf = np.full(pad + n * P + pad, sentinel)
+            rc = getattr(L, "hibag_hip_predict" + c_suffix)(m.handle, *head, 1, None, None, None, None, None, q(buf[pad:]))
+            assert rc == 0, (name, L.hibag_hip_last_error())
+            assert np.array_equal(buf[pad:pad + n * P].reshape(n, P), want["postprob"], equal_nan=True), name
+            assert np.all(buf[:pad] == sentinel) and np.all(buf[pad + n * P:] == sentinel), name
+            top = getattr(m, "predict_topk" + suffix)(*args, c["k"], 1, **kw)
+            assert_topk_equal(top, dict(c["topk"], matching=want["matching"]), name)
+            drawn = getattr(m, "predict_draw" + suffix)(*args, c["n_draw"], c["seed"], 1, sample0=c["sample0"], **kw)
+            assert_draws_equal(drawn, dict(c["draws"], matching=want["matching"]), name)
+    assert m.status() == 0 and m.handover_faults() == 0
