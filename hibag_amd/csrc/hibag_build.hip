@@ -30,11 +30,15 @@
 
 int hibag_selected_device();      // hibag_api.hip
 #include "hibag_plugin.h"
+#include "hibag_build_prof.h"
 #include "hibag_combine.h"
 
 namespace {
 
 constexpr int NW = 4;                       // 32-bit words of a 128-SNP string
+
+// A buffer that is replaced by a larger one when it is outgrown: device memory (reserve) or pinned host memory (reserve_pinned)
+struct Buf { void *p = nullptr; size_t cap = 0; };
 
 struct BuildState {
 	bool active = false;
@@ -45,27 +49,35 @@ struct BuildState {
 	int n_haplo = 0, n_snp = 0;
 	std::vector<int> true1, true2;          // true allele pair per sample, a1 <= a2
 	bool evaluated = false;
-	std::vector<int> best1, best2;
-	std::vector<double> postprob;
-	// device
-	void *d_hb = nullptr, *d_hf = nullptr, *d_start = nullptr, *d_planes = nullptr, *d_true = nullptr,
-		*d_best = nullptr, *d_post = nullptr, *d_tab = nullptr, *d_match = nullptr, *d_batch = nullptr;
-	void *h_stage = nullptr;                // pinned host staging of the batched evaluation
-	size_t cap_h = 0, cap_s = 0, cap_match = 0, cap_batch = 0, cap_stage = 0;
-	// small uploads of the pair-list step: staged in pinned memory and sent asynchronously (a pageable hipMemcpy is a
-	// synchronisation each; a growth step made a dozen of them)
+	std::vector<int> best;                  // [2][n_pad] _BestGuess per sample
+	std::vector<double> postprob;           // [n_pad]
+	// device: sized by build_init ...
+	void *d_start = nullptr, *d_planes = nullptr, *d_true = nullptr, *d_best = nullptr, *d_post = nullptr, *d_tab = nullptr;
+	void *d_geno8 = nullptr; int geno8_snps = 0;   // the cohort's genotype codes [n_snp][n_pad] (hibag_build_set_genotypes), or null
+	// ... and grown on demand: haplotype words and, behind them, frequencies (d_hf points into it); the pair-list step's arena;
+	// the pairs of its two-operation form
+	Buf hb, match, pairs;
+	void *d_hf = nullptr;
 	// the batched evaluation runs in up to two slots at a time (hibag_build_eval_launch / _collect): while the device scores
 	// one half of a growth step's candidates the host threads still fit the other half
 	struct Slot {
-		void *d = nullptr, *h = nullptr; size_t cap_d = 0, cap_h = 0;
-		int n_cand = 0, np = 0; size_t o_best = 0, o_post = 0;
-		double t_launch = 0;
+		Buf d, h;                                                   // device arena and its pinned staging area
+		int n_cand = 0; size_t o_best = 0, o_post = 0;              // what collect reads: set once the slot's operation has run
 	} slot[2];
-	void *h_up = nullptr; size_t cap_up = 0, up_at = 0;
+	// small uploads of the pair-list step: staged in pinned memory and sent asynchronously (a pageable hipMemcpy is a
+	// synchronisation each; a growth step made a dozen of them)
+	Buf up; size_t up_at = 0;
 	std::vector<void *> h_retired;          // staging areas outgrown while an operation was being put together (freed at the next rewind)
-	void *h_dn = nullptr; size_t cap_dn = 0; // pinned landing area of the pair-list step's read-backs
-	void *d_geno8 = nullptr; int geno8_snps = 0;   // the cohort's genotype codes [n_snp][n_pad] (hibag_build_set_genotypes), or null
-	void *d_pairs = nullptr; size_t cap_pairs = 0;
+	Buf dn;                                 // pinned landing area of the pair-list step's read-backs
+
+	// every pointer above (hibag_build_done resets the rest with `g = BuildState()`); never throws
+	void release()
+	{
+		for (void *p : {d_start, d_planes, d_true, d_best, d_post, d_tab, d_geno8, hb.p, match.p, pairs.p, slot[0].d.p, slot[1].d.p})
+			if (p) (void)hipFree(p);
+		for (void *p : {slot[0].h.p, slot[1].h.p, up.p, dn.p}) if (p) (void)hipHostFree(p);
+		for (void *p : h_retired) (void)hipHostFree(p);
+	}
 };
 // One state per HOST THREAD (thread_local), and every copy / launch of this file on the calling thread's own default
 // stream (the file is compiled with -fgpu-default-stream=per-thread): several trainers of one process -- each driven by its
@@ -88,6 +100,25 @@ thread_local HibagOp *g_op = nullptr;
 
 void dev_free(void *&p) { if (p) (void)hipFree(p); p = nullptr; }
 
+void reserve(Buf &b, size_t bytes, const char *what)
+{
+	if (bytes <= b.cap && b.p) return;
+	dev_free(b.p);
+	bytes = std::max(bytes, b.cap + b.cap / 2);  // geometric growth: a free + allocation of ~100 MB costs about a millisecond
+	HIP_OK(hipMalloc(&b.p, bytes), what);
+	b.cap = bytes;
+}
+
+// (what the old area held is gone: for areas that are written anew before each use)
+void reserve_pinned(Buf &b, size_t bytes, size_t grow_to, const char *what)
+{
+	if (bytes <= b.cap) return;
+	if (b.p) (void)hipHostFree(b.p);
+	b.p = nullptr; b.cap = 0;
+	HIP_OK(hipHostMalloc(&b.p, grow_to, hipHostMallocDefault), what);
+	b.cap = grow_to;
+}
+
 // Host -> device through the pinned staging area, asynchronously on the null stream (in order with the kernels that
 // follow).  The area is rewound by upload_rewind() at a point where everything sent before has been consumed.
 void upload_rewind()
@@ -99,42 +130,30 @@ void upload_rewind()
 void upload(void *dst, const void *src, size_t bytes, const char *what)
 {
 	if (bytes == 0) return;
-	if (g.up_at + bytes > g.cap_up) {
+	if (g.up_at + bytes > g.up.cap) {
 		// (rare: grow; what is in flight from the old area must land first -- or, while an operation is being put together,
 		// the old area stays alive until that operation has run: its recorded copies point into it)
 		if (!g_op) HIP_OK(hipStreamSynchronize(0), what);
-		if (g.h_up) { if (g_op) g.h_retired.push_back(g.h_up); else (void)hipHostFree(g.h_up); }
-		g.h_up = nullptr;
-		g.cap_up = std::max<size_t>((g.up_at + bytes) * 2, 1 << 20);
-		HIP_OK(hipHostMalloc(&g.h_up, g.cap_up, hipHostMallocDefault), "hipHostMalloc(upload staging)");
+		if (g.up.p) { if (g_op) g.h_retired.push_back(g.up.p); else (void)hipHostFree(g.up.p); }
+		g.up.p = nullptr;
+		g.up.cap = std::max<size_t>((g.up_at + bytes) * 2, 1 << 20);
+		HIP_OK(hipHostMalloc(&g.up.p, g.up.cap, hipHostMallocDefault), "hipHostMalloc(upload staging)");
 		g.up_at = 0;
 	}
-	char *at = (char *)g.h_up + g.up_at;
+	char *at = (char *)g.up.p + g.up_at;
 	memcpy(at, src, bytes);
 	g.up_at += (bytes + 63) & ~(size_t)63;
 	if (g_op) g_op->up.push_back(HibagCopy{dst, at, bytes});
 	else HIP_OK(hipMemcpyAsync(dst, at, bytes, hipMemcpyHostToDevice, 0), what);
 }
 
-void *landing(size_t bytes)
-{
-	if (bytes > g.cap_dn) {
-		if (g.h_dn) (void)hipHostFree(g.h_dn);
-		g.h_dn = nullptr; g.cap_dn = 0;
-		HIP_OK(hipHostMalloc(&g.h_dn, bytes * 2 + 4096, hipHostMallocDefault), "hipHostMalloc(read-back staging)");
-		g.cap_dn = bytes * 2 + 4096;
-	}
-	return g.h_dn;
-}
+void *landing(size_t bytes) { reserve_pinned(g.dn, bytes, bytes * 2 + 4096, "hipHostMalloc(read-back staging)"); return g.dn.p; }
 
-void reserve(void *&p, size_t &cap, size_t bytes, const char *what)
-{
-	if (bytes <= cap && p) return;
-	dev_free(p);
-	bytes = std::max(bytes, cap + cap / 2);      // geometric growth: a free + allocation of ~100 MB costs about a millisecond
-	HIP_OK(hipMalloc(&p, bytes), what);
-	cap = bytes;
-}
+// While one of these lives, upload() records its copies into `op` instead of issuing them.
+struct Recording {
+	explicit Recording(HibagOp *op) { g_op = op; }
+	~Recording() { g_op = nullptr; }
+};
 
 // ---------------------------------------------------------------------------
 // device side
@@ -558,76 +577,103 @@ __global__ __launch_bounds__(HIBAG_WAVE) void k_build_match(HibagMulti<MatchView
 // ---------------------------------------------------------------------------
 // host side
 
-void upload_haplo(const PluginHaplotype haplo[], int n_haplo, int n_snp, bool alleles_from_aux,
-	const size_t *len_per_hla_or_null)
+// ---- the packers: one per input, for build_set_haplo_geno, build_haplomatch and the batched evaluation alike ----
+// 32-bit word w of a 128-SNP string kept as two 64-bit words (inst/include/LibHLA_ext.h:240-255)
+inline uint32_t word32(const int64_t packed[2], int w) { return (uint32_t)((uint64_t)packed[w >> 1] >> (32 * (w & 1))); }
+
+// Haplotype i's word w to dst[w * stride + at + i], its frequency to freq_or_null[i].
+void pack_haplotypes(uint32_t *dst, size_t stride, size_t at, double *freq_or_null, const PluginHaplotype haplo[], size_t n,
+	int nw, int n_snp)
 {
-	const int nh = g.n_hla;
-	g.n_haplo = n_haplo; g.n_snp = n_snp;
-	const int nw = std::max(1, (n_snp + 31) / 32);
-	std::vector<uint32_t> hb((size_t)NW * std::max(n_haplo, 1), 0);
-	std::vector<double> hf(std::max(n_haplo, 1), 0.0);
-	std::vector<int> start(nh + 1, 0);
-	for (int i = 0; i < n_haplo; i++) {
-		for (int w = 0; w < nw; w++) {
-			uint32_t v = (uint32_t)((uint64_t)haplo[i].packed[w >> 1] >> (32 * (w & 1)));
-			const int lo = 32 * w;                       // clear bits >= n_snp (uninitialised in the reference, src/LibHLA.cpp:287-292)
-			if (n_snp < lo + 32) v &= (n_snp <= lo) ? 0u : ((1u << (n_snp - lo)) - 1);
-			hb[(size_t)w * n_haplo + i] = v;
-		}
-		hf[i] = haplo[i].freq;
-		if (alleles_from_aux) {
-			const int a = haplo[i].aux.hla_allele;
-			if (a < 0 || a >= nh) build_throw("haplotype with an invalid HLA allele index");
-			start[a + 1]++;
-		}
+	// the tail mask: bits >= n_snp are cleared (uninitialised in the reference, src/LibHLA.cpp:287-292)
+	uint32_t keep[NW];
+	for (int w = 0, lo = 0; w < nw; w++, lo += 32) keep[w] = n_snp >= lo + 32 ? 0xFFFFFFFFu : n_snp <= lo ? 0u : (1u << (n_snp - lo)) - 1;
+	for (size_t i = 0; i < n; i++) {
+		for (int w = 0; w < nw; w++) dst[(size_t)w * stride + at + i] = word32(haplo[i].packed, w) & keep[w];
+		if (freq_or_null) freq_or_null[i] = haplo[i].freq;
 	}
-	if (len_per_hla_or_null) for (int h = 0; h < nh; h++) start[h + 1] = (int)len_per_hla_or_null[h];
-	for (int h = 0; h < nh; h++) start[h + 1] += start[h];
-	if (start[nh] != n_haplo) build_throw("haplotype counts per allele do not add up");
-	reserve(g.d_hb, g.cap_h, (size_t)NW * std::max(n_haplo, 1) * 4 + std::max(n_haplo, 1) * 8 + 64, "hipMalloc(haplotypes)");
-	g.d_hf = (char *)g.d_hb + (((size_t)NW * std::max(n_haplo, 1) * 4 + 7) & ~(size_t)7);
-	upload(g.d_hb, hb.data(), (size_t)nw * std::max(n_haplo, 1) * 4, "copy haplotypes");
-	upload(g.d_hf, hf.data(), hf.size() * 8, "copy frequencies");
-	upload(g.d_start, start.data(), (nh + 1) * sizeof(int), "copy allele starts");
 }
 
-void upload_geno(const PluginGenotype geno[])
+constexpr uint32_t PAD_S1 = 0u, PAD_S2 = 0xFFFFFFFFu;         // padding lanes: all missing
+
+// The genotypes' two bit planes [2 * NW][np]: S1 words, then S2 words (branch-free per word: the compiler vectorises it)
+void pack_planes(uint32_t *planes, int np, const PluginGenotype geno[], int n)
 {
-	const int n = g.n_sample, np = g.n_pad, nh = g.n_hla;
-	std::vector<uint32_t> planes((size_t)2 * NW * np);
-	std::vector<int> true_cell(np, -1);
-	g.true1.assign(n, 0); g.true2.assign(n, 0);
-	for (int w = 0; w < NW; w++)
-		for (int s = 0; s < np; s++) {                     // padding lanes: all missing
-			planes[(size_t)w * np + s] = s < n ? (uint32_t)((uint64_t)geno[s].snp1[w >> 1] >> (32 * (w & 1))) : 0u;
-			planes[(size_t)(NW + w) * np + s] = s < n ? (uint32_t)((uint64_t)geno[s].snp2[w >> 1] >> (32 * (w & 1))) : 0xFFFFFFFFu;
+	for (int w = 0; w < NW; w++) {
+		uint32_t *p1 = planes + (size_t)w * np, *p2 = planes + (size_t)(NW + w) * np;
+		for (int s = 0; s < n; s++) {
+			p1[s] = word32(geno[s].snp1, w);
+			p2[s] = word32(geno[s].snp2, w);
 		}
+		for (int s = n; s < np; s++) { p1[s] = PAD_S1; p2[s] = PAD_S2; }
+	}
+}
+
+// g.true1 / g.true2: the samples' true alleles, a1 <= a2; true_cell_or_null[n_pad]: the pairs' posterior indices, -1 on padding
+void set_true_pairs(const PluginGenotype geno[], int *true_cell_or_null)
+{
+	const int n = g.n_sample, nh = g.n_hla;
+	g.true1.resize(n); g.true2.resize(n);
 	for (int s = 0; s < n; s++) {
 		int a1 = geno[s].hla1, a2 = geno[s].hla2;
 		if (a1 > a2) std::swap(a1, a2);                    // src/LibHLA.cpp:1710, :1863-1868
 		if (a1 < 0 || a2 >= nh) build_throw("genotype with an invalid true HLA pair");
 		g.true1[s] = a1; g.true2[s] = a2;
-		true_cell[s] = a2 + a1 * (2 * nh - a1 - 1) / 2;    // src/LibHLA.cpp:1712
+		if (true_cell_or_null) true_cell_or_null[s] = a2 + a1 * (2 * nh - a1 - 1) / 2;    // src/LibHLA.cpp:1712
 	}
+	if (true_cell_or_null) for (int s = n; s < g.n_pad; s++) true_cell_or_null[s] = -1;
+}
+
+// count[a + 1] += the haplotypes of allele a (aux.hla_allele): a prefix sum away from the alleles' starts
+void count_alleles(int *count, const PluginHaplotype haplo[], int n)
+{
+	for (int i = 0; i < n; i++) {
+		const int a = haplo[i].aux.hla_allele;
+		if (a < 0 || a >= g.n_hla) build_throw("haplotype with an invalid HLA allele index");
+		count[a + 1]++;
+	}
+}
+
+// A haplotype list and the cohort's genotypes into the evaluation's buffers: what evaluate() and the two-operation pair lists
+// read.  The alleles' list lengths from `len_per_hla`, or, where that is null, counted from aux.hla_allele.
+void upload_lists(const PluginHaplotype haplo[], int n_haplo, int n_snp, const size_t *len_per_hla, const PluginGenotype geno[])
+{
+	const int nh = g.n_hla, np = g.n_pad;
+	g.n_haplo = n_haplo; g.n_snp = n_snp;
+	const int nw = std::max(1, (n_snp + 31) / 32);
+	const size_t Hs = std::max(n_haplo, 1);
+	std::vector<uint32_t> hb((size_t)NW * Hs, 0), planes((size_t)2 * NW * np);
+	std::vector<double> hf(Hs, 0.0);
+	std::vector<int> start(nh + 1, 0), true_cell(np);
+	pack_haplotypes(hb.data(), n_haplo, 0, hf.data(), haplo, n_haplo, nw, n_snp);
+	if (len_per_hla) for (int h = 0; h < nh; h++) start[h + 1] = (int)len_per_hla[h];
+	else count_alleles(start.data(), haplo, n_haplo);
+	for (int h = 0; h < nh; h++) start[h + 1] += start[h];
+	if (start[nh] != n_haplo) build_throw("haplotype counts per allele do not add up");
+	reserve(g.hb, (size_t)NW * Hs * 4 + Hs * 8 + 64, "hipMalloc(haplotypes)");
+	g.d_hf = (char *)g.hb.p + (((size_t)NW * Hs * 4 + 7) & ~(size_t)7);
+	upload(g.hb.p, hb.data(), (size_t)nw * Hs * 4, "copy haplotypes");
+	upload(g.d_hf, hf.data(), hf.size() * 8, "copy frequencies");
+	upload(g.d_start, start.data(), (nh + 1) * sizeof(int), "copy allele starts");
+	pack_planes(planes.data(), np, geno, g.n_sample);
+	set_true_pairs(geno, true_cell.data());
 	upload(g.d_planes, planes.data(), planes.size() * 4, "copy genotypes");
 	upload(g.d_true, true_cell.data(), np * sizeof(int), "copy true pairs");
+	g.evaluated = false;
 }
 
 void evaluate()
 {
 	if (g.evaluated) return;
 	BuildView V{g.n_hla, g.n_sample, g.n_pad, g.n_haplo, std::max(1, (g.n_snp + 31) / 32),
-		(const uint32_t *)g.d_hb, (const double *)g.d_hf, (const int *)g.d_start, (const uint32_t *)g.d_planes,
+		(const uint32_t *)g.hb.p, (const double *)g.d_hf, (const int *)g.d_start, (const uint32_t *)g.d_planes,
 		(const int *)g.d_true, (const double *)g.d_tab, (int *)g.d_best, (double *)g.d_post};
 	hipLaunchKernelGGL(k_build_eval, dim3(g.n_pad / HIBAG_WAVE), dim3(HIBAG_WAVE), 0, 0, V);
 	HIP_OK(hipGetLastError(), "k_build_eval");
-	std::vector<int> best((size_t)2 * g.n_pad);
-	std::vector<double> post(g.n_pad);
-	HIP_OK(hipMemcpy(best.data(), g.d_best, best.size() * sizeof(int), hipMemcpyDeviceToHost), "read best guesses");
-	HIP_OK(hipMemcpy(post.data(), g.d_post, post.size() * sizeof(double), hipMemcpyDeviceToHost), "read posteriors");
-	g.best1.assign(best.begin(), best.begin() + g.n_sample);
-	g.best2.assign(best.begin() + g.n_pad, best.begin() + g.n_pad + g.n_sample);
-	g.postprob.assign(post.begin(), post.begin() + g.n_sample);
+	g.best.resize((size_t)2 * g.n_pad);
+	g.postprob.resize(g.n_pad);
+	HIP_OK(hipMemcpy(g.best.data(), g.d_best, g.best.size() * sizeof(int), hipMemcpyDeviceToHost), "read best guesses");
+	HIP_OK(hipMemcpy(g.postprob.data(), g.d_post, g.postprob.size() * sizeof(double), hipMemcpyDeviceToHost), "read posteriors");
 	g.evaluated = true;
 }
 
@@ -638,6 +684,290 @@ int compare_hla(int p1, int p2, int t1, int t2)
 	if (p1 == t1 || p1 == t2) { cnt = 1; if (p1 == t1) t1 = -1; else t2 = -1; }
 	if (p2 == t1 || p2 == t2) cnt++;
 	return cnt;
+}
+
+// ---- build_haplomatch: its result and its two forms ----
+// build_haplomatch's result: a malloc()ed buffer the host free()s -- buf[0] = 2 * total, then the pairs
+uint32_t *match_result(size_t total, const uint32_t *pairs, size_t &out_n)
+{
+	uint32_t *buf = (uint32_t *)malloc((1 + 2 * total) * sizeof(uint32_t));
+	if (!buf) build_throw("out of memory");
+	buf[0] = (uint32_t)(2 * total);
+	if (total > 0) memcpy(buf + 1, pairs, 2 * total * sizeof(uint32_t));
+	out_n = 1 + 2 * total;
+	return buf;
+}
+
+// ONE operation where an upper bound on the number of pairs is small (it always is for the driver's growth steps: the
+// bound is the number of candidate pairs, a few per in-bag sample): the step's inputs in one copy into one arena, both
+// passes back to back -- the second finds its offsets from the first's counts on the device --, counts and pairs back in
+// one copy sized by the bound.  Two device round trips and a dozen copies less per growth step.
+// (g.n_haplo / g.n_snp / g.hb describe what build_set_haplo_geno uploaded for evaluate(): this path has an arena of its own
+// and leaves them alone)
+uint32_t *match_fused(const PluginHaplotype haplo[], const size_t n_haplo[], size_t H, int n_snp, const PluginGenotype geno[],
+	size_t bound, size_t &out_n)
+{
+	const int nib = (int)g.inbag.size(), nh = g.n_hla, np = g.n_pad;
+	const int nw = std::max(1, (n_snp + 31) / 32);
+	const size_t Hs = std::max<size_t>(H, 1);
+	// the arena, in 4-byte units: inputs [hb | start | planes | samp | a1 | a2], scratch [min_d], results [count | pairs]
+	const size_t o_hb = 0, o_start = o_hb + (size_t)nw * Hs, o_planes = o_start + (nh + 1), o_samp = o_planes + (size_t)2 * NW * np,
+		o_a1 = o_samp + nib, o_a2 = o_a1 + nib, in_end = o_a2 + nib, o_min = in_end, o_cnt = o_min + nib, o_pairs = o_cnt + nib,
+		end = o_pairs + 2 * bound;
+	std::vector<uint32_t> blob(in_end, 0);
+	pack_haplotypes(&blob[o_hb], Hs, 0, nullptr, haplo, H, nw, n_snp);
+	for (int h = 0; h < nh; h++) blob[o_start + h + 1] = blob[o_start + h] + (uint32_t)n_haplo[h];
+	pack_planes(&blob[o_planes], np, geno, g.n_sample);
+	for (int k = 0; k < nib; k++) {
+		blob[o_samp + k] = (uint32_t)g.inbag[k];
+		blob[o_a1 + k] = (uint32_t)g.true1[g.inbag[k]];
+		blob[o_a2 + k] = (uint32_t)g.true2[g.inbag[k]];
+	}
+	reserve(g.match, end * 4 + 64, "hipMalloc(match)");
+	uint32_t *const d = (uint32_t *)g.match.p;
+	HibagOp op;
+	{
+		Recording recording(&op);
+		upload(d, blob.data(), in_end * 4, "copy match inputs");
+	}
+	const MatchView V{(int)Hs, nw, np, d + o_hb, (const int *)(d + o_start), d + o_planes, (const int *)(d + o_samp),
+		(const int *)(d + o_a1), (const int *)(d + o_a2), (int *)(d + o_min), (int *)(d + o_cnt), nullptr, d + o_pairs, nib};
+	op.kind = HIBAG_OP_MATCH; op.view = &V;
+	uint32_t *const land = (uint32_t *)landing((end - o_cnt) * 4);
+	op.down.push_back(HibagCopy{land, d + o_cnt, (end - o_cnt) * 4});
+	hibag_combine_run(op);
+	size_t total = 0;
+	for (int k = 0; k < nib; k++) total += (size_t)(int)land[k];
+	if (total > bound) build_throw("build_haplomatch: the device returned more pairs than the candidates allow");
+	return match_result(total, land + nib, out_n);
+}
+
+// Two operations (hibag_combine.h): pass 0 -- the step's uploads, per in-bag sample the minimum distance and the number of
+// pairs at it --, then, once the host has turned the counts into offsets, pass 1, which writes the pairs.  The uploads go
+// into the evaluation's buffers, as build_set_haplo_geno's do.
+uint32_t *match_two_pass(const PluginHaplotype haplo[], const size_t n_haplo[], size_t H, int n_snp, const PluginGenotype geno[],
+	size_t &out_n)
+{
+	const int nib = (int)g.inbag.size();
+	MatchView V{};                                 // (no in-bag sample: no workgroup)
+	HibagOp op0, op1;
+	op0.kind = HIBAG_OP_MATCH0; op0.view = &V;
+	op1.kind = HIBAG_OP_MATCH1; op1.view = &V;
+	{
+		Recording recording(&op0);
+		upload_lists(haplo, (int)H, n_snp, n_haplo, geno);
+		if (nib > 0) {
+			// the scratch buffer: samp, a1, a2, min_d, count, offset (ints); the pairs have a buffer of their own
+			reserve(g.match, (size_t)6 * nib * sizeof(int) + 64, "hipMalloc(match)");
+			int *const d_i = (int *)g.match.p;
+			std::vector<int> a1(nib), a2(nib);
+			for (int k = 0; k < nib; k++) { a1[k] = g.true1[g.inbag[k]]; a2[k] = g.true2[g.inbag[k]]; }
+			upload(d_i, g.inbag.data(), nib * sizeof(int), "copy match args");
+			upload(d_i + nib, a1.data(), nib * sizeof(int), "copy match args");
+			upload(d_i + 2 * nib, a2.data(), nib * sizeof(int), "copy match args");
+			V = MatchView{(int)H, std::max(1, (n_snp + 31) / 32), g.n_pad, (const uint32_t *)g.hb.p, (const int *)g.d_start,
+				(const uint32_t *)g.d_planes, d_i, d_i + nib, d_i + 2 * nib, d_i + 3 * nib, d_i + 4 * nib, d_i + 5 * nib, nullptr, nib};
+		}
+	}
+	if (nib == 0) {
+		hibag_combine_run(op0);                            // (the uploads alone: a later build_set_haplo_geno-free evaluation may rely on them)
+		return match_result(0, nullptr, out_n);
+	}
+	int *const count = (int *)landing((size_t)nib * sizeof(int));
+	op0.down.push_back(HibagCopy{count, V.count, (size_t)nib * sizeof(int)});
+	hibag_combine_run(op0);
+	std::vector<int> offset(nib); size_t total = 0;
+	for (int k = 0; k < nib; k++) { offset[k] = (int)total; total += (size_t)count[k]; }
+	if (total == 0) return match_result(0, nullptr, out_n);
+	reserve(g.pairs, 2 * total * sizeof(uint32_t), "hipMalloc(pairs)");
+	V.out = (uint32_t *)g.pairs.p;
+	{
+		Recording recording(&op1);
+		upload((void *)V.offset, offset.data(), nib * sizeof(int), "copy match offsets");
+	}
+	uint32_t *const pairs = (uint32_t *)landing(2 * total * sizeof(uint32_t));
+	op1.down.push_back(HibagCopy{pairs, g.pairs.p, 2 * total * sizeof(uint32_t)});
+	hibag_combine_run(op1);
+	return match_result(total, pairs, out_n);
+}
+
+// ---- the batched evaluation of a growth step's candidates: the stages of hibag_build_eval_launch ----
+// A growth step's cell plan.  It lives with the thread: a growth step is a millisecond, and allocating (and page-faulting)
+// a few hundred KB of vectors per step was a quarter of what the step cost the host.
+struct BatchPlan {
+	std::vector<int> start;                         // [n_cand][n_hla + 1] allele starts, absolute haplotype indices
+	std::vector<std::vector<int>> cell_list;        // per candidate its non-empty cells (h1 << 16 | h2), posterior order
+	std::vector<std::vector<uint64_t>> cell_work;   // ... and the haplotype pairs of each
+	std::vector<int> present, at;                   // scratch: alleles with haplotypes; cell -> place in the list
+};
+thread_local BatchPlan g_plan;
+
+// Plan the cells: per candidate the haplotypes per allele and the list of its non-empty cells, in posterior order.
+// Returns the longest list's length, rounded up to whole groups of k_batch_scan.
+int plan_cells(BatchPlan &S, const HibagBuildCandidate cand[], int n_cand)
+{
+	const int nh = g.n_hla;
+	S.start.assign((size_t)n_cand * (nh + 1), 0);
+	if ((int)S.cell_list.size() < n_cand) { S.cell_list.resize(n_cand); S.cell_work.resize(n_cand); }
+	int max_cells = 1;
+	size_t off = 0;
+	for (int c = 0; c < n_cand; c++) {
+		int *st = &S.start[(size_t)c * (nh + 1)];
+		count_alleles(st, cand[c].haplo, cand[c].n_haplo);
+		st[0] = (int)off;
+		for (int h = 0; h < nh; h++) st[h + 1] += st[h];
+		off += (size_t)cand[c].n_haplo;
+		std::vector<int> &cl = S.cell_list[c];
+		std::vector<uint64_t> &cwk = S.cell_work[c];
+		cl.clear(); cwk.clear();
+		// (posterior order = h1 ascending, h2 >= h1 ascending, over the alleles that have haplotypes: src/LibHLA.cpp:1653-1691)
+		S.present.clear();
+		for (int h = 0; h < nh; h++) if (st[h + 1] > st[h]) S.present.push_back(h);
+		for (size_t i1 = 0; i1 < S.present.size(); i1++) {
+			const int h1 = S.present[i1];
+			const uint64_t n1 = (uint64_t)(st[h1 + 1] - st[h1]);
+			for (size_t i2 = i1; i2 < S.present.size(); i2++) {
+				const int h2 = S.present[i2];
+				const uint64_t n2 = (uint64_t)(st[h2 + 1] - st[h2]);
+				cl.push_back((h1 << 16) | h2);
+				cwk.push_back(h1 == h2 ? n1 * (n1 + 1) / 2 : n1 * n2);
+			}
+		}
+		max_cells = std::max(max_cells, (int)cl.size());
+	}
+	return (max_cells + SCAN_NB - 1) / SCAN_NB * SCAN_NB;
+}
+
+// One device arena = [inputs | outputs | scratch], byte offsets; the inputs travel in ONE copy from a pinned staging buffer
+// of the same layout and the outputs come back in one: a growth step is a handful of small arrays, and a dozen separate
+// pageable copies cost more than the kernels.  Two routes: with the cohort's genotypes resident on the device (the driver's
+// trainers, hibag_build_set_genotypes; BatchView "Round 6") `cw` holds the candidates' SNP indices, `wpos` the samples' packed
+// true pairs, and there is no `cellb`; otherwise the caller's expanded form travels (pack_expanded).
+struct BatchArena { size_t hb, cw, start, cells, cellb, seg, planes, true_cell, wpos, hf, in_end, best, post, out_end, cellv, end; };
+
+BatchArena lay_out_arena(int nw, size_t Hs, size_t n_cand, size_t np, size_t max_cells, int n_seg, int nh, bool resident)
+{
+	size_t o = 0;
+	auto take = [&](size_t bytes) { const size_t at = o; o = (o + bytes + 15) & ~(size_t)15; return at; };
+	BatchArena A;
+	A.hb = take(nw * Hs * 4); A.cw = take(resident ? n_cand * 4 : n_cand * 2 * np * 4); A.start = take(n_cand * (nh + 1) * 4);
+	A.cells = take(n_cand * max_cells * 4); A.cellb = take(resident ? 0 : n_cand * max_cells * 16); A.seg = take(n_cand * (n_seg + 1) * 4);
+	A.planes = take(2 * NW * np * 4); A.true_cell = take(np * 4); A.wpos = take(resident ? np * 4 : n_cand * np * 4); A.hf = take(Hs * 8);
+	A.in_end = o;
+	A.best = take(n_cand * 2 * np * 4); A.post = take(n_cand * np * 8);
+	A.out_end = o;
+	A.cellv = take(n_cand * max_cells * np * 8);
+	A.end = o;
+	return A;
+}
+
+// The inputs of both routes, written where they travel from: allele starts, haplotype words and frequencies (candidates back
+// to back), the base genotypes' planes, the true pairs.
+void pack_shared(char *h, const BatchArena &A, const BatchPlan &S, const PluginGenotype base_geno[], int n_snp, const HibagBuildCandidate cand[],
+	int n_cand, int nw, size_t Hs)
+{
+	uint32_t *const hb = (uint32_t *)(h + A.hb);
+	double *const hf = (double *)(h + A.hf);
+	memcpy(h + A.start, S.start.data(), S.start.size() * 4);
+	size_t off = 0;
+	for (int c = 0; c < n_cand; c++) {
+		pack_haplotypes(hb, Hs, off, hf + off, cand[c].haplo, (size_t)cand[c].n_haplo, nw, n_snp);
+		off += (size_t)cand[c].n_haplo;
+	}
+	if (off == 0) { for (int w = 0; w < nw; w++) hb[w] = 0; hf[0] = 0.0; }
+	pack_planes((uint32_t *)(h + A.planes), g.n_pad, base_geno, g.n_sample);
+	set_true_pairs(base_geno, (int *)(h + A.true_cell));
+}
+
+// Resident route: the candidates' SNP indices, the bare cell lists, the samples' packed true pairs (the scan compares them
+// with the cells' itself).
+void pack_resident(char *h, const BatchArena &A, const BatchPlan &S, const HibagBuildCandidate cand[], int n_cand, int max_cells)
+{
+	const int n = g.n_sample, np = g.n_pad;
+	uint32_t *const snp = (uint32_t *)(h + A.cw);
+	int *const cells = (int *)(h + A.cells), *const pair = (int *)(h + A.wpos);
+	for (int c = 0; c < n_cand; c++) {
+		snp[c] = (uint32_t)cand[c].snp;
+		const std::vector<int> &cl = S.cell_list[c];
+		int *cc = cells + (size_t)c * max_cells;
+		memcpy(cc, cl.data(), cl.size() * sizeof(int));
+		for (size_t i = cl.size(); i < (size_t)max_cells; i++) cc[i] = -1;     // (never equal to a sample's packed true pair)
+	}
+	for (int s = 0; s < n; s++) pair[s] = (g.true1[s] << 16) | g.true2[s];
+	for (int s = n; s < np; s++) pair[s] = -1;
+}
+
+// Expanded route: per candidate the two planes' word with its SNP set, the cells with their haplotype ranges, and where each
+// sample's true pair sits in its cell list.  (After pack_shared: from the base planes and the true pairs' cells it wrote.)
+void pack_expanded(char *h, const BatchArena &A, BatchPlan &S, int n_snp, const HibagBuildCandidate cand[], int n_cand, int max_cells)
+{
+	const int n = g.n_sample, np = g.n_pad, nh = g.n_hla;
+	const int word = (n_snp - 1) >> 5, bit = (n_snp - 1) & 31;
+	uint32_t *const cw = (uint32_t *)(h + A.cw);
+	int *const cells = (int *)(h + A.cells), *const cellb = (int *)(h + A.cellb), *const wpos = (int *)(h + A.wpos);
+	const int *const true_cell = (const int *)(h + A.true_cell);
+	const uint32_t *const b1p = (const uint32_t *)(h + A.planes) + (size_t)word * np, *const b2p = b1p + (size_t)NW * np;
+	S.at.resize((size_t)nh * (nh + 1) / 2);
+	for (int c = 0; c < n_cand; c++) {
+		// the candidate SNP's bit in the two planes of its word (branch-free: the compiler vectorises it)
+		uint32_t *o1 = &cw[((size_t)c * 2) * np], *o2 = &cw[((size_t)c * 2 + 1) * np];
+		const int32_t *col = cand[c].column;
+		const uint32_t keep = ~(1u << bit);
+		for (int s = 0; s < n; s++) {
+			const uint32_t v = (uint32_t)col[s];
+			const uint32_t b1 = (uint32_t)(v == 1u) | (uint32_t)(v == 2u), b2 = (uint32_t)(v > 1u);   // TGenotype::_SetSNP, src/LibHLA.cpp:609-622
+			o1[s] = (b1p[s] & keep) | (b1 << bit);
+			o2[s] = (b2p[s] & keep) | (b2 << bit);
+		}
+		for (int s = n; s < np; s++) { o1[s] = PAD_S1; o2[s] = PAD_S2; }
+		const int *st = &S.start[(size_t)c * (nh + 1)];
+		const std::vector<int> &cl = S.cell_list[c];
+		int *cc = cells + (size_t)c * max_cells, *cbv = cellb + (size_t)c * max_cells * 4;
+		std::fill(S.at.begin(), S.at.end(), -1);
+		for (size_t i = 0; i < cl.size(); i++) {
+			const int h1 = cl[i] >> 16, h2 = cl[i] & 0xFFFF;
+			cc[i] = cl[i];
+			cbv[4 * i] = st[h1]; cbv[4 * i + 1] = st[h1 + 1]; cbv[4 * i + 2] = st[h2]; cbv[4 * i + 3] = st[h2 + 1];
+			S.at[h2 + h1 * (2 * nh - h1 - 1) / 2] = (int)i;
+		}
+		for (size_t i = cl.size(); i < (size_t)max_cells; i++) { cc[i] = 0; cbv[4 * i] = cbv[4 * i + 1] = cbv[4 * i + 2] = cbv[4 * i + 3] = 0; }
+		int *wp = wpos + (size_t)c * np;
+		for (int s = 0; s < n; s++) wp[s] = S.at[true_cell[s]];
+		for (int s = n; s < np; s++) wp[s] = -1;
+	}
+}
+
+// Cut every candidate's cell list into n_seg segments of equal work, contiguous cells: seg[n_cand][n_seg + 1]
+void cut_segments(int *seg, const BatchPlan &S, int n_cand, int n_seg)
+{
+	for (int c = 0; c < n_cand; c++) {
+		const std::vector<uint64_t> &cwk = S.cell_work[c];
+		uint64_t total = 0;
+		for (uint64_t w : cwk) total += w + 4;
+		int *sg = seg + (size_t)c * (n_seg + 1);
+		sg[0] = 0;
+		uint64_t acc = 0;
+		int k = 1;
+		for (size_t i = 0; i < cwk.size(); i++) {
+			while (k < n_seg && acc * n_seg >= total * k) sg[k++] = (int)i;
+			acc += cwk[i] + 4;
+		}
+		while (k <= n_seg) sg[k++] = (int)cwk.size();
+	}
+}
+
+BatchView batch_view(char *d, const BatchArena &A, int n_snp, int nw, size_t Hs, int n_cand, int n_seg, int max_cells, bool resident)
+{
+	BatchView B{};                                 // (what a route does not use stays null: the kernels choose by that)
+	B.n_hla = g.n_hla; B.n_pad = g.n_pad; B.nw = nw; B.n_cand = n_cand; B.n_seg = n_seg; B.max_cells = max_cells;
+	B.word = (n_snp - 1) >> 5; B.bit = (n_snp - 1) & 31;
+	B.hb = (const uint32_t *)(d + A.hb); B.hf = (const double *)(d + A.hf); B.n_haplo_total = (int)Hs;
+	B.start = (const int *)(d + A.start); B.cells = (const int *)(d + A.cells); B.seg = (const int *)(d + A.seg);
+	B.planes = (const uint32_t *)(d + A.planes); B.true_cell = (const int *)(d + A.true_cell); B.tab = (const double *)g.d_tab;
+	B.cellv = (double *)(d + A.cellv); B.best = (int *)(d + A.best); B.post = (double *)(d + A.post);
+	if (resident) { B.gdev = (const int8_t *)g.d_geno8; B.cand_snp = (const int *)(d + A.cw); B.true_pair = (const int *)(d + A.wpos); }
+	else { B.cand_w = (const uint32_t *)(d + A.cw); B.cellb = (const int4 *)(d + A.cellb); B.wpos = (const int *)(d + A.wpos); }
+	return B;
 }
 
 // ---- fused launches (hibag_combine.h): the operations' views as kernel arguments, their workgroups back to back ----
@@ -657,28 +987,13 @@ HibagMulti<V> multi_of(const HibagOp *const ops[], int n, Blocks &&blocks, int &
 	return M;
 }
 
-void match0_launch(const HibagOp *const ops[], int n, hipStream_t st)
-{
-	int total = 0;
-	const HibagMulti<MatchView> M = multi_of<MatchView>(ops, n, [](const MatchView &v) { return v.n_inbag; }, total);
-	if (total > 0) hipLaunchKernelGGL(k_build_match<0>, dim3(total), dim3(HIBAG_WAVE), 0, st, M);
-}
-
-void match1_launch(const HibagOp *const ops[], int n, hipStream_t st)
-{
-	int total = 0;
-	const HibagMulti<MatchView> M = multi_of<MatchView>(ops, n, [](const MatchView &v) { return v.n_inbag; }, total);
-	if (total > 0) hipLaunchKernelGGL(k_build_match<1>, dim3(total), dim3(HIBAG_WAVE), 0, st, M);
-}
-
+template <bool PASS0, bool PASS1>
 void match_launch(const HibagOp *const ops[], int n, hipStream_t st)
 {
 	int total = 0;
 	const HibagMulti<MatchView> M = multi_of<MatchView>(ops, n, [](const MatchView &v) { return v.n_inbag; }, total);
-	if (total > 0) {
-		hipLaunchKernelGGL(k_build_match<0>, dim3(total), dim3(HIBAG_WAVE), 0, st, M);
-		hipLaunchKernelGGL(k_build_match<1>, dim3(total), dim3(HIBAG_WAVE), 0, st, M);
-	}
+	if (total > 0 && PASS0) hipLaunchKernelGGL(k_build_match<0>, dim3(total), dim3(HIBAG_WAVE), 0, st, M);
+	if (total > 0 && PASS1) hipLaunchKernelGGL(k_build_match<1>, dim3(total), dim3(HIBAG_WAVE), 0, st, M);
 }
 
 void eval_launch(const HibagOp *const ops[], int n, hipStream_t st)
@@ -691,15 +1006,16 @@ void eval_launch(const HibagOp *const ops[], int n, hipStream_t st)
 	if (total > 0) hipLaunchKernelGGL(k_batch_scan, dim3(total), dim3(HIBAG_WAVE), 0, st, Ms);
 }
 
-const bool g_build_registered = (hibag_combine_register(HIBAG_OP_MATCH0, match0_launch), hibag_combine_register(HIBAG_OP_MATCH1, match1_launch),
-	hibag_combine_register(HIBAG_OP_EVAL, eval_launch), hibag_combine_register(HIBAG_OP_MATCH, match_launch), true);
+const bool g_build_registered = (hibag_combine_register(HIBAG_OP_MATCH0, match_launch<true, false>),
+	hibag_combine_register(HIBAG_OP_MATCH1, match_launch<false, true>), hibag_combine_register(HIBAG_OP_EVAL, eval_launch),
+	hibag_combine_register(HIBAG_OP_MATCH, match_launch<true, true>), true);
 
 } // namespace
 
 // build_init(nHLA, nSample): src/LibHLA.cpp:2256-2260
 void hibag_build_init(int n_hla, int n_sample)
 {
-	hibag_build_done();
+	hibag_build_done();                            // (the state is fresh after this: every vector empty, every pointer null)
 	if (n_hla <= 0 || n_sample < 0) build_throw("build_init: invalid dimensions");
 	// every allocation and launch of the build entries goes to the device the calling thread selected
 	// with hibag_hip_set_device (one process per GPU: LOCAL_RANK), not to whatever HIP's current device is
@@ -707,7 +1023,6 @@ void hibag_build_init(int n_hla, int n_sample)
 	g.n_hla = n_hla; g.n_sample = n_sample;
 	g.n_pad = (std::max(n_sample, 1) + HIBAG_WAVE - 1) / HIBAG_WAVE * HIBAG_WAVE;
 	g.boot.assign(n_sample, 1);
-	g.inbag.clear(); g.oob.clear();
 	for (int i = 0; i < n_sample; i++) g.inbag.push_back(i);
 	double tab[HIBAG_TAB_N];
 	for (int i = 0; i < HIBAG_TAB_N; i++) tab[i] = std::exp(i * std::log(1e-5));     // src/LibHLA.cpp:166-183
@@ -726,25 +1041,8 @@ void hibag_build_init(int n_hla, int n_sample)
 // build_done(): called from a destructor (src/LibHLA.cpp:2262-2266) -- must not throw
 void hibag_build_done()
 {
-	for (void **p : {&g.d_hb, &g.d_start, &g.d_planes, &g.d_true, &g.d_best, &g.d_post, &g.d_tab, &g.d_match, &g.d_batch}) dev_free(*p);
-	for (BuildState::Slot &sl : g.slot) {
-		dev_free(sl.d);
-		if (sl.h) (void)hipHostFree(sl.h);
-		sl = BuildState::Slot();
-	}
-	g.d_hf = nullptr;
-	if (g.h_stage) (void)hipHostFree(g.h_stage);
-	g.h_stage = nullptr;
-	if (g.h_up) (void)hipHostFree(g.h_up);
-	g.h_up = nullptr;
-	for (void *p : g.h_retired) (void)hipHostFree(p);
-	g.h_retired.clear();
-	if (g.h_dn) (void)hipHostFree(g.h_dn);
-	g.h_dn = nullptr; g.cap_dn = 0;
-	dev_free(g.d_pairs);
-	dev_free(g.d_geno8); g.geno8_snps = 0;
-	g.cap_h = g.cap_s = g.cap_match = g.cap_batch = g.cap_stage = g.cap_up = g.up_at = g.cap_pairs = 0;
-	g.active = false; g.evaluated = false;
+	g.release();
+	g = BuildState();
 }
 
 // build_set_bootstrap(counts[nSample]): src/LibHLA.cpp:2290-2293; 0 = out-of-bag
@@ -784,9 +1082,7 @@ void hibag_build_set_haplo_geno(const PluginHaplotype haplo[], int n_haplo, cons
 	if (n_snp < 0 || n_snp > 128 || n_haplo < 0) build_throw("build_set_haplo_geno: invalid sizes");
 	HIP_OK(hipStreamSynchronize(0), "build_set_haplo_geno");       // (nothing of an earlier call may still read the staging area)
 	upload_rewind();
-	upload_haplo(haplo, n_haplo, n_snp, true, nullptr);
-	upload_geno(geno);
-	g.evaluated = false;
+	upload_lists(haplo, n_haplo, n_snp, nullptr, geno);
 }
 
 // build_acc_oob(): src/LibHLA.cpp:1938-1941 -- number of correct alleles over the out-of-bag samples
@@ -795,7 +1091,7 @@ int hibag_build_acc_oob()
 	if (!g.active) build_throw("build_acc_oob before build_init");
 	evaluate();
 	int correct = 0;
-	for (int s : g.oob) correct += compare_hla(g.best1[s], g.best2[s], g.true1[s], g.true2[s]);
+	for (int s : g.oob) correct += compare_hla(g.best[s], g.best[g.n_pad + s], g.true1[s], g.true2[s]);
 	return correct;
 }
 
@@ -806,8 +1102,7 @@ double hibag_build_acc_ib()
 	evaluate();
 	double loglik = 0;
 	for (int s : g.inbag) loglik += g.boot[s] * std::log(g.postprob[s]);
-	loglik *= -2;
-	return loglik;
+	return loglik * -2;
 }
 
 // build_haplomatch(haplo, nHaplo[nHLA], n_snp, geno, out_n): src/LibHLA.cpp:1037-1063.
@@ -823,150 +1118,25 @@ uint32_t *hibag_build_haplomatch(const PluginHaplotype haplo[], const size_t n_h
 		H += n_haplo[h];
 	}
 	upload_rewind();                               // (every earlier upload was consumed: an operation returns when its results are back)
-	{
-		// ONE operation where an upper bound on the number of pairs is small (it always is for the driver's growth steps: the
-		// bound is the number of candidate pairs, a few per in-bag sample): the step's inputs in one copy into one arena, both
-		// passes back to back -- the second finds its offsets from the first's counts on the device --, counts and pairs back in
-		// one copy sized by the bound.  Two device round trips and a dozen copies less per growth step.
-		const int nib1 = (int)g.inbag.size(), nh = g.n_hla, np = g.n_pad, n = g.n_sample;
-		const int nw = std::max(1, (n_snp + 31) / 32);
-		std::vector<int> start(nh + 1, 0);
-		for (int h = 0; h < nh; h++) start[h + 1] = start[h] + (int)n_haplo[h];
-		// (g.n_haplo / g.n_snp / g.d_hb describe what build_set_haplo_geno uploaded for evaluate(): this path has an arena of its own and leaves them alone)
-		g.true1.assign(n, 0); g.true2.assign(n, 0);
-		for (int s = 0; s < n; s++) {
-			int a1 = geno[s].hla1, a2 = geno[s].hla2;
-			if (a1 > a2) std::swap(a1, a2);
-			if (a1 < 0 || a2 >= nh) build_throw("genotype with an invalid true HLA pair");
-			g.true1[s] = a1; g.true2[s] = a2;
-		}
-		size_t bound = 0;
-		for (int k = 0; k < nib1; k++) {
-			const size_t n1 = n_haplo[g.true1[g.inbag[k]]], n2 = n_haplo[g.true2[g.inbag[k]]];
-			bound += g.true1[g.inbag[k]] == g.true2[g.inbag[k]] ? n1 * (n1 + 1) / 2 : n1 * n2;
-		}
-		if (nib1 > 0 && bound > 0 && bound <= ((size_t)1 << 20)) {
-			g.evaluated = false;
-			const size_t Hs = std::max<size_t>(H, 1);
-			// the arena, in 4-byte units: inputs [hb | start | planes | samp | a1 | a2], scratch [min_d], results [count | pairs]
-			const size_t o_hb = 0, o_start = o_hb + (size_t)nw * Hs, o_planes = o_start + (nh + 1), o_samp = o_planes + (size_t)2 * NW * np,
-				o_a1 = o_samp + nib1, o_a2 = o_a1 + nib1, in_end = o_a2 + nib1, o_min = in_end, o_cnt = o_min + nib1, o_pairs = o_cnt + nib1,
-				end = o_pairs + 2 * bound;
-			std::vector<uint32_t> blob(in_end, 0);
-			for (size_t i = 0; i < H; i++)
-				for (int w = 0; w < nw; w++) {
-					uint32_t v = (uint32_t)((uint64_t)haplo[i].packed[w >> 1] >> (32 * (w & 1)));
-					const int lo = 32 * w;                   // clear bits >= n_snp (uninitialised in the reference, src/LibHLA.cpp:287-292)
-					if (n_snp < lo + 32) v &= (n_snp <= lo) ? 0u : ((1u << (n_snp - lo)) - 1);
-					blob[o_hb + (size_t)w * Hs + i] = v;
-				}
-			for (int h = 0; h <= nh; h++) blob[o_start + h] = (uint32_t)start[h];
-			for (int w = 0; w < NW; w++)
-				for (int s = 0; s < np; s++) {               // padding lanes: all missing
-					blob[o_planes + (size_t)w * np + s] = s < n ? (uint32_t)((uint64_t)geno[s].snp1[w >> 1] >> (32 * (w & 1))) : 0u;
-					blob[o_planes + (size_t)(NW + w) * np + s] = s < n ? (uint32_t)((uint64_t)geno[s].snp2[w >> 1] >> (32 * (w & 1))) : 0xFFFFFFFFu;
-				}
-			for (int k = 0; k < nib1; k++) {
-				blob[o_samp + k] = (uint32_t)g.inbag[k];
-				blob[o_a1 + k] = (uint32_t)g.true1[g.inbag[k]];
-				blob[o_a2 + k] = (uint32_t)g.true2[g.inbag[k]];
-			}
-			reserve(g.d_match, g.cap_match, end * 4 + 64, "hipMalloc(match)");
-			uint32_t *const d = (uint32_t *)g.d_match;
-			HibagOp op;
-			op.kind = HIBAG_OP_MATCH;
-			{
-				struct Collect { Collect(HibagOp *o) { g_op = o; } ~Collect() { g_op = nullptr; } } collecting(&op);
-				upload(d, blob.data(), in_end * 4, "copy match inputs");
-			}
-			const MatchView V{(int)Hs, nw, np, d + o_hb, (const int *)(d + o_start), d + o_planes, (const int *)(d + o_samp),
-				(const int *)(d + o_a1), (const int *)(d + o_a2), (int *)(d + o_min), (int *)(d + o_cnt), nullptr, d + o_pairs, nib1};
-			op.view = &V;
-			uint32_t *const land = (uint32_t *)landing((end - o_cnt) * 4);
-			op.down.push_back(HibagCopy{land, d + o_cnt, (end - o_cnt) * 4});
-			hibag_combine_run(op);
-			size_t total = 0;
-			for (int k = 0; k < nib1; k++) total += (size_t)(int)land[k];
-			if (total > bound) build_throw("build_haplomatch: the device returned more pairs than the candidates allow");
-			uint32_t *buf = (uint32_t *)malloc((1 + 2 * total) * sizeof(uint32_t));
-			if (!buf) build_throw("out of memory");
-			buf[0] = (uint32_t)(2 * total);
-			memcpy(buf + 1, land + nib1, 2 * total * sizeof(uint32_t));
-			out_n = 1 + 2 * total;
-			return buf;
-		}
+	set_true_pairs(geno, nullptr);                 // (for the bound; the two-operation form redoes it in upload_lists, for the true cells)
+	size_t bound = 0;                              // the candidate pairs of the in-bag samples: no more can come back
+	for (int s : g.inbag) {
+		const size_t n1 = n_haplo[g.true1[s]], n2 = n_haplo[g.true2[s]];
+		bound += g.true1[s] == g.true2[s] ? n1 * (n1 + 1) / 2 : n1 * n2;
 	}
-	// Otherwise two operations (hibag_combine.h): pass 0 -- the step's uploads, per in-bag sample the minimum distance and the
-	// number of pairs at it --, then, once the host has turned the counts into offsets, pass 1, which writes the pairs.
-	HibagOp op0;
-	op0.kind = HIBAG_OP_MATCH0;
-	struct Collect { Collect(HibagOp *o) { g_op = o; } ~Collect() { g_op = nullptr; } };
-	const int nib = (int)g.inbag.size();
-	MatchView V{};                                 // (no in-bag sample: no workgroup)
-	op0.view = &V;
-	{
-		Collect collecting(&op0);
-		upload_haplo(haplo, (int)H, n_snp, false, n_haplo);
-		upload_geno(geno);
-		g.evaluated = false;
-		if (nib == 0) {
-			hibag_combine_run(op0);                        // (the uploads alone: a later build_set_haplo_geno-free evaluation may rely on them)
-			uint32_t *buf = (uint32_t *)malloc(sizeof(uint32_t));
-			if (!buf) build_throw("out of memory");
-			buf[0] = 0; out_n = 1;
-			return buf;
-		}
-		std::vector<int> samp(g.inbag), a1(nib), a2(nib);
-		for (int k = 0; k < nib; k++) { a1[k] = g.true1[samp[k]]; a2[k] = g.true2[samp[k]]; }
-		// layout of the scratch buffer: samp, a1, a2, min_d, count, offset (ints), then the pairs
-		const size_t ints = (size_t)6 * nib;
-		reserve(g.d_match, g.cap_match, ints * sizeof(int) + 64, "hipMalloc(match)");
-		int *d_i = (int *)g.d_match;
-		upload(d_i, samp.data(), nib * sizeof(int), "copy match args");
-		upload(d_i + nib, a1.data(), nib * sizeof(int), "copy match args");
-		upload(d_i + 2 * nib, a2.data(), nib * sizeof(int), "copy match args");
-		V = MatchView{(int)H, std::max(1, (n_snp + 31) / 32), g.n_pad, (const uint32_t *)g.d_hb, (const int *)g.d_start,
-			(const uint32_t *)g.d_planes, d_i, d_i + nib, d_i + 2 * nib, d_i + 3 * nib, d_i + 4 * nib, d_i + 5 * nib, nullptr, nib};
-	}
-	int *const d_i = (int *)g.d_match;
-	int *const count = (int *)landing((size_t)nib * sizeof(int));
-	op0.down.push_back(HibagCopy{count, d_i + 4 * nib, (size_t)nib * sizeof(int)});
-	hibag_combine_run(op0);
-	std::vector<int> offset(nib);
-	size_t total = 0;
-	for (int k = 0; k < nib; k++) { offset[k] = (int)total; total += (size_t)count[k]; }
-	uint32_t *buf = (uint32_t *)malloc((1 + 2 * total) * sizeof(uint32_t));
-	if (!buf) build_throw("out of memory");
-	buf[0] = (uint32_t)(2 * total);
-	if (total > 0) {
-		struct Guard { uint32_t *b; ~Guard() { free(b); } } guard{buf};       // (the calls below throw on failure)
-		reserve(g.d_pairs, g.cap_pairs, 2 * total * sizeof(uint32_t), "hipMalloc(pairs)");
-		V.out = (uint32_t *)g.d_pairs;
-		HibagOp op1;
-		op1.kind = HIBAG_OP_MATCH1;
-		op1.view = &V;
-		{
-			Collect collecting(&op1);
-			upload(d_i + 5 * nib, offset.data(), nib * sizeof(int), "copy match offsets");
-		}
-		uint32_t *const pairs = (uint32_t *)landing(2 * total * sizeof(uint32_t));
-		op1.down.push_back(HibagCopy{pairs, g.d_pairs, 2 * total * sizeof(uint32_t)});
-		hibag_combine_run(op1);
-		memcpy(buf + 1, pairs, 2 * total * sizeof(uint32_t));
-		guard.b = nullptr;
-	}
-	out_n = 1 + 2 * total;
-	return buf;
+	g.evaluated = false;
+	if (!g.inbag.empty() && bound > 0 && bound <= ((size_t)1 << 20)) return match_fused(haplo, n_haplo, H, n_snp, geno, bound, out_n);
+	return match_two_pass(haplo, n_haplo, H, n_snp, geno, out_n);
 }
 
 // ---------------------------------------------------------------------------
+thread_local double g_batch_prof[HIBAG_BATCH_PROF_N] = {};   // seconds (hibag_build_prof.h)
+static double batch_now() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec + 1e-9 * ts.tv_nsec; }
+
 // hibag_build_eval_batch: what a sequence of build_set_haplo_geno + build_acc_oob +
 // build_acc_ib calls returns for n_cand candidate SNPs that extend the same genotype list
 // (src/LibHLA.cpp:2018-2038), evaluated together.  base_geno holds the committed SNPs
 // (position n_snp-1 missing); cand[i].column is the raw genotype of candidate i per sample.
-thread_local double g_batch_prof[6] = {0, 0, 0, 0, 0, 0};     // host packing, copies + kernels, read-back, host reductions; of the packing: staging copy, (re)allocation (s)
-static double batch_now() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec + 1e-9 * ts.tv_nsec; }
-
 void hibag_build_eval_batch(const PluginGenotype base_geno[], int n_snp, const HibagBuildCandidate cand[], int n_cand,
 	int acc_floor, int acc_oob[], double loss_ib[])
 {
@@ -984,227 +1154,54 @@ void hibag_build_eval_launch(int slot, const PluginGenotype base_geno[], int n_s
 	if (slot < 0 || slot > 1) build_throw("build_eval_launch: slot must be 0 or 1");
 	if (n_snp < 1 || n_snp > 128 || n_cand < 0) build_throw("build_eval_batch: invalid sizes");
 	BuildState::Slot &SL = g.slot[slot];
-	SL.n_cand = n_cand;
+	SL.n_cand = 0;                                 // (nothing to collect until this launch's operation has run)
 	if (n_cand == 0) return;
-	const int nh = g.n_hla, n = g.n_sample, np = g.n_pad;
-	const int nw = (n_snp + 31) / 32, word = (n_snp - 1) >> 5, bit = (n_snp - 1) & 31;
+	const int nh = g.n_hla, np = g.n_pad, nw = (n_snp + 31) / 32;
 	size_t H = 0;
 	for (int c = 0; c < n_cand; c++) H += (size_t)cand[c].n_haplo;
 	const size_t Hs = std::max<size_t>(H, 1);
 	static const int wave_target = getenv("HIBAG_BATCH_WAVES") ? atoi(getenv("HIBAG_BATCH_WAVES")) : 8192;
 	const int n_seg = std::max(1, std::min(64, wave_target / std::max(1, (np / HIBAG_WAVE) * n_cand)));
+	bool resident = g.d_geno8 != nullptr;          // (the route: every candidate must name a row of the resident matrix)
+	for (int c = 0; c < n_cand && resident; c++) resident = cand[c].snp >= 0 && cand[c].snp < g.geno8_snps;
 
-	// Pass 1 (small): per candidate the haplotypes per allele and the list of its non-empty cells, in posterior order.  The
-	// scratch lives with the thread: a growth step is a millisecond, and allocating (and page-faulting) a few hundred KB of
-	// vectors per step was a quarter of what the step cost the host.
-	struct Scratch {
-		std::vector<int> start, true_cell, at, present;
-		std::vector<std::vector<int>> cell_list;
-		std::vector<std::vector<uint64_t>> cell_work;
-		std::vector<uint32_t> base_w1, base_w2;
-	};
-	static thread_local Scratch S;
-	S.start.assign((size_t)n_cand * (nh + 1), 0);
-	if ((int)S.cell_list.size() < n_cand) { S.cell_list.resize(n_cand); S.cell_work.resize(n_cand); }
-	int max_cells = 1;
-	{
-		size_t off = 0;
-		for (int c = 0; c < n_cand; c++) {
-			const PluginHaplotype *hp = cand[c].haplo;
-			int *st = &S.start[(size_t)c * (nh + 1)];
-			for (int i = 0; i < cand[c].n_haplo; i++) {
-				const int a = hp[i].aux.hla_allele;
-				if (a < 0 || a >= nh) build_throw("haplotype with an invalid HLA allele index");
-				st[a + 1]++;
-			}
-			st[0] = (int)off;
-			for (int h = 0; h < nh; h++) st[h + 1] += st[h];
-			off += (size_t)cand[c].n_haplo;
-			std::vector<int> &cl = S.cell_list[c];
-			std::vector<uint64_t> &cwk = S.cell_work[c];
-			cl.clear(); cwk.clear();
-			// (posterior order = h1 ascending, h2 >= h1 ascending, over the alleles that have haplotypes: src/LibHLA.cpp:1653-1691)
-			S.present.clear();
-			for (int h = 0; h < nh; h++) if (st[h + 1] > st[h]) S.present.push_back(h);
-			for (size_t i1 = 0; i1 < S.present.size(); i1++) {
-				const int h1 = S.present[i1];
-				const uint64_t n1 = (uint64_t)(st[h1 + 1] - st[h1]);
-				for (size_t i2 = i1; i2 < S.present.size(); i2++) {
-					const int h2 = S.present[i2];
-					const uint64_t n2 = (uint64_t)(st[h2 + 1] - st[h2]);
-					cl.push_back((h1 << 16) | h2);
-					cwk.push_back(h1 == h2 ? n1 * (n1 + 1) / 2 : n1 * n2);
-				}
-			}
-			max_cells = std::max(max_cells, (int)cl.size());
-		}
-	}
-	max_cells = (max_cells + SCAN_NB - 1) / SCAN_NB * SCAN_NB;
-
-	// One device arena = [inputs | outputs | scratch]; the inputs travel in ONE copy from a pinned
-	// staging buffer and the outputs come back in one: a growth step is a handful of small arrays,
-	// and a dozen separate pageable copies cost more than the kernels.
-	size_t o = 0;
-	auto take = [&](size_t bytes) { const size_t at = o; o = (o + bytes + 15) & ~(size_t)15; return at; };
-	// (the driver's trainers keep the cohort's genotypes on the device: no bit planes per candidate, no range table per cell,
-	// no per-sample position table -- BatchView "Round 6")
-	bool use_dev = g.d_geno8 != nullptr;
-	for (int c = 0; c < n_cand && use_dev; c++) use_dev = cand[c].snp >= 0 && cand[c].snp < g.geno8_snps;
-	const size_t o_hb = take((size_t)nw * Hs * 4), o_cw = take(use_dev ? (size_t)n_cand * 4 : (size_t)n_cand * 2 * np * 4), o_start = take(S.start.size() * 4),
-		o_cells = take((size_t)n_cand * max_cells * 4), o_cellb = take(use_dev ? 0 : (size_t)n_cand * max_cells * 16), o_seg = take((size_t)n_cand * (n_seg + 1) * 4),
-		o_planes = take((size_t)2 * NW * np * 4), o_true = take((size_t)np * 4), o_wpos = take(use_dev ? (size_t)np * 4 : (size_t)n_cand * np * 4), o_hf = take(Hs * 8), in_end = o;
-	const size_t b_best = (size_t)n_cand * 2 * np * 4, b_post = (size_t)n_cand * np * 8;
-	const size_t o_best = take(b_best), o_post = take(b_post), out_end = o;
-	const size_t o_cellv = take((size_t)n_cand * max_cells * np * 8);
+	BatchPlan &S = g_plan;
+	const int max_cells = plan_cells(S, cand, n_cand);
+	const BatchArena A = lay_out_arena(nw, Hs, n_cand, np, max_cells, n_seg, nh, resident);
 	const double t_res0 = batch_now();
-	reserve(SL.d, SL.cap_d, o, "hipMalloc(batch)");
-	if (out_end > SL.cap_h) {
-		if (SL.h) (void)hipHostFree(SL.h);
-		SL.h = nullptr; SL.cap_h = 0;
-		HIP_OK(hipHostMalloc(&SL.h, out_end * 2, hipHostMallocDefault), "hipHostMalloc(staging)");
-		SL.cap_h = out_end * 2;
-	}
+	reserve(SL.d, A.end, "hipMalloc(batch)");
+	reserve_pinned(SL.h, A.out_end, A.out_end * 2, "hipHostMalloc(staging)");
 	const double t_res1 = batch_now();
-	char *d = (char *)SL.d, *h = (char *)SL.h;
+	char *d = (char *)SL.d.p, *h = (char *)SL.h.p;
 
-	// Pass 2: every input array written where it travels from (the pinned staging area), once.
-	uint32_t *const hb = (uint32_t *)(h + o_hb), *const cw = (uint32_t *)(h + o_cw), *const planes = (uint32_t *)(h + o_planes);
-	double *const hf = (double *)(h + o_hf);
-	int *const cells = (int *)(h + o_cells), *const cellb = (int *)(h + o_cellb), *const seg = (int *)(h + o_seg),
-		*const true_cell = (int *)(h + o_true), *const wpos = (int *)(h + o_wpos);
-	memcpy(h + o_start, S.start.data(), S.start.size() * 4);
-	if (H == 0) { for (int w = 0; w < nw; w++) hb[w] = 0; hf[0] = 0.0; }
-	S.base_w1.resize(np); S.base_w2.resize(np);                      // word `word` of every sample's base genotype
-	for (int s = 0; s < n; s++) {
-		S.base_w1[s] = (uint32_t)((uint64_t)base_geno[s].snp1[word >> 1] >> (32 * (word & 1)));
-		S.base_w2[s] = (uint32_t)((uint64_t)base_geno[s].snp2[word >> 1] >> (32 * (word & 1)));
-	}
-	{
-		size_t off = 0;
-		for (int c = 0; c < n_cand; c++) {
-			const PluginHaplotype *hp = cand[c].haplo;
-			for (int i = 0; i < cand[c].n_haplo; i++) {
-				for (int w = 0; w < nw; w++) {
-					uint32_t v = (uint32_t)((uint64_t)hp[i].packed[w >> 1] >> (32 * (w & 1)));
-					const int lo = 32 * w;
-					if (n_snp < lo + 32) v &= (n_snp <= lo) ? 0u : ((1u << (n_snp - lo)) - 1);
-					hb[(size_t)w * Hs + off + i] = v;
-				}
-				hf[off + i] = hp[i].freq;
-			}
-			off += (size_t)cand[c].n_haplo;
-			if (use_dev) cw[c] = (uint32_t)cand[c].snp;                      // (the slot holds the candidates' SNP indices instead)
-			else {
-			// the candidate SNP's bit in the two planes of its word (branch-free: the compiler vectorises it)
-			uint32_t *o1 = &cw[((size_t)c * 2) * np], *o2 = &cw[((size_t)c * 2 + 1) * np];
-			const int32_t *col = cand[c].column;
-			const uint32_t keep = ~(1u << bit);
-			const uint32_t *b1p = S.base_w1.data(), *b2p = S.base_w2.data();
-			for (int s = 0; s < n; s++) {
-				const uint32_t v = (uint32_t)col[s];
-				const uint32_t b1 = (uint32_t)(v == 1u) | (uint32_t)(v == 2u), b2 = (uint32_t)(v > 1u);   // TGenotype::_SetSNP, src/LibHLA.cpp:609-622
-				o1[s] = (b1p[s] & keep) | (b1 << bit);
-				o2[s] = (b2p[s] & keep) | (b2 << bit);
-			}
-			for (int s = n; s < np; s++) { o1[s] = 0u; o2[s] = 0xFFFFFFFFu; }      // padding lanes: all missing
-			}
-			// the cell list, the cells' haplotype ranges, the segments of equal work
-			const int *st = &S.start[(size_t)c * (nh + 1)];
-			const std::vector<int> &cl = S.cell_list[c];
-			const std::vector<uint64_t> &cwk = S.cell_work[c];
-			int *cc = cells + (size_t)c * max_cells, *cbv = cellb + (size_t)c * max_cells * 4;
-			if (use_dev) {
-				memcpy(cc, cl.data(), cl.size() * sizeof(int));
-				for (size_t i = cl.size(); i < (size_t)max_cells; i++) cc[i] = -1;     // (never equal to a sample's packed true pair)
-			} else {
-				for (size_t i = 0; i < cl.size(); i++) {
-					const int h1 = cl[i] >> 16, h2 = cl[i] & 0xFFFF;
-					cc[i] = cl[i];
-					cbv[4 * i] = st[h1]; cbv[4 * i + 1] = st[h1 + 1]; cbv[4 * i + 2] = st[h2]; cbv[4 * i + 3] = st[h2 + 1];
-				}
-				for (size_t i = cl.size(); i < (size_t)max_cells; i++) { cc[i] = 0; cbv[4 * i] = cbv[4 * i + 1] = cbv[4 * i + 2] = cbv[4 * i + 3] = 0; }
-			}
-			uint64_t total = 0;
-			for (uint64_t w : cwk) total += w + 4;
-			int *sg = seg + (size_t)c * (n_seg + 1);
-			sg[0] = 0;
-			uint64_t acc = 0;
-			int k = 1;
-			for (size_t i = 0; i < cl.size(); i++) {                        // equal work per segment, contiguous cells
-				while (k < n_seg && acc * n_seg >= total * k) sg[k++] = (int)i;
-				acc += cwk[i] + 4;
-			}
-			while (k <= n_seg) sg[k++] = (int)cl.size();
-		}
-	}
-
-	// genotype planes and true pairs of the cohort (what upload_geno does, but into the same transfer)
-	g.true1.assign(n, 0); g.true2.assign(n, 0);
-	for (int w = 0; w < NW; w++) {
-		uint32_t *p1 = planes + (size_t)w * np, *p2 = planes + (size_t)(NW + w) * np;
-		for (int s = 0; s < n; s++) {
-			p1[s] = (uint32_t)((uint64_t)base_geno[s].snp1[w >> 1] >> (32 * (w & 1)));
-			p2[s] = (uint32_t)((uint64_t)base_geno[s].snp2[w >> 1] >> (32 * (w & 1)));
-		}
-		for (int s = n; s < np; s++) { p1[s] = 0u; p2[s] = 0xFFFFFFFFu; }
-	}
-	for (int s = 0; s < n; s++) {
-		int a1 = base_geno[s].hla1, a2 = base_geno[s].hla2;
-		if (a1 > a2) std::swap(a1, a2);
-		if (a1 < 0 || a2 >= nh) build_throw("genotype with an invalid true HLA pair");
-		g.true1[s] = a1; g.true2[s] = a2;
-		true_cell[s] = a2 + a1 * (2 * nh - a1 - 1) / 2;
-	}
-	for (int s = n; s < np; s++) true_cell[s] = -1;
-
-	// where each sample's true pair sits in each candidate's cell list -- or just the packed pair, which the scan compares itself
-	if (use_dev) {
-		for (int s = 0; s < n; s++) wpos[s] = (g.true1[s] << 16) | g.true2[s];
-		for (int s = n; s < np; s++) wpos[s] = -1;
-	}
-	S.at.resize((size_t)nh * (nh + 1) / 2);
-	for (int c = 0; c < n_cand && !use_dev; c++) {
-		std::fill(S.at.begin(), S.at.end(), -1);
-		const std::vector<int> &cl = S.cell_list[c];
-		for (size_t i = 0; i < cl.size(); i++) {
-			const int h1 = cl[i] >> 16, h2 = cl[i] & 0xFFFF;
-			S.at[h2 + h1 * (2 * nh - h1 - 1) / 2] = (int)i;
-		}
-		int *wp = wpos + (size_t)c * np;
-		for (int s = 0; s < n; s++) wp[s] = S.at[true_cell[s]];
-		for (int s = n; s < np; s++) wp[s] = -1;
-	}
+	pack_shared(h, A, S, base_geno, n_snp, cand, n_cand, nw, Hs);
+	if (resident) pack_resident(h, A, S, cand, n_cand, max_cells);
+	else pack_expanded(h, A, S, n_snp, cand, n_cand, max_cells);
+	cut_segments((int *)(h + A.seg), S, n_cand, n_seg);
+	const BatchView B = batch_view(d, A, n_snp, nw, Hs, n_cand, n_seg, max_cells, resident);
 	const double t1 = batch_now();
-	g_batch_prof[4] += t1 - t_res1; g_batch_prof[5] += t_res1 - t_res0;
-	BatchView B{nh, np, nw, n_cand, n_seg, word, (const uint32_t *)(d + o_hb), (const double *)(d + o_hf), (int)Hs,
-		(const int *)(d + o_start), (const uint32_t *)(d + o_planes), (const uint32_t *)(d + o_cw), (const int *)(d + o_cells),
-		(const int4 *)(d + o_cellb), (const int *)(d + o_seg), max_cells, (const int *)(d + o_true), (const int *)(d + o_wpos), (const double *)g.d_tab, (double *)(d + o_cellv),
-		(int *)(d + o_best), (double *)(d + o_post), nullptr, nullptr, bit, nullptr};
-	if (use_dev) {
-		B.gdev = (const int8_t *)g.d_geno8; B.cand_snp = (const int *)(d + o_cw); B.true_pair = (const int *)(d + o_wpos);
-		B.cand_w = nullptr; B.cellb = nullptr; B.wpos = nullptr;
-	}
+	g_batch_prof[HIBAG_BATCH_PROF_STAGING] += t1 - t_res1; g_batch_prof[HIBAG_BATCH_PROF_ALLOC] += t_res1 - t_res0;
+
 	// one operation (hibag_combine.h): the step's inputs in one copy, the two kernels -- alone, or fused with the scoring of
 	// the other trainers' steps of the moment --, the results back in one; returns when they are in the staging area
 	HibagOp op;
-	op.kind = HIBAG_OP_EVAL;
-	op.view = &B;
-	op.up.push_back(HibagCopy{d, h, in_end});
-	op.down.push_back(HibagCopy{h + o_best, d + o_best, out_end - o_best});
+	op.kind = HIBAG_OP_EVAL; op.view = &B;
+	op.up.push_back(HibagCopy{d, h, A.in_end});
+	op.down.push_back(HibagCopy{h + A.best, d + A.best, A.out_end - A.best});
 	hibag_combine_run(op);
 	const double t2 = batch_now();
-	SL.np = np; SL.o_best = o_best; SL.o_post = o_post; SL.t_launch = t2;
-	g_batch_prof[0] += t1 - t0; g_batch_prof[1] += t2 - t1;
+	SL.n_cand = n_cand; SL.o_best = A.best; SL.o_post = A.post;
+	g_batch_prof[HIBAG_BATCH_PROF_PACK] += t1 - t0; g_batch_prof[HIBAG_BATCH_PROF_DEVICE] += t2 - t1;
 }
 
 void hibag_build_eval_collect(int slot, int *acc_floor, int acc_oob[], double loss_ib[])
 {
 	if (slot < 0 || slot > 1) build_throw("build_eval_collect: slot must be 0 or 1");
 	BuildState::Slot &SL = g.slot[slot];
-	const int n_cand = SL.n_cand, np = SL.np;
+	const int n_cand = SL.n_cand, np = g.n_pad;
 	if (n_cand == 0) return;
 	const double t2 = batch_now();                 // (the slot's operation was waited for by hibag_build_eval_launch)
-	const char *h = (const char *)SL.h;
+	const char *h = (const char *)SL.h.p;
 	const int *best = (const int *)(h + SL.o_best);
 	const double *post = (const double *)(h + SL.o_post);
 	const double t3 = batch_now();
@@ -1223,5 +1220,5 @@ void hibag_build_eval_collect(int slot, int *acc_floor, int acc_oob[], double lo
 	}
 	*acc_floor = run_max;
 	g.evaluated = false;
-	g_batch_prof[2] += t3 - t2; g_batch_prof[3] += batch_now() - t3;
+	g_batch_prof[HIBAG_BATCH_PROF_READBACK] += t3 - t2; g_batch_prof[HIBAG_BATCH_PROF_REDUCE] += batch_now() - t3;
 }

@@ -41,13 +41,13 @@
 
 #include "../../include/hibag_hip.h"
 #include "hibag_plugin.h"
+#include "hibag_build_prof.h"
 #include "hibag_pool.h"
 #include "hibag_em.h"
 #include "hibag_combine.h"
 
 int hibag_fail(int code, const char *fmt, ...);       // hibag_api.hip: sets the thread's last error
 int hibag_selected_device();                          // hibag_api.hip: the thread's hibag_hip_set_device() choice
-extern thread_local double g_batch_prof[6];           // hibag_build.hip
 extern thread_local double g_em_prof[3];              // hibag_em.hip
 
 namespace {
@@ -874,7 +874,8 @@ int hibag_hip_trainer_new_classifiers(hibag_hip_trainer *t, int nclassifier, int
 		if (getenv("HIBAG_TRAIN_PROFILE"))
 			fprintf(stderr, "[hibag train] total %.3f s: pair lists (device) %.3f, EM (host) %.3f, scoring (device) %.3f "
 				"[pack %.3f (staging %.3f, allocation %.3f), copy+kernels %.3f, read-back %.3f, reductions %.3f], compare + accept %.3f, select %.3f; search() %.3f, %d growth steps\n",
-				Profile::now() - t0, g_prof.t[0], g_prof.t[1], g_prof.t[2], g_batch_prof[0], g_batch_prof[4], g_batch_prof[5], g_batch_prof[1], g_batch_prof[2], g_batch_prof[3],
+				Profile::now() - t0, g_prof.t[0], g_prof.t[1], g_prof.t[2], g_batch_prof[HIBAG_BATCH_PROF_PACK], g_batch_prof[HIBAG_BATCH_PROF_STAGING], g_batch_prof[HIBAG_BATCH_PROF_ALLOC],
+				g_batch_prof[HIBAG_BATCH_PROF_DEVICE], g_batch_prof[HIBAG_BATCH_PROF_READBACK], g_batch_prof[HIBAG_BATCH_PROF_REDUCE],
 				g_prof.t[3], g_prof.t[4], g_prof.t[5], (int)g_prof.t[7]);
 		if (getenv("HIBAG_TRAIN_PROFILE"))
 			fprintf(stderr, "[hibag train] this thread's CPU time: pair lists %.3f, EM %.3f, scoring %.3f, compare %.3f, select %.3f; search() %.3f s = %.3f ms per growth step; of EM: fits on this thread %.3f\n",

@@ -115,6 +115,75 @@ def test_training_entries(which, oracle, hapmap_geno, hla_type_table, model_oob,
     tab.build_done()
 
 
+class _Entries:
+    """The plugin table over one constructed case (tests/training_reference.py), from build_init to build_done."""
+
+    def __init__(self, cs):
+        import hibag_amd
+        from hibag_amd import _lib
+        hibag_amd.hlaSetKernelTarget("hip")
+        lst = cs.lst
+        self.n, self.nh, self.k, self.H = len(cs.boot), lst.n_hla, lst.n_snp, len(lst.allele)
+        self.tab = _FullTable.from_address(_lib.lib().hibag_hip_gpu_ext_proc())
+        self.libc = C.CDLL(None)
+        self.libc.free.argtypes = [C.c_void_p]
+        self.hap_r, self.geno_r = lst.records(), cs.records()
+        self.hap = C.cast(self.hap_r.ctypes.data, C.POINTER(_THaplotype))
+        self.geno = C.cast(self.geno_r.ctypes.data, C.POINTER(_TGenotype))
+        self.n_per = (C.c_size_t * self.nh)(*[int(v) for v in lst.lens])
+
+    def __enter__(self):
+        self.tab.build_init(self.nh, self.n)
+        return self
+
+    def __exit__(self, *exc):
+        self.tab.build_done()
+
+    def bootstrap(self, counts):
+        self.tab.build_set_bootstrap((C.c_int * self.n)(*[int(v) for v in counts]))
+
+    def scores(self):
+        """build_set_haplo_geno, then (build_acc_oob, build_acc_ib)"""
+        self.tab.build_set_haplo_geno(self.hap, self.H, self.geno, self.k)
+        return self.tab.build_acc_oob(), self.tab.build_acc_ib()
+
+    def haplomatch(self):
+        """build_haplomatch's buffer, copied and freed, and its out_n"""
+        out_n = C.c_size_t(0)
+        buf = self.tab.build_haplomatch(self.hap, self.n_per, self.k, self.geno, C.byref(out_n))
+        pairs = np.ctypeslib.as_array(buf, shape=(1 + buf[0],)).copy()
+        self.libc.free(buf)
+        return pairs, out_n.value
+
+
+def _check_entries(key, cs, want, scores_again=False):
+    """build_set_haplo_geno + build_acc_oob / build_acc_ib / build_haplomatch through the table on one constructed case,
+    against the oracle, exactly.  ``scores_again``: the two scores once more after build_haplomatch."""
+    with _Entries(cs) as e:
+        e.bootstrap(cs.boot)
+        got_oob, got_ib = e.scores()
+        pairs, out_n = e.haplomatch()
+        again = e.scores() if scores_again else None
+    cnt = int(pairs[0]) // 2
+    print(f"{key}: acc_oob {got_oob} (want {want.acc_oob}), acc_ib {got_ib!r} (want {want.loss_ib!r}), {cnt} pairs")
+    assert got_oob == want.acc_oob
+    assert got_ib == want.loss_ib
+    assert out_n == 1 + 2 * cnt
+    got = {}
+    for q in range(cnt):
+        kk, v = int(pairs[1 + 2 * q]), int(pairs[2 + 2 * q])
+        got.setdefault(kk, []).append((v & 0xFFFF, v >> 16))
+    refs = T.haplo_matches(cs)
+    assert len(refs) == int((cs.boot > 0).sum())
+    for kk, ref in enumerate(refs):
+        assert got.get(kk, []) == ref, f"in-bag sample {kk}"
+        assert len(ref) >= 1            # the host insists on a non-empty list (src/LibHLA.cpp:1066-1072)
+    assert set(got) <= set(range(len(refs)))
+    if scores_again:
+        print(f"{key}: after build_haplomatch acc_oob {again[0]}, acc_ib {again[1]!r}")
+        assert again == (want.acc_oob, want.loss_ib)
+
+
 @pytest.mark.parametrize("key", list(T.PLUGIN_CASES))
 def test_training_entries_every_width(key, oracle):
     """build_set_haplo_geno + build_acc_oob / build_acc_ib / build_haplomatch through the table, as above, on generated
@@ -124,48 +193,26 @@ def test_training_entries_every_width(key, oracle):
     (33...64 SNPs), <3> (65...96), <4> (97...128) -- the [w * n_haplo + a] strides against the NW-strided planes, bits 0
     and 31 of every word, the mask of the top word -- and match_dist with nw > 1.  In "far" one out-of-bag sample is far
     from every pair: no best guess, which counts as no correct allele; its NaN posterior stays out of the in-bag sum."""
-    import hibag_amd
-    from hibag_amd import _lib
-    hibag_amd.hlaSetKernelTarget("hip")
-    cs, want = T.plugin_case(key), T.case_score(key)
-    lst = cs.lst
-    n, nh, k, H = len(cs.boot), lst.n_hla, lst.n_snp, len(lst.allele)
-    tab = _FullTable.from_address(_lib.lib().hibag_hip_gpu_ext_proc())
-    libc = C.CDLL(None)
-    libc.free.argtypes = [C.c_void_p]
-    hap_r, geno_r = lst.records(), cs.records()
-    hap = C.cast(hap_r.ctypes.data, C.POINTER(_THaplotype))
-    geno = C.cast(geno_r.ctypes.data, C.POINTER(_TGenotype))
-    boot = (C.c_int * n)(*[int(v) for v in cs.boot])
+    _check_entries(key, T.plugin_case(key), T.case_score(key))
 
-    tab.build_init(nh, n)
-    try:
-        tab.build_set_bootstrap(boot)
-        tab.build_set_haplo_geno(hap, H, geno, k)
-        got_oob, got_ib = tab.build_acc_oob(), tab.build_acc_ib()
-        n_per = (C.c_size_t * nh)(*[int(v) for v in lst.lens])
-        out_n = C.c_size_t(0)
-        buf = tab.build_haplomatch(hap, n_per, k, geno, C.byref(out_n))
-        cnt = buf[0] // 2
-        pairs = np.ctypeslib.as_array(buf, shape=(1 + 2 * cnt,)).copy()
-        libc.free(buf)
-    finally:
-        tab.build_done()
-    print(f"{key}: acc_oob {got_oob} (want {want.acc_oob}), acc_ib {got_ib!r} (want {want.loss_ib!r}), {cnt} pairs")
-    assert got_oob == want.acc_oob
-    assert got_ib == want.loss_ib
-    assert out_n.value == 1 + 2 * cnt
-    got = {}
-    for q in range(cnt):
-        kk, v = int(pairs[1 + 2 * q]), int(pairs[2 + 2 * q])
-        got.setdefault(kk, []).append((v & 0xFFFF, v >> 16))
-    fm = T.flat_model([lst])
-    st = np.concatenate([[0], np.cumsum(lst.lens)])
-    inbag = np.where(cs.boot > 0)[0]
-    for kk, s in enumerate(inbag):
-        lo, hi = sorted((int(cs.a1[s]), int(cs.a2[s])))
-        ref = oracle.prep_haplo_match(fm, 0, cs.s1[s], cs.s2[s], lo, hi)
-        ref = [(int(i) - int(st[lo]), int(j) - int(st[hi])) for i, j in ref]
-        assert got.get(kk, []) == ref, f"in-bag sample {kk}"
-        assert len(ref) >= 1            # the host insists on a non-empty list (src/LibHLA.cpp:1066-1072)
-    assert set(got) <= set(range(len(inbag)))
+
+def test_haplomatch_beyond_the_pair_bound(oracle):
+    """The same on "two-pass" (T.MATCH_CASES): 1,100 haplotypes, a pair bound of 4.6 million -- past 1 << 20, where
+    build_haplomatch counts the pairs in an operation of its own, sums the counts on the host and writes the pairs in a
+    second one.  That path uploads into the buffers build_set_haplo_geno fills, so the two scores are taken once more after
+    it and must come out the same."""
+    _check_entries("two-pass", T.match_case("two-pass"), T.match_score("two-pass"), scores_again=True)
+
+
+def test_haplomatch_without_in_bag_samples(oracle):
+    """build_set_bootstrap with all zeros: build_haplomatch returns the empty list (buf[0] == 0, out_n == 1), and the state
+    is as usable afterwards as before -- the case's own counts and a build_set_haplo_geno give the case's scores."""
+    cs, want = T.plugin_case("snp33"), T.case_score("snp33")
+    with _Entries(cs) as e:
+        e.bootstrap(np.zeros(len(cs.boot), np.int32))
+        pairs, out_n = e.haplomatch()
+        e.bootstrap(cs.boot)
+        got = e.scores()
+    print(f"no in-bag sample: buffer {pairs.tolist()}, out_n {out_n}; then acc_oob {got[0]}, acc_ib {got[1]!r}")
+    assert pairs.tolist() == [0] and out_n == 1
+    assert got == (want.acc_oob, want.loss_ib)

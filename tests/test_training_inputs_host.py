@@ -85,6 +85,21 @@ def test_plugin_case(key, oracle):
     assert ref.acc_oob == sc.acc_oob and ref.loss_ib == sc.loss_ib
 
 
+@pytest.mark.parametrize("key", list(T.MATCH_CASES))
+def test_match_case(key, oracle):
+    """The case is past build_haplomatch's pair bound -- or it would run the path every other case runs --, every in-bag
+    sample has pairs to return, and its scores say something."""
+    cs = T.match_case(key)
+    assert T.match_bound(cs) > 1 << 20
+    inbag = np.where(cs.boot > 0)[0]
+    pairs = T.haplo_matches(cs)
+    assert len(inbag) >= 1 and len(pairs) == len(inbag) and all(len(p) >= 1 for p in pairs)
+    assert (cs.boot == 0).any() and (cs.a1 > cs.a2).any() and (cs.a1 <= cs.a2).any()
+    sc = _check_scores(key, cs.lst, cs.geno, cs.a1, cs.a2, cs.boot, cs.far, False)
+    ref = T.match_score(key)
+    assert ref.acc_oob == sc.acc_oob and ref.loss_ib == sc.loss_ib
+
+
 @pytest.mark.parametrize("key", list(T.BATCH_CASES))
 def test_batch_case(key, oracle):
     b = T.batch_case(key)

@@ -404,6 +404,39 @@ def case_score(key) -> Score:
 
 
 @functools.lru_cache(maxsize=None)
+def match_score(key) -> Score:
+    cs = match_case(key)
+    return score(cs.lst, cs.geno, cs.a1, cs.a2, cs.boot)
+
+
+@functools.lru_cache(maxsize=None)
+def haplo_matches(cs: Case) -> tuple:
+    """What build_haplomatch returns, per in-bag sample in order: the (i1, i2) of _PrepHaploMatch (src/LibHLA.cpp:1569-1637),
+    each index inside its allele's sub-list."""
+    lst = cs.lst
+    fm = flat_model([lst])
+    st = np.concatenate([[0], np.cumsum(lst.lens)])
+    out = []
+    for s in np.where(cs.boot > 0)[0]:
+        lo, hi = sorted((int(cs.a1[s]), int(cs.a2[s])))
+        ref = O.prep_haplo_match(fm, 0, cs.s1[s], cs.s2[s], lo, hi)
+        out.append([(int(i) - int(st[lo]), int(j) - int(st[hi])) for i, j in ref])
+    return tuple(out)
+
+
+def match_bound(cs: Case) -> int:
+    """The library's upper bound on the number of pairs build_haplomatch can return: per in-bag sample n1 (n1 + 1) / 2 on the
+    diagonal, else n1 n2.  Above 1 << 20 it sizes the pair list from a first pass's counts instead of from the bound."""
+    lens = cs.lst.lens
+    bound = 0
+    for s in np.where(cs.boot > 0)[0]:
+        lo, hi = sorted((int(cs.a1[s]), int(cs.a2[s])))
+        n1, n2 = int(lens[lo]), int(lens[hi])
+        bound += n1 * (n1 + 1) // 2 if lo == hi else n1 * n2
+    return bound
+
+
+@functools.lru_cache(maxsize=None)
 def batch_scores(key) -> tuple:
     b = make_batch(**dict(BATCH_CASES[key]))
     return tuple(score(b.lists[c], b.geno(c), b.a1, b.a2, b.boot) for c in range(len(b.lists)))
@@ -450,9 +483,18 @@ BATCH_CASES["direct"] = _kw(n_snp=97, n_cand=2, n_hla=6, per_allele=("counts", 3
 BATCH_CASES["far"] = _kw(n_snp=128, n_cand=3, n_sample=65, seed=25, far=True)
 EXEMPT = {"far"}                        # the one case (of each form) with a deliberately far sample
 
+# build_haplomatch beyond its pair bound (1 << 20): 1,100 haplotypes over 4 alleles, so that the in-bag samples' candidate
+# pairs add up to millions and the entry sizes its result from a counting pass of its own.  (A dict of its own: the
+# PLUGIN_CASES lists are capped at 40 haplotypes.)
+MATCH_CASES = {"two-pass": _kw(n_snp=97, n_hla=6, per_allele=("counts", 367, 1, 366, 366), n_sample=65, seed=31)}
+
 
 def plugin_case(key) -> Case:
     return make_case(**dict(PLUGIN_CASES[key]))
+
+
+def match_case(key) -> Case:
+    return make_case(**dict(MATCH_CASES[key]))
 
 
 def batch_case(key) -> Batch:
