@@ -27,6 +27,8 @@ from .curve import HlaPredictCurve, hlaPredictCurve  # noqa: F401
 from .topk import HlaTopCalls, hlaPredictTopK  # noqa: F401
 from .cohort import HlaDeviceCohort, hlaPredictLoci  # noqa: F401
 from .draws import HlaPosteriorDraws, hlaPredictDraws  # noqa: F401
+from .groups import (HlaAlleleGroups, HlaGroupCalls, hlaGroupsByMap, hlaGroupsByResolution, hlaGroupsBySequence,  # noqa: F401
+                     hlaPredictGroups)
 from ._lib import HibagHipError  # noqa: F401
 
 __all__ = ["engine_kind", "engine_nkb", "engine_steps", "NA_INTEGER", "Classifier", "HlaAttrBagObj", "HlaSNPGeno", "load_geno", "load_model", "model_to_robj", "save_model",

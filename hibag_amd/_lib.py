@@ -52,9 +52,14 @@ EXPORTS = [
     "hibag_hip_test_build_eval_batch",
     "hibag_hip_predict_draw", "hibag_hip_predict_draw_device", "hibag_hip_predict_draw_mapped",
     "hibag_hip_predict_draw_snp_major", "hibag_hip_predict_draw_bed", "hibag_hip_predict_draw_cohort",
+    "hibag_hip_groups_create", "hibag_hip_groups_free", "hibag_hip_groups_levels", "hibag_hip_groups_tile",
+    "hibag_hip_predict_groups", "hibag_hip_predict_groups_device", "hibag_hip_predict_groups_mapped",
+    "hibag_hip_predict_groups_snp_major", "hibag_hip_predict_groups_bed", "hibag_hip_predict_groups_cohort",
 ]
 TOPK_MAX = 16      # HIBAG_HIP_TOPK_MAX of include/hibag_hip.h
 DRAW_MAX = 64      # HIBAG_HIP_DRAW_MAX
+GROUPS_MAX_PART = 512        # HIBAG_HIP_GROUPS_MAX_PART
+GROUPS_MAX_LEVELS = 4096     # HIBAG_HIP_GROUPS_MAX_LEVELS
 
 
 class HibagHipError(RuntimeError):
@@ -126,6 +131,18 @@ def lib() -> C.CDLL:
         L.hibag_hip_predict_draw_snp_major.argtypes = [vp, vp, C.c_size_t, i32, i32, vp, vp, i32, i32, u64, i64, vp, vp, vp, vp]
         L.hibag_hip_predict_draw_bed.argtypes = [vp, C.c_char_p, i32, i32, vp, vp, i32, i32, u64, i64, vp, vp, vp, vp]
         L.hibag_hip_predict_draw_cohort.argtypes = [vp, vp, i32, i32, vp, vp, i32, i32, u64, i64, vp, vp, vp, vp]
+    if hasattr(L, "hibag_hip_groups_create"):         # (absent from an older build selected with HIBAG_HIP_LIBRARY)
+        L.hibag_hip_groups_create.argtypes = [vp, i32, vp, C.POINTER(vp)]
+        L.hibag_hip_groups_free.argtypes = [vp]
+        L.hibag_hip_groups_free.restype = None
+        L.hibag_hip_groups_levels.argtypes = [vp, vp]
+        L.hibag_hip_groups_tile.argtypes = [vp, C.POINTER(i32)]
+        L.hibag_hip_predict_groups.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp]
+        L.hibag_hip_predict_groups_device.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]
+        L.hibag_hip_predict_groups_mapped.argtypes = [vp, vp, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp]
+        L.hibag_hip_predict_groups_snp_major.argtypes = [vp, vp, C.c_size_t, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp]
+        L.hibag_hip_predict_groups_bed.argtypes = [vp, C.c_char_p, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp]
+        L.hibag_hip_predict_groups_cohort.argtypes = [vp, vp, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp]
     if hasattr(L, "hibag_hip_cohort_new"):
         # (an older build selected with HIBAG_HIP_LIBRARY, e.g. the parent commit's for a baseline timing, lacks the cohort
         # entries: everything else still binds, and a call that needs them fails with AttributeError)

@@ -260,7 +260,7 @@ int predict_cohort_entry(hibag_hip_model *m, const hibag_hip_cohort *c, int firs
 		return hibag_fail(HIBAG_HIP_EINVAL, "the cohort is on device %d, the model on device %d", c->device, m->device);
 	if (first < 0 || count < 0 || (long long)first + count > c->n_samp)
 		return hibag_fail(HIBAG_HIP_EINVAL, "samples [%d, %d + %d) lie outside the cohort's %d samples", first, first, count, c->n_samp);
-	if (out.list.on) if (int rc = check_list_args(count, out.list)) return rc;
+	if (out.list.on) if (int rc = check_list_args(m, count, out.list)) return rc;
 	if (!snp_col && m->n_snp > 0) return hibag_fail(HIBAG_HIP_EINVAL, "snp_col is NULL");
 	for (int k = 0; k < m->n_snp; k++)
 		if (snp_col[k] >= c->n_snp)
@@ -338,6 +338,13 @@ int hibag_hip_predict_draw_cohort(hibag_hip_model *m, const hibag_hip_cohort *c,
 	double *matching)
 {
 	return predict_cohort_entry(m, c, first, count, snp_col, flip, vote_method, PredictOut::draw(n_draw, seed, sample0, h1, h2, prob, matching));
+}
+
+int hibag_hip_predict_groups_cohort(hibag_hip_model *m, const hibag_hip_cohort *c, int first, int count, const int32_t *snp_col,
+	const int32_t *flip, int vote_method, const hibag_hip_groups *plan, int32_t *g1, int32_t *g2, double *prob, double *matching,
+	double *dosage)
+{
+	return predict_cohort_entry(m, c, first, count, snp_col, flip, vote_method, PredictOut::groups(plan, g1, g2, prob, matching, dosage));
 }
 
 } // extern "C"

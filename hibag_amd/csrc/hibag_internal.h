@@ -10,6 +10,7 @@
 //   hibag_prefix.hip   hibag_hip_predict_prefix: every sub-model "first k classifiers" from one pass 1
 //   hibag_merge.hip    hibag_hip_predict_merge: k models' predictions and their merge on one stream
 //   hibag_cohort.hip   a cohort's genotypes resident on a device in 2-bit form, and the prediction entries that read them
+//   hibag_groups.hip   the plan of the group entries (hibag_hip_predict_groups*): the caller's partitions in list form
 #ifndef HIBAG_INTERNAL_H_
 #define HIBAG_INTERNAL_H_
 
@@ -259,6 +260,17 @@ struct hibag_hip_model {
 	}
 };
 
+// The plan of the group entries (include/hibag_hip.h "allele groups"): the caller's partitions of ONE model's alleles as the
+// lists k_finish_groups walks, on that model's device (hibag_groups.hip).
+struct hibag_hip_groups {
+	const hibag_hip_model *model = nullptr;    // whose alleles are partitioned: the entries take the plan with this model only
+	int device = 0;
+	int n_hla = 0;
+	std::vector<int32_t> levels;           // G_q per partition
+	DevBuf d_call, d_dose, d_group, d_offset;
+	HibagGroupsView view{};
+};
+
 namespace hibag_detail {
 
 void build_table(double *tab);                               // hibag_model.hip: exp(d * log(1e-5)), the host libm's
@@ -281,9 +293,11 @@ struct PackSource {
 	const int32_t *d_row = nullptr, *d_flip = nullptr;
 };
 
-// The list output set of the top-k entries (hibag_hip_predict_topk*) and of the draw entries (hibag_hip_predict_draw*): per
-// sample k pairs and their probabilities, [n_samp][k] each.  With it the finish is k_finish_topk (the k best pairs) or, with
-// `draws` set, k_finish_draw (k = n_draw pairs drawn from the posterior) instead of the call / dosage / posterior kernels.
+// The list output set of the top-k entries (hibag_hip_predict_topk*), of the draw entries (hibag_hip_predict_draw*) and of
+// the group entries (hibag_hip_predict_groups*): per sample k pairs and their probabilities, [n_samp][k] each.  With it the
+// finish is k_finish_topk (the k best pairs), with `draws` set k_finish_draw (k = n_draw pairs drawn from the posterior), with
+// `plan` set k_finish_groups (k = the plan's partitions: per partition the best pair of groups, and optionally the group
+// dosages) instead of the call / dosage / posterior kernels.
 struct ListOut {
 	bool on = false;                       // the call is a list entry's
 	int k = 0;                             // pairs per sample: the k of the top-k entries, the n_draw of the draw entries
@@ -292,6 +306,10 @@ struct ListOut {
 	bool draws = false;                    // which finish runs
 	uint64_t seed = 0;                     // draws: the generator's key ...
 	int64_t sample0 = 0;                   // ... and the index, in the caller's numbering, of sample 0 of h1 / h2 / prob
+	bool groups = false;                   // the group finish runs (h1 / h2: group indices) ...
+	const hibag_hip_groups *plan = nullptr; // ... with this plan's lists ...
+	double *dosage = nullptr;              // ... and, if asked for, the group dosages [n_samp][levels()]
+	size_t levels() const { return plan ? (size_t)plan->view.n_level : 0; }
 };
 
 // What a prediction call returns, the one "outputs" parameter of the drivers: the six per-sample outputs of PredictHLA (any
@@ -318,6 +336,12 @@ struct PredictOut {
 		o.list.draws = true; o.list.seed = seed; o.list.sample0 = sample0;
 		return o;
 	}
+	static PredictOut groups(const hibag_hip_groups *plan, int32_t *g1, int32_t *g2, double *prob, double *matching, double *dosage)
+	{
+		PredictOut o = topk(plan ? plan->view.n_part : 0, g1, g2, prob, matching);
+		o.list.groups = true; o.list.plan = plan; o.list.dosage = dosage;
+		return o;
+	}
 	// the set `s0` samples further on (null stays null; a draw is keyed with the sample's index in the caller's numbering)
 	PredictOut advanced(size_t s0, size_t n_hla, size_t n_cell) const
 	{
@@ -326,6 +350,7 @@ struct PredictOut {
 		adv(o.H1, s0); adv(o.H2, s0); adv(o.max_prob, s0); adv(o.matching, s0);
 		adv(o.dosage, s0 * n_hla); adv(o.postprob, s0 * n_cell);
 		adv(o.list.h1, s0 * (size_t)list.k); adv(o.list.h2, s0 * (size_t)list.k); adv(o.list.prob, s0 * (size_t)list.k);
+		adv(o.list.dosage, s0 * list.levels());
 		o.list.sample0 += (int64_t)s0;
 		return o;
 	}
@@ -367,7 +392,7 @@ int make_batch(hibag_hip_model *m, int n_samp, bool need_best, HibagBatchView &B
 void enqueue_pack(hibag_hip_model *m, HibagBatchView &B, const PackSource &src, int s0, hipStream_t st);
 void run_core(hibag_hip_model *m, HibagBatchView &B, int vote_method, double *d_part, hipStream_t st);   // passes 1 and 2 behind a pack
 int check_predict_args(hibag_hip_model *m, const void *geno, int n_samp, int vote_method, const void *H1, const void *H2);
-int check_list_args(int n_samp, const ListOut &list);       // the list entries' own arguments, behind check_predict_args
+int check_list_args(const hibag_hip_model *m, int n_samp, const ListOut &list);       // the list entries' own arguments, behind check_predict_args
 bool take_fault(hibag_hip_model *m);                         // a hand-over failed since the last look: counted, hand-overs off
 int sticky_fault(hibag_hip_model *m);
 int workspace_enter(hibag_hip_model *m, hipStream_t st);

@@ -52,6 +52,27 @@ void hibag_launch_finish_topk(const HibagModelView &M, const HibagBatchView &B, 
 #define HIBAG_DRAW_MAX 64
 void hibag_launch_finish_draw(const HibagModelView &M, const HibagBatchView &B, double *d_part, int n_draw, uint64_t seed,
 	int64_t sample_index_of_first_lane, int32_t *d_H1, int32_t *d_H2, double *d_prob, double *d_matching, hipStream_t st);
+// The finish of the group entries (hibag_k_groups.h), launched INSTEAD of hibag_launch_finish: per sample and partition the
+// best pair of groups under the collapsed posterior, d_G1 / d_G2 / d_prob [n_samp][n_part], d_matching [n_samp] (may be
+// nullptr) and the group dosages d_dosage [n_samp][n_level] (may be nullptr).  The view is a plan's lists on the device
+// (hibag_groups.hip builds them): entries are a cell index with the GRP_* marks of hibag_k_groups.h.
+struct HibagGroupsView {
+	int n_part;                        // Q
+	int n_dose;                        // entries per partition of the dosage list (the longest partition's; the others padded)
+	int n_level;                       // D: the groups of all partitions
+	const uint32_t *call;              // [n_cell][n_part]: the cells by (bin, cell), the last of each bin marked
+	const uint32_t *dose;              // [n_dose][n_part]: the cells by (group, cell), marks for "twice", "group ends", "empty group"
+	const int32_t *group_of;           // [n_part][n_hla]
+	const int32_t *offset;             // [n_part + 1]: where a partition's groups start in a row of d_dosage
+};
+#define HIBAG_GROUPS_TILE_MAX 64                   // samples per workgroup at most
+#define HIBAG_GROUPS_LDS_DOUBLES 8064              // posterior values a workgroup stages in LDS (63 KiB; with the kernel's 1 KiB of per-sample scalars 64 KiB: two workgroups per CU)
+// samples per workgroup the launcher takes for a plan of n_part partitions on a model of n_cell cells, and whether their
+// posteriors are staged in LDS (*lds = 0: the walk reads the ensemble sums themselves -- n_cell > HIBAG_GROUPS_LDS_DOUBLES, or
+// HIBAG_GROUPS_NO_LDS=1 in the environment, read at every call)
+int hibag_groups_tile(int n_cell, int n_part, int *lds);
+void hibag_launch_finish_groups(const HibagModelView &M, const HibagBatchView &B, double *d_part, const HibagGroupsView &V,
+	int32_t *d_G1, int32_t *d_G2, double *d_prob, double *d_matching, double *d_dosage, hipStream_t st);
 // hlaOutOfBag (hibag_k_oob.h): each classifier predicts its own out-of-bag samples.  The per-classifier arrays are
 // [C][ld] with the batch's sample 0 at column 0 (the caller offsets the pointers); the plain haplotype table (grouped by
 // allele, hla_start[c][n_hla + 1] relative to hap_off[c]) serves the rare lane whose record log cannot settle its call.

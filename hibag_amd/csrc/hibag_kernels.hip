@@ -84,6 +84,7 @@ static_assert(2 * HIBAG_FP4_MAX_SNPS + 1 <= ACCUM_TAB_N, "pass 2's table must co
 #include "hibag_k_finish.h"
 #include "hibag_k_topk.h"
 #include "hibag_k_draw.h"
+#include "hibag_k_groups.h"
 #include "hibag_k_oob.h"
 #include "hibag_k_mask.h"
 #include "hibag_k_cohort.h"
@@ -350,6 +351,36 @@ void hibag_launch_finish_draw(const HibagModelView &M, const HibagBatchView &B, 
 	else if (n_draw <= 2 * DRAW_PER_WAVE) LAUNCH_DRAW(2);
 	else LAUNCH_DRAW(4);
 #undef LAUNCH_DRAW
+}
+
+// the finish of the group entries, in place of hibag_launch_finish (hibag_k_groups.h).  A workgroup takes `tile` samples: as many
+// as give each of its 256 threads at most ONE (sample, partition) pair (one sample for more than 256 partitions: several
+// rounds), at most what fits in LDS.  Small tiles on purpose: a walk is a chain of dependent loads, so what counts is the
+// number of wavefronts in flight, and a workgroup's LDS is what bounds them (HLA-B shape, 100 partitions: 2 samples, 20 KB).
+int hibag_groups_tile(int n_cell, int n_part, int *lds)
+{
+	const char *e = getenv("HIBAG_GROUPS_NO_LDS");
+	const int fit = HIBAG_GROUPS_LDS_DOUBLES / std::max(n_cell, 1);
+	const bool use_lds = fit >= 1 && !(e && atoi(e) != 0);
+	int tile = std::min(HIBAG_GROUPS_TILE_MAX, GROUPS_THREADS / std::max(n_part, 1));
+	if (use_lds) tile = std::min(tile, fit);
+	if (lds) *lds = use_lds ? 1 : 0;
+	return std::max(tile, 1);
+}
+
+void hibag_launch_finish_groups(const HibagModelView &M, const HibagBatchView &B, double *d_part, const HibagGroupsView &V,
+	int32_t *d_G1, int32_t *d_G2, double *d_prob, double *d_matching, double *d_dosage, hipStream_t st)
+{
+	if (V.n_part < 1 || B.n_samp < 1) return;           // (the entries have checked the plan)
+	int lds = 0;
+	const int tile = hibag_groups_tile(M.n_cell, V.n_part, &lds);
+	const dim3 grid((unsigned)((B.n_samp + tile - 1) / tile));
+	if (lds)
+		hipLaunchKernelGGL(k_finish_groups<true>, grid, dim3(GROUPS_THREADS), (size_t)tile * M.n_cell * sizeof(double), st, M, B,
+			(const double *)d_part, V, tile, d_G1, d_G2, d_prob, d_matching, d_dosage);
+	else
+		hipLaunchKernelGGL(k_finish_groups<false>, grid, dim3(GROUPS_THREADS), 0, st, M, B,
+			(const double *)d_part, V, tile, d_G1, d_G2, d_prob, d_matching, d_dosage);
 }
 
 void hibag_launch_oob(const HibagModelView &M, const HibagBatchView &B, const uint8_t *d_codes, const HibagOobOut &O,

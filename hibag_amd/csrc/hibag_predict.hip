@@ -136,10 +136,13 @@ int check_predict_args(hibag_hip_model *m, const void *geno, int n_samp, int vot
 }
 
 // the top-k and the draw entries' own arguments, behind check_predict_args
-int check_list_args(int n_samp, const ListOut &list)
+int check_list_args(const hibag_hip_model *m, int n_samp, const ListOut &list)
 {
 	static_assert(HIBAG_HIP_TOPK_MAX == HIBAG_TOPK_MAX && HIBAG_HIP_DRAW_MAX == HIBAG_DRAW_MAX, "the public bounds are the kernels' bounds");
-	if (list.draws) {
+	if (list.groups) {
+		if (!list.plan) return hibag_fail(HIBAG_HIP_EINVAL, "the group plan is NULL");
+		if (list.plan->model != m) return hibag_fail(HIBAG_HIP_EINVAL, "the group plan was made for another model");
+	} else if (list.draws) {
 		if (list.k < 1 || list.k > HIBAG_HIP_DRAW_MAX)
 			return hibag_fail(HIBAG_HIP_EINVAL, "n_draw = %d is outside 1 .. %d (HIBAG_HIP_DRAW_MAX)", list.k, HIBAG_HIP_DRAW_MAX);
 		if (list.sample0 < 0) return hibag_fail(HIBAG_HIP_EINVAL, "sample0 = %lld is negative", (long long)list.sample0);
@@ -224,7 +227,9 @@ static int predict_device_locked(hibag_hip_model *m, const PackSource &src, int 
 		run_core(m, B, vote_method, m->ws_part.as<double>(), st);
 		const PredictOut o = out.advanced((size_t)s0, (size_t)m->n_hla, (size_t)m->view.n_cell);
 		m->timer.begin(HIBAG_HIP_K_FINISH, st, true);
-		if (o.list.on && o.list.draws)
+		if (o.list.on && o.list.groups)
+			hibag_launch_finish_groups(m->view, B, B.part, o.list.plan->view, o.list.h1, o.list.h2, o.list.prob, o.matching, o.list.dosage, st);
+		else if (o.list.on && o.list.draws)
 			hibag_launch_finish_draw(m->view, B, B.part, o.list.k, o.list.seed, o.list.sample0, o.list.h1, o.list.h2, o.list.prob,
 				o.matching, st);
 		else if (o.list.on)
@@ -275,22 +280,22 @@ int staged_slice(const hibag_hip_model *m, int n_samp, size_t row_len)
 // vectors, so that a slice still comes down in one copy.
 struct SliceLayout {
 	PredictOut want;                       // the caller's set: which outputs are asked for, and where they go in the end
-	size_t nh = 0, P = 0, tk = 0;
-	size_t o_h1 = 0, o_h2 = 0, o_mp = 0, o_mt = 0, o_ds = 0, o_pp = 0, o_t1 = 0, o_t2 = 0, o_tp = 0;
+	size_t nh = 0, P = 0, tk = 0, gd = 0;  // (gd: group dosages per sample, if asked for)
+	size_t o_h1 = 0, o_h2 = 0, o_mp = 0, o_mt = 0, o_ds = 0, o_pp = 0, o_t1 = 0, o_t2 = 0, o_tp = 0, o_gd = 0;
 	size_t bytes = 0;                      // of the buffer of one slice
 
 	SliceLayout() = default;
 	SliceLayout(size_t slice, size_t n_hla, size_t n_cell, const PredictOut &out)
-		: want(out), nh(n_hla), P(n_cell), tk(out.list.on ? (size_t)out.list.k : 0)
+		: want(out), nh(n_hla), P(n_cell), tk(out.list.on ? (size_t)out.list.k : 0), gd(out.list.on && out.list.dosage ? out.list.levels() : 0)
 	{
 		o_h2 = o_h1 + slice * 4; o_mp = (o_h2 + slice * 4 + 7) / 8 * 8; o_mt = o_mp + slice * 8; o_ds = o_mt + slice * 8;
 		o_pp = o_ds + slice * nh * 8;
-		o_t1 = o_ds; o_t2 = o_t1 + slice * tk * 4; o_tp = o_t2 + slice * tk * 4;
-		bytes = ((want.list.on ? o_tp + slice * tk * 8 : o_pp + (want.postprob ? slice * P * 8 : 0)) + 255) / 256 * 256;
+		o_t1 = o_ds; o_t2 = o_t1 + slice * tk * 4; o_tp = o_t2 + slice * tk * 4; o_gd = o_tp + slice * tk * 8;      // (the group dosages: behind the lists)
+		bytes = ((want.list.on ? o_gd + slice * gd * 8 : o_pp + (want.postprob ? slice * P * 8 : 0)) + 255) / 256 * 256;
 	}
 	// bytes from the start of the buffer that a slice of n samples uses: of the vectors (the lists ride along), of everything asked for
 	size_t vectors(size_t n) const { return want.list.on ? o_tp + n * tk * 8 : o_ds; }
-	size_t used(size_t n) const { return want.list.on ? vectors(n) : want.postprob ? o_pp + n * P * 8 : want.dosage ? o_ds + n * nh * 8 : o_ds; }
+	size_t used(size_t n) const { return want.list.on ? (gd ? o_gd + n * gd * 8 : vectors(n)) : want.postprob ? o_pp + n * P * 8 : want.dosage ? o_ds + n * nh * 8 : o_ds; }
 	// the output set of a slice in the buffer at `base`: what is asked for, null for the rest
 	PredictOut bind(char *base) const
 	{
@@ -302,6 +307,7 @@ struct SliceLayout {
 		if (want.dosage) d.dosage = (double *)(base + o_ds);
 		if (want.postprob) d.postprob = (double *)(base + o_pp);
 		if (want.list.on) { d.list.h1 = (int32_t *)(base + o_t1); d.list.h2 = (int32_t *)(base + o_t2); d.list.prob = (double *)(base + o_tp); }
+		if (gd) d.list.dosage = (double *)(base + o_gd);
 		return d;
 	}
 	// a host copy of a slice's buffer -> samples [s0, s0 + n) of the caller's arrays; `matrices`: the dosage and the posterior too
@@ -316,6 +322,7 @@ struct SliceLayout {
 		if (d.list.on) {
 			memcpy(d.list.h1, s.list.h1, n * tk * 4); memcpy(d.list.h2, s.list.h2, n * tk * 4);
 			memcpy(d.list.prob, s.list.prob, n * tk * 8);
+			if (matrices && gd) memcpy(d.list.dosage, s.list.dosage, n * gd * 8);
 		}
 	}
 };
@@ -451,6 +458,7 @@ int StagedRun::download(int i)
 	const PredictOut d = L.bind(dev_out(i)), h = out.advanced((size_t)s0, L.nh, L.P);
 	if (h.dosage) HIP_TRY(hipMemcpyAsync(h.dosage, d.dosage, (size_t)n * L.nh * 8, hipMemcpyDeviceToHost, st));
 	if (h.postprob) HIP_TRY(hipMemcpyAsync(h.postprob, d.postprob, (size_t)n * L.P * 8, hipMemcpyDeviceToHost, st));
+	if (L.gd) HIP_TRY(hipMemcpyAsync(h.list.dosage, d.list.dosage, (size_t)n * L.gd * 8, hipMemcpyDeviceToHost, st));
 	return 0;
 }
 
@@ -786,7 +794,7 @@ static int predict_device_entry(hibag_hip_model *m, const PackSource &src, int n
 	void *stream)
 {
 	if (int rc = check_predict_args(m, src.d_geno, n_samp, vote_method, out.H1, out.H2)) return rc;
-	if (out.list.on) if (int rc = check_list_args(n_samp, out.list)) return rc;
+	if (out.list.on) if (int rc = check_list_args(m, n_samp, out.list)) return rc;
 	std::lock_guard<std::mutex> g(m->lock);
 	if (int rc = sticky_fault(m)) return rc;
 	return predict_device_locked(m, src, n_samp, vote_method, out, (hipStream_t)stream);
@@ -795,7 +803,7 @@ static int predict_device_entry(hibag_hip_model *m, const PackSource &src, int n
 static int predict_entry(hibag_hip_model *m, const int32_t *geno, int n_samp, int vote_method, const PredictOut &out)
 {
 	if (int rc = check_predict_args(m, geno, n_samp, vote_method, out.H1, out.H2)) return rc;
-	if (out.list.on) if (int rc = check_list_args(n_samp, out.list)) return rc;
+	if (out.list.on) if (int rc = check_list_args(m, n_samp, out.list)) return rc;
 	if (n_samp == 0) return 0;
 	std::lock_guard<std::mutex> g(m->lock);
 	HIP_TRY(hipSetDevice(m->device));
@@ -914,7 +922,7 @@ static int predict_mapped_entry(hibag_hip_model *m, const int32_t *geno, int n_s
 	const int32_t *snp_col, const int32_t *flip, int vote_method, const PredictOut &out)
 {
 	if (int rc = check_predict_args(m, geno, n_samp, vote_method, out.H1, out.H2)) return rc;
-	if (out.list.on) if (int rc = check_list_args(n_samp, out.list)) return rc;
+	if (out.list.on) if (int rc = check_list_args(m, n_samp, out.list)) return rc;
 	if (n_geno_snp <= 0) return hibag_fail(HIBAG_HIP_EINVAL, "n_geno_snp must be positive");
 	if (!snp_col && m->n_snp > 0) return hibag_fail(HIBAG_HIP_EINVAL, "snp_col is NULL");
 	for (int k = 0; k < m->n_snp; k++)
@@ -956,7 +964,7 @@ static int predict_snp_major_entry(hibag_hip_model *m, const int32_t *geno, size
 	const int32_t *snp_col, const int32_t *flip, int vote_method, const PredictOut &out)
 {
 	if (int rc = check_predict_args(m, geno, n_samp, vote_method, out.H1, out.H2)) return rc;
-	if (out.list.on) if (int rc = check_list_args(n_samp, out.list)) return rc;
+	if (out.list.on) if (int rc = check_list_args(m, n_samp, out.list)) return rc;
 	if (n_geno_snp <= 0) return hibag_fail(HIBAG_HIP_EINVAL, "n_geno_snp must be positive");
 	if (ld < (size_t)n_samp) return hibag_fail(HIBAG_HIP_EINVAL, "ld = %zu is smaller than n_samp = %d", ld, n_samp);
 	if (!snp_col && m->n_snp > n_geno_snp)
@@ -1058,7 +1066,7 @@ static int predict_bed_entry(hibag_hip_model *m, const char *bed_fn, int n_samp,
 	const int32_t *snp_col, const int32_t *flip, int vote_method, const PredictOut &out)
 {
 	if (int rc = check_predict_args(m, bed_fn, n_samp, vote_method, out.H1, out.H2)) return rc;
-	if (out.list.on) if (int rc = check_list_args(n_samp, out.list)) return rc;
+	if (out.list.on) if (int rc = check_list_args(m, n_samp, out.list)) return rc;
 	if (!snp_col && m->n_snp > 0) return hibag_fail(HIBAG_HIP_EINVAL, "snp_col is NULL");
 	BedImage img;
 	if (int rc = load_bed(bed_fn, n_samp, n_snp, snp_col, m->n_snp, img)) return rc;
@@ -1162,6 +1170,47 @@ int hibag_hip_predict_draw_bed(hibag_hip_model *m, const char *bed_fn, int n_sam
 {
 	return predict_bed_entry(m, bed_fn, n_samp, n_snp, snp_col, flip, vote_method,
 		PredictOut::draw(n_draw, seed, sample0, h1, h2, prob, matching));
+}
+
+// ---- calls over allele groups (include/hibag_hip.h "allele groups") -------------------------------------------------
+// The same fronts with the group output set: k_finish_groups with the plan's lists (hibag_groups.hip) in place of the others.
+
+int hibag_hip_predict_groups(hibag_hip_model *m, const int32_t *geno, int n_samp, int vote_method, const hibag_hip_groups *plan,
+	int32_t *g1, int32_t *g2, double *prob, double *matching, double *dosage)
+{
+	return predict_entry(m, geno, n_samp, vote_method, PredictOut::groups(plan, g1, g2, prob, matching, dosage));
+}
+
+int hibag_hip_predict_groups_device(hibag_hip_model *m, const int32_t *d_geno, int n_samp, int vote_method,
+	const hibag_hip_groups *plan, int32_t *d_g1, int32_t *d_g2, double *d_prob, double *d_matching, double *d_dosage, void *stream)
+{
+	PackSource src;
+	src.d_geno = d_geno;
+	return predict_device_entry(m, src, n_samp, vote_method, PredictOut::groups(plan, d_g1, d_g2, d_prob, d_matching, d_dosage), stream);
+}
+
+int hibag_hip_predict_groups_mapped(hibag_hip_model *m, const int32_t *geno, int n_samp, int n_geno_snp,
+	const int32_t *snp_col, const int32_t *flip, int vote_method, const hibag_hip_groups *plan,
+	int32_t *g1, int32_t *g2, double *prob, double *matching, double *dosage)
+{
+	return predict_mapped_entry(m, geno, n_samp, n_geno_snp, snp_col, flip, vote_method,
+		PredictOut::groups(plan, g1, g2, prob, matching, dosage));
+}
+
+int hibag_hip_predict_groups_snp_major(hibag_hip_model *m, const int32_t *geno, size_t ld, int n_samp, int n_geno_snp,
+	const int32_t *snp_col, const int32_t *flip, int vote_method, const hibag_hip_groups *plan,
+	int32_t *g1, int32_t *g2, double *prob, double *matching, double *dosage)
+{
+	return predict_snp_major_entry(m, geno, ld, n_samp, n_geno_snp, snp_col, flip, vote_method,
+		PredictOut::groups(plan, g1, g2, prob, matching, dosage));
+}
+
+int hibag_hip_predict_groups_bed(hibag_hip_model *m, const char *bed_fn, int n_samp, int n_snp,
+	const int32_t *snp_col, const int32_t *flip, int vote_method, const hibag_hip_groups *plan,
+	int32_t *g1, int32_t *g2, double *prob, double *matching, double *dosage)
+{
+	return predict_bed_entry(m, bed_fn, n_samp, n_snp, snp_col, flip, vote_method,
+		PredictOut::groups(plan, g1, g2, prob, matching, dosage));
 }
 
 int hibag_hip_predict_partial_device(hibag_hip_model *m, const int32_t *d_geno, int n_samp,

@@ -489,6 +489,59 @@ class HlaAttrBagClass:
             self.handle, p(d_geno), int(n_samp), int(vote_method), int(n), seed, sample0, p(d_h1), p(d_h2), p(d_prob),
             p(d_matching), p(stream)))
 
+    # --- the group entries: per sample and partition of the alleles the best pair of groups under the collapsed posterior
+    # (hibag_hip_predict_groups and its routes; include/hibag_hip.h "allele groups"): the routes above with the group tail.
+    def groups_plan(self, groups) -> "GroupsPlan":
+        """The device plan of ``groups`` -- an ``HlaAlleleGroups`` (``hibag_amd.groups``) or an integer matrix
+        [n_part, n_hla] of group ids -- for this model (``hibag_hip_groups_create``).  Made once, used by any number of
+        ``predict_groups*`` calls of this model; ``close()`` frees it."""
+        return GroupsPlan(self, getattr(groups, "group_of", groups))
+
+    def _groups(self, plan, want_dosage: bool):
+        if not isinstance(plan, GroupsPlan):
+            raise TypeError("plan must come from HlaAttrBagClass.groups_plan()")
+        q, d = plan.n_part, plan.n_level
+        return ("hibag_hip_predict_groups", (plan.handle,), ("g1", "g2", "prob", "matching", "dosage"),
+                lambda n: dict(g1=np.empty((n, q), np.int32), g2=np.empty((n, q), np.int32), prob=np.empty((n, q), np.float64),
+                               matching=np.empty(n, np.float64), **({"dosage": np.empty((n, d), np.float64)} if want_dosage else {})))
+
+    def predict_groups(self, genomat: np.ndarray, plan, vote_method: int = 1, want_dosage: bool = True) -> dict:
+        """``hibag_hip_predict_groups``: per sample and partition of ``plan`` the best pair of groups under the posterior
+        collapsed over the groups -- ``g1``, ``g2`` (group indices, g1 <= g2, NA = INT_MIN where no pair qualifies) and
+        ``prob``, each [n_samp, n_part] --, ``matching`` [n_samp] and, with ``want_dosage``, the expected dosage of every
+        group ``dosage`` [n_samp, n_level] (partition q's groups from ``plan.offsets[q]``).  With the identity partition these
+        are ``predict_raw``'s ``h1``, ``h2``, ``prob`` and ``dosage`` bit for bit.  ``genomat`` int32
+        [n_samp, n_snp]."""
+        return self._call(self._route_raw(genomat), vote_method, self._groups(plan, want_dosage))
+
+    def predict_groups_mapped(self, genomat: np.ndarray, snp_col: np.ndarray, flip: Optional[np.ndarray], plan,
+                              vote_method: int = 1, want_dosage: bool = True) -> dict:
+        """:meth:`predict_groups` on the cohort's own matrix [n_samp, n_geno_snp], as :meth:`predict_mapped`."""
+        return self._call(self._route_mapped(genomat, snp_col, flip), vote_method, self._groups(plan, want_dosage))
+
+    def predict_groups_snp_major(self, genomat: np.ndarray, snp_col: Optional[np.ndarray], flip: Optional[np.ndarray], plan,
+                                 vote_method: int = 1, want_dosage: bool = True) -> dict:
+        """:meth:`predict_groups` on a SNP-major matrix [n_geno_snp, n_samp] in C order, as :meth:`predict_snp_major`."""
+        return self._call(self._route_snp_major(genomat, snp_col, flip), vote_method, self._groups(plan, want_dosage))
+
+    def predict_groups_bed(self, bed_fn: str, n_samp: int, n_snp: int, snp_col: np.ndarray, flip: Optional[np.ndarray], plan,
+                           vote_method: int = 1, want_dosage: bool = True) -> dict:
+        """:meth:`predict_groups` on every sample of a PLINK BED file, as :meth:`predict_bed`."""
+        return self._call(self._route_bed(bed_fn, n_samp, n_snp, snp_col, flip), vote_method, self._groups(plan, want_dosage))
+
+    def predict_groups_cohort(self, cohort, snp_col: np.ndarray, flip: Optional[np.ndarray], plan, vote_method: int = 1,
+                              want_dosage: bool = True, first: int = 0, count: Optional[int] = None) -> dict:
+        """:meth:`predict_groups` on samples ``[first, first + count)`` of a resident cohort, as :meth:`predict_cohort`."""
+        return self._call(self._route_cohort(cohort, snp_col, flip, first, count), vote_method, self._groups(plan, want_dosage))
+
+    def predict_groups_device(self, d_geno, n_samp: int, plan, d_g1, d_g2, d_prob, d_matching=None, d_dosage=None,
+                              vote_method: int = 1, stream=None):
+        """Device-pointer form of :meth:`predict_groups`; pointer arguments are ints (``tensor.data_ptr()``) or None."""
+        p = _dev_ptr
+        _lib.check(_lib.lib().hibag_hip_predict_groups_device(
+            self.handle, p(d_geno), int(n_samp), int(vote_method), plan.handle, p(d_g1), p(d_g2), p(d_prob), p(d_matching),
+            p(d_dosage), p(stream)))
+
     def predict_device(self, d_geno, n_samp: int, vote_method: int = 1, d_h1=None, d_h2=None, d_prob=None,
                        d_matching=None, d_dosage=None, d_postprob=None, stream=None):
         """Device-pointer form; arguments are ints (``tensor.data_ptr()``) or None."""
@@ -511,6 +564,63 @@ class HlaAttrBagClass:
         _lib.check(_lib.lib().hibag_hip_finish_device(
             self.handle, p(d_partial), int(n_samp), p(d_h1), p(d_h2), p(d_prob), p(d_matching), p(d_dosage),
             p(d_postprob), p(stream)))
+
+
+class GroupsPlan:
+    """``hibag_hip_groups``: partitions of one model's alleles as the lists the group finish walks, on the model's device.
+    ``group_of`` int32 [n_part, n_hla]; ``levels[q]`` the number of groups of partition q, ``offsets`` [n_part + 1] where its
+    groups start in a row of the dosage output, ``n_level`` their total."""
+
+    def __init__(self, model: HlaAttrBagClass, group_of):
+        g = np.asarray(group_of)
+        if g.dtype.kind not in "iu" or g.ndim != 2 or g.shape[1] != model.obj.n_hla:
+            raise ValueError(f"group_of must be an integer matrix [n_part, n_hla = {model.obj.n_hla}]")
+        self.group_of = np.ascontiguousarray(g, np.int32)
+        if not np.array_equal(self.group_of, g):
+            raise ValueError("group_of holds ids an int32 cannot hold")
+        self.model = model
+        self._h = None
+        h = C.c_void_p()
+        _lib.check(_lib.lib().hibag_hip_groups_create(model.handle, int(g.shape[0]), _as_ptr(self.group_of), C.byref(h)))
+        self._h = h
+        self.n_part = int(g.shape[0])
+        lv = np.empty(self.n_part, np.int32)
+        _lib.check(_lib.lib().hibag_hip_groups_levels(self._h, _as_ptr(lv)))
+        self.levels = lv
+        self.offsets = np.concatenate([[0], np.cumsum(lv, dtype=np.int64)])
+        self.n_level = int(self.offsets[-1])
+
+    @property
+    def handle(self) -> C.c_void_p:
+        if self._h is None:
+            raise HibagHipError(-4, "the plan has been closed")
+        return self._h
+
+    def tile(self):
+        """(samples per workgroup of the finish kernel, whether their posteriors are staged in LDS) as the launcher decides
+        them now (``HIBAG_GROUPS_NO_LDS=1`` in the environment forces the direct path)."""
+        lds = C.c_int(0)
+        t = int(_lib.lib().hibag_hip_groups_tile(self.handle, C.byref(lds)))
+        if t < 0:
+            _lib.check(t)
+        return t, bool(lds.value)
+
+    def close(self):
+        if getattr(self, "_h", None) is not None:
+            _lib.lib().hibag_hip_groups_free(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def multi_slice(n_samp: int, n_models: int, i: int):

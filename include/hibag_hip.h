@@ -590,6 +590,65 @@ int hibag_hip_predict_draw_cohort(hibag_hip_model *m, const hibag_hip_cohort *c,
 	const int32_t *flip, int vote_method, int n_draw, uint64_t seed, int64_t sample0, int32_t *h1, int32_t *h2, double *prob,
 	double *matching);
 
+/* ---- allele groups: calls under the posterior collapsed over groups of alleles: hlaPredictGroups ----------------
+ * Imputed types are mostly analysed at a coarser level than the four-digit pair: two-digit types, P / G groups, serological
+ * groups, the amino acid at a position of the protein.  Each is a PARTITION of the model's alleles into groups, and the call
+ * at that level is the maximum of the collapsed posterior -- the pair posterior summed over the allele pairs that fall into
+ * each pair of groups --, not the relabelled allele-level call.  A plan holds n_part partitions of one model's alleles; the
+ * group entries compute, per sample and partition, on the device from the ensemble sums: the best pair of groups, its
+ * probability and (optionally) the expected dosage of every group.  n_part * 16 + 8 bytes per sample come back (+ 8 per group
+ * with the dosages) instead of 8 * n_hla (n_hla + 1) / 2.
+ * The rule (exact), p[c] the sample's NORMALISED posterior in pair order -- the values the postprob output of
+ * hibag_hip_predict holds for that vote_method --, cell c = the pair (h1 <= h2), m(h) in 0 .. G - 1 the group of allele h:
+ *   bin (a <= b) has index b + a (2 G - a - 1) / 2; a cell belongs to the bin (min, max) of (m(h1), m(h2));
+ *   B[bin] = the sum of p[c] over the bin's cells in increasing c, plain double additions from +0.0 (no FMA); empty: +0.0;
+ *   the call is the first bin in bin order with best < B strictly, best starting at 0 (hibag_hip_predict's own rule, on
+ *   bins); a bin whose sum is NaN never wins;
+ *   D[g] = the sum, over the cells with m(h1) = g or m(h2) = g in increasing c, of p[c] -- or 2 p[c] where both are.
+ * With m(h) = h this is hibag_hip_predict's H1, H2, max_prob and dosage bit for bit.  Results do not depend on batches,
+ * routes, a repaired hand-over, the other partitions of the plan or on whether the dosages were asked for.
+ *   hibag_hip_groups_create  group_of[n_part][n_hla]: the group of every allele in every partition, ids 0 .. n_hla - 1
+ *                            (G = the largest id of the partition + 1; an id no allele has is an empty group that never
+ *                            wins and has dosage 0).  1 <= n_part <= HIBAG_HIP_GROUPS_MAX_PART, the G of all partitions
+ *                            together <= HIBAG_HIP_GROUPS_MAX_LEVELS; HIBAG_HIP_EINVAL otherwise.  The model must be
+ *                            finalized; the plan lives on its device and is taken with THAT model only (EINVAL otherwise).
+ *                            Freeing the model does not free its plans.
+ *   hibag_hip_groups_levels  counts[n_part] = G of every partition
+ *   hibag_hip_groups_tile    samples per workgroup of the finish kernel for this plan; *lds (may be NULL) = 1 if their
+ *                            posteriors are staged in LDS, 0 if the kernel reads the ensemble sums directly (the model's
+ *                            posterior does not fit, or HIBAG_GROUPS_NO_LDS=1 in the environment: read at every call)
+ * Outputs of the entries, sample-major:
+ *   g1, g2 [n_samp][n_part]   group indices (g1 <= g2); HIBAG_HIP_NA_INTEGER where no bin qualifies
+ *   prob   [n_samp][n_part]   the called bin's B; 0 where no bin qualifies, NaN in a poisoned batch
+ *   matching [n_samp]         as hibag_hip_predict; may be NULL
+ *   dosage [n_samp][D]        D = the G of all partitions together, partition q's groups from the sum of the G before it;
+ *                             may be NULL
+ * g1, g2 and prob are required.  Everything else is as for the draw entry of the same suffix, whose other arguments these
+ * take in the same order.  (Added within ABI version 7) */
+#define HIBAG_HIP_GROUPS_MAX_PART 512
+#define HIBAG_HIP_GROUPS_MAX_LEVELS 4096
+typedef struct hibag_hip_groups hibag_hip_groups;
+int hibag_hip_groups_create(hibag_hip_model *m, int n_part, const int32_t *group_of, hibag_hip_groups **plan);
+void hibag_hip_groups_free(hibag_hip_groups *plan);
+int hibag_hip_groups_levels(const hibag_hip_groups *plan, int32_t *counts);
+int hibag_hip_groups_tile(const hibag_hip_groups *plan, int *lds);
+int hibag_hip_predict_groups(hibag_hip_model *m, const int32_t *geno, int n_samp, int vote_method, const hibag_hip_groups *plan,
+	int32_t *g1, int32_t *g2, double *prob, double *matching, double *dosage);
+int hibag_hip_predict_groups_device(hibag_hip_model *m, const int32_t *d_geno, int n_samp, int vote_method,
+	const hibag_hip_groups *plan, int32_t *d_g1, int32_t *d_g2, double *d_prob, double *d_matching, double *d_dosage, void *stream);
+int hibag_hip_predict_groups_mapped(hibag_hip_model *m, const int32_t *geno, int n_samp, int n_geno_snp,
+	const int32_t *snp_col, const int32_t *flip, int vote_method, const hibag_hip_groups *plan,
+	int32_t *g1, int32_t *g2, double *prob, double *matching, double *dosage);
+int hibag_hip_predict_groups_snp_major(hibag_hip_model *m, const int32_t *geno, size_t ld, int n_samp, int n_geno_snp,
+	const int32_t *snp_col, const int32_t *flip, int vote_method, const hibag_hip_groups *plan,
+	int32_t *g1, int32_t *g2, double *prob, double *matching, double *dosage);
+int hibag_hip_predict_groups_bed(hibag_hip_model *m, const char *bed_fn, int n_samp, int n_snp,
+	const int32_t *snp_col, const int32_t *flip, int vote_method, const hibag_hip_groups *plan,
+	int32_t *g1, int32_t *g2, double *prob, double *matching, double *dosage);
+int hibag_hip_predict_groups_cohort(hibag_hip_model *m, const hibag_hip_cohort *c, int first, int count, const int32_t *snp_col,
+	const int32_t *flip, int vote_method, const hibag_hip_groups *plan, int32_t *g1, int32_t *g2, double *prob, double *matching,
+	double *dosage);
+
 /* ---- training: replaces HIBAG_Training + HIBAG_NewClassifiers ---------------- */
 
 typedef struct hibag_hip_trainer hibag_hip_trainer;  /* opaque handle */
