@@ -29,6 +29,8 @@ from .cohort import HlaDeviceCohort, hlaPredictLoci  # noqa: F401
 from .draws import HlaPosteriorDraws, hlaPredictDraws  # noqa: F401
 from .groups import (HlaAlleleGroups, HlaGroupCalls, hlaGroupsByMap, hlaGroupsByResolution, hlaGroupsBySequence,  # noqa: F401
                      hlaPredictGroups)
+from .given import (HlaAlleleConstraint, HlaGivenCalls, hlaConstraintFromAllele, hlaConstraintFromSets,  # noqa: F401
+                    hlaPredictGiven)
 from ._lib import HibagHipError  # noqa: F401
 
 __all__ = ["engine_kind", "engine_nkb", "engine_steps", "NA_INTEGER", "Classifier", "HlaAttrBagObj", "HlaSNPGeno", "load_geno", "load_model", "model_to_robj", "save_model",
@@ -38,4 +40,5 @@ __all__ = ["engine_kind", "engine_nkb", "engine_steps", "NA_INTEGER", "Classifie
            "hlaSplitAllele", "r_sample", "hlaOutOfBag", "hlaOutOfBagEnsemble", "out_of_bag_mask", "hlaGenoLD", "hlaLDMatrix", "hlaDistance",
            "hlaSubModelObj", "hlaCombineModelObj", "hlaPredictCurve", "HlaPredictCurve", "hlaPredictTopK", "HlaTopCalls",
            "HlaDeviceCohort", "hlaPredictLoci", "load_model_list", "hlaPredictDraws", "HlaPosteriorDraws",
+           "HlaAlleleConstraint", "HlaGivenCalls", "hlaConstraintFromAllele", "hlaConstraintFromSets", "hlaPredictGiven",
            "set_seed"]

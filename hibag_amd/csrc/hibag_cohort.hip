@@ -347,4 +347,14 @@ int hibag_hip_predict_groups_cohort(hibag_hip_model *m, const hibag_hip_cohort *
 	return predict_cohort_entry(m, c, first, count, snp_col, flip, vote_method, PredictOut::groups(plan, g1, g2, prob, matching, dosage));
 }
 
+// (`allow` is indexed like the outputs: by the call's sample, not by the cohort's)
+int hibag_hip_predict_given_cohort(hibag_hip_model *m, const hibag_hip_cohort *c, int first, int count, const int32_t *snp_col,
+	const int32_t *flip, int vote_method, const uint32_t *allow, int32_t *h1, int32_t *h2, double *prob, double *support,
+	double *matching, double *dosage)
+{
+	if (int rc = check_given_model(m)) return rc;
+	return predict_cohort_entry(m, c, first, count, snp_col, flip, vote_method,
+		PredictOut::given_sets(m, allow, h1, h2, prob, support, matching, dosage));
+}
+
 } // extern "C"

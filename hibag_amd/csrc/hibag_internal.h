@@ -188,6 +188,9 @@ struct hibag_hip_model {
 
 	// per-batch workspace (grow-only)
 	DevBuf ws_planes, ws_cw, ws_tot, ws_inv, ws_winv, ws_part, ws_best, ws_vrec, ws_geno, ws_out, ws_codes, ws_bt, ws_bias, ws_cells, ws_sync;
+	// the given entries (hibag_hip_predict_given*): a host-pointer call's constraint on the device, sample-major as the caller
+	// gave it, and a batch's masks as k_finish_given reads them ([2 W][n_pad])
+	DevBuf ws_allow, ws_masks;
 	std::vector<int> engine_of, steps_of;  // per classifier: HIBAG_HIP_ENGINE_* and K steps, as finalized
 	int store_mode = 0;                    // which cell sums pass 1 stores for pass 2 (HibagModelView::store_cells)
 	int64_t second_pass_pairs = 0;         // haplotype pairs per sample pass 2 evaluates again
@@ -252,7 +255,7 @@ struct hibag_hip_model {
 		if (dist_st) (void)hipStreamDestroy(dist_st);
 		for (hipEvent_t e : dist_ev) if (e) (void)hipEventDestroy(e);
 		for (DevBuf *b : {&d_int, &d_stream, &d_tile, &d_tab, &d_blk, &d_pfac, &d_phdr, &d_parow, &ws_bt, &ws_bias, &ws_cells, &ws_sync, &ws_err, &ws_planes, &ws_cw, &ws_tot, &ws_inv, &ws_winv,
-		                  &ws_part, &ws_best, &ws_vrec, &ws_geno, &ws_out, &ws_codes, &ws_bed, &ws_bedidx, &oob_hap,
+		                  &ws_part, &ws_best, &ws_vrec, &ws_geno, &ws_out, &ws_codes, &ws_allow, &ws_masks, &ws_bed, &ws_bedidx, &oob_hap,
 		                  &dist_cells, &dist_tri, &dist_acc, &dist_num, &dist_out, &pfx_tab, &pfx_cw, &pfx_best, &pfx_cell,
 		                  &mask_idx, &mask_use, &mask_cnt})
 			b->release();
@@ -297,7 +300,9 @@ struct PackSource {
 // the group entries (hibag_hip_predict_groups*): per sample k pairs and their probabilities, [n_samp][k] each.  With it the
 // finish is k_finish_topk (the k best pairs), with `draws` set k_finish_draw (k = n_draw pairs drawn from the posterior), with
 // `plan` set k_finish_groups (k = the plan's partitions: per partition the best pair of groups, and optionally the group
-// dosages) instead of the call / dosage / posterior kernels.
+// dosages), with `given` set k_finish_given (k = 1: the best pair among the cells consistent with the sample's two allele sets
+// `allow`, a per-sample INPUT that travels with the outputs; `support`, and optionally the restricted allele dosages) instead
+// of the call / dosage / posterior kernels.
 struct ListOut {
 	bool on = false;                       // the call is a list entry's
 	int k = 0;                             // pairs per sample: the k of the top-k entries, the n_draw of the draw entries
@@ -309,7 +314,12 @@ struct ListOut {
 	bool groups = false;                   // the group finish runs (h1 / h2: group indices) ...
 	const hibag_hip_groups *plan = nullptr; // ... with this plan's lists ...
 	double *dosage = nullptr;              // ... and, if asked for, the group dosages [n_samp][levels()]
-	size_t levels() const { return plan ? (size_t)plan->view.n_level : 0; }
+	bool given = false;                    // the given finish runs (k = 1) ...
+	int n_hla = 0;                         // ... on a model of so many alleles (dosage: the restricted allele dosages [n_samp][n_hla]) ...
+	double *support = nullptr;             // ... with the consistent cells' posterior mass [n_samp] ...
+	const uint32_t *allow = nullptr;       // ... under the samples' sets [n_samp][2][W]: where the outputs are (host / device)
+	size_t levels() const { return plan ? (size_t)plan->view.n_level : given ? (size_t)n_hla : 0; }
+	size_t allow_words() const { return given ? (size_t)2 * (((size_t)n_hla + 31) / 32) : 0; }      // of one sample
 };
 
 // What a prediction call returns, the one "outputs" parameter of the drivers: the six per-sample outputs of PredictHLA (any
@@ -342,6 +352,8 @@ struct PredictOut {
 		o.list.groups = true; o.list.plan = plan; o.list.dosage = dosage;
 		return o;
 	}
+	static PredictOut given_sets(const hibag_hip_model *m, const uint32_t *allow, int32_t *h1, int32_t *h2, double *prob, double *support,
+		double *matching, double *dosage);         // (hibag_predict.hip: reads the model's allele count)
 	// the set `s0` samples further on (null stays null; a draw is keyed with the sample's index in the caller's numbering)
 	PredictOut advanced(size_t s0, size_t n_hla, size_t n_cell) const
 	{
@@ -351,6 +363,7 @@ struct PredictOut {
 		adv(o.dosage, s0 * n_hla); adv(o.postprob, s0 * n_cell);
 		adv(o.list.h1, s0 * (size_t)list.k); adv(o.list.h2, s0 * (size_t)list.k); adv(o.list.prob, s0 * (size_t)list.k);
 		adv(o.list.dosage, s0 * list.levels());
+		adv(o.list.support, s0); adv(o.list.allow, s0 * list.allow_words());
 		o.list.sample0 += (int64_t)s0;
 		return o;
 	}
@@ -393,6 +406,7 @@ void enqueue_pack(hibag_hip_model *m, HibagBatchView &B, const PackSource &src, 
 void run_core(hibag_hip_model *m, HibagBatchView &B, int vote_method, double *d_part, hipStream_t st);   // passes 1 and 2 behind a pack
 int check_predict_args(hibag_hip_model *m, const void *geno, int n_samp, int vote_method, const void *H1, const void *H2);
 int check_list_args(const hibag_hip_model *m, int n_samp, const ListOut &list);       // the list entries' own arguments, behind check_predict_args
+int check_given_model(const hibag_hip_model *m);             // the given entries' first look at the model, before check_predict_args
 bool take_fault(hibag_hip_model *m);                         // a hand-over failed since the last look: counted, hand-overs off
 int sticky_fault(hibag_hip_model *m);
 int workspace_enter(hibag_hip_model *m, hipStream_t st);

@@ -73,6 +73,13 @@ struct HibagGroupsView {
 int hibag_groups_tile(int n_cell, int n_part, int *lds);
 void hibag_launch_finish_groups(const HibagModelView &M, const HibagBatchView &B, double *d_part, const HibagGroupsView &V,
 	int32_t *d_G1, int32_t *d_G2, double *d_prob, double *d_matching, double *d_dosage, hipStream_t st);
+// The finish of the given entries (hibag_k_given.h), launched INSTEAD of hibag_launch_finish: per sample the best allele pair
+// among the cells consistent with the sample's two allele sets, d_H1 / d_H2 / d_prob (joint) / d_support [n_samp], d_matching
+// [n_samp] (may be nullptr) and the restricted dosages d_dosage [n_samp][n_hla] (may be nullptr).  d_allow: the batch's sets,
+// uint32 [n_samp][2][W] with W = (n_hla + 31) / 32, on the device; d_masks: 2 W n_pad words of workspace.
+void hibag_launch_finish_given(const HibagModelView &M, const HibagBatchView &B, double *d_part, const uint32_t *d_allow,
+	uint32_t *d_masks, int32_t *d_H1, int32_t *d_H2, double *d_prob, double *d_support, double *d_matching, double *d_dosage,
+	hipStream_t st);
 // hlaOutOfBag (hibag_k_oob.h): each classifier predicts its own out-of-bag samples.  The per-classifier arrays are
 // [C][ld] with the batch's sample 0 at column 0 (the caller offsets the pointers); the plain haplotype table (grouped by
 // allele, hla_start[c][n_hla + 1] relative to hap_off[c]) serves the rare lane whose record log cannot settle its call.

@@ -85,6 +85,7 @@ static_assert(2 * HIBAG_FP4_MAX_SNPS + 1 <= ACCUM_TAB_N, "pass 2's table must co
 #include "hibag_k_topk.h"
 #include "hibag_k_draw.h"
 #include "hibag_k_groups.h"
+#include "hibag_k_given.h"
 #include "hibag_k_oob.h"
 #include "hibag_k_mask.h"
 #include "hibag_k_cohort.h"
@@ -381,6 +382,23 @@ void hibag_launch_finish_groups(const HibagModelView &M, const HibagBatchView &B
 	else
 		hipLaunchKernelGGL(k_finish_groups<false>, grid, dim3(GROUPS_THREADS), 0, st, M, B,
 			(const double *)d_part, V, tile, d_G1, d_G2, d_prob, d_matching, d_dosage);
+}
+
+// the finish of the given entries, in place of hibag_launch_finish (hibag_k_given.h): the batch's constraint transposed into
+// d_masks ([2 W][n_pad] words of the caller's workspace), the walk, and -- if asked for -- the dosage as a second launch
+void hibag_launch_finish_given(const HibagModelView &M, const HibagBatchView &B, double *d_part, const uint32_t *d_allow,
+	uint32_t *d_masks, int32_t *d_H1, int32_t *d_H2, double *d_prob, double *d_support, double *d_matching, double *d_dosage,
+	hipStream_t st)
+{
+	if (B.n_samp < 1 || M.n_hla < 1) return;
+	const int W = (M.n_hla + 31) / 32;
+	const size_t words = (size_t)2 * W * (size_t)B.n_pad;
+	hipLaunchKernelGGL(k_given_masks, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, st, d_allow, B.n_samp, B.n_pad, 2 * W, d_masks);
+	hipLaunchKernelGGL(k_finish_given, dim3(B.n_pad / 64), dim3(64), 0, st, M, B, (const double *)d_part,
+		(const uint32_t *)d_masks, W, d_H1, d_H2, d_prob, d_support, d_matching);
+	if (d_dosage)
+		hipLaunchKernelGGL(k_given_dosage, dim3(B.n_pad / 64, (M.n_hla + FIN_SEG - 1) / FIN_SEG), dim3(64 * FIN_SEG), 0, st, M, B,
+			(const double *)d_part, (const uint32_t *)d_masks, W, d_dosage);
 }
 
 void hibag_launch_oob(const HibagModelView &M, const HibagBatchView &B, const uint8_t *d_codes, const HibagOobOut &O,

@@ -135,10 +135,33 @@ int check_predict_args(hibag_hip_model *m, const void *geno, int n_samp, int vot
 	return 0;
 }
 
+// The given entries state their rejections as HIBAG_HIP_EINVAL throughout (include/hibag_hip.h "partial typing"), the
+// unfinalized model too, which check_predict_args reports as ESTATE to the older entries.
+int check_given_model(const hibag_hip_model *m)
+{
+	if (m && !m->finalized) return hibag_fail(HIBAG_HIP_EINVAL, "model not finalized");
+	return 0;
+}
+
+PredictOut PredictOut::given_sets(const hibag_hip_model *m, const uint32_t *allow, int32_t *h1, int32_t *h2, double *prob,
+	double *support, double *matching, double *dosage)
+{
+	PredictOut o = topk(1, h1, h2, prob, matching);
+	o.list.given = true; o.list.n_hla = m ? m->n_hla : 0;
+	o.list.allow = allow; o.list.support = support; o.list.dosage = dosage;
+	return o;
+}
+
 // the top-k and the draw entries' own arguments, behind check_predict_args
 int check_list_args(const hibag_hip_model *m, int n_samp, const ListOut &list)
 {
 	static_assert(HIBAG_HIP_TOPK_MAX == HIBAG_TOPK_MAX && HIBAG_HIP_DRAW_MAX == HIBAG_DRAW_MAX, "the public bounds are the kernels' bounds");
+	if (list.given) {
+		if (n_samp > 0 && !list.allow) return hibag_fail(HIBAG_HIP_EINVAL, "allow is NULL");
+		if (n_samp > 0 && (!list.h1 || !list.h2 || !list.prob || !list.support))
+			return hibag_fail(HIBAG_HIP_EINVAL, "h1, h2, prob and support are all required");
+		return 0;
+	}
 	if (list.groups) {
 		if (!list.plan) return hibag_fail(HIBAG_HIP_EINVAL, "the group plan is NULL");
 		if (list.plan->model != m) return hibag_fail(HIBAG_HIP_EINVAL, "the group plan was made for another model");
@@ -218,6 +241,8 @@ static int predict_device_locked(hibag_hip_model *m, const PackSource &src, int 
 	// must be chained behind it (an error in a later batch used to skip the record).
 	WorkspaceGuard guard{m, st};
 	const int lim = batch_limit(m);
+	if (out.list.on && out.list.given && n_samp > 0)       // a batch's masks, word-major ([2 W][n_pad]: hibag_k_given.h)
+		if (int rc = m->ws_masks.reserve(out.list.allow_words() * (size_t)round_up(std::min(lim, n_samp), HIBAG_WAVE) * sizeof(uint32_t))) return rc;
 	for (int s0 = 0; s0 < n_samp; s0 += lim) {
 		const int n = std::min(lim, n_samp - s0);
 		HibagBatchView B;
@@ -227,7 +252,10 @@ static int predict_device_locked(hibag_hip_model *m, const PackSource &src, int 
 		run_core(m, B, vote_method, m->ws_part.as<double>(), st);
 		const PredictOut o = out.advanced((size_t)s0, (size_t)m->n_hla, (size_t)m->view.n_cell);
 		m->timer.begin(HIBAG_HIP_K_FINISH, st, true);
-		if (o.list.on && o.list.groups)
+		if (o.list.on && o.list.given)
+			hibag_launch_finish_given(m->view, B, B.part, o.list.allow, m->ws_masks.as<uint32_t>(), o.list.h1, o.list.h2, o.list.prob,
+				o.list.support, o.matching, o.list.dosage, st);
+		else if (o.list.on && o.list.groups)
 			hibag_launch_finish_groups(m->view, B, B.part, o.list.plan->view, o.list.h1, o.list.h2, o.list.prob, o.matching, o.list.dosage, st);
 		else if (o.list.on && o.list.draws)
 			hibag_launch_finish_draw(m->view, B, B.part, o.list.k, o.list.seed, o.list.sample0, o.list.h1, o.list.h2, o.list.prob,
@@ -280,21 +308,23 @@ int staged_slice(const hibag_hip_model *m, int n_samp, size_t row_len)
 // vectors, so that a slice still comes down in one copy.
 struct SliceLayout {
 	PredictOut want;                       // the caller's set: which outputs are asked for, and where they go in the end
-	size_t nh = 0, P = 0, tk = 0, gd = 0;  // (gd: group dosages per sample, if asked for)
-	size_t o_h1 = 0, o_h2 = 0, o_mp = 0, o_mt = 0, o_ds = 0, o_pp = 0, o_t1 = 0, o_t2 = 0, o_tp = 0, o_gd = 0;
+	size_t nh = 0, P = 0, tk = 0, gd = 0, sp = 0;  // (gd: group or given dosages per sample, if asked for; sp: 1 with the given entries' support)
+	size_t o_h1 = 0, o_h2 = 0, o_mp = 0, o_mt = 0, o_ds = 0, o_pp = 0, o_t1 = 0, o_t2 = 0, o_tp = 0, o_sp = 0, o_gd = 0;
 	size_t bytes = 0;                      // of the buffer of one slice
 
 	SliceLayout() = default;
 	SliceLayout(size_t slice, size_t n_hla, size_t n_cell, const PredictOut &out)
-		: want(out), nh(n_hla), P(n_cell), tk(out.list.on ? (size_t)out.list.k : 0), gd(out.list.on && out.list.dosage ? out.list.levels() : 0)
+		: want(out), nh(n_hla), P(n_cell), tk(out.list.on ? (size_t)out.list.k : 0), gd(out.list.on && out.list.dosage ? out.list.levels() : 0),
+		  sp(out.list.on && out.list.given ? 1 : 0)
 	{
 		o_h2 = o_h1 + slice * 4; o_mp = (o_h2 + slice * 4 + 7) / 8 * 8; o_mt = o_mp + slice * 8; o_ds = o_mt + slice * 8;
 		o_pp = o_ds + slice * nh * 8;
-		o_t1 = o_ds; o_t2 = o_t1 + slice * tk * 4; o_tp = o_t2 + slice * tk * 4; o_gd = o_tp + slice * tk * 8;      // (the group dosages: behind the lists)
+		o_t1 = o_ds; o_t2 = o_t1 + slice * tk * 4; o_tp = o_t2 + slice * tk * 4;
+		o_sp = o_tp + slice * tk * 8; o_gd = o_sp + slice * sp * 8;      // (the support, then the group dosages: behind the lists)
 		bytes = ((want.list.on ? o_gd + slice * gd * 8 : o_pp + (want.postprob ? slice * P * 8 : 0)) + 255) / 256 * 256;
 	}
 	// bytes from the start of the buffer that a slice of n samples uses: of the vectors (the lists ride along), of everything asked for
-	size_t vectors(size_t n) const { return want.list.on ? o_tp + n * tk * 8 : o_ds; }
+	size_t vectors(size_t n) const { return want.list.on ? (sp ? o_sp + n * 8 : o_tp + n * tk * 8) : o_ds; }
 	size_t used(size_t n) const { return want.list.on ? (gd ? o_gd + n * gd * 8 : vectors(n)) : want.postprob ? o_pp + n * P * 8 : want.dosage ? o_ds + n * nh * 8 : o_ds; }
 	// the output set of a slice in the buffer at `base`: what is asked for, null for the rest
 	PredictOut bind(char *base) const
@@ -307,6 +337,7 @@ struct SliceLayout {
 		if (want.dosage) d.dosage = (double *)(base + o_ds);
 		if (want.postprob) d.postprob = (double *)(base + o_pp);
 		if (want.list.on) { d.list.h1 = (int32_t *)(base + o_t1); d.list.h2 = (int32_t *)(base + o_t2); d.list.prob = (double *)(base + o_tp); }
+		if (sp) d.list.support = (double *)(base + o_sp);
 		if (gd) d.list.dosage = (double *)(base + o_gd);
 		return d;
 	}
@@ -322,6 +353,7 @@ struct SliceLayout {
 		if (d.list.on) {
 			memcpy(d.list.h1, s.list.h1, n * tk * 4); memcpy(d.list.h2, s.list.h2, n * tk * 4);
 			memcpy(d.list.prob, s.list.prob, n * tk * 8);
+			if (sp) memcpy(d.list.support, s.list.support, n * 8);
 			if (matrices && gd) memcpy(d.list.dosage, s.list.dosage, n * gd * 8);
 		}
 	}
@@ -356,6 +388,7 @@ struct StagedRun {
 	char *dev_out(int i) const { return m->ws_out.as<char>() + (size_t)(i % nbuf) * L.bytes; }
 	char *pin_out(int i) const { return (char *)m->pin_out.p + (size_t)(i & 1) * L.bytes; }
 	int plan();
+	int upload_allow();
 	int upload(int i);
 	int download(int i);
 	int drain(int i);
@@ -380,6 +413,8 @@ int StagedRun::plan()
 	if (host)
 		if (int rc = m->ws_geno.reserve(geno_bytes * nbuf)) return rc;
 	if (int rc = m->ws_out.reserve(L.bytes * nbuf)) return rc;
+	if (out.list.on && out.list.given)
+		if (int rc = m->ws_allow.reserve((size_t)n_samp * out.list.allow_words() * sizeof(uint32_t))) return rc;
 	if (int rc = staged_streams(m, &ss)) return rc;
 	if (piped) {
 		// pinned staging on the host side, so that every copy call returns at once and the host thread's own work -- filling
@@ -392,6 +427,18 @@ int StagedRun::plan()
 			if (int rc = m->pin_geno.reserve(geno_bytes)) return rc;          // (scattered rows are gathered on the host side)
 		if (int rc = m->pin_out.reserve(L.vectors((size_t)slice))) return rc;
 	}
+	return 0;
+}
+
+// host -> device of the call's constraint (the given entries), once per run -- so a run repeated after a failed hand-over
+// sends it again --, ahead of the first slice's genotypes on the stream they take: the upload stream of a pipelined run with
+// host genotypes (in order, so the first slice's `up` event stands for it too), the kernels' stream otherwise.  It is a few
+// words per sample; every slice reads its part of the one device copy.
+int StagedRun::upload_allow()
+{
+	if (!(out.list.on && out.list.given)) return 0;
+	HIP_TRY(hipMemcpyAsync(m->ws_allow.p, out.list.allow, (size_t)n_samp * out.list.allow_words() * sizeof(uint32_t),
+		hipMemcpyHostToDevice, piped && src.geno ? ss->in : ss->run));
 	return 0;
 }
 
@@ -477,6 +524,7 @@ int StagedRun::run()
 	static const bool trace = getenv("HIBAG_STAGED_TRACE") != nullptr;     // diagnostic: host time of each phase on stderr
 	auto now = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
 	double tr[6] = {now(), 0, 0, 0, 0, 0};
+	if (int rc = upload_allow()) return rc;
 	if (int rc = upload(0)) return rc;
 	if (trace) { if (!piped) (void)hipStreamSynchronize(ss->run); tr[1] = now(); }
 	for (int i = 0; i < n_slice; i++) {
@@ -491,6 +539,7 @@ int StagedRun::run()
 		if (piped && i >= 2) HIP_TRY(hipStreamWaitEvent(ss->run, ss->down[i & 1], 0));    // slice i - 2 has left the device output buffer
 		PredictOut d = L.bind(dev_out(i));
 		d.list.sample0 += s0;              // (a draw is keyed with the sample's index in the caller's numbering)
+		if (d.list.given) d.list.allow = m->ws_allow.as<uint32_t>() + (size_t)s0 * d.list.allow_words();      // (the slice's part of the device copy)
 		if (int rc = predict_device_locked(m, p, n, vote_method, d, ss->run)) return rc;
 		if (piped) HIP_TRY(hipEventRecord(ss->ran[i & 1], ss->run));
 		if (trace && piped) fprintf(stderr, "[hibag staged] slice %d enqueued at %.3f ms\n", i, now() - tr[0]);
@@ -1211,6 +1260,54 @@ int hibag_hip_predict_groups_bed(hibag_hip_model *m, const char *bed_fn, int n_s
 {
 	return predict_bed_entry(m, bed_fn, n_samp, n_snp, snp_col, flip, vote_method,
 		PredictOut::groups(plan, g1, g2, prob, matching, dosage));
+}
+
+// ---- calls given partial typing (include/hibag_hip.h "partial typing") ----------------------------------------------
+// The same fronts with the given output set: k_finish_given under the samples' allele sets `allow`, an input that is sliced
+// and advanced like the outputs.
+
+int hibag_hip_predict_given(hibag_hip_model *m, const int32_t *geno, int n_samp, int vote_method, const uint32_t *allow,
+	int32_t *h1, int32_t *h2, double *prob, double *support, double *matching, double *dosage)
+{
+	if (int rc = check_given_model(m)) return rc;
+	return predict_entry(m, geno, n_samp, vote_method, PredictOut::given_sets(m, allow, h1, h2, prob, support, matching, dosage));
+}
+
+int hibag_hip_predict_given_device(hibag_hip_model *m, const int32_t *d_geno, int n_samp, int vote_method, const uint32_t *d_allow,
+	int32_t *d_h1, int32_t *d_h2, double *d_prob, double *d_support, double *d_matching, double *d_dosage, void *stream)
+{
+	if (int rc = check_given_model(m)) return rc;
+	PackSource src;
+	src.d_geno = d_geno;
+	return predict_device_entry(m, src, n_samp, vote_method,
+		PredictOut::given_sets(m, d_allow, d_h1, d_h2, d_prob, d_support, d_matching, d_dosage), stream);
+}
+
+int hibag_hip_predict_given_mapped(hibag_hip_model *m, const int32_t *geno, int n_samp, int n_geno_snp,
+	const int32_t *snp_col, const int32_t *flip, int vote_method, const uint32_t *allow,
+	int32_t *h1, int32_t *h2, double *prob, double *support, double *matching, double *dosage)
+{
+	if (int rc = check_given_model(m)) return rc;
+	return predict_mapped_entry(m, geno, n_samp, n_geno_snp, snp_col, flip, vote_method,
+		PredictOut::given_sets(m, allow, h1, h2, prob, support, matching, dosage));
+}
+
+int hibag_hip_predict_given_snp_major(hibag_hip_model *m, const int32_t *geno, size_t ld, int n_samp, int n_geno_snp,
+	const int32_t *snp_col, const int32_t *flip, int vote_method, const uint32_t *allow,
+	int32_t *h1, int32_t *h2, double *prob, double *support, double *matching, double *dosage)
+{
+	if (int rc = check_given_model(m)) return rc;
+	return predict_snp_major_entry(m, geno, ld, n_samp, n_geno_snp, snp_col, flip, vote_method,
+		PredictOut::given_sets(m, allow, h1, h2, prob, support, matching, dosage));
+}
+
+int hibag_hip_predict_given_bed(hibag_hip_model *m, const char *bed_fn, int n_samp, int n_snp,
+	const int32_t *snp_col, const int32_t *flip, int vote_method, const uint32_t *allow,
+	int32_t *h1, int32_t *h2, double *prob, double *support, double *matching, double *dosage)
+{
+	if (int rc = check_given_model(m)) return rc;
+	return predict_bed_entry(m, bed_fn, n_samp, n_snp, snp_col, flip, vote_method,
+		PredictOut::given_sets(m, allow, h1, h2, prob, support, matching, dosage));
 }
 
 int hibag_hip_predict_partial_device(hibag_hip_model *m, const int32_t *d_geno, int n_samp,

@@ -542,6 +542,68 @@ class HlaAttrBagClass:
             self.handle, p(d_geno), int(n_samp), int(vote_method), plan.handle, p(d_g1), p(d_g2), p(d_prob), p(d_matching),
             p(d_dosage), p(stream)))
 
+    # --- the given entries: per sample the best allele pair among the cells consistent with two allele sets, a per-sample
+    # INPUT (hibag_hip_predict_given and its routes; include/hibag_hip.h "partial typing"): the routes above with the given tail.
+    def given_words(self) -> int:
+        """W: the uint32 words of one allele set of this model, (n_hla + 31) // 32."""
+        return (int(self.obj.n_hla) + 31) // 32
+
+    def _given(self, allow, want_dosage: bool):
+        a = getattr(allow, "pack", None)
+        a = np.asarray(a() if callable(a) else allow)
+        if a.dtype != np.uint32 or a.ndim != 3 or a.shape[1:] != (2, self.given_words()):
+            raise ValueError(f"allow must be a uint32 array [n_samp, 2, W = {self.given_words()}] (HlaAlleleConstraint.pack()), "
+                             f"got {a.dtype} {a.shape}")
+        a = np.ascontiguousarray(a)
+        nh = int(self.obj.n_hla)
+
+        def make(n):
+            if a.shape[0] != n:
+                raise ValueError(f"allow holds {a.shape[0]} samples, the genotypes {n}")
+            return dict(h1=np.empty(n, np.int32), h2=np.empty(n, np.int32), prob=np.empty(n, np.float64),
+                        support=np.empty(n, np.float64), matching=np.empty(n, np.float64),
+                        **({"dosage": np.empty((n, nh), np.float64)} if want_dosage else {}))
+        return ("hibag_hip_predict_given", (_as_ptr(a),), ("h1", "h2", "prob", "support", "matching", "dosage"), make)
+
+    def predict_given(self, genomat: np.ndarray, allow, vote_method: int = 1, want_dosage: bool = False) -> dict:
+        """``hibag_hip_predict_given``: per sample the best allele pair among the cells CONSISTENT with the sample's two
+        allele sets -- ``h1``, ``h2`` (0-based, h1 <= h2, NA = INT_MIN where no consistent cell qualifies), ``prob`` (that
+        cell's JOINT posterior), ``support`` (the consistent cells' posterior mass, added in pair order), ``matching``, each
+        [n_samp], and with ``want_dosage`` the allele ``dosage`` [n_samp, n_hla] restricted to the consistent cells (joint
+        too).  ``allow``: uint32 [n_samp, 2, W] (allele h = bit h % 32 of word h // 32 of set A (0) or B (1)), or an
+        ``HlaAlleleConstraint``.  With both sets full these are ``predict_raw``'s ``h1``, ``h2``, ``prob`` and ``dosage`` bit
+        for bit.  ``genomat`` int32 [n_samp, n_snp]."""
+        return self._call(self._route_raw(genomat), vote_method, self._given(allow, want_dosage))
+
+    def predict_given_mapped(self, genomat: np.ndarray, snp_col: np.ndarray, flip: Optional[np.ndarray], allow,
+                             vote_method: int = 1, want_dosage: bool = False) -> dict:
+        """:meth:`predict_given` on the cohort's own matrix [n_samp, n_geno_snp], as :meth:`predict_mapped`."""
+        return self._call(self._route_mapped(genomat, snp_col, flip), vote_method, self._given(allow, want_dosage))
+
+    def predict_given_snp_major(self, genomat: np.ndarray, snp_col: Optional[np.ndarray], flip: Optional[np.ndarray], allow,
+                                vote_method: int = 1, want_dosage: bool = False) -> dict:
+        """:meth:`predict_given` on a SNP-major matrix [n_geno_snp, n_samp] in C order, as :meth:`predict_snp_major`."""
+        return self._call(self._route_snp_major(genomat, snp_col, flip), vote_method, self._given(allow, want_dosage))
+
+    def predict_given_bed(self, bed_fn: str, n_samp: int, n_snp: int, snp_col: np.ndarray, flip: Optional[np.ndarray], allow,
+                          vote_method: int = 1, want_dosage: bool = False) -> dict:
+        """:meth:`predict_given` on every sample of a PLINK BED file, as :meth:`predict_bed`."""
+        return self._call(self._route_bed(bed_fn, n_samp, n_snp, snp_col, flip), vote_method, self._given(allow, want_dosage))
+
+    def predict_given_cohort(self, cohort, snp_col: np.ndarray, flip: Optional[np.ndarray], allow, vote_method: int = 1,
+                             want_dosage: bool = False, first: int = 0, count: Optional[int] = None) -> dict:
+        """:meth:`predict_given` on samples ``[first, first + count)`` of a resident cohort, as :meth:`predict_cohort`;
+        row i of ``allow`` belongs to sample ``first + i``."""
+        return self._call(self._route_cohort(cohort, snp_col, flip, first, count), vote_method, self._given(allow, want_dosage))
+
+    def predict_given_device(self, d_geno, n_samp: int, d_allow, d_h1, d_h2, d_prob, d_support, d_matching=None, d_dosage=None,
+                             vote_method: int = 1, stream=None):
+        """Device-pointer form of :meth:`predict_given`; pointer arguments are ints (``tensor.data_ptr()``) or None."""
+        p = _dev_ptr
+        _lib.check(_lib.lib().hibag_hip_predict_given_device(
+            self.handle, p(d_geno), int(n_samp), int(vote_method), p(d_allow), p(d_h1), p(d_h2), p(d_prob), p(d_support),
+            p(d_matching), p(d_dosage), p(stream)))
+
     def predict_device(self, d_geno, n_samp: int, vote_method: int = 1, d_h1=None, d_h2=None, d_prob=None,
                        d_matching=None, d_dosage=None, d_postprob=None, stream=None):
         """Device-pointer form; arguments are ints (``tensor.data_ptr()``) or None."""

@@ -649,6 +649,62 @@ int hibag_hip_predict_groups_cohort(hibag_hip_model *m, const hibag_hip_cohort *
 	const int32_t *flip, int vote_method, const hibag_hip_groups *plan, int32_t *g1, int32_t *g2, double *prob, double *matching,
 	double *dosage);
 
+/* ---- partial typing: calls conditioned on what is already known of a sample's type: hlaPredictGiven ----------------
+ * Many cohorts carry partial typing at the locus -- serology, two-digit types, one allele typed and the other not, an
+ * ambiguity list of sequence-based typing -- and want the four-digit call CONSISTENT with it.  The constraint is a per-sample
+ * input: two allele sets A and B, each a bit mask over the model's alleles.  The given entries compute, per sample, on the
+ * device from the ensemble sums: the best pair among the consistent cells, its probability, the posterior mass of the
+ * consistent cells and (optionally) every allele's dosage restricted to them.  24 bytes per sample come back (+ 8 n_hla with
+ * the dosages) instead of 8 * n_hla (n_hla + 1) / 2.
+ * The rule (exact), p[c] the sample's NORMALISED posterior in pair order -- the values the postprob output of
+ * hibag_hip_predict holds for that vote_method --, cell c = the pair (h1 <= h2), c = h2 + h1 (2 n_hla - h1 - 1) / 2:
+ *   cell (h1, h2) is consistent iff (h1 in A and h2 in B) or (h1 in B and h2 in A);
+ *   support = the sum of p[c] over the consistent cells in increasing c: plain double additions from +0.0 (no FMA, no
+ *   reassociation), one serial sum;
+ *   the call is the first consistent cell in cell order with best < p[c] strictly, best starting at 0 (hibag_hip_predict's
+ *   own rule, on the consistent cells); prob = p[that cell], the JOINT probability: it is not divided by support.  No such
+ *   cell: NA / NA with prob 0.  A NaN cell never wins; where it is consistent it makes support NaN.  A NaN weight sum (a
+ *   poisoned batch) gives NA / NA with prob and support NaN, whatever the sets;
+ *   dosage[h] = the sum, over the consistent cells that contain h in increasing c, of p[c] -- 2 p[c] (exact) on the diagonal
+ *   cell; joint values too.  A NaN weight sum gives that NaN, as in hibag_hip_predict.
+ * The conditional probability is prob / support and the conditional dosage dosage / support, one IEEE division each; the
+ * CALLER forms them.  (The sum of p over all cells is not exactly 1, so a device that divided could not keep the next line.)
+ * With A and B both full, h1, h2, prob, dosage and matching are hibag_hip_predict's H1, H2, max_prob, dosage and matching bit
+ * for bit, NaN cases included, and support is the running sum of the posterior row in pair order (the S of the draw
+ * entries).  Swapping A and B changes nothing; an empty A or B gives the "no such cell" result with support +0.0.  Results do
+ * not depend on batches, slices, routes, a repaired hand-over, the other samples' sets or on which optional outputs were
+ * asked for.
+ *   allow  uint32 [n_samp][2][W], W = (n_hla + 31) / 32: sample s, set A (0) or B (1); allele h is bit h % 32 of word h / 32;
+ *          bits at or above n_hla are ignored.  Host memory for the host-pointer entries, device memory for _device.  In
+ *          _bed and _cohort it is indexed like the outputs: by the call's sample, not by the file's or the cohort's.
+ * Outputs, [n_samp] each unless stated:
+ *   h1, h2    allele indices (h1 <= h2); HIBAG_HIP_NA_INTEGER where no consistent cell qualifies
+ *   prob      the called cell's p (joint); 0 where none qualifies, NaN in a poisoned batch
+ *   support   as above
+ *   matching  as hibag_hip_predict; may be NULL
+ *   dosage    [n_samp][n_hla]; may be NULL
+ * h1, h2, prob and support are required.  HIBAG_HIP_EINVAL, with a message in hibag_hip_last_error: a NULL allow or a missing
+ * required output together with n_samp > 0, a bad vote_method, a model that is not finalized.  n_samp == 0 with NULL
+ * pointers returns 0.  There is no bound on n_hla beyond the model's own.  Everything else is as for the draw entry of the
+ * same suffix, whose arguments these take in the same order with (n_draw, seed, sample0) replaced by allow.  (Added within
+ * ABI version 7) */
+int hibag_hip_predict_given(hibag_hip_model *m, const int32_t *geno, int n_samp, int vote_method, const uint32_t *allow,
+	int32_t *h1, int32_t *h2, double *prob, double *support, double *matching, double *dosage);
+int hibag_hip_predict_given_device(hibag_hip_model *m, const int32_t *d_geno, int n_samp, int vote_method, const uint32_t *d_allow,
+	int32_t *d_h1, int32_t *d_h2, double *d_prob, double *d_support, double *d_matching, double *d_dosage, void *stream);
+int hibag_hip_predict_given_mapped(hibag_hip_model *m, const int32_t *geno, int n_samp, int n_geno_snp,
+	const int32_t *snp_col, const int32_t *flip, int vote_method, const uint32_t *allow,
+	int32_t *h1, int32_t *h2, double *prob, double *support, double *matching, double *dosage);
+int hibag_hip_predict_given_snp_major(hibag_hip_model *m, const int32_t *geno, size_t ld, int n_samp, int n_geno_snp,
+	const int32_t *snp_col, const int32_t *flip, int vote_method, const uint32_t *allow,
+	int32_t *h1, int32_t *h2, double *prob, double *support, double *matching, double *dosage);
+int hibag_hip_predict_given_bed(hibag_hip_model *m, const char *bed_fn, int n_samp, int n_snp,
+	const int32_t *snp_col, const int32_t *flip, int vote_method, const uint32_t *allow,
+	int32_t *h1, int32_t *h2, double *prob, double *support, double *matching, double *dosage);
+int hibag_hip_predict_given_cohort(hibag_hip_model *m, const hibag_hip_cohort *c, int first, int count, const int32_t *snp_col,
+	const int32_t *flip, int vote_method, const uint32_t *allow, int32_t *h1, int32_t *h2, double *prob, double *support,
+	double *matching, double *dosage);
+
 /* ---- training: replaces HIBAG_Training + HIBAG_NewClassifiers ---------------- */
 
 typedef struct hibag_hip_trainer hibag_hip_trainer;  /* opaque handle */
