@@ -31,6 +31,8 @@ from .groups import (HlaAlleleGroups, HlaGroupCalls, hlaGroupsByMap, hlaGroupsBy
                      hlaPredictGroups)
 from .given import (HlaAlleleConstraint, HlaGivenCalls, hlaConstraintFromAllele, hlaConstraintFromSets,  # noqa: F401
                     hlaPredictGiven)
+from .family import (HlaFamilyCalls, HlaMendelCheck, HlaPedigree, hlaMendelCheck, hlaModelAllelePrior,  # noqa: F401
+                     hlaPedigreeFromFam, hlaPredictFamily)
 from ._lib import HibagHipError  # noqa: F401
 
 __all__ = ["engine_kind", "engine_nkb", "engine_steps", "NA_INTEGER", "Classifier", "HlaAttrBagObj", "HlaSNPGeno", "load_geno", "load_model", "model_to_robj", "save_model",
@@ -41,4 +43,6 @@ __all__ = ["engine_kind", "engine_nkb", "engine_steps", "NA_INTEGER", "Classifie
            "hlaSubModelObj", "hlaCombineModelObj", "hlaPredictCurve", "HlaPredictCurve", "hlaPredictTopK", "HlaTopCalls",
            "HlaDeviceCohort", "hlaPredictLoci", "load_model_list", "hlaPredictDraws", "HlaPosteriorDraws",
            "HlaAlleleConstraint", "HlaGivenCalls", "hlaConstraintFromAllele", "hlaConstraintFromSets", "hlaPredictGiven",
+           "HlaFamilyCalls", "HlaMendelCheck", "HlaPedigree", "hlaMendelCheck", "hlaModelAllelePrior", "hlaPedigreeFromFam",
+           "hlaPredictFamily",
            "set_seed"]

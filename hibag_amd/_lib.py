@@ -57,6 +57,8 @@ EXPORTS = [
     "hibag_hip_predict_groups_snp_major", "hibag_hip_predict_groups_bed", "hibag_hip_predict_groups_cohort",
     "hibag_hip_predict_given", "hibag_hip_predict_given_device", "hibag_hip_predict_given_mapped",
     "hibag_hip_predict_given_snp_major", "hibag_hip_predict_given_bed", "hibag_hip_predict_given_cohort",
+    "hibag_hip_predict_family", "hibag_hip_predict_family_device", "hibag_hip_predict_family_mapped",
+    "hibag_hip_predict_family_snp_major",
 ]
 TOPK_MAX = 16      # HIBAG_HIP_TOPK_MAX of include/hibag_hip.h
 DRAW_MAX = 64      # HIBAG_HIP_DRAW_MAX
@@ -152,6 +154,11 @@ def lib() -> C.CDLL:
         L.hibag_hip_predict_given_snp_major.argtypes = [vp, vp, C.c_size_t, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]
         L.hibag_hip_predict_given_bed.argtypes = [vp, C.c_char_p, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]
         L.hibag_hip_predict_given_cohort.argtypes = [vp, vp, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]
+    if hasattr(L, "hibag_hip_predict_family"):        # (absent from an older build selected with HIBAG_HIP_LIBRARY)
+        L.hibag_hip_predict_family.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.hibag_hip_predict_family_device.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.hibag_hip_predict_family_mapped.argtypes = [vp, vp, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.hibag_hip_predict_family_snp_major.argtypes = [vp, vp, C.c_size_t, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
     if hasattr(L, "hibag_hip_cohort_new"):
         # (an older build selected with HIBAG_HIP_LIBRARY, e.g. the parent commit's for a baseline timing, lacks the cohort
         # entries: everything else still binds, and a call that needs them fails with AttributeError)

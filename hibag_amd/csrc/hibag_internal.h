@@ -191,6 +191,10 @@ struct hibag_hip_model {
 	// the given entries (hibag_hip_predict_given*): a host-pointer call's constraint on the device, sample-major as the caller
 	// gave it, and a batch's masks as k_finish_given reads them ([2 W][n_pad])
 	DevBuf ws_allow, ws_masks;
+	// the family entries (hibag_hip_predict_family*): the call's pedigree, depths and prior as uploaded (ws_fam_in), every
+	// finished sample's joint dosage and support ([n_call][n_hla] then [n_call]: what the samples' children read, rebuilt by
+	// every run), and a batch's ratio vectors as k_finish_family reads them ([2 n_hla][n_pad])
+	DevBuf ws_fam_in, ws_family, ws_ratios;
 	std::vector<int> engine_of, steps_of;  // per classifier: HIBAG_HIP_ENGINE_* and K steps, as finalized
 	int store_mode = 0;                    // which cell sums pass 1 stores for pass 2 (HibagModelView::store_cells)
 	int64_t second_pass_pairs = 0;         // haplotype pairs per sample pass 2 evaluates again
@@ -255,7 +259,7 @@ struct hibag_hip_model {
 		if (dist_st) (void)hipStreamDestroy(dist_st);
 		for (hipEvent_t e : dist_ev) if (e) (void)hipEventDestroy(e);
 		for (DevBuf *b : {&d_int, &d_stream, &d_tile, &d_tab, &d_blk, &d_pfac, &d_phdr, &d_parow, &ws_bt, &ws_bias, &ws_cells, &ws_sync, &ws_err, &ws_planes, &ws_cw, &ws_tot, &ws_inv, &ws_winv,
-		                  &ws_part, &ws_best, &ws_vrec, &ws_geno, &ws_out, &ws_codes, &ws_allow, &ws_masks, &ws_bed, &ws_bedidx, &oob_hap,
+		                  &ws_part, &ws_best, &ws_vrec, &ws_geno, &ws_out, &ws_codes, &ws_allow, &ws_masks, &ws_fam_in, &ws_family, &ws_ratios, &ws_bed, &ws_bedidx, &oob_hap,
 		                  &dist_cells, &dist_tri, &dist_acc, &dist_num, &dist_out, &pfx_tab, &pfx_cw, &pfx_best, &pfx_cell,
 		                  &mask_idx, &mask_use, &mask_cnt})
 			b->release();
@@ -301,8 +305,10 @@ struct PackSource {
 // finish is k_finish_topk (the k best pairs), with `draws` set k_finish_draw (k = n_draw pairs drawn from the posterior), with
 // `plan` set k_finish_groups (k = the plan's partitions: per partition the best pair of groups, and optionally the group
 // dosages), with `given` set k_finish_given (k = 1: the best pair among the cells consistent with the sample's two allele sets
-// `allow`, a per-sample INPUT that travels with the outputs; `support`, and optionally the restricted allele dosages) instead
-// of the call / dosage / posterior kernels.
+// `allow`, a per-sample INPUT that travels with the outputs; `support`, and optionally the restricted allele dosages), with
+// `family` set k_finish_family (k = 1: the best pair under the posterior weighted by the parents' results; `support` and the
+// dosage as for `given`; the pedigree is an input in the CALL's numbering that does not travel with the outputs -- call0 says
+// where in the call the outputs stand) instead of the call / dosage / posterior kernels.
 struct ListOut {
 	bool on = false;                       // the call is a list entry's
 	int k = 0;                             // pairs per sample: the k of the top-k entries, the n_draw of the draw entries
@@ -318,7 +324,13 @@ struct ListOut {
 	int n_hla = 0;                         // ... on a model of so many alleles (dosage: the restricted allele dosages [n_samp][n_hla]) ...
 	double *support = nullptr;             // ... with the consistent cells' posterior mass [n_samp] ...
 	const uint32_t *allow = nullptr;       // ... under the samples' sets [n_samp][2][W]: where the outputs are (host / device)
-	size_t levels() const { return plan ? (size_t)plan->view.n_level : given ? (size_t)n_hla : 0; }
+	bool family = false;                   // the family finish runs (k = 1; n_hla, support, dosage as above) ...
+	const int32_t *pedigree = nullptr;     // ... under the call's pedigree [n_call][2] (HOST memory on every route) ...
+	const double *prior = nullptr;         // ... and allele prior [n_hla] (host memory; null: all 1.0) ...
+	const int32_t *depth = nullptr;        // ... with the samples' depths [n_call], which the entry computed (host memory);
+	int n_call = 0;                        // the call's samples ...
+	size_t call0 = 0;                      // ... of which sample call0 is sample 0 of the outputs
+	size_t levels() const { return plan ? (size_t)plan->view.n_level : (given || family) ? (size_t)n_hla : 0; }
 	size_t allow_words() const { return given ? (size_t)2 * (((size_t)n_hla + 31) / 32) : 0; }      // of one sample
 };
 
@@ -364,7 +376,7 @@ struct PredictOut {
 		adv(o.list.h1, s0 * (size_t)list.k); adv(o.list.h2, s0 * (size_t)list.k); adv(o.list.prob, s0 * (size_t)list.k);
 		adv(o.list.dosage, s0 * list.levels());
 		adv(o.list.support, s0); adv(o.list.allow, s0 * list.allow_words());
-		o.list.sample0 += (int64_t)s0;
+		o.list.sample0 += (int64_t)s0; o.list.call0 += s0;
 		return o;
 	}
 };
@@ -406,7 +418,7 @@ void enqueue_pack(hibag_hip_model *m, HibagBatchView &B, const PackSource &src, 
 void run_core(hibag_hip_model *m, HibagBatchView &B, int vote_method, double *d_part, hipStream_t st);   // passes 1 and 2 behind a pack
 int check_predict_args(hibag_hip_model *m, const void *geno, int n_samp, int vote_method, const void *H1, const void *H2);
 int check_list_args(const hibag_hip_model *m, int n_samp, const ListOut &list);       // the list entries' own arguments, behind check_predict_args
-int check_given_model(const hibag_hip_model *m);             // the given entries' first look at the model, before check_predict_args
+int check_given_model(const hibag_hip_model *m);             // the given and family entries' first look at the model, before check_predict_args
 bool take_fault(hibag_hip_model *m);                         // a hand-over failed since the last look: counted, hand-overs off
 int sticky_fault(hibag_hip_model *m);
 int workspace_enter(hibag_hip_model *m, hipStream_t st);

@@ -80,6 +80,23 @@ void hibag_launch_finish_groups(const HibagModelView &M, const HibagBatchView &B
 void hibag_launch_finish_given(const HibagModelView &M, const HibagBatchView &B, double *d_part, const uint32_t *d_allow,
 	uint32_t *d_masks, int32_t *d_H1, int32_t *d_H2, double *d_prob, double *d_support, double *d_matching, double *d_dosage,
 	hipStream_t st);
+// The finish of the family entries (hibag_k_family.h), launched INSTEAD of hibag_launch_finish: per sample the best allele
+// pair under its posterior weighted by its parents' results, d_H1 / d_H2 / d_prob (joint) / d_support [n_samp], d_matching
+// [n_samp] (may be nullptr) and the weighted dosages d_dosage [n_samp][n_hla] (may be nullptr).  The call-wide state on the
+// device: the pedigree, the depths and the prior as the entry uploaded them, and every finished sample's (D, S).
+struct HibagFamilyView {
+	const int32_t *ped = nullptr;      // [n_call][2]: (father, mother) in the call's numbering, -1 = not in this call
+	const int32_t *depth = nullptr;    // [n_call]: generations above the sample within the call
+	const double *prior = nullptr;     // [n_hla], or nullptr (all 1.0)
+	double *fam_D = nullptr;           // [n_call][n_hla]: the finished samples' joint dosages
+	double *fam_S = nullptr;           // [n_call]: ... and supports
+	double *ratios = nullptr;          // workspace of one batch: [2 n_hla][n_pad]
+	size_t call0 = 0;                  // the call's index of the batch's sample 0
+};
+// rounds[n_rounds]: the distinct depths among the batch's samples, ascending (one round of three launches each)
+void hibag_launch_finish_family(const HibagModelView &M, const HibagBatchView &B, double *d_part, const HibagFamilyView &F,
+	const int *rounds, int n_rounds, int32_t *d_H1, int32_t *d_H2, double *d_prob, double *d_support, double *d_matching,
+	double *d_dosage, hipStream_t st);
 // hlaOutOfBag (hibag_k_oob.h): each classifier predicts its own out-of-bag samples.  The per-classifier arrays are
 // [C][ld] with the batch's sample 0 at column 0 (the caller offsets the pointers); the plain haplotype table (grouped by
 // allele, hla_start[c][n_hla + 1] relative to hap_off[c]) serves the rare lane whose record log cannot settle its call.

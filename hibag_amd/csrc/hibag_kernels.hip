@@ -86,6 +86,7 @@ static_assert(2 * HIBAG_FP4_MAX_SNPS + 1 <= ACCUM_TAB_N, "pass 2's table must co
 #include "hibag_k_draw.h"
 #include "hibag_k_groups.h"
 #include "hibag_k_given.h"
+#include "hibag_k_family.h"
 #include "hibag_k_oob.h"
 #include "hibag_k_mask.h"
 #include "hibag_k_cohort.h"
@@ -399,6 +400,27 @@ void hibag_launch_finish_given(const HibagModelView &M, const HibagBatchView &B,
 	if (d_dosage)
 		hipLaunchKernelGGL(k_given_dosage, dim3(B.n_pad / 64, (M.n_hla + FIN_SEG - 1) / FIN_SEG), dim3(64 * FIN_SEG), 0, st, M, B,
 			(const double *)d_part, (const uint32_t *)d_masks, W, d_dosage);
+}
+
+// the finish of the family entries, in place of hibag_launch_finish (hibag_k_family.h): per depth present in the batch,
+// ascending, the ratio vectors of that depth's samples from their parents' finished (D, S), the walk, and the dosage --
+// always: it is what the samples' children read, into the caller's array too if that is asked for
+void hibag_launch_finish_family(const HibagModelView &M, const HibagBatchView &B, double *d_part, const HibagFamilyView &F,
+	const int *rounds, int n_rounds, int32_t *d_H1, int32_t *d_H2, double *d_prob, double *d_support, double *d_matching,
+	double *d_dosage, hipStream_t st)
+{
+	if (B.n_samp < 1 || M.n_hla < 1) return;
+	const size_t n_ratio = (size_t)2 * (size_t)M.n_hla * (size_t)B.n_pad;
+	const int32_t *ped = F.ped + 2 * F.call0, *depth = F.depth + F.call0;
+	double *fam_D = F.fam_D + F.call0 * (size_t)M.n_hla, *fam_S = F.fam_S + F.call0;
+	for (int r = 0; r < n_rounds; r++) {
+		hipLaunchKernelGGL(k_family_ratios, dim3((unsigned)((n_ratio + 255) / 256)), dim3(256), 0, st, (const double *)F.fam_D,
+			(const double *)F.fam_S, ped, depth, F.prior, B.n_samp, B.n_pad, M.n_hla, rounds[r], F.ratios);
+		hipLaunchKernelGGL(k_finish_family, dim3(B.n_pad / 64), dim3(64), 0, st, M, B, (const double *)d_part,
+			(const double *)F.ratios, depth, rounds[r], d_H1, d_H2, d_prob, d_support, d_matching, fam_S);
+		hipLaunchKernelGGL(k_family_dosage, dim3(B.n_pad / 64, (M.n_hla + FIN_SEG - 1) / FIN_SEG), dim3(64 * FIN_SEG), 0, st, M, B,
+			(const double *)d_part, (const double *)F.ratios, depth, rounds[r], fam_D, d_dosage);
+	}
 }
 
 void hibag_launch_oob(const HibagModelView &M, const HibagBatchView &B, const uint8_t *d_codes, const HibagOobOut &O,

@@ -152,10 +152,95 @@ PredictOut PredictOut::given_sets(const hibag_hip_model *m, const uint32_t *allo
 	return o;
 }
 
+// ---- the family entries' call-wide state (include/hibag_hip.h "pedigrees") ----------------------------------------
+// depth(s) = 0 without a parent in the call, else 1 + the larger depth of its parents: one pass, parents precede their
+// children.  Run BEFORE the arguments are checked (the output set carries the depths), so an index the check will reject
+// counts as "no parent" here.
+static int family_depths(const int32_t *pedigree, int n_samp, std::vector<int32_t> &depth)
+{
+	depth.clear();
+	if (!pedigree || n_samp <= 0) return 0;
+	try { depth.assign((size_t)n_samp, 0); } catch (...) { return hibag_fail(HIBAG_HIP_ENOMEM, "out of host memory"); }
+	for (int s = 0; s < n_samp; s++)
+		for (int k = 0; k < 2; k++) {
+			const int32_t p = pedigree[2 * (size_t)s + k];
+			if (p >= 0 && p < s) depth[s] = std::max(depth[s], depth[p] + 1);
+		}
+	return 0;
+}
+
+// The family output set of a call: `depth` is the entry's own vector and outlives the call.
+static int family_out(const hibag_hip_model *m, int n_samp, const int32_t *pedigree, const double *prior, int32_t *h1, int32_t *h2,
+	double *prob, double *support, double *matching, double *dosage, std::vector<int32_t> &depth, PredictOut &o)
+{
+	if (int rc = check_given_model(m)) return rc;
+	if (int rc = family_depths(pedigree, n_samp, depth)) return rc;
+	o = PredictOut::topk(1, h1, h2, prob, matching);
+	o.list.family = true; o.list.n_hla = m ? m->n_hla : 0;
+	o.list.support = support; o.list.dosage = dosage;
+	o.list.pedigree = pedigree; o.list.prior = prior;
+	o.list.depth = depth.empty() ? nullptr : depth.data(); o.list.n_call = std::max(n_samp, 0);
+	return 0;
+}
+
+// where the call's inputs lie in m->ws_fam_in: the pedigree, the depths (int32), then the prior (double, 8-aligned)
+static size_t family_prior_at(size_t n_call) { return (3 * n_call * sizeof(int32_t) + 7) / 8 * 8; }
+
+static int family_reserve(hibag_hip_model *m, const ListOut &list)
+{
+	const size_t n = (size_t)list.n_call, nh = (size_t)list.n_hla;
+	if (int rc = m->ws_fam_in.reserve(family_prior_at(n) + std::max<size_t>(nh, 1) * sizeof(double))) return rc;
+	return m->ws_family.reserve(std::max<size_t>(n * (nh + 1), 1) * sizeof(double));
+}
+
+// host -> device of the call's pedigree, depths and prior on `st`, once per run (so a run repeated after a failed hand-over
+// sends them again; ws_family is rebuilt by the run itself, parents first).  Waits for the copy: the image is pageable host
+// memory about to go out of scope.
+static int family_upload(hibag_hip_model *m, const ListOut &list, hipStream_t st)
+{
+	const size_t n = (size_t)list.n_call, nh = (size_t)list.n_hla, at = family_prior_at(n);
+	std::vector<char> image;
+	try { image.assign(at + nh * sizeof(double), 0); } catch (...) { return hibag_fail(HIBAG_HIP_ENOMEM, "out of host memory"); }
+	memcpy(image.data(), list.pedigree, 2 * n * sizeof(int32_t));
+	memcpy(image.data() + 2 * n * sizeof(int32_t), list.depth, n * sizeof(int32_t));
+	if (list.prior) memcpy(image.data() + at, list.prior, nh * sizeof(double));
+	HIP_TRY(hipMemcpyAsync(m->ws_fam_in.p, image.data(), image.size(), hipMemcpyHostToDevice, st));
+	HIP_TRY(hipStreamSynchronize(st));
+	return 0;
+}
+
+static HibagFamilyView family_view(hibag_hip_model *m, const ListOut &list)
+{
+	const size_t n = (size_t)list.n_call;
+	HibagFamilyView F;
+	F.ped = m->ws_fam_in.as<int32_t>(); F.depth = F.ped + 2 * n;
+	F.prior = list.prior ? (const double *)(m->ws_fam_in.as<char>() + family_prior_at(n)) : nullptr;
+	F.fam_D = m->ws_family.as<double>(); F.fam_S = F.fam_D + n * (size_t)list.n_hla;
+	F.ratios = m->ws_ratios.as<double>();
+	F.call0 = list.call0;
+	return F;
+}
+
 // the top-k and the draw entries' own arguments, behind check_predict_args
 int check_list_args(const hibag_hip_model *m, int n_samp, const ListOut &list)
 {
 	static_assert(HIBAG_HIP_TOPK_MAX == HIBAG_TOPK_MAX && HIBAG_HIP_DRAW_MAX == HIBAG_DRAW_MAX, "the public bounds are the kernels' bounds");
+	if (list.family) {
+		if (n_samp > 0 && !list.pedigree) return hibag_fail(HIBAG_HIP_EINVAL, "pedigree is NULL");
+		if (n_samp > 0 && (!list.h1 || !list.h2 || !list.prob || !list.support))
+			return hibag_fail(HIBAG_HIP_EINVAL, "h1, h2, prob and support are all required");
+		for (int s = 0; s < n_samp; s++)
+			for (int k = 0; k < 2; k++) {
+				const int32_t p = list.pedigree[2 * (size_t)s + k];
+				if (p < -1 || p >= s)
+					return hibag_fail(HIBAG_HIP_EINVAL, "pedigree[%d][%d] = %d: a parent index must lie in -1 .. %d (parents precede "
+						"their children in the call)", s, k, (int)p, s - 1);
+			}
+		for (int h = 0; list.prior && n_samp > 0 && h < list.n_hla; h++)
+			if (!(list.prior[h] > 0) || !(list.prior[h] <= 1.79769313486231570815e+308))
+				return hibag_fail(HIBAG_HIP_EINVAL, "prior[%d] = %g: every entry of the prior must be finite and > 0", h, list.prior[h]);
+		return 0;
+	}
 	if (list.given) {
 		if (n_samp > 0 && !list.allow) return hibag_fail(HIBAG_HIP_EINVAL, "allow is NULL");
 		if (n_samp > 0 && (!list.h1 || !list.h2 || !list.prob || !list.support))
@@ -243,6 +328,10 @@ static int predict_device_locked(hibag_hip_model *m, const PackSource &src, int 
 	const int lim = batch_limit(m);
 	if (out.list.on && out.list.given && n_samp > 0)       // a batch's masks, word-major ([2 W][n_pad]: hibag_k_given.h)
 		if (int rc = m->ws_masks.reserve(out.list.allow_words() * (size_t)round_up(std::min(lim, n_samp), HIBAG_WAVE) * sizeof(uint32_t))) return rc;
+	const bool family = out.list.on && out.list.family;
+	std::vector<int> rounds;                               // the family finish: the distinct depths of a batch, ascending
+	if (family && n_samp > 0)                              // a batch's ratio vectors, allele-major ([2 n_hla][n_pad]: hibag_k_family.h)
+		if (int rc = m->ws_ratios.reserve((size_t)2 * std::max(out.list.n_hla, 1) * (size_t)round_up(std::min(lim, n_samp), HIBAG_WAVE) * sizeof(double))) return rc;
 	for (int s0 = 0; s0 < n_samp; s0 += lim) {
 		const int n = std::min(lim, n_samp - s0);
 		HibagBatchView B;
@@ -252,7 +341,18 @@ static int predict_device_locked(hibag_hip_model *m, const PackSource &src, int 
 		run_core(m, B, vote_method, m->ws_part.as<double>(), st);
 		const PredictOut o = out.advanced((size_t)s0, (size_t)m->n_hla, (size_t)m->view.n_cell);
 		m->timer.begin(HIBAG_HIP_K_FINISH, st, true);
-		if (o.list.on && o.list.given)
+		if (family) {
+			const int32_t *depth = o.list.depth + o.list.call0;
+			try {                                          // (one pass: a depth is at most the batch's generations, a small number)
+				const int deepest = *std::max_element(depth, depth + n);
+				std::vector<char> seen((size_t)deepest + 1, 0);
+				for (int s = 0; s < n; s++) seen[depth[s]] = 1;
+				rounds.clear();
+				for (int d = 0; d <= deepest; d++) if (seen[d]) rounds.push_back(d);
+			} catch (...) { return hibag_fail(HIBAG_HIP_ENOMEM, "out of host memory"); }
+			hibag_launch_finish_family(m->view, B, B.part, family_view(m, o.list), rounds.data(), (int)rounds.size(), o.list.h1,
+				o.list.h2, o.list.prob, o.list.support, o.matching, o.list.dosage, st);
+		} else if (o.list.on && o.list.given)
 			hibag_launch_finish_given(m->view, B, B.part, o.list.allow, m->ws_masks.as<uint32_t>(), o.list.h1, o.list.h2, o.list.prob,
 				o.list.support, o.matching, o.list.dosage, st);
 		else if (o.list.on && o.list.groups)
@@ -308,14 +408,14 @@ int staged_slice(const hibag_hip_model *m, int n_samp, size_t row_len)
 // vectors, so that a slice still comes down in one copy.
 struct SliceLayout {
 	PredictOut want;                       // the caller's set: which outputs are asked for, and where they go in the end
-	size_t nh = 0, P = 0, tk = 0, gd = 0, sp = 0;  // (gd: group or given dosages per sample, if asked for; sp: 1 with the given entries' support)
+	size_t nh = 0, P = 0, tk = 0, gd = 0, sp = 0;  // (gd: group, given or family dosages per sample, if asked for; sp: 1 with the given and family entries' support)
 	size_t o_h1 = 0, o_h2 = 0, o_mp = 0, o_mt = 0, o_ds = 0, o_pp = 0, o_t1 = 0, o_t2 = 0, o_tp = 0, o_sp = 0, o_gd = 0;
 	size_t bytes = 0;                      // of the buffer of one slice
 
 	SliceLayout() = default;
 	SliceLayout(size_t slice, size_t n_hla, size_t n_cell, const PredictOut &out)
 		: want(out), nh(n_hla), P(n_cell), tk(out.list.on ? (size_t)out.list.k : 0), gd(out.list.on && out.list.dosage ? out.list.levels() : 0),
-		  sp(out.list.on && out.list.given ? 1 : 0)
+		  sp(out.list.on && (out.list.given || out.list.family) ? 1 : 0)
 	{
 		o_h2 = o_h1 + slice * 4; o_mp = (o_h2 + slice * 4 + 7) / 8 * 8; o_mt = o_mp + slice * 8; o_ds = o_mt + slice * 8;
 		o_pp = o_ds + slice * nh * 8;
@@ -389,6 +489,7 @@ struct StagedRun {
 	char *pin_out(int i) const { return (char *)m->pin_out.p + (size_t)(i & 1) * L.bytes; }
 	int plan();
 	int upload_allow();
+	int upload_family();
 	int upload(int i);
 	int download(int i);
 	int drain(int i);
@@ -415,6 +516,8 @@ int StagedRun::plan()
 	if (int rc = m->ws_out.reserve(L.bytes * nbuf)) return rc;
 	if (out.list.on && out.list.given)
 		if (int rc = m->ws_allow.reserve((size_t)n_samp * out.list.allow_words() * sizeof(uint32_t))) return rc;
+	if (out.list.on && out.list.family)
+		if (int rc = family_reserve(m, out.list)) return rc;
 	if (int rc = staged_streams(m, &ss)) return rc;
 	if (piped) {
 		// pinned staging on the host side, so that every copy call returns at once and the host thread's own work -- filling
@@ -440,6 +543,14 @@ int StagedRun::upload_allow()
 	HIP_TRY(hipMemcpyAsync(m->ws_allow.p, out.list.allow, (size_t)n_samp * out.list.allow_words() * sizeof(uint32_t),
 		hipMemcpyHostToDevice, piped && src.geno ? ss->in : ss->run));
 	return 0;
+}
+
+// host -> device of the call's pedigree, depths and prior (the family entries), once per run like the constraint above, on
+// the kernels' stream
+int StagedRun::upload_family()
+{
+	if (!(out.list.on && out.list.family)) return 0;
+	return family_upload(m, out.list, ss->run);
 }
 
 // host -> device of slice i's genotypes (nothing to do for a payload on the device)
@@ -525,6 +636,7 @@ int StagedRun::run()
 	auto now = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
 	double tr[6] = {now(), 0, 0, 0, 0, 0};
 	if (int rc = upload_allow()) return rc;
+	if (int rc = upload_family()) return rc;
 	if (int rc = upload(0)) return rc;
 	if (trace) { if (!piped) (void)hipStreamSynchronize(ss->run); tr[1] = now(); }
 	for (int i = 0; i < n_slice; i++) {
@@ -539,6 +651,7 @@ int StagedRun::run()
 		if (piped && i >= 2) HIP_TRY(hipStreamWaitEvent(ss->run, ss->down[i & 1], 0));    // slice i - 2 has left the device output buffer
 		PredictOut d = L.bind(dev_out(i));
 		d.list.sample0 += s0;              // (a draw is keyed with the sample's index in the caller's numbering)
+		d.list.call0 += (size_t)s0;        // (the family entries' pedigree is in the call's numbering)
 		if (d.list.given) d.list.allow = m->ws_allow.as<uint32_t>() + (size_t)s0 * d.list.allow_words();      // (the slice's part of the device copy)
 		if (int rc = predict_device_locked(m, p, n, vote_method, d, ss->run)) return rc;
 		if (piped) HIP_TRY(hipEventRecord(ss->ran[i & 1], ss->run));
@@ -1308,6 +1421,63 @@ int hibag_hip_predict_given_bed(hibag_hip_model *m, const char *bed_fn, int n_sa
 	if (int rc = check_given_model(m)) return rc;
 	return predict_bed_entry(m, bed_fn, n_samp, n_snp, snp_col, flip, vote_method,
 		PredictOut::given_sets(m, allow, h1, h2, prob, support, matching, dosage));
+}
+
+// ---- calls weighted by the parents' posteriors (include/hibag_hip.h "pedigrees") --------------------------------------
+// The same fronts with the family output set: k_finish_family in rounds of ascending depth, on the call-wide (D, S) of the
+// samples finished so far.  `pedigree` and `prior` are host memory on every route: the entry checks them and computes the
+// depths before anything is launched.
+
+int hibag_hip_predict_family(hibag_hip_model *m, const int32_t *geno, int n_samp, int vote_method, const int32_t *pedigree,
+	const double *prior, int32_t *h1, int32_t *h2, double *prob, double *support, double *matching, double *dosage)
+{
+	std::vector<int32_t> depth;
+	PredictOut out;
+	if (int rc = family_out(m, n_samp, pedigree, prior, h1, h2, prob, support, matching, dosage, depth, out)) return rc;
+	return predict_entry(m, geno, n_samp, vote_method, out);
+}
+
+int hibag_hip_predict_family_device(hibag_hip_model *m, const int32_t *d_geno, int n_samp, int vote_method, const int32_t *pedigree,
+	const double *prior, int32_t *d_h1, int32_t *d_h2, double *d_prob, double *d_support, double *d_matching, double *d_dosage,
+	void *stream)
+{
+	std::vector<int32_t> depth;
+	PredictOut out;
+	if (int rc = family_out(m, n_samp, pedigree, prior, d_h1, d_h2, d_prob, d_support, d_matching, d_dosage, depth, out)) return rc;
+	if (int rc = check_predict_args(m, d_geno, n_samp, vote_method, out.H1, out.H2)) return rc;
+	if (int rc = check_list_args(m, n_samp, out.list)) return rc;
+	if (n_samp == 0) return 0;
+	PackSource src;
+	src.d_geno = d_geno;
+	std::lock_guard<std::mutex> g(m->lock);
+	if (int rc = sticky_fault(m)) return rc;
+	// the call's inputs go up on the caller's stream, behind whatever still uses the model's workspace
+	const hipStream_t st = (hipStream_t)stream;
+	HIP_TRY(hipSetDevice(m->device));
+	if (int rc = workspace_enter(m, st)) return rc;
+	if (int rc = family_reserve(m, out.list)) return rc;
+	if (int rc = family_upload(m, out.list, st)) return rc;
+	return predict_device_locked(m, src, n_samp, vote_method, out, st);
+}
+
+int hibag_hip_predict_family_mapped(hibag_hip_model *m, const int32_t *geno, int n_samp, int n_geno_snp,
+	const int32_t *snp_col, const int32_t *flip, int vote_method, const int32_t *pedigree, const double *prior,
+	int32_t *h1, int32_t *h2, double *prob, double *support, double *matching, double *dosage)
+{
+	std::vector<int32_t> depth;
+	PredictOut out;
+	if (int rc = family_out(m, n_samp, pedigree, prior, h1, h2, prob, support, matching, dosage, depth, out)) return rc;
+	return predict_mapped_entry(m, geno, n_samp, n_geno_snp, snp_col, flip, vote_method, out);
+}
+
+int hibag_hip_predict_family_snp_major(hibag_hip_model *m, const int32_t *geno, size_t ld, int n_samp, int n_geno_snp,
+	const int32_t *snp_col, const int32_t *flip, int vote_method, const int32_t *pedigree, const double *prior,
+	int32_t *h1, int32_t *h2, double *prob, double *support, double *matching, double *dosage)
+{
+	std::vector<int32_t> depth;
+	PredictOut out;
+	if (int rc = family_out(m, n_samp, pedigree, prior, h1, h2, prob, support, matching, dosage, depth, out)) return rc;
+	return predict_snp_major_entry(m, geno, ld, n_samp, n_geno_snp, snp_col, flip, vote_method, out);
 }
 
 int hibag_hip_predict_partial_device(hibag_hip_model *m, const int32_t *d_geno, int n_samp,

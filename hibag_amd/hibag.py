@@ -604,6 +604,65 @@ class HlaAttrBagClass:
             self.handle, p(d_geno), int(n_samp), int(vote_method), p(d_allow), p(d_h1), p(d_h2), p(d_prob), p(d_support),
             p(d_matching), p(d_dosage), p(stream)))
 
+    # --- the family entries: per sample the best allele pair under its posterior weighted by its parents' results
+    # (hibag_hip_predict_family and its routes; include/hibag_hip.h "pedigrees"): the routes above with the family tail.
+    def _family_args(self, pedigree, prior, n: Optional[int] = None):
+        ped = np.asarray(pedigree)
+        if ped.dtype.kind not in "iu" or ped.ndim != 2 or ped.shape[1] != 2:
+            raise ValueError(f"pedigree must be an integer array [n_samp, 2] of (father, mother) sample indices, got {ped.dtype} {ped.shape}")
+        if n is not None and ped.shape[0] != n:
+            raise ValueError(f"pedigree holds {ped.shape[0]} samples, the genotypes {n}")
+        ped = np.ascontiguousarray(ped, np.int32)
+        pr = None
+        if prior is not None:
+            pr = np.ascontiguousarray(prior, np.float64)
+            if pr.shape != (int(self.obj.n_hla),):
+                raise ValueError(f"prior must hold one entry per allele of the model ({int(self.obj.n_hla)}), got {pr.shape}")
+        return ped, pr
+
+    def _family(self, pedigree, prior, want_dosage: bool):
+        ped, pr = self._family_args(pedigree, prior)
+        nh = int(self.obj.n_hla)
+
+        def make(n):
+            if ped.shape[0] != n:
+                raise ValueError(f"pedigree holds {ped.shape[0]} samples, the genotypes {n}")
+            return dict(h1=np.empty(n, np.int32), h2=np.empty(n, np.int32), prob=np.empty(n, np.float64),
+                        support=np.empty(n, np.float64), matching=np.empty(n, np.float64),
+                        **({"dosage": np.empty((n, nh), np.float64)} if want_dosage else {}))
+        return ("hibag_hip_predict_family", (_as_ptr(ped), _as_ptr(pr)), ("h1", "h2", "prob", "support", "matching", "dosage"), make)
+
+    def predict_family(self, genomat: np.ndarray, pedigree, prior=None, vote_method: int = 1, want_dosage: bool = False) -> dict:
+        """``hibag_hip_predict_family``: per sample the best allele pair under its own posterior WEIGHTED by the Mendelian
+        transmission probability its parents' results give each pair -- ``h1``, ``h2`` (0-based, h1 <= h2, NA = INT_MIN
+        where no pair qualifies), ``prob`` (that pair's JOINT weighted posterior), ``support`` (the weighted mass of all
+        pairs, added in pair order), ``matching``, each [n_samp], and with ``want_dosage`` the weighted allele ``dosage``
+        [n_samp, n_hla] (joint too).  ``pedigree``: int [n_samp, 2], (father, mother) as sample indices of this call, -1 for
+        "not in this call"; parents must precede their children.  ``prior``: float [n_hla], finite and > 0, or None (all
+        1.0).  For a sample without known parents these are ``predict_raw``'s ``h1``, ``h2``, ``prob`` and ``dosage`` bit for
+        bit.  ``genomat`` int32 [n_samp, n_snp]."""
+        return self._call(self._route_raw(genomat), vote_method, self._family(pedigree, prior, want_dosage))
+
+    def predict_family_mapped(self, genomat: np.ndarray, snp_col: np.ndarray, flip: Optional[np.ndarray], pedigree, prior=None,
+                              vote_method: int = 1, want_dosage: bool = False) -> dict:
+        """:meth:`predict_family` on the cohort's own matrix [n_samp, n_geno_snp], as :meth:`predict_mapped`."""
+        return self._call(self._route_mapped(genomat, snp_col, flip), vote_method, self._family(pedigree, prior, want_dosage))
+
+    def predict_family_snp_major(self, genomat: np.ndarray, snp_col: Optional[np.ndarray], flip: Optional[np.ndarray], pedigree,
+                                 prior=None, vote_method: int = 1, want_dosage: bool = False) -> dict:
+        """:meth:`predict_family` on a SNP-major matrix [n_geno_snp, n_samp] in C order, as :meth:`predict_snp_major`."""
+        return self._call(self._route_snp_major(genomat, snp_col, flip), vote_method, self._family(pedigree, prior, want_dosage))
+
+    def predict_family_device(self, d_geno, n_samp: int, pedigree, prior, d_h1, d_h2, d_prob, d_support, d_matching=None,
+                              d_dosage=None, vote_method: int = 1, stream=None):
+        """Device-pointer form of :meth:`predict_family`: ``pedigree`` and ``prior`` are HOST arrays (the library checks them
+        and orders the work by them), the other pointer arguments are ints (``tensor.data_ptr()``) or None."""
+        ped, pr = self._family_args(pedigree, prior, int(n_samp))
+        p = _dev_ptr
+        _lib.check(_lib.lib().hibag_hip_predict_family_device(
+            self.handle, p(d_geno), int(n_samp), int(vote_method), _as_ptr(ped), _as_ptr(pr), p(d_h1), p(d_h2), p(d_prob),
+            p(d_support), p(d_matching), p(d_dosage), p(stream)))
+
     def predict_device(self, d_geno, n_samp: int, vote_method: int = 1, d_h1=None, d_h2=None, d_prob=None,
                        d_matching=None, d_dosage=None, d_postprob=None, stream=None):
         """Device-pointer form; arguments are ints (``tensor.data_ptr()``) or None."""

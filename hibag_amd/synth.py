@@ -100,6 +100,30 @@ def make_samples(founders: np.ndarray, allele_freq: np.ndarray, n_samp: int, see
     return np.ascontiguousarray(g), np.sort(a, axis=1).astype(np.int32)
 
 
+def make_family(founders: np.ndarray, allele_freq: np.ndarray, n_fam: int, seed: int = DEFAULT_SEED + 2,
+                err: float = 0.002, miss: float = 0.01) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """``n_fam`` trios: the parents' allele pairs are drawn from ``allele_freq``, the child gets one random allele of each
+    parent; genotypes are made as :func:`make_samples` makes them (two founders + errors + missingness, no heavily missing
+    samples).  Returns ``(G, truth, pedigree)``: int32 [3 n_fam, n_snp], the true sorted allele pairs int32 [3 n_fam, 2] and
+    int32 [3 n_fam, 2] (father, mother) indices, -1 for the parents -- PARENTS FIRST: fathers 0 .. n_fam - 1, mothers
+    n_fam .. 2 n_fam - 1, then the children, child i of father i and mother n_fam + i."""
+    rng = np.random.default_rng(seed)
+    n_hla, S = founders.shape
+    par = rng.choice(n_hla, size=(2 * n_fam, 2), p=allele_freq)
+    pick = rng.integers(0, 2, (n_fam, 2))
+    kid = np.stack([par[np.arange(n_fam), pick[:, 0]], par[n_fam + np.arange(n_fam), pick[:, 1]]], axis=1)
+    a = np.concatenate([par, kid])
+    n = len(a)
+    g = founders[a[:, 0]].astype(np.int32) + founders[a[:, 1]].astype(np.int32)
+    e = rng.random((n, S)) < err
+    g = np.where(e, (g + rng.integers(1, 3, (n, S))) % 3, g).astype(np.int32)
+    g[rng.random((n, S)) < miss] = NA_INTEGER
+    ped = np.full((n, 2), -1, np.int32)
+    ped[2 * n_fam:, 0] = np.arange(n_fam)
+    ped[2 * n_fam:, 1] = n_fam + np.arange(n_fam)
+    return np.ascontiguousarray(g), np.sort(a, axis=1).astype(np.int32), ped
+
+
 def as_snp_geno(model: HlaAttrBagObj, genomat: np.ndarray, order: str = "C") -> HlaSNPGeno:
     """Wrap a sample-major matrix as an ``hlaSNPGenoClass`` over the model's SNPs: ``genotype`` [n_snp, n_samp] in
     numpy's row-major order (``"C"``, a transposed copy) or in R's column-major order (``"F"``: a view of ``genomat``)."""

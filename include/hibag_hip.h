@@ -705,6 +705,65 @@ int hibag_hip_predict_given_cohort(hibag_hip_model *m, const hibag_hip_cohort *c
 	const int32_t *flip, int vote_method, const uint32_t *allow, int32_t *h1, int32_t *h2, double *prob, double *support,
 	double *matching, double *dosage);
 
+/* ---- pedigrees: children's calls weighted by their parents' posteriors: hlaPredictFamily --------------------------
+ * A child's two alleles are one allele of each parent, so the parents' SNPs say a great deal about a child whose own SNPs
+ * are sparse.  The family entries take the call's pedigree and weight every sample's posterior, on the device, with the
+ * Mendelian transmission probability its parents' results give each allele pair, divided by the pair's prior.  Parents are
+ * finished before their children within the call; 24 bytes per sample come back (+ 8 n_hla with the dosages).
+ * The rule (exact), p[c] the sample's NORMALISED posterior in pair order -- the values the postprob output of
+ * hibag_hip_predict holds for that vote_method --, cell c = the pair (h1 <= h2), c = h2 + h1 (2 n_hla - h1 - 1) / 2:
+ *   1 the ratio vector of a parent j with joint dosage D_j (rule 5) and support S_j (rule 3), S_j > 0:
+ *       r_j[h] = (0.5 * (D_j[h] / S_j)) / prior[h]    one division, an exact halving, one division (skipped for a NULL prior);
+ *     a parent index -1, or a parent whose S_j is not > 0 (zero or NaN), is UNKNOWN: r == 1.0;
+ *   2 the weight of a cell:  a = rf[h1] * rm[h2], b = rf[h2] * rm[h1], w[c] = 0.5 * (a + b), x[c] = p[c] * w[c] -- plain double
+ *     operations in that order, no FMA.  Both parents unknown: w == 1.0 and x[c] == p[c] bit for bit;
+ *   3 support = the sum of x[c] over all cells in increasing c, one serial sum from +0.0;
+ *   4 the call is the first cell in cell order with best < x[c] strictly, best starting at 0; prob = x[that cell], the JOINT
+ *     value: it is not divided by support.  No such cell: NA / NA with prob 0.  A NaN x never wins and makes support NaN.  A
+ *     NaN weight sum (a poisoned batch) gives NA / NA with prob and support NaN;
+ *   5 dosage[h] = the sum of x[c] over the cells that contain h in increasing c, 2 x[c] (exact) on the diagonal cell; a NaN
+ *     weight sum gives that NaN.  Always formed on the device (descendants need it), returned only if asked for;
+ *   6 matching is hibag_hip_predict's.
+ * The conditional probability is prob / support and the conditional dosage dosage / support where support > 0; the CALLER
+ * forms them.  Information flows DOWN only: a parent that is itself a child transmits its own weighted (D, S); children
+ * never change their parents' results, and siblings do not see each other.  For a sample with both parents unknown h1, h2,
+ * prob, dosage and matching are hibag_hip_predict's H1, H2, max_prob, dosage and matching bit for bit, NaN cases included,
+ * and support is the running sum of the posterior row in pair order.  Swapping father and mother changes nothing.  A
+ * sample's result depends on its own genotypes and its ancestors' only: not on batches, slices, routes, a repaired
+ * hand-over, the order of unrelated samples or on which optional outputs were asked for.
+ * w is the Mendelian transmission probability of the pair under the parents' posteriors divided by the pair's prior
+ * (2 - [h1 == h2]) q[h1] q[h2]; support is therefore a Bayes-factor-like "family fit", well below 1 where the child's own
+ * SNPs contradict the parents (a sample swap, non-paternity).
+ *   pedigree  int32 [n_samp][2]: (father, mother) of sample s as sample indices of THIS call, or -1 for "not in this call".
+ *             Every index p of sample s must satisfy -1 <= p < s: parents precede their children.  HOST memory on every
+ *             route, _device included: the entry checks it and orders the work by it before anything is launched.
+ *   prior     double [n_hla], every entry finite and > 0, or NULL (all 1.0); host memory on every route.  The prior to
+ *             give is the one the model's classifiers carry (hlaModelAllelePrior of the Python package).
+ * Outputs, [n_samp] each unless stated (device memory for _device):
+ *   h1, h2    allele indices (h1 <= h2); HIBAG_HIP_NA_INTEGER where no cell qualifies
+ *   prob      the called cell's x (joint); 0 where none qualifies, NaN in a poisoned batch
+ *   support   as above
+ *   matching  as hibag_hip_predict; may be NULL
+ *   dosage    [n_samp][n_hla]; may be NULL
+ * h1, h2, prob and support are required.  HIBAG_HIP_EINVAL, with a message in hibag_hip_last_error and before any launch: a
+ * NULL pedigree or a missing required output together with n_samp > 0, a parent index outside -1 .. s - 1, a prior entry that
+ * is not finite and > 0, a bad vote_method, a model that is not finalized.  n_samp == 0 with NULL pointers returns 0.  The
+ * _device entry waits for its upload of pedigree and prior on `stream` before it enqueues the kernels.  There are no _bed
+ * and _cohort routes: their sample order is the file's or the cohort's, and the caller cannot arrange for parents to
+ * precede children.  Everything else is as for the given entry of the same suffix, whose arguments these take in the same
+ * order with allow replaced by (pedigree, prior).  (Added within ABI version 7) */
+int hibag_hip_predict_family(hibag_hip_model *m, const int32_t *geno, int n_samp, int vote_method, const int32_t *pedigree,
+	const double *prior, int32_t *h1, int32_t *h2, double *prob, double *support, double *matching, double *dosage);
+int hibag_hip_predict_family_device(hibag_hip_model *m, const int32_t *d_geno, int n_samp, int vote_method, const int32_t *pedigree,
+	const double *prior, int32_t *d_h1, int32_t *d_h2, double *d_prob, double *d_support, double *d_matching, double *d_dosage,
+	void *stream);
+int hibag_hip_predict_family_mapped(hibag_hip_model *m, const int32_t *geno, int n_samp, int n_geno_snp,
+	const int32_t *snp_col, const int32_t *flip, int vote_method, const int32_t *pedigree, const double *prior,
+	int32_t *h1, int32_t *h2, double *prob, double *support, double *matching, double *dosage);
+int hibag_hip_predict_family_snp_major(hibag_hip_model *m, const int32_t *geno, size_t ld, int n_samp, int n_geno_snp,
+	const int32_t *snp_col, const int32_t *flip, int vote_method, const int32_t *pedigree, const double *prior,
+	int32_t *h1, int32_t *h2, double *prob, double *support, double *matching, double *dosage);
+
 /* ---- training: replaces HIBAG_Training + HIBAG_NewClassifiers ---------------- */
 
 typedef struct hibag_hip_trainer hibag_hip_trainer;  /* opaque handle */
