@@ -49,7 +49,7 @@ EXPORTS = [
     "hibag_hip_cohort_new", "hibag_hip_cohort_from_bed", "hibag_hip_cohort_free", "hibag_hip_cohort_device",
     "hibag_hip_cohort_n_samp", "hibag_hip_cohort_n_snp", "hibag_hip_cohort_bytes", "hibag_hip_cohort_snp_counts",
     "hibag_hip_predict_cohort", "hibag_hip_predict_topk_cohort", "hibag_hip_predict_masked",
-    "hibag_hip_test_build_eval_batch",
+    "hibag_hip_test_build_eval_batch", "hibag_hip_test_em_fit", "hibag_hip_test_em_layout", "hibag_hip_trainer_em_counts",
     "hibag_hip_predict_draw", "hibag_hip_predict_draw_device", "hibag_hip_predict_draw_mapped",
     "hibag_hip_predict_draw_snp_major", "hibag_hip_predict_draw_bed", "hibag_hip_predict_draw_cohort",
     "hibag_hip_groups_create", "hibag_hip_groups_free", "hibag_hip_groups_levels", "hibag_hip_groups_tile",
@@ -254,6 +254,10 @@ def lib() -> C.CDLL:
     L.hibag_hip_test_time_avg_prob.argtypes = [vp, vp, i32, i32, i32, vp, vp, C.POINTER(dbl)]
     if hasattr(L, "hibag_hip_test_build_eval_batch"):     # (absent from an older build selected with HIBAG_HIP_LIBRARY)
         L.hibag_hip_test_build_eval_batch.argtypes = [i32, i32, vp, vp, i32, i32, vp, vp, vp, vp, i32, vp, i32, vp, vp]
+    if hasattr(L, "hibag_hip_test_em_fit"):               # (likewise)
+        L.hibag_hip_test_em_fit.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp]
+        L.hibag_hip_test_em_layout.argtypes = [i32, i32, i32]
+        L.hibag_hip_trainer_em_counts.argtypes = [vp, C.POINTER(C.c_longlong)]
     if hasattr(L, "hibag_hip_test_read_diag"):
         L.hibag_hip_test_read_diag.argtypes = [vp, vp, i32]
         L.hibag_hip_plugin_degraded_calls.restype = i64

@@ -5,6 +5,7 @@
 // There is no CPU fallback here: every compute entry runs the HIP kernels or fails with an error code.
 
 #include "hibag_internal.h"
+#include "hibag_em.h"
 
 namespace {
 
@@ -163,6 +164,55 @@ extern "C" int hibag_hip_test_build_eval_batch(int n_hla, int n_sample, const in
 		hibag_build_set_bootstrap(boot);
 		if (geno_snp_major) hibag_build_set_genotypes(geno_snp_major, n_matrix_snp);
 		hibag_build_eval_batch((const PluginGenotype *)base_geno, n_snp, cand.data(), n_cand, acc_floor, acc_oob, loss_ib);
+	} catch (const char *msg) {
+		return hibag_fail(HIBAG_HIP_ENODEV, "%s", msg);
+	} catch (const std::bad_alloc &) {
+		return hibag_fail(HIBAG_HIP_ENOMEM, "out of host memory");
+	}
+	return 0;
+}
+
+// The device EM fit of one growth step (hibag_em_fit_batch, hibag_em.h) is C++-only too and otherwise reached only through the
+// greedy search, which shows the winner of every step and nothing else.  This entry runs it once on the caller's own arrays:
+// the transposed lists come from the driver's own builder (hibag_em_transpose), the layout from the driver's own rule.
+// Everything the kernel indexes with is checked BEFORE the device is touched, so no argument can make the kernel read or
+// write out of bounds; the calling thread's EM arena is released on every way out.  Tests only.
+extern "C" int hibag_hip_test_em_layout(int n_ib, int n_pair, int n_hap) { return hibag_em_layout(n_ib, n_pair, n_hap); }
+
+extern "C" int hibag_hip_test_em_fit(int n_ib, int n_pair, int n_hap, int n_samp_total, const int *h1, const int *h2, const int *off,
+	const int *boot, const double *cur_freq, int n_cand, const int8_t *geno, const double *afreq, double *out_freq, int *status,
+	int *iters, int *layout)
+{
+	if (n_ib <= 0 || n_pair <= 0 || n_hap <= 0 || n_samp_total <= 0 || n_cand <= 0 || n_cand > 65535)
+		return hibag_fail(HIBAG_HIP_EINVAL, "test_em_fit: invalid sizes");
+	if (n_hap & 1) return hibag_fail(HIBAG_HIP_EINVAL, "test_em_fit: n_hap = %d is odd (the list is a doubled one)", n_hap);
+	if (!h1 || !h2 || !off || !boot || !cur_freq || !geno || !afreq || !out_freq || !status)
+		return hibag_fail(HIBAG_HIP_EINVAL, "test_em_fit: a required array is NULL");
+	if (!hibag_em_fits(n_ib, n_pair, n_hap))
+		return hibag_fail(HIBAG_HIP_EINVAL, "test_em_fit: a step of %d samples, %d pairs, %d haplotypes does not fit the kernel", n_ib, n_pair, n_hap);
+	if (off[0] != 0 || off[n_ib] != n_pair) return hibag_fail(HIBAG_HIP_EINVAL, "test_em_fit: off must start at 0 and end at n_pair");
+	for (int i = 0; i < n_ib; i++) {
+		if (off[i + 1] < off[i]) return hibag_fail(HIBAG_HIP_EINVAL, "test_em_fit: off decreases at sample %d", i);
+		if (boot[i] < 1) return hibag_fail(HIBAG_HIP_EINVAL, "test_em_fit: boot[%d] = %d, an in-bag sample's count is at least 1", i, boot[i]);
+	}
+	for (int j = 0; j < n_pair; j++)
+		if (h1[j] < 0 || h1[j] >= n_hap || h2[j] < 0 || h2[j] >= n_hap)
+			return hibag_fail(HIBAG_HIP_EINVAL, "test_em_fit: pair %d = (%d, %d) is outside the %d haplotypes", j, h1[j], h2[j], n_hap);
+	for (size_t k = 0; k < (size_t)n_cand * n_ib; k++)
+		if (geno[k] < 0 || geno[k] > 3) return hibag_fail(HIBAG_HIP_EINVAL, "test_em_fit: genotype %d at candidate %d, sample %d (0, 1, 2 or 3 = missing)",
+			(int)geno[k], (int)(k / n_ib), (int)(k % n_ib));
+	for (int c = 0; c < n_cand; c++)
+		if (!(afreq[c] > 0 && afreq[c] < 1)) return hibag_fail(HIBAG_HIP_EINVAL, "test_em_fit: afreq[%d] = %g is not inside (0, 1)", c, afreq[c]);
+	try {
+		std::vector<int> hoff, hent, at;
+		hibag_em_transpose(n_pair, n_hap, h1, h2, hoff, hent, at);
+		std::vector<const int8_t *> gp((size_t)n_cand);
+		for (int c = 0; c < n_cand; c++) gp[c] = geno + (size_t)c * n_ib;
+		if (hipSetDevice(hibag_selected_device()) != hipSuccess)
+			return hibag_fail(HIBAG_HIP_ENODEV, "test_em_fit: hipSetDevice(%d) failed", hibag_selected_device());
+		struct Scope { ~Scope() { hibag_em_release(); } } scope;          // (also when the call below throws)
+		const HibagEmPairs P{n_ib, n_pair, n_hap, n_samp_total, h1, h2, off, boot, hoff.data(), hent.data(), cur_freq};
+		hibag_em_fit_batch(P, gp.data(), afreq, n_cand, out_freq, status, iters, layout);
 	} catch (const char *msg) {
 		return hibag_fail(HIBAG_HIP_ENODEV, "%s", msg);
 	} catch (const std::bad_alloc &) {

@@ -30,7 +30,9 @@
 // sum), the test |dL| <= tol is settled whenever |dL| is further than the accumulated bounds from tol -- then host and
 // device agree for certain -- and where it is not (a band eight orders of magnitude narrower than tol) the candidate is
 // handed back to the host, which fits it with its own log().  Stored models are reproduced bit for bit
-// (tests/test_hip_train_driver.py, tests/test_hip_configs.py) with the host idle.
+// (tests/test_hip_train_driver.py, tests/test_hip_configs.py) with the host idle, and every candidate of constructed growth
+// steps -- both LDS layouts, the edges of every unrolled loop below -- equals the reference's fit bit for bit
+// (tests/test_hip_em.py, through hibag_hip_test_em_fit).
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -443,7 +445,8 @@ void hibag_em_release()
 }
 
 // Fits `n_cand` candidates on the current device; see hibag_em.h.
-void hibag_em_fit_batch(const HibagEmPairs &P, const int8_t *const geno[], const double afreq[], int n_cand, double *out_freq, int *status, int *iters)
+void hibag_em_fit_batch(const HibagEmPairs &P, const int8_t *const geno[], const double afreq[], int n_cand, double *out_freq, int *status, int *iters,
+	int *layout)
 {
 	if (n_cand <= 0) return;
 	const double t_in = em_now();
@@ -452,7 +455,8 @@ void hibag_em_fit_batch(const HibagEmPairs &P, const int8_t *const geno[], const
 	if (g_em.device != dev) { hibag_em_release(); g_em.device = dev; }
 	const size_t np = (size_t)P.n_pair, nib = (size_t)P.n_ib, nh = (size_t)P.n_hap, nc = (size_t)n_cand;
 	// (the lists' own copy of G where the step leaves LDS room for it, else the gather through offsets)
-	const bool staged = 2 * np + 4 * nh <= 65535 && EmLayout(P.n_ib, P.n_pair, P.n_hap, true).total + 64 <= EM_LDS_BYTES;
+	const bool staged = hibag_em_layout(P.n_ib, P.n_pair, P.n_hap) == 1;
+	if (layout) *layout = staged ? 1 : 2;
 	// upload area (one copy), then the results (one copy back)
 	size_t o = 0;
 	auto take = [&](size_t bytes) { const size_t at = o; o = (o + std::max<size_t>(bytes, 8) + 63) & ~(size_t)63; return at; };
@@ -546,5 +550,23 @@ void hibag_em_fit_batch(const HibagEmPairs &P, const int8_t *const geno[], const
 bool hibag_em_fits(int n_ib, int n_pair, int n_hap)
 {
 	return n_hap <= 16384 && n_pair <= 65535 && n_ib > 0 && n_ib <= 65535 && EmLayout(n_ib, n_pair, n_hap, false).total + 64 <= EM_LDS_BYTES;
+}
+
+// which LDS layout a step gets: the lists' own copy of G where 16-bit positions reach every entry and LDS has room for it
+// (a step that fits staged also fits the smaller gather layout), else the gather through offsets; see hibag_em.h
+int hibag_em_layout(int n_ib, int n_pair, int n_hap)
+{
+	if (n_pair < 0 || n_hap < 0 || !hibag_em_fits(n_ib, n_pair, n_hap)) return 0;
+	const bool staged = 2 * (size_t)n_pair + 4 * (size_t)n_hap <= 65535 && EmLayout(n_ib, n_pair, n_hap, true).total + 64 <= EM_LDS_BYTES;
+	return staged ? 1 : 2;
+}
+
+void hibag_em_transpose(int n_pair, int n_hap, const int *h1, const int *h2, std::vector<int> &hoff, std::vector<int> &hent, std::vector<int> &at)
+{
+	hoff.assign((size_t)n_hap + 1, 0); hent.resize(2 * (size_t)n_pair);
+	for (int j = 0; j < n_pair; j++) { hoff[h1[j] + 1]++; hoff[h2[j] + 1]++; }
+	for (int h = 0; h < n_hap; h++) hoff[h + 1] += hoff[h];
+	at.assign(hoff.begin(), hoff.end() - 1);
+	for (int j = 0; j < n_pair; j++) { hent[at[h1[j]]++] = j; hent[at[h2[j]]++] = j; }      // (pair order; (h, h) twice)
 }
 

@@ -558,13 +558,9 @@ void search(T &t, Sampling &vs, OutClassifier &o, int mtry, bool prune, bool ver
 			const PairSet &pls = t.pl;
 			const int n_ib = (int)pls.size(), n_pair = (int)pls.p.size(), n_hap = (int)next.list.size();
 			std::vector<int> &ph1 = E.ph1, &ph2 = E.ph2, &hoff = E.hoff, &hent = E.hent;
-			ph1.resize(n_pair); ph2.resize(n_pair); hoff.assign(n_hap + 1, 0); hent.resize(2 * (size_t)n_pair);
-			for (int j = 0; j < n_pair; j++) { ph1[j] = pls.p[j].h1; ph2[j] = pls.p[j].h2; hoff[ph1[j] + 1]++; hoff[ph2[j] + 1]++; }
-			for (int h = 0; h < n_hap; h++) hoff[h + 1] += hoff[h];
-			{
-				E.at.assign(hoff.begin(), hoff.end() - 1);
-				for (int j = 0; j < n_pair; j++) { hent[E.at[ph1[j]]++] = j; hent[E.at[ph2[j]]++] = j; }      // (pair order; (h, h) twice)
-			}
+			ph1.resize(n_pair); ph2.resize(n_pair);
+			for (int j = 0; j < n_pair; j++) { ph1[j] = pls.p[j].h1; ph2[j] = pls.p[j].h2; }
+			hibag_em_transpose(n_pair, n_hap, ph1.data(), ph2.data(), hoff, hent, E.at);
 			g_em_stats[3] += n_pair; g_em_stats[4] = std::max<long long>(g_em_stats[4], n_pair);
 			for (int h = 0; h < n_hap; h++) g_em_stats[5] = std::max<long long>(g_em_stats[5], hoff[h + 1] - hoff[h]);
 			for (int k = 0; k < n_ib; k++) g_em_stats[7] = std::max<long long>(g_em_stats[7], pls.off[k + 1] - pls.off[k]);
@@ -891,6 +887,13 @@ int hibag_hip_trainer_new_classifiers(hibag_hip_trainer *t, int nclassifier, int
 }
 
 int hibag_hip_trainer_n_classifier(const hibag_hip_trainer *t) { return t ? (int)t->out.size() : 0; }
+
+int hibag_hip_trainer_em_counts(const hibag_hip_trainer *t, long long out[2])
+{
+	if (!t || !out) return hibag_fail(HIBAG_HIP_EINVAL, "trainer_em_counts: NULL argument");
+	out[0] = g_em_stats[0]; out[1] = g_em_stats[1];                  // (the calling thread's: set by its last hibag_hip_trainer_new_classifiers)
+	return 0;
+}
 
 int hibag_hip_trainer_classifier_dims(const hibag_hip_trainer *t, int idx, int *n_snp_c, int *n_haplo)
 {

@@ -171,6 +171,13 @@ class _Trainer:
         """Where the EM fits run: "auto" (the device where the trainer has two host threads or fewer), "host", "device"."""
         _lib.check(_lib.lib().hibag_hip_trainer_set_em_mode(self._h, {"auto": 0, "host": 1, "device": 2}[mode]))
 
+    def em_counts(self):
+        """(fitted, handed_back) of the calling thread's last ``new_classifiers``: the candidate SNPs the device kernel fitted
+        and how many of those it handed back to the host's own fit; (0, 0) where the host fitted everything."""
+        out = (C.c_longlong * 2)()
+        _lib.check(_lib.lib().hibag_hip_trainer_em_counts(self._h, out))
+        return int(out[0]), int(out[1])
+
     def set_shared(self, shared: bool = True):
         """The trainer runs beside others of this process: its device work goes through the device's combiners -- one fused
         launch per kind of operation for all of them (``csrc/hibag_combine.h``).  Same classifiers, bit for bit."""

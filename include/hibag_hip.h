@@ -31,7 +31,8 @@ extern "C" {
                                        + the resident cohort (hibag_hip_cohort_*, hibag_hip_predict_cohort, hibag_hip_predict_topk_cohort): likewise;
                                        + hibag_hip_predict_masked: likewise;
                                        + the draw entries (hibag_hip_predict_draw[_device, _mapped, _snp_major, _bed, _cohort]): likewise;
-                                       + hibag_hip_test_build_eval_batch (a test entry): likewise */
+                                       + hibag_hip_test_build_eval_batch (a test entry): likewise;
+                                       + hibag_hip_test_em_fit, hibag_hip_test_em_layout (test entries), hibag_hip_trainer_em_counts: likewise */
 
 /* error codes */
 #define HIBAG_HIP_OK          0
@@ -794,6 +795,10 @@ int hibag_hip_trainer_threads(const hibag_hip_trainer *t);
  * host's order; the stopping test decided with a margin for the device's log(), candidates it cannot decide handed back to the
  * host), 0 = automatic: the device where the trainer has two host threads or fewer.  Both give the same classifiers bit for bit. */
 int hibag_hip_trainer_set_em_mode(hibag_hip_trainer *t, int mode);
+/* Of the CALLING THREAD's last hibag_hip_trainer_new_classifiers call: out[0] = candidate SNPs fitted by the device kernel,
+ * out[1] = how many of those it handed back to the host (status 2).  Both 0 where the host fitted everything (EM mode 1, or
+ * steps too large for the kernel).  (Added within ABI version 7.) */
+int hibag_hip_trainer_em_counts(const hibag_hip_trainer *t, long long out[2]);
 
 /* Several trainers of ONE process on one device -- the decomposition of hlaParallelAttrBagging's workers (R/HIBAG.R:329-390:
  * independent classifiers, one random stream per worker) without a process per worker.  A trainer flagged `shared` hands
@@ -926,6 +931,37 @@ int hibag_hip_test_time_avg_prob(const void *geno, const double *weight, int n_s
 int hibag_hip_test_build_eval_batch(int n_hla, int n_sample, const int *boot, const void *base_geno, int n_snp,
 	int n_cand, const int *n_haplo, const void *haplo, const int32_t *columns, const int32_t *geno_snp_major, int n_matrix_snp,
 	const int *cand_snp, int acc_floor, int *acc_oob, double *loss_ib);
+
+/* The EM fits of one growth step's candidate SNPs on the device, on the caller's own arrays, for tests: what the training
+ * driver does per step in EM mode 2 (CAlg_EM::PrepareNewSNP + ExpectationMaximization per candidate, src/LibHLA.cpp:1127-1255)
+ * -- one call of the kernel on the calling thread's selected device, with the transposed pair lists the driver's own builder
+ * makes and the LDS layout the driver's own rule picks.
+ *   n_ib, n_pair, n_hap   in-bag samples, their haplotype pairs, DOUBLED haplotypes (even: entry 2 i carries allele 0 of the
+ *                         new SNP, 2 i + 1 allele 1)
+ *   n_samp_total          all samples of the cohort (the M step scales by 0.5 / n_samp_total)
+ *   h1, h2 [n_pair]       the pairs, indices into the doubled list; sample i owns pairs [off[i], off[i + 1]); off [n_ib + 1]
+ *   boot [n_ib]           bootstrap counts, >= 1
+ *   cur_freq [n_hap / 2]  frequencies of the current (undoubled) haplotypes
+ *   geno [n_cand][n_ib]   int8: the in-bag samples' genotype at each candidate, 0, 1, 2, or 3 = missing
+ *   afreq [n_cand]        each candidate's allele frequency in the bag, strictly inside (0, 1)
+ *   out_freq [n_cand][n_hap]   out: the fitted frequencies
+ *   status [n_cand]       out: 1 = fitted, bit-identical to the host's fit; 2 = the stopping test was too close to its
+ *                         tolerance (or the log-likelihood not finite) for the device's log() to decide it: the host must fit
+ *                         this candidate, out_freq[c] is not to be used
+ *   iters [n_cand]        out, optional: the 0-based number of the last iteration whose frequencies are returned (the
+ *                         reference's loop counter at its `break`); 501 where 500 iterations passed without convergence
+ *   layout                out, optional: the LDS layout that ran, as hibag_hip_test_em_layout names it
+ * Every size, offset, index, count, genotype and frequency is checked before the device is touched (HIBAG_HIP_EINVAL, also
+ * where hibag_hip_test_em_layout() is 0), so no input reaches the kernel that could make it index out of bounds.  Releases
+ * the calling thread's EM arena when it returns, also on an error.  (Added within ABI version 7.) */
+int hibag_hip_test_em_fit(int n_ib, int n_pair, int n_hap, int n_samp_total, const int *h1, const int *h2, const int *off,
+	const int *boot, const double *cur_freq, int n_cand, const int8_t *geno, const double *afreq, double *out_freq, int *status,
+	int *iters, int *layout);
+
+/* The LDS layout the device EM fit uses for a growth step of these dimensions -- the rule the driver itself applies, pure
+ * arithmetic, no device access: 0 = the step does not fit the kernel (the host fits it), 1 = "staged" (every haplotype's
+ * pair values have a contiguous copy the M step reads in order), 2 = "gather" (the M step reads them through offsets). */
+int hibag_hip_test_em_layout(int n_ib, int n_pair, int n_hap);
 
 #ifdef __cplusplus
 }

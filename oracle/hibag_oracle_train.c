@@ -359,12 +359,14 @@ static int prepare_new_snp(Trainer *t, int snp, const HapList *cur, HapList *nex
 	return 1;
 }
 
-/* CAlg_EM::ExpectationMaximization, :1185-1255 */
-static void expectation_maximization(Trainer *t, HapList *next)
+/* CAlg_EM::ExpectationMaximization, :1185-1255.  Returns the loop counter at the end: the 0-based number of the iteration
+ * that met the stopping test, EM_MAX_ITER + 1 where none did (the reference returns nothing; oracle_em_fit reports it). */
+static int expectation_maximization(Trainer *t, HapList *next)
 {
 	const int total = t->d.n_samp;
 	double conv_tol = 0, loglik = -1e+30;
-	for (int iter = 0; iter <= EM_MAX_ITER; iter++) {
+	int iter;
+	for (iter = 0; iter <= EM_MAX_ITER; iter++) {
 		const double old_loglik = loglik;
 		for (size_t i = 0; i < next->n; i++) { next->list[i].old_freq = next->list[i].freq; next->list[i].freq = 0; }
 		for (int i = 0; i < t->n_pl; i++) {
@@ -402,6 +404,7 @@ static void expectation_maximization(Trainer *t, HapList *next)
 			if (conv_tol < 0) conv_tol = 0;
 		}
 	}
+	return iter;
 }
 
 typedef struct { int *len; uint64_t *bits; double *freq; } Soa;
@@ -596,4 +599,52 @@ void oracle_train_free(void *handle)
 	for (int i = 0; i < t->d.n_samp; i++) free(t->pl[i].p);
 	free(t->out); free(t->g); free(t->inbag); free(t->outbag); free(t->pl); free(t->log_buf);
 	free(t);
+}
+
+/* ---- public: one candidate's EM fit on given pair lists -------------------- */
+
+/* CAlg_EM::PrepareNewSNP's frequencies and flags + ExpectationMaximization for ONE candidate SNP, on pair lists the caller
+ * gives instead of PrepareHaplotypes: h1 / h2 [n_pair] index the doubled list of n_hap haplotypes (entry 2 i: allele 0 of the
+ * new SNP, 2 i + 1: allele 1), sample i owns pairs [off[i], off[i + 1]) and has count boot[i] and genotype geno[i] (0, 1, 2,
+ * anything else = missing) at the candidate.  Fills a Trainer's own structures and runs the static functions above
+ * unchanged.  out_freq [n_hap]; returns the loop counter of expectation_maximization, -1 on a bad argument. */
+int oracle_em_fit(int n_ib, int n_hap, int n_samp_total, const int *h1, const int *h2, const int *off, const int *boot,
+	const int *geno, const double *cur_freq, double afreq, double *out_freq)
+{
+	if (n_ib <= 0 || n_hap <= 0 || (n_hap & 1) || n_samp_total <= 0 || off[0] != 0) return -1;
+	Trainer t;
+	memset(&t, 0, sizeof(t));
+	t.d.n_samp = n_samp_total;
+	t.n_pl = n_ib;
+	t.pl = (PairList *)calloc((size_t)n_ib, sizeof(PairList));
+	t.log_buf = (double *)malloc(sizeof(double) * (size_t)n_ib);
+	HapList cur, next;
+	hl_init(&cur, 1); hl_init(&next, 1);
+	hl_reserve(&cur, (size_t)n_hap / 2); hl_reserve(&next, (size_t)n_hap);
+	cur.n = (size_t)n_hap / 2; next.n = (size_t)n_hap;
+	memset(cur.list, 0, sizeof(Hap) * cur.n); memset(next.list, 0, sizeof(Hap) * next.n);
+	for (size_t i = 0; i < cur.n; i++) cur.list[i].freq = cur_freq[i];
+	/* the new SNP is bit 0 of the doubled list (DoubleHaplos with cur.n_snp = 0) */
+	cur.n_snp = 0; next.n_snp = 1;
+	for (size_t i = 0; i < next.n; i++) set_allele(&next.list[i], 0, (int)(i & 1));
+	double_haplos_init_freq(&cur, &next, afreq);
+	const int idx_new = next.n_snp - 1;
+	for (int i = 0; i < n_ib; i++) {
+		PairList *pl = &t.pl[i];
+		const int n = off[i + 1] - off[i], g = geno[i];
+		pl->boot = boot[i]; pl->samp = i; pl->n = n;
+		pl->p = (Pair *)malloc(sizeof(Pair) * (size_t)(n > 0 ? n : 1));
+		for (int j = 0; j < n; j++) {
+			Pair *p = &pl->p[j];
+			p->h1 = h1[off[i] + j]; p->h2 = h2[off[i] + j]; p->gfreq = 0;
+			p->flag = (0 <= g && g <= 2) ?                                   /* prepare_new_snp's flags, :1133-1183 */
+				(get_allele(&next.list[p->h1], idx_new) + get_allele(&next.list[p->h2], idx_new) == g) : 1;
+		}
+	}
+	const int iters = expectation_maximization(&t, &next);
+	for (size_t i = 0; i < next.n; i++) out_freq[i] = next.list[i].freq;
+	for (int i = 0; i < n_ib; i++) free(t.pl[i].p);
+	free(t.pl); free(t.log_buf);
+	hl_free(&cur); hl_free(&next);
+	return iters;
 }

@@ -269,3 +269,28 @@ def train(genomat: np.ndarray, h1, h2, n_hla: int, nclassifier: int, mtry: int, 
     finally:
         L.oracle_train_free(h)
 
+
+
+def em_fit(h1, h2, off, boot, geno_c, cur_freq, afreq: float, n_samp_total: int):
+    """One candidate SNP's EM fit (``oracle_em_fit``: PrepareNewSNP's frequencies and flags + ExpectationMaximization of the
+    oracle's trainer) on given pair lists: ``h1``/``h2`` [n_pair] index the doubled list of ``2 * len(cur_freq)`` haplotypes,
+    sample i owns pairs ``off[i]:off[i + 1]``, ``geno_c`` [n_ib] is 0/1/2 or anything else = missing.  Returns
+    (freq [n_hap], iters) -- iters = the loop counter at the stop, 501 where 500 iterations did not converge."""
+    L = lib()
+    L.oracle_em_fit.argtypes = [C.c_int, C.c_int, C.c_int, _i32p, _i32p, _i32p, _i32p, _i32p, _f64p, C.c_double, _f64p]
+    a1 = np.ascontiguousarray(h1, np.int32)
+    a2 = np.ascontiguousarray(h2, np.int32)
+    o = np.ascontiguousarray(off, np.int32)
+    b = np.ascontiguousarray(boot, np.int32)
+    g = np.ascontiguousarray(geno_c, np.int32)
+    cf = np.ascontiguousarray(cur_freq, np.float64)
+    n_ib, n_hap = len(b), 2 * len(cf)
+    if len(o) != n_ib + 1 or len(g) != n_ib or len(a1) != o[-1] or len(a2) != o[-1] or np.any(np.diff(o) < 0):
+        raise ValueError("em_fit: inconsistent pair lists")
+    if len(a1) and (min(a1.min(), a2.min()) < 0 or max(a1.max(), a2.max()) >= n_hap):
+        raise ValueError("em_fit: a pair is outside the doubled list")
+    out = np.zeros(n_hap, np.float64)
+    it = L.oracle_em_fit(n_ib, n_hap, int(n_samp_total), a1, a2, o, b, g, cf, float(afreq), out)
+    if it < 0:
+        raise ValueError("em_fit: bad arguments")
+    return out, int(it)

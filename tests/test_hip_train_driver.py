@@ -255,6 +255,18 @@ def test_training_runs_on_the_selected_device(hib, oracle):
     assert L.hibag_hip_set_device(0) == 0
 
 
+def _check_em_counts(em, fitted, handed_back):
+    """hibag_hip_trainer_em_counts of the training call just made: with the fits forced onto the device the kernel fitted
+    candidates and kept some of them (a kernel that handed everything back, or a silent fall-back to the host, would leave the
+    classifiers right and these counts wrong); forced onto the host it fitted none.  The share is printed, not capped."""
+    print(f"EM fits ({em}): {fitted} candidates on the device, {handed_back} handed back to the host"
+          + (f" ({100.0 * handed_back / fitted:.3f} %)" if fitted else ""))
+    if em == "device":
+        assert fitted > 0 and 0 <= handed_back < fitted
+    else:
+        assert (fitted, handed_back) == (0, 0)
+
+
 @pytest.mark.parametrize("em", ["device", "host"])
 def test_both_em_routes_reproduce_the_stored_model(hib, hapmap_geno, hla_type_table, model_a, em):
     """inst/extdata/ModelList.RData (set.seed(100), all 60 samples, 100 classifiers) re-trained with the EM fits forced onto the
@@ -269,7 +281,9 @@ def test_both_em_routes_reproduce_the_stored_model(hib, hapmap_geno, hla_type_ta
     tr.set_seed(100)
     tr.new_classifiers(len(model_a.classifiers), mtry, True, False, False)
     got = tr.classifiers()
+    fitted, handed_back = tr.em_counts()
     tr.close()
+    _check_em_counts(em, fitted, handed_back)
     assert len(got) == len(model_a.classifiers)
     for i, (g, w) in enumerate(zip(got, model_a.classifiers)):
         assert_same_classifier(_as_dict(g), w, i)
@@ -296,7 +310,9 @@ def test_device_em_on_random_problems(hib, oracle, seed):
     tr.set_seed(70 + seed)
     tr.new_classifiers(3, mtry, True, False, False)
     got = tr.classifiers()
+    fitted, handed_back = tr.em_counts()
     tr.close()
+    _check_em_counts("device", fitted, handed_back)
     for i, (g, w) in enumerate(zip(got, want)):
         c = hib.Classifier(snpidx=w["snpidx"], freq=w["freq"], hla=w["hla"], haplo=w["haplo"], samp_num=w["samp_num"],
                            outofbag_acc=w["acc"])
