@@ -254,13 +254,14 @@ int cohort_from_bed(const char *bed_fn, int n_samp, int n_snp, const int32_t *sn
 int predict_cohort_entry(hibag_hip_model *m, const hibag_hip_cohort *c, int first, int count, const int32_t *snp_col,
 	const int32_t *flip, int vote_method, const PredictOut &out)
 {
-	if (m && !c) return hibag_fail(HIBAG_HIP_EINVAL, "cohort is NULL");
-	if (int rc = check_predict_args(m, c, std::max(count, 0), vote_method, out.H1, out.H2)) return rc;
+	// (an unfinalized model is stated first by the entries that state it as EINVAL: check_predict_args does, before it looks at `c`)
+	if (m && !c && (m->finalized || out.list.unfinalized_code() != HIBAG_HIP_EINVAL)) return hibag_fail(HIBAG_HIP_EINVAL, "cohort is NULL");
+	if (int rc = check_predict_args(m, c, std::max(count, 0), vote_method, out.H1, out.H2, out.list.unfinalized_code())) return rc;
 	if (m->device != c->device)
 		return hibag_fail(HIBAG_HIP_EINVAL, "the cohort is on device %d, the model on device %d", c->device, m->device);
 	if (first < 0 || count < 0 || (long long)first + count > c->n_samp)
 		return hibag_fail(HIBAG_HIP_EINVAL, "samples [%d, %d + %d) lie outside the cohort's %d samples", first, first, count, c->n_samp);
-	if (out.list.on) if (int rc = check_list_args(m, count, out.list)) return rc;
+	if (int rc = check_list_args(m, count, out.list)) return rc;
 	if (!snp_col && m->n_snp > 0) return hibag_fail(HIBAG_HIP_EINVAL, "snp_col is NULL");
 	for (int k = 0; k < m->n_snp; k++)
 		if (snp_col[k] >= c->n_snp)
@@ -352,7 +353,6 @@ int hibag_hip_predict_given_cohort(hibag_hip_model *m, const hibag_hip_cohort *c
 	const int32_t *flip, int vote_method, const uint32_t *allow, int32_t *h1, int32_t *h2, double *prob, double *support,
 	double *matching, double *dosage)
 {
-	if (int rc = check_given_model(m)) return rc;
 	return predict_cohort_entry(m, c, first, count, snp_col, flip, vote_method,
 		PredictOut::given_sets(m, allow, h1, h2, prob, support, matching, dosage));
 }

@@ -7,6 +7,8 @@
 //   hibag_predict.hip  the batch driver that replaces CAttrBag_Model::PredictHLA: workspace, kernel sequence (enqueue_pack,
 //                      run_core), the host-pointer pipeline (predict_staged_locked), the SNP map upload, BED input, the
 //                      out-of-bag and masked drivers, partial sums, launch status, timing
+//   hibag_finish.hip   what depends on the finish a call runs (ListOut::kind): its argument check, the call's state on the
+//                      device, its workspace, its launch
 //   hibag_prefix.hip   hibag_hip_predict_prefix: every sub-model "first k classifiers" from one pass 1
 //   hibag_merge.hip    hibag_hip_predict_merge: k models' predictions and their merge on one stream
 //   hibag_cohort.hip   a cohort's genotypes resident on a device in 2-bit form, and the prediction entries that read them
@@ -195,6 +197,7 @@ struct hibag_hip_model {
 	// finished sample's joint dosage and support ([n_call][n_hla] then [n_call]: what the samples' children read, rebuilt by
 	// every run), and a batch's ratio vectors as k_finish_family reads them ([2 n_hla][n_pad])
 	DevBuf ws_fam_in, ws_family, ws_ratios;
+	std::vector<int32_t> fam_depth;        // the call's depths on the host [n_call]: the rounds of every batch are read off them
 	std::vector<int> engine_of, steps_of;  // per classifier: HIBAG_HIP_ENGINE_* and K steps, as finalized
 	int store_mode = 0;                    // which cell sums pass 1 stores for pass 2 (HibagModelView::store_cells)
 	int64_t second_pass_pairs = 0;         // haplotype pairs per sample pass 2 evaluates again
@@ -300,38 +303,55 @@ struct PackSource {
 	const int32_t *d_row = nullptr, *d_flip = nullptr;
 };
 
-// The list output set of the top-k entries (hibag_hip_predict_topk*), of the draw entries (hibag_hip_predict_draw*) and of
-// the group entries (hibag_hip_predict_groups*): per sample k pairs and their probabilities, [n_samp][k] each.  With it the
-// finish is k_finish_topk (the k best pairs), with `draws` set k_finish_draw (k = n_draw pairs drawn from the posterior), with
-// `plan` set k_finish_groups (k = the plan's partitions: per partition the best pair of groups, and optionally the group
-// dosages), with `given` set k_finish_given (k = 1: the best pair among the cells consistent with the sample's two allele sets
-// `allow`, a per-sample INPUT that travels with the outputs; `support`, and optionally the restricted allele dosages), with
-// `family` set k_finish_family (k = 1: the best pair under the posterior weighted by the parents' results; `support` and the
-// dosage as for `given`; the pedigree is an input in the CALL's numbering that does not travel with the outputs -- call0 says
-// where in the call the outputs stand) instead of the call / dosage / posterior kernels.
+// Which finish a call runs behind passes 1 and 2.  CALL is PredictHLA's own (the call, the dosage, the posterior matrix); the
+// others are the list entries' (include/hibag_hip.h): per sample pairs() pairs and their probabilities, [n_samp][pairs()] each.
+//   TOPK    k_finish_topk: the k best pairs
+//   DRAW    k_finish_draw: k = n_draw pairs drawn from the posterior, keyed with `seed` and the sample's index
+//   GROUPS  k_finish_groups: per partition of `plan` the best pair of groups, and optionally the group dosages
+//   GIVEN   k_finish_given: the best pair among the cells consistent with the sample's two allele sets `allow`, a per-sample
+//           INPUT that travels with the outputs; `support`, and optionally the restricted allele dosages
+//   FAMILY  k_finish_family: the best pair under the posterior weighted by the parents' results; `support` and the dosage as
+//           for GIVEN; the pedigree is an input in the CALL's numbering that does not travel with the outputs -- call0 says
+//           where in the call the outputs stand
+// What the drivers need to know of a kind they ask the methods below and hibag_finish.hip; only the fronts that build an
+// output set name one.
+enum class Finish { CALL, TOPK, DRAW, GROUPS, GIVEN, FAMILY };
+
 struct ListOut {
-	bool on = false;                       // the call is a list entry's
-	int k = 0;                             // pairs per sample: the k of the top-k entries, the n_draw of the draw entries
-	int32_t *h1 = nullptr, *h2 = nullptr;
+	Finish kind = Finish::CALL;
+	int k = 0;                             // TOPK, DRAW: the pairs per sample asked for
+	int32_t *h1 = nullptr, *h2 = nullptr;  // (GROUPS: group indices)
 	double *prob = nullptr;
-	bool draws = false;                    // which finish runs
-	uint64_t seed = 0;                     // draws: the generator's key ...
+	uint64_t seed = 0;                     // DRAW: the generator's key ...
 	int64_t sample0 = 0;                   // ... and the index, in the caller's numbering, of sample 0 of h1 / h2 / prob
-	bool groups = false;                   // the group finish runs (h1 / h2: group indices) ...
-	const hibag_hip_groups *plan = nullptr; // ... with this plan's lists ...
-	double *dosage = nullptr;              // ... and, if asked for, the group dosages [n_samp][levels()]
-	bool given = false;                    // the given finish runs (k = 1) ...
-	int n_hla = 0;                         // ... on a model of so many alleles (dosage: the restricted allele dosages [n_samp][n_hla]) ...
-	double *support = nullptr;             // ... with the consistent cells' posterior mass [n_samp] ...
-	const uint32_t *allow = nullptr;       // ... under the samples' sets [n_samp][2][W]: where the outputs are (host / device)
-	bool family = false;                   // the family finish runs (k = 1; n_hla, support, dosage as above) ...
-	const int32_t *pedigree = nullptr;     // ... under the call's pedigree [n_call][2] (HOST memory on every route) ...
-	const double *prior = nullptr;         // ... and allele prior [n_hla] (host memory; null: all 1.0) ...
-	const int32_t *depth = nullptr;        // ... with the samples' depths [n_call], which the entry computed (host memory);
-	int n_call = 0;                        // the call's samples ...
+	const hibag_hip_groups *plan = nullptr; // GROUPS: the plan whose lists the finish walks
+	double *dosage = nullptr;              // GROUPS, GIVEN, FAMILY: if asked for, [n_samp][levels()]
+	int n_hla = 0;                         // GIVEN, FAMILY: the model's alleles
+	double *support = nullptr;             // GIVEN, FAMILY: [n_samp]
+	const uint32_t *allow = nullptr;       // GIVEN: the samples' sets [n_samp][2][W], where the outputs are (host / device)
+	const int32_t *pedigree = nullptr;     // FAMILY: the call's pedigree [n_call][2] (HOST memory on every route) ...
+	const double *prior = nullptr;         // ... and allele prior [n_hla] (host memory; null: all 1.0);
+	int n_call = 0;                        // the call's samples (set with the call's state, finish_call_state) ...
 	size_t call0 = 0;                      // ... of which sample call0 is sample 0 of the outputs
-	size_t levels() const { return plan ? (size_t)plan->view.n_level : (given || family) ? (size_t)n_hla : 0; }
-	size_t allow_words() const { return given ? (size_t)2 * (((size_t)n_hla + 31) / 32) : 0; }      // of one sample
+
+	bool is_list() const { return kind != Finish::CALL; }
+	size_t pairs() const                   // per sample
+	{
+		switch (kind) {
+		case Finish::CALL: return 0;
+		case Finish::GROUPS: return plan ? (size_t)plan->view.n_part : 0;
+		case Finish::GIVEN: case Finish::FAMILY: return 1;
+		default: return (size_t)k;
+		}
+	}
+	bool has_support() const { return kind == Finish::GIVEN || kind == Finish::FAMILY; }
+	// dosage columns per sample: the plan's groups, the model's alleles
+	size_t levels() const { return kind == Finish::GROUPS ? (plan ? (size_t)plan->view.n_level : 0) : has_support() ? (size_t)n_hla : 0; }
+	size_t allow_words() const { return kind == Finish::GIVEN ? (size_t)2 * (((size_t)n_hla + 31) / 32) : 0; }      // of one sample
+	// inputs in host memory on every route: a device-pointer entry uploads them itself, and so has nothing to do for no samples
+	bool host_inputs() const { return kind == Finish::FAMILY; }
+	// an unfinalized model is ESTATE to the older entries; the given and the family entries state every rejection as EINVAL
+	int unfinalized_code() const { return has_support() ? HIBAG_HIP_EINVAL : HIBAG_HIP_ESTATE; }
 };
 
 // What a prediction call returns, the one "outputs" parameter of the drivers: the six per-sample outputs of PredictHLA (any
@@ -345,27 +365,45 @@ struct PredictOut {
 	double *postprob = nullptr;            // [n_samp][n_cell]
 	ListOut list;
 
-	static PredictOut topk(int k, int32_t *h1, int32_t *h2, double *prob, double *matching)
+	static PredictOut list_of(Finish kind, int k, int32_t *h1, int32_t *h2, double *prob, double *matching)
 	{
 		PredictOut o;
 		o.matching = matching;
-		o.list.on = true; o.list.k = k; o.list.h1 = h1; o.list.h2 = h2; o.list.prob = prob;
+		o.list.kind = kind; o.list.k = k; o.list.h1 = h1; o.list.h2 = h2; o.list.prob = prob;
 		return o;
+	}
+	static PredictOut topk(int k, int32_t *h1, int32_t *h2, double *prob, double *matching)
+	{
+		return list_of(Finish::TOPK, k, h1, h2, prob, matching);
 	}
 	static PredictOut draw(int n_draw, uint64_t seed, int64_t sample0, int32_t *h1, int32_t *h2, double *prob, double *matching)
 	{
-		PredictOut o = topk(n_draw, h1, h2, prob, matching);
-		o.list.draws = true; o.list.seed = seed; o.list.sample0 = sample0;
+		PredictOut o = list_of(Finish::DRAW, n_draw, h1, h2, prob, matching);
+		o.list.seed = seed; o.list.sample0 = sample0;
 		return o;
 	}
 	static PredictOut groups(const hibag_hip_groups *plan, int32_t *g1, int32_t *g2, double *prob, double *matching, double *dosage)
 	{
-		PredictOut o = topk(plan ? plan->view.n_part : 0, g1, g2, prob, matching);
-		o.list.groups = true; o.list.plan = plan; o.list.dosage = dosage;
+		PredictOut o = list_of(Finish::GROUPS, 0, g1, g2, prob, matching);
+		o.list.plan = plan; o.list.dosage = dosage;
 		return o;
 	}
 	static PredictOut given_sets(const hibag_hip_model *m, const uint32_t *allow, int32_t *h1, int32_t *h2, double *prob, double *support,
-		double *matching, double *dosage);         // (hibag_predict.hip: reads the model's allele count)
+		double *matching, double *dosage)
+	{
+		PredictOut o = list_of(Finish::GIVEN, 0, h1, h2, prob, matching);
+		o.list.n_hla = m ? m->n_hla : 0;
+		o.list.allow = allow; o.list.support = support; o.list.dosage = dosage;
+		return o;
+	}
+	// (the same outputs under a pedigree; the samples' depths are the call's state: finish_call_state computes them)
+	static PredictOut family(const hibag_hip_model *m, const int32_t *pedigree, const double *prior, int32_t *h1, int32_t *h2, double *prob,
+		double *support, double *matching, double *dosage)
+	{
+		PredictOut o = given_sets(m, nullptr, h1, h2, prob, support, matching, dosage);
+		o.list.kind = Finish::FAMILY; o.list.pedigree = pedigree; o.list.prior = prior;
+		return o;
+	}
 	// the set `s0` samples further on (null stays null; a draw is keyed with the sample's index in the caller's numbering)
 	PredictOut advanced(size_t s0, size_t n_hla, size_t n_cell) const
 	{
@@ -373,7 +411,7 @@ struct PredictOut {
 		auto adv = [](auto *&p, size_t by) { if (p) p += by; };
 		adv(o.H1, s0); adv(o.H2, s0); adv(o.max_prob, s0); adv(o.matching, s0);
 		adv(o.dosage, s0 * n_hla); adv(o.postprob, s0 * n_cell);
-		adv(o.list.h1, s0 * (size_t)list.k); adv(o.list.h2, s0 * (size_t)list.k); adv(o.list.prob, s0 * (size_t)list.k);
+		adv(o.list.h1, s0 * list.pairs()); adv(o.list.h2, s0 * list.pairs()); adv(o.list.prob, s0 * list.pairs());
 		adv(o.list.dosage, s0 * list.levels());
 		adv(o.list.support, s0); adv(o.list.allow, s0 * list.allow_words());
 		o.list.sample0 += (int64_t)s0; o.list.call0 += s0;
@@ -416,9 +454,21 @@ int make_batch(hibag_hip_model *m, int n_samp, bool need_best, HibagBatchView &B
 // the pack of batch samples [s0, s0 + B.n_samp) of `src` into m->ws_codes, whichever of the three forms `src` has
 void enqueue_pack(hibag_hip_model *m, HibagBatchView &B, const PackSource &src, int s0, hipStream_t st);
 void run_core(hibag_hip_model *m, HibagBatchView &B, int vote_method, double *d_part, hipStream_t st);   // passes 1 and 2 behind a pack
-int check_predict_args(hibag_hip_model *m, const void *geno, int n_samp, int vote_method, const void *H1, const void *H2);
-int check_list_args(const hibag_hip_model *m, int n_samp, const ListOut &list);       // the list entries' own arguments, behind check_predict_args
-int check_given_model(const hibag_hip_model *m);             // the given and family entries' first look at the model, before check_predict_args
+// (`unfinalized`: the code an unfinalized model gets -- ListOut::unfinalized_code() where the call has an output set)
+int check_predict_args(hibag_hip_model *m, const void *geno, int n_samp, int vote_method, const void *H1, const void *H2, int unfinalized = HIBAG_HIP_ESTATE);
+
+// ---- hibag_finish.hip: what depends on the finish a call runs, one switch over ListOut::kind each ----
+int check_list_args(const hibag_hip_model *m, int n_samp, const ListOut &list);       // the finish's own arguments, behind check_predict_args
+// What a call needs on the device before its first batch, once per run by the call's owner (StagedRun::run,
+// predict_device_entry) behind the argument checks: the constraint of a host route up on `up` (`list.allow` becomes the device
+// copy), the family entries' depths, pedigree and prior up on `st` (waited for).  `host_route`: the arrays of `list` are the
+// caller's host memory; else the call is a device-pointer entry's on the caller's stream `st`, and what goes up is chained
+// behind whatever still uses the model's workspace.
+int finish_call_state(hibag_hip_model *m, ListOut &list, int n_samp, bool host_route, hipStream_t st, hipStream_t up);
+int finish_reserve_batch(hibag_hip_model *m, const ListOut &list, int n_pad);          // the finish's own workspace for batches of up to n_pad samples
+// the finish of batch B on its partial sums B.part, with `out` already advanced to the batch's first sample
+int finish_launch(hibag_hip_model *m, HibagBatchView &B, const PredictOut &out, hipStream_t st);
+
 bool take_fault(hibag_hip_model *m);                         // a hand-over failed since the last look: counted, hand-overs off
 int sticky_fault(hibag_hip_model *m);
 int workspace_enter(hibag_hip_model *m, hipStream_t st);

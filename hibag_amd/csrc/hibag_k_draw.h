@@ -108,16 +108,13 @@ __global__ __launch_bounds__(64 * NW) void k_finish_draw(HibagModelView M, Hibag
 		int b1 = NA_INTEGER, b2 = NA_INTEGER;
 		double pr = S != S ? S : 0.0;
 		if (cell >= 0) {
-			// invert p = h2 + h1*(2n-h1-1)/2 (src/LibHLA.cpp:1523), as finish_call does
-			int h1 = 0, row = M.n_hla, rem = cell;
-			while (rem >= row) { rem -= row; row--; h1++; }
-			b1 = h1; b2 = h1 + rem;
+			cell_pair(cell, M.n_hla, b1, b2);
 			pr = normalised(part[(size_t)cell * np + s], scale, ff);      // the drawn pair's posterior: the value pass 2 added
 		}
 		H1[at + j] = b1; H2[at + j] = b2;
 		prob[at + j] = pr;
 	}
-	if (matching && wave == 0) matching[s] = part[(size_t)(P + 1) * np + s] / part[(size_t)(P + 2) * np + s];
+	if (matching && wave == 0) matching[s] = matching_of(part, P, np, s);
 }
 
 #endif

@@ -63,6 +63,21 @@ __device__ __forceinline__ double normalised(double v, bool scale, double ff) { 
 // (The call and the dosage read the ensemble sums with the default cache policy: the second and third read come out of the
 // caches.  Streamed (nt) they were measured 17 % slower for no gain elsewhere; k_finish_prob, the last reader, streams.)
 
+// What every finish kernel ends with.  The pair (h1, h2), h1 <= h2, of a cell of a model of n alleles: the inverse of
+// p = h2 + h1*(2n-h1-1)/2 (src/LibHLA.cpp:1523).
+__device__ __forceinline__ void cell_pair(int cell, int n, int &h1, int &h2)
+{
+	int row = n, rem = cell;
+	h1 = 0;
+	while (rem >= row) { rem -= row; row--; h1++; }
+	h2 = h1 + rem;
+}
+// The matching proportion (src/LibHLA.cpp:2480) of sample s: rows P + 1 and P + 2 of the ensemble sums.
+__device__ __forceinline__ double matching_of(const double *__restrict__ part, int P, size_t np, int s)
+{
+	return part[(size_t)(P + 1) * np + s] / part[(size_t)(P + 2) * np + s];
+}
+
 // k_finish_call: BestGuessEnsemble (src/LibHLA.cpp:1549-1566: first strict
 // maximum in cell order, NA when nothing is positive), the called pair's
 // probability (:2376-2382) and the matching proportion (:2480).
@@ -110,15 +125,10 @@ __device__ __forceinline__ void finish_call(const HibagModelView &M, const Hibag
 		if (best < best_s[g][lane]) { best = best_s[g][lane]; cell = cell_s[g][lane]; }
 	if (sum_w != sum_w) { cell = -1; best = sum_w; }     // poisoned batch (k_scalars): NA call, NaN probability and matching
 	int b1 = NA_INTEGER, b2 = NA_INTEGER;
-	if (cell >= 0) {
-		// invert p = h2 + h1*(2n-h1-1)/2 (src/LibHLA.cpp:1523)
-		int h1 = 0, row = M.n_hla, rem = cell;
-		while (rem >= row) { rem -= row; row--; h1++; }
-		b1 = h1; b2 = h1 + rem;
-	}
+	if (cell >= 0) cell_pair(cell, M.n_hla, b1, b2);
 	if (H1) { H1[s] = b1; H2[s] = b2; }
 	if (max_prob) max_prob[s] = (cell >= 0 || sum_w != sum_w) ? best : 0.0;
-	if (matching) matching[s] = part[(size_t)(P + 1) * np + s] / part[(size_t)(P + 2) * np + s];
+	if (matching) matching[s] = matching_of(part, P, np, s);
 }
 
 __global__ __launch_bounds__(64 * FIN_SEG) void k_finish_call(HibagModelView M, HibagBatchView B,

@@ -86,16 +86,11 @@ __global__ __launch_bounds__(64) void k_finish_given(HibagModelView M, HibagBatc
 	if (s >= B.n_samp) return;
 	if (poisoned) { cell = -1; best = sum_w; support = sum_w; }      // poisoned batch (k_scalars): NA call, NaN everywhere
 	int b1 = NA_INTEGER, b2 = NA_INTEGER;
-	if (cell >= 0) {
-		// invert p = h2 + h1*(2n-h1-1)/2 (src/LibHLA.cpp:1523), as finish_call does
-		int h1 = 0, row = n, rem = cell;
-		while (rem >= row) { rem -= row; row--; h1++; }
-		b1 = h1; b2 = h1 + rem;
-	}
+	if (cell >= 0) cell_pair(cell, n, b1, b2);
 	H1[s] = b1; H2[s] = b2;
 	prob[s] = (cell >= 0 || poisoned) ? best : 0.0;
 	support_out[s] = support;
-	if (matching) matching[s] = part[(size_t)(P + 1) * np + s] / part[(size_t)(P + 2) * np + s];
+	if (matching) matching[s] = matching_of(part, P, np, s);
 }
 
 // The dosage: thread = (sample, allele), finish_dosage's walk -- term g of allele h is the cell (g, h) for g < h, (h, g) for

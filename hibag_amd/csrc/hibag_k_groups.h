@@ -94,6 +94,7 @@ __global__ __launch_bounds__(GROUPS_THREADS) void k_finish_groups(HibagModelView
 			double pr = poisoned ? sum_w : 0.0;
 			if (cell >= 0 && !poisoned) {
 				// invert p = h2 + h1*(2n-h1-1)/2 (src/LibHLA.cpp:1523), as finish_call does: any cell of the bin names its groups
+				// (written out, not cell_pair: with the helper this kernel's register count and occupancy change)
 				int h1 = 0, row = M.n_hla, rem = cell;
 				while (rem >= row) { rem -= row; row--; h1++; }
 				const int32_t *__restrict__ of = V.group_of + (size_t)q * M.n_hla;
@@ -124,7 +125,7 @@ __global__ __launch_bounds__(GROUPS_THREADS) void k_finish_groups(HibagModelView
 				}
 			}
 		}
-		if (matching && q == 0) matching[s] = part[(size_t)(P + 1) * np + s] / part[(size_t)(P + 2) * np + s];
+		if (matching && q == 0) matching[s] = matching_of(part, P, np, s);
 	}
 }
 

@@ -95,16 +95,11 @@ __global__ __launch_bounds__(64 * (64 / KMAX)) void k_finish_topk(HibagModelView
 		if (r >= k) break;
 		const int cell = poisoned ? -1 : idx[r];
 		int b1 = NA_INTEGER, b2 = NA_INTEGER;
-		if (cell >= 0) {
-			// invert p = h2 + h1*(2n-h1-1)/2 (src/LibHLA.cpp:1523), as finish_call does
-			int h1 = 0, row = M.n_hla, rem = cell;
-			while (rem >= row) { rem -= row; row--; h1++; }
-			b1 = h1; b2 = h1 + rem;
-		}
+		if (cell >= 0) cell_pair(cell, M.n_hla, b1, b2);
 		H1[at + r] = b1; H2[at + r] = b2;
 		prob[at + r] = poisoned ? sum_w : val[r];     // (a rank without a cell still holds the list's initial 0)
 	}
-	if (matching) matching[s] = part[(size_t)(P + 1) * np + s] / part[(size_t)(P + 2) * np + s];
+	if (matching) matching[s] = matching_of(part, P, np, s);
 }
 
 #endif

@@ -121,10 +121,10 @@ void run_core(hibag_hip_model *m, HibagBatchView &B, int vote_method, double *d_
 }
 
 int check_predict_args(hibag_hip_model *m, const void *geno, int n_samp, int vote_method,
-	const void *H1, const void *H2)
+	const void *H1, const void *H2, int unfinalized)
 {
 	if (!m) return hibag_fail(HIBAG_HIP_EINVAL, "model is NULL");
-	if (!m->finalized) return hibag_fail(HIBAG_HIP_ESTATE, "model not finalized");
+	if (!m->finalized) return hibag_fail(unfinalized, "model not finalized");
 	if (vote_method < 1 || vote_method > 2)
 		return hibag_fail(HIBAG_HIP_EINVAL, "Invalid 'vote_method'.");   // src/LibHLA.cpp:2321-2322
 	if (n_samp < 0) return hibag_fail(HIBAG_HIP_EINVAL, "n_samp < 0");
@@ -132,131 +132,6 @@ int check_predict_args(hibag_hip_model *m, const void *geno, int n_samp, int vot
 	if ((H1 == nullptr) != (H2 == nullptr)) return hibag_fail(HIBAG_HIP_EINVAL, "H1 and H2 must be given together");
 	if (!m->have_snpidx)
 		return hibag_fail(HIBAG_HIP_ESTATE, "model was built without SNP indices: raw genotypes cannot be packed");
-	return 0;
-}
-
-// The given entries state their rejections as HIBAG_HIP_EINVAL throughout (include/hibag_hip.h "partial typing"), the
-// unfinalized model too, which check_predict_args reports as ESTATE to the older entries.
-int check_given_model(const hibag_hip_model *m)
-{
-	if (m && !m->finalized) return hibag_fail(HIBAG_HIP_EINVAL, "model not finalized");
-	return 0;
-}
-
-PredictOut PredictOut::given_sets(const hibag_hip_model *m, const uint32_t *allow, int32_t *h1, int32_t *h2, double *prob,
-	double *support, double *matching, double *dosage)
-{
-	PredictOut o = topk(1, h1, h2, prob, matching);
-	o.list.given = true; o.list.n_hla = m ? m->n_hla : 0;
-	o.list.allow = allow; o.list.support = support; o.list.dosage = dosage;
-	return o;
-}
-
-// ---- the family entries' call-wide state (include/hibag_hip.h "pedigrees") ----------------------------------------
-// depth(s) = 0 without a parent in the call, else 1 + the larger depth of its parents: one pass, parents precede their
-// children.  Run BEFORE the arguments are checked (the output set carries the depths), so an index the check will reject
-// counts as "no parent" here.
-static int family_depths(const int32_t *pedigree, int n_samp, std::vector<int32_t> &depth)
-{
-	depth.clear();
-	if (!pedigree || n_samp <= 0) return 0;
-	try { depth.assign((size_t)n_samp, 0); } catch (...) { return hibag_fail(HIBAG_HIP_ENOMEM, "out of host memory"); }
-	for (int s = 0; s < n_samp; s++)
-		for (int k = 0; k < 2; k++) {
-			const int32_t p = pedigree[2 * (size_t)s + k];
-			if (p >= 0 && p < s) depth[s] = std::max(depth[s], depth[p] + 1);
-		}
-	return 0;
-}
-
-// The family output set of a call: `depth` is the entry's own vector and outlives the call.
-static int family_out(const hibag_hip_model *m, int n_samp, const int32_t *pedigree, const double *prior, int32_t *h1, int32_t *h2,
-	double *prob, double *support, double *matching, double *dosage, std::vector<int32_t> &depth, PredictOut &o)
-{
-	if (int rc = check_given_model(m)) return rc;
-	if (int rc = family_depths(pedigree, n_samp, depth)) return rc;
-	o = PredictOut::topk(1, h1, h2, prob, matching);
-	o.list.family = true; o.list.n_hla = m ? m->n_hla : 0;
-	o.list.support = support; o.list.dosage = dosage;
-	o.list.pedigree = pedigree; o.list.prior = prior;
-	o.list.depth = depth.empty() ? nullptr : depth.data(); o.list.n_call = std::max(n_samp, 0);
-	return 0;
-}
-
-// where the call's inputs lie in m->ws_fam_in: the pedigree, the depths (int32), then the prior (double, 8-aligned)
-static size_t family_prior_at(size_t n_call) { return (3 * n_call * sizeof(int32_t) + 7) / 8 * 8; }
-
-static int family_reserve(hibag_hip_model *m, const ListOut &list)
-{
-	const size_t n = (size_t)list.n_call, nh = (size_t)list.n_hla;
-	if (int rc = m->ws_fam_in.reserve(family_prior_at(n) + std::max<size_t>(nh, 1) * sizeof(double))) return rc;
-	return m->ws_family.reserve(std::max<size_t>(n * (nh + 1), 1) * sizeof(double));
-}
-
-// host -> device of the call's pedigree, depths and prior on `st`, once per run (so a run repeated after a failed hand-over
-// sends them again; ws_family is rebuilt by the run itself, parents first).  Waits for the copy: the image is pageable host
-// memory about to go out of scope.
-static int family_upload(hibag_hip_model *m, const ListOut &list, hipStream_t st)
-{
-	const size_t n = (size_t)list.n_call, nh = (size_t)list.n_hla, at = family_prior_at(n);
-	std::vector<char> image;
-	try { image.assign(at + nh * sizeof(double), 0); } catch (...) { return hibag_fail(HIBAG_HIP_ENOMEM, "out of host memory"); }
-	memcpy(image.data(), list.pedigree, 2 * n * sizeof(int32_t));
-	memcpy(image.data() + 2 * n * sizeof(int32_t), list.depth, n * sizeof(int32_t));
-	if (list.prior) memcpy(image.data() + at, list.prior, nh * sizeof(double));
-	HIP_TRY(hipMemcpyAsync(m->ws_fam_in.p, image.data(), image.size(), hipMemcpyHostToDevice, st));
-	HIP_TRY(hipStreamSynchronize(st));
-	return 0;
-}
-
-static HibagFamilyView family_view(hibag_hip_model *m, const ListOut &list)
-{
-	const size_t n = (size_t)list.n_call;
-	HibagFamilyView F;
-	F.ped = m->ws_fam_in.as<int32_t>(); F.depth = F.ped + 2 * n;
-	F.prior = list.prior ? (const double *)(m->ws_fam_in.as<char>() + family_prior_at(n)) : nullptr;
-	F.fam_D = m->ws_family.as<double>(); F.fam_S = F.fam_D + n * (size_t)list.n_hla;
-	F.ratios = m->ws_ratios.as<double>();
-	F.call0 = list.call0;
-	return F;
-}
-
-// the top-k and the draw entries' own arguments, behind check_predict_args
-int check_list_args(const hibag_hip_model *m, int n_samp, const ListOut &list)
-{
-	static_assert(HIBAG_HIP_TOPK_MAX == HIBAG_TOPK_MAX && HIBAG_HIP_DRAW_MAX == HIBAG_DRAW_MAX, "the public bounds are the kernels' bounds");
-	if (list.family) {
-		if (n_samp > 0 && !list.pedigree) return hibag_fail(HIBAG_HIP_EINVAL, "pedigree is NULL");
-		if (n_samp > 0 && (!list.h1 || !list.h2 || !list.prob || !list.support))
-			return hibag_fail(HIBAG_HIP_EINVAL, "h1, h2, prob and support are all required");
-		for (int s = 0; s < n_samp; s++)
-			for (int k = 0; k < 2; k++) {
-				const int32_t p = list.pedigree[2 * (size_t)s + k];
-				if (p < -1 || p >= s)
-					return hibag_fail(HIBAG_HIP_EINVAL, "pedigree[%d][%d] = %d: a parent index must lie in -1 .. %d (parents precede "
-						"their children in the call)", s, k, (int)p, s - 1);
-			}
-		for (int h = 0; list.prior && n_samp > 0 && h < list.n_hla; h++)
-			if (!(list.prior[h] > 0) || !(list.prior[h] <= 1.79769313486231570815e+308))
-				return hibag_fail(HIBAG_HIP_EINVAL, "prior[%d] = %g: every entry of the prior must be finite and > 0", h, list.prior[h]);
-		return 0;
-	}
-	if (list.given) {
-		if (n_samp > 0 && !list.allow) return hibag_fail(HIBAG_HIP_EINVAL, "allow is NULL");
-		if (n_samp > 0 && (!list.h1 || !list.h2 || !list.prob || !list.support))
-			return hibag_fail(HIBAG_HIP_EINVAL, "h1, h2, prob and support are all required");
-		return 0;
-	}
-	if (list.groups) {
-		if (!list.plan) return hibag_fail(HIBAG_HIP_EINVAL, "the group plan is NULL");
-		if (list.plan->model != m) return hibag_fail(HIBAG_HIP_EINVAL, "the group plan was made for another model");
-	} else if (list.draws) {
-		if (list.k < 1 || list.k > HIBAG_HIP_DRAW_MAX)
-			return hibag_fail(HIBAG_HIP_EINVAL, "n_draw = %d is outside 1 .. %d (HIBAG_HIP_DRAW_MAX)", list.k, HIBAG_HIP_DRAW_MAX);
-		if (list.sample0 < 0) return hibag_fail(HIBAG_HIP_EINVAL, "sample0 = %lld is negative", (long long)list.sample0);
-	} else if (list.k < 1 || list.k > HIBAG_HIP_TOPK_MAX)
-		return hibag_fail(HIBAG_HIP_EINVAL, "k = %d is outside 1 .. %d (HIBAG_HIP_TOPK_MAX)", list.k, HIBAG_HIP_TOPK_MAX);
-	if (n_samp > 0 && (!list.h1 || !list.h2 || !list.prob)) return hibag_fail(HIBAG_HIP_EINVAL, "h1, h2 and prob are all required");
 	return 0;
 }
 
@@ -315,8 +190,8 @@ void enqueue_pack(hibag_hip_model *m, HibagBatchView &B, const PackSource &src, 
 	m->timer.end(st);
 }
 
-// `out`: device pointers.  With out.list the top-k or the draw finish runs in place of the others (of H1 .. postprob only
-// `matching` is looked at then).
+// `out`: device pointers.  The finish of out.list.kind runs behind passes 1 and 2 (finish_launch); the call's state for it is
+// on the device already (finish_call_state: the call's owner has seen to it).
 static int predict_device_locked(hibag_hip_model *m, const PackSource &src, int n_samp, int vote_method, const PredictOut &out,
 	hipStream_t st)
 {
@@ -326,12 +201,7 @@ static int predict_device_locked(hibag_hip_model *m, const PackSource &src, int 
 	// must be chained behind it (an error in a later batch used to skip the record).
 	WorkspaceGuard guard{m, st};
 	const int lim = batch_limit(m);
-	if (out.list.on && out.list.given && n_samp > 0)       // a batch's masks, word-major ([2 W][n_pad]: hibag_k_given.h)
-		if (int rc = m->ws_masks.reserve(out.list.allow_words() * (size_t)round_up(std::min(lim, n_samp), HIBAG_WAVE) * sizeof(uint32_t))) return rc;
-	const bool family = out.list.on && out.list.family;
-	std::vector<int> rounds;                               // the family finish: the distinct depths of a batch, ascending
-	if (family && n_samp > 0)                              // a batch's ratio vectors, allele-major ([2 n_hla][n_pad]: hibag_k_family.h)
-		if (int rc = m->ws_ratios.reserve((size_t)2 * std::max(out.list.n_hla, 1) * (size_t)round_up(std::min(lim, n_samp), HIBAG_WAVE) * sizeof(double))) return rc;
+	if (int rc = finish_reserve_batch(m, out.list, round_up(std::min(lim, n_samp), HIBAG_WAVE))) return rc;     // (nothing for no samples)
 	for (int s0 = 0; s0 < n_samp; s0 += lim) {
 		const int n = std::min(lim, n_samp - s0);
 		HibagBatchView B;
@@ -339,30 +209,8 @@ static int predict_device_locked(hibag_hip_model *m, const PackSource &src, int 
 		guard.enqueued = true;
 		enqueue_pack(m, B, src, s0, st);
 		run_core(m, B, vote_method, m->ws_part.as<double>(), st);
-		const PredictOut o = out.advanced((size_t)s0, (size_t)m->n_hla, (size_t)m->view.n_cell);
 		m->timer.begin(HIBAG_HIP_K_FINISH, st, true);
-		if (family) {
-			const int32_t *depth = o.list.depth + o.list.call0;
-			try {                                          // (one pass: a depth is at most the batch's generations, a small number)
-				const int deepest = *std::max_element(depth, depth + n);
-				std::vector<char> seen((size_t)deepest + 1, 0);
-				for (int s = 0; s < n; s++) seen[depth[s]] = 1;
-				rounds.clear();
-				for (int d = 0; d <= deepest; d++) if (seen[d]) rounds.push_back(d);
-			} catch (...) { return hibag_fail(HIBAG_HIP_ENOMEM, "out of host memory"); }
-			hibag_launch_finish_family(m->view, B, B.part, family_view(m, o.list), rounds.data(), (int)rounds.size(), o.list.h1,
-				o.list.h2, o.list.prob, o.list.support, o.matching, o.list.dosage, st);
-		} else if (o.list.on && o.list.given)
-			hibag_launch_finish_given(m->view, B, B.part, o.list.allow, m->ws_masks.as<uint32_t>(), o.list.h1, o.list.h2, o.list.prob,
-				o.list.support, o.matching, o.list.dosage, st);
-		else if (o.list.on && o.list.groups)
-			hibag_launch_finish_groups(m->view, B, B.part, o.list.plan->view, o.list.h1, o.list.h2, o.list.prob, o.matching, o.list.dosage, st);
-		else if (o.list.on && o.list.draws)
-			hibag_launch_finish_draw(m->view, B, B.part, o.list.k, o.list.seed, o.list.sample0, o.list.h1, o.list.h2, o.list.prob,
-				o.matching, st);
-		else if (o.list.on)
-			hibag_launch_finish_topk(m->view, B, B.part, o.list.k, o.list.h1, o.list.h2, o.list.prob, o.matching, st);
-		else hibag_launch_finish(m->view, B, B.part, o.H1, o.H2, o.max_prob, o.matching, o.dosage, o.postprob, st);
+		if (int rc = finish_launch(m, B, out.advanced((size_t)s0, (size_t)m->n_hla, (size_t)m->view.n_cell), st)) return rc;
 		m->timer.end(st);
 	}
 	HIP_TRY(hipGetLastError());
@@ -408,35 +256,33 @@ int staged_slice(const hibag_hip_model *m, int n_samp, size_t row_len)
 // vectors, so that a slice still comes down in one copy.
 struct SliceLayout {
 	PredictOut want;                       // the caller's set: which outputs are asked for, and where they go in the end
-	size_t nh = 0, P = 0, tk = 0, gd = 0, sp = 0;  // (gd: group, given or family dosages per sample, if asked for; sp: 1 with the given and family entries' support)
+	size_t nh = 0, P = 0, tk = 0, gd = 0, sp = 0;  // (of a list set, per sample: tk pairs, gd dosages if asked for, sp: 1 with a support column)
 	size_t o_h1 = 0, o_h2 = 0, o_mp = 0, o_mt = 0, o_ds = 0, o_pp = 0, o_t1 = 0, o_t2 = 0, o_tp = 0, o_sp = 0, o_gd = 0;
 	size_t bytes = 0;                      // of the buffer of one slice
 
 	SliceLayout() = default;
 	SliceLayout(size_t slice, size_t n_hla, size_t n_cell, const PredictOut &out)
-		: want(out), nh(n_hla), P(n_cell), tk(out.list.on ? (size_t)out.list.k : 0), gd(out.list.on && out.list.dosage ? out.list.levels() : 0),
-		  sp(out.list.on && (out.list.given || out.list.family) ? 1 : 0)
+		: want(out), nh(n_hla), P(n_cell), tk(out.list.pairs()), gd(out.list.dosage ? out.list.levels() : 0), sp(out.list.has_support() ? 1 : 0)
 	{
 		o_h2 = o_h1 + slice * 4; o_mp = (o_h2 + slice * 4 + 7) / 8 * 8; o_mt = o_mp + slice * 8; o_ds = o_mt + slice * 8;
 		o_pp = o_ds + slice * nh * 8;
 		o_t1 = o_ds; o_t2 = o_t1 + slice * tk * 4; o_tp = o_t2 + slice * tk * 4;
 		o_sp = o_tp + slice * tk * 8; o_gd = o_sp + slice * sp * 8;      // (the support, then the group dosages: behind the lists)
-		bytes = ((want.list.on ? o_gd + slice * gd * 8 : o_pp + (want.postprob ? slice * P * 8 : 0)) + 255) / 256 * 256;
+		bytes = ((want.list.is_list() ? o_gd + slice * gd * 8 : o_pp + (want.postprob ? slice * P * 8 : 0)) + 255) / 256 * 256;
 	}
 	// bytes from the start of the buffer that a slice of n samples uses: of the vectors (the lists ride along), of everything asked for
-	size_t vectors(size_t n) const { return want.list.on ? (sp ? o_sp + n * 8 : o_tp + n * tk * 8) : o_ds; }
-	size_t used(size_t n) const { return want.list.on ? (gd ? o_gd + n * gd * 8 : vectors(n)) : want.postprob ? o_pp + n * P * 8 : want.dosage ? o_ds + n * nh * 8 : o_ds; }
-	// the output set of a slice in the buffer at `base`: what is asked for, null for the rest
-	PredictOut bind(char *base) const
+	size_t vectors(size_t n) const { return want.list.is_list() ? (sp ? o_sp + n * 8 : o_tp + n * tk * 8) : o_ds; }
+	size_t used(size_t n) const { return want.list.is_list() ? (gd ? o_gd + n * gd * 8 : vectors(n)) : want.postprob ? o_pp + n * P * 8 : want.dosage ? o_ds + n * nh * 8 : o_ds; }
+	// the output set of a slice in the buffer at `base`: what is asked for, null for the rest; the inputs of the set are `d`'s
+	PredictOut bind(char *base, PredictOut d) const
 	{
-		PredictOut d = want;
 		if (want.H1) d.H1 = (int32_t *)(base + o_h1);
 		if (want.H2) d.H2 = (int32_t *)(base + o_h2);
 		if (want.max_prob) d.max_prob = (double *)(base + o_mp);
 		if (want.matching) d.matching = (double *)(base + o_mt);
 		if (want.dosage) d.dosage = (double *)(base + o_ds);
 		if (want.postprob) d.postprob = (double *)(base + o_pp);
-		if (want.list.on) { d.list.h1 = (int32_t *)(base + o_t1); d.list.h2 = (int32_t *)(base + o_t2); d.list.prob = (double *)(base + o_tp); }
+		if (want.list.is_list()) { d.list.h1 = (int32_t *)(base + o_t1); d.list.h2 = (int32_t *)(base + o_t2); d.list.prob = (double *)(base + o_tp); }
 		if (sp) d.list.support = (double *)(base + o_sp);
 		if (gd) d.list.dosage = (double *)(base + o_gd);
 		return d;
@@ -444,13 +290,13 @@ struct SliceLayout {
 	// a host copy of a slice's buffer -> samples [s0, s0 + n) of the caller's arrays; `matrices`: the dosage and the posterior too
 	void copy_out(const char *staged, size_t s0, size_t n, bool matrices) const
 	{
-		const PredictOut s = bind(const_cast<char *>(staged)), d = want.advanced(s0, nh, P);
+		const PredictOut s = bind(const_cast<char *>(staged), want), d = want.advanced(s0, nh, P);
 		if (d.H1) { memcpy(d.H1, s.H1, n * 4); memcpy(d.H2, s.H2, n * 4); }
 		if (d.max_prob) memcpy(d.max_prob, s.max_prob, n * 8);
 		if (d.matching) memcpy(d.matching, s.matching, n * 8);
 		if (matrices && d.dosage) memcpy(d.dosage, s.dosage, n * nh * 8);
 		if (matrices && d.postprob) memcpy(d.postprob, s.postprob, n * P * 8);
-		if (d.list.on) {
+		if (d.list.is_list()) {
 			memcpy(d.list.h1, s.list.h1, n * tk * 4); memcpy(d.list.h2, s.list.h2, n * tk * 4);
 			memcpy(d.list.prob, s.list.prob, n * tk * 8);
 			if (sp) memcpy(d.list.support, s.list.support, n * 8);
@@ -488,8 +334,6 @@ struct StagedRun {
 	char *dev_out(int i) const { return m->ws_out.as<char>() + (size_t)(i % nbuf) * L.bytes; }
 	char *pin_out(int i) const { return (char *)m->pin_out.p + (size_t)(i & 1) * L.bytes; }
 	int plan();
-	int upload_allow();
-	int upload_family();
 	int upload(int i);
 	int download(int i);
 	int drain(int i);
@@ -514,10 +358,6 @@ int StagedRun::plan()
 	if (host)
 		if (int rc = m->ws_geno.reserve(geno_bytes * nbuf)) return rc;
 	if (int rc = m->ws_out.reserve(L.bytes * nbuf)) return rc;
-	if (out.list.on && out.list.given)
-		if (int rc = m->ws_allow.reserve((size_t)n_samp * out.list.allow_words() * sizeof(uint32_t))) return rc;
-	if (out.list.on && out.list.family)
-		if (int rc = family_reserve(m, out.list)) return rc;
 	if (int rc = staged_streams(m, &ss)) return rc;
 	if (piped) {
 		// pinned staging on the host side, so that every copy call returns at once and the host thread's own work -- filling
@@ -531,26 +371,6 @@ int StagedRun::plan()
 		if (int rc = m->pin_out.reserve(L.vectors((size_t)slice))) return rc;
 	}
 	return 0;
-}
-
-// host -> device of the call's constraint (the given entries), once per run -- so a run repeated after a failed hand-over
-// sends it again --, ahead of the first slice's genotypes on the stream they take: the upload stream of a pipelined run with
-// host genotypes (in order, so the first slice's `up` event stands for it too), the kernels' stream otherwise.  It is a few
-// words per sample; every slice reads its part of the one device copy.
-int StagedRun::upload_allow()
-{
-	if (!(out.list.on && out.list.given)) return 0;
-	HIP_TRY(hipMemcpyAsync(m->ws_allow.p, out.list.allow, (size_t)n_samp * out.list.allow_words() * sizeof(uint32_t),
-		hipMemcpyHostToDevice, piped && src.geno ? ss->in : ss->run));
-	return 0;
-}
-
-// host -> device of the call's pedigree, depths and prior (the family entries), once per run like the constraint above, on
-// the kernels' stream
-int StagedRun::upload_family()
-{
-	if (!(out.list.on && out.list.family)) return 0;
-	return family_upload(m, out.list, ss->run);
 }
 
 // host -> device of slice i's genotypes (nothing to do for a payload on the device)
@@ -609,11 +429,11 @@ int StagedRun::download(int i)
 	// come down in ONE copy into pinned staging and are handed out behind the final synchronisation -- a copy into the
 	// caller's pageable memory holds the calling thread for ~12 us whatever its size, and there were four of them; the
 	// large ones (dosage, posterior) go straight to the caller's arrays.
-	if (out.H1 || out.max_prob || out.matching || out.list.on) {
+	if (out.H1 || out.max_prob || out.matching || out.list.is_list()) {
 		HIP_TRY(hipMemcpyAsync(m->pin_out.p, dev_out(i), L.vectors((size_t)n), hipMemcpyDeviceToHost, st));     // (the lists ride along)
 		small_staged = true;
 	}
-	const PredictOut d = L.bind(dev_out(i)), h = out.advanced((size_t)s0, L.nh, L.P);
+	const PredictOut d = L.bind(dev_out(i), out), h = out.advanced((size_t)s0, L.nh, L.P);
 	if (h.dosage) HIP_TRY(hipMemcpyAsync(h.dosage, d.dosage, (size_t)n * L.nh * 8, hipMemcpyDeviceToHost, st));
 	if (h.postprob) HIP_TRY(hipMemcpyAsync(h.postprob, d.postprob, (size_t)n * L.P * 8, hipMemcpyDeviceToHost, st));
 	if (L.gd) HIP_TRY(hipMemcpyAsync(h.list.dosage, d.list.dosage, (size_t)n * L.gd * 8, hipMemcpyDeviceToHost, st));
@@ -635,8 +455,10 @@ int StagedRun::run()
 	static const bool trace = getenv("HIBAG_STAGED_TRACE") != nullptr;     // diagnostic: host time of each phase on stderr
 	auto now = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
 	double tr[6] = {now(), 0, 0, 0, 0, 0};
-	if (int rc = upload_allow()) return rc;
-	if (int rc = upload_family()) return rc;
+	// the call's inputs as the kernels read them: its state goes up ahead of the first slice's genotypes, per-sample inputs on
+	// the stream those take (the upload stream of a pipelined run with host genotypes, the kernels' stream otherwise)
+	PredictOut in = out;
+	if (int rc = finish_call_state(m, in.list, n_samp, true, ss->run, piped && src.geno ? ss->in : ss->run)) return rc;
 	if (int rc = upload(0)) return rc;
 	if (trace) { if (!piped) (void)hipStreamSynchronize(ss->run); tr[1] = now(); }
 	for (int i = 0; i < n_slice; i++) {
@@ -649,10 +471,8 @@ int StagedRun::run()
 			if (piped) HIP_TRY(hipStreamWaitEvent(ss->run, ss->up[i & 1], 0));
 		}
 		if (piped && i >= 2) HIP_TRY(hipStreamWaitEvent(ss->run, ss->down[i & 1], 0));    // slice i - 2 has left the device output buffer
-		PredictOut d = L.bind(dev_out(i));
-		d.list.sample0 += s0;              // (a draw is keyed with the sample's index in the caller's numbering)
-		d.list.call0 += (size_t)s0;        // (the family entries' pedigree is in the call's numbering)
-		if (d.list.given) d.list.allow = m->ws_allow.as<uint32_t>() + (size_t)s0 * d.list.allow_words();      // (the slice's part of the device copy)
+		// (the inputs advance with the slice: per-sample arrays to its part of the device copy, indices in the caller's numbering)
+		const PredictOut d = L.bind(dev_out(i), in.advanced((size_t)s0, L.nh, L.P));
 		if (int rc = predict_device_locked(m, p, n, vote_method, d, ss->run)) return rc;
 		if (piped) HIP_TRY(hipEventRecord(ss->ran[i & 1], ss->run));
 		if (trace && piped) fprintf(stderr, "[hibag staged] slice %d enqueued at %.3f ms\n", i, now() - tr[0]);
@@ -950,22 +770,25 @@ static int predict_masked_locked(hibag_hip_model *m, const int32_t *geno, int n_
 
 extern "C" {
 
-// (the bodies of the device-pointer and host-pointer entries of each route: the plain, the top-k and the draw entries are
-// the same calls with their own output set)
-static int predict_device_entry(hibag_hip_model *m, const PackSource &src, int n_samp, int vote_method, const PredictOut &out,
-	void *stream)
+// (the bodies of the device-pointer and host-pointer entries of each route: the plain and the list entries are the same
+// calls with their own output set)
+static int predict_device_entry(hibag_hip_model *m, const PackSource &src, int n_samp, int vote_method, PredictOut out, void *stream)
 {
-	if (int rc = check_predict_args(m, src.d_geno, n_samp, vote_method, out.H1, out.H2)) return rc;
-	if (out.list.on) if (int rc = check_list_args(m, n_samp, out.list)) return rc;
+	if (int rc = check_predict_args(m, src.d_geno, n_samp, vote_method, out.H1, out.H2, out.list.unfinalized_code())) return rc;
+	if (int rc = check_list_args(m, n_samp, out.list)) return rc;
+	if (n_samp == 0 && out.list.host_inputs()) return 0;
 	std::lock_guard<std::mutex> g(m->lock);
 	if (int rc = sticky_fault(m)) return rc;
+	// the call's state goes up on the caller's stream
+	HIP_TRY(hipSetDevice(m->device));
+	if (int rc = finish_call_state(m, out.list, n_samp, false, (hipStream_t)stream, (hipStream_t)stream)) return rc;
 	return predict_device_locked(m, src, n_samp, vote_method, out, (hipStream_t)stream);
 }
 
 static int predict_entry(hibag_hip_model *m, const int32_t *geno, int n_samp, int vote_method, const PredictOut &out)
 {
-	if (int rc = check_predict_args(m, geno, n_samp, vote_method, out.H1, out.H2)) return rc;
-	if (out.list.on) if (int rc = check_list_args(m, n_samp, out.list)) return rc;
+	if (int rc = check_predict_args(m, geno, n_samp, vote_method, out.H1, out.H2, out.list.unfinalized_code())) return rc;
+	if (int rc = check_list_args(m, n_samp, out.list)) return rc;
 	if (n_samp == 0) return 0;
 	std::lock_guard<std::mutex> g(m->lock);
 	HIP_TRY(hipSetDevice(m->device));
@@ -1083,8 +906,8 @@ int hibag_hip_predict_multi(hibag_hip_model *const *models, int n_models, const 
 static int predict_mapped_entry(hibag_hip_model *m, const int32_t *geno, int n_samp, int n_geno_snp,
 	const int32_t *snp_col, const int32_t *flip, int vote_method, const PredictOut &out)
 {
-	if (int rc = check_predict_args(m, geno, n_samp, vote_method, out.H1, out.H2)) return rc;
-	if (out.list.on) if (int rc = check_list_args(m, n_samp, out.list)) return rc;
+	if (int rc = check_predict_args(m, geno, n_samp, vote_method, out.H1, out.H2, out.list.unfinalized_code())) return rc;
+	if (int rc = check_list_args(m, n_samp, out.list)) return rc;
 	if (n_geno_snp <= 0) return hibag_fail(HIBAG_HIP_EINVAL, "n_geno_snp must be positive");
 	if (!snp_col && m->n_snp > 0) return hibag_fail(HIBAG_HIP_EINVAL, "snp_col is NULL");
 	for (int k = 0; k < m->n_snp; k++)
@@ -1125,8 +948,8 @@ int hibag_hip_predict_mapped_device(hibag_hip_model *m, const int32_t *d_geno, i
 static int predict_snp_major_entry(hibag_hip_model *m, const int32_t *geno, size_t ld, int n_samp, int n_geno_snp,
 	const int32_t *snp_col, const int32_t *flip, int vote_method, const PredictOut &out)
 {
-	if (int rc = check_predict_args(m, geno, n_samp, vote_method, out.H1, out.H2)) return rc;
-	if (out.list.on) if (int rc = check_list_args(m, n_samp, out.list)) return rc;
+	if (int rc = check_predict_args(m, geno, n_samp, vote_method, out.H1, out.H2, out.list.unfinalized_code())) return rc;
+	if (int rc = check_list_args(m, n_samp, out.list)) return rc;
 	if (n_geno_snp <= 0) return hibag_fail(HIBAG_HIP_EINVAL, "n_geno_snp must be positive");
 	if (ld < (size_t)n_samp) return hibag_fail(HIBAG_HIP_EINVAL, "ld = %zu is smaller than n_samp = %d", ld, n_samp);
 	if (!snp_col && m->n_snp > n_geno_snp)
@@ -1227,8 +1050,8 @@ int hibag_hip_conv_bed(const char *bed_fn, int n_samp, int n_snp, int n_save_snp
 static int predict_bed_entry(hibag_hip_model *m, const char *bed_fn, int n_samp, int n_snp,
 	const int32_t *snp_col, const int32_t *flip, int vote_method, const PredictOut &out)
 {
-	if (int rc = check_predict_args(m, bed_fn, n_samp, vote_method, out.H1, out.H2)) return rc;
-	if (out.list.on) if (int rc = check_list_args(m, n_samp, out.list)) return rc;
+	if (int rc = check_predict_args(m, bed_fn, n_samp, vote_method, out.H1, out.H2, out.list.unfinalized_code())) return rc;
+	if (int rc = check_list_args(m, n_samp, out.list)) return rc;
 	if (!snp_col && m->n_snp > 0) return hibag_fail(HIBAG_HIP_EINVAL, "snp_col is NULL");
 	BedImage img;
 	if (int rc = load_bed(bed_fn, n_samp, n_snp, snp_col, m->n_snp, img)) return rc;
@@ -1382,14 +1205,12 @@ int hibag_hip_predict_groups_bed(hibag_hip_model *m, const char *bed_fn, int n_s
 int hibag_hip_predict_given(hibag_hip_model *m, const int32_t *geno, int n_samp, int vote_method, const uint32_t *allow,
 	int32_t *h1, int32_t *h2, double *prob, double *support, double *matching, double *dosage)
 {
-	if (int rc = check_given_model(m)) return rc;
 	return predict_entry(m, geno, n_samp, vote_method, PredictOut::given_sets(m, allow, h1, h2, prob, support, matching, dosage));
 }
 
 int hibag_hip_predict_given_device(hibag_hip_model *m, const int32_t *d_geno, int n_samp, int vote_method, const uint32_t *d_allow,
 	int32_t *d_h1, int32_t *d_h2, double *d_prob, double *d_support, double *d_matching, double *d_dosage, void *stream)
 {
-	if (int rc = check_given_model(m)) return rc;
 	PackSource src;
 	src.d_geno = d_geno;
 	return predict_device_entry(m, src, n_samp, vote_method,
@@ -1400,7 +1221,6 @@ int hibag_hip_predict_given_mapped(hibag_hip_model *m, const int32_t *geno, int 
 	const int32_t *snp_col, const int32_t *flip, int vote_method, const uint32_t *allow,
 	int32_t *h1, int32_t *h2, double *prob, double *support, double *matching, double *dosage)
 {
-	if (int rc = check_given_model(m)) return rc;
 	return predict_mapped_entry(m, geno, n_samp, n_geno_snp, snp_col, flip, vote_method,
 		PredictOut::given_sets(m, allow, h1, h2, prob, support, matching, dosage));
 }
@@ -1409,7 +1229,6 @@ int hibag_hip_predict_given_snp_major(hibag_hip_model *m, const int32_t *geno, s
 	const int32_t *snp_col, const int32_t *flip, int vote_method, const uint32_t *allow,
 	int32_t *h1, int32_t *h2, double *prob, double *support, double *matching, double *dosage)
 {
-	if (int rc = check_given_model(m)) return rc;
 	return predict_snp_major_entry(m, geno, ld, n_samp, n_geno_snp, snp_col, flip, vote_method,
 		PredictOut::given_sets(m, allow, h1, h2, prob, support, matching, dosage));
 }
@@ -1418,66 +1237,45 @@ int hibag_hip_predict_given_bed(hibag_hip_model *m, const char *bed_fn, int n_sa
 	const int32_t *snp_col, const int32_t *flip, int vote_method, const uint32_t *allow,
 	int32_t *h1, int32_t *h2, double *prob, double *support, double *matching, double *dosage)
 {
-	if (int rc = check_given_model(m)) return rc;
 	return predict_bed_entry(m, bed_fn, n_samp, n_snp, snp_col, flip, vote_method,
 		PredictOut::given_sets(m, allow, h1, h2, prob, support, matching, dosage));
 }
 
 // ---- calls weighted by the parents' posteriors (include/hibag_hip.h "pedigrees") --------------------------------------
 // The same fronts with the family output set: k_finish_family in rounds of ascending depth, on the call-wide (D, S) of the
-// samples finished so far.  `pedigree` and `prior` are host memory on every route: the entry checks them and computes the
-// depths before anything is launched.
+// samples finished so far.  `pedigree` and `prior` are host memory on every route: the call's owner checks them, computes the
+// depths and sends all three up before anything is launched (finish_call_state).
 
 int hibag_hip_predict_family(hibag_hip_model *m, const int32_t *geno, int n_samp, int vote_method, const int32_t *pedigree,
 	const double *prior, int32_t *h1, int32_t *h2, double *prob, double *support, double *matching, double *dosage)
 {
-	std::vector<int32_t> depth;
-	PredictOut out;
-	if (int rc = family_out(m, n_samp, pedigree, prior, h1, h2, prob, support, matching, dosage, depth, out)) return rc;
-	return predict_entry(m, geno, n_samp, vote_method, out);
+	return predict_entry(m, geno, n_samp, vote_method, PredictOut::family(m, pedigree, prior, h1, h2, prob, support, matching, dosage));
 }
 
 int hibag_hip_predict_family_device(hibag_hip_model *m, const int32_t *d_geno, int n_samp, int vote_method, const int32_t *pedigree,
 	const double *prior, int32_t *d_h1, int32_t *d_h2, double *d_prob, double *d_support, double *d_matching, double *d_dosage,
 	void *stream)
 {
-	std::vector<int32_t> depth;
-	PredictOut out;
-	if (int rc = family_out(m, n_samp, pedigree, prior, d_h1, d_h2, d_prob, d_support, d_matching, d_dosage, depth, out)) return rc;
-	if (int rc = check_predict_args(m, d_geno, n_samp, vote_method, out.H1, out.H2)) return rc;
-	if (int rc = check_list_args(m, n_samp, out.list)) return rc;
-	if (n_samp == 0) return 0;
 	PackSource src;
 	src.d_geno = d_geno;
-	std::lock_guard<std::mutex> g(m->lock);
-	if (int rc = sticky_fault(m)) return rc;
-	// the call's inputs go up on the caller's stream, behind whatever still uses the model's workspace
-	const hipStream_t st = (hipStream_t)stream;
-	HIP_TRY(hipSetDevice(m->device));
-	if (int rc = workspace_enter(m, st)) return rc;
-	if (int rc = family_reserve(m, out.list)) return rc;
-	if (int rc = family_upload(m, out.list, st)) return rc;
-	return predict_device_locked(m, src, n_samp, vote_method, out, st);
+	return predict_device_entry(m, src, n_samp, vote_method,
+		PredictOut::family(m, pedigree, prior, d_h1, d_h2, d_prob, d_support, d_matching, d_dosage), stream);
 }
 
 int hibag_hip_predict_family_mapped(hibag_hip_model *m, const int32_t *geno, int n_samp, int n_geno_snp,
 	const int32_t *snp_col, const int32_t *flip, int vote_method, const int32_t *pedigree, const double *prior,
 	int32_t *h1, int32_t *h2, double *prob, double *support, double *matching, double *dosage)
 {
-	std::vector<int32_t> depth;
-	PredictOut out;
-	if (int rc = family_out(m, n_samp, pedigree, prior, h1, h2, prob, support, matching, dosage, depth, out)) return rc;
-	return predict_mapped_entry(m, geno, n_samp, n_geno_snp, snp_col, flip, vote_method, out);
+	return predict_mapped_entry(m, geno, n_samp, n_geno_snp, snp_col, flip, vote_method,
+		PredictOut::family(m, pedigree, prior, h1, h2, prob, support, matching, dosage));
 }
 
 int hibag_hip_predict_family_snp_major(hibag_hip_model *m, const int32_t *geno, size_t ld, int n_samp, int n_geno_snp,
 	const int32_t *snp_col, const int32_t *flip, int vote_method, const int32_t *pedigree, const double *prior,
 	int32_t *h1, int32_t *h2, double *prob, double *support, double *matching, double *dosage)
 {
-	std::vector<int32_t> depth;
-	PredictOut out;
-	if (int rc = family_out(m, n_samp, pedigree, prior, h1, h2, prob, support, matching, dosage, depth, out)) return rc;
-	return predict_snp_major_entry(m, geno, ld, n_samp, n_geno_snp, snp_col, flip, vote_method, out);
+	return predict_snp_major_entry(m, geno, ld, n_samp, n_geno_snp, snp_col, flip, vote_method,
+		PredictOut::family(m, pedigree, prior, h1, h2, prob, support, matching, dosage));
 }
 
 int hibag_hip_predict_partial_device(hibag_hip_model *m, const int32_t *d_geno, int n_samp,

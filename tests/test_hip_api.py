@@ -184,6 +184,9 @@ def crossing_case(oracle, tmp_path_factory):
     effective model-order matrix is ``Gm``; the sample-major route takes ``Gm`` itself."""
     from conftest import write_bed
     from draws_reference import draws_from_postprob
+    from family_reference import family_from_postprob, model_prior
+    from given_reference import given_from_postprob, pack
+    from groups_reference import groups_from_postprob
     from hibag_amd import synth
     from topk_reference import select
     model, founders, af = synth.make_model("hla-a-small", seed=51)
@@ -211,7 +214,28 @@ def crossing_case(oracle, tmp_path_factory):
     resident = np.concatenate([rng.integers(0, 3, (n_geno, lead)).astype(np.int32), cohorts["scattered"]], axis=1)
     want = oracle.predict(oracle.flatten(model), Gm, vote_method=1)
     k, n_draw, seed, sample0 = 3, 5, 20261018, 1000
-    return dict(model=model, n=n, lead=lead, n_geno=n_geno, Gm=Gm, flip=flip, cols=cols, cohorts=cohorts, beds=beds,
+    nh, pp = model.n_hla, want["postprob"]
+    # groups: the identity and a random map of the alleles onto 5 groups
+    group_of = np.stack([np.arange(nh), rng.integers(0, 5, nh)]).astype(np.int32)
+    # given: every set holds each allele with probability one half; sample 20 has both sets full, sample 150 an empty set A,
+    # so with slices of 64 constrained samples lie in each of the four slices (3, 70, 130 and 196 among them)
+    allowed = rng.random((n, 2, nh)) < 0.5
+    allowed[20] = True
+    allowed[150, 0] = False
+    assert all(not allowed[s].all() for s in (3, 70, 130, 196))
+    # family, with slices of 64: child 130 (slice 2) of 10 (slice 0) and 70 (slice 1); its child 195 in the last slice, the one
+    # of 8 (depth 2: three rounds); child 5 of father 0, an all-NA row and so an unknown parent; child 40 in the wavefront of
+    # both its parents 33 and 37
+    pedigree = np.full((n, 2), -1, np.int32)
+    pedigree[130] = (10, 70)
+    pedigree[195] = (130, -1)
+    pedigree[5] = (0, -1)
+    pedigree[40] = (33, 37)
+    prior = model_prior(model)
+    return dict(group_of=group_of, groups=groups_from_postprob(pp, nh, group_of), allow=pack(allowed),
+                given=given_from_postprob(pp, nh, allowed), pedigree=pedigree, prior=prior,
+                family=family_from_postprob(pp, nh, pedigree, prior),
+                model=model, n=n, lead=lead, n_geno=n_geno, Gm=Gm, flip=flip, cols=cols, cohorts=cohorts, beds=beds,
                 resident=resident, want=want, k=k, n_draw=n_draw, seed=seed, sample0=sample0,
                 topk=select(want["postprob"], k, model.n_hla),
                 draws=draws_from_postprob(want["postprob"], n_draw, seed, sample0, model.n_hla))
@@ -222,12 +246,16 @@ def test_every_route_with_every_output_set(hib, crossing_case, monkeypatch, slic
     """Routes crossed with output sets, unsliced and on the pipelined path: with ``HIBAG_STAGED_SLICE=64`` the 200 samples
     go down as slices of 64, 64, 64 and 8, so both double buffers are used twice, slices 0 and 1 are drained while 2 and 3
     run, and the last slice ends inside a wavefront.  Every plain output equals the oracle's on the effective model-order
-    matrix exactly; the lists equal the reference selection / the reference draws from the oracle's posterior; an array that
-    is not asked for is not touched."""
+    matrix exactly; the lists equal the reference selection / the reference draws from the oracle's posterior; the group,
+    given and family calls equal their references on that posterior (the constraint is advanced slice by slice, the pedigree
+    is read across slices); an array that is not asked for is not touched."""
     import ctypes as C
     import os
     import hibag_amd as hb
     from draws_reference import assert_draws_equal
+    from family_reference import assert_family_equal
+    from given_reference import assert_given_equal
+    from groups_reference import assert_groups_equal
     from hibag_amd import _lib
     from topk_reference import assert_topk_equal
     if slice_env:
@@ -241,6 +269,7 @@ def test_every_route_with_every_output_set(hib, crossing_case, monkeypatch, slic
     snp = hb.HlaSNPGeno(genotype=c["resident"], sample_id=[str(i) for i in range(n_res)], snp_id=[f"r{i}" for i in range(c["n_geno"])],
                         snp_position=np.arange(c["n_geno"], dtype=np.float64), snp_allele=["A/G"] * c["n_geno"], assembly="hg19")
     sm = np.ascontiguousarray(c["cohorts"]["scattered"].T)                   # the cohort's own matrix, sample-major
+    plan = m.groups_plan(c["group_of"])
     with hb.HlaDeviceCohort(snp) as coh:
         window = dict(first=c["lead"], count=n)
         # route: (the wrapper's method suffix, its arguments, its keywords, the C entry's suffix, the C arguments before vote_method)
@@ -276,4 +305,16 @@ def test_every_route_with_every_output_set(hib, crossing_case, monkeypatch, slic
             assert_topk_equal(top, dict(c["topk"], matching=want["matching"]), name)
             drawn = getattr(m, "predict_draw" + suffix)(*args, c["n_draw"], c["seed"], 1, sample0=c["sample0"], **kw)
             assert_draws_equal(drawn, dict(c["draws"], matching=want["matching"]), name)
+            for want_dosage in (False, True):
+                got = getattr(m, "predict_groups" + suffix)(*args, plan, 1, want_dosage=want_dosage, **kw)
+                assert ("dosage" in got) == want_dosage, name
+                assert_groups_equal(got, dict(c["groups"], matching=want["matching"]), name + ", groups")
+                got = getattr(m, "predict_given" + suffix)(*args, c["allow"], 1, want_dosage=want_dosage, **kw)
+                assert ("dosage" in got) == want_dosage, name
+                assert_given_equal(got, dict(c["given"], matching=want["matching"]), name + ", given")
+                if suffix in ("", "_mapped", "_snp_major"):                  # (the routes the family entries have)
+                    got = getattr(m, "predict_family" + suffix)(*args, c["pedigree"], c["prior"], 1, want_dosage=want_dosage, **kw)
+                    assert ("dosage" in got) == want_dosage, name
+                    assert_family_equal(got, dict(c["family"], matching=want["matching"]), name + ", family")
+    plan.close()
     assert m.status() == 0 and m.handover_faults() == 0
