@@ -5,11 +5,13 @@
  * Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg use it,
  * and only as the checker / the timed CPU baseline.
  *
- * PARITY PIN.  The reference sources cannot be compiled in this image (every
- * translation unit of /root/reference/src includes <R.h>; R, RcppParallel and
- * TBB are absent, and stand-in headers are not allowed), so there is no
- * oracle/_ref build.  The restatement is instead pinned against outputs the
- * reference itself produced and stored in its own fixtures:
+ * PARITY PIN.  Twice.  By execution: where the HIBAG package sources are at
+ * hand, oracle.build_ref() compiles its library files as they are (stand-in R
+ * headers in oracle/ref_shim, a C front end in oracle/ref_driver.cpp) into the
+ * ignored oracle/_ref/, and tests/test_ref_pin.py requires PredictHLA and
+ * BuildClassifiers of that library to equal this restatement as bits, at every
+ * SNP word count, for both votes, under five of its kernel targets.  And
+ * against outputs the reference itself produced and stored in its own fixtures:
  *   - `outofbag.acc` of each of the 2 x 100 classifiers in
  *     inst/extdata/ModelList.RData and inst/extdata/OutOfBag.RData
  *     (= 0.5 * #correct alleles / #OOB from _BestGuess over the out-of-bag

@@ -39,6 +39,55 @@ def build(force: bool = False) -> str:
     return _LIB_PATH
 
 
+REF_DIR_DEFAULT = "/root/reference"
+REF_LIB_PATH = os.path.join(_HERE, "_ref", "libhibag_ref.so")
+# what R's own build passes (CXX_STD, -O2, -fPIC), and nothing else: no -march, so no fused multiply-add outside the
+# translation units that select a target for themselves
+REF_CXXFLAGS = ["-O2", "-std=c++14", "-fPIC"]
+
+
+def ref_dir() -> str:
+    """Where the HIBAG package sources are looked for (``HIBAG_REFERENCE_DIR``)."""
+    return os.environ.get("HIBAG_REFERENCE_DIR") or REF_DIR_DEFAULT
+
+
+def build_ref(force: bool = False):
+    """Compile the HIBAG library sources (``src/LibHLA*.cpp`` of the package in :func:`ref_dir`) with ``ref_driver.cpp``
+    against the stand-in R headers of ``ref_shim/`` into ``oracle/_ref/libhibag_ref.so`` and return its path.
+
+    Without the source directory nothing is rebuilt or deleted: the existing library's path, or ``None``.  Neither the
+    sources nor anything compiled from them belongs in the repository; ``oracle/_ref/`` is ignored."""
+    import glob
+    src_dir = os.path.join(ref_dir(), "src")
+    srcs = sorted(glob.glob(os.path.join(src_dir, "LibHLA*.cpp")))
+    if not srcs:
+        return REF_LIB_PATH if os.path.exists(REF_LIB_PATH) else None
+    shim = os.path.join(_HERE, "ref_shim")
+    driver = os.path.join(_HERE, "ref_driver.cpp")
+    inc = os.path.join(ref_dir(), "inst", "include")
+    deps = srcs + [driver] + glob.glob(os.path.join(src_dir, "*.h")) + glob.glob(os.path.join(inc, "*.h")) + \
+        glob.glob(os.path.join(shim, "*.h")) + glob.glob(os.path.join(shim, "tbb", "*.h"))
+    if not force and os.path.exists(REF_LIB_PATH) and all(
+            os.path.getmtime(d) <= os.path.getmtime(REF_LIB_PATH) for d in deps):
+        return REF_LIB_PATH
+    out_dir = os.path.dirname(REF_LIB_PATH)
+    os.makedirs(out_dir, exist_ok=True)
+    cxx = os.environ.get("CXX", "g++")
+    head = [cxx] + REF_CXXFLAGS + ["-I" + shim, "-I" + inc, "-I" + src_dir]
+    objs, procs = [], []
+    for s in srcs + [driver]:
+        o = os.path.join(out_dir, os.path.splitext(os.path.basename(s))[0] + ".o")
+        objs.append(o)
+        procs.append((s, subprocess.Popen(head + ["-c", s, "-o", o])))
+    failed = [s for s, p in procs if p.wait() != 0]
+    if failed:
+        raise RuntimeError(f"build_ref: compiling failed for {failed}")
+    tmp = REF_LIB_PATH + ".tmp"
+    subprocess.check_call([cxx] + REF_CXXFLAGS + ["-shared", "-o", tmp] + objs)
+    os.replace(tmp, REF_LIB_PATH)
+    return REF_LIB_PATH
+
+
 _lib = None
 
 

@@ -1,8 +1,8 @@
 """Pins the CPU oracle against outputs the reference itself produced.
 
-The reference's own tests hold no golden posteriors, and
-its sources cannot be compiled here (they need R).  What the reference does
-ship are two pre-fit models whose stored fields are outputs of the hot path:
+The reference's own tests hold no golden posteriors.  What
+the reference does ship are two pre-fit models whose stored fields are outputs
+of the hot path (tests/test_ref_pin.py runs the reference's code itself):
 
 * ``outofbag.acc`` of every classifier = 0.5 * (#correct alleles) / #OOB, with
   the count coming from ``_BestGuess`` over the out-of-bag samples
