@@ -33,6 +33,7 @@ from .given import (HlaAlleleConstraint, HlaGivenCalls, hlaConstraintFromAllele,
                     hlaPredictGiven)
 from .family import (HlaFamilyCalls, HlaMendelCheck, HlaPedigree, hlaMendelCheck, hlaModelAllelePrior,  # noqa: F401
                      hlaPedigreeFromFam, hlaPredictFamily)
+from .assoc import HlaAssocResult, hlaAssocTest  # noqa: F401
 from ._lib import HibagHipError  # noqa: F401
 
 __all__ = ["engine_kind", "engine_nkb", "engine_steps", "NA_INTEGER", "Classifier", "HlaAttrBagObj", "HlaSNPGeno", "load_geno", "load_model", "model_to_robj", "save_model",
@@ -44,5 +45,5 @@ __all__ = ["engine_kind", "engine_nkb", "engine_steps", "NA_INTEGER", "Classifie
            "HlaDeviceCohort", "hlaPredictLoci", "load_model_list", "hlaPredictDraws", "HlaPosteriorDraws",
            "HlaAlleleConstraint", "HlaGivenCalls", "hlaConstraintFromAllele", "hlaConstraintFromSets", "hlaPredictGiven",
            "HlaFamilyCalls", "HlaMendelCheck", "HlaPedigree", "hlaMendelCheck", "hlaModelAllelePrior", "hlaPedigreeFromFam",
-           "hlaPredictFamily",
+           "hlaPredictFamily", "HlaAssocResult", "hlaAssocTest",
            "set_seed"]

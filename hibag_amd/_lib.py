@@ -59,6 +59,8 @@ EXPORTS = [
     "hibag_hip_predict_given_snp_major", "hibag_hip_predict_given_bed", "hibag_hip_predict_given_cohort",
     "hibag_hip_predict_family", "hibag_hip_predict_family_device", "hibag_hip_predict_family_mapped",
     "hibag_hip_predict_family_snp_major",
+    "hibag_hip_assoc_new", "hibag_hip_assoc_free", "hibag_hip_assoc_n_tests", "hibag_hip_assoc_observed",
+    "hibag_hip_assoc_permute", "hibag_hip_assoc_labels",
 ]
 TOPK_MAX = 16      # HIBAG_HIP_TOPK_MAX of include/hibag_hip.h
 DRAW_MAX = 64      # HIBAG_HIP_DRAW_MAX
@@ -159,6 +161,15 @@ def lib() -> C.CDLL:
         L.hibag_hip_predict_family_device.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.hibag_hip_predict_family_mapped.argtypes = [vp, vp, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
         L.hibag_hip_predict_family_snp_major.argtypes = [vp, vp, C.c_size_t, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+    if hasattr(L, "hibag_hip_assoc_new"):             # (absent from an older build selected with HIBAG_HIP_LIBRARY)
+        L.hibag_hip_assoc_new.argtypes = [vp, vp, vp, i32, i32, vp, i32, i32]
+        L.hibag_hip_assoc_new.restype = vp
+        L.hibag_hip_assoc_free.argtypes = [vp]
+        L.hibag_hip_assoc_free.restype = None
+        L.hibag_hip_assoc_n_tests.argtypes = [vp]
+        L.hibag_hip_assoc_observed.argtypes = [vp, vp, vp]
+        L.hibag_hip_assoc_permute.argtypes = [vp, C.c_uint64, C.c_uint64, i64, vp, vp]
+        L.hibag_hip_assoc_labels.argtypes = [vp, C.c_uint64, C.c_uint64, i32, vp]
     if hasattr(L, "hibag_hip_cohort_new"):
         # (an older build selected with HIBAG_HIP_LIBRARY, e.g. the parent commit's for a baseline timing, lacks the cohort
         # entries: everything else still binds, and a call that needs them fails with AttributeError)

@@ -24,21 +24,9 @@
 #ifndef HIBAG_K_DRAW_H_
 #define HIBAG_K_DRAW_H_
 
-#define DRAW_PER_WAVE 16
+#include "hibag_k_philox.h"         // philox4x32_10, shared with the association tests' permutations
 
-// Philox4x32-10 (Salmon et al., SC'11): 32 x 32 -> 64 multiplies and xors on the vector ALU; the first two output words
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
-	uint32_t &w0, uint32_t &w1)
-{
-#pragma unroll
-	for (int r = 0; r < 10; r++) {
-		const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-		const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-		c1 = (uint32_t)p1; c3 = (uint32_t)p0; c0 = n0; c2 = n2;
-		k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-	}
-	w0 = c0; w1 = c1;
-}
+#define DRAW_PER_WAVE 16
 
 // one cell of the search: the running sum, then every draw that has no cell yet and whose threshold the sum has passed
 __device__ __forceinline__ void draw_step(double x, int c, double &cum, int &last, const double (&thr)[DRAW_PER_WAVE],

@@ -32,7 +32,8 @@ extern "C" {
                                        + hibag_hip_predict_masked: likewise;
                                        + the draw entries (hibag_hip_predict_draw[_device, _mapped, _snp_major, _bed, _cohort]): likewise;
                                        + hibag_hip_test_build_eval_batch (a test entry): likewise;
-                                       + hibag_hip_test_em_fit, hibag_hip_test_em_layout (test entries), hibag_hip_trainer_em_counts: likewise */
+                                       + hibag_hip_test_em_fit, hibag_hip_test_em_layout (test entries), hibag_hip_trainer_em_counts: likewise;
+                                       + the association entries (hibag_hip_assoc_*): likewise */
 
 /* error codes */
 #define HIBAG_HIP_OK          0
@@ -235,6 +236,55 @@ int hibag_hip_ld_gram_ms(hibag_hip_ld_geno *g, double *ms);
  *   r2_or_null         float64 [n_snp][n_allele], the single r^2 values (may be NULL) */
 int hibag_hip_ld_hla(hibag_hip_ld_geno *g, const int32_t *allele1, const int32_t *allele2, int n_allele,
 	double *ld, double *r2_or_null);
+
+/* ---- association tests: hlaAssocTest with max-T permutation p-values --------
+ * Chi-square tests of every allele, and of every level of every partition of the alleles, against a case / control label
+ * (R/Association.R:164-260), under the observed labelling and under permutations of it.  Every statistic is a function of
+ * the margins and of the number of case carriers, a dot product over samples; all tests under all permutations of a panel
+ * are one int8 Gram matrix on the matrix cores with exact int32 sums.  The definitions -- the statistics' operation order,
+ * the permutation generator, the counts -- are DESIGN.md section 20; results do not depend on the panel size or on how a
+ * run of permutations is split over calls. */
+typedef struct hibag_hip_assoc hibag_hip_assoc;          /* the tests of one cohort, resident on the calling thread's device */
+
+#define HIBAG_HIP_ASSOC_DOMINANT  0   /* unit = sample, feature = carries the allele                        */
+#define HIBAG_HIP_ASSOC_ADDITIVE  1   /* unit = chromosome (N = 2 n, cases = 2 n_case), feature = dosage    */
+#define HIBAG_HIP_ASSOC_RECESSIVE 2   /* unit = sample, feature = homozygous                                */
+#define HIBAG_HIP_ASSOC_GENOTYPE  3   /* 3 x 2 table none / het / hom, no continuity correction             */
+
+/* Builds the tests on the device selected by the calling thread and computes the observed statistics.
+ *   allele1 / allele2  int32 [n_samp]: 0-based indices into the caller's allele list, HIBAG_HIP_NA_INTEGER = NA; a sample
+ *                      with an NA allele is dropped, the others are the KEPT samples, in order
+ *   y                  int32 [n_samp]: 0 = control, 1 = case
+ *   group_of           int32 [n_part][n_allele]: the group of every allele in every partition, ids from 0; may be NULL
+ *                      with n_part = 0
+ *   model              HIBAG_HIP_ASSOC_*
+ * The tests, in order: one per allele, then for every partition one per level 0 .. the partition's largest id ("an allele
+ * of the sample is in the level" in place of "is the allele").  1 <= n_samp <= 2^24, n_allele >= 1, at most 32,767 tests;
+ * EINVAL otherwise, and for an allele index outside [0, n_allele), a label other than 0 / 1 and an unknown model.
+ * NULL on failure (hibag_hip_last_error says why). */
+hibag_hip_assoc *hibag_hip_assoc_new(const int32_t *allele1, const int32_t *allele2, const int32_t *y, int n_samp, int n_allele,
+	const int32_t *group_of, int n_part, int model);
+void hibag_hip_assoc_free(hibag_hip_assoc *h);
+int hibag_hip_assoc_n_tests(const hibag_hip_assoc *h);
+
+/* The observed labelling: stat float64 [n_tests] (NaN with an empty margin) and table int64 [n_tests][6], the cell counts
+ * in units, row-major rows x (control, case): rows (without, with) for the 2 x 2 models -- cells 4 and 5 are 0 --, rows
+ * (none, het, hom) for HIBAG_HIP_ASSOC_GENOTYPE. */
+int hibag_hip_assoc_observed(hibag_hip_assoc *h, double *stat, int64_t *table);
+
+/* Permutations perm0 .. perm0 + n_perm - 1 of the labels over the kept samples (perm0 >= 1: permutation 0 is the observed
+ * labelling; permutation p depends on (seed, p) and the kept samples' number and case count alone):
+ *   max_stat     float64 [n_perm]: the largest non-NaN statistic over the tests under each permutation, NaN if none
+ *   count_point  int64 [n_tests]: the permutations of THIS call with stat[t] >= the observed stat[t] (0 where that is NaN)
+ * A run may be split over calls, handles and devices: max_stat concatenates and the counts add.  The work goes in panels
+ * of permutations (HIBAG_ASSOC_PANEL_PERMS per panel if that is set, read per call; else about 64 MB per buffer), so
+ * device memory does not grow with n_perm beyond 8 bytes each. */
+int hibag_hip_assoc_permute(hibag_hip_assoc *h, uint64_t seed, uint64_t perm0, int64_t n_perm, double *max_stat,
+	int64_t *count_point);
+
+/* The label rows of permutations perm0 .. perm0 + n - 1 themselves: out int8 [n][kept samples], 0 / 1 (for tests of the
+ * generator). */
+int hibag_hip_assoc_labels(hibag_hip_assoc *h, uint64_t seed, uint64_t perm0, int n, int8_t *out);
 
 /* ---- several models of one locus, merged: hlaPredMerge on the device ----------
  * hlaPredMerge(hlaPredict(m1, type = "response+prob"), hlaPredict(m2, ...), ...) (R/HIBAG.R:825-1023 around HIBAG_SumList,
