@@ -20,6 +20,7 @@ from .evaluate import (hlaAlleleSubset, hlaCompareAllele, hlaFlankingSNP, hlaGen
                        r_sample)
 from .oob import hlaOutOfBag  # noqa: F401
 from .oobens import hlaOutOfBagEnsemble, out_of_bag_mask  # noqa: F401
+from .importance import HlaSNPImportance, hlaSNPImportance  # noqa: F401
 from .ld import hlaGenoLD, hlaLDMatrix  # noqa: F401
 from .distance import hlaDistance  # noqa: F401
 from .submodel import hlaCombineModelObj, hlaSubModelObj  # noqa: F401
@@ -36,7 +37,7 @@ from .family import (HlaFamilyCalls, HlaMendelCheck, HlaPedigree, hlaMendelCheck
 from .assoc import HlaAssocResult, hlaAssocTest  # noqa: F401
 from ._lib import HibagHipError  # noqa: F401
 
-__all__ = ["engine_kind", "engine_nkb", "engine_steps", "NA_INTEGER", "Classifier", "HlaAttrBagObj", "HlaSNPGeno", "load_geno", "load_model", "model_to_robj", "save_model",
+__all__ = ["hlaSNPImportance", "HlaSNPImportance", "engine_kind", "engine_nkb", "engine_steps", "NA_INTEGER", "Classifier", "HlaAttrBagObj", "HlaSNPGeno", "load_geno", "load_model", "model_to_robj", "save_model",
            "HlaAlleleClass", "HlaAttrBagClass", "hlaClose", "hlaModelFromObj", "hlaModelToObj",
            "hlaPredict", "hlaSetKernelTarget", "hlaGenoSwitchStrand", "hlaSNPID", "HibagHipError",
            "HlaBEDGeno", "hlaBED2Geno", "hlaLociInfo", "RRandom", "hlaAllele", "hlaAttrBagging", "hlaConcurrentAttrBagging", "hlaParallelAttrBagging", "hlaUniqueAllele", "hlaAlleleDigit", "hlaPredMerge", "hlaPredictMerge", "hlaAlleleSubset", "hlaCompareAllele", "hlaFlankingSNP", "hlaGenoSubset",

@@ -61,6 +61,7 @@ EXPORTS = [
     "hibag_hip_predict_family_snp_major",
     "hibag_hip_assoc_new", "hibag_hip_assoc_free", "hibag_hip_assoc_n_tests", "hibag_hip_assoc_observed",
     "hibag_hip_assoc_permute", "hibag_hip_assoc_labels",
+    "hibag_hip_oob_knock_variants", "hibag_hip_oob_knock",
 ]
 TOPK_MAX = 16      # HIBAG_HIP_TOPK_MAX of include/hibag_hip.h
 DRAW_MAX = 64      # HIBAG_HIP_DRAW_MAX
@@ -122,6 +123,9 @@ def lib() -> C.CDLL:
     L.hibag_hip_predict_oob.argtypes = [vp, vp, i32, vp, vp, vp, vp]
     if hasattr(L, "hibag_hip_predict_masked"):        # (absent from an older build selected with HIBAG_HIP_LIBRARY, as below)
         L.hibag_hip_predict_masked.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp]
+    if hasattr(L, "hibag_hip_oob_knock"):             # (likewise)
+        L.hibag_hip_oob_knock_variants.argtypes = [vp, C.POINTER(i32)]
+        L.hibag_hip_oob_knock.argtypes = [vp, vp, i32, vp, vp, dbl, vp, vp, vp, vp]
     L.hibag_hip_predict_prefix.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp, vp]
     L.hibag_hip_predict_prefix_ms.argtypes = [vp, C.POINTER(dbl)]
     L.hibag_hip_predict_topk.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp]

@@ -13,6 +13,7 @@
 //   hibag_merge.hip    hibag_hip_predict_merge: k models' predictions and their merge on one stream
 //   hibag_cohort.hip   a cohort's genotypes resident on a device in 2-bit form, and the prediction entries that read them
 //   hibag_groups.hip   the plan of the group entries (hibag_hip_predict_groups*): the caller's partitions in list form
+//   hibag_knock.hip    hibag_hip_oob_knock: the out-of-bag SNP knock-out tallies in one call on the model's workspace
 #ifndef HIBAG_INTERNAL_H_
 #define HIBAG_INTERNAL_H_
 
@@ -242,6 +243,12 @@ struct hibag_hip_model {
 	// the first call), the call's mask [C][n_samp] and the batch's per-sample SNP counts [n_snp][n_pad]
 	DevBuf mask_idx, mask_use, mask_cnt;
 	bool mask_idx_ready = false;
+	// hibag_hip_oob_knock (hibag_knock.hip): the inverted index SNP -> (classifier, variant) (CSR: n_snp + 1 offsets, the
+	// classifiers, the variants; built at the first call, with its host twin), the cohort's byte codes, the call's inputs
+	// (bootstrap counts, truth, group table), a batch's picks with the base calls, and the tallies with the raw outputs
+	DevBuf knock_idx, knock_base, knock_in, knock_res, knock_out;
+	std::vector<int> knock_user_off;       // [n_snp + 1]
+	bool knock_idx_ready = false;
 
 	KernelTimer timer;
 	std::mutex lock;
@@ -264,7 +271,7 @@ struct hibag_hip_model {
 		for (DevBuf *b : {&d_int, &d_stream, &d_tile, &d_tab, &d_blk, &d_pfac, &d_phdr, &d_parow, &ws_bt, &ws_bias, &ws_cells, &ws_sync, &ws_err, &ws_planes, &ws_cw, &ws_tot, &ws_inv, &ws_winv,
 		                  &ws_part, &ws_best, &ws_vrec, &ws_geno, &ws_out, &ws_codes, &ws_allow, &ws_masks, &ws_fam_in, &ws_family, &ws_ratios, &ws_bed, &ws_bedidx, &oob_hap,
 		                  &dist_cells, &dist_tri, &dist_acc, &dist_num, &dist_out, &pfx_tab, &pfx_cw, &pfx_best, &pfx_cell,
-		                  &mask_idx, &mask_use, &mask_cnt})
+		                  &mask_idx, &mask_use, &mask_cnt, &knock_idx, &knock_base, &knock_in, &knock_res, &knock_out})
 			b->release();
 		delete prefix_layout;
 	}

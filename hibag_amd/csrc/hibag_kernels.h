@@ -125,5 +125,33 @@ struct HibagMaskView {
 // after a pack of the batch, before pass 1: the sub-models' SNP counts, then their classifier weights into B.cw / B.winv
 void hibag_launch_mask_weights(const HibagModelView &M, const HibagBatchView &B, const uint8_t *d_codes, const HibagMaskView &K,
 	hipStream_t st);
+// The out-of-bag SNP knock-out of hibag_hip_oob_knock (hibag_k_knock.h).  The call's table of virtual
+// 64-lane groups -- (snp, block): samples 64 block .. 64 block + 63 of the cohort with SNP `snp` set to missing, snp = -1
+// for a base group -- and what its three kernels read and write; a batch is groups g0 .. g0 + B.n_pad / 64 of the table.
+struct HibagKnockView {
+	const int2 *group;                 // [groups of the call]
+	int g0;                            // the batch's first group
+	int n_cohort, n_pad0;              // the cohort's samples, and their number rounded up to 64
+	const uint8_t *base;               // [n_snp][n_pad0]: the cohort's byte codes (k_codes)
+	const int32_t *samp_num;           // [C][n_cohort] bootstrap counts: 0 = out of bag
+	const int32_t *truth;              // [n_cohort][2]: the true pair as indices of the model's alleles, NA_integer_ = not counted
+	const int *user_off;               // [n_snp + 1]: the users of a SNP in model order ...
+	const int *user_cls;               // ... their classifiers ...
+	const int *user_var;               // ... and the variant snp_off[c] + j of each
+	int32_t *base_h1, *base_h2;        // [C][n_pad0]: the base groups' calls, kept for the call
+	long long *tally;                  // [n_variant + C][5]: n_ind, n_call, crt_ind, crt_haplo, n_changed; base rows last
+	int n_variant;
+	int use_threshold;                 // 0: every call counts
+	double threshold;
+	int32_t *H1, *H2;                  // optional (both or none) [n_variant + C][n_cohort]
+	double *prob;                      // optional, the same shape
+};
+// the cohort's codes, once per call: k_codes over all of d_geno [n_samp][n_snp] into d_base [n_snp][round_up(n_samp, 64)]
+void hibag_launch_knock_base(const HibagModelView &M, const int32_t *d_geno, int n_samp, uint8_t *d_base, hipStream_t st);
+// one batch of virtual groups (B from make_batch(m, 64 * groups, true, B)): the virtual codes, k_pack, the weights, pass 1
+// with its record log and the picks of hibag_launch_oob into O ([C][B.n_pad], O.ld = B.n_pad), the tallies -- the batch's
+// first `n_base` groups are base groups
+void hibag_launch_knock(const HibagModelView &M, const HibagBatchView &B, const HibagKnockView &K, uint8_t *d_codes,
+	const HibagOobOut &O, int n_base, int force_rescan, const HibagSideStream &side, hipStream_t st);
 
 #endif

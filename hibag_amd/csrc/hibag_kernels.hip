@@ -89,6 +89,7 @@ static_assert(2 * HIBAG_FP4_MAX_SNPS + 1 <= ACCUM_TAB_N, "pass 2's table must co
 #include "hibag_k_family.h"
 #include "hibag_k_oob.h"
 #include "hibag_k_mask.h"
+#include "hibag_k_knock.h"
 #include "hibag_k_cohort.h"
 
 // ---------------------------------------------------------------------------
@@ -443,4 +444,39 @@ void hibag_launch_mask_weights(const HibagModelView &M, const HibagBatchView &B,
 	if (M.n_classifier == 0 || M.n_snp == 0) return;
 	hipLaunchKernelGGL(k_mask_counts, dim3(B.n_pad / 64, M.n_snp), dim3(64), 0, st, M, B, K);
 	hipLaunchKernelGGL(k_mask_weight, dim3(B.n_pad / 64, M.n_classifier), dim3(64), 0, st, M, B, d_codes, K);
+}
+
+void hibag_launch_knock_base(const HibagModelView &M, const int32_t *d_geno, int n_samp, uint8_t *d_base, hipStream_t st)
+{
+	if (M.n_classifier == 0 || M.n_snp == 0 || n_samp <= 0) return;
+	HibagBatchView B0{};                              // (k_codes reads the two sizes only)
+	B0.n_samp = n_samp;
+	B0.n_pad = (n_samp + 63) / 64 * 64;
+	hipLaunchKernelGGL(k_codes, dim3(B0.n_pad / 64, (M.n_snp + 63) / 64), dim3(256), 0, st, M, B0, d_geno, M.n_snp,
+		(const int32_t *)nullptr, (const int32_t *)nullptr, d_base);
+}
+
+// The launcher of a knock-out batch beside hibag_launch_oob: its pass 1 and picks, launched the same way, between the
+// virtual pack and the tallies.
+#define KNOCK_TALLY_Y 16                            // workgroups that share the users of a group's SNP
+void hibag_launch_knock(const HibagModelView &M, const HibagBatchView &B, const HibagKnockView &K, uint8_t *d_codes,
+	const HibagOobOut &O, int n_base, int force_rescan, const HibagSideStream &side, hipStream_t st)
+{
+	if (M.n_classifier == 0 || M.n_snp == 0) return;
+	const unsigned groups = (unsigned)(B.n_pad / 64);
+	hipLaunchKernelGGL(k_knock_codes, dim3(groups, (M.n_snp + 3) / 4), dim3(256), 0, st, M, B, K, d_codes);
+	hipLaunchKernelGGL(k_pack, dim3(B.n_pad / HIBAG_WAVE, (M.n_classifier + PACK_WAVES - 1) / PACK_WAVES), dim3(PACK_WAVES * HIBAG_WAVE), 0, st, M, B,
+		(const uint8_t *)d_codes);
+	hipLaunchKernelGGL(k_knock_weight, dim3(groups, M.n_classifier), dim3(64), 0, st, M, B, (const uint8_t *)d_codes, K);
+	hibag_launch_total(M, B, st, side, true);
+	hipLaunchKernelGGL(k_oob_pick, dim3(B.n_pad / 64, M.n_classifier), dim3(64), 0, st, M, B, (const uint8_t *)d_codes, O, force_rescan);
+	if (M.n_wide > 0) hipLaunchKernelGGL(k_oob_scan, dim3(B.n_pad / 64, M.n_wide), dim3(64), 0, st, M, B, O);
+	if (M.n_valu > 0) {
+		const unsigned gx = (unsigned)((B.n_pad / HIBAG_WAVE + BLOCK_WAVES - 1) / BLOCK_WAVES);
+		hipLaunchKernelGGL(k_oob_best_valu, dim3(gx, M.n_classifier), dim3(BLOCK_THREADS), 0, st, M, B, O);
+	}
+	// the base groups first: the variants of this and of every later batch read the calls they keep
+	const unsigned nb = (unsigned)std::min<int>(std::max(n_base, 0), (int)groups);
+	if (nb > 0) hipLaunchKernelGGL(k_knock_tally, dim3(nb, KNOCK_TALLY_Y), dim3(64), 0, st, M, B, K, O, 0);
+	if (groups > nb) hipLaunchKernelGGL(k_knock_tally, dim3(groups - nb, KNOCK_TALLY_Y), dim3(64), 0, st, M, B, K, O, (int)nb);
 }

@@ -362,6 +362,51 @@ class HlaAttrBagClass:
                                                     _as_ptr(out["h2"]), _as_ptr(out["prob"])))
         return out
 
+    def knock_variants(self) -> int:
+        """The model's (classifier, SNP of that classifier) pairs: the rows of :meth:`predict_oob_knock` ahead of the base
+        rows (``hibag_hip_oob_knock_variants``)."""
+        n = C.c_int(0)
+        _lib.check(_lib.lib().hibag_hip_oob_knock_variants(self.handle, C.byref(n)))
+        return n.value
+
+    def predict_oob_knock(self, genomat: np.ndarray, samp_num, truth=None, call_threshold: float = float("nan"),
+                          raw: bool = False) -> dict:
+        """The out-of-bag SNP knock-out in one device call (``hibag_hip_oob_knock``): row ``v = snp_off[c] + j`` is
+        classifier c, as a one-classifier model of its own, predicting its out-of-bag samples with its j-th SNP set to
+        missing; rows ``n_variant + c`` are the base rows, nothing knocked out (:meth:`predict_oob`'s row c).
+        ``genomat`` and ``samp_num`` as for :meth:`predict_oob`; ``truth`` int32 [n_samp, 2], the true alleles as 0-based
+        indices of the model's alleles, NA = INT_MIN for a sample that is not counted (``None``: nobody is).  Returns
+        ``tally`` int64 [n_variant + n_classifier, 5] -- ``n_ind``, ``n_call``, ``crt_ind``, ``crt_haplo``, ``n_changed`` as
+        ``hlaCompareAllele`` counts them --, ``classifier`` and ``snp`` (the model SNP index) of every variant row, and with
+        ``raw=True`` the predictions ``h1``, ``h2``, ``prob`` [n_variant + n_classifier, n_samp] (NA / 0 in the bag)."""
+        g = self._genomat(genomat)
+        n, nc = g.shape[0], len(self.obj.classifiers)
+        sn = np.ascontiguousarray(samp_num, np.int32)
+        if sn.shape != (nc, n):
+            raise ValueError(f"samp_num must be [n_classifier, n_samp] = [{nc}, {n}]")
+        if truth is None:
+            tr = np.full((n, 2), np.iinfo(np.int32).min, np.int32)
+        else:
+            tr = np.asarray(truth)
+            if tr.dtype.kind not in "iu":
+                raise TypeError("truth must be an integer array")
+            if tr.shape != (n, 2):
+                raise ValueError(f"truth must be [n_samp, 2] = [{n}, 2]")
+            tr = np.ascontiguousarray(tr, np.int32)
+            if np.any((tr != np.iinfo(np.int32).min) & ((tr < 0) | (tr >= self.obj.n_hla))):
+                raise ValueError("truth holds an index outside the model's alleles")
+        nv = self.knock_variants()
+        rows = nv + nc
+        out = {"tally": np.empty((rows, 5), np.int64), "n_variant": nv,
+               "classifier": np.repeat(np.arange(nc, dtype=np.int32), [len(c.snpidx) for c in self.obj.classifiers]),
+               "snp": np.concatenate([np.asarray(c.snpidx, np.int32) for c in self.obj.classifiers] + [np.empty(0, np.int32)])}
+        if raw:
+            out.update(h1=np.empty((rows, n), np.int32), h2=np.empty((rows, n), np.int32), prob=np.empty((rows, n), np.float64))
+        _lib.check(_lib.lib().hibag_hip_oob_knock(self.handle, _as_ptr(g), n, _as_ptr(sn), _as_ptr(tr), float(call_threshold),
+                                                  _as_ptr(out["tally"]), _as_ptr(out.get("h1")), _as_ptr(out.get("h2")),
+                                                  _as_ptr(out.get("prob"))))
+        return out
+
     def predict_masked(self, geno: np.ndarray, use, vote_method: int = 1, want_dosage: bool = True,
                        want_prob: bool = False) -> dict:
         """``hibag_hip_predict_masked``: a per-sample classifier mask.  Sample s gets what ``predict_raw`` returns for it

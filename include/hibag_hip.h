@@ -33,7 +33,8 @@ extern "C" {
                                        + the draw entries (hibag_hip_predict_draw[_device, _mapped, _snp_major, _bed, _cohort]): likewise;
                                        + hibag_hip_test_build_eval_batch (a test entry): likewise;
                                        + hibag_hip_test_em_fit, hibag_hip_test_em_layout (test entries), hibag_hip_trainer_em_counts: likewise;
-                                       + the association entries (hibag_hip_assoc_*): likewise */
+                                       + the association entries (hibag_hip_assoc_*): likewise;
+                                       + the out-of-bag knock-out (hibag_hip_oob_knock, hibag_hip_oob_knock_variants): likewise */
 
 /* error codes */
 #define HIBAG_HIP_OK          0
@@ -165,6 +166,32 @@ int hibag_hip_predict_oob(hibag_hip_model *m, const int32_t *geno, int n_samp, c
  * and both passes are the model's own kernels. */
 int hibag_hip_predict_masked(hibag_hip_model *m, const int32_t *geno, int n_samp, const uint8_t *use, int vote_method,
 	int32_t *H1, int32_t *H2, double *max_prob, double *matching, double *dosage, double *postprob);
+
+/* Out-of-bag SNP knock-out (hlaSNPImportance; additive, no reference counterpart: DESIGN.md section 21).  A VARIANT is a
+ * (classifier c, position j of its SNP list) pair, numbered v = snp_off[c] + j in the order the classifiers and their SNPs
+ * were added; hibag_hip_oob_knock_variants returns their number.  Variant (c, j) is classifier c, taken as a one-classifier
+ * model of its own as in hibag_hip_predict_oob, predicting its out-of-bag samples with SNP snpidx[c][j] set to missing --
+ * bit-identical to hlaPredict(vote = "prob") of that model on those genotypes.  Beside the variants stands one BASE row per
+ * classifier with nothing knocked out: row c of hibag_hip_predict_oob.
+ *   geno, samp_num  as for hibag_hip_predict_oob
+ *   truth           int32 [n_samp][2]: the samples' true alleles as 0-based indices of the model's alleles; a sample with an
+ *                   NA_integer_ in its pair (unknown, or an allele the model does not have) is not counted
+ *   call_threshold  finite: only calls with prob >= call_threshold count as calls; not finite: every call does
+ *   tally           int64 [n_variant + n_classifier][5], the variants' rows first, then the base rows; over the samples
+ *                   that are out of bag for the row's classifier and have a truth, counted as hlaCompareAllele does
+ *                   (R/DataUtilities.R:1376-1420):
+ *                     [0] n_ind      those samples
+ *                     [1] n_call     ... with a call (not NA) that passes the threshold
+ *                     [2] crt_ind    called samples with both alleles right, in either order
+ *                     [3] crt_haplo  right alleles of the called samples (0, 1 or 2 each)
+ *                     [4] n_changed  of n_ind, the samples whose (H1, H2) differs from the base row's call (0 in base rows)
+ *   H1, H2, prob    optional (NULL: not returned; H1 and H2 only together) [n_variant + n_classifier][n_samp], rows as in
+ *                   `tally`: the predictions themselves, NA_integer_ / 0 where the sample is in the bag of the classifier
+ * All pointers are host memory.  Rejected before any launch: a NULL or unfinalized model, a model without SNP indices,
+ * n_samp < 0, a NULL input or tally.  One call: the cohort goes up once, 40 bytes per row come down. */
+int hibag_hip_oob_knock_variants(const hibag_hip_model *m, int *n_variant);
+int hibag_hip_oob_knock(hibag_hip_model *m, const int32_t *geno, int n_samp, const int32_t *samp_num, const int32_t *truth,
+	double call_threshold, int64_t *tally, int32_t *H1, int32_t *H2, double *prob);
 
 /* ---- allele distances: hlaDistance ------------------------------------------
  * hlaDistance(model) (R/HIBAG.R:1545-1570) in one call: for each classifier HIBAG_Distance (src/HIBAG.cpp:1284-1332),
