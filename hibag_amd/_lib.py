@@ -62,6 +62,7 @@ EXPORTS = [
     "hibag_hip_assoc_new", "hibag_hip_assoc_free", "hibag_hip_assoc_n_tests", "hibag_hip_assoc_observed",
     "hibag_hip_assoc_permute", "hibag_hip_assoc_labels",
     "hibag_hip_oob_knock_variants", "hibag_hip_oob_knock",
+    "hibag_hip_test_layout_plan", "hibag_hip_test_layout_count", "hibag_hip_test_layout_get", "hibag_hip_test_layout_free",
 ]
 TOPK_MAX = 16      # HIBAG_HIP_TOPK_MAX of include/hibag_hip.h
 DRAW_MAX = 64      # HIBAG_HIP_DRAW_MAX
@@ -273,6 +274,13 @@ def lib() -> C.CDLL:
         L.hibag_hip_test_em_fit.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp]
         L.hibag_hip_test_em_layout.argtypes = [i32, i32, i32]
         L.hibag_hip_trainer_em_counts.argtypes = [vp, C.POINTER(C.c_longlong)]
+    if hasattr(L, "hibag_hip_test_layout_plan"):          # (likewise)
+        L.hibag_hip_test_layout_plan.argtypes = [vp]
+        L.hibag_hip_test_layout_plan.restype = vp
+        L.hibag_hip_test_layout_count.argtypes = [vp]
+        L.hibag_hip_test_layout_get.argtypes = [vp, i32, C.POINTER(C.c_char_p), C.POINTER(vp), C.POINTER(C.c_uint64), C.POINTER(i32)]
+        L.hibag_hip_test_layout_free.argtypes = [vp]
+        L.hibag_hip_test_layout_free.restype = None
     if hasattr(L, "hibag_hip_test_read_diag"):
         L.hibag_hip_test_read_diag.argtypes = [vp, vp, i32]
         L.hibag_hip_plugin_degraded_calls.restype = i64

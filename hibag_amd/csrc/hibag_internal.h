@@ -167,6 +167,9 @@ struct StagedStreams { hipStream_t run = nullptr, in = nullptr, out = nullptr; h
 
 
 inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
+// rows of HibagBatchView::bt for a model of `bt_rows` operand rows: the model's and two spare (what pass 2 requests for a
+// block of a classifier without rows of its own)
+inline int hibag_bt_rows_alloc(int bt_rows) { return std::max(bt_rows, 1) + 2; }
 
 } // namespace hibag_detail
 using namespace hibag_detail;

@@ -789,21 +789,100 @@ int plan_ctile(ModelLayout &L)
 	return 0;
 }
 
-// One array of a device buffer: `bytes` from `src` in `room` (>= bytes) at an `align`-byte boundary, pointed at by `field`.
-struct Part { const void *src; size_t bytes, room, align; void *field; };
-template <class F, class T> Part part(const F *&field, const std::vector<T> &v, size_t align, size_t min_n = 0)
+// One array of a device buffer: `bytes` from `src` in `room` (>= bytes) at an `align`-byte boundary, pointed at by `field`;
+// `name` and `elem` (bytes per element) are what the layout export (hibag_hip_test_layout_*) hands out.
+struct Part { const char *name; const void *src; size_t bytes, room, align, elem; void *field; };
+template <class F, class T> Part part(const char *name, const F *&field, const std::vector<T> &v, size_t align, size_t min_n = 0)
 {
-	return {v.data(), v.size() * sizeof(T), std::max(v.size(), min_n) * sizeof(T), align, &field};
+	return {name, v.data(), v.size() * sizeof(T), std::max(v.size(), min_n) * sizeof(T), align, sizeof(T), &field};
+}
+
+// The arrays of the layout, one list per device buffer (in the order of LayoutTables::buf), with the room each gets and the
+// field of `V` that will point at it: what upload_layout uploads and what the layout export shows, from the same list.
+struct LayoutTables {
+	enum { INT, TILE, STREAM, BLK, PFAC, PHDR, PAROW, N_BUF };
+	std::vector<Part> buf[N_BUF];
+};
+LayoutTables layout_tables(const ModelLayout &L, HibagModelView &V)
+{
+	LayoutTables T;
+	T.buf[LayoutTables::INT] = {      // the int arrays back to back (an empty one as a single 0)
+		part("n_snp_c", V.n_snp_c, L.n_snp_c, 4, 1), part("nwp", V.nwp, L.nwp, 4, 1), part("snp_off", V.snp_off, L.snp_off, 4, 1),
+		part("snp_index", V.snp_index, L.snp_index, 4, 1), part("snp_weight", V.snp_weight, L.snp_weight, 4, 1), part("mask_row", V.mask_row, L.mask_row, 4, 1),
+		part("c_order", V.c_order, L.c_order, 4, 1), part("tile_p0", V.tile_p0, L.tile_p0, 4, 1), part("tile_n", V.tile_n, L.tile_n, 4, 1), part("cls_off", V.cls_off, L.cls_off, 4, 1),
+		part("cls_n", V.cls_n, L.cls_n, 4, 1), part("engine", V.engine, L.engine, 4, 1), part("n_step", V.n_step, L.n_step, 4, 1), part("bt_row", V.bt_row, L.bt_row, 4, 1),
+		part("cls_nblk", V.cls_nblk, L.cls_nblk, 4, 1), part("hap_off", V.hap_off, L.hap_off, 4, 1), part("item_split", V.item_split, L.item, 4, 1), part("split_row", V.split_row, L.split_row, 4, 1),
+		part("split_cls", V.split_cls, L.split_cls, 4, 1), part("item_whole", V.item_whole, L.item_whole, 4, 1), part("cell_row", V.cell_row, L.cell_row, 4, 1),
+		part("wide_cls", V.wide_cls, L.wide_cls, 4, 1), part("wide_seg", V.wide_seg, L.wseg, 4, 1), part("wide_scan", V.wide_scan, L.wide_scan, 4, 1)};
+	T.buf[LayoutTables::TILE] = {     // the tables of the pass-1 walkers and of pass 2, at the alignment of their loads
+		part("stream_off", V.stream_off, L.stream_off, 8), part("tile_meta", V.tile_meta, L.tile_meta, 4), part("cls_cnt", V.cls_cnt, L.cls_cnt, 4),
+		part("cls_cell", V.cls_cell, L.cls_cell, 4), part("blk_off", V.blk_off, L.blk_off, 8), part("ctile", V.ctile, L.ctile, 32), part("hap", V.hap, L.hap, 16),
+		part("ehdr", V.ehdr, L.ehdr, 32), part("etile_cstart", V.etile_cstart, L.etile_cstart, 4, 1), part("etile_blk0", V.etile_blk0, L.etile_blk0, 8),
+		part("blk_close", V.blk_close, L.blk_close, 4), part("wide_seg_off", V.wide_seg_off, L.wseg_off, 8, 1)};
+	T.buf[LayoutTables::STREAM] = {part("stream", V.stream, L.stream, 4)};
+	T.buf[LayoutTables::BLK] = {part("plist", V.plist, L.plist, 4)};
+	T.buf[LayoutTables::PFAC] = {part("pfac", V.pfac, L.pfac, 8)};
+	T.buf[LayoutTables::PHDR] = {part("phdr", V.phdr, L.phdr, 4)};
+	T.buf[LayoutTables::PAROW] = {{"parow", L.parow.data(), L.parow.size() * 4, std::max<size_t>(L.parow.size(), 256) * 4, 16, 4, &V.parow}};
+	return T;
+}
+
+// The scalars of the layout: those of `V`, and those the model keeps beside its view.
+struct LayoutScalars {
+	uint32_t spin_limit = 0;
+	int64_t pair_evals = 0, second_pass_pairs = 0;
+	int store_mode = 0, cell_rows = 0, bt_rows = 0, mask_rows = 0;
+	size_t stream_bytes = 0;
+	std::vector<int> engine_of, steps_of;
+};
+void layout_scalars(const ModelLayout &L, HibagModelView &V, LayoutScalars &s)
+{
+	V.n_hla = L.nh; V.n_classifier = L.C; V.n_snp = L.S; V.n_cell = L.P; V.mask_rows = L.rows; V.n_tile = L.n_tile;
+	V.n_item_split = (int)L.item.size() / 4; V.n_item_whole = (int)L.item_whole.size() / 4; V.n_split = (int)L.split_cls.size();
+	V.n_item = V.n_item_whole;
+	V.all_fp4 = 1; V.n_valu = 0;
+	for (int c = 0; c < L.C; c++) {
+		if (L.n_step[c] == 1 && !(L.engine[c] == HIBAG_ENGINE_FP4)) V.all_fp4 = 0;      // (classifiers of several K steps are not work items of k_total)
+		V.n_valu += L.engine[c] == HIBAG_ENGINE_VALU;
+	}
+	V.n_wide = (int)L.wide_cls.size();
+	V.n_wide_scan = (int)L.wide_scan.size();
+	V.n_wide_seg = (int)L.wseg.size() / 4;
+	V.split_heavy_ns = L.split_heavy_ns; V.split_rest_ns = L.split_rest_ns;
+	V.hap_dwords = (uint32_t)L.hap.size();
+	V.estream_blocks = L.estream_blocks;
+	V.p1_base = L.p1_base;
+	V.p1_blocks = L.p1_blocks;
+	V.store_cells = L.store_mode;
+	V.plist_dwords = L.plist.size();
+	V.parow_blocks = L.parow_blocks;
+	V.p1_prebuilt = L.p1_prebuilt ? 1 : 0;
+	// A chunk waits for the chunk before it, which was dispatched a whole round earlier; in the worst case the chunks of
+	// an item run one after the other, so the wait is bounded by the item's own length.  One poll lasts ~1 us (s_sleep +
+	// an L2 round trip), a 32-slot block ~1.5 us of elapsed time at full occupancy: 16 polls per block of the longest
+	// item is an order of magnitude of slack on top of the fixed 2^19 (~0.5 s).
+	long long longest = 0;
+	for (int c = 0; c < L.C; c++) longest = std::max<long long>(longest, L.engine[c] ? L.cls_nblk[c] : L.cp[c].pairs / 8);
+	s.spin_limit = (uint32_t)std::min<long long>(0xFFFFFFF0ll, (1ll << 19) + 16 * longest);
+	s.pair_evals = L.pair_evals;
+	s.store_mode = L.store_mode;
+	s.second_pass_pairs = L.second_pass_pairs;
+	s.cell_rows = L.cell_row[L.C];
+	s.bt_rows = L.bt_rows;
+	s.mask_rows = L.rows;
+	s.stream_bytes = L.stream.size() * sizeof(uint32_t);
+	s.engine_of.assign(L.engine.begin(), L.engine.begin() + L.C);
+	s.steps_of.assign(L.n_step.begin(), L.n_step.begin() + L.C);
 }
 
 // Lays `parts` out back to back in `buf` at their alignments, copies them (several: in one host image) and points their fields.
-int upload_parts(DevBuf &buf, std::initializer_list<Part> parts)
+int upload_parts(DevBuf &buf, const std::vector<Part> &parts)
 {
 	std::vector<size_t> at;
 	size_t end = 0;
 	for (const Part &p : parts) { at.push_back((end + p.align - 1) / p.align * p.align); end = at.back() + p.room; }
 	if (int rc = buf.reserve(end)) return rc;
-	const Part *p = parts.begin();
+	const Part *p = parts.data();
 	if (parts.size() == 1 && p->bytes) HIP_TRY(hipMemcpy(buf.p, p->src, p->bytes, hipMemcpyHostToDevice));     // (big arrays: no staging)
 	else if (parts.size() > 1) {
 		std::vector<char> img(end, 0);
@@ -819,76 +898,37 @@ int upload_layout(hibag_hip_model *m, const ModelLayout &L)
 {
 	HIP_TRY(hipSetDevice(m->device));
 	HibagModelView &V = m->view;
-	if (int rc = upload_parts(m->d_int, {      // the int arrays back to back (an empty one as a single 0)
-		part(V.n_snp_c, L.n_snp_c, 4, 1), part(V.nwp, L.nwp, 4, 1), part(V.snp_off, L.snp_off, 4, 1),
-		part(V.snp_index, L.snp_index, 4, 1), part(V.snp_weight, L.snp_weight, 4, 1), part(V.mask_row, L.mask_row, 4, 1),
-		part(V.c_order, L.c_order, 4, 1), part(V.tile_p0, L.tile_p0, 4, 1), part(V.tile_n, L.tile_n, 4, 1), part(V.cls_off, L.cls_off, 4, 1),
-		part(V.cls_n, L.cls_n, 4, 1), part(V.engine, L.engine, 4, 1), part(V.n_step, L.n_step, 4, 1), part(V.bt_row, L.bt_row, 4, 1),
-		part(V.cls_nblk, L.cls_nblk, 4, 1), part(V.hap_off, L.hap_off, 4, 1), part(V.item_split, L.item, 4, 1), part(V.split_row, L.split_row, 4, 1),
-		part(V.split_cls, L.split_cls, 4, 1), part(V.item_whole, L.item_whole, 4, 1), part(V.cell_row, L.cell_row, 4, 1),
-		part(V.wide_cls, L.wide_cls, 4, 1), part(V.wide_seg, L.wseg, 4, 1), part(V.wide_scan, L.wide_scan, 4, 1)})) return rc;
-	if (int rc = upload_parts(m->d_tile, {     // the tables of the pass-1 walkers and of pass 2, at the alignment of their loads
-		part(V.stream_off, L.stream_off, 8), part(V.tile_meta, L.tile_meta, 4), part(V.cls_cnt, L.cls_cnt, 4),
-		part(V.cls_cell, L.cls_cell, 4), part(V.blk_off, L.blk_off, 8), part(V.ctile, L.ctile, 32), part(V.hap, L.hap, 16),
-		part(V.ehdr, L.ehdr, 32), part(V.etile_cstart, L.etile_cstart, 4, 1), part(V.etile_blk0, L.etile_blk0, 8),
-		part(V.blk_close, L.blk_close, 4), part(V.wide_seg_off, L.wseg_off, 8, 1)})) return rc;
-	if (int rc = upload_parts(m->d_stream, {part(V.stream, L.stream, 4)})) return rc;
-	if (int rc = upload_parts(m->d_blk, {part(V.plist, L.plist, 4)})) return rc;
-	if (int rc = upload_parts(m->d_pfac, {part(V.pfac, L.pfac, 8)})) return rc;
-	if (int rc = upload_parts(m->d_phdr, {part(V.phdr, L.phdr, 4)})) return rc;
-	if (int rc = upload_parts(m->d_parow, {{L.parow.data(), L.parow.size() * 4, std::max<size_t>(L.parow.size(), 256) * 4, 16, &V.parow}})) return rc;
-	if (int rc = upload_parts(m->d_tab, {{m->tab, sizeof(m->tab), sizeof(m->tab), 8, &V.tab}})) return rc;
-	V.n_hla = L.nh; V.n_classifier = L.C; V.n_snp = L.S; V.n_cell = L.P; V.mask_rows = L.rows; V.n_tile = L.n_tile;
-	V.n_item_split = (int)L.item.size() / 4; V.n_item_whole = (int)L.item_whole.size() / 4; V.n_split = (int)L.split_cls.size();
-	V.item = V.item_whole; V.n_item = V.n_item_whole;
-	V.all_fp4 = 1; V.n_valu = 0;
-	for (int c = 0; c < L.C; c++) {
-		if (L.n_step[c] == 1 && !(L.engine[c] == HIBAG_ENGINE_FP4)) V.all_fp4 = 0;      // (classifiers of several K steps are not work items of k_total)
-		V.n_valu += L.engine[c] == HIBAG_ENGINE_VALU;
-	}
-	V.n_wide = (int)L.wide_cls.size();
-	V.n_wide_scan = (int)L.wide_scan.size();
-	V.n_wide_seg = (int)L.wseg.size() / 4;
+	const LayoutTables T = layout_tables(L, V);
+	DevBuf *const bufs[LayoutTables::N_BUF] = {&m->d_int, &m->d_tile, &m->d_stream, &m->d_blk, &m->d_pfac, &m->d_phdr, &m->d_parow};
+	for (int i = 0; i < LayoutTables::N_BUF; i++)
+		if (int rc = upload_parts(*bufs[i], T.buf[i])) return rc;
+	if (int rc = upload_parts(m->d_tab, {{"tab", m->tab, sizeof(m->tab), sizeof(m->tab), 8, 8, &V.tab}})) return rc;
+	LayoutScalars s;
+	layout_scalars(L, V, s);
+	V.item = V.item_whole;
 	if (V.n_wide > 0 && !m->side.stream) {
 		HIP_TRY(hipStreamCreateWithFlags(&m->side.stream, hipStreamNonBlocking));
 		HIP_TRY(hipEventCreateWithFlags(&m->side.fork, hipEventDisableTiming));
 		HIP_TRY(hipEventCreateWithFlags(&m->side.join, hipEventDisableTiming));
 	}
-	V.split_heavy_ns = L.split_heavy_ns; V.split_rest_ns = L.split_rest_ns;
-	V.hap_dwords = (uint32_t)L.hap.size();
-	V.estream_blocks = L.estream_blocks;
-	V.p1_base = L.p1_base;
-	V.p1_blocks = L.p1_blocks;
-	V.store_cells = L.store_mode;
 	hibag_query_slots(V.slots_total, &V.slots_accum);
-	V.plist_dwords = L.plist.size();
-	V.parow_blocks = L.parow_blocks;
-	V.p1_prebuilt = L.p1_prebuilt ? 1 : 0;
-	// A chunk waits for the chunk before it, which was dispatched a whole round earlier; in the worst case the chunks of
-	// an item run one after the other, so the wait is bounded by the item's own length.  One poll lasts ~1 us (s_sleep +
-	// an L2 round trip), a 32-slot block ~1.5 us of elapsed time at full occupancy: 16 polls per block of the longest
-	// item is an order of magnitude of slack on top of the fixed 2^19 (~0.5 s).
-	long long longest = 0;
-	for (int c = 0; c < L.C; c++) longest = std::max<long long>(longest, L.engine[c] ? L.cls_nblk[c] : L.cp[c].pairs / 8);
-	m->spin_limit = (uint32_t)std::min<long long>(0xFFFFFFF0ll, (1ll << 19) + 16 * longest);
-	m->pair_evals = L.pair_evals;
-	m->store_mode = L.store_mode;
-	m->second_pass_pairs = L.second_pass_pairs;
-	m->cell_rows = L.cell_row[L.C];
-	m->bt_rows = L.bt_rows;
-	m->mask_rows = L.rows;
-	m->stream_bytes = L.stream.size() * sizeof(uint32_t);
-	m->engine_of.assign(L.engine.begin(), L.engine.begin() + L.C);
-	m->steps_of.assign(L.n_step.begin(), L.n_step.begin() + L.C);
+	m->spin_limit = s.spin_limit;
+	m->pair_evals = s.pair_evals;
+	m->store_mode = s.store_mode;
+	m->second_pass_pairs = s.second_pass_pairs;
+	m->cell_rows = s.cell_rows;
+	m->bt_rows = s.bt_rows;
+	m->mask_rows = s.mask_rows;
+	m->stream_bytes = s.stream_bytes;
+	m->engine_of = s.engine_of;
+	m->steps_of = s.steps_of;
 	m->finalized = true;
 	return 0;
 }
 
-// The planning stages in order (any of them may reject the model, before anything is allocated), then the upload.
-static int finalize_with(hibag_hip_model *m, const FinalizeOptions &opt)
+// The planning stages in order: fills `L` from the model without a HIP call; any of them may reject the model.
+int plan_layout(const hibag_hip_model *m, const FinalizeOptions &opt, ModelLayout &L)
 {
-	if (m->finalized) return hibag_fail(HIBAG_HIP_ESTATE, "model already finalized");
-	ModelLayout L(m);
 	if (int rc = plan_classifiers(m, opt, L)) return rc;
 	plan_tiles(L);
 	plan_store(opt, L);
@@ -897,7 +937,15 @@ static int finalize_with(hibag_hip_model *m, const FinalizeOptions &opt)
 	if (int rc = plan_pair_lists(m, L)) return rc;
 	plan_factors(m, L);
 	plan_parow(opt, L);
-	if (int rc = plan_ctile(L)) return rc;
+	return plan_ctile(L);
+}
+
+// The plan (before anything is allocated), then the upload.
+static int finalize_with(hibag_hip_model *m, const FinalizeOptions &opt)
+{
+	if (m->finalized) return hibag_fail(HIBAG_HIP_ESTATE, "model already finalized");
+	ModelLayout L(m);
+	if (int rc = plan_layout(m, opt, L)) return rc;
 	return upload_layout(m, L);
 }
 
@@ -911,6 +959,19 @@ int finalize_model_stream(hibag_hip_model *m)
 }
 
 } // namespace hibag_detail
+
+// What plan_layout makes of the model, as upload_layout would hand it to the device: the arrays of layout_tables with the
+// room each is given, and the scalars of layout_scalars (hibag_hip_test_layout_*).
+struct hibag_hip_layout {
+	ModelLayout L;
+	HibagModelView V{};
+	LayoutScalars s;
+	struct Entry { std::string name; const void *data; uint64_t bytes; int elem; };
+	std::vector<Entry> entries;
+	std::vector<int64_t> ints;           // the integer scalars, one array of one element each
+	std::vector<double> dbls;
+	explicit hibag_hip_layout(const hibag_hip_model *m) : L(m) {}
+};
 
 // ===========================================================================
 // C ABI: the model
@@ -1031,6 +1092,59 @@ int hibag_hip_model_mutation_table(const hibag_hip_model *m, double *out)
 	memcpy(out, m->tab, sizeof(m->tab));
 	return 0;
 }
+
+// ---- the planned layout, for the host tests (tests/test_layout_host.py) -------------------------------------------
+
+hibag_hip_layout *hibag_hip_test_layout_plan(hibag_hip_model *m)
+{
+	if (!m) { hibag_fail(HIBAG_HIP_EINVAL, "model is NULL"); return nullptr; }
+	std::lock_guard<std::mutex> g(m->lock);
+	if (m->finalized) { hibag_fail(HIBAG_HIP_ESTATE, "model already finalized"); return nullptr; }
+	hibag_hip_layout *p = new (std::nothrow) hibag_hip_layout(m);
+	if (!p) { hibag_fail(HIBAG_HIP_ENOMEM, "out of host memory"); return nullptr; }
+	if (plan_layout(m, FinalizeOptions(), p->L)) { delete p; return nullptr; }
+	const LayoutTables T = layout_tables(p->L, p->V);
+	layout_scalars(p->L, p->V, p->s);
+	for (const auto &parts : T.buf)
+		for (const Part &q : parts) p->entries.push_back({q.name, q.src, q.bytes, (int)q.elem});
+	const ModelLayout &L = p->L;
+	const HibagModelView &V = p->V;
+	std::vector<std::pair<std::string, int64_t>> iv;
+	for (const auto &parts : T.buf)
+		for (const Part &q : parts) iv.push_back({std::string("room:") + q.name, (int64_t)q.room});
+	for (const auto &kv : std::initializer_list<std::pair<const char *, int64_t>>{
+		{"n_hla", V.n_hla}, {"n_classifier", V.n_classifier}, {"n_snp", V.n_snp}, {"n_cell", V.n_cell}, {"mask_rows", V.mask_rows},
+		{"n_tile", V.n_tile}, {"n_item_split", V.n_item_split}, {"n_item_whole", V.n_item_whole}, {"n_split", V.n_split},
+		{"all_fp4", V.all_fp4}, {"n_valu", V.n_valu}, {"n_wide", V.n_wide}, {"n_wide_scan", V.n_wide_scan}, {"n_wide_seg", V.n_wide_seg},
+		{"hap_dwords", V.hap_dwords}, {"estream_blocks", (int64_t)V.estream_blocks}, {"p1_base", (int64_t)V.p1_base},
+		{"p1_blocks", V.p1_blocks}, {"store_cells", V.store_cells}, {"plist_dwords", (int64_t)V.plist_dwords},
+		{"parow_blocks", (int64_t)V.parow_blocks}, {"p1_prebuilt", V.p1_prebuilt}, {"spin_limit", p->s.spin_limit},
+		{"pair_evals", p->s.pair_evals}, {"second_pass_pairs", p->s.second_pass_pairs}, {"cell_rows", p->s.cell_rows},
+		{"bt_rows", p->s.bt_rows}, {"bt_rows_alloc", hibag_bt_rows_alloc(p->s.bt_rows)}, {"stream_bytes", (int64_t)p->s.stream_bytes},
+		{"tile", HIBAG_TILE}, {"stored_per_visit", HIBAG_STORED_PER_VISIT}, {"use_mfma", m->use_mfma}, {"use_fp4", m->use_fp4}})
+		iv.push_back({kv.first, kv.second});
+	p->ints.reserve(iv.size());
+	for (const auto &kv : iv) { p->ints.push_back(kv.second); p->entries.push_back({kv.first, &p->ints.back(), 8, 8}); }
+	p->dbls = {L.split_heavy_ns, L.split_rest_ns};
+	p->entries.push_back({"split_heavy_ns", &p->dbls[0], 8, 8});
+	p->entries.push_back({"split_rest_ns", &p->dbls[1], 8, 8});
+	return p;
+}
+
+int hibag_hip_test_layout_count(const hibag_hip_layout *p) { return p ? (int)p->entries.size() : 0; }
+
+int hibag_hip_test_layout_get(const hibag_hip_layout *p, int index, const char **name, const void **data, uint64_t *bytes, int *elem_size)
+{
+	if (!p || index < 0 || index >= (int)p->entries.size()) return hibag_fail(HIBAG_HIP_EINVAL, "no such layout entry");
+	const auto &e = p->entries[index];
+	if (name) *name = e.name.c_str();
+	if (data) *data = e.data;
+	if (bytes) *bytes = e.bytes;
+	if (elem_size) *elem_size = e.elem;
+	return 0;
+}
+
+void hibag_hip_test_layout_free(hibag_hip_layout *p) { delete p; }
 
 // ---- several devices ------------------------------------------------------------------------------------
 

@@ -39,7 +39,7 @@ int make_batch(hibag_hip_model *m, int n_samp, bool need_best, HibagBatchView &B
 	if (int rc = m->ws_part.reserve((size_t)(m->view.n_cell + 3) * n_pad * sizeof(double))) return rc;
 	if (int rc = m->ws_codes.reserve((size_t)std::max(m->n_snp, 1) * n_pad)) return rc;
 	// (two rows more than the model has: k_accum reads rows bt and bt + 1 of every block header it passes, whatever the block holds)
-	if (int rc = m->ws_bt.reserve((size_t)(std::max(m->bt_rows, 1) + 2) * n_pad * sizeof(uint4))) return rc;
+	if (int rc = m->ws_bt.reserve((size_t)hibag_bt_rows_alloc(m->bt_rows) * n_pad * sizeof(uint4))) return rc;
 	if (int rc = m->ws_bias.reserve(2 * C * n_pad * sizeof(int))) return rc;
 	if (int rc = m->ws_cells.reserve((size_t)std::max(m->cell_rows, 1) * n_pad * sizeof(double))) return rc;
 	if (need_best) {
@@ -80,7 +80,7 @@ int make_batch(hibag_hip_model *m, int n_samp, bool need_best, HibagBatchView &B
 	B.cw = m->ws_cw.as<double>(); B.tot = m->ws_tot.as<double>(); B.inv = m->ws_inv.as<double>(); B.winv = m->ws_winv.as<double>();
 	B.part = m->ws_part.as<double>();
 	B.bt = m->ws_bt.as<uint4>(); B.bias = m->ws_bias.as<int>();
-	B.bt_rows = std::max(m->bt_rows, 1) + 2;
+	B.bt_rows = hibag_bt_rows_alloc(m->bt_rows);
 	B.cells = m->ws_cells.as<double>();
 	B.vrec = need_best ? m->ws_vrec.as<uint4>() : nullptr;
 	return 0;

@@ -34,7 +34,8 @@ extern "C" {
                                        + hibag_hip_test_build_eval_batch (a test entry): likewise;
                                        + hibag_hip_test_em_fit, hibag_hip_test_em_layout (test entries), hibag_hip_trainer_em_counts: likewise;
                                        + the association entries (hibag_hip_assoc_*): likewise;
-                                       + the out-of-bag knock-out (hibag_hip_oob_knock, hibag_hip_oob_knock_variants): likewise */
+                                       + the out-of-bag knock-out (hibag_hip_oob_knock, hibag_hip_oob_knock_variants): likewise;
+                                       + hibag_hip_test_layout_plan, _count, _get, _free (test entries): likewise */
 
 /* error codes */
 #define HIBAG_HIP_OK          0
@@ -1039,6 +1040,20 @@ int hibag_hip_test_em_fit(int n_ib, int n_pair, int n_hap, int n_samp_total, con
  * arithmetic, no device access: 0 = the step does not fit the kernel (the host fits it), 1 = "staged" (every haplotype's
  * pair values have a contiguous copy the M step reads in order), 2 = "gather" (the M step reads them through offsets). */
 int hibag_hip_test_em_layout(int n_ib, int n_pair, int n_hap);
+
+/* Test entries: the layout hibag_hip_model_finalize would upload for the model as it stands -- the planning stages run on
+ * the host, with the same environment overrides (HIBAG_PASS2, HIBAG_STORE_PAIRS, HIBAG_PREBUILT_MB), no device is touched
+ * and the model stays unfinalized and usable.  The plan is a list of named entries: every array of the layout, the bytes
+ * reserved for each ("room:<array>"), and its scalars as arrays of one int64 or double; it does not depend on the model
+ * once made.  NULL (a plan the stages reject: their error; a finalized model: HIBAG_HIP_ESTATE) or a plan the caller frees.
+ * tests/layout_reference.py interprets it.  (Added within ABI version 7.) */
+typedef struct hibag_hip_layout hibag_hip_layout;
+hibag_hip_layout *hibag_hip_test_layout_plan(hibag_hip_model *m);
+int hibag_hip_test_layout_count(const hibag_hip_layout *plan);
+/* entry `index` in [0, count): its name, first byte, size in bytes and bytes per element (each out pointer optional) */
+int hibag_hip_test_layout_get(const hibag_hip_layout *plan, int index, const char **name, const void **data, uint64_t *bytes,
+	int *elem_size);
+void hibag_hip_test_layout_free(hibag_hip_layout *plan);
 
 #ifdef __cplusplus
 }
