@@ -35,9 +35,10 @@ from .given import (HlaAlleleConstraint, HlaGivenCalls, hlaConstraintFromAllele,
 from .family import (HlaFamilyCalls, HlaMendelCheck, HlaPedigree, hlaMendelCheck, hlaModelAllelePrior,  # noqa: F401
                      hlaPedigreeFromFam, hlaPredictFamily)
 from .assoc import HlaAssocResult, hlaAssocTest  # noqa: F401
+from .assocglm import HlaAssocGlmResult, hlaAssocGlm  # noqa: F401
 from ._lib import HibagHipError  # noqa: F401
 
-__all__ = ["hlaSNPImportance", "HlaSNPImportance", "engine_kind", "engine_nkb", "engine_steps", "NA_INTEGER", "Classifier", "HlaAttrBagObj", "HlaSNPGeno", "load_geno", "load_model", "model_to_robj", "save_model",
+__all__ = ["hlaAssocGlm", "HlaAssocGlmResult", "hlaSNPImportance", "HlaSNPImportance", "engine_kind", "engine_nkb", "engine_steps", "NA_INTEGER", "Classifier", "HlaAttrBagObj", "HlaSNPGeno", "load_geno", "load_model", "model_to_robj", "save_model",
            "HlaAlleleClass", "HlaAttrBagClass", "hlaClose", "hlaModelFromObj", "hlaModelToObj",
            "hlaPredict", "hlaSetKernelTarget", "hlaGenoSwitchStrand", "hlaSNPID", "HibagHipError",
            "HlaBEDGeno", "hlaBED2Geno", "hlaLociInfo", "RRandom", "hlaAllele", "hlaAttrBagging", "hlaConcurrentAttrBagging", "hlaParallelAttrBagging", "hlaUniqueAllele", "hlaAlleleDigit", "hlaPredMerge", "hlaPredictMerge", "hlaAlleleSubset", "hlaCompareAllele", "hlaFlankingSNP", "hlaGenoSubset",

@@ -61,6 +61,7 @@ EXPORTS = [
     "hibag_hip_predict_family_snp_major",
     "hibag_hip_assoc_new", "hibag_hip_assoc_free", "hibag_hip_assoc_n_tests", "hibag_hip_assoc_observed",
     "hibag_hip_assoc_permute", "hibag_hip_assoc_labels",
+    "hibag_hip_assoc_n_kept", "hibag_hip_assoc_feature_rows", "hibag_hip_assoc_glm",
     "hibag_hip_oob_knock_variants", "hibag_hip_oob_knock",
     "hibag_hip_test_layout_plan", "hibag_hip_test_layout_count", "hibag_hip_test_layout_get", "hibag_hip_test_layout_free",
 ]
@@ -175,6 +176,10 @@ def lib() -> C.CDLL:
         L.hibag_hip_assoc_observed.argtypes = [vp, vp, vp]
         L.hibag_hip_assoc_permute.argtypes = [vp, C.c_uint64, C.c_uint64, i64, vp, vp]
         L.hibag_hip_assoc_labels.argtypes = [vp, C.c_uint64, C.c_uint64, i32, vp]
+    if hasattr(L, "hibag_hip_assoc_glm"):
+        L.hibag_hip_assoc_n_kept.argtypes = [vp]
+        L.hibag_hip_assoc_feature_rows.argtypes = [vp, i32, i32, vp]
+        L.hibag_hip_assoc_glm.argtypes = [vp, vp, i32, vp, i32, C.c_double, vp, vp, vp, vp, vp]
     if hasattr(L, "hibag_hip_cohort_new"):
         # (an older build selected with HIBAG_HIP_LIBRARY, e.g. the parent commit's for a baseline timing, lacks the cohort
         # entries: everything else still binds, and a call that needs them fails with AttributeError)

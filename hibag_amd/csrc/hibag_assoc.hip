@@ -6,9 +6,14 @@
 // device the creating thread had selected, and runs the observed labelling through the same Gram and statistic kernels
 // as the permutations.  hibag_hip_assoc_permute then works in panels of permutations: label rows (k_assoc_permute), one
 // Gram features x labels, one pass over it (k_assoc_stat).  A handle has one stream and is used by one host thread at a time.
+//
+// hibag_hip_assoc_glm (hlaAssocGlm; kernels: hibag_k_glm.h) fits one logistic regression per test on
+// the same feature rows, with the kept samples' labels that the handle keeps in `y` (the `labels` panel is overwritten by
+// every permutation call).
 
 #include "hibag_internal.h"
 #include "hibag_k_assoc.h"
+#include "hibag_k_glm.h"
 
 using hibag_detail::DevBuf;
 
@@ -19,6 +24,9 @@ struct hibag_hip_assoc {
 	hipStream_t st = nullptr;
 	DevBuf feat, row_sum, stat_obs;              // int8 [rows][kp], int32 [rows], double [n_test]
 	DevBuf labels, gram, max_stat, count;        // per-call panel: int8 [pp][kp], int32 [rows][pp]; double [n_perm]; uint64 [n_test]
+	DevBuf y;                                    // int8 [kp]: the kept samples' labels, zero padding (hibag_hip_assoc_glm)
+	DevBuf glm_in, glm_img, glm_wt, glm_fits, glm_out; // hibag_hip_assoc_glm: covariates and weights as given, the operand image, the padded weights, GlmFit [n_fit], the outputs
+	std::vector<int32_t> h_row_sum;              // the feature rows' sums [rows]
 	std::vector<double> h_stat;                  // the observed statistics and tables, made once by hibag_hip_assoc_new
 	std::vector<int64_t> h_table;
 
@@ -26,7 +34,7 @@ struct hibag_hip_assoc {
 	{
 		(void)hipSetDevice(device);
 		if (st) (void)hipStreamSynchronize(st);
-		for (DevBuf *b : {&feat, &row_sum, &stat_obs, &labels, &gram, &max_stat, &count}) b->release();
+		for (DevBuf *b : {&feat, &row_sum, &stat_obs, &labels, &gram, &max_stat, &count, &y, &glm_in, &glm_img, &glm_wt, &glm_fits, &glm_out}) b->release();
 		if (st) (void)hipStreamDestroy(st);
 	}
 };
@@ -81,7 +89,7 @@ int build(hibag_hip_assoc *h, const std::vector<int32_t> &a1, const std::vector<
 	DevBuf d_a, d_g, d_t;                        // alleles [2][n], the partitions, part / level of every test: needed by k_assoc_features only
 	struct Release { DevBuf &a, &b, &c; ~Release() { a.release(); b.release(); c.release(); } } rel{d_a, d_g, d_t};
 	if (h->feat.reserve((size_t)rows * kp) || h->row_sum.reserve(sizeof(int32_t) * rows) || h->stat_obs.reserve(sizeof(double) * T) ||
-		h->labels.reserve((size_t)kp) || h->gram.reserve(sizeof(int32_t) * rows) ||
+		h->labels.reserve((size_t)kp) || h->y.reserve((size_t)kp) || h->gram.reserve(sizeof(int32_t) * rows) ||
 		d_a.reserve(sizeof(int32_t) * 2 * std::max(n, 1)) || d_g.reserve(sizeof(int32_t) * group_of.size()) ||
 		d_t.reserve(sizeof(int32_t) * 2 * T))
 		return HIBAG_HIP_ENOMEM;
@@ -102,6 +110,7 @@ int build(hibag_hip_assoc *h, const std::vector<int32_t> &a1, const std::vector<
 	std::vector<int8_t> row((size_t)kp, 0);
 	std::copy(y.begin(), y.end(), row.begin());
 	HIP_TRY(hipMemcpyAsync(h->labels.p, row.data(), (size_t)kp, hipMemcpyHostToDevice, h->st));
+	HIP_TRY(hipMemcpyAsync(h->y.p, row.data(), (size_t)kp, hipMemcpyHostToDevice, h->st));
 	launch_gram(h, h->labels.as<int8_t>(), 1, h->gram.as<int32_t>());
 	hipLaunchKernelGGL(k_assoc_stat, dim3(1), dim3(64), 0, h->st, h->gram.as<int32_t>(), (size_t)1, 1, h->D, h->row_sum.as<int32_t>(),
 		h->stat_obs.as<double>(), (double *)nullptr, (const double *)nullptr, (unsigned long long *)nullptr);
@@ -112,6 +121,7 @@ int build(hibag_hip_assoc *h, const std::vector<int32_t> &a1, const std::vector<
 	HIP_TRY(hipMemcpyAsync(r.data(), h->row_sum.p, sizeof(int32_t) * rows, hipMemcpyDeviceToHost, h->st));
 	HIP_TRY(hipMemcpyAsync(h->h_stat.data(), h->stat_obs.p, sizeof(double) * T, hipMemcpyDeviceToHost, h->st));
 	HIP_TRY(hipStreamSynchronize(h->st));
+	h->h_row_sum = r;
 
 	// the tables, rows (none, carrier) or (none, het, hom) x columns (control, case), from the exact sums
 	h->h_table.assign((size_t)T * 6, 0);
@@ -278,6 +288,87 @@ int hibag_hip_assoc_labels(hibag_hip_assoc *h, uint64_t seed, uint64_t perm0, in
 			hipMemcpyDeviceToHost, h->st));
 		HIP_TRY(hipStreamSynchronize(h->st));
 	}
+	return 0;
+}
+
+int hibag_hip_assoc_n_kept(const hibag_hip_assoc *h) { return h ? h->D.n : hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_n_kept: null handle"); }
+
+int hibag_hip_assoc_feature_rows(hibag_hip_assoc *h, int row0, int n_rows, int8_t *out)
+{
+	if (!h || n_rows < 0 || (n_rows > 0 && !out)) return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_feature_rows: null argument or n_rows < 0");
+	if (row0 < 0 || row0 > h->rows || n_rows > h->rows - row0)
+		return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_feature_rows: rows %d .. %d + %d are outside the handle's %d", row0, row0, n_rows, h->rows);
+	if (n_rows == 0 || h->D.n == 0) return 0;
+	HIP_TRY(hipSetDevice(h->device));
+	HIP_TRY(hipMemcpy2DAsync(out, (size_t)h->D.n, h->feat.as<int8_t>() + (size_t)row0 * h->kp, (size_t)h->kp, (size_t)h->D.n, (size_t)n_rows,
+		hipMemcpyDeviceToHost, h->st));
+	HIP_TRY(hipStreamSynchronize(h->st));
+	return 0;
+}
+
+int hibag_hip_assoc_glm(hibag_hip_assoc *h, const double *covar, int n_covar, const double *weight, int maxit, double epsilon,
+	double *coef, double *se, double *deviance, int32_t *iterations, int32_t *flags)
+{
+	if (!h || !coef || !se || !deviance || !iterations || !flags) return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_glm: null argument");
+	if (n_covar < 0 || n_covar > HIBAG_HIP_GLM_MAX_COVAR || (n_covar > 0 && !covar))
+		return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_glm: %d covariates; 0 .. %d, with covar", n_covar, HIBAG_HIP_GLM_MAX_COVAR);
+	if (maxit < 1) return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_glm: maxit = %d; at least 1", maxit);
+	if (!(epsilon > 0)) return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_glm: epsilon must be > 0");
+	static_assert(GLM_COV0 + HIBAG_HIP_GLM_MAX_COVAR == GLM_SLOTS - 1, "intercept, two h slots, the covariates, then z");
+	const int n = h->D.n, T = h->D.n_test, kp = h->kp, q = n_covar, n_fit = T + 1;
+	for (size_t i = 0; i < (size_t)q * n; i++)
+		if (!std::isfinite(covar[i]))
+			return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_glm: covariate %zu of kept sample %zu is not finite", i / n, i % n);
+	if (weight)
+		for (int i = 0; i < n; i++)
+			if (!std::isfinite(weight[i]) || weight[i] < 0)
+				return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_glm: weight[%d] = %g; weights are finite and >= 0", i, weight[i]);
+
+	// the fits: which feature rows stand behind slots 1 and 2, decided from the integer row sums
+	std::vector<GlmFit> fits((size_t)n_fit);
+	const std::vector<int32_t> &r = h->h_row_sum;
+	for (int t = 0; t < T; t++) {
+		GlmFit &f = fits[(size_t)t];
+		if (h->D.model == ASSOC_GENOTYPE) {
+			const int64_t het = r[2 * t], hom = r[2 * t + 1];
+			f.row_a = het > 0 ? 2 * t : -1;
+			f.row_b = hom > 0 ? 2 * t + 1 : -1;
+			if ((het == 0 && hom == 0) || het + hom == n) f.row_a = -2;
+		} else {
+			const int64_t top = (int64_t)(h->D.model == ASSOC_ADDITIVE ? 2 : 1) * n;
+			f.row_a = (r[t] == 0 || r[t] == top) ? -2 : t;
+			f.row_b = -1;
+		}
+	}
+	fits[(size_t)T] = GlmFit{-1, -1};
+
+	HIP_TRY(hipSetDevice(h->device));
+	const size_t in_doubles = (size_t)q * n + (weight ? (size_t)n : 0);
+	const size_t out_bytes = (size_t)n_fit * (2 * GLM_SLOTS * sizeof(double) + sizeof(double) + 2 * sizeof(int32_t));
+	if (h->glm_in.reserve(sizeof(double) * std::max<size_t>(in_doubles, 1)) || h->glm_img.reserve(sizeof(double) * GLM_SLOTS * (size_t)kp) ||
+		h->glm_wt.reserve(sizeof(double) * (size_t)kp) || h->glm_fits.reserve(sizeof(GlmFit) * (size_t)n_fit) || h->glm_out.reserve(out_bytes))
+		return HIBAG_HIP_ENOMEM;
+	double *d_cov = h->glm_in.as<double>(), *d_w = weight ? d_cov + (size_t)q * n : nullptr;
+	if (q) HIP_TRY(hipMemcpyAsync(d_cov, covar, sizeof(double) * (size_t)q * n, hipMemcpyHostToDevice, h->st));
+	if (weight) HIP_TRY(hipMemcpyAsync(d_w, weight, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, h->st));
+	HIP_TRY(hipMemcpyAsync(h->glm_fits.p, fits.data(), sizeof(GlmFit) * (size_t)n_fit, hipMemcpyHostToDevice, h->st));
+	hipLaunchKernelGGL(k_glm_image, dim3((unsigned)(((size_t)kp * GLM_SLOTS + 255) / 256)), dim3(256), 0, h->st, d_cov, d_w, n, q, kp,
+		h->glm_img.as<double>(), h->glm_wt.as<double>());
+	HIP_TRY(hipGetLastError());
+	double *d_coef = h->glm_out.as<double>(), *d_se = d_coef + (size_t)n_fit * GLM_SLOTS, *d_dev = d_se + (size_t)n_fit * GLM_SLOTS;
+	int32_t *d_it = (int32_t *)(d_dev + n_fit), *d_fl = d_it + n_fit;
+	hipLaunchKernelGGL(k_glm_fit, dim3(n_fit), dim3(GLM_WAVES * 64), 0, h->st, h->glm_img.as<double>(), h->glm_wt.as<double>(),
+		h->y.as<int8_t>(), h->feat.as<int8_t>(), h->glm_fits.as<GlmFit>(), n, kp, q, maxit, epsilon, d_coef, d_se, d_dev, d_it, d_fl);
+	if (hipGetLastError() != hipSuccess) {
+		(void)hipStreamSynchronize(h->st);
+		return hibag_fail(HIBAG_HIP_ENODEV, "hibag_hip_assoc_glm: a kernel launch failed");
+	}
+	HIP_TRY(hipMemcpyAsync(coef, d_coef, sizeof(double) * (size_t)n_fit * GLM_SLOTS, hipMemcpyDeviceToHost, h->st));
+	HIP_TRY(hipMemcpyAsync(se, d_se, sizeof(double) * (size_t)n_fit * GLM_SLOTS, hipMemcpyDeviceToHost, h->st));
+	HIP_TRY(hipMemcpyAsync(deviance, d_dev, sizeof(double) * (size_t)n_fit, hipMemcpyDeviceToHost, h->st));
+	HIP_TRY(hipMemcpyAsync(iterations, d_it, sizeof(int32_t) * (size_t)n_fit, hipMemcpyDeviceToHost, h->st));
+	HIP_TRY(hipMemcpyAsync(flags, d_fl, sizeof(int32_t) * (size_t)n_fit, hipMemcpyDeviceToHost, h->st));
+	HIP_TRY(hipStreamSynchronize(h->st));
 	return 0;
 }
 

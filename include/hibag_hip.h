@@ -35,7 +35,8 @@ extern "C" {
                                        + hibag_hip_test_em_fit, hibag_hip_test_em_layout (test entries), hibag_hip_trainer_em_counts: likewise;
                                        + the association entries (hibag_hip_assoc_*): likewise;
                                        + the out-of-bag knock-out (hibag_hip_oob_knock, hibag_hip_oob_knock_variants): likewise;
-                                       + hibag_hip_test_layout_plan, _count, _get, _free (test entries): likewise */
+                                       + hibag_hip_test_layout_plan, _count, _get, _free (test entries): likewise;
+                                       + the regression entries (hibag_hip_assoc_glm, _n_kept, _feature_rows): likewise */
 
 /* error codes */
 #define HIBAG_HIP_OK          0
@@ -313,6 +314,36 @@ int hibag_hip_assoc_permute(hibag_hip_assoc *h, uint64_t seed, uint64_t perm0, i
 /* The label rows of permutations perm0 .. perm0 + n - 1 themselves: out int8 [n][kept samples], 0 / 1 (for tests of the
  * generator). */
 int hibag_hip_assoc_labels(hibag_hip_assoc *h, uint64_t seed, uint64_t perm0, int n, int8_t *out);
+
+/* The samples the handle kept (two known alleles), and its feature rows themselves: out int8 [n_rows][n_kept], rows
+ * row0 .. row0 + n_rows - 1 without their padding.  Row t is test t's 0 / 1 / 2 column; HIBAG_HIP_ASSOC_GENOTYPE has the rows
+ * 2 t (het) and 2 t + 1 (hom).  EINVAL for rows outside the handle's. */
+int hibag_hip_assoc_n_kept(const hibag_hip_assoc *h);
+int hibag_hip_assoc_feature_rows(hibag_hip_assoc *h, int row0, int n_rows, int8_t *out);
+
+/* ---- covariate-adjusted logistic regression per test: hlaAssocGlm ------------
+ * glm(y ~ h + covariates, family = binomial) for every test of the handle (R/Association.R:315-436) and for the base model
+ * y ~ covariates: R's glm.fit restated -- iteratively reweighted least squares from R's start value, convergence on the
+ * relative change of the deviance, no step halving -- with the standard errors of summary.glm (dispersion 1).  The unit is
+ * a sample for every model; `additive` regresses on the dosage 0 / 1 / 2.  The definitions are DESIGN.md section 23.  A
+ * fit's numbers depend on the kept samples, its own columns and the arguments below, not on the other tests of the handle.
+ *   covar       float64 [n_covar][n_kept], one row per covariate (NULL with n_covar = 0); 0 <= n_covar <= HIBAG_HIP_GLM_MAX_COVAR
+ *   weight      float64 [n_kept] prior weights, finite and >= 0, or NULL for 1
+ *   maxit       >= 1 iterations at most (R: 25); epsilon > 0 (R: 1e-8)
+ * Outputs for n_tests + 1 fits, fit n_tests the base model:
+ *   coef, se    float64 [n_tests + 1][16] by slot: 0 the intercept, 1 h (het for GENOTYPE), 2 hom (GENOTYPE only),
+ *               3 .. 2 + n_covar the covariates; every other slot NaN
+ *   deviance    float64, iterations int32, flags int32 (HIBAG_HIP_GLM_*) [n_tests + 1]
+ * A test whose column is constant over the kept samples is not fitted (RANK, NaN).  GENOTYPE: a dummy that nobody carries
+ * is left out of its fit (its slot NaN); both empty, or nobody without the allele: RANK.
+ * EINVAL for a null handle or output, n_covar outside its range, maxit < 1, epsilon not > 0, a non-finite covariate, a
+ * non-finite or negative weight. */
+#define HIBAG_HIP_GLM_MAX_COVAR 12
+#define HIBAG_HIP_GLM_MAXIT     1   /* not converged within maxit: the last iteration's values are reported */
+#define HIBAG_HIP_GLM_RANK      2   /* rank-deficient (a pivot <= 1e-11 A_jj) or not fitted: the values are NaN */
+#define HIBAG_HIP_GLM_BOUNDARY  4   /* a fitted probability below 10 eps or above 1 - 10 eps (R's warning)  */
+int hibag_hip_assoc_glm(hibag_hip_assoc *h, const double *covar, int n_covar, const double *weight, int maxit, double epsilon,
+	double *coef, double *se, double *deviance, int32_t *iterations, int32_t *flags);
 
 /* ---- several models of one locus, merged: hlaPredMerge on the device ----------
  * hlaPredMerge(hlaPredict(m1, type = "response+prob"), hlaPredict(m2, ...), ...) (R/HIBAG.R:825-1023 around HIBAG_SumList,
