@@ -64,11 +64,22 @@ EXPORTS = [
     "hibag_hip_assoc_n_kept", "hibag_hip_assoc_feature_rows", "hibag_hip_assoc_glm",
     "hibag_hip_oob_knock_variants", "hibag_hip_oob_knock",
     "hibag_hip_test_layout_plan", "hibag_hip_test_layout_count", "hibag_hip_test_layout_get", "hibag_hip_test_layout_free",
+    "hibag_hip_test_set_chunking", "hibag_hip_test_last_launch", "hibag_hip_test_plan_total", "hibag_hip_test_plan_accum",
 ]
 TOPK_MAX = 16      # HIBAG_HIP_TOPK_MAX of include/hibag_hip.h
 DRAW_MAX = 64      # HIBAG_HIP_DRAW_MAX
 GROUPS_MAX_PART = 512        # HIBAG_HIP_GROUPS_MAX_PART
 GROUPS_MAX_LEVELS = 4096     # HIBAG_HIP_GROUPS_MAX_LEVELS
+
+
+class LaunchInfo(C.Structure):
+    """``hibag_hip_launch_info`` of include/hibag_hip.h: what passes 1 and 2 launched, or would launch."""
+    _fields_ = [(name, C.c_int32) for name in (
+        "p1_launches", "p1_kernel", "p1_n", "p1_slots", "p1_k", "p1_n_whole", "p1_rest", "p1_stride", "p1_grid", "p1_many",
+        "p1_walk", "p1_store", "p1_vote", "p2_launches", "p2_kernel", "p2_nx", "p2_sx", "p2_k", "p2_n_whole", "p2_grid")]
+
+    def as_dict(self) -> dict:
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
 
 
 class HibagHipError(RuntimeError):
@@ -286,6 +297,11 @@ def lib() -> C.CDLL:
         L.hibag_hip_test_layout_get.argtypes = [vp, i32, C.POINTER(C.c_char_p), C.POINTER(vp), C.POINTER(C.c_uint64), C.POINTER(i32)]
         L.hibag_hip_test_layout_free.argtypes = [vp]
         L.hibag_hip_test_layout_free.restype = None
+    if hasattr(L, "hibag_hip_test_set_chunking"):         # (likewise)
+        L.hibag_hip_test_set_chunking.argtypes = [vp, i32, i32, i32]
+        L.hibag_hip_test_last_launch.argtypes = [vp, C.POINTER(LaunchInfo)]
+        L.hibag_hip_test_plan_total.argtypes = [i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(LaunchInfo)]
+        L.hibag_hip_test_plan_accum.argtypes = [i32, i32, i32, C.POINTER(LaunchInfo)]
     if hasattr(L, "hibag_hip_test_read_diag"):
         L.hibag_hip_test_read_diag.argtypes = [vp, vp, i32]
         L.hibag_hip_plugin_degraded_calls.restype = i64

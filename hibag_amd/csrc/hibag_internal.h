@@ -215,7 +215,15 @@ struct hibag_hip_model {
 	int64_t fault_count = 0;
 	bool no_chunks = false;
 	int drop_next = 0;                     // fault injection (hibag_hip_test_inject_handover_fault): pass whose first hand-over the next batch drops
-	uint32_t spin_limit = 1u << 19;        // polls a waiting workgroup makes before it gives up (set at finalize from the longest item)
+	// The chunking hook of the tests (hibag_hip_test_set_chunking): the resident-workgroup figures as the device reported them
+	// (view.slots_* hold min(queried, asked) while the hook is set), what the hook asked for (0 = nothing), and what the most
+	// recent passes 1 and 2 of run_core launched (hibag_hip_test_last_launch)
+	int slots_queried[5] = {0, 0, 0, 0, 0};  // slots_total[0..3], slots_accum
+	int test_slots[2] = {0, 0}, test_tail_k = 0;
+	HibagLaunchTotal last_total;
+	HibagLaunchAccum last_accum;
+	int n_launch_total = 0, n_launch_accum = 0;
+	uint32_t spin_limit = 1u << 19;       // polls a waiting workgroup makes before it gives up (set at finalize from the longest item)
 	// The workspace is one per model: calls on different streams are chained on the device through this event, each
 	// waits for the one enqueued before it.
 	hipEvent_t ws_done = nullptr;

@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "hibag_device.h"
+#include "hibag_plan.h"
 
 // d_col / d_flip (optional): the cohort's own matrix with `row_len` SNPs per sample, gathered and flipped on the device
 void hibag_launch_pack(const HibagModelView &M, const HibagBatchView &B, const int32_t *d_geno, int row_len,
@@ -29,11 +30,12 @@ void hibag_launch_cohort_counts(const uint8_t *d_rows, size_t stride, int n_snp,
 struct HibagSideStream { hipStream_t stream = nullptr; hipEvent_t fork = nullptr, join = nullptr; };
 // vote: the call is a majority vote (vote_method = 2) -- pass 1 logs the records of the cell sums (HibagBatchView::vrec) for
 // hibag_launch_vote, stores no cell sums for a second pass and cuts no work items
-void hibag_launch_total(const HibagModelView &M, const HibagBatchView &B, hipStream_t st, const HibagSideStream &side, bool vote = false);
+// (returns what it launched: the plan of hibag_plan.h and the build of k_total -- for hibag_hip_test_last_launch)
+HibagLaunchTotal hibag_launch_total(const HibagModelView &M, const HibagBatchView &B, hipStream_t st, const HibagSideStream &side, bool vote = false);
 // resident workgroups of k_total<STORE, occupancy> -- [0] <false, 5>, [1] <false, 6>, [2] <true, 5>, [3] <true, 6> -- and of
 // k_accum on the current device (0 = unknown)
 void hibag_query_slots(int total[4], int *accum);
-void hibag_launch_accum(const HibagModelView &M, const HibagBatchView &B, hipStream_t st);
+HibagLaunchAccum hibag_launch_accum(const HibagModelView &M, const HibagBatchView &B, hipStream_t st);
 void hibag_launch_vote(const HibagModelView &M, const HibagBatchView &B, int *d_best_cell, hipStream_t st);
 void hibag_launch_scalars(const HibagModelView &M, const HibagBatchView &B, const int *d_best_cell, hipStream_t st);
 void hibag_launch_finish(const HibagModelView &M, const HibagBatchView &B, double *d_part,

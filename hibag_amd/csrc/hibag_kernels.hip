@@ -190,9 +190,10 @@ void hibag_query_slots(int total[4], int *accum)
 	*accum = resident_blocks(k_accum, ACCUM_WAVES * HIBAG_WAVE);
 }
 
-void hibag_launch_total(const HibagModelView &M, const HibagBatchView &B, hipStream_t st, const HibagSideStream &side, bool vote)
+HibagLaunchTotal hibag_launch_total(const HibagModelView &M, const HibagBatchView &B, hipStream_t st, const HibagSideStream &side, bool vote)
 {
-	if (M.n_classifier == 0) return;
+	HibagLaunchTotal R;
+	if (M.n_classifier == 0) return R;
 	const bool wide = M.n_wide > 0;
 	if (wide) {
 		// the classifiers of several K steps: their own kernel, beside k_total (more registers than k_total's hot loop may have)
@@ -213,7 +214,7 @@ void hibag_launch_total(const HibagModelView &M, const HibagBatchView &B, hipStr
 	}
 	if (M.n_item_whole == 0) {                        // (every classifier is one of those)
 		if (wide && side.stream) (void)hipStreamWaitEvent(st, side.join, 0);
-		return;
+		return R;
 	}
 	const unsigned gx = (unsigned)((B.n_pad / HIBAG_WAVE + BLOCK_WAVES - 1) / BLOCK_WAVES);
 	// A classifier far heavier than the rest (VALU engine, > 112 SNPs) is only worth cutting up when its
@@ -225,27 +226,15 @@ void hibag_launch_total(const HibagModelView &M, const HibagBatchView &B, hipStr
 	V.item = split ? M.item_split : M.item_whole;
 	V.n_item = split ? M.n_item_split : M.n_item_whole;
 	if (!split) V.n_split = 0;
-	// more items than resident workgroups: the last, incomplete round and the full round before it go in K chunks each
-	const unsigned n = gx * (unsigned)V.n_item;
-	// two rounds of the denser build's resident workgroups or more: six workgroups per CU, otherwise five (above)
+	// which items go whole, which in chunks, and the build: hibag_plan_total (hibag_plan.h)
 	const int sbase = (M.store_cells && !vote) ? 2 : 0;       // (the vote's build stores no cell sums: the occupancy figures of the non-storing one)
-	const int slots_many = M.slots_total[sbase + 1];
-	// (the denser build holds the one-step FP4 loop only: models with other work items always take the general one)
-	const bool many = M.all_fp4 && !split && slots_many > 0 && n >= 2u * (unsigned)slots_many;
-	const int slots = M.slots_total[sbase + (many ? 1 : 0)];
-	unsigned n_whole = n, rest = 0, stride = 8, K = 1;
-	const int k_pass1 = tail_chunks(B.tail_k, M.p1_blocks / std::max(M.n_classifier, 1));
-	// (the majority vote's record log is not handed over between chunks: its items stay whole)
-	if (!vote && k_pass1 > 1 && slots > 0 && n > (unsigned)slots) {
-		K = (unsigned)k_pass1;
-		rest = n % (unsigned)slots + (unsigned)slots;
-		n_whole = n - rest;
-		stride = (rest + 7) / 8 * 8;
-	}
-	const dim3 grid(n_whole + (rest ? K * stride : 0));
+	const HibagPlanTotal P = hibag_plan_total(gx, (unsigned)V.n_item, M.slots_total[sbase], M.slots_total[sbase + 1],
+		tail_chunks(B.tail_k, M.p1_blocks / std::max(M.n_classifier, 1)), vote, M.all_fp4 != 0, split);
+	const bool many = P.many != 0;
+	const dim3 grid(P.grid);
 	// the build: storing (models whose pass 2 reads cell sums back) / plain / voting (no second pass: nothing stored, records
 	// logged) x the walk -- every engine at five workgroups per CU, or one of the two FP4-only builds at six
-#define LAUNCH_TOTAL(STORE, OCC, WALK, VOTE) hipLaunchKernelGGL((k_total<STORE, OCC, WALK, VOTE>), grid, dim3(BLOCK_THREADS), 0, st, V, B, (int)gx, (int)n_whole, (int)rest, (int)stride, (int)K)
+#define LAUNCH_TOTAL(STORE, OCC, WALK, VOTE) hipLaunchKernelGGL((k_total<STORE, OCC, WALK, VOTE>), grid, dim3(BLOCK_THREADS), 0, st, V, B, (int)gx, (int)P.n_whole, (int)P.rest, (int)P.stride, (int)P.K)
 #define LAUNCH_WALK(STORE, VOTE) do { if (!many) LAUNCH_TOTAL(STORE, HIBAG_TOT_OCC, 0, VOTE);                                 \
 		else if (M.p1_prebuilt) LAUNCH_TOTAL(STORE, HIBAG_TOT_OCC_MANY, 2, VOTE); else LAUNCH_TOTAL(STORE, HIBAG_TOT_OCC_MANY, 1, VOTE); } while (0)
 	if (vote) LAUNCH_WALK(false, true);
@@ -256,31 +245,36 @@ void hibag_launch_total(const HibagModelView &M, const HibagBatchView &B, hipStr
 	if (split)
 		hipLaunchKernelGGL(k_total_scan, dim3(B.n_pad / 64, V.n_split), dim3(64), 0, st, V, B);
 	if (wide && side.stream) (void)hipStreamWaitEvent(st, side.join, 0);
+	R.plan = P;
+	R.launched = 1;
+	R.walk = !many ? 0 : M.p1_prebuilt ? 2 : 1;
+	R.store = !vote && M.store_cells;
+	R.vote = vote;
+	return R;
 }
 
-void hibag_launch_accum(const HibagModelView &M, const HibagBatchView &B, hipStream_t st)
+HibagLaunchAccum hibag_launch_accum(const HibagModelView &M, const HibagBatchView &B, hipStream_t st)
 {
+	HibagLaunchAccum R;
 	if (M.store_cells == 1 && M.n_classifier > 0) {    // pass 1 stored every cell: read them back
 		const unsigned groups_x = (unsigned)((B.n_pad / HIBAG_WAVE + 7) / 8), tq = (unsigned)((M.n_tile + CELLS_WAVES - 1) / CELLS_WAVES);
 		hipLaunchKernelGGL(k_accum_cells, dim3(8 * groups_x * tq), dim3(CELLS_WAVES * HIBAG_WAVE), 0, st, M, B);
-		return;
+		R.kernel = 2;
+		return R;
 	}
 	const unsigned n_group = (unsigned)(B.n_pad / HIBAG_WAVE);
 	const unsigned n = 8u * (((n_group + 7) / 8 + ACCUM_WAVES - 1) / ACCUM_WAVES) * (unsigned)M.n_tile;   // work items, see k_accum
 	if (n == 0 || M.n_classifier == 0) {
 		// no classifier: the ensemble sums are all zero (src/LibHLA.cpp:1491-1495)
 		(void)hipMemsetAsync(B.part, 0, (size_t)M.n_cell * B.n_pad * sizeof(double), st);
-		return;
+		return R;
 	}
-	// more items than resident workgroups: the last, incomplete round and the full round before it go in K chunks each
-	const int slots = M.slots_accum;
-	const unsigned nx = n / 8, sx = (unsigned)slots / 8;
-	unsigned n_whole = nx, K = 1;
-	if (tail_chunks(B.tail_k, 0, 2) > 1 && sx > 0 && nx > sx) {
-		K = (unsigned)tail_chunks(B.tail_k, 0, 2);
-		n_whole = nx - (nx % sx + sx);
-	}
-	hipLaunchKernelGGL(k_accum, dim3(8 * (n_whole + K * (nx - n_whole))), dim3(ACCUM_WAVES * HIBAG_WAVE), 0, st, M, B, (int)n_whole, (int)K);
+	// which items go whole and which in chunks: hibag_plan_accum (hibag_plan.h)
+	const HibagPlanAccum P = hibag_plan_accum(n / 8, M.slots_accum, tail_chunks(B.tail_k, 0, 2));
+	hipLaunchKernelGGL(k_accum, dim3(P.grid), dim3(ACCUM_WAVES * HIBAG_WAVE), 0, st, M, B, (int)P.n_whole, (int)P.K);
+	R.plan = P;
+	R.kernel = 1;
+	return R;
 }
 
 void hibag_launch_vote(const HibagModelView &M, const HibagBatchView &B, int *d_best_cell, hipStream_t st)

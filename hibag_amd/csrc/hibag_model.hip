@@ -912,6 +912,9 @@ int upload_layout(hibag_hip_model *m, const ModelLayout &L)
 		HIP_TRY(hipEventCreateWithFlags(&m->side.join, hipEventDisableTiming));
 	}
 	hibag_query_slots(V.slots_total, &V.slots_accum);
+	for (int i = 0; i < 4; i++) m->slots_queried[i] = V.slots_total[i];
+	m->slots_queried[4] = V.slots_accum;
+	m->test_slots[0] = m->test_slots[1] = m->test_tail_k = 0;     // (the tests' chunking hook is set on a finalized model)
 	m->spin_limit = s.spin_limit;
 	m->pair_evals = s.pair_evals;
 	m->store_mode = s.store_mode;

@@ -71,7 +71,7 @@ int make_batch(hibag_hip_model *m, int n_samp, bool need_best, HibagBatchView &B
 	B.sync = m->ws_sync.as<unsigned long long>(); B.epoch = m->epoch; B.err = m->h_err;
 	B.err_dev = m->ws_err.as<uint32_t>();
 	B.spin_limit = m->spin_limit;
-	B.tail_k = m->no_chunks ? 1 : 0;
+	B.tail_k = m->no_chunks ? 1 : m->test_tail_k;     // (test_tail_k: hibag_hip_test_set_chunking, 0 unless a test set it)
 	B.drop_post = m->drop_next;
 	if (m->drop_next) { B.spin_limit = 4096; m->drop_next = 0; }     // (the injected fault should not take the full time-out)
 	B.sync_total = B.sync + 8 * (((size_t)(n_pad / HIBAG_WAVE + 7) / 8 + HIBAG_ACCUM_WAVES - 1) / HIBAG_ACCUM_WAVES) * (size_t)std::max(m->view.n_tile, 1);
@@ -104,12 +104,14 @@ void run_core(hibag_hip_model *m, HibagBatchView &B, int vote_method, double *d_
 	B.part = d_part;
 	debug_stage("pack", st);
 	T.begin(HIBAG_HIP_K_TOTAL, st, true);      // (callers enqueue nothing between their pack and this)
-	hibag_launch_total(m->view, B, st, m->side, vote_method == 2);
+	m->last_total = hibag_launch_total(m->view, B, st, m->side, vote_method == 2);
+	m->n_launch_total++;
 	T.end(st);
 	debug_stage("pass 1", st);
 	T.begin(HIBAG_HIP_K_ACCUM, st, true);
 	if (vote_method == 1) {
-		hibag_launch_accum(m->view, B, st);
+		m->last_accum = hibag_launch_accum(m->view, B, st);
+		m->n_launch_accum++;
 		debug_stage("pass 2 (accumulate)", st);
 		hibag_launch_scalars(m->view, B, nullptr, st);
 	} else {
@@ -1369,6 +1371,77 @@ int hibag_hip_test_inject_handover_fault(hibag_hip_model *m, int pass)
 	if (!m || pass < 0 || pass > 2) return hibag_fail(HIBAG_HIP_EINVAL, "pass must be 0 (none), 1 or 2");
 	std::lock_guard<std::mutex> g(m->lock);
 	m->drop_next = pass;
+	return 0;
+}
+
+// The tests' chunking hook: fewer resident workgroups than the device has (never more: a waiting workgroup may only
+// wait for one that the device has dispatched, and the launch arithmetic derives that from these figures) and the chunk count
+// of both passes, so that a small cohort reaches the chunked tail.  0 restores an argument's default.
+int hibag_hip_test_set_chunking(hibag_hip_model *m, int slots_pass1, int slots_pass2, int tail_k)
+{
+	if (!m) return hibag_fail(HIBAG_HIP_EINVAL, "model is NULL");
+	if (slots_pass1 < 0 || slots_pass2 < 0) return hibag_fail(HIBAG_HIP_EINVAL, "test_set_chunking: slots must not be negative (0 = the device's figure)");
+	if (tail_k < 0 || tail_k > 64) return hibag_fail(HIBAG_HIP_EINVAL, "test_set_chunking: tail_k must be 0 (default) or 1 .. 64");
+	std::lock_guard<std::mutex> g(m->lock);
+	if (!m->finalized) return hibag_fail(HIBAG_HIP_ESTATE, "test_set_chunking: model not finalized");
+	m->test_slots[0] = slots_pass1;
+	m->test_slots[1] = slots_pass2;
+	m->test_tail_k = tail_k;
+	// (an unknown figure, 0, stays 0: chunking stays off)
+	auto lowered = [](int queried, int asked) { return asked > 0 ? std::min(queried, asked) : queried; };
+	for (int i = 0; i < 4; i++) m->view.slots_total[i] = lowered(m->slots_queried[i], slots_pass1);
+	m->view.slots_accum = lowered(m->slots_queried[4], slots_pass2);
+	return 0;
+}
+
+int hibag_hip_test_last_launch(hibag_hip_model *m, hibag_hip_launch_info *out)
+{
+	if (!m) return hibag_fail(HIBAG_HIP_EINVAL, "model is NULL");
+	if (!out) return hibag_fail(HIBAG_HIP_EINVAL, "test_last_launch: out is NULL");
+	std::lock_guard<std::mutex> g(m->lock);
+	if (!m->finalized) return hibag_fail(HIBAG_HIP_ESTATE, "test_last_launch: model not finalized");
+	const HibagLaunchTotal &T = m->last_total;
+	const HibagLaunchAccum &A = m->last_accum;
+	out->p1_launches = m->n_launch_total;
+	out->p1_kernel = T.launched;
+	out->p1_n = (int32_t)T.plan.n; out->p1_slots = (int32_t)T.plan.slots; out->p1_k = (int32_t)T.plan.K;
+	out->p1_n_whole = (int32_t)T.plan.n_whole; out->p1_rest = (int32_t)T.plan.rest; out->p1_stride = (int32_t)T.plan.stride;
+	out->p1_grid = (int32_t)T.plan.grid;
+	out->p1_many = T.plan.many; out->p1_walk = T.walk; out->p1_store = T.store; out->p1_vote = T.vote;
+	out->p2_launches = m->n_launch_accum;
+	out->p2_kernel = A.kernel;
+	out->p2_nx = (int32_t)A.plan.nx; out->p2_sx = (int32_t)A.plan.sx; out->p2_k = (int32_t)A.plan.K;
+	out->p2_n_whole = (int32_t)A.plan.n_whole; out->p2_grid = (int32_t)A.plan.grid;
+	return 0;
+}
+
+int hibag_hip_test_plan_total(int gx, int n_item, int slots_few, int slots_many, int k_req, int vote, int all_fp4, int split,
+	hibag_hip_launch_info *out)
+{
+	if (!out) return hibag_fail(HIBAG_HIP_EINVAL, "test_plan_total: out is NULL");
+	if (gx < 0 || n_item < 0 || (long long)gx * n_item > (1ll << 24))
+		return hibag_fail(HIBAG_HIP_EINVAL, "test_plan_total: gx and n_item must not be negative, gx * n_item at most 2^24");
+	if (slots_few < 0 || slots_many < 0 || slots_few > (1 << 24) || slots_many > (1 << 24))
+		return hibag_fail(HIBAG_HIP_EINVAL, "test_plan_total: slots must be within 0 .. 2^24");
+	if (k_req < 1 || k_req > 64) return hibag_fail(HIBAG_HIP_EINVAL, "test_plan_total: k_req must be within 1 .. 64");
+	const HibagPlanTotal P = hibag_plan_total((unsigned)gx, (unsigned)n_item, slots_few, slots_many, k_req, vote != 0, all_fp4 != 0, split != 0);
+	memset(out, 0, sizeof *out);
+	out->p1_n = (int32_t)P.n; out->p1_slots = (int32_t)P.slots; out->p1_k = (int32_t)P.K; out->p1_n_whole = (int32_t)P.n_whole;
+	out->p1_rest = (int32_t)P.rest; out->p1_stride = (int32_t)P.stride; out->p1_grid = (int32_t)P.grid; out->p1_many = P.many;
+	out->p1_vote = vote != 0;
+	return 0;
+}
+
+int hibag_hip_test_plan_accum(int nx, int slots, int k_req, hibag_hip_launch_info *out)
+{
+	if (!out) return hibag_fail(HIBAG_HIP_EINVAL, "test_plan_accum: out is NULL");
+	if (nx < 0 || nx > (1 << 21)) return hibag_fail(HIBAG_HIP_EINVAL, "test_plan_accum: nx must be within 0 .. 2^21");
+	if (slots < 0 || slots > (1 << 24)) return hibag_fail(HIBAG_HIP_EINVAL, "test_plan_accum: slots must be within 0 .. 2^24");
+	if (k_req < 1 || k_req > 64) return hibag_fail(HIBAG_HIP_EINVAL, "test_plan_accum: k_req must be within 1 .. 64");
+	const HibagPlanAccum P = hibag_plan_accum((unsigned)nx, slots, k_req);
+	memset(out, 0, sizeof *out);
+	out->p2_nx = (int32_t)P.nx; out->p2_sx = (int32_t)P.sx; out->p2_k = (int32_t)P.K; out->p2_n_whole = (int32_t)P.n_whole;
+	out->p2_grid = (int32_t)P.grid;
 	return 0;
 }
 

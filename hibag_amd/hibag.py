@@ -175,6 +175,17 @@ class HlaAttrBagClass:
         """Tests only: the next batch drops the first hand-over of pass 1 or 2."""
         _lib.check(_lib.lib().hibag_hip_test_inject_handover_fault(self.handle, int(which_pass)))
 
+    def set_chunking(self, slots_pass1: int = 0, slots_pass2: int = 0, tail_k: int = 0):
+        """Tests only: lower the resident-workgroup figures of pass 1 / pass 2 (never above what the device reported) and
+        set the chunks per item of both passes; 0 restores an argument's default (``hibag_hip_test_set_chunking``)."""
+        _lib.check(_lib.lib().hibag_hip_test_set_chunking(self.handle, int(slots_pass1), int(slots_pass2), int(tail_k)))
+
+    def last_launch(self) -> dict:
+        """Tests only: what the model's most recent passes 1 and 2 launched (``hibag_hip_launch_info`` as a dict)."""
+        info = _lib.LaunchInfo()
+        _lib.check(_lib.lib().hibag_hip_test_last_launch(self.handle, C.byref(info)))
+        return info.as_dict()
+
     def engine(self, classifier: int):
         """(engine name, K steps) of a classifier as the library finalized it."""
         e, k = C.c_int(0), C.c_int(0)
@@ -794,6 +805,25 @@ def multi_slice(n_samp: int, n_models: int, i: int):
     a, b = C.c_int(0), C.c_int(0)
     _lib.check(_lib.lib().hibag_hip_multi_slice(int(n_samp), int(n_models), int(i), C.byref(a), C.byref(b)))
     return a.value, b.value
+
+
+def plan_total(gx: int, n_item: int, slots_few: int, slots_many: int, k_req: int, vote: bool = False, all_fp4: bool = False,
+               split: bool = False) -> dict:
+    """Tests only: pass 1's launch arithmetic with every input given (``hibag_hip_test_plan_total``; no device): the
+    ``p1_*`` plan fields of ``hibag_hip_launch_info`` without the prefix."""
+    info = _lib.LaunchInfo()
+    _lib.check(_lib.lib().hibag_hip_test_plan_total(int(gx), int(n_item), int(slots_few), int(slots_many), int(k_req),
+                                                    int(bool(vote)), int(bool(all_fp4)), int(bool(split)), C.byref(info)))
+    d = info.as_dict()
+    return {k: d["p1_" + k] for k in ("n", "slots", "k", "n_whole", "rest", "stride", "grid", "many")}
+
+
+def plan_accum(nx: int, slots: int, k_req: int) -> dict:
+    """Tests only: pass 2's launch arithmetic (``hibag_hip_test_plan_accum``; no device): the ``p2_*`` plan fields."""
+    info = _lib.LaunchInfo()
+    _lib.check(_lib.lib().hibag_hip_test_plan_accum(int(nx), int(slots), int(k_req), C.byref(info)))
+    d = info.as_dict()
+    return {k: d["p2_" + k] for k in ("nx", "sx", "k", "n_whole", "grid")}
 
 
 def predict_multi(models: Sequence[HlaAttrBagClass], genomat: np.ndarray, vote_method: int = 1, want_dosage: bool = True,

@@ -469,6 +469,47 @@ int64_t hibag_hip_model_handover_faults(const hibag_hip_model *m);
 /* Fault injection for the tests of the above: the next batch on the model drops the first hand-over of pass `pass`
  * (1 or 2; 0 = disarm) and uses a short time-out.  Not for production use. */
 int hibag_hip_test_inject_handover_fault(hibag_hip_model *m, int pass);
+/* The chunked tail at small shapes, for the tests (DESIGN.md "The chunked tail, replayed and forced").  Not for production use.
+ *
+ * hibag_hip_test_set_chunking: on a finalized model, a positive slots_pass1 / slots_pass2 replaces the number of resident
+ * workgroups the device reported for pass 1 (all four builds of k_total) / pass 2 (k_accum) by min(reported, value) -- it can
+ * only be lowered -- and tail_k in 1 .. 64 becomes the chunks per item of both passes (what HIBAG_TAIL_K sets process-wide).
+ * 0 restores that argument's default.  Where the device reported nothing (0) chunking stays off, and a model that has had a
+ * failed hand-over keeps launching without chunks.  Finalizing the model again forgets the hook.
+ *
+ * hibag_hip_test_last_launch: what the model's most recent passes 1 and 2 launched (a predict step's; zeros before the first).
+ *
+ * hibag_hip_test_plan_total / _accum: the launchers' arithmetic alone, every input given: no device, no model.  They fill
+ * the p1_* resp. p2_* plan fields of `out` and zero the rest.  gx = group quads (of 4 x 64 samples), n_item = the model's
+ * work items, slots_few / slots_many = resident workgroups of the five- and the six-per-CU build, k_req = chunks asked for
+ * (1 .. 64); nx = pass-2 items per XCD (group quads x tiles), slots = resident workgroups of k_accum on the device. */
+typedef struct hibag_hip_launch_info {
+	int32_t p1_launches;   /* passes 1 of the model so far */
+	int32_t p1_kernel;     /* 1: k_total was launched (0: no classifier, or none that k_total walks) */
+	int32_t p1_n;          /* work items = group quads x items */
+	int32_t p1_slots;      /* resident workgroups of the build chosen (0 = unknown) */
+	int32_t p1_k;          /* chunks per cut item (1: none cut) */
+	int32_t p1_n_whole;    /* undivided items: workgroups [0, n_whole) */
+	int32_t p1_rest;       /* cut items (0: none) */
+	int32_t p1_stride;     /* rest rounded up to a multiple of 8 */
+	int32_t p1_grid;       /* workgroups = n_whole + K * stride */
+	int32_t p1_many;       /* 1: the FP4-only build at six workgroups per CU */
+	int32_t p1_walk;       /* the build's walk: 0 = every engine, 1 = FP4-only on generated rows, 2 = FP4-only on prebuilt rows */
+	int32_t p1_store;      /* 1: the build that stores every cell sum */
+	int32_t p1_vote;       /* 1: the majority vote's build */
+	int32_t p2_launches;   /* passes 2 (vote_method 1) of the model so far */
+	int32_t p2_kernel;     /* 0 = none, 1 = k_accum (the block stream), 2 = k_accum_cells (every cell read back: never chunked) */
+	int32_t p2_nx;         /* items per XCD */
+	int32_t p2_sx;         /* resident workgroups per XCD */
+	int32_t p2_k;          /* chunks per cut item */
+	int32_t p2_n_whole;    /* undivided items per XCD */
+	int32_t p2_grid;       /* workgroups = 8 * (n_whole + K * (nx - n_whole)) */
+} hibag_hip_launch_info;
+int hibag_hip_test_set_chunking(hibag_hip_model *m, int slots_pass1, int slots_pass2, int tail_k);
+int hibag_hip_test_last_launch(hibag_hip_model *m, hibag_hip_launch_info *out);
+int hibag_hip_test_plan_total(int gx, int n_item, int slots_few, int slots_many, int k_req, int vote, int all_fp4, int split,
+	hibag_hip_launch_info *out);
+int hibag_hip_test_plan_accum(int nx, int slots, int k_req, hibag_hip_launch_info *out);
 /* Kept for ABI compatibility: writes n (<= 40) zeros to `out` and returns 0.  (It read the clock sums of diagnostic kernel
  * builds that no longer exist.) */
 int hibag_hip_test_read_diag(hibag_hip_model *m, unsigned long long *out, int n);

@@ -332,6 +332,17 @@ def test_status_entries_reject_bad_arguments_without_a_gpu():
     e, k = C.c_int(0), C.c_int(0)
     assert L.hibag_hip_model_engine(m, 0, C.byref(e), C.byref(k)) == -4          # not finalized
     assert L.hibag_hip_model_status(m) in (0, -2)                                # no launches; -2 where there is no device
+    # the chunking hook and the launch record beside it: NULL handle, values out of range, a model that is not finalized
+    info = _lib.LaunchInfo()
+    assert L.hibag_hip_test_set_chunking(None, 0, 0, 0) == -1
+    assert L.hibag_hip_test_last_launch(None, C.byref(info)) == -1
+    for bad in ((-1, 0, 0), (0, -1, 0), (0, 0, -1), (0, 0, 65)):
+        assert L.hibag_hip_test_set_chunking(m, *bad) == -1, bad
+        assert "test_set_chunking" in L.hibag_hip_last_error().decode()
+    assert L.hibag_hip_test_last_launch(m, None) == -1
+    assert L.hibag_hip_test_set_chunking(m, 8, 8, 2) == -4                       # not finalized
+    assert L.hibag_hip_test_set_chunking(m, 0, 0, 0) == -4
+    assert L.hibag_hip_test_last_launch(m, C.byref(info)) == -4
     L.hibag_hip_model_free(m)
 
 
