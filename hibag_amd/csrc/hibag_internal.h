@@ -5,8 +5,10 @@
 //   hibag_api.hip      error state, device selection, kernel target, the plugin table
 //   hibag_model.hip    the model: classifiers in, the device layout out (hibag_hip_model_new ... _finalize, replicas, shards)
 //   hibag_predict.hip  the batch driver that replaces CAttrBag_Model::PredictHLA: workspace, kernel sequence (enqueue_pack,
-//                      run_core), the host-pointer pipeline (predict_staged_locked), the SNP map upload, BED input, the
-//                      out-of-bag and masked drivers, partial sums, launch status, timing
+//                      run_core), the host-pointer pipeline (predict_staged_locked), the SNP map upload, BED input, partial
+//                      sums, launch status, timing
+//   hibag_whole.hip    the entries that take a small cohort through the device in ONE call: their frame (WholeCall), the
+//                      batch knobs, the SNP-users index, the out-of-bag and masked drivers with their entries
 //   hibag_finish.hip   what depends on the finish a call runs (ListOut::kind): its argument check, the call's state on the
 //                      device, its workspace, its launch
 //   hibag_prefix.hip   hibag_hip_predict_prefix: every sub-model "first k classifiers" from one pass 1
@@ -25,6 +27,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <mutex>
 #include <new>
 #include <string>
@@ -194,6 +197,9 @@ struct hibag_hip_model {
 
 	// per-batch workspace (grow-only)
 	DevBuf ws_planes, ws_cw, ws_tot, ws_inv, ws_winv, ws_part, ws_best, ws_vrec, ws_geno, ws_out, ws_codes, ws_bt, ws_bias, ws_cells, ws_sync;
+	// the whole-call entries (WholeCall below): a call's inputs beside the genotypes, and what only its own kernels read
+	// and write; their outputs share ws_out
+	DevBuf ws_in, ws_scratch;
 	// the given entries (hibag_hip_predict_given*): a host-pointer call's constraint on the device, sample-major as the caller
 	// gave it, and a batch's masks as k_finish_given reads them ([2 W][n_pad])
 	DevBuf ws_allow, ws_masks;
@@ -245,21 +251,15 @@ struct hibag_hip_model {
 	DevBuf dist_cells, dist_tri, dist_acc, dist_num, dist_out;
 	double dist_ms = 0;
 	// hibag_hip_predict_prefix (hibag_prefix.hip): the second layout of this model, finalized with every cell sum stored
-	// (built at the first call on a model whose own layout is not store mode 1, never touched by the other entries), and
-	// the entry's workspace: the sub-models' SNP counts, their classifier weights, the tiles' maxima
+	// (built at the first call on a model whose own layout is not store mode 1, never touched by the other entries; the
+	// call runs on that layout's workspace)
 	hibag_hip_model *prefix_layout = nullptr;
-	DevBuf pfx_tab, pfx_cw, pfx_best, pfx_cell;
 	double pfx_accum_ms = 0;
-	// hibag_hip_predict_masked: the inverted index SNP -> classifiers (CSR: n_snp + 1 offsets, then the classifiers; built at
-	// the first call), the call's mask [C][n_samp] and the batch's per-sample SNP counts [n_snp][n_pad]
-	DevBuf mask_idx, mask_use, mask_cnt;
-	bool mask_idx_ready = false;
-	// hibag_hip_oob_knock (hibag_knock.hip): the inverted index SNP -> (classifier, variant) (CSR: n_snp + 1 offsets, the
-	// classifiers, the variants; built at the first call, with its host twin), the cohort's byte codes, the call's inputs
-	// (bootstrap counts, truth, group table), a batch's picks with the base calls, and the tallies with the raw outputs
-	DevBuf knock_idx, knock_base, knock_in, knock_res, knock_out;
-	std::vector<int> knock_user_off;       // [n_snp + 1]
-	bool knock_idx_ready = false;
+	// hibag_hip_predict_masked, hibag_hip_oob_knock: the inverted index SNP -> (classifier, variant) (snp_users_index; CSR:
+	// n_snp + 1 offsets, the classifiers, the variants; built at the first call, with the offsets' host twin)
+	DevBuf snp_users;
+	std::vector<int> snp_users_off;        // [n_snp + 1]
+	bool snp_users_ready = false;
 
 	KernelTimer timer;
 	std::mutex lock;
@@ -280,9 +280,8 @@ struct hibag_hip_model {
 		if (dist_st) (void)hipStreamDestroy(dist_st);
 		for (hipEvent_t e : dist_ev) if (e) (void)hipEventDestroy(e);
 		for (DevBuf *b : {&d_int, &d_stream, &d_tile, &d_tab, &d_blk, &d_pfac, &d_phdr, &d_parow, &ws_bt, &ws_bias, &ws_cells, &ws_sync, &ws_err, &ws_planes, &ws_cw, &ws_tot, &ws_inv, &ws_winv,
-		                  &ws_part, &ws_best, &ws_vrec, &ws_geno, &ws_out, &ws_codes, &ws_allow, &ws_masks, &ws_fam_in, &ws_family, &ws_ratios, &ws_bed, &ws_bedidx, &oob_hap,
-		                  &dist_cells, &dist_tri, &dist_acc, &dist_num, &dist_out, &pfx_tab, &pfx_cw, &pfx_best, &pfx_cell,
-		                  &mask_idx, &mask_use, &mask_cnt, &knock_idx, &knock_base, &knock_in, &knock_res, &knock_out})
+		                  &ws_part, &ws_best, &ws_vrec, &ws_geno, &ws_out, &ws_in, &ws_scratch, &ws_codes, &ws_allow, &ws_masks, &ws_fam_in, &ws_family, &ws_ratios, &ws_bed, &ws_bedidx, &oob_hap,
+		                  &dist_cells, &dist_tri, &dist_acc, &dist_num, &dist_out, &snp_users})
 			b->release();
 		delete prefix_layout;
 	}
@@ -305,7 +304,7 @@ void build_table(double *tab);                               // hibag_model.hip:
 int finalize_model(hibag_hip_model *m);                      // hibag_model.hip
 int finalize_model_stream(hibag_hip_model *m);               // hibag_model.hip: the same with FinalizeOptions::STREAM (every cell sum stored), whatever the environment says
 int batch_limit(const hibag_hip_model *m);                   // hibag_predict.hip: samples per batch (workspace bound)
-int oob_hap_table(hibag_hip_model *m);                       // hibag_predict.hip: m->oob_hap from m->cls (once)
+int oob_hap_table(hibag_hip_model *m);                       // hibag_whole.hip: m->oob_hap from m->cls (once)
 
 // ---- hibag_predict.hip's batch driver, as far as hibag_merge.hip drives it too ----
 // Where a batch's genotypes come from: the int32 matrix, or a PLINK BED payload.
@@ -472,6 +471,8 @@ int make_batch(hibag_hip_model *m, int n_samp, bool need_best, HibagBatchView &B
 // the pack of batch samples [s0, s0 + B.n_samp) of `src` into m->ws_codes, whichever of the three forms `src` has
 void enqueue_pack(hibag_hip_model *m, HibagBatchView &B, const PackSource &src, int s0, hipStream_t st);
 void run_core(hibag_hip_model *m, HibagBatchView &B, int vote_method, double *d_part, hipStream_t st);   // passes 1 and 2 behind a pack
+// HIBAG_DEBUG_SYNC=1: wait for the stream behind a stage and name it on stderr (which kernel a device fault belongs to)
+void debug_stage(const char *what, hipStream_t st);
 // (`unfinalized`: the code an unfinalized model gets -- ListOut::unfinalized_code() where the call has an output set)
 int check_predict_args(hibag_hip_model *m, const void *geno, int n_samp, int vote_method, const void *H1, const void *H2, int unfinalized = HIBAG_HIP_ESTATE);
 
@@ -507,6 +508,62 @@ struct WorkspaceGuard {
 	int leave() { left = true; return workspace_leave(m, st); }
 	~WorkspaceGuard() { if (enqueued && !left && m->ws_done) { (void)hipEventRecord(m->ws_done, st); m->ws_pending = true; } }
 };
+
+// ---- hibag_whole.hip: a small (training-sized) cohort through the device in ONE call ----
+// hibag_hip_predict_oob, hibag_hip_predict_masked, hibag_hip_oob_knock and hibag_hip_predict_prefix upload the genotypes and
+// the call's inputs once, run batches on the model's workspace and download the results once.  WholeCall is the frame they
+// share; the entries hold m->lock for the whole call, run it under with_handover_repair and end synchronised.
+
+// The layout of one device buffer: take() hands out consecutive 8-byte-aligned blocks (0 bytes for what is not asked for),
+// `bytes` is what they need in all, at() a block's address once the buffer is reserved.
+struct Arena {
+	size_t bytes = 0;
+	char *base = nullptr;
+	size_t take(size_t n) { const size_t at = bytes; bytes = at + (n + 7) / 8 * 8; return at; }
+	template <class T> T *at(size_t off) const { return (T *)(base + off); }
+};
+
+// The frame of one whole call on the workspace of `m` (for the prefix entry the layout it runs on).  The driver lays out
+// `in` (ws_in: the call's inputs), `out` (ws_out: what goes back to the caller) and `scratch` (ws_scratch: what only the
+// call's kernels touch) with take(), then
+//   open()            the model's run stream, every reserve, workspace_enter, the armed guard: from here on ws_done is
+//                     recorded on every return
+//   upload*()         the genotypes into ws_geno (`geno`: where the packs of the batches read them), the inputs into `in`
+//   for_each_batch()  make_batch and the driver's launches for `count` samples from `first` on
+//   close()           hipGetLastError, the downloads (a null destination: not asked for), the ws_done record, the synchronise
+struct WholeCall {
+	struct Download { void *dst; const void *src; size_t bytes; };
+	hibag_hip_model *m;
+	hipStream_t st = nullptr;
+	Arena in, out, scratch;
+	PackSource geno;                       // the call's genotypes on the device: [n_samp][n_snp] in ws_geno
+	size_t geno_bytes = 0;
+	WorkspaceGuard guard;
+
+	explicit WholeCall(hibag_hip_model *model) : m(model) {}
+	int open(int n_samp);
+	int upload(void *dst, const void *src, size_t bytes) { HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st)); return 0; }
+	int upload_geno(const int32_t *host) { return upload(m->ws_geno.p, host, geno_bytes); }
+	int download(void *dst, const void *src, size_t bytes) { if (dst) HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st)); return 0; }
+	int close(std::initializer_list<Download> downloads);
+	// (`lim`: the unit's batch cap -- samples, or for the knock-out the lanes of its 64-lane groups)
+	template <class Body> int for_each_batch(size_t total, size_t lim, bool need_best, Body body)
+	{
+		for (size_t first = 0; first < total; first += lim) {
+			const int count = (int)std::min(lim, total - first);
+			HibagBatchView B;
+			if (int rc = make_batch(m, count, need_best, B)) return rc;
+			if (int rc = body(B, first, count)) return rc;
+		}
+		return 0;
+	}
+};
+
+// `lim` lowered to the diagnostic knob `env_name` (smaller batches), in whole wavefronts: at least 64
+int batch_cap(const char *env_name, int lim);
+int oob_force_rescan();                                      // HIBAG_OOB_RESCAN (diagnostic): every pick by the full walk
+void oob_hap_view(const hibag_hip_model *m, HibagOobOut &O); // the hap_* and hla_start fields of O from m->oob_hap
+int snp_users_index(hibag_hip_model *m);                     // m->snp_users from m->cls (once)
 
 // The repair of a failed hand-over, for every driver whose results go to the caller's host arrays.  A device-pointer launch
 // still running on another stream may yet fail a hand-over: it is waited for first, so that its fault becomes the model's

@@ -55,8 +55,7 @@ void push_classifier(hibag_hip_model *m, int n_snp_c, const int32_t *snpidx, int
 	c.bits = std::move(bits);
 	m->cls.push_back(std::move(c));
 	m->oob_hap_ready = false;                // hibag_hip_model_distance may have built the table of an unfinalized model
-	m->mask_idx_ready = false;
-	m->knock_idx_ready = false;
+	m->snp_users_ready = false;
 }
 
 // Words per pair record: ceil(3k/32) rounded up to a width the kernels are

@@ -89,7 +89,7 @@ int make_batch(hibag_hip_model *m, int n_samp, bool need_best, HibagBatchView &B
 // Passes 1 and 2 (+ majority-vote variant) and the ensemble scalars for a
 // batch whose planes / weights are already on the device.
 // HIBAG_DEBUG_SYNC=1: wait for the stream behind every stage and name it on stderr (which kernel a device fault belongs to)
-static void debug_stage(const char *what, hipStream_t st)
+void debug_stage(const char *what, hipStream_t st)
 {
 	static const bool on = getenv("HIBAG_DEBUG_SYNC") != nullptr;
 	if (!on) return;
@@ -588,183 +588,6 @@ int load_bed(const char *fn, int n_samp, int n_snp, const int32_t *want, int n_w
 	return 0;
 }
 
-// ---------------------------------------------------------------------------
-// hlaOutOfBag's per-classifier predictions (hibag_hip_predict_oob)
-
-// The plain haplotype table of every classifier on the device (HibagOobOut): what oob_rescan walks.
-int oob_hap_table(hibag_hip_model *m)
-{
-	if (m->oob_hap_ready) return 0;
-	const int C = (int)m->cls.size(), nh = m->n_hla;
-	std::vector<uint64_t> bits;
-	std::vector<double> freq;
-	std::vector<int> off(std::max(C, 1), 0), start((size_t)std::max(C, 1) * (nh + 1), 0);
-	for (int c = 0; c < C; c++) {
-		const HostClassifier &k = m->cls[c];
-		off[c] = (int)freq.size();
-		int *st = &start[(size_t)c * (nh + 1)];
-		for (int h : k.hla) st[h + 1]++;                       // (haplotypes are grouped by allele, as the model's builder takes them)
-		for (int h = 0; h < nh; h++) st[h + 1] += st[h];
-		bits.insert(bits.end(), k.bits.begin(), k.bits.end());
-		freq.insert(freq.end(), k.freq.begin(), k.freq.end());
-	}
-	if (freq.empty()) { bits.assign(2, 0); freq.assign(1, 0.0); }
-	const size_t b_bits = bits.size() * sizeof(uint64_t), b_freq = freq.size() * sizeof(double), b_off = off.size() * sizeof(int);
-	m->oob_freq_at = b_bits;
-	m->oob_off_at = m->oob_freq_at + b_freq;
-	m->oob_start_at = m->oob_off_at + b_off;
-	if (int rc = m->oob_hap.reserve(m->oob_start_at + start.size() * sizeof(int))) return rc;
-	char *d = m->oob_hap.as<char>();
-	HIP_TRY(hipMemcpy(d, bits.data(), b_bits, hipMemcpyHostToDevice));
-	HIP_TRY(hipMemcpy(d + m->oob_freq_at, freq.data(), b_freq, hipMemcpyHostToDevice));
-	HIP_TRY(hipMemcpy(d + m->oob_off_at, off.data(), b_off, hipMemcpyHostToDevice));
-	HIP_TRY(hipMemcpy(d + m->oob_start_at, start.data(), start.size() * sizeof(int), hipMemcpyHostToDevice));
-	m->oob_hap_ready = true;
-	return 0;
-}
-
-// The whole call on the device: genotypes and bootstrap counts up once, batches of at most batch_limit samples (pack,
-// one-classifier weights, pass 1 with its record log, the picks), the [C][n_samp] results down once.  The entry runs it
-// under with_handover_repair, like predict_staged_locked.
-static int predict_oob_locked(hibag_hip_model *m, const int32_t *geno, int n_samp, const int32_t *samp_num,
-	int32_t *H1, int32_t *H2, double *prob)
-{
-	if (int rc = oob_hap_table(m)) return rc;
-	StagedStreams *ss;
-	if (int rc = staged_streams(m, &ss)) return rc;
-	const hipStream_t st = ss->run;
-	const size_t C = (size_t)m->view.n_classifier, n = (size_t)n_samp, S = (size_t)m->n_snp;
-	const size_t o_samp = 0, o_h1 = o_samp + C * n * 4, o_h2 = o_h1 + C * n * 4, o_prob = (o_h2 + C * n * 4 + 7) / 8 * 8,
-		out_bytes = o_prob + C * n * 8;
-	if (int rc = m->ws_geno.reserve(std::max<size_t>(n * S * sizeof(int32_t), 4))) return rc;
-	if (int rc = m->ws_out.reserve(out_bytes)) return rc;
-	char *o = m->ws_out.as<char>();
-	const int32_t *d_geno = m->ws_geno.as<int32_t>();
-	if (int rc = workspace_enter(m, st)) return rc;
-	WorkspaceGuard guard{m, st};
-	guard.enqueued = true;
-	HIP_TRY(hipMemcpyAsync(m->ws_geno.p, geno, n * S * sizeof(int32_t), hipMemcpyHostToDevice, st));
-	HIP_TRY(hipMemcpyAsync(o + o_samp, samp_num, C * n * 4, hipMemcpyHostToDevice, st));
-	int lim = batch_limit(m);
-	if (const char *e = getenv("HIBAG_OOB_BATCH")) lim = std::min(lim, std::max(64, atoi(e)) / 64 * 64);     // (diagnostic: smaller batches)
-	const int force_rescan = getenv("HIBAG_OOB_RESCAN") && atoi(getenv("HIBAG_OOB_RESCAN")) != 0;           // (diagnostic: every call by the full walk)
-	const char *d_base = m->oob_hap.as<char>();
-	for (int s0 = 0; s0 < n_samp; s0 += lim) {
-		const int nb = std::min(lim, n_samp - s0);
-		HibagBatchView B;
-		if (int rc = make_batch(m, nb, true, B)) return rc;
-		HibagOobOut O;
-		O.samp_num = (const int32_t *)(o + o_samp) + s0;
-		O.h1 = (int32_t *)(o + o_h1) + s0; O.h2 = (int32_t *)(o + o_h2) + s0; O.prob = (double *)(o + o_prob) + s0;
-		O.ld = n;
-		O.hap_bits = (const uint64_t *)d_base; O.hap_freq = (const double *)(d_base + m->oob_freq_at);
-		O.hap_off = (const int *)(d_base + m->oob_off_at); O.hla_start = (const int *)(d_base + m->oob_start_at);
-		m->timer.begin(HIBAG_HIP_K_PACK, st);
-		hibag_launch_pack(m->view, B, d_geno + (size_t)s0 * S, 0, nullptr, nullptr, m->ws_codes.as<uint8_t>(), st);
-		m->timer.end(st);
-		m->timer.begin(HIBAG_HIP_K_TOTAL, st, true);
-		hibag_launch_oob(m->view, B, m->ws_codes.as<uint8_t>(), O, force_rescan, m->side, st);
-		m->timer.end(st);
-		debug_stage("out-of-bag batch", st);
-	}
-	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipMemcpyAsync(H1, o + o_h1, C * n * 4, hipMemcpyDeviceToHost, st));
-	HIP_TRY(hipMemcpyAsync(H2, o + o_h2, C * n * 4, hipMemcpyDeviceToHost, st));
-	HIP_TRY(hipMemcpyAsync(prob, o + o_prob, C * n * 8, hipMemcpyDeviceToHost, st));
-	if (int rc = guard.leave()) return rc;
-	HIP_TRY(hipStreamSynchronize(st));
-	return 0;
-}
-
-// ---------------------------------------------------------------------------
-// A per-sample classifier mask (hibag_hip_predict_masked)
-
-// The inverted index SNP -> classifiers of the model on the device (HibagMaskView::user_off / user_cls): what
-// k_mask_counts walks.  Users are listed in model order.
-int mask_user_index(hibag_hip_model *m)
-{
-	if (m->mask_idx_ready) return 0;
-	const int S = std::max(m->n_snp, 0);
-	std::vector<int> tab((size_t)S + 1, 0);
-	for (const HostClassifier &k : m->cls) for (int v : k.snpidx) tab[(size_t)v + 1]++;
-	for (int v = 0; v < S; v++) tab[(size_t)v + 1] += tab[v];
-	const size_t n_user = (size_t)tab[S];
-	std::vector<int> at(tab.begin(), tab.end() - 1);
-	tab.resize((size_t)S + 1 + std::max<size_t>(n_user, 1), 0);
-	for (size_t c = 0; c < m->cls.size(); c++) for (int v : m->cls[c].snpidx) tab[(size_t)S + 1 + at[v]++] = (int)c;
-	if (int rc = m->mask_idx.reserve(tab.size() * sizeof(int))) return rc;
-	HIP_TRY(hipMemcpy(m->mask_idx.p, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice));
-	m->mask_idx_ready = true;
-	return 0;
-}
-
-// The whole call on the device, in the manner of predict_oob_locked (training cohorts are small): genotypes and mask up
-// once, batches of at most batch_limit samples (pack, the sub-models' weights, passes 1 and 2 or the vote, finish), the
-// outputs down once.  The entry runs it under with_handover_repair, as there.
-static int predict_masked_locked(hibag_hip_model *m, const int32_t *geno, int n_samp, const uint8_t *use, int vote_method,
-	const PredictOut &out)
-{
-	if (int rc = mask_user_index(m)) return rc;
-	StagedStreams *ss;
-	if (int rc = staged_streams(m, &ss)) return rc;
-	const hipStream_t st = ss->run;
-	const size_t C = (size_t)m->view.n_classifier, n = (size_t)n_samp, S = (size_t)m->n_snp, P = (size_t)m->view.n_cell,
-		nh = (size_t)m->n_hla;
-	const size_t o_h1 = 0, o_h2 = o_h1 + n * 4, o_mp = (o_h2 + n * 4 + 7) / 8 * 8, o_mt = o_mp + n * 8, o_ds = o_mt + n * 8,
-		o_pp = o_ds + (out.dosage ? n * nh * 8 : 0), out_bytes = o_pp + (out.postprob ? n * P * 8 : 0);
-	int lim = batch_limit(m);
-	if (const char *e = getenv("HIBAG_MASK_BATCH")) lim = std::min(lim, std::max(64, atoi(e)) / 64 * 64);     // (diagnostic: smaller batches)
-	const size_t pad_max = (size_t)round_up(std::min(lim, n_samp), HIBAG_WAVE);
-	if (int rc = m->ws_geno.reserve(std::max<size_t>(n * S * sizeof(int32_t), 4))) return rc;
-	if (int rc = m->ws_out.reserve(out_bytes)) return rc;
-	if (int rc = m->mask_use.reserve(std::max<size_t>(C * n, 1))) return rc;
-	if (int rc = m->mask_cnt.reserve(std::max<size_t>(S, 1) * pad_max * sizeof(int32_t))) return rc;
-	char *o = m->ws_out.as<char>();
-	PredictOut d;                              // the outputs asked for, on the device
-	if (out.H1) { d.H1 = (int32_t *)(o + o_h1); d.H2 = (int32_t *)(o + o_h2); }
-	if (out.max_prob) d.max_prob = (double *)(o + o_mp);
-	if (out.matching) d.matching = (double *)(o + o_mt);
-	if (out.dosage) d.dosage = (double *)(o + o_ds);
-	if (out.postprob) d.postprob = (double *)(o + o_pp);
-	const int32_t *d_geno = m->ws_geno.as<int32_t>();
-	if (int rc = workspace_enter(m, st)) return rc;
-	WorkspaceGuard guard{m, st};
-	guard.enqueued = true;
-	HIP_TRY(hipMemcpyAsync(m->ws_geno.p, geno, n * S * sizeof(int32_t), hipMemcpyHostToDevice, st));
-	HIP_TRY(hipMemcpyAsync(m->mask_use.p, use, C * n, hipMemcpyHostToDevice, st));
-	for (int s0 = 0; s0 < n_samp; s0 += lim) {
-		const int nb = std::min(lim, n_samp - s0);
-		HibagBatchView B;
-		if (int rc = make_batch(m, nb, vote_method == 2, B)) return rc;
-		HibagMaskView K;
-		K.use = m->mask_use.as<uint8_t>() + s0; K.ld = n;
-		K.user_off = m->mask_idx.as<int>(); K.user_cls = K.user_off + S + 1;
-		K.cnt = m->mask_cnt.as<int32_t>();
-		m->timer.begin(HIBAG_HIP_K_PACK, st);
-		hibag_launch_pack(m->view, B, d_geno + (size_t)s0 * S, 0, nullptr, nullptr, m->ws_codes.as<uint8_t>(), st);
-		hibag_launch_mask_weights(m->view, B, m->ws_codes.as<uint8_t>(), K, st);
-		m->timer.end(st);
-		run_core(m, B, vote_method, m->ws_part.as<double>(), st);
-		m->timer.begin(HIBAG_HIP_K_FINISH, st, true);
-		const PredictOut b = d.advanced((size_t)s0, nh, P);
-		hibag_launch_finish(m->view, B, B.part, b.H1, b.H2, b.max_prob, b.matching, b.dosage, b.postprob, st);
-		m->timer.end(st);
-		debug_stage("masked batch", st);
-	}
-	HIP_TRY(hipGetLastError());
-	if (out.H1) {
-		HIP_TRY(hipMemcpyAsync(out.H1, d.H1, n * 4, hipMemcpyDeviceToHost, st));
-		HIP_TRY(hipMemcpyAsync(out.H2, d.H2, n * 4, hipMemcpyDeviceToHost, st));
-	}
-	if (out.max_prob) HIP_TRY(hipMemcpyAsync(out.max_prob, d.max_prob, n * 8, hipMemcpyDeviceToHost, st));
-	if (out.matching) HIP_TRY(hipMemcpyAsync(out.matching, d.matching, n * 8, hipMemcpyDeviceToHost, st));
-	if (out.dosage) HIP_TRY(hipMemcpyAsync(out.dosage, d.dosage, n * nh * 8, hipMemcpyDeviceToHost, st));
-	if (out.postprob) HIP_TRY(hipMemcpyAsync(out.postprob, d.postprob, n * P * 8, hipMemcpyDeviceToHost, st));
-	if (int rc = guard.leave()) return rc;
-	HIP_TRY(hipStreamSynchronize(st));
-	return 0;
-}
-
 } // namespace hibag_detail
 
 // ===========================================================================
@@ -812,35 +635,6 @@ int hibag_hip_predict(hibag_hip_model *m, const int32_t *geno, int n_samp, int v
 	int32_t *H1, int32_t *H2, double *max_prob, double *matching, double *dosage, double *postprob)
 {
 	return predict_entry(m, geno, n_samp, vote_method, {H1, H2, max_prob, matching, dosage, postprob});
-}
-
-int hibag_hip_predict_oob(hibag_hip_model *m, const int32_t *geno, int n_samp, const int32_t *samp_num,
-	int32_t *H1, int32_t *H2, double *prob)
-{
-	if (!m) return hibag_fail(HIBAG_HIP_EINVAL, "model is NULL");
-	if (!m->finalized) return hibag_fail(HIBAG_HIP_ESTATE, "model not finalized");
-	if (n_samp < 0) return hibag_fail(HIBAG_HIP_EINVAL, "n_samp < 0");
-	if (n_samp > 0 && !geno) return hibag_fail(HIBAG_HIP_EINVAL, "geno is NULL");
-	if (n_samp > 0 && !samp_num) return hibag_fail(HIBAG_HIP_EINVAL, "samp_num is NULL");
-	if (n_samp > 0 && (!H1 || !H2 || !prob)) return hibag_fail(HIBAG_HIP_EINVAL, "H1, H2 and prob are all required");
-	if (!m->have_snpidx)
-		return hibag_fail(HIBAG_HIP_ESTATE, "model was built without SNP indices: raw genotypes cannot be packed");
-	if (n_samp == 0 || m->view.n_classifier == 0) return 0;
-	std::lock_guard<std::mutex> g(m->lock);
-	HIP_TRY(hipSetDevice(m->device));
-	return with_handover_repair(&m, 1, [&]() { return predict_oob_locked(m, geno, n_samp, samp_num, H1, H2, prob); });
-}
-
-int hibag_hip_predict_masked(hibag_hip_model *m, const int32_t *geno, int n_samp, const uint8_t *use, int vote_method,
-	int32_t *H1, int32_t *H2, double *max_prob, double *matching, double *dosage, double *postprob)
-{
-	if (int rc = check_predict_args(m, geno, n_samp, vote_method, H1, H2)) return rc;
-	if (n_samp > 0 && !use) return hibag_fail(HIBAG_HIP_EINVAL, "use is NULL");
-	if (n_samp == 0) return 0;
-	std::lock_guard<std::mutex> g(m->lock);
-	HIP_TRY(hipSetDevice(m->device));
-	const PredictOut out{H1, H2, max_prob, matching, dosage, postprob};
-	return with_handover_repair(&m, 1, [&]() { return predict_masked_locked(m, geno, n_samp, use, vote_method, out); });
 }
 
 // samples per batch of the device-pointer entries that take ONE batch (hibag_hip_predict_partial_device); 0 = not finalized

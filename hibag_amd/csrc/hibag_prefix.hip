@@ -44,17 +44,43 @@ static int prefix_layout(hibag_hip_model *m, hibag_hip_model **out)
 static int prefix_batch(const hibag_hip_model *L, int64_t sum_sizes, int n_sizes)
 {
 	const double per_sample = 8.0 * (double)sum_sizes + 12.0 * (double)n_sizes * std::max(L->view.n_tile, 1);
-	int lim = std::min<double>(batch_limit(L), 8e9 / per_sample);
-	if (const char *e = getenv("HIBAG_PREFIX_BATCH")) lim = std::min(lim, atoi(e));
-	return std::max(64, lim / 64 * 64);
+	const int lim = std::min<double>(batch_limit(L), 8e9 / per_sample);
+	return batch_cap("HIBAG_PREFIX_BATCH", std::max(64, lim / 64 * 64));
 }
 
+// The event pairs around every batch's k_prefix_accum on `st`.  The holder destroys them, and a run that fails on the way
+// still waits for the stream first.
+namespace {
+struct EventPairs {
+	hipStream_t st = nullptr;
+	std::vector<hipEvent_t> ev;
+	bool waited = false;                   // the stream has been synchronised behind the last record
+	int add(hipEvent_t &a, hipEvent_t &b)
+	{
+		for (hipEvent_t *e : {&a, &b}) { HIP_TRY(hipEventCreate(e)); ev.push_back(*e); }
+		return 0;
+	}
+	double ms() const
+	{
+		double sum = 0;
+		for (size_t i = 0; i + 1 < ev.size(); i += 2) {
+			float t = 0;
+			if (hipEventElapsedTime(&t, ev[i], ev[i + 1]) == hipSuccess) sum += t;
+		}
+		return sum;
+	}
+	~EventPairs()
+	{
+		if (!waited && st) (void)hipStreamSynchronize(st);
+		for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+	}
+};
+} // namespace
+
+// The whole call on the workspace of the layout L (WholeCall); the classifiers' SNP lists are read from the model itself.
 static int predict_prefix_locked(hibag_hip_model *m, hibag_hip_model *L, const int32_t *geno, int n_samp, const int32_t *sizes, int n_sizes,
 	int32_t *H1, int32_t *H2, double *prob, double *matching)
 {
-	StagedStreams *ss;
-	if (int rc = staged_streams(L, &ss)) return rc;
-	const hipStream_t st = ss->run;
 	const int C = L->view.n_classifier, S = L->n_snp, n_tile = L->view.n_tile;
 	const size_t n = (size_t)n_samp, K = (size_t)n_sizes;
 
@@ -76,68 +102,45 @@ static int predict_prefix_locked(hibag_hip_model *m, hibag_hip_model *L, const i
 	if (sum_sizes >= (int64_t)1 << 31) return hibag_fail(HIBAG_HIP_EINVAL, "sizes: too many classifiers in all");
 	const int lim = prefix_batch(L, sum_sizes, n_sizes);
 	const size_t pad_max = (size_t)round_up(std::min(lim, n_samp), HIBAG_WAVE);
-	if (int rc = L->pfx_tab.reserve(tab.size() * sizeof(int32_t))) return rc;
-	if (int rc = L->pfx_cw.reserve((size_t)sum_sizes * pad_max * sizeof(double))) return rc;
-	if (int rc = L->pfx_best.reserve(K * n_tile * pad_max * sizeof(double))) return rc;
-	if (int rc = L->pfx_cell.reserve(K * n_tile * pad_max * sizeof(int))) return rc;
-	const size_t o_h1 = 0, o_h2 = o_h1 + K * n * 4, o_prob = (o_h2 + K * n * 4 + 7) / 8 * 8, o_mt = o_prob + K * n * 8, out_bytes = o_mt + K * n * 8;
-	if (int rc = L->ws_geno.reserve(std::max<size_t>(n * S * sizeof(int32_t), 4))) return rc;
-	if (int rc = L->ws_out.reserve(out_bytes)) return rc;
-	char *o = L->ws_out.as<char>();
-	const int32_t *d_geno = L->ws_geno.as<int32_t>();
-	if (int rc = workspace_enter(L, st)) return rc;
-	WorkspaceGuard guard{L, st, true};
-	HIP_TRY(hipMemcpyAsync(L->pfx_tab.p, tab.data(), tab.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-	HIP_TRY(hipMemcpyAsync(L->ws_geno.p, geno, n * S * sizeof(int32_t), hipMemcpyHostToDevice, st));
+	WholeCall F(L);
+	EventPairs pairs;
+	const size_t i_tab = F.in.take(tab.size() * sizeof(int32_t));
+	// a batch's sub-model weights [sum of sizes][n_pad] and tile maxima with their cells [n_sizes][n_tile][n_pad]
+	const size_t x_cw = F.scratch.take((size_t)sum_sizes * pad_max * sizeof(double)), x_best = F.scratch.take(K * n_tile * pad_max * sizeof(double)),
+		x_cell = F.scratch.take(K * n_tile * pad_max * sizeof(int));
+	const size_t o_h1 = F.out.take(K * n * 4), o_h2 = F.out.take(K * n * 4), o_prob = F.out.take(K * n * 8), o_mt = F.out.take(K * n * 8);
+	if (int rc = F.open(n_samp)) return rc;
+	const hipStream_t st = pairs.st = F.st;
+	if (int rc = F.upload(F.in.at<char>(i_tab), tab.data(), tab.size() * sizeof(int32_t))) return rc;
+	if (int rc = F.upload_geno(geno)) return rc;
 
 	HibagPrefixView Q;
 	Q.n_sizes = n_sizes;
-	Q.sizes = L->pfx_tab.as<int>(); Q.row0 = Q.sizes + K; Q.snp_weight = Q.sizes + 2 * K;
-	Q.cw = L->pfx_cw.as<double>(); Q.pbest = L->pfx_best.as<double>(); Q.pcell = L->pfx_cell.as<int>();
+	Q.sizes = F.in.at<int>(i_tab); Q.row0 = Q.sizes + K; Q.snp_weight = Q.sizes + 2 * K;
+	Q.cw = F.scratch.at<double>(x_cw); Q.pbest = F.scratch.at<double>(x_best); Q.pcell = F.scratch.at<int>(x_cell);
 	Q.ld = n;
-	std::vector<hipEvent_t> ev;
-	int rc_loop = 0;
-	for (int s0 = 0; s0 < n_samp && !rc_loop; s0 += lim) {
-		const int nb = std::min(lim, n_samp - s0);
-		HibagBatchView B;
-		if ((rc_loop = make_batch(L, nb, false, B))) break;
-		Q.h1 = (int32_t *)(o + o_h1) + s0; Q.h2 = (int32_t *)(o + o_h2) + s0;
-		Q.prob = (double *)(o + o_prob) + s0; Q.matching = (double *)(o + o_mt) + s0;
-		L->timer.begin(HIBAG_HIP_K_PACK, st);
-		hibag_launch_pack(L->view, B, d_geno + (size_t)s0 * S, 0, nullptr, nullptr, L->ws_codes.as<uint8_t>(), st);
-		L->timer.end(st);
+	if (int rc = F.for_each_batch(n, (size_t)lim, false, [&](HibagBatchView &B, size_t s0, int) {
+		Q.h1 = F.out.at<int32_t>(o_h1) + s0; Q.h2 = F.out.at<int32_t>(o_h2) + s0;
+		Q.prob = F.out.at<double>(o_prob) + s0; Q.matching = F.out.at<double>(o_mt) + s0;
+		enqueue_pack(L, B, F.geno, (int)s0, st);
 		L->timer.begin(HIBAG_HIP_K_TOTAL, st, true);
 		hibag_launch_total(L->view, B, st, L->side, false);
 		L->timer.end(st);
 		const unsigned n_group = (unsigned)(B.n_pad / HIBAG_WAVE);
 		hipLaunchKernelGGL(k_prefix_weights, dim3(n_group, C), dim3(64), 0, st, L->view, B, Q, (const uint8_t *)L->ws_codes.as<uint8_t>());
 		hipEvent_t a, b;
-		if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) { rc_loop = hibag_fail(HIBAG_HIP_ENODEV, "hipEventCreate failed"); break; }
-		ev.push_back(a); ev.push_back(b);
+		if (int rc = pairs.add(a, b)) return rc;
 		(void)hipEventRecord(a, st);
 		const unsigned n_sq = (unsigned)((n_sizes + PREFIX_WAVES - 1) / PREFIX_WAVES);
 		hipLaunchKernelGGL(k_prefix_accum, dim3(8u * ((n_group + 7) / 8) * (unsigned)n_tile * n_sq), dim3(PREFIX_WAVES * HIBAG_WAVE), 0, st, L->view, B, Q);
 		(void)hipEventRecord(b, st);
 		hipLaunchKernelGGL(k_prefix_finish, dim3(n_group, n_sizes), dim3(64), 0, st, L->view, B, Q);
-	}
-	auto drop_events = [&]() { for (hipEvent_t e : ev) (void)hipEventDestroy(e); ev.clear(); };
-	if (rc_loop) { (void)hipStreamSynchronize(st); drop_events(); return rc_loop; }
-	hipError_t e = hipGetLastError();
-	if (e == hipSuccess) e = hipMemcpyAsync(H1, o + o_h1, K * n * 4, hipMemcpyDeviceToHost, st);
-	if (e == hipSuccess) e = hipMemcpyAsync(H2, o + o_h2, K * n * 4, hipMemcpyDeviceToHost, st);
-	if (e == hipSuccess) e = hipMemcpyAsync(prob, o + o_prob, K * n * 8, hipMemcpyDeviceToHost, st);
-	if (e == hipSuccess) e = hipMemcpyAsync(matching, o + o_mt, K * n * 8, hipMemcpyDeviceToHost, st);
-	const int rc_leave = guard.leave();
-	if (e == hipSuccess) e = hipStreamSynchronize(st);
-	double ms = 0;
-	for (size_t i = 0; i + 1 < ev.size() && e == hipSuccess; i += 2) {
-		float t = 0;
-		if (hipEventElapsedTime(&t, ev[i], ev[i + 1]) == hipSuccess) ms += t;
-	}
-	drop_events();
-	if (e != hipSuccess) return hibag_fail(HIBAG_HIP_ENODEV, "hibag_hip_predict_prefix failed: %s", hipGetErrorString(e));
-	if (rc_leave) return rc_leave;
-	m->pfx_accum_ms = ms;                      // (only a completed run sets it; a repair's second run sets it again)
+		return 0;
+	})) return rc;
+	if (int rc = F.close({{H1, F.out.at<char>(o_h1), K * n * 4}, {H2, F.out.at<char>(o_h2), K * n * 4}, {prob, F.out.at<char>(o_prob), K * n * 8},
+		{matching, F.out.at<char>(o_mt), K * n * 8}})) return rc;
+	pairs.waited = true;
+	m->pfx_accum_ms = pairs.ms();              // (only a completed run sets it; a repair's second run sets it again)
 	return 0;
 }
 

@@ -4,8 +4,10 @@ tallies equal as integers, the base rows equal to predict_oob, and hlaSNPImporta
 import numpy as np
 import pytest
 
+import curve_reference as CR
 import hibag_amd as hb
 import importance_reference as ref
+import masked_reference as MR
 from conftest import align_geno
 from hibag_amd import NA_INTEGER, synth
 
@@ -105,8 +107,13 @@ def test_engine_mix(mix, monkeypatch):
     dev = hb.hlaModelFromObj(model)
     before = dev.predict_raw(G, want_dosage=False)             # the whole model first: stale rows in the workspace
     oob_before = dev.predict_oob(G, sn)
+    # the other whole-call entries share the knock-out's input and output arenas and its SNP-users index: what they return
+    # before the knock-out runs, between its runs and after them is the same, bit for bit
+    use = np.random.default_rng(10).integers(0, 2, (len(model.classifiers), G.shape[0])).astype(np.uint8)
+    shared = lambda: (dev.predict_masked(G, use, want_dosage=True, want_prob=True), dev.predict_prefix(G, [1, 5, 12]))
+    shared_runs = [shared()]
     runs = []
-    for env in ({"HIBAG_KNOCK_BATCH": "128"}, {}, {"HIBAG_OOB_RESCAN": "1"}):
+    for i, env in enumerate(({"HIBAG_KNOCK_BATCH": "128"}, {}, {"HIBAG_OOB_RESCAN": "1"})):
         with monkeypatch.context() as mp:
             for k, v in env.items():
                 mp.setenv(k, v)
@@ -115,9 +122,17 @@ def test_engine_mix(mix, monkeypatch):
         between = dev.predict_raw(G, want_dosage=False)
         for k in ("h1", "h2", "prob", "matching"):
             assert np.array_equal(between[k], before[k], equal_nan=True), k
+        if i == 0:
+            shared_runs.append(shared())
+    shared_runs.append(shared())
     oob_after = dev.predict_oob(G, sn)
     assert dev.handover_faults() == 0 and dev.status() == 0
     dev.close()
+    # (bit for bit: the same 64 bits, or NaN in both -- the sample without a SNP has NaN in matching, dosage and posterior)
+    for i, (masked, prefix) in enumerate(shared_runs[1:], 1):
+        assert set(masked) == set(MR.KEYS) and set(prefix) == set(CR.KEYS)
+        MR.same_bits(masked, shared_runs[0][0], f"predict_masked, call {i}")
+        CR.assert_curve_equal(prefix, shared_runs[0][1], f"predict_prefix, call {i}")
     for got in runs:
         _assert_raw(got, raw)
         assert np.array_equal(got["tally"], want_tally)
