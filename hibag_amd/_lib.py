@@ -62,6 +62,8 @@ EXPORTS = [
     "hibag_hip_assoc_new", "hibag_hip_assoc_free", "hibag_hip_assoc_n_tests", "hibag_hip_assoc_observed",
     "hibag_hip_assoc_permute", "hibag_hip_assoc_labels",
     "hibag_hip_assoc_n_kept", "hibag_hip_assoc_feature_rows", "hibag_hip_assoc_glm",
+    "hibag_hip_assoc_quant_new", "hibag_hip_assoc_quant_free", "hibag_hip_assoc_quant_classes", "hibag_hip_assoc_quant_observed",
+    "hibag_hip_assoc_quant_permute", "hibag_hip_assoc_quant_perm_rows", "hibag_hip_assoc_quant_gram_ms",
     "hibag_hip_oob_knock_variants", "hibag_hip_oob_knock",
     "hibag_hip_test_layout_plan", "hibag_hip_test_layout_count", "hibag_hip_test_layout_get", "hibag_hip_test_layout_free",
     "hibag_hip_test_set_chunking", "hibag_hip_test_last_launch", "hibag_hip_test_plan_total", "hibag_hip_test_plan_accum",
@@ -191,6 +193,16 @@ def lib() -> C.CDLL:
         L.hibag_hip_assoc_n_kept.argtypes = [vp]
         L.hibag_hip_assoc_feature_rows.argtypes = [vp, i32, i32, vp]
         L.hibag_hip_assoc_glm.argtypes = [vp, vp, i32, vp, i32, C.c_double, vp, vp, vp, vp, vp]
+    if hasattr(L, "hibag_hip_assoc_quant_new"):
+        L.hibag_hip_assoc_quant_new.argtypes = [vp, vp, vp, i32]
+        L.hibag_hip_assoc_quant_new.restype = vp
+        L.hibag_hip_assoc_quant_free.argtypes = [vp]
+        L.hibag_hip_assoc_quant_free.restype = None
+        L.hibag_hip_assoc_quant_classes.argtypes = [vp, vp, vp, vp, vp]
+        L.hibag_hip_assoc_quant_observed.argtypes = [vp, vp, vp, vp, vp, vp]
+        L.hibag_hip_assoc_quant_permute.argtypes = [vp, C.c_uint64, C.c_uint64, i64, vp, vp]
+        L.hibag_hip_assoc_quant_perm_rows.argtypes = [vp, C.c_uint64, C.c_uint64, i32, vp]
+        L.hibag_hip_assoc_quant_gram_ms.argtypes = [vp, C.POINTER(dbl)]
     if hasattr(L, "hibag_hip_cohort_new"):
         # (an older build selected with HIBAG_HIP_LIBRARY, e.g. the parent commit's for a baseline timing, lacks the cohort
         # entries: everything else still binds, and a call that needs them fails with AttributeError)

@@ -9,8 +9,9 @@ of case carriers, a dot product over samples; all tests under all permutations a
 (``hibag_hip_assoc_*``) with exact integer sums.  The result is defined exactly and does not depend
 on panel sizes or on how the permutations are split over calls.
 
-Not built: quantitative traits (R's t-test and ANOVA columns) and ``fisher_p`` of the ``genotype`` model (R's 3 x 2 network
-algorithm), which stays NaN.  The ``glm`` regression with covariates and ``use.prob`` is ``hlaAssocGlm`` (assocglm.py)."""
+Not built: ``fisher_p`` of the ``genotype`` model (R's 3 x 2 network algorithm), which stays NaN.  The ``glm`` regression
+with covariates and ``use.prob`` is ``hlaAssocGlm`` (assocglm.py); quantitative traits (R's t-test and ANOVA columns) are
+``hlaAssocQuant`` (assocquant.py)."""
 
 from __future__ import annotations
 
@@ -272,8 +273,8 @@ def hlaAssocTest(hla: HlaAlleleClass, y: Sequence, model: str = "dominant", prob
       when ``None``): ``perm_p[t] = (1 + #{p: stat[t][p] >= stat[t]}) / (n_perm + 1)`` and the family-wise
       ``perm_p_adj[t]`` with the permutation's largest statistic over all tests in place of ``stat[t][p]``.
 
-    Not built: quantitative traits, and ``fisher_p`` for the ``genotype`` model, which is NaN; the ``glm`` regression with
-    covariates and ``use.prob`` is ``hlaAssocGlm``.  The statistics, the generator and the counts are defined in DESIGN.md
+    Not built: ``fisher_p`` for the ``genotype`` model, which is NaN; the ``glm`` regression with covariates and ``use.prob``
+    is ``hlaAssocGlm``, a quantitative trait ``hlaAssocQuant``.  The statistics, the generator and the counts are defined in DESIGN.md
     section 20."""
     if model not in MODELS:
         raise ValueError("'arg' should be one of " + ", ".join(f'"{m}"' for m in MODELS))

@@ -8,8 +8,9 @@ confidence interval and Wald p-value per ``h`` column, and a likelihood-ratio te
 covariates; they run on the device (``hibag_hip_assoc_glm``), one workgroup per fit, with ``X'WX`` and ``X'Wz`` of every
 iteration as one 16 x 16 FP64 matrix-core tile.  The fit is R's ``glm.fit`` restated.
 
-Not built: quantitative traits and other ``family`` values, the t-test and ANOVA columns, permutation p-values for the
-regression, R's step halving, interaction terms, and ``fisher_p`` of the genotype model."""
+Not built: other ``family`` values (a quantitative trait with the t-test and ANOVA columns is ``hlaAssocQuant``,
+assocquant.py), permutation p-values for this regression, R's step halving, interaction terms, and ``fisher_p`` of the
+genotype model."""
 
 from __future__ import annotations
 
@@ -147,7 +148,7 @@ def hlaAssocGlm(hla: HlaAlleleClass, y: Sequence, covariates=None, model: str = 
     re-base the factor, which is not mirrored: the test has bit 1.  The likelihood-ratio columns are NaN unless both the fit
     and the base model converged.  A rank-deficient base model is a ValueError.
 
-    Not built: quantitative traits and other families, the t-test and ANOVA columns, permutation p-values for the
+    Not built: other families (a quantitative trait: ``hlaAssocQuant``), permutation p-values for this
     regression, R's step halving (with the clamps of section 23 the deviance is always finite), interaction terms, and
     ``fisher_p`` of the genotype model.  (``_backend``: the tests' seam -- a class with the interface of ``_DeviceGlm`` that
     stands in for the device.)"""

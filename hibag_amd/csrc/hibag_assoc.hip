@@ -10,10 +10,14 @@
 // hibag_hip_assoc_glm (hlaAssocGlm; kernels: hibag_k_glm.h) fits one logistic regression per test on
 // the same feature rows, with the kept samples' labels that the handle keeps in `y` (the `labels` panel is overwritten by
 // every permutation call).
+//
+// hibag_hip_assoc_quant_* (hlaAssocQuant; kernels: hibag_k_quant.h) test a quantitative trait on the
+// same feature rows, through a handle of their own that borrows this one; they are at the end of the file.
 
 #include "hibag_internal.h"
 #include "hibag_k_assoc.h"
 #include "hibag_k_glm.h"
+#include "hibag_k_quant.h"
 
 using hibag_detail::DevBuf;
 
@@ -369,6 +373,351 @@ int hibag_hip_assoc_glm(hibag_hip_assoc *h, const double *covar, int n_covar, co
 	HIP_TRY(hipMemcpyAsync(iterations, d_it, sizeof(int32_t) * (size_t)n_fit, hipMemcpyDeviceToHost, h->st));
 	HIP_TRY(hipMemcpyAsync(flags, d_fl, sizeof(int32_t) * (size_t)n_fit, hipMemcpyDeviceToHost, h->st));
 	HIP_TRY(hipStreamSynchronize(h->st));
+	return 0;
+}
+
+} // extern "C"
+
+// ---- hlaAssocQuant (kernels: hibag_k_quant.h) ---------------------------------------------------
+// A quantitative trait on the tests of an association handle.  hibag_hip_assoc_quant_new orthonormalises the basis (the
+// constant and the covariates) and takes the residual trait on the host, uploads both, and has the device sum the classes,
+// project the feature rows on the basis and run the observed trait -- permutation 0, the identity -- through the kernels of
+// the permutations.  hibag_hip_assoc_quant_permute then works in panels of permutations: rows (k_quant_perm), residual panel
+// and rr (k_quant_project), one FP64 Gram features x residuals (k_quant_gram), one pass over it (k_quant_stat).  The handle
+// borrows the association handle: its feature rows, its stream, its one-host-thread rule.
+
+struct hibag_hip_quant {
+	hibag_hip_assoc *h = nullptr;                // borrowed; outlives this handle
+	int nb = 0;                                  // basis rows: the constant and the covariates
+	double ybar = 0, h_rr = 0, gram_ms = 0;
+	DevBuf basis, yt, yc, tests, stat_obs;       // double [nb][kp], [kp], [kp]; QuantTest [n_test]; double [n_test]
+	DevBuf perm, panel, rr, gram, max_stat, count; // per-call panel: int32 [pp][kp], double [pp / 16][kp / 4][64], [pp], [rows][pp]; double [n_perm]; uint64 [n_test]
+	std::vector<int64_t> h_cnt;                  // [n_test][3]
+	std::vector<double> h_S1, h_S2, h_proj, h_g, h_stat; // [n_test][3] twice, [rows][nb], [rows], [n_test]
+	std::vector<int32_t> h_flags;                // [n_test]
+	std::vector<hipEvent_t> ev;                  // pairs around the Gram launches of the last permutation call
+
+	~hibag_hip_quant()
+	{
+		if (!h) return;
+		(void)hipSetDevice(h->device);
+		if (h->st) (void)hipStreamSynchronize(h->st);
+		for (DevBuf *b : {&basis, &yt, &yc, &tests, &stat_obs, &perm, &panel, &rr, &gram, &max_stat, &count}) b->release();
+		for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+	}
+};
+
+namespace {
+
+constexpr size_t kQuantPanelBytes = (size_t)256 << 20;   // default size of a panel's residual operand
+
+// permutations of one panel, in whole tiles: HIBAG_QUANT_PANEL_PERMS (read per call), else about kQuantPanelBytes of residuals
+int quant_panel_perms(const hibag_hip_quant *q, int64_t n_perm)
+{
+	const char *e = getenv("HIBAG_QUANT_PANEL_PERMS");
+	long pp = e && *e ? strtol(e, nullptr, 10) : 0;
+	if (pp <= 0) pp = (long)(kQuantPanelBytes / (sizeof(double) * (size_t)q->h->kp));
+	pp = std::min<long>(pp, 1 << 22);
+	pp = std::max<long>(pp / QUANT_TILE * QUANT_TILE, QUANT_TILE);
+	return (int)std::min<int64_t>(pp, (n_perm + QUANT_TILE - 1) / QUANT_TILE * QUANT_TILE);
+}
+
+int quant_reserve_panel(hibag_hip_quant *q, int pp)
+{
+	const hibag_hip_assoc *h = q->h;
+	if (q->perm.reserve(sizeof(int32_t) * (size_t)pp * h->kp) || q->panel.reserve(sizeof(double) * (size_t)pp * h->kp) ||
+		q->rr.reserve(sizeof(double) * (size_t)pp) || q->gram.reserve(sizeof(double) * (size_t)h->rows * pp))
+		return HIBAG_HIP_ENOMEM;
+	return 0;
+}
+
+// permutations p0 .. p0 + n_lab - 1 (n_lab <= the reserved panel) through the four kernels; the Gram has row stride ldc
+int quant_enqueue_panel(hibag_hip_quant *q, uint64_t seed, uint64_t p0, int n_lab, size_t ldc, double *stat_out, double *max_out,
+	const double *stat_obs, unsigned long long *count, hipEvent_t e0, hipEvent_t e1)
+{
+	hibag_hip_assoc *h = q->h;
+	const int n = h->D.n, kp = h->kp, tiles = (n_lab + QUANT_TILE - 1) / QUANT_TILE;
+	hipLaunchKernelGGL(k_quant_perm, dim3((n_lab + 63) / 64), dim3(64), 0, h->st, n, kp, seed, p0, n_lab, q->perm.as<int32_t>());
+	hipLaunchKernelGGL(k_quant_project, dim3(tiles), dim3(256), 0, h->st, q->perm.as<int32_t>(), kp, n_lab, n, kp, q->yt.as<double>(),
+		q->basis.as<double>(), q->nb, q->panel.as<double>(), q->rr.as<double>());
+	if (e0) HIP_TRY(hipEventRecord(e0, h->st));
+	hipLaunchKernelGGL(k_quant_gram, dim3(tiles, (h->rows + QUANT_TILE - 1) / QUANT_TILE), dim3(QUANT_GRAM_WAVES * 64), 0, h->st,
+		h->feat.as<int8_t>(), h->rows, kp, q->panel.as<double>(), q->gram.as<double>(), ldc);
+	if (e1) HIP_TRY(hipEventRecord(e1, h->st));
+	hipLaunchKernelGGL(k_quant_stat, dim3((n_lab + 63) / 64), dim3(64), 0, h->st, q->gram.as<double>(), ldc, q->rr.as<double>(), n_lab,
+		q->tests.as<QuantTest>(), h->D.n_test, stat_out, max_out, stat_obs, count);
+	HIP_TRY(hipGetLastError());
+	return 0;
+}
+
+// the basis: the constant, then the covariates, orthonormalised by modified Gram-Schmidt applied twice.  Returns the column
+// that is in the span of the earlier ones, or -1.
+int quant_orthonormalise(const double *covar, int n, int nb, std::vector<double> &Q)
+{
+	Q.assign((size_t)nb * n, 0.0);
+	std::vector<double> v((size_t)n);
+	for (int k = 0; k < nb; k++) {
+		double zz = 0.0;
+		for (int i = 0; i < n; i++) {
+			v[i] = k == 0 ? 1.0 : covar[(size_t)(k - 1) * n + i];
+			zz += v[i] * v[i];
+		}
+		for (int pass = 0; pass < 2; pass++)
+			for (int j = 0; j < k; j++) {
+				const double *qj = &Q[(size_t)j * n];
+				double c = 0.0;
+				for (int i = 0; i < n; i++) c += qj[i] * v[i];
+				for (int i = 0; i < n; i++) v[i] -= c * qj[i];
+			}
+		double ss = 0.0;
+		for (int i = 0; i < n; i++) ss += v[i] * v[i];
+		const double s = sqrt(ss);
+		if (!(s > 1e-9 * sqrt(zz))) return k;
+		for (int i = 0; i < n; i++) Q[(size_t)k * n + i] = v[i] / s;
+	}
+	return -1;
+}
+
+// the tests' constants from the class counts and the projections
+void quant_tests(const hibag_hip_quant *q, std::vector<QuantTest> &tests, std::vector<int32_t> &flags)
+{
+	const hibag_hip_assoc *h = q->h;
+	const int T = h->D.n_test, nb = q->nb;
+	const int64_t n = h->D.n;
+	const double nan = std::nan("");
+	auto sum_sq = [&](int row) {
+		double a = 0.0;
+		for (int k = 0; k < nb; k++) a += q->h_proj[(size_t)row * nb + k] * q->h_proj[(size_t)row * nb + k];
+		return a;
+	};
+	tests.assign((size_t)T, QuantTest{-1, -1, nan, nan, nan, nan, nan});
+	flags.assign((size_t)T, QUANT_FLAG_RANK);
+	for (int t = 0; t < T; t++) {
+		const int64_t *c = &q->h_cnt[(size_t)t * 3];
+		QuantTest &qt = tests[(size_t)t];
+		int row = t;
+		double xx;
+		if (h->D.model == ASSOC_GENOTYPE) {
+			if ((c[1] == 0 && c[2] == 0) || c[0] == 0) continue;
+			if (c[1] > 0 && c[2] > 0) {
+				const double xx1 = (double)c[1], xx2 = (double)c[2];
+				const double a11 = xx1 - sum_sq(2 * t), a22 = xx2 - sum_sq(2 * t + 1);
+				double a = 0.0;
+				for (int k = 0; k < nb; k++) a += q->h_proj[(size_t)(2 * t) * nb + k] * q->h_proj[(size_t)(2 * t + 1) * nb + k];
+				const double a12 = -a;
+				if (!(a11 > 1e-11 * xx1) || !(a22 > 1e-11 * xx2)) continue;
+				const double det = a11 * a22 - a12 * a12;
+				if (!(det > 1e-11 * (a11 * a22))) continue;
+				qt = QuantTest{2 * t, 2 * t + 1, (double)(n - nb - 2), a11, a22, a12, det};
+				flags[(size_t)t] = 0;
+				continue;
+			}
+			row = c[1] > 0 ? 2 * t : 2 * t + 1;
+			xx = (double)(c[1] + c[2]);
+		} else {
+			if (c[0] == n || c[1] == n || c[2] == n) continue;
+			xx = (double)(c[1] + 4 * c[2]);
+		}
+		const double sxx = xx - sum_sq(row);
+		if (!(sxx > 1e-11 * xx)) continue;
+		qt = QuantTest{row, -1, (double)(n - nb - 1), sxx, nan, nan, nan};
+		flags[(size_t)t] = 0;
+	}
+}
+
+// what hibag_hip_assoc_quant_new does on the device
+int quant_build(hibag_hip_quant *q, const std::vector<double> &Q, const std::vector<double> &yt, const std::vector<double> &yc)
+{
+	hibag_hip_assoc *h = q->h;
+	const int n = h->D.n, kp = h->kp, T = h->D.n_test, rows = h->rows, nb = q->nb;
+	HIP_TRY(hipSetDevice(h->device));
+	DevBuf d_cls, d_proj;                        // int64 [T][3] and double [T][3] twice; double [rows][nb]
+	struct Release { DevBuf &a, &b; ~Release() { a.release(); b.release(); } } rel{d_cls, d_proj};
+	if (q->basis.reserve(sizeof(double) * (size_t)nb * kp) || q->yt.reserve(sizeof(double) * (size_t)kp) ||
+		q->yc.reserve(sizeof(double) * (size_t)kp) || q->tests.reserve(sizeof(QuantTest) * (size_t)T) ||
+		q->stat_obs.reserve(sizeof(double) * (size_t)T) || d_cls.reserve((size_t)T * 3 * (sizeof(long long) + 2 * sizeof(double))) ||
+		d_proj.reserve(sizeof(double) * (size_t)rows * nb) || quant_reserve_panel(q, QUANT_TILE))
+		return HIBAG_HIP_ENOMEM;
+	std::vector<double> img((size_t)(nb + 2) * kp, 0.0);      // the padded rows: basis, residual trait, centred trait
+	for (int k = 0; k < nb; k++) std::copy(&Q[(size_t)k * n], &Q[(size_t)k * n] + n, &img[(size_t)k * kp]);
+	std::copy(yt.begin(), yt.end(), &img[(size_t)nb * kp]);
+	std::copy(yc.begin(), yc.end(), &img[(size_t)(nb + 1) * kp]);
+	HIP_TRY(hipMemcpyAsync(q->basis.p, img.data(), sizeof(double) * (size_t)nb * kp, hipMemcpyHostToDevice, h->st));
+	HIP_TRY(hipMemcpyAsync(q->yt.p, &img[(size_t)nb * kp], sizeof(double) * (size_t)kp, hipMemcpyHostToDevice, h->st));
+	HIP_TRY(hipMemcpyAsync(q->yc.p, &img[(size_t)(nb + 1) * kp], sizeof(double) * (size_t)kp, hipMemcpyHostToDevice, h->st));
+	long long *d_cnt = d_cls.as<long long>();
+	double *d_S1 = (double *)(d_cnt + (size_t)T * 3), *d_S2 = d_S1 + (size_t)T * 3;
+	hipLaunchKernelGGL(k_quant_classes, dim3(T), dim3(256), 0, h->st, h->feat.as<int8_t>(), kp, n, h->D.model == ASSOC_GENOTYPE ? 1 : 0,
+		q->yc.as<double>(), d_cnt, d_S1, d_S2);
+	hipLaunchKernelGGL(k_quant_proj, dim3(rows), dim3(256), 0, h->st, h->feat.as<int8_t>(), kp, n, q->basis.as<double>(), nb,
+		d_proj.as<double>());
+	HIP_TRY(hipGetLastError());
+	q->h_cnt.resize((size_t)T * 3); q->h_S1.resize((size_t)T * 3); q->h_S2.resize((size_t)T * 3);
+	q->h_proj.resize((size_t)rows * nb); q->h_g.resize((size_t)rows); q->h_stat.resize((size_t)T);
+	static_assert(sizeof(long long) == sizeof(int64_t), "the counts are copied as they are");
+	HIP_TRY(hipMemcpyAsync(q->h_cnt.data(), d_cnt, sizeof(int64_t) * (size_t)T * 3, hipMemcpyDeviceToHost, h->st));
+	HIP_TRY(hipMemcpyAsync(q->h_S1.data(), d_S1, sizeof(double) * (size_t)T * 3, hipMemcpyDeviceToHost, h->st));
+	HIP_TRY(hipMemcpyAsync(q->h_S2.data(), d_S2, sizeof(double) * (size_t)T * 3, hipMemcpyDeviceToHost, h->st));
+	HIP_TRY(hipMemcpyAsync(q->h_proj.data(), d_proj.p, sizeof(double) * (size_t)rows * nb, hipMemcpyDeviceToHost, h->st));
+	HIP_TRY(hipStreamSynchronize(h->st));
+
+	std::vector<QuantTest> tests;
+	quant_tests(q, tests, q->h_flags);
+	HIP_TRY(hipMemcpyAsync(q->tests.p, tests.data(), sizeof(QuantTest) * (size_t)T, hipMemcpyHostToDevice, h->st));
+	// the observed trait: permutation 0, a panel of its own
+	int e = quant_enqueue_panel(q, 0, 0, 1, QUANT_TILE, q->stat_obs.as<double>(), nullptr, nullptr, nullptr, nullptr, nullptr);
+	if (e) { (void)hipStreamSynchronize(h->st); return e; }
+	HIP_TRY(hipMemcpy2DAsync(q->h_g.data(), sizeof(double), q->gram.p, sizeof(double) * QUANT_TILE, sizeof(double), (size_t)rows,
+		hipMemcpyDeviceToHost, h->st));
+	HIP_TRY(hipMemcpyAsync(&q->h_rr, q->rr.p, sizeof(double), hipMemcpyDeviceToHost, h->st));
+	HIP_TRY(hipMemcpyAsync(q->h_stat.data(), q->stat_obs.p, sizeof(double) * (size_t)T, hipMemcpyDeviceToHost, h->st));
+	HIP_TRY(hipStreamSynchronize(h->st));
+	return 0;
+}
+
+} // namespace
+
+extern "C" {
+
+hibag_hip_quant *hibag_hip_assoc_quant_new(hibag_hip_assoc *h, const double *y, const double *covar, int n_covar)
+{
+	if (!h || !y) { hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_quant_new: null handle or y"); return nullptr; }
+	if (n_covar < 0 || n_covar > HIBAG_HIP_GLM_MAX_COVAR || (n_covar > 0 && !covar)) {
+		hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_quant_new: %d covariates; 0 .. %d, with covar", n_covar, HIBAG_HIP_GLM_MAX_COVAR);
+		return nullptr;
+	}
+	static_assert(QUANT_MAX_BASIS == HIBAG_HIP_GLM_MAX_COVAR + 1, "the constant and the covariates");
+	const int n = h->D.n, nb = n_covar + 1;
+	for (int i = 0; i < n; i++)
+		if (!std::isfinite(y[i])) { hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_quant_new: y of kept sample %d is not finite", i); return nullptr; }
+	for (size_t i = 0; i < (size_t)n_covar * n; i++)
+		if (!std::isfinite(covar[i])) {
+			hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_quant_new: covariate %zu of kept sample %zu is not finite", i / n, i % n);
+			return nullptr;
+		}
+	const int d = h->D.model == ASSOC_GENOTYPE ? 2 : 1;
+	if (n - nb - d < 1) {
+		hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_quant_new: %d kept samples leave %d residual degrees of freedom with %d covariates; "
+			"at least 1", n, n - nb - d, n_covar);
+		return nullptr;
+	}
+	std::vector<double> Q;
+	const int bad = quant_orthonormalise(covar, n, nb, Q);
+	if (bad >= 0) {
+		hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_quant_new: the covariates are collinear (column %d lies in the span of the constant "
+			"and the columns before it)", bad - 1);
+		return nullptr;
+	}
+	// the residual trait and the centred trait
+	std::vector<double> yt(y, y + n), yc((size_t)n);
+	for (int k = 0; k < nb; k++) {
+		const double *qk = &Q[(size_t)k * n];
+		double c = 0.0;
+		for (int i = 0; i < n; i++) c += qk[i] * yt[i];
+		for (int i = 0; i < n; i++) yt[i] -= c * qk[i];
+	}
+	double sum = 0.0;
+	for (int i = 0; i < n; i++) sum += y[i];
+	hibag_hip_quant *q = new (std::nothrow) hibag_hip_quant;
+	if (!q) { hibag_fail(HIBAG_HIP_ENOMEM, "out of host memory"); return nullptr; }
+	q->h = h;
+	q->nb = nb;
+	q->ybar = sum / (double)n;
+	for (int i = 0; i < n; i++) yc[i] = y[i] - q->ybar;
+	if (quant_build(q, Q, yt, yc) != 0) { delete q; return nullptr; }
+	return q;
+}
+
+void hibag_hip_assoc_quant_free(hibag_hip_quant *q) { delete q; }
+
+int hibag_hip_assoc_quant_classes(hibag_hip_quant *q, int64_t *cnt, double *S1, double *S2, double *ybar)
+{
+	if (!q || !cnt || !S1 || !S2 || !ybar) return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_quant_classes: null argument");
+	std::copy(q->h_cnt.begin(), q->h_cnt.end(), cnt);
+	std::copy(q->h_S1.begin(), q->h_S1.end(), S1);
+	std::copy(q->h_S2.begin(), q->h_S2.end(), S2);
+	*ybar = q->ybar;
+	return 0;
+}
+
+int hibag_hip_assoc_quant_observed(hibag_hip_quant *q, double *proj, double *g, double *rr, double *stat, int32_t *flags)
+{
+	if (!q || !proj || !g || !rr || !stat || !flags) return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_quant_observed: null argument");
+	std::copy(q->h_proj.begin(), q->h_proj.end(), proj);
+	std::copy(q->h_g.begin(), q->h_g.end(), g);
+	*rr = q->h_rr;
+	std::copy(q->h_stat.begin(), q->h_stat.end(), stat);
+	std::copy(q->h_flags.begin(), q->h_flags.end(), flags);
+	return 0;
+}
+
+int hibag_hip_assoc_quant_permute(hibag_hip_quant *q, uint64_t seed, uint64_t perm0, int64_t n_perm, double *max_stat, int64_t *count_point)
+{
+	if (!q || n_perm < 0 || !count_point || (n_perm > 0 && !max_stat))
+		return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_quant_permute: null argument or n_perm < 0");
+	if (perm0 < 1 || perm0 + (uint64_t)n_perm < perm0)
+		return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_quant_permute: permutations are numbered from 1 (0 is the observed trait) and stay below 2^64");
+	hibag_hip_assoc *h = q->h;
+	const int T = h->D.n_test;
+	std::fill(count_point, count_point + T, (int64_t)0);
+	q->gram_ms = 0;
+	if (n_perm == 0) return 0;
+	HIP_TRY(hipSetDevice(h->device));
+	const int pp = quant_panel_perms(q, n_perm);
+	const size_t n_panel = (size_t)((n_perm + pp - 1) / pp);
+	if (quant_reserve_panel(q, pp) || q->max_stat.reserve(sizeof(double) * (size_t)n_perm) ||
+		q->count.reserve(sizeof(unsigned long long) * (size_t)T))
+		return HIBAG_HIP_ENOMEM;
+	while (q->ev.size() < 2 * n_panel) {
+		hipEvent_t e;
+		HIP_TRY(hipEventCreate(&e));
+		q->ev.push_back(e);
+	}
+	HIP_TRY(hipMemsetAsync(q->count.p, 0, sizeof(unsigned long long) * (size_t)T, h->st));
+	size_t k = 0;
+	for (int64_t done = 0; done < n_perm; done += pp, k++) {
+		const int n_lab = (int)std::min<int64_t>(pp, n_perm - done);
+		int e = quant_enqueue_panel(q, seed, perm0 + (uint64_t)done, n_lab, (size_t)pp, nullptr, q->max_stat.as<double>() + done,
+			q->stat_obs.as<double>(), q->count.as<unsigned long long>(), q->ev[2 * k], q->ev[2 * k + 1]);
+		if (e) { (void)hipStreamSynchronize(h->st); return e; }
+	}
+	HIP_TRY(hipMemcpyAsync(max_stat, q->max_stat.p, sizeof(double) * (size_t)n_perm, hipMemcpyDeviceToHost, h->st));
+	HIP_TRY(hipMemcpyAsync(count_point, q->count.p, sizeof(int64_t) * (size_t)T, hipMemcpyDeviceToHost, h->st));
+	HIP_TRY(hipStreamSynchronize(h->st));
+	for (size_t j = 0; j < n_panel; j++) {
+		float ms = 0;
+		HIP_TRY(hipEventElapsedTime(&ms, q->ev[2 * j], q->ev[2 * j + 1]));
+		q->gram_ms += ms;
+	}
+	return 0;
+}
+
+int hibag_hip_assoc_quant_perm_rows(hibag_hip_quant *q, uint64_t seed, uint64_t perm0, int n, int32_t *out)
+{
+	if (!q || n < 0 || (n > 0 && !out)) return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_quant_perm_rows: null argument or n < 0");
+	if (perm0 < 1 || perm0 + (uint64_t)n < perm0)
+		return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_quant_perm_rows: permutations are numbered from 1 (0 is the observed trait) and stay below 2^64");
+	if (n == 0) return 0;
+	hibag_hip_assoc *h = q->h;
+	HIP_TRY(hipSetDevice(h->device));
+	const int pp = quant_panel_perms(q, n), kp = h->kp, ns = h->D.n;
+	if (q->perm.reserve(sizeof(int32_t) * (size_t)pp * kp)) return HIBAG_HIP_ENOMEM;
+	for (int done = 0; done < n; done += pp) {
+		const int n_lab = std::min(pp, n - done);
+		hipLaunchKernelGGL(k_quant_perm, dim3((n_lab + 63) / 64), dim3(64), 0, h->st, ns, kp, seed, perm0 + (uint64_t)done, n_lab,
+			q->perm.as<int32_t>());
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipMemcpy2DAsync(out + (size_t)done * ns, sizeof(int32_t) * (size_t)ns, q->perm.p, sizeof(int32_t) * (size_t)kp,
+			sizeof(int32_t) * (size_t)ns, (size_t)n_lab, hipMemcpyDeviceToHost, h->st));
+		HIP_TRY(hipStreamSynchronize(h->st));
+	}
+	return 0;
+}
+
+int hibag_hip_assoc_quant_gram_ms(const hibag_hip_quant *q, double *ms)
+{
+	if (!q || !ms) return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_quant_gram_ms: null argument");
+	*ms = q->gram_ms;
 	return 0;
 }
 

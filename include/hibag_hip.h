@@ -36,7 +36,8 @@ extern "C" {
                                        + the association entries (hibag_hip_assoc_*): likewise;
                                        + the out-of-bag knock-out (hibag_hip_oob_knock, hibag_hip_oob_knock_variants): likewise;
                                        + hibag_hip_test_layout_plan, _count, _get, _free (test entries): likewise;
-                                       + the regression entries (hibag_hip_assoc_glm, _n_kept, _feature_rows): likewise */
+                                       + the regression entries (hibag_hip_assoc_glm, _n_kept, _feature_rows): likewise;
+                                       + the quantitative-trait entries (hibag_hip_assoc_quant_*): likewise */
 
 /* error codes */
 #define HIBAG_HIP_OK          0
@@ -344,6 +345,51 @@ int hibag_hip_assoc_feature_rows(hibag_hip_assoc *h, int row0, int n_rows, int8_
 #define HIBAG_HIP_GLM_BOUNDARY  4   /* a fitted probability below 10 eps or above 1 - 10 eps (R's warning)  */
 int hibag_hip_assoc_glm(hibag_hip_assoc *h, const double *covar, int n_covar, const double *weight, int maxit, double epsilon,
 	double *coef, double *se, double *deviance, int32_t *iterations, int32_t *flags);
+
+/* ---- a quantitative trait on the tests of a handle: hlaAssocQuant ------------
+ * lm(y ~ h + covariates) for every test of the handle (R/Association.R:262-313, 368-376 with a continuous y), with max-T
+ * permutation p-values by Freedman-Lane permutations of the residual trait, and the class sums behind the t-test and ANOVA
+ * columns.  The unit is a sample for every model.  With the constant and the covariates orthonormalised (q_0 .. q_q), a
+ * permuted statistic is a function of g = F r, a real-valued Gram matrix int8 feature rows x FP64 residual rows on the FP64
+ * matrix cores, and of rr = sum r^2.  The definitions -- basis, permutation generator, orders of the sums, statistic -- are
+ * DESIGN.md section 25; results do not depend on the panel size, on the other tests of the handle or on how a run of
+ * permutations is split over calls.  The labels the association handle was built with play no part. */
+typedef struct hibag_hip_quant hibag_hip_quant;          /* a trait and its basis on a hibag_hip_assoc, which it borrows */
+
+#define HIBAG_HIP_QUANT_RANK 2   /* the test is not fitted (a constant column, sxx <= 1e-11 xx, det <= 1e-11 a11 a22): NaN */
+
+/* Orthonormalises (1, covariates) on the host by modified Gram-Schmidt applied twice, takes the residual trait, and runs the
+ * class sums, the projections of the feature rows and the observed trait (permutation 0) on the device of `h`.
+ *   y       float64 [n_kept], finite
+ *   covar   float64 [n_covar][n_kept], one row per covariate (NULL with n_covar = 0), finite; 0 <= n_covar <= HIBAG_HIP_GLM_MAX_COVAR
+ * The handle is owned separately (hibag_hip_assoc_quant_free) and must be freed before `h`; it uses the stream of `h`, so
+ * the two are used by one host thread at a time.  NULL on failure: EINVAL for a null pointer, n_covar outside its range, a
+ * non-finite value, fewer than 1 residual degree of freedom (n_kept - 1 - n_covar - d, d = 2 for HIBAG_HIP_ASSOC_GENOTYPE,
+ * else 1), and for a covariate in the span of the constant and the earlier ones (the message says "collinear"). */
+hibag_hip_quant *hibag_hip_assoc_quant_new(hibag_hip_assoc *h, const double *y, const double *covar, int n_covar);
+void hibag_hip_assoc_quant_free(hibag_hip_quant *q);
+
+/* Per test and class d = 0, 1, 2 of its samples (the row value; het = 1, hom = 2 for GENOTYPE): cnt int64, S1 = sum y_c and
+ * S2 = sum y_c^2 float64, each [n_tests][3], with y_c = y - *ybar. */
+int hibag_hip_assoc_quant_classes(hibag_hip_quant *q, int64_t *cnt, double *S1, double *S2, double *ybar);
+
+/* The observed trait: proj float64 [rows][1 + n_covar] (feature row x basis column; rows = n_tests, 2 n_tests for GENOTYPE),
+ * g float64 [rows], *rr, stat float64 [n_tests] (NaN where not fitted or rr - m <= 0), flags int32 [n_tests]
+ * (HIBAG_HIP_QUANT_RANK). */
+int hibag_hip_assoc_quant_observed(hibag_hip_quant *q, double *proj, double *g, double *rr, double *stat, int32_t *flags);
+
+/* Permutations perm0 .. perm0 + n_perm - 1 of the residual trait (perm0 >= 1: permutation 0 is the identity; permutation p
+ * depends on (seed, p) and the number of kept samples alone); max_stat [n_perm] and count_point [n_tests] as
+ * hibag_hip_assoc_permute's.  The work goes in panels of permutations, in whole tiles of 16 (HIBAG_QUANT_PANEL_PERMS per panel
+ * if that is set, read per call; else about 256 MB of residuals). */
+int hibag_hip_assoc_quant_permute(hibag_hip_quant *q, uint64_t seed, uint64_t perm0, int64_t n_perm, double *max_stat,
+	int64_t *count_point);
+
+/* The permutations themselves: out int32 [n][n_kept], row j = permutation perm0 + j (for tests of the generator). */
+int hibag_hip_assoc_quant_perm_rows(hibag_hip_quant *q, uint64_t seed, uint64_t perm0, int n, int32_t *out);
+
+/* Event time of the Gram kernels of the last hibag_hip_assoc_quant_permute call, in ms (for measurements). */
+int hibag_hip_assoc_quant_gram_ms(const hibag_hip_quant *q, double *ms);
 
 /* ---- several models of one locus, merged: hlaPredMerge on the device ----------
  * hlaPredMerge(hlaPredict(m1, type = "response+prob"), hlaPredict(m2, ...), ...) (R/HIBAG.R:825-1023 around HIBAG_SumList,
