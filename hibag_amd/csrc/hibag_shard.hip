@@ -8,9 +8,18 @@
 // [P + 3][n_pad] (hibag_hip_predict_partial_device); ncclAllReduce(ncclDouble, ncclSum) adds them over the devices;
 // hibag_hip_finish_device turns the merged sums into the PredictHLA outputs.  The reference's own multi-worker branch,
 // hlaPredict(cl = ) (R/HIBAG.R:764-808), splits the SAMPLES (that is hibag_hip_predict_multi); splitting the
-// classifiers is for models too large to replicate and for small, latency-bound batches.  The order in which the
-// classifiers' terms are added changes with the split, so the result is held to identical calls and 1e-10 relative on
-// the posteriors against the unsharded run, not to bit equality (tests/test_hip_shard.py).
+// classifiers is for models too large to replicate and for small, latency-bound batches.
+//
+// What the result is held to (tests/test_hip_shard.py, tests/test_hip_multi_device.py, against the host's replay of the
+// split in tests/shard_reference.py):
+//   * a shard's partial sums are its classifiers' terms added in classifier order from +0.0, and shards on ONE device are
+//     added in shard order (k_add_partial; the one-rank all-reduce is the identity): the in-order sum, defined in its bits
+//     by the split -- one classifier per shard is the unsharded sum, since 0 + term is exact; a shard that the split
+//     leaves without classifiers adds +0.0;
+//   * over TWO devices each device's in-order sum, then one addition of the two, which commutes: defined in its bits too;
+//   * over more than two ranks the order of the all-reduce is RCCL's: identical calls to the unsharded run's wherever a
+//     sample's two best cells do not tie to within rounding, and 1e-10 relative on the posteriors.
+// hibag_hip_finish_device is a pure function of the merged sums (hibag_k_finish.h) and is held to its bits on any input.
 //
 // One RCCL rank per DISTINCT device (ncclCommInitAll): shards that share a device are added up on it first, in shard
 // order.  The whole call is driven by the calling thread -- per batch: upload + partial pass on every shard's stream,

@@ -10,9 +10,11 @@ Two ways to spread `hlaPredict()` over ranks:
 * **classifier sharding**: every rank holds a subset of the classifiers, writes
   the un-normalised partial ensemble sums, ONE sum all-reduce merges them, then
   every rank finishes (arg-max, dosage, ...).  Changes the order in which
-  classifier contributions are added, so it is held to 1e-10 relative with
-  identical calls (wherever the two best cells of a sample do not tie to within
-  rounding: a call is the first strict maximum), not to bit equality.
+  classifier contributions are added, so against the unsharded run it is held
+  to 1e-10 relative with identical calls (wherever the two best cells of a
+  sample do not tie to within rounding: a call is the first strict maximum),
+  not to bit equality; two ranks add two addends, which is defined in its bits
+  (``tests/shard_reference.py``).
 
 The compute is injected as callables so that the orchestration can be tested
 with gloo on CPU; on a GPU box the callables are the HIP entry points of

@@ -615,8 +615,13 @@ int hibag_hip_finish_device(hibag_hip_model *m, const double *d_partial, int n_s
  *                               hibag_hip_predict: per batch the genotypes go to every rank, every shard writes its
  *                               un-normalised partial sums (the sum split is src/LibHLA.cpp:2448-2476 with :1497-1518),
  *                               ONE ncclAllReduce(ncclDouble, ncclSum) of [P + 3][n_pad] doubles merges them over xGMI,
- *                               rank 0 finishes.  Calls are identical to the unsharded run's and posteriors within 1e-10
- *                               relative (the order of the classifiers' additions changes with the split).  A failed
+ *                               rank 0 finishes.  The order of the classifiers' additions changes with the split, and the
+ *                               split defines it: shards on ONE device give the in-order sum (each shard its classifiers
+ *                               in order from +0.0, then the shards in shard order) in its bits -- one classifier per shard
+ *                               is the unsharded result, a shard without classifiers adds +0.0 --, TWO devices each their
+ *                               in-order sum and then one commutative addition, in its bits too; over more than two ranks
+ *                               the all-reduce's order is RCCL's: calls identical to the unsharded run's up to ties at
+ *                               rounding level between a sample's two best cells, posteriors within 1e-10 relative.  A failed
  *                               hand-over on any shard reaches every rank as NaN through the sum and the batch is run again.
  *   hibag_hip_predict_multi_sharded   group_new + group_predict + group_free in one call (pays the communicator set-up each time)
  *   hibag_hip_shard_group_ranks / _allreduces   RCCL ranks of the group, all-reduces it has issued;  hibag_hip_rccl_version: NCCL_VERSION_CODE of the loaded library, 0 = none

@@ -37,43 +37,6 @@ def _result(q, procs, timeout=180):
     raise AssertionError("no result from the workers within the time limit")
 
 
-def _oracle_partial(O, fm_full, model, lo, hi, G):
-    """[P+3, n] partial sums of classifiers lo..hi-1, as the HIP partial entry defines them."""
-    P = fm_full.n_hla * (fm_full.n_hla + 1) // 2
-    n = G.shape[0]
-    sw = np.zeros(model.n_snp, np.int64)
-    for c in model.classifiers:
-        np.add.at(sw, c.snpidx, 1)
-    part = np.zeros((P + 3, n))
-    for i in range(n):
-        for c in range(lo, hi):
-            cl = model.classifiers[c]
-            g = G[i][cl.snpidx]
-            ok = (g >= 0) & (g <= 2)
-            tot = int(sw[cl.snpidx].sum())
-            w = float(int(sw[cl.snpidx][ok].sum())) / tot if tot > 0 else 0.0
-            if w <= 0:
-                continue
-            s1, s2 = O.int_to_snp(G[i], cl.snpidx)
-            prob, total = O.post_prob2(fm_full, c, s1, s2)
-            part[:P, i] += prob * w
-            part[P, i] += w
-            part[P + 1, i] += total * w
-            part[P + 2, i] += w
-    return part
-
-
-def _finish(part, n_hla):
-    P = n_hla * (n_hla + 1) // 2
-    S = part[:P].copy()
-    sw = part[P]
-    S[:, sw > 0] /= sw[sw > 0]
-    h1 = np.repeat(np.arange(n_hla), np.arange(n_hla, 0, -1))
-    h2 = np.concatenate([np.arange(i, n_hla) for i in range(n_hla)])
-    am = S.argmax(axis=0)
-    return dict(h1=h1[am], h2=h2[am], postprob=S.T, matching=part[P + 1] / part[P + 2])
-
-
 def _worker(rank, world, port, q):
     import sys
     sys.path.insert(0, ROOT)
@@ -94,9 +57,10 @@ def _worker(rank, world, port, q):
     lo, hi = hd.shard_bounds(len(model.classifiers), world, rank)
     sub, sw = hd.classifier_shard(model, world, rank)
     assert len(sub.classifiers) == hi - lo and sw.sum() == sum(len(c.snpidx) for c in model.classifiers)
+    from shard_reference import finish, partial_sums
     got2 = hd.predict_classifier_sharded(
-        lambda g: torch.from_numpy(_oracle_partial(O, fm, model, lo, hi, g)),
-        lambda p: _finish(p.numpy(), model.n_hla), G)
+        lambda g: torch.from_numpy(partial_sums(O, fm, model, lo, hi, g)),
+        lambda p: finish(p.numpy(), model.n_hla, len(G)), G)
     if rank == 0:
         q.put((got, got2))
     dist.barrier()
@@ -125,6 +89,11 @@ def test_two_rank_gloo_orchestration(oracle):
     assert np.array_equal(got2["h1"], want["h1"]) and np.array_equal(got2["h2"], want["h2"])
     np.testing.assert_allclose(got2["postprob"], want["postprob"], rtol=1e-10, atol=0)
     np.testing.assert_allclose(got2["matching"], want["matching"], rtol=1e-10, atol=0)
+    # and in its bits what the split defines: each rank's classifiers in order, then two addends (which commute)
+    import shard_reference as R
+    fm = oracle.flatten(model)
+    parts = [R.partial_sums(oracle, fm, model, *R.shard_bounds(7, 2, r), G) for r in range(2)]
+    R.assert_same(got2, R.finish(R.merge(parts), model.n_hla, len(G)), what="two gloo ranks")
 
 
 def test_shard_bounds_cover_everything():

@@ -6,7 +6,8 @@ shards / ranks on the one device.
   * hibag_hip_predict_multi over replicas on DISTINCT devices: samples are independent (src/LibHLA.cpp:2362-2411), so every
     output must equal the one-device run bit for bit;
   * hibag_hip_shard_group_predict with one RCCL rank per device: the classifiers' terms are added in another order, so
-    identical calls and 1e-10 relative on the posteriors (north_star's tolerance);
+    identical calls and 1e-10 relative on the posteriors (north_star's tolerance) against the unsharded run -- and, over
+    two devices, the bits of the host's replay of the split (tests/shard_reference.py: two addends commute);
   * `python bench.py --gpus 2` over real RCCL: the line's rccl_ranks must say 2;
   * concurrent trainers of ONE process spread over the devices (train.grow_concurrently(device=[0, 1, ...]): a combiner per
     device): every classifier equal to the oracle's serial run from its stream."""
@@ -109,6 +110,29 @@ def test_one_rccl_rank_per_device_merges_the_classifier_shards(hib, case, ranks)
     for s in grp.shards:
         assert s.handover_faults() == 0
     grp.close()
+
+
+@needs_two
+def test_two_ranks_of_two_shards_each_equal_the_host_merge_bit_for_bit(hib, oracle):
+    """Four shards on devices [0, 0, 1, 1]: each device adds its two shards in shard order, the all-reduce adds the two
+    devices' sums -- two addends, which commute -- so the result is defined in its bits (tests/shard_reference.py,
+    merge_by_rank) on the hand-built 13-classifier case of tests/test_hip_shard.py."""
+    import shard_reference as R
+    from hibag_amd.hibag import ShardGroup
+    model, founders = R.hand_model()
+    G = R.hand_samples(model, founders)
+    devices = [0, 0, 1, 1]
+    parts = R.shard_parts(oracle, oracle.flatten(model), model, 4, G)
+    ref = R.finish(R.merge_by_rank(parts, devices), model.n_hla, len(G))
+    m = hib.hlaModelFromObj(model, device=0)
+    grp = ShardGroup(m, devices)
+    assert grp.ranks == 2 and [s.device() for s in grp.shards] == devices
+    for want_prob in (True, False):
+        got = grp.predict_raw(G, want_dosage=True, want_prob=want_prob)
+        R.assert_same(got, ref, keys=R.KEYS if want_prob else R.KEYS[:5], what="shards on devices [0, 0, 1, 1]")
+    for s in grp.shards:
+        assert s.handover_faults() == 0
+    grp.close(); m.close()
 
 
 @needs_two
