@@ -6,7 +6,8 @@ each allele of the typed cohort and, with ``groups``, each level of every partit
 confidence interval and Wald p-value per ``h`` column, and a likelihood-ratio test against the base model
 ``y ~ c1 + ... + cq``.  ``condition`` repeats the scan conditioned on earlier hits.  All fits are independent and share the
 covariates; they run on the device (``hibag_hip_assoc_glm``), one workgroup per fit, with ``X'WX`` and ``X'Wz`` of every
-iteration as one 16 x 16 FP64 matrix-core tile.  The fit is R's ``glm.fit`` restated.
+iteration as one 16 x 16 FP64 matrix-core tile.  The fit is R's ``glm.fit`` restated.  The test of a
+whole partition -- all residues of a position at once -- is ``hlaAssocOmnibus`` (assocomni.py).
 
 Not built: other ``family`` values (a quantitative trait with the t-test and ANOVA columns is ``hlaAssocQuant``,
 assocquant.py), permutation p-values for this regression, R's step halving, interaction terms, and ``fisher_p`` of the

@@ -11,12 +11,17 @@
 // the same feature rows, with the kept samples' labels that the handle keeps in `y` (the `labels` panel is overwritten by
 // every permutation call).
 //
+// hibag_hip_assoc_glm_sets (hlaAssocOmnibus; kernels: hibag_k_glmw.h) fits one regression per SET of
+// feature rows -- all residues of a position at once -- over a 32-slot design, with aliased columns dropped; it shares the
+// buffers of hibag_hip_assoc_glm.
+//
 // hibag_hip_assoc_quant_* (hlaAssocQuant; kernels: hibag_k_quant.h) test a quantitative trait on the
 // same feature rows, through a handle of their own that borrows this one; they are at the end of the file.
 
 #include "hibag_internal.h"
 #include "hibag_k_assoc.h"
 #include "hibag_k_glm.h"
+#include "hibag_k_glmw.h"
 #include "hibag_k_quant.h"
 
 using hibag_detail::DevBuf;
@@ -372,6 +377,111 @@ int hibag_hip_assoc_glm(hibag_hip_assoc *h, const double *covar, int n_covar, co
 	HIP_TRY(hipMemcpyAsync(deviance, d_dev, sizeof(double) * (size_t)n_fit, hipMemcpyDeviceToHost, h->st));
 	HIP_TRY(hipMemcpyAsync(iterations, d_it, sizeof(int32_t) * (size_t)n_fit, hipMemcpyDeviceToHost, h->st));
 	HIP_TRY(hipMemcpyAsync(flags, d_fl, sizeof(int32_t) * (size_t)n_fit, hipMemcpyDeviceToHost, h->st));
+	HIP_TRY(hipStreamSynchronize(h->st));
+	return 0;
+}
+
+int hibag_hip_assoc_row_sums(hibag_hip_assoc *h, int32_t *out)
+{
+	if (!h || !out) return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_row_sums: null argument");
+	std::copy(h->h_row_sum.begin(), h->h_row_sum.end(), out);
+	return 0;
+}
+
+int hibag_hip_assoc_glm_sets(hibag_hip_assoc *h, const int32_t *set_start, const int32_t *set_rows, int n_sets, const double *covar,
+	int n_covar, const double *weight, int maxit, double epsilon, double *coef, double *se, double *deviance, int32_t *iterations,
+	int32_t *flags, int32_t *df_h)
+{
+	if (!h || !coef || !se || !deviance || !iterations || !flags || !df_h)
+		return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_glm_sets: null argument");
+	static_assert(GLMW_SLOTS == HIBAG_HIP_GLM_WIDE_SLOTS && GLMW_MAX_ROWS == GLMW_SLOTS - 2, "intercept, the h slots and covariates, then z");
+	static_assert(GLM_FLAG_ALIASED == HIBAG_HIP_GLM_ALIASED && GLM_FLAG_TOO_WIDE == HIBAG_HIP_GLM_TOO_WIDE, "the header's flags");
+	static_assert(sizeof(GlmWideFit) == sizeof(int) * (2 + GLMW_MAX_ROWS), "uploaded as it is");
+	if (n_covar < 0 || n_covar > GLMW_MAX_ROWS - 1 || (n_covar > 0 && !covar))
+		return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_glm_sets: %d covariates; 0 .. %d, with covar", n_covar, GLMW_MAX_ROWS - 1);
+	if (maxit < 1) return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_glm_sets: maxit = %d; at least 1", maxit);
+	if (!(epsilon > 0)) return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_glm_sets: epsilon must be > 0");
+	if (n_sets < 0 || n_sets > kMaxTests || !set_start || set_start[0] != 0)
+		return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_glm_sets: need 0 <= n_sets <= %d and set_start with set_start[0] = 0", kMaxTests);
+	for (int t = 0; t < n_sets; t++)
+		if (set_start[t + 1] < set_start[t])
+			return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_glm_sets: set_start is not monotone at set %d", t);
+	if (set_start[n_sets] > 0 && !set_rows) return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_glm_sets: set_rows is null");
+	const int n = h->D.n, kp = h->kp, q = n_covar, n_fit = n_sets + 1, room = GLMW_MAX_ROWS - q;
+	for (size_t i = 0; i < (size_t)q * n; i++)
+		if (!std::isfinite(covar[i]))
+			return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_glm_sets: covariate %zu of kept sample %zu is not finite", i / n, i % n);
+	if (weight)
+		for (int i = 0; i < n; i++)
+			if (!std::isfinite(weight[i]) || weight[i] < 0)
+				return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_glm_sets: weight[%d] = %g; weights are finite and >= 0", i, weight[i]);
+
+	// the fits: a set's rows behind slots 1, 2, ... in the order given; what cannot be fitted is decided from the integer row
+	// sums.  H, the h slots of the call's layout, is the largest set that is fitted.
+	std::vector<GlmWideFit> fits((size_t)n_fit);
+	std::vector<int> seen((size_t)h->rows, -1);
+	const std::vector<int32_t> &r = h->h_row_sum;
+	int H = 0;
+	for (int t = 0; t < n_sets; t++) {
+		GlmWideFit &f = fits[(size_t)t];
+		const int32_t *rows = set_rows + set_start[t];
+		const int m = set_start[t + 1] - set_start[t];
+		for (int j = 0; j < m; j++) {
+			if (rows[j] < 0 || rows[j] >= h->rows)
+				return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_glm_sets: set %d names row %d, outside the handle's %d", t, rows[j], h->rows);
+			if (seen[(size_t)rows[j]] == t)
+				return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_glm_sets: set %d names row %d twice", t, rows[j]);
+			seen[(size_t)rows[j]] = t;
+		}
+		f.n_rows = -1;
+		f.flags0 = GLM_FLAG_RANK;
+		std::fill(f.rows, f.rows + GLMW_MAX_ROWS, -1);
+		if (m > room) { f.flags0 |= GLM_FLAG_TOO_WIDE; continue; }
+		int carried = 0;
+		for (int j = 0; j < m; j++) carried += r[(size_t)rows[j]] > 0;
+		if (carried == 0) continue;
+		f.n_rows = m;
+		f.flags0 = carried < m ? GLM_FLAG_ALIASED : 0;
+		for (int j = 0; j < m; j++) f.rows[j] = r[(size_t)rows[j]] > 0 ? rows[j] : -1;
+		H = std::max(H, m);
+	}
+	GlmWideFit &base = fits[(size_t)n_sets];
+	base.n_rows = 0;
+	base.flags0 = 0;
+	std::fill(base.rows, base.rows + GLMW_MAX_ROWS, -1);
+
+	HIP_TRY(hipSetDevice(h->device));
+	const size_t in_doubles = (size_t)q * n + (weight ? (size_t)n : 0);
+	const size_t out_bytes = (size_t)n_fit * (2 * GLMW_SLOTS * sizeof(double) + sizeof(double) + 3 * sizeof(int32_t));
+	if (h->glm_in.reserve(sizeof(double) * std::max<size_t>(in_doubles, 1)) || h->glm_img.reserve(sizeof(double) * GLMW_SLOTS * (size_t)kp) ||
+		h->glm_wt.reserve(sizeof(double) * (size_t)kp) || h->glm_fits.reserve(sizeof(GlmWideFit) * (size_t)n_fit) || h->glm_out.reserve(out_bytes))
+		return HIBAG_HIP_ENOMEM;
+	double *d_cov = h->glm_in.as<double>(), *d_w = weight ? d_cov + (size_t)q * n : nullptr;
+	// everything that is enqueued: `fits` and the caller's arrays are read and written asynchronously, so a failure part-way
+	// waits for the stream before this frame goes away
+	auto enqueue = [&]() -> int {
+		if (q) HIP_TRY(hipMemcpyAsync(d_cov, covar, sizeof(double) * (size_t)q * n, hipMemcpyHostToDevice, h->st));
+		if (weight) HIP_TRY(hipMemcpyAsync(d_w, weight, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, h->st));
+		HIP_TRY(hipMemcpyAsync(h->glm_fits.p, fits.data(), sizeof(GlmWideFit) * (size_t)n_fit, hipMemcpyHostToDevice, h->st));
+		hipLaunchKernelGGL(k_glm_image_wide, dim3((unsigned)(((size_t)kp * GLMW_SLOTS + 255) / 256)), dim3(256), 0, h->st, d_cov, d_w, n, q, H,
+			kp, h->glm_img.as<double>(), h->glm_wt.as<double>());
+		HIP_TRY(hipGetLastError());
+		double *d_coef = h->glm_out.as<double>(), *d_se = d_coef + (size_t)n_fit * GLMW_SLOTS, *d_dev = d_se + (size_t)n_fit * GLMW_SLOTS;
+		int32_t *d_it = (int32_t *)(d_dev + n_fit), *d_fl = d_it + n_fit, *d_df = d_fl + n_fit;
+		hipLaunchKernelGGL(k_glm_fit_wide, dim3(n_fit), dim3(GLM_WAVES * 64), 0, h->st, h->glm_img.as<double>(), h->glm_wt.as<double>(),
+			h->y.as<int8_t>(), h->feat.as<int8_t>(), h->glm_fits.as<GlmWideFit>(), n, kp, q, H, maxit, epsilon, d_coef, d_se, d_dev, d_it,
+			d_fl, d_df);
+		if (hipGetLastError() != hipSuccess) return hibag_fail(HIBAG_HIP_ENODEV, "hibag_hip_assoc_glm_sets: a kernel launch failed");
+		HIP_TRY(hipMemcpyAsync(coef, d_coef, sizeof(double) * (size_t)n_fit * GLMW_SLOTS, hipMemcpyDeviceToHost, h->st));
+		HIP_TRY(hipMemcpyAsync(se, d_se, sizeof(double) * (size_t)n_fit * GLMW_SLOTS, hipMemcpyDeviceToHost, h->st));
+		HIP_TRY(hipMemcpyAsync(deviance, d_dev, sizeof(double) * (size_t)n_fit, hipMemcpyDeviceToHost, h->st));
+		HIP_TRY(hipMemcpyAsync(iterations, d_it, sizeof(int32_t) * (size_t)n_fit, hipMemcpyDeviceToHost, h->st));
+		HIP_TRY(hipMemcpyAsync(flags, d_fl, sizeof(int32_t) * (size_t)n_fit, hipMemcpyDeviceToHost, h->st));
+		HIP_TRY(hipMemcpyAsync(df_h, d_df, sizeof(int32_t) * (size_t)n_fit, hipMemcpyDeviceToHost, h->st));
+		return 0;
+	};
+	const int rc = enqueue();
+	if (rc) { (void)hipStreamSynchronize(h->st); return rc; }
 	HIP_TRY(hipStreamSynchronize(h->st));
 	return 0;
 }

@@ -37,7 +37,8 @@ extern "C" {
                                        + the out-of-bag knock-out (hibag_hip_oob_knock, hibag_hip_oob_knock_variants): likewise;
                                        + hibag_hip_test_layout_plan, _count, _get, _free (test entries): likewise;
                                        + the regression entries (hibag_hip_assoc_glm, _n_kept, _feature_rows): likewise;
-                                       + the quantitative-trait entries (hibag_hip_assoc_quant_*): likewise */
+                                       + the quantitative-trait entries (hibag_hip_assoc_quant_*): likewise;
+                                       + the set regression (hibag_hip_assoc_glm_sets, hibag_hip_assoc_row_sums): likewise */
 
 /* error codes */
 #define HIBAG_HIP_OK          0
@@ -345,6 +346,37 @@ int hibag_hip_assoc_feature_rows(hibag_hip_assoc *h, int row0, int n_rows, int8_
 #define HIBAG_HIP_GLM_BOUNDARY  4   /* a fitted probability below 10 eps or above 1 - 10 eps (R's warning)  */
 int hibag_hip_assoc_glm(hibag_hip_assoc *h, const double *covar, int n_covar, const double *weight, int maxit, double epsilon,
 	double *coef, double *se, double *deviance, int32_t *iterations, int32_t *flags);
+
+/* ---- multi-column logistic regression per set of feature rows: hlaAssocOmnibus ------------
+ * glm(y ~ r_1 + ... + r_d + covariates, family = binomial) for every SET of feature rows of the handle -- the residues of an
+ * amino-acid position, the two-digit types, any partition's levels -- and for the base model y ~ covariates: the fit of
+ * hibag_hip_assoc_glm over a design of 32 slots, with R's treatment of aliased columns:
+ * a column whose pivot is <= 1e-11 A_jj is dropped (coefficient and standard error NaN, HIBAG_HIP_GLM_ALIASED) and the fit
+ * goes on without it.  The factorisation takes the columns in the order intercept, covariates, set rows, so that of two
+ * aliased columns the set's is the one dropped.  The definitions are DESIGN.md section 26.
+ *   set_start   int32 [n_sets + 1], set_start[0] = 0, not decreasing; set t is set_rows[set_start[t] .. set_start[t + 1])
+ *   set_rows    int32 row indices of the handle, as hibag_hip_assoc_feature_rows numbers them; no row twice in a set
+ *   covar       float64 [n_covar][n_kept] (NULL with n_covar = 0); 0 <= n_covar <= 29
+ *   weight, maxit, epsilon: as hibag_hip_assoc_glm
+ * Outputs for n_sets + 1 fits, fit n_sets the base model.  With H the largest size among the sets that are fitted:
+ *   coef, se    float64 [n_sets + 1][32] by slot: 0 the intercept, 1 + j row j of the set, 1 + H .. H + n_covar the
+ *               covariates; every other slot, and every dropped column, NaN
+ *   deviance    float64, iterations int32, flags int32 (HIBAG_HIP_GLM_*) [n_sets + 1]
+ *   df_h        int32 [n_sets + 1]: the set's columns still in the fit at its last solve (0 where not fitted)
+ * An empty set and a set whose rows all have row sum 0 are not fitted (RANK, NaN); a row with row sum 0 beside others is
+ * left out before the fit and counts as ALIASED; a set of more than 30 - n_covar rows is not fitted (TOO_WIDE | RANK).
+ * A set's numbers depend on the kept samples, its own rows, the arguments and H -- not on the other sets otherwise.
+ * EINVAL as hibag_hip_assoc_glm, and for n_sets < 0, a null set_start or one that does not start at 0 or decreases, a null
+ * set_rows with rows to read, a row index outside the handle's rows, the same row twice in a set. */
+#define HIBAG_HIP_GLM_WIDE_SLOTS 32
+#define HIBAG_HIP_GLM_ALIASED    8   /* a column was dropped as aliased (or left out with row sum 0): its values are NaN */
+#define HIBAG_HIP_GLM_TOO_WIDE   16  /* the set has more than 30 - n_covar rows: not fitted (with RANK)                */
+int hibag_hip_assoc_glm_sets(hibag_hip_assoc *h, const int32_t *set_start, const int32_t *set_rows, int n_sets, const double *covar,
+	int n_covar, const double *weight, int maxit, double epsilon, double *coef, double *se, double *deviance, int32_t *iterations,
+	int32_t *flags, int32_t *df_h);
+
+/* The sums of the handle's feature rows over the kept samples: out int32 [rows], rows as hibag_hip_assoc_feature_rows. */
+int hibag_hip_assoc_row_sums(hibag_hip_assoc *h, int32_t *out);
 
 /* ---- a quantitative trait on the tests of a handle: hlaAssocQuant ------------
  * lm(y ~ h + covariates) for every test of the handle (R/Association.R:262-313, 368-376 with a continuous y), with max-T
