@@ -35,6 +35,9 @@ def merge_reference(postprobs, matchings, weight, row_of_cell, n_hla, use_matchi
         for j in range(i, n_hla):
             first_of.append(j)
             second_of.append(i)
+    # an allele's rows as first and as second name, ascending: the order its dosage is summed in
+    first_rows = [[r for r in range(P) if first_of[r] == a] for a in range(n_hla)]
+    second_rows = [[r for r in range(P) if second_of[r] == a] for a in range(n_hla)]
     # gather lists: model order, then ascending source cell
     gather = [[] for _ in range(P)]
     for i in range(k):
@@ -73,13 +76,11 @@ def merge_reference(postprobs, matchings, weight, row_of_cell, n_hla, use_matchi
                 best, key = r, x
         for a in range(n_hla):                               # step 7
             d1 = 0.0
-            for r in range(P):
-                if first_of[r] == a:
-                    d1 += prob[r]
+            for r in first_rows[a]:
+                d1 += prob[r]
             d2 = 0.0
-            for r in range(P):
-                if second_of[r] == a:
-                    d2 += prob[r]
+            for r in second_rows[a]:
+                d2 += prob[r]
             out["dosage"][a, s] = d1 + d2
         out["matching"][s] = m
         out["h2"][s], out["h1"][s] = first_of[best], second_of[best]

@@ -92,8 +92,81 @@ def odd_values_model():
     return model, G
 
 
+def subnormal_model():
+    """A total that is positive and below 1 / DBL_MAX: 1 / total = inf, so the positive cells become inf and the empty ones
+    0 * inf = NaN, and the reference still makes a call, with prob = inf (the first inf cell; src/LibHLA.cpp:1826-1828).
+    Every pair of ``sub`` is 62 to 64 mismatches from sample 0: its total is a few 1e-310.  Sample 1 (one SNP fewer) and
+    sample 3 (four mismatches fewer) have normal totals, sample 2 types nothing."""
+    k = 32
+    near = Classifier(np.arange(4), [0.3, 0.3, 0.4], [0, 1, 2], ["0000", "0101", "1111"])
+    sub = Classifier(np.arange(k), [0.4, 0.2, 0.2, 0.2], [0, 0, 1, 2],
+                     ["1" * k, "0" + "1" * (k - 1), "1" + "0" + "1" * (k - 2), "1" * k])
+    model = HlaAttrBagObj(0, k, ["a", "b", "c"], [near, sub])
+    G = np.zeros((4, k), np.int32)
+    G[1, k - 1] = NA_INTEGER
+    G[2, :] = NA_INTEGER
+    G[3, :2] = 2
+    return model, G
+
+
+def subnormal_lanes_model(n_samp=72):
+    """The four samples of ``subnormal_model`` dealt over 72 lanes in a seeded order, so that a 64-sample group holds finite,
+    inf, NaN-matching lanes side by side (and the group of eight that follows it too).  The inf lanes' posterior is inf in
+    every cell and NaN in none -- every pair of ``sub`` exists and stays positive --, which is what a merge with a second
+    model needs to normalise a column to NaN in some rows and 0 in others."""
+    model, four = subnormal_model()
+    kind = np.random.default_rng(5).integers(0, 4, n_samp)
+    kind[:4] = np.arange(4)
+    return model, np.ascontiguousarray(four[kind])
+
+
+MIXED_COUNTS = [12, 113, 18, 40, 24, 30, 31, 32, 56, 84, 100, 120, 128, 20]
+MIXED_SCALE = 1e-140
+# which classifiers' haplotype frequencies are scaled down, by what, and the error rate at the noisy end of a 64-sample group
+MIXED_ENSEMBLE = {"scaled": {3: MIXED_SCALE, 12: MIXED_SCALE}, "rate": 0.25}
+MIXED_PER_CLASSIFIER = {"scaled": {0: 1e-150, 1: MIXED_SCALE, 3: MIXED_SCALE, 6: MIXED_SCALE, 7: MIXED_SCALE, 9: MIXED_SCALE},
+                        "rate": 0.5}
+MIXED_ALL_MISSING = 7
+
+
+def mixed_lanes_model(recipe=MIXED_ENSEMBLE, n_samp=200):
+    """Healthy, inf, NaN and inactive lanes inside one 64-sample group.  The engine-mix model of the curve and out-of-bag
+    tests (one-step and multi-step matrix engine, int8, VALU) on 200 samples: three full groups and one of eight.  Sample s
+    gets uniform random genotype errors at rate (s % 64) / 64 * rate, so every group runs from clean to noisy, and the
+    haplotype frequencies of the ``scaled`` classifiers are multiplied by 1e-140 or less (tests/test_hip_chunks.py::
+    underflow_model): a sample a few mismatches from its best pair has a subnormal total there (1 / total = inf: inf in its
+    positive cells, NaN in its empty ones, and a call with prob = inf -- the first inf cell), one further away has total 0
+    (NaN in every cell: no call).  Sample 7 types nothing.  ``MIXED_ENSEMBLE`` ("mixed-lanes") is for the entries that sum
+    over classifiers, ``MIXED_PER_CLASSIFIER`` ("mixed-lanes-each") for the ones that evaluate each classifier on its own: a
+    scaled classifier on every pick kernel, and 1e-150 for the 12-SNP one, which 1e-140 leaves nearly without such lanes."""
+    model, founders, af = synth.make_model("hla-b", seed=7, n_snp=160, n_classifier=len(MIXED_COUNTS), snp_counts=MIXED_COUNTS)
+    G, _ = synth.make_samples(founders, af, n_samp, seed=8)
+    rng = np.random.default_rng(29)
+    rate = (np.arange(n_samp) % 64) / 64.0 * recipe["rate"]
+    wrong = rng.random(G.shape) < rate[:, None]
+    G = np.where(wrong & (G != NA_INTEGER), rng.integers(0, 3, G.shape), G).astype(np.int32)
+    G[MIXED_ALL_MISSING, :] = NA_INTEGER
+    for c, factor in recipe["scaled"].items():
+        model.classifiers[c].freq = np.asarray(model.classifiers[c].freq, np.float64) * factor
+    return model, np.ascontiguousarray(G)
+
+
+def mixed_lanes_per_classifier():
+    """``mixed_lanes_model`` with the ``MIXED_PER_CLASSIFIER`` recipe."""
+    return mixed_lanes_model(MIXED_PER_CLASSIFIER)
+
+
 PREDICT_CASES = {"widths": width_model, "no-haplotypes": no_haplotype_model, "zero-frequency": zero_frequency_model,
-                 "underflow": underflow_model, "mirrored": mirrored_model, "odd-values": odd_values_model}
+                 "underflow": underflow_model, "mirrored": mirrored_model, "odd-values": odd_values_model,
+                 "subnormal": subnormal_model, "subnormal-lanes": subnormal_lanes_model, "mixed-lanes": mixed_lanes_model,
+                 "mixed-lanes-each": mixed_lanes_per_classifier}
+
+
+def lane_kinds(h1, prob):
+    """(no call, finite call, call with prob = +inf) as boolean arrays."""
+    h1, prob = np.asarray(h1), np.asarray(prob)
+    na = h1 == NA_INTEGER
+    return na, ~na & np.isfinite(prob), ~na & np.isposinf(prob)
 
 
 def training_cohort(n_samp=80, n_snp=60, n_hla=7, seed=41):
