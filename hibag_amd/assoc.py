@@ -60,17 +60,34 @@ def _labels(y, n: int) -> np.ndarray:
     return np.array([int(v == values[1]) for v in y], np.int32)
 
 
+def _check_model(model: str, models: Sequence[str] = MODELS) -> None:
+    if model not in models:
+        raise ValueError("'arg' should be one of " + ", ".join(f'"{m}"' for m in models))
+
+
+def _check_perm(n_perm, seed) -> Tuple[int, Optional[int]]:
+    """(n_perm, seed) as ints; the seed is drawn when there are permutations and none is given."""
+    if isinstance(n_perm, bool) or not isinstance(n_perm, (int, np.integer)) or n_perm < 0:
+        raise ValueError("n_perm must be an integer >= 0")
+    if seed is not None and (isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 1 << 64):
+        raise ValueError("seed must be an integer in 0 .. 2^64 - 1")
+    if n_perm > 0 and seed is None:
+        seed = secrets.randbits(64)
+    return int(n_perm), None if seed is None else int(seed)
+
+
 class _Plan:
-    """What the device is told and how its tests are called: the samples left after the call threshold (``keep_thr``),
-    their allele indices into ``alleles`` (NA where unknown: the device drops those samples), their labels, the partitions
-    restricted to ``alleles``, and per test of the RESULT its name and its row among the device's tests (-1: a level that
-    no allele of the data belongs to, which the device does not know and whose statistics are NaN)."""
+    """What the device is told and how its tests are called: ``sel``, the indices of the samples left after the call
+    threshold that have two known alleles, their allele indices into ``alleles``, their labels (``y=None``, an entry without
+    a case / control label: all 0), the partitions restricted to ``alleles``, and per test of the RESULT its name and its row
+    among the device's tests (-1: a level that no allele of the data belongs to, which the device does not know and whose
+    statistics are NaN; ``spread`` maps the device's arrays onto the result's tests)."""
 
     def __init__(self, hla: HlaAlleleClass, y, prob_threshold: float, groups: Optional[HlaAlleleGroups]):
         if not isinstance(hla, HlaAlleleClass):
             raise TypeError('inherits(hla, "hlaAlleleClass") is not TRUE')
         n_all = len(hla.sample_id)
-        lab = _labels(y, n_all)
+        lab = np.zeros(n_all, np.int32) if y is None else _labels(y, n_all)
         h1, h2 = list(hla.allele1), list(hla.allele2)
         keep = np.ones(n_all, bool)
         if isinstance(prob_threshold, bool) or not isinstance(prob_threshold, (int, float, np.integer, np.floating)):
@@ -87,6 +104,7 @@ class _Plan:
             raise ValueError("no sample with two known alleles is left")
         if sel.size > MAX_SAMPLES:
             raise ValueError(f"{sel.size} samples; at most 2^24")
+        self.sel = sel
         self.n_samp = int(sel.size)
         self.alleles = hlaUniqueAllele([h1[i] for i in sel] + [h2[i] for i in sel])
         pos = {a: i for i, a in enumerate(self.alleles)}
@@ -116,6 +134,13 @@ class _Plan:
         else:
             self.n_device_tests = len(self.alleles)
 
+    def spread(self, a, fill=np.nan) -> np.ndarray:
+        """The per-device-test array ``a`` [n_device_tests, ...] per test of the result, ``fill`` for a level unknown to the
+        device (no allele of the data belongs to it, so it has no carrier)."""
+        a = np.asarray(a)
+        row = np.array(self.row, np.int64)
+        return np.where((row >= 0).reshape((-1,) + (1,) * (a.ndim - 1)), a[np.maximum(row, 0)], fill)
+
 
 def _columns(model: str, table: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
     """The reference's count columns and ``%.`` columns from the integer tables [n_test, 6] (rows x (control, case)):
@@ -129,13 +154,33 @@ def _columns(model: str, table: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
     return counts, pct
 
 
+def chisq_sf(x: float, df: int) -> float:
+    """The upper tail of chi-square with an integer ``df`` >= 1, in closed form: for even df
+    ``exp(-x/2) sum_{k < df/2} (x/2)^k / k!``; for odd df ``erfc(sqrt(x/2))`` plus the half-integer terms
+    ``exp(-x/2) sum_{k=1}^{(df-1)/2} (x/2)^(k-1/2) / Gamma(k+1/2)``.  Every term is positive: nothing cancels."""
+    if math.isnan(x) or df < 1:
+        return math.nan
+    h = max(x, 0.0) / 2.0
+    if df % 2 == 0:
+        term, total = 1.0, 1.0
+        for k in range(1, df // 2):
+            term = term * h / k
+            total = total + term
+        return math.exp(-h) * total
+    tail = math.erfc(math.sqrt(h))
+    if df == 1:
+        return tail
+    term = math.sqrt(h) / (math.sqrt(math.pi) / 2.0)       # (x/2)^(1/2) / Gamma(3/2)
+    total = term
+    for k in range(1, (df - 1) // 2):
+        term = term * h / (k + 0.5)
+        total = total + term
+    return tail + math.exp(-h) * total
+
+
 def _chisq_p(stat: np.ndarray, df: int) -> np.ndarray:
-    """The upper tail of chi-square with 1 or 2 degrees of freedom: erfc(sqrt(st / 2)), exp(-st / 2)."""
-    out = np.full(len(stat), np.nan)
-    for t, st in enumerate(stat):
-        if not math.isnan(st):
-            out[t] = math.erfc(math.sqrt(st / 2.0)) if df == 1 else math.exp(-st / 2.0)
-    return out
+    """``chisq_sf`` of every statistic: for 1 and 2 degrees of freedom erfc(sqrt(st / 2)) and exp(-st / 2)."""
+    return np.array([chisq_sf(float(st), df) for st in stat], np.float64)
 
 
 def _fisher_p(table: np.ndarray) -> np.ndarray:
@@ -175,6 +220,7 @@ class _DeviceAssoc:
         if not self._h:
             raise _lib.HibagHipError(-1, L.hibag_hip_last_error().decode("utf-8", "replace"))
         self.n_tests = L.hibag_hip_assoc_n_tests(self._h)
+        self.n_rows = self.n_tests * (2 if MODELS[model] == "genotype" else 1)       # the feature rows
         self.n_kept = int(np.count_nonzero((a1 != NA_INTEGER) & (a2 != NA_INTEGER)))
 
     def close(self) -> None:
@@ -253,6 +299,12 @@ def _perm_p(stat_obs: np.ndarray, count_point: np.ndarray, max_stat: np.ndarray,
     return perm_p, perm_p_adj
 
 
+def _attach_perm(res, plan: _Plan, stat: np.ndarray, max_stat: np.ndarray, d_count: np.ndarray, n_perm: int, seed: int) -> None:
+    """The permutation columns of a result from the device's ``max_stat`` and per-device-test counts."""
+    res.perm_p, res.perm_p_adj = _perm_p(stat, plan.spread(d_count, 0), max_stat, n_perm)
+    res.max_stat, res.n_perm, res.seed = max_stat, n_perm, seed
+
+
 def hlaAssocTest(hla: HlaAlleleClass, y: Sequence, model: str = "dominant", prob_threshold: float = float("nan"),
                  groups: Optional[HlaAlleleGroups] = None, n_perm: int = 0, seed: Optional[int] = None) -> HlaAssocResult:
     """Association tests of the alleles of ``hla`` with the case / control label ``y`` (``hlaAssocTest`` of the reference
@@ -276,36 +328,23 @@ def hlaAssocTest(hla: HlaAlleleClass, y: Sequence, model: str = "dominant", prob
     Not built: ``fisher_p`` for the ``genotype`` model, which is NaN; the ``glm`` regression with covariates and ``use.prob``
     is ``hlaAssocGlm``, a quantitative trait ``hlaAssocQuant``.  The statistics, the generator and the counts are defined in DESIGN.md
     section 20."""
-    if model not in MODELS:
-        raise ValueError("'arg' should be one of " + ", ".join(f'"{m}"' for m in MODELS))
-    if isinstance(n_perm, bool) or not isinstance(n_perm, (int, np.integer)) or n_perm < 0:
-        raise ValueError("n_perm must be an integer >= 0")
-    if seed is not None and (isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 1 << 64):
-        raise ValueError("seed must be an integer in 0 .. 2^64 - 1")
+    _check_model(model)
+    n_perm, seed = _check_perm(n_perm, seed)
     plan = _Plan(hla, y, prob_threshold, groups)
-    n_perm = int(n_perm)
-    if n_perm > 0 and seed is None:
-        seed = secrets.randbits(64)
     with _DeviceAssoc(plan.a1, plan.a2, plan.y, len(plan.alleles), plan.group_of, MODELS.index(model)) as dev:
         assert dev.n_tests == plan.n_device_tests
         d_stat, d_table = dev.observed()
         if n_perm > 0:
-            max_stat, d_count = dev.permute(int(seed), 1, n_perm)
-    # the result's tests from the device's: a level unknown to the device has no carrier
-    row = np.array(plan.row, np.int64)
-    known = row >= 0
-    stat = np.where(known, d_stat[np.maximum(row, 0)], np.nan)
-    table = d_table[np.maximum(row, 0)].copy()
+            max_stat, d_count = dev.permute(seed, 1, n_perm)
+    stat = plan.spread(d_stat)
     unit = 2 if model == "additive" else 1
-    table[~known] = [unit * (plan.n_samp - plan.n_case), unit * plan.n_case, 0, 0, 0, 0]
+    table = plan.spread(d_table, [unit * (plan.n_samp - plan.n_case), unit * plan.n_case, 0, 0, 0, 0])
     counts, pct = _columns(model, table)
-    fisher = _fisher_p(table) if model != "genotype" else np.full(len(row), np.nan)
+    fisher = _fisher_p(table) if model != "genotype" else np.full(len(stat), np.nan)
     res = HlaAssocResult(model, hla.locus, plan.names, counts, pct, stat, _chisq_p(stat, 2 if model == "genotype" else 1), fisher,
                          plan.n_samp, plan.n_case, plan.n_excluded)
     if n_perm > 0:
-        count = np.where(known, d_count[np.maximum(row, 0)], 0)
-        res.perm_p, res.perm_p_adj = _perm_p(stat, count, max_stat, n_perm)
-        res.max_stat, res.n_perm, res.seed = max_stat, n_perm, int(seed)
+        _attach_perm(res, plan, stat, max_stat, d_count, n_perm, seed)
     return res
 
 

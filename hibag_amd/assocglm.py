@@ -21,7 +21,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib
-from .assoc import MODELS, _DeviceAssoc, _Plan, _chisq_p, _is_na, _ptr
+from .assoc import MODELS, _check_model, _DeviceAssoc, _Plan, _chisq_p, _ptr
 from .groups import HlaAlleleGroups
 from .hibag import HlaAlleleClass
 
@@ -95,17 +95,6 @@ class HlaAssocGlmResult:
                 f"{self.n_samp} samples with {self.n_case} cases)")
 
 
-def _kept_index(hla: HlaAlleleClass, prob_threshold: float) -> np.ndarray:
-    """The samples ``assoc._Plan`` keeps, in order: at or above the call threshold, both alleles known."""
-    n_all = len(hla.sample_id)
-    keep = np.ones(n_all, bool)
-    if math.isfinite(prob_threshold):
-        with np.errstate(invalid="ignore"):
-            keep = np.asarray(hla.prob, np.float64) >= float(prob_threshold)
-    known = np.array([not _is_na(a) and not _is_na(b) for a, b in zip(hla.allele1, hla.allele2)], bool)
-    return np.flatnonzero(keep & known)
-
-
 def _covariates(covariates, n_all: int) -> Tuple[List[str], np.ndarray]:
     """(names, float64 [q, n_all]) from an array [n_all, q] (a vector is one covariate) or a dict name -> vector."""
     if covariates is None:
@@ -125,6 +114,59 @@ def _covariates(covariates, n_all: int) -> Tuple[List[str], np.ndarray]:
         if len(c) != n_all:
             raise ValueError(f"covariate {name!r} has {len(c)} values for {n_all} samples")
     return names, (np.stack(cols) if cols else np.zeros((0, n_all)))
+
+
+def _check_fit_control(maxit, epsilon) -> None:
+    if isinstance(maxit, bool) or not isinstance(maxit, (int, np.integer)) or maxit < 1:
+        raise ValueError("maxit must be an integer >= 1")
+    if isinstance(epsilon, bool) or not isinstance(epsilon, (int, float, np.integer, np.floating)) or not epsilon > 0:
+        raise ValueError("epsilon must be > 0")
+
+
+def _design(plan: _Plan, hla: HlaAlleleClass, covariates, use_prob: bool) -> Tuple[List[str], np.ndarray, Optional[np.ndarray]]:
+    """(covariate names, covariates [q, n_kept], prior weights [n_kept] or None) over the kept samples of ``plan``."""
+    cov_names, cov = _covariates(covariates, len(hla.sample_id))
+    cov = np.ascontiguousarray(cov[:, plan.sel])
+    if not np.isfinite(cov).all():
+        bad = cov_names[int(np.flatnonzero(~np.isfinite(cov).all(axis=1))[0])]
+        raise ValueError(f"covariate {bad!r} has a missing or non-finite value: subset the samples first")
+    weight = None
+    if use_prob:
+        if hla.prob is None:
+            raise ValueError("No posterior probability in 'hla' ('hla.prob' should be available).")
+        weight = np.ascontiguousarray(np.asarray(hla.prob, np.float64)[plan.sel])
+        if not (np.isfinite(weight).all() and (weight >= 0).all()):
+            raise ValueError("use_prob: the posterior probabilities of the kept samples must be finite and >= 0")
+    return cov_names, cov, weight
+
+
+def _condition_list(condition, what: str = "test") -> List[str]:
+    condition = [condition] if isinstance(condition, str) else list(condition) if condition is not None else []
+    if any(not isinstance(c, str) for c in condition):
+        raise ValueError(f"'condition' is a list of {what} names")
+    return condition
+
+
+def _condition_tests(plan: _Plan, condition: Sequence[str], per: int) -> Tuple[List[int], List[str]]:
+    """(device test per name, covariate names of their ``per`` h columns) of ``condition``, names of single tests."""
+    rows, names = [], []
+    for c in condition:
+        if c not in plan.names:
+            raise ValueError(f"condition: {c!r} is not a test of this analysis")
+        row = plan.row[plan.names.index(c)]
+        if row < 0:
+            raise ValueError(f"condition: no allele of the data belongs to {c!r}")
+        rows.append(row)
+        names += [f"h[{c}]"] if per == 1 else [f"h1[{c}]", f"h2[{c}]"]
+    return rows, names
+
+
+def _base_model(coef, se, deviance, iterations, flags, slots: Sequence[int], names: List[str]) -> Dict[str, object]:
+    """The ``base`` entry of a result from the base model's fit: its intercept and the covariates in ``slots``."""
+    est, sd = coef[list(slots)], se[list(slots)]
+    lower, upper, pval = _wald(est, sd)
+    return {"name": ["(Intercept)"] + names, "est": est, "se": sd, "lower": lower, "upper": upper, "pval": pval,
+            "deviance": float(deviance), "iterations": int(iterations), "flags": int(flags)}
 
 
 def hlaAssocGlm(hla: HlaAlleleClass, y: Sequence, covariates=None, model: str = "dominant", prob_threshold: float = float("nan"),
@@ -153,40 +195,14 @@ def hlaAssocGlm(hla: HlaAlleleClass, y: Sequence, covariates=None, model: str = 
     regression, R's step halving (with the clamps of section 23 the deviance is always finite), interaction terms, and
     ``fisher_p`` of the genotype model.  (``_backend``: the tests' seam -- a class with the interface of ``_DeviceGlm`` that
     stands in for the device.)"""
-    if model not in MODELS:
-        raise ValueError("'arg' should be one of " + ", ".join(f'"{m}"' for m in MODELS))
-    if isinstance(maxit, bool) or not isinstance(maxit, (int, np.integer)) or maxit < 1:
-        raise ValueError("maxit must be an integer >= 1")
-    if isinstance(epsilon, bool) or not isinstance(epsilon, (int, float, np.integer, np.floating)) or not epsilon > 0:
-        raise ValueError("epsilon must be > 0")
+    _check_model(model)
+    _check_fit_control(maxit, epsilon)
     plan = _Plan(hla, y, prob_threshold, groups)
-    sel = _kept_index(hla, prob_threshold)
-    assert len(sel) == plan.n_samp
-    cov_names, cov = _covariates(covariates, len(hla.sample_id))
-    cov = np.ascontiguousarray(cov[:, sel])
-    if not np.isfinite(cov).all():
-        bad = cov_names[int(np.flatnonzero(~np.isfinite(cov).all(axis=1))[0])]
-        raise ValueError(f"covariate {bad!r} has a missing or non-finite value: subset the samples first")
-    weight = None
-    if use_prob:
-        if hla.prob is None:
-            raise ValueError("No posterior probability in 'hla' ('hla.prob' should be available).")
-        weight = np.ascontiguousarray(np.asarray(hla.prob, np.float64)[sel])
-        if not (np.isfinite(weight).all() and (weight >= 0).all()):
-            raise ValueError("use_prob: the posterior probabilities of the kept samples must be finite and >= 0")
-    condition = [condition] if isinstance(condition, str) else list(condition) if condition is not None else []
-    if any(not isinstance(c, str) for c in condition):
-        raise ValueError("'condition' is a list of test names")
+    cov_names, cov, weight = _design(plan, hla, covariates, use_prob)
+    condition = _condition_list(condition)
     per = 2 if model == "genotype" else 1
-    cond_rows = []
-    for c in condition:
-        if c not in plan.names:
-            raise ValueError(f"condition: {c!r} is not a test of this analysis")
-        row = plan.row[plan.names.index(c)]
-        if row < 0:
-            raise ValueError(f"condition: no allele of the data belongs to {c!r}")
-        cond_rows.append(row)
-        cov_names += [f"h[{c}]"] if per == 1 else [f"h1[{c}]", f"h2[{c}]"]
+    cond_rows, cond_names = _condition_tests(plan, condition, per)
+    cov_names += cond_names
     q = len(cov_names)
     if q > MAX_COVAR:
         raise ValueError(f"{q} covariate columns ({len(condition)} conditioned tests included); at most {MAX_COVAR}")
@@ -202,14 +218,9 @@ def hlaAssocGlm(hla: HlaAlleleClass, y: Sequence, covariates=None, model: str = 
     if fl[T] & FLAG_RANK:
         raise ValueError("the covariates are collinear (the base model is rank-deficient)")
     d = per
-    row = np.array(plan.row, np.int64)
-    known = row >= 0
-    at = np.maximum(row, 0)
-    est = np.where(known[:, None], coef[at, 1:1 + d], np.nan)
-    sd = np.where(known[:, None], se[at, 1:1 + d], np.nan)
-    deviance = np.where(known, dev_t[at], np.nan)
-    iterations = np.where(known, it[at], 0).astype(np.int32)
-    flags = np.where(known, fl[at], FLAG_RANK).astype(np.int32)
+    est, sd, deviance = plan.spread(coef[:T, 1:1 + d]), plan.spread(se[:T, 1:1 + d]), plan.spread(dev_t[:T])
+    iterations = plan.spread(it[:T], 0).astype(np.int32)
+    flags = plan.spread(fl[:T], FLAG_RANK).astype(np.int32)
     lower, upper, pval = _wald(est, sd)
     bad = ((flags | fl[T]) & (FLAG_MAXIT | FLAG_RANK)) != 0
     lrt_stat = np.where(bad, np.nan, dev_t[T] - deviance)
@@ -220,11 +231,7 @@ def hlaAssocGlm(hla: HlaAlleleClass, y: Sequence, covariates=None, model: str = 
     lrt_p[bad | (df == 0)] = np.nan
     if show_or:
         est, lower, upper = np.exp(est), np.exp(lower), np.exp(upper)
-    used = [0] + list(range(COV0, COV0 + q))
-    b_est, b_se = coef[T, used], se[T, used]
-    b_lo, b_up, b_p = _wald(b_est, b_se)
-    base = {"name": ["(Intercept)"] + cov_names, "est": b_est, "se": b_se, "lower": b_lo, "upper": b_up, "pval": b_p,
-            "deviance": float(dev_t[T]), "iterations": int(it[T]), "flags": int(fl[T])}
+    base = _base_model(coef[T], se[T], dev_t[T], it[T], fl[T], [0] + list(range(COV0, COV0 + q)), cov_names)
     return HlaAssocGlmResult(model, hla.locus, plan.names, ("h1", "h2") if d == 2 else ("h",), est, sd, lower, upper, pval, deviance,
                              lrt_stat, lrt_p, iterations, flags, base, plan.n_samp, plan.n_case, plan.n_excluded, bool(show_or))
 

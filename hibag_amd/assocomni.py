@@ -20,8 +20,9 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib
-from .assoc import MODELS, _Plan, _ptr
-from .assocglm import FLAG_MAXIT, FLAG_RANK, _DeviceGlm, _covariates, _kept_index, _wald
+from .assoc import MODELS, _check_model, _Plan, _ptr, chisq_sf
+from .assocglm import (FLAG_MAXIT, FLAG_RANK, _base_model, _check_fit_control, _condition_list, _condition_tests, _design, _DeviceGlm,
+                       _wald)
 from .groups import HlaAlleleGroups
 from .hibag import HlaAlleleClass
 
@@ -34,10 +35,6 @@ OMNIBUS_MODELS = ("additive", "dominant", "recessive")
 
 class _DeviceOmni(_DeviceGlm):
     """The tests of one cohort on the device, with the set regression."""
-
-    def __init__(self, a1, a2, y, n_allele, group_of, model: int):
-        super().__init__(a1, a2, y, n_allele, group_of, model)
-        self.n_rows = self.n_tests * (2 if MODELS[model] == "genotype" else 1)
 
     def row_sums(self) -> np.ndarray:
         """int32 [feature rows]: each row's sum over the kept samples."""
@@ -61,30 +58,6 @@ class _DeviceOmni(_DeviceGlm):
                                                        0 if covar is None else covar.shape[0], _ptr(weight), maxit, epsilon,
                                                        _ptr(coef), _ptr(se), _ptr(dev), _ptr(it), _ptr(fl), _ptr(df)))
         return coef, se, dev, it, fl, df
-
-
-def chisq_sf(x: float, df: int) -> float:
-    """The upper tail of chi-square with an integer ``df`` >= 1, in closed form: for even df
-    ``exp(-x/2) sum_{k < df/2} (x/2)^k / k!``; for odd df ``erfc(sqrt(x/2))`` plus the half-integer terms
-    ``exp(-x/2) sum_{k=1}^{(df-1)/2} (x/2)^(k-1/2) / Gamma(k+1/2)``.  Every term is positive: nothing cancels."""
-    if math.isnan(x) or df < 1:
-        return math.nan
-    h = max(x, 0.0) / 2.0
-    if df % 2 == 0:
-        term, total = 1.0, 1.0
-        for k in range(1, df // 2):
-            term = term * h / k
-            total = total + term
-        return math.exp(-h) * total
-    tail = math.erfc(math.sqrt(h))
-    if df == 1:
-        return tail
-    term = math.sqrt(h) / (math.sqrt(math.pi) / 2.0)       # (x/2)^(1/2) / Gamma(3/2)
-    total = term
-    for k in range(1, (df - 1) // 2):
-        term = term * h / (k + 0.5)
-        total = total + term
-    return tail + math.exp(-h) * total
 
 
 class HlaAssocOmnibusResult:
@@ -187,33 +160,14 @@ def hlaAssocOmnibus(hla: HlaAlleleClass, y: Sequence, groups: HlaAlleleGroups, c
     (``_backend``: the tests' seam -- a class with the interface of ``_DeviceOmni`` that stands in for the device.)"""
     if model == "genotype":
         raise ValueError("the genotype coding is not built for the omnibus test: additive, dominant or recessive")
-    if model not in OMNIBUS_MODELS:
-        raise ValueError("'arg' should be one of " + ", ".join(f'"{m}"' for m in OMNIBUS_MODELS))
+    _check_model(model, OMNIBUS_MODELS)
     if not isinstance(groups, HlaAlleleGroups):
         raise TypeError("'groups' must be an HlaAlleleGroups")
-    if isinstance(maxit, bool) or not isinstance(maxit, (int, np.integer)) or maxit < 1:
-        raise ValueError("maxit must be an integer >= 1")
-    if isinstance(epsilon, bool) or not isinstance(epsilon, (int, float, np.integer, np.floating)) or not epsilon > 0:
-        raise ValueError("epsilon must be > 0")
+    _check_fit_control(maxit, epsilon)
     plan = _Plan(hla, y, prob_threshold, groups)
-    sel = _kept_index(hla, prob_threshold)
-    assert len(sel) == plan.n_samp
-    cov_names, cov = _covariates(covariates, len(hla.sample_id))
-    cov = np.ascontiguousarray(cov[:, sel])
-    if not np.isfinite(cov).all():
-        bad = cov_names[int(np.flatnonzero(~np.isfinite(cov).all(axis=1))[0])]
-        raise ValueError(f"covariate {bad!r} has a missing or non-finite value: subset the samples first")
+    cov_names, cov, weight = _design(plan, hla, covariates, use_prob)
     n_user = len(cov_names)
-    weight = None
-    if use_prob:
-        if hla.prob is None:
-            raise ValueError("No posterior probability in 'hla' ('hla.prob' should be available).")
-        weight = np.ascontiguousarray(np.asarray(hla.prob, np.float64)[sel])
-        if not (np.isfinite(weight).all() and (weight >= 0).all()):
-            raise ValueError("use_prob: the posterior probabilities of the kept samples must be finite and >= 0")
-    condition = [condition] if isinstance(condition, str) else list(condition) if condition is not None else []
-    if any(not isinstance(c, str) for c in condition):
-        raise ValueError("'condition' is a list of partition or test names")
+    condition = _condition_list(condition, "partition or test")
     part_names = list(groups.names)
     part_rows = _partition_rows(plan, groups)
     for c in condition:
@@ -233,11 +187,9 @@ def hlaAssocOmnibus(hla: HlaAlleleClass, y: Sequence, groups: HlaAlleleGroups, c
                 cond_rows += [part_rows[p][lv] for lv in sets[p]]
                 cov_names += [f"h[{c}:{groups.levels[p][lv]}]" for lv in sets[p]]
             else:
-                row = plan.row[plan.names.index(c)]
-                if row < 0:
-                    raise ValueError(f"condition: no allele of the data belongs to {c!r}")
-                cond_rows.append(row)
-                cov_names.append(f"h[{c}]")
+                rows, names = _condition_tests(plan, [c], 1)
+                cond_rows += rows
+                cov_names += names
         q = len(cov_names)
         if q > MAX_COVAR:
             raise ValueError(f"{q} covariate columns ({q - n_user} conditioned columns included); at most {MAX_COVAR}")
@@ -271,11 +223,7 @@ def hlaAssocOmnibus(hla: HlaAlleleClass, y: Sequence, groups: HlaAlleleGroups, c
         est.append(e)
         sd.append(d)
     wald = [_wald(e, d) for e, d in zip(est, sd)]
-    used = [0] + cov_slots
-    b_est, b_se = coef[P, used], se[P, used]
-    b_lo, b_up, b_p = _wald(b_est, b_se)
-    base = {"name": ["(Intercept)"] + cov_names, "est": b_est, "se": b_se, "lower": b_lo, "upper": b_up, "pval": b_p,
-            "deviance": float(dev_t[P]), "iterations": int(it[P]), "flags": int(fl[P])}
+    base = _base_model(coef[P], se[P], dev_t[P], it[P], fl[P], [0] + cov_slots, cov_names)
     reference = [None if r < 0 else groups.levels[p][r] for p, r in enumerate(ref)]
     return HlaAssocOmnibusResult(model, hla.locus, part_names, np.array(carried_n, np.int32), reference, df, deviance, lrt_stat, lrt_p,
                                  np.array(it[:P], np.int32), np.array(fl[:P], np.int32), level_names, est, sd,

@@ -17,14 +17,13 @@ Not built: ``use_prob`` weights (and exchangeability under weights), other famil
 from __future__ import annotations
 
 import math
-import secrets
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
 from . import _lib
-from .assoc import MODELS, _Plan, _perm_p, _ptr
-from .assocglm import MAX_COVAR, Z975, _DeviceGlm, _covariates, _kept_index
+from .assoc import MODELS, _attach_perm, _check_model, _check_perm, _Plan, _ptr
+from .assocglm import MAX_COVAR, Z975, _condition_list, _condition_tests, _design, _DeviceGlm
 from .groups import HlaAlleleGroups
 from .hibag import HlaAlleleClass
 
@@ -35,10 +34,6 @@ class _DeviceQuant(_DeviceGlm):
     """The tests of one cohort on the device, with a quantitative trait on them (``hibag_hip_quant``)."""
 
     _q = None
-
-    def __init__(self, a1, a2, y, n_allele, group_of, model):
-        super().__init__(a1, a2, y, n_allele, group_of, model)
-        self._rows = self.n_tests * (2 if model == MODELS.index("genotype") else 1)
 
     def quant(self, y: np.ndarray, covar: Optional[np.ndarray]) -> None:
         """The trait ``y`` [n_kept] and the covariates [q, n_kept]; ValueError for collinear covariates."""
@@ -72,7 +67,7 @@ class _DeviceQuant(_DeviceGlm):
 
     def quant_observed(self):
         """(proj [rows, n_basis], g [rows], rr, stat [n_tests], flags [n_tests])."""
-        proj, g, rr = np.empty((self._rows, self.n_basis)), np.empty(self._rows), np.empty(1)
+        proj, g, rr = np.empty((self.n_rows, self.n_basis)), np.empty(self.n_rows), np.empty(1)
         stat, flags = np.empty(self.n_tests), np.empty(self.n_tests, np.int32)
         _lib.check(_lib.lib().hibag_hip_assoc_quant_observed(self._q, _ptr(proj), _ptr(g), _ptr(rr), _ptr(stat), _ptr(flags)))
         return proj, g, float(rr[0]), stat, flags
@@ -315,14 +310,10 @@ def hlaAssocQuant(hla: HlaAlleleClass, y: Sequence, covariates=None, model: str 
     bit 1.  Not built: ``use_prob`` weights (``use_prob=True`` is a ValueError: a weighted permutation test needs
     exchangeability under weights), other families, interactions, and permutations for
     ``hlaAssocGlm``.  (``_backend``: the tests' seam, a class with the interface of ``_DeviceQuant``.)"""
-    if model not in MODELS:
-        raise ValueError("'arg' should be one of " + ", ".join(f'"{m}"' for m in MODELS))
+    _check_model(model)
     if use_prob:
         raise ValueError("use_prob is not built for hlaAssocQuant (DESIGN.md section 25, 'Not built'): threshold the calls with prob_threshold")
-    if isinstance(n_perm, bool) or not isinstance(n_perm, (int, np.integer)) or n_perm < 0:
-        raise ValueError("n_perm must be an integer >= 0")
-    if seed is not None and (isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 1 << 64):
-        raise ValueError("seed must be an integer in 0 .. 2^64 - 1")
+    n_perm, seed = _check_perm(n_perm, seed)
     if not isinstance(hla, HlaAlleleClass):
         raise TypeError('inherits(hla, "hlaAlleleClass") is not TRUE')
     n_all = len(hla.sample_id)
@@ -332,39 +323,21 @@ def hlaAssocQuant(hla: HlaAlleleClass, y: Sequence, covariates=None, model: str 
         raise ValueError("y must be numeric") from None
     if len(yv) != n_all:
         raise ValueError(f"'hla' and 'y' must have the same length ({n_all} samples, {len(yv)} values of y)")
-    plan = _Plan(hla, np.zeros(n_all, np.int32), prob_threshold, groups)
-    sel = _kept_index(hla, prob_threshold)
-    assert len(sel) == plan.n_samp
-    yk = np.ascontiguousarray(yv[sel])
+    plan = _Plan(hla, None, prob_threshold, groups)
+    yk = np.ascontiguousarray(yv[plan.sel])
     if not np.isfinite(yk).all():
         raise ValueError("y has a missing or non-finite value: subset the samples first")
-    cov_names, cov = _covariates(covariates, n_all)
-    cov = np.ascontiguousarray(cov[:, sel])
-    if not np.isfinite(cov).all():
-        bad = cov_names[int(np.flatnonzero(~np.isfinite(cov).all(axis=1))[0])]
-        raise ValueError(f"covariate {bad!r} has a missing or non-finite value: subset the samples first")
-    condition = [condition] if isinstance(condition, str) else list(condition) if condition is not None else []
-    if any(not isinstance(c, str) for c in condition):
-        raise ValueError("'condition' is a list of test names")
+    cov_names, cov, _ = _design(plan, hla, covariates, False)
+    condition = _condition_list(condition)
     per = 2 if model == "genotype" else 1
-    cond_rows = []
-    for c in condition:
-        if c not in plan.names:
-            raise ValueError(f"condition: {c!r} is not a test of this analysis")
-        row = plan.row[plan.names.index(c)]
-        if row < 0:
-            raise ValueError(f"condition: no allele of the data belongs to {c!r}")
-        cond_rows.append(row)
-        cov_names += [f"h[{c}]"] if per == 1 else [f"h1[{c}]", f"h2[{c}]"]
+    cond_rows, cond_names = _condition_tests(plan, condition, per)
+    cov_names += cond_names
     q = len(cov_names)
     if q > MAX_COVAR:
         raise ValueError(f"{q} covariate columns ({len(condition)} conditioned tests included); at most {MAX_COVAR}")
     n, nb = plan.n_samp, q + 1
     if n - nb - per < 1:
         raise ValueError(f"{n} samples leave no residual degree of freedom with {q} covariate columns")
-    n_perm = int(n_perm)
-    if n_perm > 0 and seed is None:
-        seed = secrets.randbits(64)
 
     backend = _DeviceQuant if _backend is None else _backend
     with backend(plan.a1, plan.a2, plan.y, len(plan.alleles), plan.group_of, MODELS.index(model)) as dev:
@@ -375,19 +348,11 @@ def hlaAssocQuant(hla: HlaAlleleClass, y: Sequence, covariates=None, model: str 
         d_cnt, d_S1, d_S2, ybar = dev.quant_classes()
         d_proj, d_g, rr, d_stat, d_flags = dev.quant_observed()
         if n_perm > 0:
-            max_stat, d_count = dev.quant_permute(int(seed), 1, n_perm)
+            max_stat, d_count = dev.quant_permute(seed, 1, n_perm)
 
     d_avg, d_tp, d_ap = _class_columns(model, d_cnt, d_S1, d_S2, ybar, n)
     d_est, d_se, d_rss, d_df = _fit_columns(model, n, nb, d_cnt, d_proj, d_g, rr, d_stat, d_flags)
-    # the result's tests from the device's: a level unknown to the device has no carrier
-    row = np.array(plan.row, np.int64)
-    known = row >= 0
-    at = np.maximum(row, 0)
-
-    def pick(a, fill=np.nan):
-        a = np.asarray(a)
-        return np.where(known.reshape((-1,) + (1,) * (a.ndim - 1)), a[at], fill)
-
+    pick, known = plan.spread, np.array(plan.row) >= 0
     counts = pick(d_cnt[:, :d_avg.shape[1]], 0).astype(np.int64)
     counts[~known, 0] = n
     avg = pick(d_avg)
@@ -404,9 +369,7 @@ def hlaAssocQuant(hla: HlaAlleleClass, y: Sequence, covariates=None, model: str 
                               None if d_ap is None else pick(d_ap), ("h1", "h2") if per == 2 else ("h",), est, se, est - Z975 * se,
                               est + Z975 * se, pval, stat, stat_p, rss, df, flags, cov_names, plan.n_samp, plan.n_excluded)
     if n_perm > 0:
-        count = np.where(known, d_count[at], 0)
-        res.perm_p, res.perm_p_adj = _perm_p(stat, count, max_stat, n_perm)
-        res.max_stat, res.n_perm, res.seed = max_stat, n_perm, int(seed)
+        _attach_perm(res, plan, stat, max_stat, d_count, n_perm, seed)
     return res
 
 

@@ -13,10 +13,12 @@
 //
 // hibag_hip_assoc_glm_sets (hlaAssocOmnibus; kernels: hibag_k_glmw.h) fits one regression per SET of
 // feature rows -- all residues of a position at once -- over a 32-slot design, with aliased columns dropped; it shares the
-// buffers of hibag_hip_assoc_glm.
+// buffers and the driver (`GlmCall`) of hibag_hip_assoc_glm.
 //
 // hibag_hip_assoc_quant_* (hlaAssocQuant; kernels: hibag_k_quant.h) test a quantitative trait on the
-// same feature rows, through a handle of their own that borrows this one; they are at the end of the file.
+// same feature rows, through a handle of their own that borrows this one; they are at the end of the file.  The two
+// permutation sides share one panel driver (`panel_perms`, `check_perm_range`, `for_each_panel`, `PermOut`, `download_panels`),
+// and every function that enqueues work on host memory follows one drain rule (`enqueued`): the first namespace below.
 
 #include "hibag_internal.h"
 #include "hibag_k_assoc.h"
@@ -26,13 +28,98 @@
 
 using hibag_detail::DevBuf;
 
+namespace {
+
+struct TempBuf : DevBuf { ~TempBuf() { release(); } };   // a buffer of one function's frame
+
+// The drain rule.  HIP_TRY returns on the spot, and what an entry has enqueued by then may still read from, or write into,
+// memory of the frame that is left or of the caller.  So every function that enqueues such work does it inside `body`, which
+// ends with its own wait for the stream; when `body` fails part-way, the stream is drained before the frame goes away.
+// Host memory that a copy touches is therefore declared OUTSIDE `body`: its own locals are gone before the drain.
+template <class Body> int enqueued(hipStream_t st, Body body)
+{
+	const int rc = body();
+	if (rc) (void)hipStreamSynchronize(st);
+	return rc;
+}
+
+// Permutations of one panel of a call for `n`: the variable `env` (read per call), else `budget` bytes at `per_perm` bytes a
+// permutation in whole tiles, one tile at least; never above 2^22.  `whole_tiles` (the quantitative side, whose kernels work
+// on whole tiles): the variable's value and the call's count are rounded to whole tiles too, else taken as they are.
+int panel_perms(const char *env, size_t budget, size_t per_perm, int tile, bool whole_tiles, int64_t n)
+{
+	const char *e = getenv(env);
+	long pp = e && *e ? strtol(e, nullptr, 10) : 0;
+	const bool given = pp > 0;
+	if (!given) pp = (long)(budget / per_perm);
+	pp = std::min<long>(pp, 1 << 22);
+	if (whole_tiles || !given) pp = std::max<long>(pp / tile * tile, tile);
+	return (int)std::min<int64_t>(pp, whole_tiles ? (n + tile - 1) / tile * tile : n);
+}
+
+// permutations perm0 .. perm0 + n - 1 of `entry`; `observed` is what permutation 0 stands for
+int check_perm_range(const char *entry, const char *observed, uint64_t perm0, uint64_t n)
+{
+	if (perm0 < 1 || perm0 + n < perm0)
+		return hibag_fail(HIBAG_HIP_EINVAL, "%s: permutations are numbered from 1 (0 is the observed %s) and stay below 2^64", entry, observed);
+	return 0;
+}
+
+// panel(done, n_lab) for the panels of `pp` that cover [0, n)
+template <class Panel> int for_each_panel(int64_t n, int pp, Panel panel)
+{
+	for (int64_t done = 0; done < n; done += pp)
+		if (int rc = panel(done, (int)std::min<int64_t>(pp, n - done))) return rc;
+	return 0;
+}
+
+// `n` rows of `width` bytes to `out`: made panel by panel by make(done, n_lab) at `src` (row pitch `pitch`) and copied without
+// their padding; the next panel overwrites the buffer, so each one is on the host first
+template <class Make> int download_panels(hipStream_t st, int n, int pp, const void *src, size_t pitch, size_t width, void *out, Make make)
+{
+	return enqueued(st, [&]() -> int {
+		return for_each_panel(n, pp, [&](int64_t done, int n_lab) -> int {
+			if (int rc = make(done, n_lab)) return rc;
+			HIP_TRY(hipMemcpy2DAsync((char *)out + (size_t)done * width, width, src, pitch, width, (size_t)n_lab, hipMemcpyDeviceToHost, st));
+			HIP_TRY(hipStreamSynchronize(st));
+			return 0;
+		});
+	});
+}
+
+// What a permutation call accumulates on the device: every permutation's largest statistic and, per test, the number of
+// permutations at or above the observed statistic.
+struct PermOut {
+	DevBuf max_stat, count;                      // double [n_perm]; uint64 [n_test]
+
+	int reserve(int64_t n_perm, int T) { return max_stat.reserve(sizeof(double) * (size_t)n_perm) || count.reserve(sizeof(unsigned long long) * (size_t)T); }
+	void release() { max_stat.release(); count.release(); }
+
+	// one call: the counts zeroed, panel(done, n_lab) for every panel of `pp`, both outputs on the host
+	template <class Panel> int run(hipStream_t st, int T, int64_t n_perm, int pp, double *h_max, int64_t *h_count, Panel panel)
+	{
+		static_assert(sizeof(unsigned long long) == sizeof(int64_t), "the counts are copied as they are");
+		return enqueued(st, [&]() -> int {
+			HIP_TRY(hipMemsetAsync(count.p, 0, sizeof(unsigned long long) * (size_t)T, st));
+			if (int rc = for_each_panel(n_perm, pp, panel)) return rc;
+			HIP_TRY(hipMemcpyAsync(h_max, max_stat.p, sizeof(double) * (size_t)n_perm, hipMemcpyDeviceToHost, st));
+			HIP_TRY(hipMemcpyAsync(h_count, count.p, sizeof(int64_t) * (size_t)T, hipMemcpyDeviceToHost, st));
+			HIP_TRY(hipStreamSynchronize(st));
+			return 0;
+		});
+	}
+};
+
+} // namespace
+
 struct hibag_hip_assoc {
 	int device = 0;
 	AssocDims D;
 	int n_case = 0, rows = 0, kp = 0;
 	hipStream_t st = nullptr;
 	DevBuf feat, row_sum, stat_obs;              // int8 [rows][kp], int32 [rows], double [n_test]
-	DevBuf labels, gram, max_stat, count;        // per-call panel: int8 [pp][kp], int32 [rows][pp]; double [n_perm]; uint64 [n_test]
+	DevBuf labels, gram;                         // per-call panel: int8 [pp][kp], int32 [rows][pp]
+	PermOut out;                                 // per permutation call
 	DevBuf y;                                    // int8 [kp]: the kept samples' labels, zero padding (hibag_hip_assoc_glm)
 	DevBuf glm_in, glm_img, glm_wt, glm_fits, glm_out; // hibag_hip_assoc_glm: covariates and weights as given, the operand image, the padded weights, GlmFit [n_fit], the outputs
 	std::vector<int32_t> h_row_sum;              // the feature rows' sums [rows]
@@ -43,7 +130,8 @@ struct hibag_hip_assoc {
 	{
 		(void)hipSetDevice(device);
 		if (st) (void)hipStreamSynchronize(st);
-		for (DevBuf *b : {&feat, &row_sum, &stat_obs, &labels, &gram, &max_stat, &count, &y, &glm_in, &glm_img, &glm_wt, &glm_fits, &glm_out}) b->release();
+		for (DevBuf *b : {&feat, &row_sum, &stat_obs, &labels, &gram, &y, &glm_in, &glm_img, &glm_wt, &glm_fits, &glm_out}) b->release();
+		out.release();
 		if (st) (void)hipStreamDestroy(st);
 	}
 };
@@ -56,17 +144,10 @@ constexpr size_t kPanelBytes = (size_t)64 << 20; // default size of a panel's la
 
 size_t pad_to(size_t x, size_t m) { return (x + m - 1) / m * m; }
 
-// permutations of one panel: HIBAG_ASSOC_PANEL_PERMS (read per call), else about kPanelBytes per buffer in whole tiles
-int panel_perms(const hibag_hip_assoc *h, int64_t n_perm)
+int assoc_panel_perms(const hibag_hip_assoc *h, int64_t n)
 {
-	const char *e = getenv("HIBAG_ASSOC_PANEL_PERMS");
-	long pp = e && *e ? strtol(e, nullptr, 10) : 0;
-	if (pp <= 0) {
-		const size_t per = std::max<size_t>((size_t)h->kp, sizeof(int32_t) * (size_t)h->rows);
-		pp = (long)(kPanelBytes / per) / HIBAG_LD_TILE * HIBAG_LD_TILE;
-		pp = std::max<long>(pp, HIBAG_LD_TILE);
-	}
-	return (int)std::min<int64_t>(std::min<long>(pp, 1 << 22), n_perm);
+	return panel_perms("HIBAG_ASSOC_PANEL_PERMS", kPanelBytes, std::max<size_t>((size_t)h->kp, sizeof(int32_t) * (size_t)h->rows), HIBAG_LD_TILE,
+		false, n);
 }
 
 // C [rows][n_lab] (row stride n_lab) = features x labels
@@ -88,6 +169,76 @@ int enqueue_labels(hibag_hip_assoc *h, uint64_t seed, uint64_t p0, int n_lab)
 	return 0;
 }
 
+// The regression driver: what hibag_hip_assoc_glm and hibag_hip_assoc_glm_sets share.  An entry checks its arguments
+// (`check_control`, what is its own, `check_values`, in the order the messages have always had), decides its fit records
+// from the row sums, and hands them to `run` with its slot count and the launches of its two kernels.
+struct GlmOut { double *coef, *se, *dev; int32_t *it, *fl, *df; };   // the device's outputs, carved from glm_out
+
+struct GlmCall {
+	const char *entry;
+	hibag_hip_assoc *h;
+	const double *covar; int q;                  // [q][n]
+	const double *weight;                        // [n] or null
+	int maxit; double epsilon;
+	double *coef, *se, *deviance;                // the caller's [n_fit][slots] twice, [n_fit]
+	int32_t *iterations, *flags, *df_h;          // the caller's [n_fit]; df_h: null for an entry without it
+
+	int check_control(int max_covar) const
+	{
+		if (q < 0 || q > max_covar || (q > 0 && !covar)) return hibag_fail(HIBAG_HIP_EINVAL, "%s: %d covariates; 0 .. %d, with covar", entry, q, max_covar);
+		if (maxit < 1) return hibag_fail(HIBAG_HIP_EINVAL, "%s: maxit = %d; at least 1", entry, maxit);
+		if (!(epsilon > 0)) return hibag_fail(HIBAG_HIP_EINVAL, "%s: epsilon must be > 0", entry);
+		return 0;
+	}
+
+	int check_values() const
+	{
+		const int n = h->D.n;
+		for (size_t i = 0; i < (size_t)q * n; i++)
+			if (!std::isfinite(covar[i])) return hibag_fail(HIBAG_HIP_EINVAL, "%s: covariate %zu of kept sample %zu is not finite", entry, i / n, i % n);
+		if (weight)
+			for (int i = 0; i < n; i++)
+				if (!std::isfinite(weight[i]) || weight[i] < 0)
+					return hibag_fail(HIBAG_HIP_EINVAL, "%s: weight[%d] = %g; weights are finite and >= 0", entry, i, weight[i]);
+		return 0;
+	}
+
+	// Uploads the covariates, the weights and the `n_fit` fit records of `fit_bytes` each, has `image(d_cov, d_w)` build the
+	// operand image and `fit(O)` run the fits into the outputs O, and downloads them.
+	template <class Image, class Fit> int run(int slots, const void *fits, size_t fit_bytes, int n_fit, Image image, Fit fit) const
+	{
+		const int n = h->D.n, kp = h->kp;
+		const hipStream_t st = h->st;
+		HIP_TRY(hipSetDevice(h->device));
+		const size_t in_doubles = (size_t)q * n + (weight ? (size_t)n : 0), nf = (size_t)n_fit;
+		const size_t out_bytes = nf * (2 * slots * sizeof(double) + sizeof(double) + (df_h ? 3 : 2) * sizeof(int32_t));
+		if (h->glm_in.reserve(sizeof(double) * std::max<size_t>(in_doubles, 1)) || h->glm_img.reserve(sizeof(double) * slots * (size_t)kp) ||
+			h->glm_wt.reserve(sizeof(double) * (size_t)kp) || h->glm_fits.reserve(fit_bytes * nf) || h->glm_out.reserve(out_bytes))
+			return HIBAG_HIP_ENOMEM;
+		double *d_cov = h->glm_in.as<double>(), *d_w = weight ? d_cov + (size_t)q * n : nullptr;
+		GlmOut O;
+		O.coef = h->glm_out.as<double>(); O.se = O.coef + nf * slots; O.dev = O.se + nf * slots;
+		O.it = (int32_t *)(O.dev + nf); O.fl = O.it + nf; O.df = df_h ? O.fl + nf : nullptr;
+		return enqueued(h->st, [&]() -> int {
+			if (q) HIP_TRY(hipMemcpyAsync(d_cov, covar, sizeof(double) * (size_t)q * n, hipMemcpyHostToDevice, st));
+			if (weight) HIP_TRY(hipMemcpyAsync(d_w, weight, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, st));
+			HIP_TRY(hipMemcpyAsync(h->glm_fits.p, fits, fit_bytes * nf, hipMemcpyHostToDevice, st));
+			image(d_cov, d_w);
+			HIP_TRY(hipGetLastError());
+			fit(O);
+			if (hipGetLastError() != hipSuccess) return hibag_fail(HIBAG_HIP_ENODEV, "%s: a kernel launch failed", entry);
+			HIP_TRY(hipMemcpyAsync(coef, O.coef, sizeof(double) * nf * slots, hipMemcpyDeviceToHost, st));
+			HIP_TRY(hipMemcpyAsync(se, O.se, sizeof(double) * nf * slots, hipMemcpyDeviceToHost, st));
+			HIP_TRY(hipMemcpyAsync(deviance, O.dev, sizeof(double) * nf, hipMemcpyDeviceToHost, st));
+			HIP_TRY(hipMemcpyAsync(iterations, O.it, sizeof(int32_t) * nf, hipMemcpyDeviceToHost, st));
+			HIP_TRY(hipMemcpyAsync(flags, O.fl, sizeof(int32_t) * nf, hipMemcpyDeviceToHost, st));
+			if (df_h) HIP_TRY(hipMemcpyAsync(df_h, O.df, sizeof(int32_t) * nf, hipMemcpyDeviceToHost, st));
+			HIP_TRY(hipStreamSynchronize(st));
+			return 0;
+		});
+	}
+};
+
 // what hibag_hip_assoc_new does on the device: features, then the observed labelling as a panel of one
 int build(hibag_hip_assoc *h, const std::vector<int32_t> &a1, const std::vector<int32_t> &a2, const std::vector<int8_t> &y,
 	const std::vector<int32_t> &group_of, int n_allele, const std::vector<int32_t> &part, const std::vector<int32_t> &lev)
@@ -95,41 +246,41 @@ int build(hibag_hip_assoc *h, const std::vector<int32_t> &a1, const std::vector<
 	const int n = h->D.n, T = h->D.n_test, rows = h->rows, kp = h->kp;
 	HIP_TRY(hipSetDevice(h->device));
 	HIP_TRY(hipStreamCreateWithFlags(&h->st, hipStreamNonBlocking));
-	DevBuf d_a, d_g, d_t;                        // alleles [2][n], the partitions, part / level of every test: needed by k_assoc_features only
-	struct Release { DevBuf &a, &b, &c; ~Release() { a.release(); b.release(); c.release(); } } rel{d_a, d_g, d_t};
+	TempBuf d_a, d_g, d_t;                       // alleles [2][n], the partitions, part / level of every test: needed by k_assoc_features only
 	if (h->feat.reserve((size_t)rows * kp) || h->row_sum.reserve(sizeof(int32_t) * rows) || h->stat_obs.reserve(sizeof(double) * T) ||
 		h->labels.reserve((size_t)kp) || h->y.reserve((size_t)kp) || h->gram.reserve(sizeof(int32_t) * rows) ||
 		d_a.reserve(sizeof(int32_t) * 2 * std::max(n, 1)) || d_g.reserve(sizeof(int32_t) * group_of.size()) ||
 		d_t.reserve(sizeof(int32_t) * 2 * T))
 		return HIBAG_HIP_ENOMEM;
 	int32_t *da = d_a.as<int32_t>(), *dt = d_t.as<int32_t>();
-	if (n) {
-		HIP_TRY(hipMemcpyAsync(da, a1.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, h->st));
-		HIP_TRY(hipMemcpyAsync(da + n, a2.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, h->st));
-	}
-	HIP_TRY(hipMemcpyAsync(d_g.p, group_of.data(), sizeof(int32_t) * group_of.size(), hipMemcpyHostToDevice, h->st));
-	HIP_TRY(hipMemcpyAsync(dt, part.data(), sizeof(int32_t) * T, hipMemcpyHostToDevice, h->st));
-	HIP_TRY(hipMemcpyAsync(dt + T, lev.data(), sizeof(int32_t) * T, hipMemcpyHostToDevice, h->st));
-	HIP_TRY(hipMemsetAsync(h->row_sum.p, 0, sizeof(int32_t) * rows, h->st));
-	hipLaunchKernelGGL(k_assoc_features, dim3((kp + 1023) / 1024, rows), dim3(256), 0, h->st, da, da + n, h->D, d_g.as<int32_t>(),
-		n_allele, dt, dt + T, kp, h->feat.as<int8_t>(), h->row_sum.as<int32_t>());
-	HIP_TRY(hipGetLastError());
-
-	// the observed labelling: y over the kept samples, zero padding
-	std::vector<int8_t> row((size_t)kp, 0);
+	std::vector<int8_t> row((size_t)kp, 0);      // the observed labelling: y over the kept samples, zero padding
 	std::copy(y.begin(), y.end(), row.begin());
-	HIP_TRY(hipMemcpyAsync(h->labels.p, row.data(), (size_t)kp, hipMemcpyHostToDevice, h->st));
-	HIP_TRY(hipMemcpyAsync(h->y.p, row.data(), (size_t)kp, hipMemcpyHostToDevice, h->st));
-	launch_gram(h, h->labels.as<int8_t>(), 1, h->gram.as<int32_t>());
-	hipLaunchKernelGGL(k_assoc_stat, dim3(1), dim3(64), 0, h->st, h->gram.as<int32_t>(), (size_t)1, 1, h->D, h->row_sum.as<int32_t>(),
-		h->stat_obs.as<double>(), (double *)nullptr, (const double *)nullptr, (unsigned long long *)nullptr);
-	HIP_TRY(hipGetLastError());
 	std::vector<int32_t> x((size_t)rows), r((size_t)rows);
 	h->h_stat.resize((size_t)T);
-	HIP_TRY(hipMemcpyAsync(x.data(), h->gram.p, sizeof(int32_t) * rows, hipMemcpyDeviceToHost, h->st));
-	HIP_TRY(hipMemcpyAsync(r.data(), h->row_sum.p, sizeof(int32_t) * rows, hipMemcpyDeviceToHost, h->st));
-	HIP_TRY(hipMemcpyAsync(h->h_stat.data(), h->stat_obs.p, sizeof(double) * T, hipMemcpyDeviceToHost, h->st));
-	HIP_TRY(hipStreamSynchronize(h->st));
+	if (int rc = enqueued(h->st, [&]() -> int {
+		if (n) {
+			HIP_TRY(hipMemcpyAsync(da, a1.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, h->st));
+			HIP_TRY(hipMemcpyAsync(da + n, a2.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, h->st));
+		}
+		HIP_TRY(hipMemcpyAsync(d_g.p, group_of.data(), sizeof(int32_t) * group_of.size(), hipMemcpyHostToDevice, h->st));
+		HIP_TRY(hipMemcpyAsync(dt, part.data(), sizeof(int32_t) * T, hipMemcpyHostToDevice, h->st));
+		HIP_TRY(hipMemcpyAsync(dt + T, lev.data(), sizeof(int32_t) * T, hipMemcpyHostToDevice, h->st));
+		HIP_TRY(hipMemsetAsync(h->row_sum.p, 0, sizeof(int32_t) * rows, h->st));
+		hipLaunchKernelGGL(k_assoc_features, dim3((kp + 1023) / 1024, rows), dim3(256), 0, h->st, da, da + n, h->D, d_g.as<int32_t>(),
+			n_allele, dt, dt + T, kp, h->feat.as<int8_t>(), h->row_sum.as<int32_t>());
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipMemcpyAsync(h->labels.p, row.data(), (size_t)kp, hipMemcpyHostToDevice, h->st));
+		HIP_TRY(hipMemcpyAsync(h->y.p, row.data(), (size_t)kp, hipMemcpyHostToDevice, h->st));
+		launch_gram(h, h->labels.as<int8_t>(), 1, h->gram.as<int32_t>());
+		hipLaunchKernelGGL(k_assoc_stat, dim3(1), dim3(64), 0, h->st, h->gram.as<int32_t>(), (size_t)1, 1, h->D, h->row_sum.as<int32_t>(),
+			h->stat_obs.as<double>(), (double *)nullptr, (const double *)nullptr, (unsigned long long *)nullptr);
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipMemcpyAsync(x.data(), h->gram.p, sizeof(int32_t) * rows, hipMemcpyDeviceToHost, h->st));
+		HIP_TRY(hipMemcpyAsync(r.data(), h->row_sum.p, sizeof(int32_t) * rows, hipMemcpyDeviceToHost, h->st));
+		HIP_TRY(hipMemcpyAsync(h->h_stat.data(), h->stat_obs.p, sizeof(double) * T, hipMemcpyDeviceToHost, h->st));
+		HIP_TRY(hipStreamSynchronize(h->st));
+		return 0;
+	})) return rc;
 	h->h_row_sum = r;
 
 	// the tables, rows (none, carrier) or (none, het, hom) x columns (control, case), from the exact sums
@@ -248,56 +399,35 @@ int hibag_hip_assoc_permute(hibag_hip_assoc *h, uint64_t seed, uint64_t perm0, i
 {
 	if (!h || n_perm < 0 || !count_point || (n_perm > 0 && !max_stat))
 		return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_permute: null argument or n_perm < 0");
-	if (perm0 < 1 || perm0 + (uint64_t)n_perm < perm0)
-		return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_permute: permutations are numbered from 1 (0 is the observed labelling) and stay below 2^64");
+	if (int rc = check_perm_range("hibag_hip_assoc_permute", "labelling", perm0, (uint64_t)n_perm)) return rc;
 	const int T = h->D.n_test;
 	std::fill(count_point, count_point + T, (int64_t)0);
 	if (n_perm == 0) return 0;
 	HIP_TRY(hipSetDevice(h->device));
-	const int pp = panel_perms(h, n_perm);
-	if (h->labels.reserve((size_t)pp * h->kp) || h->gram.reserve(sizeof(int32_t) * (size_t)h->rows * pp) ||
-		h->max_stat.reserve(sizeof(double) * (size_t)n_perm) || h->count.reserve(sizeof(unsigned long long) * T))
+	const int pp = assoc_panel_perms(h, n_perm);
+	if (h->labels.reserve((size_t)pp * h->kp) || h->gram.reserve(sizeof(int32_t) * (size_t)h->rows * pp) || h->out.reserve(n_perm, T))
 		return HIBAG_HIP_ENOMEM;
-	HIP_TRY(hipMemsetAsync(h->count.p, 0, sizeof(unsigned long long) * T, h->st));
-	for (int64_t done = 0; done < n_perm; done += pp) {
-		const int n_lab = (int)std::min<int64_t>(pp, n_perm - done);
-		int e = enqueue_labels(h, seed, perm0 + (uint64_t)done, n_lab);
-		if (e) { (void)hipStreamSynchronize(h->st); return e; }
+	return h->out.run(h->st, T, n_perm, pp, max_stat, count_point, [&](int64_t done, int n_lab) -> int {
+		if (int e = enqueue_labels(h, seed, perm0 + (uint64_t)done, n_lab)) return e;
 		launch_gram(h, h->labels.as<int8_t>(), n_lab, h->gram.as<int32_t>());
 		hipLaunchKernelGGL(k_assoc_stat, dim3((n_lab + 63) / 64), dim3(64), 0, h->st, h->gram.as<int32_t>(), (size_t)n_lab, n_lab, h->D,
-			h->row_sum.as<int32_t>(), (double *)nullptr, h->max_stat.as<double>() + done, h->stat_obs.as<double>(),
-			h->count.as<unsigned long long>());
-		if (hipGetLastError() != hipSuccess) {
-			(void)hipStreamSynchronize(h->st);
-			return hibag_fail(HIBAG_HIP_ENODEV, "hibag_hip_assoc_permute: a kernel launch failed");
-		}
-	}
-	static_assert(sizeof(unsigned long long) == sizeof(int64_t), "the counts are copied as they are");
-	HIP_TRY(hipMemcpyAsync(max_stat, h->max_stat.p, sizeof(double) * (size_t)n_perm, hipMemcpyDeviceToHost, h->st));
-	HIP_TRY(hipMemcpyAsync(count_point, h->count.p, sizeof(int64_t) * T, hipMemcpyDeviceToHost, h->st));
-	HIP_TRY(hipStreamSynchronize(h->st));
-	return 0;
+			h->row_sum.as<int32_t>(), (double *)nullptr, h->out.max_stat.as<double>() + done, h->stat_obs.as<double>(),
+			h->out.count.as<unsigned long long>());
+		if (hipGetLastError() != hipSuccess) return hibag_fail(HIBAG_HIP_ENODEV, "hibag_hip_assoc_permute: a kernel launch failed");
+		return 0;
+	});
 }
 
 int hibag_hip_assoc_labels(hibag_hip_assoc *h, uint64_t seed, uint64_t perm0, int n, int8_t *out)
 {
 	if (!h || n < 0 || (n > 0 && !out)) return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_labels: null argument or n < 0");
-	if (perm0 < 1 || perm0 + (uint64_t)n < perm0)
-		return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_labels: permutations are numbered from 1 (0 is the observed labelling) and stay below 2^64");
+	if (int rc = check_perm_range("hibag_hip_assoc_labels", "labelling", perm0, (uint64_t)n)) return rc;
 	if (n == 0 || h->D.n == 0) return 0;
 	HIP_TRY(hipSetDevice(h->device));
-	const int pp = panel_perms(h, n);
+	const int pp = assoc_panel_perms(h, n);
 	if (h->labels.reserve((size_t)pp * h->kp)) return HIBAG_HIP_ENOMEM;
-	for (int done = 0; done < n; done += pp) {
-		const int n_lab = std::min(pp, n - done);
-		int e = enqueue_labels(h, seed, perm0 + (uint64_t)done, n_lab);
-		if (e) { (void)hipStreamSynchronize(h->st); return e; }
-		// the rows without their padding; the next panel overwrites the buffer, so this one is on the host first
-		HIP_TRY(hipMemcpy2DAsync(out + (size_t)done * h->D.n, (size_t)h->D.n, h->labels.p, (size_t)h->kp, (size_t)h->D.n, (size_t)n_lab,
-			hipMemcpyDeviceToHost, h->st));
-		HIP_TRY(hipStreamSynchronize(h->st));
-	}
-	return 0;
+	return download_panels(h->st, n, pp, h->labels.p, (size_t)h->kp, (size_t)h->D.n, out,
+		[&](int64_t done, int n_lab) -> int { return enqueue_labels(h, seed, perm0 + (uint64_t)done, n_lab); });
 }
 
 int hibag_hip_assoc_n_kept(const hibag_hip_assoc *h) { return h ? h->D.n : hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_n_kept: null handle"); }
@@ -309,29 +439,19 @@ int hibag_hip_assoc_feature_rows(hibag_hip_assoc *h, int row0, int n_rows, int8_
 		return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_feature_rows: rows %d .. %d + %d are outside the handle's %d", row0, row0, n_rows, h->rows);
 	if (n_rows == 0 || h->D.n == 0) return 0;
 	HIP_TRY(hipSetDevice(h->device));
-	HIP_TRY(hipMemcpy2DAsync(out, (size_t)h->D.n, h->feat.as<int8_t>() + (size_t)row0 * h->kp, (size_t)h->kp, (size_t)h->D.n, (size_t)n_rows,
-		hipMemcpyDeviceToHost, h->st));
-	HIP_TRY(hipStreamSynchronize(h->st));
-	return 0;
+	return download_panels(h->st, n_rows, n_rows, h->feat.as<int8_t>() + (size_t)row0 * h->kp, (size_t)h->kp, (size_t)h->D.n, out,
+		[](int64_t, int) -> int { return 0; });             // the rows are there already: one panel, nothing to make
 }
 
 int hibag_hip_assoc_glm(hibag_hip_assoc *h, const double *covar, int n_covar, const double *weight, int maxit, double epsilon,
 	double *coef, double *se, double *deviance, int32_t *iterations, int32_t *flags)
 {
 	if (!h || !coef || !se || !deviance || !iterations || !flags) return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_glm: null argument");
-	if (n_covar < 0 || n_covar > HIBAG_HIP_GLM_MAX_COVAR || (n_covar > 0 && !covar))
-		return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_glm: %d covariates; 0 .. %d, with covar", n_covar, HIBAG_HIP_GLM_MAX_COVAR);
-	if (maxit < 1) return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_glm: maxit = %d; at least 1", maxit);
-	if (!(epsilon > 0)) return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_glm: epsilon must be > 0");
 	static_assert(GLM_COV0 + HIBAG_HIP_GLM_MAX_COVAR == GLM_SLOTS - 1, "intercept, two h slots, the covariates, then z");
+	const GlmCall call{"hibag_hip_assoc_glm", h, covar, n_covar, weight, maxit, epsilon, coef, se, deviance, iterations, flags, nullptr};
+	if (int rc = call.check_control(HIBAG_HIP_GLM_MAX_COVAR)) return rc;
+	if (int rc = call.check_values()) return rc;
 	const int n = h->D.n, T = h->D.n_test, kp = h->kp, q = n_covar, n_fit = T + 1;
-	for (size_t i = 0; i < (size_t)q * n; i++)
-		if (!std::isfinite(covar[i]))
-			return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_glm: covariate %zu of kept sample %zu is not finite", i / n, i % n);
-	if (weight)
-		for (int i = 0; i < n; i++)
-			if (!std::isfinite(weight[i]) || weight[i] < 0)
-				return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_glm: weight[%d] = %g; weights are finite and >= 0", i, weight[i]);
 
 	// the fits: which feature rows stand behind slots 1 and 2, decided from the integer row sums
 	std::vector<GlmFit> fits((size_t)n_fit);
@@ -351,34 +471,15 @@ int hibag_hip_assoc_glm(hibag_hip_assoc *h, const double *covar, int n_covar, co
 	}
 	fits[(size_t)T] = GlmFit{-1, -1};
 
-	HIP_TRY(hipSetDevice(h->device));
-	const size_t in_doubles = (size_t)q * n + (weight ? (size_t)n : 0);
-	const size_t out_bytes = (size_t)n_fit * (2 * GLM_SLOTS * sizeof(double) + sizeof(double) + 2 * sizeof(int32_t));
-	if (h->glm_in.reserve(sizeof(double) * std::max<size_t>(in_doubles, 1)) || h->glm_img.reserve(sizeof(double) * GLM_SLOTS * (size_t)kp) ||
-		h->glm_wt.reserve(sizeof(double) * (size_t)kp) || h->glm_fits.reserve(sizeof(GlmFit) * (size_t)n_fit) || h->glm_out.reserve(out_bytes))
-		return HIBAG_HIP_ENOMEM;
-	double *d_cov = h->glm_in.as<double>(), *d_w = weight ? d_cov + (size_t)q * n : nullptr;
-	if (q) HIP_TRY(hipMemcpyAsync(d_cov, covar, sizeof(double) * (size_t)q * n, hipMemcpyHostToDevice, h->st));
-	if (weight) HIP_TRY(hipMemcpyAsync(d_w, weight, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, h->st));
-	HIP_TRY(hipMemcpyAsync(h->glm_fits.p, fits.data(), sizeof(GlmFit) * (size_t)n_fit, hipMemcpyHostToDevice, h->st));
-	hipLaunchKernelGGL(k_glm_image, dim3((unsigned)(((size_t)kp * GLM_SLOTS + 255) / 256)), dim3(256), 0, h->st, d_cov, d_w, n, q, kp,
-		h->glm_img.as<double>(), h->glm_wt.as<double>());
-	HIP_TRY(hipGetLastError());
-	double *d_coef = h->glm_out.as<double>(), *d_se = d_coef + (size_t)n_fit * GLM_SLOTS, *d_dev = d_se + (size_t)n_fit * GLM_SLOTS;
-	int32_t *d_it = (int32_t *)(d_dev + n_fit), *d_fl = d_it + n_fit;
-	hipLaunchKernelGGL(k_glm_fit, dim3(n_fit), dim3(GLM_WAVES * 64), 0, h->st, h->glm_img.as<double>(), h->glm_wt.as<double>(),
-		h->y.as<int8_t>(), h->feat.as<int8_t>(), h->glm_fits.as<GlmFit>(), n, kp, q, maxit, epsilon, d_coef, d_se, d_dev, d_it, d_fl);
-	if (hipGetLastError() != hipSuccess) {
-		(void)hipStreamSynchronize(h->st);
-		return hibag_fail(HIBAG_HIP_ENODEV, "hibag_hip_assoc_glm: a kernel launch failed");
-	}
-	HIP_TRY(hipMemcpyAsync(coef, d_coef, sizeof(double) * (size_t)n_fit * GLM_SLOTS, hipMemcpyDeviceToHost, h->st));
-	HIP_TRY(hipMemcpyAsync(se, d_se, sizeof(double) * (size_t)n_fit * GLM_SLOTS, hipMemcpyDeviceToHost, h->st));
-	HIP_TRY(hipMemcpyAsync(deviance, d_dev, sizeof(double) * (size_t)n_fit, hipMemcpyDeviceToHost, h->st));
-	HIP_TRY(hipMemcpyAsync(iterations, d_it, sizeof(int32_t) * (size_t)n_fit, hipMemcpyDeviceToHost, h->st));
-	HIP_TRY(hipMemcpyAsync(flags, d_fl, sizeof(int32_t) * (size_t)n_fit, hipMemcpyDeviceToHost, h->st));
-	HIP_TRY(hipStreamSynchronize(h->st));
-	return 0;
+	return call.run(GLM_SLOTS, fits.data(), sizeof(GlmFit), n_fit,
+		[&](const double *d_cov, const double *d_w) {
+			hipLaunchKernelGGL(k_glm_image, dim3((unsigned)(((size_t)kp * GLM_SLOTS + 255) / 256)), dim3(256), 0, h->st, d_cov, d_w, n, q, kp,
+				h->glm_img.as<double>(), h->glm_wt.as<double>());
+		},
+		[&](const GlmOut &O) {
+			hipLaunchKernelGGL(k_glm_fit, dim3(n_fit), dim3(GLM_WAVES * 64), 0, h->st, h->glm_img.as<double>(), h->glm_wt.as<double>(),
+				h->y.as<int8_t>(), h->feat.as<int8_t>(), h->glm_fits.as<GlmFit>(), n, kp, q, maxit, epsilon, O.coef, O.se, O.dev, O.it, O.fl);
+		});
 }
 
 int hibag_hip_assoc_row_sums(hibag_hip_assoc *h, int32_t *out)
@@ -397,10 +498,8 @@ int hibag_hip_assoc_glm_sets(hibag_hip_assoc *h, const int32_t *set_start, const
 	static_assert(GLMW_SLOTS == HIBAG_HIP_GLM_WIDE_SLOTS && GLMW_MAX_ROWS == GLMW_SLOTS - 2, "intercept, the h slots and covariates, then z");
 	static_assert(GLM_FLAG_ALIASED == HIBAG_HIP_GLM_ALIASED && GLM_FLAG_TOO_WIDE == HIBAG_HIP_GLM_TOO_WIDE, "the header's flags");
 	static_assert(sizeof(GlmWideFit) == sizeof(int) * (2 + GLMW_MAX_ROWS), "uploaded as it is");
-	if (n_covar < 0 || n_covar > GLMW_MAX_ROWS - 1 || (n_covar > 0 && !covar))
-		return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_glm_sets: %d covariates; 0 .. %d, with covar", n_covar, GLMW_MAX_ROWS - 1);
-	if (maxit < 1) return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_glm_sets: maxit = %d; at least 1", maxit);
-	if (!(epsilon > 0)) return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_glm_sets: epsilon must be > 0");
+	const GlmCall call{"hibag_hip_assoc_glm_sets", h, covar, n_covar, weight, maxit, epsilon, coef, se, deviance, iterations, flags, df_h};
+	if (int rc = call.check_control(GLMW_MAX_ROWS - 1)) return rc;
 	if (n_sets < 0 || n_sets > kMaxTests || !set_start || set_start[0] != 0)
 		return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_glm_sets: need 0 <= n_sets <= %d and set_start with set_start[0] = 0", kMaxTests);
 	for (int t = 0; t < n_sets; t++)
@@ -408,13 +507,7 @@ int hibag_hip_assoc_glm_sets(hibag_hip_assoc *h, const int32_t *set_start, const
 			return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_glm_sets: set_start is not monotone at set %d", t);
 	if (set_start[n_sets] > 0 && !set_rows) return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_glm_sets: set_rows is null");
 	const int n = h->D.n, kp = h->kp, q = n_covar, n_fit = n_sets + 1, room = GLMW_MAX_ROWS - q;
-	for (size_t i = 0; i < (size_t)q * n; i++)
-		if (!std::isfinite(covar[i]))
-			return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_glm_sets: covariate %zu of kept sample %zu is not finite", i / n, i % n);
-	if (weight)
-		for (int i = 0; i < n; i++)
-			if (!std::isfinite(weight[i]) || weight[i] < 0)
-				return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_glm_sets: weight[%d] = %g; weights are finite and >= 0", i, weight[i]);
+	if (int rc = call.check_values()) return rc;
 
 	// the fits: a set's rows behind slots 1, 2, ... in the order given; what cannot be fitted is decided from the integer row
 	// sums.  H, the h slots of the call's layout, is the largest set that is fitted.
@@ -450,40 +543,16 @@ int hibag_hip_assoc_glm_sets(hibag_hip_assoc *h, const int32_t *set_start, const
 	base.flags0 = 0;
 	std::fill(base.rows, base.rows + GLMW_MAX_ROWS, -1);
 
-	HIP_TRY(hipSetDevice(h->device));
-	const size_t in_doubles = (size_t)q * n + (weight ? (size_t)n : 0);
-	const size_t out_bytes = (size_t)n_fit * (2 * GLMW_SLOTS * sizeof(double) + sizeof(double) + 3 * sizeof(int32_t));
-	if (h->glm_in.reserve(sizeof(double) * std::max<size_t>(in_doubles, 1)) || h->glm_img.reserve(sizeof(double) * GLMW_SLOTS * (size_t)kp) ||
-		h->glm_wt.reserve(sizeof(double) * (size_t)kp) || h->glm_fits.reserve(sizeof(GlmWideFit) * (size_t)n_fit) || h->glm_out.reserve(out_bytes))
-		return HIBAG_HIP_ENOMEM;
-	double *d_cov = h->glm_in.as<double>(), *d_w = weight ? d_cov + (size_t)q * n : nullptr;
-	// everything that is enqueued: `fits` and the caller's arrays are read and written asynchronously, so a failure part-way
-	// waits for the stream before this frame goes away
-	auto enqueue = [&]() -> int {
-		if (q) HIP_TRY(hipMemcpyAsync(d_cov, covar, sizeof(double) * (size_t)q * n, hipMemcpyHostToDevice, h->st));
-		if (weight) HIP_TRY(hipMemcpyAsync(d_w, weight, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, h->st));
-		HIP_TRY(hipMemcpyAsync(h->glm_fits.p, fits.data(), sizeof(GlmWideFit) * (size_t)n_fit, hipMemcpyHostToDevice, h->st));
-		hipLaunchKernelGGL(k_glm_image_wide, dim3((unsigned)(((size_t)kp * GLMW_SLOTS + 255) / 256)), dim3(256), 0, h->st, d_cov, d_w, n, q, H,
-			kp, h->glm_img.as<double>(), h->glm_wt.as<double>());
-		HIP_TRY(hipGetLastError());
-		double *d_coef = h->glm_out.as<double>(), *d_se = d_coef + (size_t)n_fit * GLMW_SLOTS, *d_dev = d_se + (size_t)n_fit * GLMW_SLOTS;
-		int32_t *d_it = (int32_t *)(d_dev + n_fit), *d_fl = d_it + n_fit, *d_df = d_fl + n_fit;
-		hipLaunchKernelGGL(k_glm_fit_wide, dim3(n_fit), dim3(GLM_WAVES * 64), 0, h->st, h->glm_img.as<double>(), h->glm_wt.as<double>(),
-			h->y.as<int8_t>(), h->feat.as<int8_t>(), h->glm_fits.as<GlmWideFit>(), n, kp, q, H, maxit, epsilon, d_coef, d_se, d_dev, d_it,
-			d_fl, d_df);
-		if (hipGetLastError() != hipSuccess) return hibag_fail(HIBAG_HIP_ENODEV, "hibag_hip_assoc_glm_sets: a kernel launch failed");
-		HIP_TRY(hipMemcpyAsync(coef, d_coef, sizeof(double) * (size_t)n_fit * GLMW_SLOTS, hipMemcpyDeviceToHost, h->st));
-		HIP_TRY(hipMemcpyAsync(se, d_se, sizeof(double) * (size_t)n_fit * GLMW_SLOTS, hipMemcpyDeviceToHost, h->st));
-		HIP_TRY(hipMemcpyAsync(deviance, d_dev, sizeof(double) * (size_t)n_fit, hipMemcpyDeviceToHost, h->st));
-		HIP_TRY(hipMemcpyAsync(iterations, d_it, sizeof(int32_t) * (size_t)n_fit, hipMemcpyDeviceToHost, h->st));
-		HIP_TRY(hipMemcpyAsync(flags, d_fl, sizeof(int32_t) * (size_t)n_fit, hipMemcpyDeviceToHost, h->st));
-		HIP_TRY(hipMemcpyAsync(df_h, d_df, sizeof(int32_t) * (size_t)n_fit, hipMemcpyDeviceToHost, h->st));
-		return 0;
-	};
-	const int rc = enqueue();
-	if (rc) { (void)hipStreamSynchronize(h->st); return rc; }
-	HIP_TRY(hipStreamSynchronize(h->st));
-	return 0;
+	return call.run(GLMW_SLOTS, fits.data(), sizeof(GlmWideFit), n_fit,
+		[&](const double *d_cov, const double *d_w) {
+			hipLaunchKernelGGL(k_glm_image_wide, dim3((unsigned)(((size_t)kp * GLMW_SLOTS + 255) / 256)), dim3(256), 0, h->st, d_cov, d_w, n, q, H,
+				kp, h->glm_img.as<double>(), h->glm_wt.as<double>());
+		},
+		[&](const GlmOut &O) {
+			hipLaunchKernelGGL(k_glm_fit_wide, dim3(n_fit), dim3(GLM_WAVES * 64), 0, h->st, h->glm_img.as<double>(), h->glm_wt.as<double>(),
+				h->y.as<int8_t>(), h->feat.as<int8_t>(), h->glm_fits.as<GlmWideFit>(), n, kp, q, H, maxit, epsilon, O.coef, O.se, O.dev, O.it,
+				O.fl, O.df);
+		});
 }
 
 } // extern "C"
@@ -501,7 +570,8 @@ struct hibag_hip_quant {
 	int nb = 0;                                  // basis rows: the constant and the covariates
 	double ybar = 0, h_rr = 0, gram_ms = 0;
 	DevBuf basis, yt, yc, tests, stat_obs;       // double [nb][kp], [kp], [kp]; QuantTest [n_test]; double [n_test]
-	DevBuf perm, panel, rr, gram, max_stat, count; // per-call panel: int32 [pp][kp], double [pp / 16][kp / 4][64], [pp], [rows][pp]; double [n_perm]; uint64 [n_test]
+	DevBuf perm, panel, rr, gram;                // per-call panel: int32 [pp][kp], double [pp / 16][kp / 4][64], [pp], [rows][pp]
+	PermOut out;                                 // per permutation call
 	std::vector<int64_t> h_cnt;                  // [n_test][3]
 	std::vector<double> h_S1, h_S2, h_proj, h_g, h_stat; // [n_test][3] twice, [rows][nb], [rows], [n_test]
 	std::vector<int32_t> h_flags;                // [n_test]
@@ -512,7 +582,8 @@ struct hibag_hip_quant {
 		if (!h) return;
 		(void)hipSetDevice(h->device);
 		if (h->st) (void)hipStreamSynchronize(h->st);
-		for (DevBuf *b : {&basis, &yt, &yc, &tests, &stat_obs, &perm, &panel, &rr, &gram, &max_stat, &count}) b->release();
+		for (DevBuf *b : {&basis, &yt, &yc, &tests, &stat_obs, &perm, &panel, &rr, &gram}) b->release();
+		out.release();
 		for (hipEvent_t e : ev) (void)hipEventDestroy(e);
 	}
 };
@@ -521,15 +592,9 @@ namespace {
 
 constexpr size_t kQuantPanelBytes = (size_t)256 << 20;   // default size of a panel's residual operand
 
-// permutations of one panel, in whole tiles: HIBAG_QUANT_PANEL_PERMS (read per call), else about kQuantPanelBytes of residuals
-int quant_panel_perms(const hibag_hip_quant *q, int64_t n_perm)
+int quant_panel_perms(const hibag_hip_quant *q, int64_t n)
 {
-	const char *e = getenv("HIBAG_QUANT_PANEL_PERMS");
-	long pp = e && *e ? strtol(e, nullptr, 10) : 0;
-	if (pp <= 0) pp = (long)(kQuantPanelBytes / (sizeof(double) * (size_t)q->h->kp));
-	pp = std::min<long>(pp, 1 << 22);
-	pp = std::max<long>(pp / QUANT_TILE * QUANT_TILE, QUANT_TILE);
-	return (int)std::min<int64_t>(pp, (n_perm + QUANT_TILE - 1) / QUANT_TILE * QUANT_TILE);
+	return panel_perms("HIBAG_QUANT_PANEL_PERMS", kQuantPanelBytes, sizeof(double) * (size_t)q->h->kp, QUANT_TILE, true, n);
 }
 
 int quant_reserve_panel(hibag_hip_quant *q, int pp)
@@ -641,8 +706,7 @@ int quant_build(hibag_hip_quant *q, const std::vector<double> &Q, const std::vec
 	hibag_hip_assoc *h = q->h;
 	const int n = h->D.n, kp = h->kp, T = h->D.n_test, rows = h->rows, nb = q->nb;
 	HIP_TRY(hipSetDevice(h->device));
-	DevBuf d_cls, d_proj;                        // int64 [T][3] and double [T][3] twice; double [rows][nb]
-	struct Release { DevBuf &a, &b; ~Release() { a.release(); b.release(); } } rel{d_cls, d_proj};
+	TempBuf d_cls, d_proj;                       // int64 [T][3] and double [T][3] twice; double [rows][nb]
 	if (q->basis.reserve(sizeof(double) * (size_t)nb * kp) || q->yt.reserve(sizeof(double) * (size_t)kp) ||
 		q->yc.reserve(sizeof(double) * (size_t)kp) || q->tests.reserve(sizeof(QuantTest) * (size_t)T) ||
 		q->stat_obs.reserve(sizeof(double) * (size_t)T) || d_cls.reserve((size_t)T * 3 * (sizeof(long long) + 2 * sizeof(double))) ||
@@ -652,37 +716,37 @@ int quant_build(hibag_hip_quant *q, const std::vector<double> &Q, const std::vec
 	for (int k = 0; k < nb; k++) std::copy(&Q[(size_t)k * n], &Q[(size_t)k * n] + n, &img[(size_t)k * kp]);
 	std::copy(yt.begin(), yt.end(), &img[(size_t)nb * kp]);
 	std::copy(yc.begin(), yc.end(), &img[(size_t)(nb + 1) * kp]);
-	HIP_TRY(hipMemcpyAsync(q->basis.p, img.data(), sizeof(double) * (size_t)nb * kp, hipMemcpyHostToDevice, h->st));
-	HIP_TRY(hipMemcpyAsync(q->yt.p, &img[(size_t)nb * kp], sizeof(double) * (size_t)kp, hipMemcpyHostToDevice, h->st));
-	HIP_TRY(hipMemcpyAsync(q->yc.p, &img[(size_t)(nb + 1) * kp], sizeof(double) * (size_t)kp, hipMemcpyHostToDevice, h->st));
-	long long *d_cnt = d_cls.as<long long>();
-	double *d_S1 = (double *)(d_cnt + (size_t)T * 3), *d_S2 = d_S1 + (size_t)T * 3;
-	hipLaunchKernelGGL(k_quant_classes, dim3(T), dim3(256), 0, h->st, h->feat.as<int8_t>(), kp, n, h->D.model == ASSOC_GENOTYPE ? 1 : 0,
-		q->yc.as<double>(), d_cnt, d_S1, d_S2);
-	hipLaunchKernelGGL(k_quant_proj, dim3(rows), dim3(256), 0, h->st, h->feat.as<int8_t>(), kp, n, q->basis.as<double>(), nb,
-		d_proj.as<double>());
-	HIP_TRY(hipGetLastError());
 	q->h_cnt.resize((size_t)T * 3); q->h_S1.resize((size_t)T * 3); q->h_S2.resize((size_t)T * 3);
 	q->h_proj.resize((size_t)rows * nb); q->h_g.resize((size_t)rows); q->h_stat.resize((size_t)T);
-	static_assert(sizeof(long long) == sizeof(int64_t), "the counts are copied as they are");
-	HIP_TRY(hipMemcpyAsync(q->h_cnt.data(), d_cnt, sizeof(int64_t) * (size_t)T * 3, hipMemcpyDeviceToHost, h->st));
-	HIP_TRY(hipMemcpyAsync(q->h_S1.data(), d_S1, sizeof(double) * (size_t)T * 3, hipMemcpyDeviceToHost, h->st));
-	HIP_TRY(hipMemcpyAsync(q->h_S2.data(), d_S2, sizeof(double) * (size_t)T * 3, hipMemcpyDeviceToHost, h->st));
-	HIP_TRY(hipMemcpyAsync(q->h_proj.data(), d_proj.p, sizeof(double) * (size_t)rows * nb, hipMemcpyDeviceToHost, h->st));
-	HIP_TRY(hipStreamSynchronize(h->st));
-
 	std::vector<QuantTest> tests;
-	quant_tests(q, tests, q->h_flags);
-	HIP_TRY(hipMemcpyAsync(q->tests.p, tests.data(), sizeof(QuantTest) * (size_t)T, hipMemcpyHostToDevice, h->st));
-	// the observed trait: permutation 0, a panel of its own
-	int e = quant_enqueue_panel(q, 0, 0, 1, QUANT_TILE, q->stat_obs.as<double>(), nullptr, nullptr, nullptr, nullptr, nullptr);
-	if (e) { (void)hipStreamSynchronize(h->st); return e; }
-	HIP_TRY(hipMemcpy2DAsync(q->h_g.data(), sizeof(double), q->gram.p, sizeof(double) * QUANT_TILE, sizeof(double), (size_t)rows,
-		hipMemcpyDeviceToHost, h->st));
-	HIP_TRY(hipMemcpyAsync(&q->h_rr, q->rr.p, sizeof(double), hipMemcpyDeviceToHost, h->st));
-	HIP_TRY(hipMemcpyAsync(q->h_stat.data(), q->stat_obs.p, sizeof(double) * (size_t)T, hipMemcpyDeviceToHost, h->st));
-	HIP_TRY(hipStreamSynchronize(h->st));
-	return 0;
+	return enqueued(h->st, [&]() -> int {
+		HIP_TRY(hipMemcpyAsync(q->basis.p, img.data(), sizeof(double) * (size_t)nb * kp, hipMemcpyHostToDevice, h->st));
+		HIP_TRY(hipMemcpyAsync(q->yt.p, &img[(size_t)nb * kp], sizeof(double) * (size_t)kp, hipMemcpyHostToDevice, h->st));
+		HIP_TRY(hipMemcpyAsync(q->yc.p, &img[(size_t)(nb + 1) * kp], sizeof(double) * (size_t)kp, hipMemcpyHostToDevice, h->st));
+		long long *d_cnt = d_cls.as<long long>();
+		double *d_S1 = (double *)(d_cnt + (size_t)T * 3), *d_S2 = d_S1 + (size_t)T * 3;
+		hipLaunchKernelGGL(k_quant_classes, dim3(T), dim3(256), 0, h->st, h->feat.as<int8_t>(), kp, n, h->D.model == ASSOC_GENOTYPE ? 1 : 0,
+			q->yc.as<double>(), d_cnt, d_S1, d_S2);
+		hipLaunchKernelGGL(k_quant_proj, dim3(rows), dim3(256), 0, h->st, h->feat.as<int8_t>(), kp, n, q->basis.as<double>(), nb,
+			d_proj.as<double>());
+		HIP_TRY(hipGetLastError());
+		static_assert(sizeof(long long) == sizeof(int64_t), "the counts are copied as they are");
+		HIP_TRY(hipMemcpyAsync(q->h_cnt.data(), d_cnt, sizeof(int64_t) * (size_t)T * 3, hipMemcpyDeviceToHost, h->st));
+		HIP_TRY(hipMemcpyAsync(q->h_S1.data(), d_S1, sizeof(double) * (size_t)T * 3, hipMemcpyDeviceToHost, h->st));
+		HIP_TRY(hipMemcpyAsync(q->h_S2.data(), d_S2, sizeof(double) * (size_t)T * 3, hipMemcpyDeviceToHost, h->st));
+		HIP_TRY(hipMemcpyAsync(q->h_proj.data(), d_proj.p, sizeof(double) * (size_t)rows * nb, hipMemcpyDeviceToHost, h->st));
+		HIP_TRY(hipStreamSynchronize(h->st));
+		quant_tests(q, tests, q->h_flags);
+		HIP_TRY(hipMemcpyAsync(q->tests.p, tests.data(), sizeof(QuantTest) * (size_t)T, hipMemcpyHostToDevice, h->st));
+		// the observed trait: permutation 0, a panel of its own
+		if (int e = quant_enqueue_panel(q, 0, 0, 1, QUANT_TILE, q->stat_obs.as<double>(), nullptr, nullptr, nullptr, nullptr, nullptr)) return e;
+		HIP_TRY(hipMemcpy2DAsync(q->h_g.data(), sizeof(double), q->gram.p, sizeof(double) * QUANT_TILE, sizeof(double), (size_t)rows,
+			hipMemcpyDeviceToHost, h->st));
+		HIP_TRY(hipMemcpyAsync(&q->h_rr, q->rr.p, sizeof(double), hipMemcpyDeviceToHost, h->st));
+		HIP_TRY(hipMemcpyAsync(q->h_stat.data(), q->stat_obs.p, sizeof(double) * (size_t)T, hipMemcpyDeviceToHost, h->st));
+		HIP_TRY(hipStreamSynchronize(h->st));
+		return 0;
+	});
 }
 
 } // namespace
@@ -765,8 +829,7 @@ int hibag_hip_assoc_quant_permute(hibag_hip_quant *q, uint64_t seed, uint64_t pe
 {
 	if (!q || n_perm < 0 || !count_point || (n_perm > 0 && !max_stat))
 		return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_quant_permute: null argument or n_perm < 0");
-	if (perm0 < 1 || perm0 + (uint64_t)n_perm < perm0)
-		return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_quant_permute: permutations are numbered from 1 (0 is the observed trait) and stay below 2^64");
+	if (int rc = check_perm_range("hibag_hip_assoc_quant_permute", "trait", perm0, (uint64_t)n_perm)) return rc;
 	hibag_hip_assoc *h = q->h;
 	const int T = h->D.n_test;
 	std::fill(count_point, count_point + T, (int64_t)0);
@@ -775,25 +838,18 @@ int hibag_hip_assoc_quant_permute(hibag_hip_quant *q, uint64_t seed, uint64_t pe
 	HIP_TRY(hipSetDevice(h->device));
 	const int pp = quant_panel_perms(q, n_perm);
 	const size_t n_panel = (size_t)((n_perm + pp - 1) / pp);
-	if (quant_reserve_panel(q, pp) || q->max_stat.reserve(sizeof(double) * (size_t)n_perm) ||
-		q->count.reserve(sizeof(unsigned long long) * (size_t)T))
-		return HIBAG_HIP_ENOMEM;
+	if (quant_reserve_panel(q, pp) || q->out.reserve(n_perm, T)) return HIBAG_HIP_ENOMEM;
 	while (q->ev.size() < 2 * n_panel) {
 		hipEvent_t e;
 		HIP_TRY(hipEventCreate(&e));
 		q->ev.push_back(e);
 	}
-	HIP_TRY(hipMemsetAsync(q->count.p, 0, sizeof(unsigned long long) * (size_t)T, h->st));
-	size_t k = 0;
-	for (int64_t done = 0; done < n_perm; done += pp, k++) {
-		const int n_lab = (int)std::min<int64_t>(pp, n_perm - done);
-		int e = quant_enqueue_panel(q, seed, perm0 + (uint64_t)done, n_lab, (size_t)pp, nullptr, q->max_stat.as<double>() + done,
-			q->stat_obs.as<double>(), q->count.as<unsigned long long>(), q->ev[2 * k], q->ev[2 * k + 1]);
-		if (e) { (void)hipStreamSynchronize(h->st); return e; }
-	}
-	HIP_TRY(hipMemcpyAsync(max_stat, q->max_stat.p, sizeof(double) * (size_t)n_perm, hipMemcpyDeviceToHost, h->st));
-	HIP_TRY(hipMemcpyAsync(count_point, q->count.p, sizeof(int64_t) * (size_t)T, hipMemcpyDeviceToHost, h->st));
-	HIP_TRY(hipStreamSynchronize(h->st));
+	int rc = q->out.run(h->st, T, n_perm, pp, max_stat, count_point, [&](int64_t done, int n_lab) -> int {
+		const size_t k = (size_t)(done / pp);
+		return quant_enqueue_panel(q, seed, perm0 + (uint64_t)done, n_lab, (size_t)pp, nullptr, q->out.max_stat.as<double>() + done,
+			q->stat_obs.as<double>(), q->out.count.as<unsigned long long>(), q->ev[2 * k], q->ev[2 * k + 1]);
+	});
+	if (rc) return rc;
 	for (size_t j = 0; j < n_panel; j++) {
 		float ms = 0;
 		HIP_TRY(hipEventElapsedTime(&ms, q->ev[2 * j], q->ev[2 * j + 1]));
@@ -805,23 +861,19 @@ int hibag_hip_assoc_quant_permute(hibag_hip_quant *q, uint64_t seed, uint64_t pe
 int hibag_hip_assoc_quant_perm_rows(hibag_hip_quant *q, uint64_t seed, uint64_t perm0, int n, int32_t *out)
 {
 	if (!q || n < 0 || (n > 0 && !out)) return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_quant_perm_rows: null argument or n < 0");
-	if (perm0 < 1 || perm0 + (uint64_t)n < perm0)
-		return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_quant_perm_rows: permutations are numbered from 1 (0 is the observed trait) and stay below 2^64");
+	if (int rc = check_perm_range("hibag_hip_assoc_quant_perm_rows", "trait", perm0, (uint64_t)n)) return rc;
 	if (n == 0) return 0;
 	hibag_hip_assoc *h = q->h;
 	HIP_TRY(hipSetDevice(h->device));
 	const int pp = quant_panel_perms(q, n), kp = h->kp, ns = h->D.n;
 	if (q->perm.reserve(sizeof(int32_t) * (size_t)pp * kp)) return HIBAG_HIP_ENOMEM;
-	for (int done = 0; done < n; done += pp) {
-		const int n_lab = std::min(pp, n - done);
-		hipLaunchKernelGGL(k_quant_perm, dim3((n_lab + 63) / 64), dim3(64), 0, h->st, ns, kp, seed, perm0 + (uint64_t)done, n_lab,
-			q->perm.as<int32_t>());
-		HIP_TRY(hipGetLastError());
-		HIP_TRY(hipMemcpy2DAsync(out + (size_t)done * ns, sizeof(int32_t) * (size_t)ns, q->perm.p, sizeof(int32_t) * (size_t)kp,
-			sizeof(int32_t) * (size_t)ns, (size_t)n_lab, hipMemcpyDeviceToHost, h->st));
-		HIP_TRY(hipStreamSynchronize(h->st));
-	}
-	return 0;
+	return download_panels(h->st, n, pp, q->perm.p, sizeof(int32_t) * (size_t)kp, sizeof(int32_t) * (size_t)ns, out,
+		[&](int64_t done, int n_lab) -> int {
+			hipLaunchKernelGGL(k_quant_perm, dim3((n_lab + 63) / 64), dim3(64), 0, h->st, ns, kp, seed, perm0 + (uint64_t)done, n_lab,
+				q->perm.as<int32_t>());
+			HIP_TRY(hipGetLastError());
+			return 0;
+		});
 }
 
 int hibag_hip_assoc_quant_gram_ms(const hibag_hip_quant *q, double *ms)

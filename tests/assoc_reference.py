@@ -3,7 +3,9 @@
 ``tests_of`` / ``features`` are the tests and their 0/1/2 feature rows, ``labels`` the permuted label rows (selection sampling
 on Philox4x32-10 of tests/draws_reference.py), ``chisq_2x2`` / ``chisq_3x2`` the statistics with the stated operation order
 (numpy's float64 operations round once each, as the device's do without contraction), ``observed`` / ``permute`` what the
-device entries return, ``chisq_p`` / ``fisher_p`` the host p-values and ``assoc_test`` the whole table."""
+device entries return, ``chisq_p`` / ``fisher_p`` the host p-values and ``assoc_test`` the whole table.  ``Backend``,
+``kept_columns``, ``allele_names``, ``gap_partition`` and ``hla_of`` are what the restatements of the other association entries
+(tests/assoc*_reference.py) share."""
 
 from __future__ import annotations
 
@@ -117,6 +119,15 @@ def _stats(model, F, rsum, L, n, n_case):
     return st, x
 
 
+def max_and_count(st, stat):
+    """(max_stat [n_perm], count_point int64 [T]) of the permuted statistics st [T, n_perm] against the observed stat [T]: the
+    largest statistic of every permutation (NaN where all are NaN) and, per test, the permutations with st >= stat."""
+    best = np.where(np.isnan(st), -1.0, st).max(axis=0) if len(st) else np.full(st.shape[1], -1.0)
+    with np.errstate(invalid="ignore"):
+        count = (st >= stat[:, None]).sum(axis=1).astype(np.int64)
+    return np.where(best < 0, np.nan, best), count
+
+
 class Analysis:
     """The tests of one cohort: ``a1``, ``a2`` (NA_INTEGER = unknown), ``y`` 0 / 1, as hibag_hip_assoc_new takes them."""
 
@@ -151,10 +162,53 @@ class Analysis:
     def permute(self, seed, perm0, n_perm):
         """(max_stat [n_perm], count_point int64 [T]) of permutations perm0 .. perm0 + n_perm - 1."""
         st, _ = _stats(self.model, self.F, self.rsum, self.labels(seed, perm0, n_perm), self.n, self.n_case)
-        best = np.where(np.isnan(st), -1.0, st).max(axis=0) if self.n_tests else np.full(n_perm, -1.0)
-        with np.errstate(invalid="ignore"):
-            count = (st >= self.stat[:, None]).sum(axis=1).astype(np.int64)
-        return np.where(best < 0, np.nan, best), count
+        return max_and_count(st, self.stat)
+
+
+class Backend:
+    """The cohort behind the interface every ``_backend`` seam of hibag_amd's association entries drives; a restatement adds
+    its entry's methods."""
+
+    dtype = np.float64
+
+    def __init__(self, a1, a2, y, n_allele, group_of, model):
+        self.model = MODELS[model]
+        self.A = Analysis(a1, a2, y, n_allele, group_of, self.model)
+        self.n_tests, self.n_kept = self.A.n_tests, self.A.n
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        pass
+
+    def feature_rows(self, row0, n_rows):
+        return self.A.F[row0:row0 + n_rows].astype(np.int8)
+
+
+def kept_columns(a1, a2, *columns):
+    """The columns (last axis = samples) restricted to the samples with two known alleles."""
+    ok = (np.asarray(a1) != NA_INTEGER) & (np.asarray(a2) != NA_INTEGER)
+    return [np.ascontiguousarray(np.asarray(c)[..., ok]) for c in columns]
+
+
+def allele_names(n_allele):
+    return [f"{k + 1:02d}:01" for k in range(n_allele)]        # (sorted order = index order)
+
+
+def gap_partition(n_allele):
+    """group_of [1, n_allele] of one partition whose level 1 is empty (levels 0, 2, 3 are in use)."""
+    return np.where(np.arange(n_allele) % 3 == 0, 0, 2 + np.arange(n_allele) % 2)[None, :].astype(np.int32)
+
+
+def hla_of(a1, a2, prob, n_allele, gap=None, locus="A"):
+    """(hla, names, groups or None): the cohort of allele indices as the entries take it, the alleles under ``allele_names``;
+    ``gap``: a ``gap_partition`` as the groups ``pos``, which name one level more than the partition has."""
+    import hibag_amd as hb
+    names = allele_names(n_allele)
+    hla = hb.HlaAlleleClass(locus=locus, sample_id=[f"s{i}" for i in range(len(a1))], allele1=[None if a < 0 else names[a] for a in a1],
+                            allele2=[None if a < 0 else names[a] for a in a2], prob=prob)
+    return hla, names, None if gap is None else hb.HlaAlleleGroups(names, ["pos"], [["x", "gap", "y", "z", "beyond"]], gap)
 
 
 def chisq_p(st, df):

@@ -11,6 +11,7 @@ from __future__ import annotations
 import numpy as np
 
 import assoc_reference as AR
+from assoc_reference import allele_names, kept_columns       # noqa: F401  (the tests reach them through this module)
 
 MODELS = AR.MODELS
 SLOTS, COV0, MAX_COVAR = 16, 3, 12
@@ -166,24 +167,8 @@ def assoc_glm(a1, a2, y, n_allele, group_of, model, covar=None, weight=None, max
     return glm_rows(A.F, model, covar, weight, A.y, maxit, epsilon, dtype)
 
 
-class Backend:
+class Backend(AR.Backend):
     """The restatement behind the interface of hibag_amd.assocglm._DeviceGlm (``hlaAssocGlm(..., _backend=Backend)``)."""
-
-    dtype = np.float64
-
-    def __init__(self, a1, a2, y, n_allele, group_of, model):
-        self.model = MODELS[model]
-        self.A = AR.Analysis(a1, a2, y, n_allele, group_of, self.model)
-        self.n_tests, self.n_kept = self.A.n_tests, self.A.n
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        pass
-
-    def feature_rows(self, row0, n_rows):
-        return self.A.F[row0:row0 + n_rows].astype(np.int8)
 
     def glm(self, covar, weight, maxit, epsilon):
         r = glm_rows(self.A.F, self.model, covar, weight, self.A.y, maxit, epsilon, self.dtype)
@@ -211,29 +196,15 @@ def cohort(n, n_allele, q, seed, partition=False):
     a[rng.choice(n, 3, replace=False), rng.integers(0, 2, 3)] = AR.NA_INTEGER
     prob = rng.uniform(0.3, 1.0, n)
     prob[rng.choice(n, 2, replace=False)] = 0.0
-    g = np.where(np.arange(n_allele) % 3 == 0, 0, 2 + np.arange(n_allele) % 2)[None, :].astype(np.int32) if partition else None
+    g = AR.gap_partition(n_allele) if partition else None
     return np.ascontiguousarray(a[:, 0]), np.ascontiguousarray(a[:, 1]), y, g, covar, prob
-
-
-def kept_columns(a1, a2, *columns):
-    """The columns (last axis = samples) restricted to the samples with two known alleles."""
-    ok = (np.asarray(a1) != AR.NA_INTEGER) & (np.asarray(a2) != AR.NA_INTEGER)
-    return [np.ascontiguousarray(np.asarray(c)[..., ok]) for c in columns]
-
-
-def allele_names(n_allele):
-    return [f"{k + 1:02d}:01" for k in range(n_allele)]        # (sorted order = index order)
 
 
 def hla_of(case):
     """The case's cohort as hlaAssocGlm takes it: (hla with ``prob``, y, groups or None, covar [n, q])."""
-    import hibag_amd as hb
     n, n_allele, q, seed, partition = CASES[case]
     a1, a2, y, g, covar, prob = cohort(n, n_allele, q, seed, partition)
-    names = allele_names(n_allele)
-    hla = hb.HlaAlleleClass(locus="A", sample_id=[f"s{i}" for i in range(n)], allele1=[None if a < 0 else names[a] for a in a1],
-                            allele2=[None if a < 0 else names[a] for a in a2], prob=prob)
-    groups = hb.HlaAlleleGroups(names, ["pos"], [["x", "gap", "y", "z", "beyond"]], g) if partition else None
+    hla, _, groups = AR.hla_of(a1, a2, prob, n_allele, g)
     return hla, y, groups, covar.T
 
 

@@ -233,7 +233,7 @@ def analysis(case, model):
     if key not in _ANALYSIS:
         n, n_allele, seed, extra = CASES[case]
         a1, a2, y, g, covar, prob = cohort(n, n_allele, seed, extra)
-        covar, prob = G.kept_columns(a1, a2, covar, prob)
+        covar, prob = AR.kept_columns(a1, a2, covar, prob)
         A = AR.Analysis(a1, a2, y, n_allele, g, model)
         assert A.n == KEPT[case]
         part_rows, at = [], n_allele
@@ -314,9 +314,7 @@ def hla_of(case, without=()):
     import hibag_amd as hb
     n, n_allele, seed, extra = CASES[case]
     a1, a2, y, g, covar, prob = cohort(n, n_allele, seed, extra)
-    names = G.allele_names(n_allele)
-    hla = hb.HlaAlleleClass(locus="DRB1", sample_id=[f"s{i}" for i in range(n)], allele1=[None if a < 0 else names[a] for a in a1],
-                            allele2=[None if a < 0 else names[a] for a in a2], prob=prob)
+    hla, names, _ = AR.hla_of(a1, a2, prob, n_allele, locus="DRB1")
     pn, levels, _ = partitions(n_allele, extra)
     keep = [i for i, nm in enumerate(pn) if nm not in without]
     return hla, y, hb.HlaAlleleGroups(names, [pn[i] for i in keep], [levels[i] for i in keep], g[keep]), covar.T

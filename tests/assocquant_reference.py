@@ -11,6 +11,7 @@ from __future__ import annotations
 import numpy as np
 
 import assoc_reference as AR
+from assoc_reference import allele_names, kept_columns       # noqa: F401  (the tests reach them through this module)
 from draws_reference import philox4x32_10
 
 MODELS = AR.MODELS
@@ -174,36 +175,18 @@ class Quant:
 
     def permute(self, seed, perm0, n_perm):
         """(max_stat [n_perm], count_point int64 [n_test]) as hibag_hip_assoc_quant_permute."""
-        st = self.stats(seed, perm0, n_perm)
-        best = np.where(np.isnan(st), -1.0, st).max(axis=0) if self.T else np.full(n_perm, -1.0)
-        with np.errstate(invalid="ignore"):
-            count = (st >= self.stat[:, None]).sum(axis=1).astype(np.int64)
-        return np.where(best < 0, np.nan, best).astype(np.float64), count
+        max_stat, count = AR.max_and_count(self.stats(seed, perm0, n_perm), self.stat)
+        return max_stat.astype(np.float64), count
 
     def observed(self):
         f = np.float64
         return self.proj.astype(f), self.g[:, 0].astype(f), float(self.rr), self.stat.astype(f), self.flags
 
 
-class Backend:
+class Backend(AR.Backend):
     """The restatement behind the interface of hibag_amd.assocquant._DeviceQuant (``hlaAssocQuant(..., _backend=Backend)``)."""
 
-    dtype = np.float64
-
-    def __init__(self, a1, a2, y, n_allele, group_of, model):
-        self.model = MODELS[model]
-        self.A = AR.Analysis(a1, a2, y, n_allele, group_of, self.model)
-        self.n_tests, self.n_kept = self.A.n_tests, self.A.n
-        self.Z = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        pass
-
-    def feature_rows(self, row0, n_rows):
-        return self.A.F[row0:row0 + n_rows].astype(np.int8)
+    Z = None
 
     def quant(self, y, covar):
         try:
@@ -267,29 +250,15 @@ def cohort(n, n_allele, q, seed, n_na, partition=False):
     gamma = rng.uniform(-1.0, 1.0, q)
     y = 50.0 + 1.5 * (a == 0).sum(axis=1) - 1.0 * (a == 1).any(axis=1) + gamma @ covar + 2.0 * rng.standard_normal(n)
     a[n_allele + rng.choice(n - n_allele, n_na, replace=False), rng.integers(0, 2, n_na)] = AR.NA_INTEGER
-    g = np.where(np.arange(n_allele) % 3 == 0, 0, 2 + np.arange(n_allele) % 2)[None, :].astype(np.int32) if partition else None
+    g = AR.gap_partition(n_allele) if partition else None
     return np.ascontiguousarray(a[:, 0]), np.ascontiguousarray(a[:, 1]), y, g, covar
-
-
-def kept_columns(a1, a2, *columns):
-    """The columns (last axis = samples) restricted to the samples with two known alleles."""
-    ok = (np.asarray(a1) != AR.NA_INTEGER) & (np.asarray(a2) != AR.NA_INTEGER)
-    return [np.ascontiguousarray(np.asarray(c)[..., ok]) for c in columns]
-
-
-def allele_names(n_allele):
-    return [f"{k + 1:02d}:01" for k in range(n_allele)]        # (sorted order = index order)
 
 
 def hla_of(case):
     """The case's cohort as hlaAssocQuant takes it: (hla, y, groups or None, covar [n, q])."""
-    import hibag_amd as hb
     n, n_allele, q, seed, n_na, partition = CASES[case]
     a1, a2, y, g, covar = cohort(n, n_allele, q, seed, n_na, partition)
-    names = allele_names(n_allele)
-    hla = hb.HlaAlleleClass(locus="A", sample_id=[f"s{i}" for i in range(n)], allele1=[None if a < 0 else names[a] for a in a1],
-                            allele2=[None if a < 0 else names[a] for a in a2], prob=np.ones(n))
-    groups = hb.HlaAlleleGroups(names, ["pos"], [["x", "gap", "y", "z", "beyond"]], g) if partition else None
+    hla, _, groups = AR.hla_of(a1, a2, np.ones(n), n_allele, g)
     return hla, y, groups, covar.T
 
 
@@ -308,10 +277,7 @@ def reference(case, model, dtype=np.float64):
         Z = Quant(A.F, model, y, covar, dtype)
         Z.seed = seed_of(case, model)
         Z.perm_g, Z.perm_rr, Z.perm_T = Z.run(perm_rows(Z.seed, 1, N_PERM[case], Z.n))
-        best = np.where(np.isnan(Z.perm_T), -1.0, Z.perm_T).max(axis=0)
-        Z.max_stat = np.where(best < 0, np.nan, best)
-        with np.errstate(invalid="ignore"):
-            Z.count = (Z.perm_T >= Z.stat[:, None]).sum(axis=1).astype(np.int64)
+        Z.max_stat, Z.count = AR.max_and_count(Z.perm_T, Z.stat)
         _CACHE[key] = Z
     return _CACHE[key]
 

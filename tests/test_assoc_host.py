@@ -239,6 +239,110 @@ def test_value_errors():
         hb.hlaAssocTest(H1, Y)
 
 
+# 5 what the association entries share --------------------------------------------------------------------------------
+def test_plan_sel_is_the_brute_force_rule():
+    """``_Plan.sel``: at or above the threshold (a NaN ``prob`` is excluded), both alleles known, in the original order."""
+    h1 = H1 + [None, "10:01", None, A, math.nan]
+    h2 = H2 + [A, None, None, B, B]
+    y = Y + [1, 0, 1, 0, 1]
+    prob = [0.9, 0.2, math.nan, 0.5, 0.7, 0.49, 1.0, 0.8, 0.9, 0.6, 0.2, math.nan, 0.9, 0.9, 0.1, math.nan, 0.9]
+    hla = _hla(h1, h2, np.array(prob))
+    for thr in (math.nan, math.inf, 0.5, 0.0):
+        want = [i for i in range(len(h1))
+                if isinstance(h1[i], str) and isinstance(h2[i], str) and (not math.isfinite(thr) or prob[i] >= thr)]
+        for labels in (y, None):
+            plan = assoc._Plan(hla, labels, thr, None)
+            assert plan.sel.tolist() == want and plan.n_samp == len(want), thr
+            assert plan.y.tolist() == [y[i] if labels is not None else 0 for i in want]
+            assert plan.n_case == sum(plan.y) and plan.y.dtype == np.int32
+            assert plan.n_excluded == (sum(1 for p in prob if not p >= thr) if math.isfinite(thr) else 0)
+
+
+def test_spread_fills_the_levels_unknown_to_the_device():
+    """``_Plan.spread``: the device numbers a partition's levels 0 .. the largest id that an allele of the data has, so the
+    filled tests are exactly the levels above it -- none of which an allele of the data belongs to; every other test gets its
+    device row, whatever the trailing shape."""
+    alleles = ["10:01", Cc, B, A, "04:01"]
+    labels = {"first": ["x", "y", "x", "z", "z"], "second": ["p", "q", "q", "q", "r"], "third": ["u", "u", "u", "u", "w"]}
+    g = hb.HlaAlleleGroups.from_labels(alleles, "first", labels["first"])
+    for part in ("second", "third"):
+        g = g + hb.HlaAlleleGroups.from_labels(alleles, part, labels[part])
+    plan = assoc._Plan(_hla(), Y, math.nan, g)                  # the data has A, B and C only
+    filled = []
+    for q, part in enumerate(g.names):
+        ids = [g.levels[q].index(lab) for a, lab in zip(alleles, labels[part]) if a in plan.alleles]
+        filled += [f"{part}:{name}" for lv, name in enumerate(g.levels[q]) if lv > max(ids)]
+        assert all(g.levels[q].index(lab) <= max(ids) for a, lab in zip(alleles, labels[part]) if a in plan.alleles)
+    assert filled == ["second:r", "third:w"]
+    assert [nm for nm, r in zip(plan.names, plan.row) if r < 0] == filled
+    T = plan.n_device_tests
+    for a in (np.arange(T) + 0.5, np.arange(3 * T, dtype=np.int64).reshape(T, 3), np.arange(4.0 * T).reshape(T, 2, 2)):
+        for fill in (np.nan, -7):
+            got = plan.spread(a, fill)
+            assert got.shape == (len(plan.names),) + a.shape[1:]
+            for t, (nm, r) in enumerate(zip(plan.names, plan.row)):
+                want = np.full(a.shape[1:], fill) if nm in filled else a[r]
+                assert np.array_equal(got[t], want, equal_nan=True), (nm, fill)
+    assert plan.spread(np.arange(T), 0).dtype == np.int64
+
+
+def _raised(entry, *args, **kw):
+    with pytest.raises((ValueError, TypeError)) as info:
+        entry(*args, **kw)
+    return type(info.value), str(info.value)
+
+
+def test_shared_argument_checks_agree():
+    """Every entry that takes one of the shared arguments refuses a bad value with the same exception and message.  (The
+    omnibus entries name their own three models, and know partitions beside tests in ``condition``: their messages say so
+    and are compared among themselves.)"""
+    import assocglm_reference as G
+    import assocomni_reference as O
+    import assocquant_reference as Q
+    hla, y, groups, covar = O.hla_of("n40")
+    cov, yq = covar[:, :2], covar[:, 2]
+    entries = {
+        "test": lambda **kw: hb.hlaAssocTest(hla, y, **kw),
+        "glm": lambda covariates=cov, **kw: hb.hlaAssocGlm(hla, y, covariates, _backend=G.Backend, **kw),
+        "quant": lambda covariates=cov, **kw: hb.hlaAssocQuant(hla, yq, covariates, _backend=Q.Backend, **kw),
+        "omnibus": lambda covariates=cov, **kw: hb.hlaAssocOmnibus(hla, y, groups, covariates, _backend=O.Backend, **kw),
+        "stepwise": lambda covariates=cov, **kw: hb.hlaAssocStepwise(hla, y, groups, covariates, _backend=O.Backend, **kw),
+    }
+    kept = assoc._Plan(hla, y, math.nan, None).sel
+    short, holed = cov[:-1], cov.copy()
+    holed[kept[3], 1] = math.nan
+    regress = ("glm", "quant", "omnibus", "stepwise")
+    cases = [
+        (dict(model="dominent"), ("test", "glm", "quant"), ValueError, 'should be one of "dominant"'),
+        (dict(model="dominent"), ("omnibus", "stepwise"), ValueError, 'should be one of "additive"'),
+        (dict(n_perm=-1), ("test", "quant"), ValueError, "n_perm must be an integer >= 0"),
+        (dict(n_perm=2.5), ("test", "quant"), ValueError, "n_perm must be an integer >= 0"),
+        (dict(n_perm=True), ("test", "quant"), ValueError, "n_perm must be an integer >= 0"),
+        (dict(n_perm=3, seed=-1), ("test", "quant"), ValueError, "seed must be an integer in 0 .. 2^64 - 1"),
+        (dict(n_perm=3, seed=1 << 64), ("test", "quant"), ValueError, "seed must be an integer in 0 .. 2^64 - 1"),
+        (dict(maxit=0), ("glm", "omnibus", "stepwise"), ValueError, "maxit must be an integer >= 1"),
+        (dict(maxit=2.0), ("glm", "omnibus", "stepwise"), ValueError, "maxit must be an integer >= 1"),
+        (dict(epsilon=0), ("glm", "omnibus", "stepwise"), ValueError, "epsilon must be > 0"),
+        (dict(epsilon="small"), ("glm", "omnibus", "stepwise"), ValueError, "epsilon must be > 0"),
+        (dict(covariates=short), regress, ValueError, f"covariate 'c1' has {len(y) - 1} values for {len(y)} samples"),
+        (dict(covariates=holed), regress, ValueError, "covariate 'c2' has a missing or non-finite value: subset the samples first"),
+        (dict(condition=["99:99"]), ("glm", "quant"), ValueError, "condition: '99:99' is not a test of this analysis"),
+        (dict(condition=["99:99"]), ("omnibus", "stepwise"), ValueError,
+         "condition: '99:99' is neither a partition nor a test of this analysis"),
+    ]
+    for kw, names, exc, text in cases:
+        seen = {name: _raised(entries[name], **kw) for name in names}
+        assert len(set(seen.values())) == 1, (kw, seen)
+        got_exc, got_text = seen[names[0]]
+        assert got_exc is exc and (got_text == text or got_text.startswith("'arg' " + text)), (kw, got_text)
+    # a hole in a sample that is not kept is no error
+    dropped = sorted(set(range(len(y))) - set(kept.tolist()))
+    assert dropped
+    holed = cov.copy()
+    holed[dropped, :] = math.nan
+    assert entries["glm"](covariates=holed).n_samp == len(kept)
+
+
 def test_assoc_entries_are_declared():
     from hibag_amd import _lib
     for name in ("hibag_hip_assoc_new", "hibag_hip_assoc_free", "hibag_hip_assoc_n_tests", "hibag_hip_assoc_observed",

@@ -48,6 +48,17 @@ def test_labels_equal_the_restatement(n):
                     assert (got.sum(axis=1) == n_case).all()
 
 
+def test_labels_across_panels(monkeypatch):
+    """70 rows in panels of 64 and 6: each panel reaches the host before the next overwrites the device's buffer."""
+    n, n_case = 300, 150
+    zeros, y = np.zeros(n, np.int32), np.zeros(n, np.int32)
+    y[np.random.default_rng(n + n_case).choice(n, n_case, replace=False)] = 1
+    monkeypatch.setenv("HIBAG_ASSOC_PANEL_PERMS", "64")
+    with assoc._DeviceAssoc(zeros, zeros, y, 1, None, 0) as dev:
+        for perm0 in (1, 1 << 33):
+            assert dev.labels(SEED, perm0, 70).tobytes() == R.labels(SEED, perm0, 70, n, n_case).tobytes(), perm0
+
+
 def test_labels_skip_the_dropped_samples():
     a1 = np.array([0, NA, 1, 0, 1, NA], np.int32)
     a2 = np.array([0, 1, NA, 1, 1, NA], np.int32)

@@ -54,6 +54,14 @@ def test_perm_rows_byte_for_byte(case):
         assert dev.quant_perm_rows(3, 5, 0).shape == (0, n)
 
 
+def test_perm_rows_across_panels(monkeypatch):
+    """40 rows in panels of 16, 16 and 8: each panel reaches the host before the next overwrites the device's buffer."""
+    monkeypatch.setenv("HIBAG_QUANT_PANEL_PERMS", "16")
+    with open_case("n40", "dominant") as dev:
+        seed = Q.seed_of("n40", "dominant")
+        assert dev.quant_perm_rows(seed, 1, 40).tobytes() == Q.perm_rows(seed, 1, 40, dev.n_kept).tobytes()
+
+
 # 2 values ---------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("model", MODELS)
 @pytest.mark.parametrize("case", list(Q.CASES))
