@@ -15,6 +15,10 @@
 // feature rows -- all residues of a position at once -- over a 32-slot design, with aliased columns dropped; it shares the
 // buffers and the driver (`GlmCall`) of hibag_hip_assoc_glm.
 //
+// hibag_hip_assoc_glm_terms (hlaAssocInteract; kernels: hibag_k_glmt.h) fits one regression per record of
+// up to three TERMS -- a feature row, or the product of two, formed while the samples are walked -- on the same buffers and
+// driver; hibag_hip_assoc_row_gram gives the exact co-carriage sums of feature rows from k_ld_gram<1>.
+//
 // hibag_hip_assoc_quant_* (hlaAssocQuant; kernels: hibag_k_quant.h) test a quantitative trait on the
 // same feature rows, through a handle of their own that borrows this one; they are at the end of the file.  The two
 // permutation sides share one panel driver (`panel_perms`, `check_perm_range`, `for_each_panel`, `PermOut`, `download_panels`),
@@ -24,6 +28,7 @@
 #include "hibag_k_assoc.h"
 #include "hibag_k_glm.h"
 #include "hibag_k_glmw.h"
+#include "hibag_k_glmt.h"
 #include "hibag_k_quant.h"
 
 using hibag_detail::DevBuf;
@@ -169,7 +174,7 @@ int enqueue_labels(hibag_hip_assoc *h, uint64_t seed, uint64_t p0, int n_lab)
 	return 0;
 }
 
-// The regression driver: what hibag_hip_assoc_glm and hibag_hip_assoc_glm_sets share.  An entry checks its arguments
+// The regression driver: what hibag_hip_assoc_glm, hibag_hip_assoc_glm_sets and hibag_hip_assoc_glm_terms share.  An entry checks its arguments
 // (`check_control`, what is its own, `check_values`, in the order the messages have always had), decides its fit records
 // from the row sums, and hands them to `run` with its slot count and the launches of its two kernels.
 struct GlmOut { double *coef, *se, *dev; int32_t *it, *fl, *df; };   // the device's outputs, carved from glm_out
@@ -238,6 +243,29 @@ struct GlmCall {
 		});
 	}
 };
+
+// C [na][nb] on the host: C[i][j] = the sum over the samples of feature rows a0 + i and b0 + j, exact (k_ld_gram<1> on the
+// handle's rows as both operands; the padding columns hold zeros).  The rows are inside the handle.
+int rows_gram(hibag_hip_assoc *h, int a0, int na, int b0, int nb, int32_t *out)
+{
+	if (h->gram.reserve(sizeof(int32_t) * (size_t)na * nb)) return HIBAG_HIP_ENOMEM;
+	return enqueued(h->st, [&]() -> int {
+		LdGramOut O;
+		O.out32 = h->gram.as<int32_t>();
+		O.ld = (size_t)nb;
+		const dim3 grid((nb + HIBAG_LD_TILE - 1) / HIBAG_LD_TILE, (na + HIBAG_LD_TILE - 1) / HIBAG_LD_TILE);
+		hipLaunchKernelGGL(k_ld_gram<1>, grid, dim3(256), 0, h->st, h->feat.as<int8_t>() + (size_t)a0 * h->kp, na,
+			h->feat.as<int8_t>() + (size_t)b0 * h->kp, nb, h->kp, O);
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipMemcpyAsync(out, h->gram.p, sizeof(int32_t) * (size_t)na * nb, hipMemcpyDeviceToHost, h->st));
+		HIP_TRY(hipStreamSynchronize(h->st));
+		return 0;
+	});
+}
+
+constexpr int kMaxGramRows = 8192;               // hibag_hip_assoc_row_gram: 256 MiB of int32 at most
+constexpr int kGramBlock = 2048;                 // hibag_hip_assoc_glm_terms: the products' sums come in blocks of rows x rows
+constexpr int kMaxTermFits = 1 << 20;
 
 // what hibag_hip_assoc_new does on the device: features, then the observed labelling as a panel of one
 int build(hibag_hip_assoc *h, const std::vector<int32_t> &a1, const std::vector<int32_t> &a2, const std::vector<int8_t> &y,
@@ -551,6 +579,114 @@ int hibag_hip_assoc_glm_sets(hibag_hip_assoc *h, const int32_t *set_start, const
 		[&](const GlmOut &O) {
 			hipLaunchKernelGGL(k_glm_fit_wide, dim3(n_fit), dim3(GLM_WAVES * 64), 0, h->st, h->glm_img.as<double>(), h->glm_wt.as<double>(),
 				h->y.as<int8_t>(), h->feat.as<int8_t>(), h->glm_fits.as<GlmWideFit>(), n, kp, q, H, maxit, epsilon, O.coef, O.se, O.dev, O.it,
+				O.fl, O.df);
+		});
+}
+
+int hibag_hip_assoc_row_gram(hibag_hip_assoc *h, int row0, int n_rows, int32_t *out)
+{
+	if (!h || n_rows < 0 || (n_rows > 0 && !out)) return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_row_gram: null argument or n_rows < 0");
+	if (row0 < 0 || row0 > h->rows || n_rows > h->rows - row0)
+		return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_row_gram: rows %d .. %d + %d are outside the handle's %d", row0, row0, n_rows, h->rows);
+	if (n_rows > kMaxGramRows) return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_row_gram: %d rows; at most %d in a call", n_rows, kMaxGramRows);
+	if (n_rows == 0) return 0;
+	HIP_TRY(hipSetDevice(h->device));
+	return rows_gram(h, row0, n_rows, row0, n_rows, out);
+}
+
+int hibag_hip_assoc_glm_terms(hibag_hip_assoc *h, const int32_t *terms, int n_fits, const double *covar, int n_covar, const double *weight,
+	int maxit, double epsilon, double *coef, double *se, double *deviance, int32_t *iterations, int32_t *flags, int32_t *df_h)
+{
+	if (!h || !coef || !se || !deviance || !iterations || !flags || !df_h)
+		return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_glm_terms: null argument");
+	static_assert(GLMT_COV0 + HIBAG_HIP_GLM_TERMS_MAX_COVAR == GLM_SLOTS - 1 && GLMT_MAX_COVAR == HIBAG_HIP_GLM_TERMS_MAX_COVAR,
+		"intercept, three term slots, the covariates, then z");
+	static_assert(sizeof(GlmTermsFit) == sizeof(int) * (2 * GLMT_TERMS + 2), "uploaded as it is");
+	const GlmCall call{"hibag_hip_assoc_glm_terms", h, covar, n_covar, weight, maxit, epsilon, coef, se, deviance, iterations, flags, df_h};
+	if (int rc = call.check_control(HIBAG_HIP_GLM_TERMS_MAX_COVAR)) return rc;
+	if (n_fits < 0 || n_fits > kMaxTermFits || (n_fits > 0 && !terms))
+		return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_glm_terms: need 0 <= n_fits <= 2^20 and terms with fits to read (n_fits = %d)", n_fits);
+	const int n = h->D.n, kp = h->kp, q = n_covar, n_fit = n_fits + 1;
+
+	// the records as given: every term a row of the handle, or a product of two, no term twice in a fit
+	std::vector<GlmTermsFit> fits((size_t)n_fit);
+	struct Product { int a, b; size_t fit; int term; };        // a <= b
+	std::vector<Product> products;
+	for (int t = 0; t < n_fits; t++) {
+		GlmTermsFit &f = fits[(size_t)t];
+		int key[GLMT_TERMS][2];
+		for (int j = 0; j < GLMT_TERMS; j++) {
+			const int a = terms[((size_t)t * GLMT_TERMS + j) * 2], b = terms[((size_t)t * GLMT_TERMS + j) * 2 + 1];
+			if (a < -1 || a >= h->rows || b < -1 || b >= h->rows)
+				return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_glm_terms: fit %d term %d names rows (%d, %d), outside the handle's %d", t, j, a,
+					b, h->rows);
+			if (a < 0 && b >= 0)
+				return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_glm_terms: fit %d term %d has row_a = -1 with row_b = %d", t, j, b);
+			key[j][0] = b < 0 ? a : std::min(a, b);
+			key[j][1] = b < 0 ? -1 : std::max(a, b);
+			for (int i = 0; i < j; i++)
+				if (a >= 0 && key[i][0] == key[j][0] && key[i][1] == key[j][1])
+					return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_glm_terms: fit %d names the term (%d, %d) twice", t, a, b);
+			f.term[j][0] = a;
+			f.term[j][1] = b;
+			if (b >= 0) products.push_back(Product{key[j][0], key[j][1], (size_t)t, j});
+		}
+	}
+	if (int rc = call.check_values()) return rc;
+	HIP_TRY(hipSetDevice(h->device));
+
+	// the terms' column sums: a row's from the row sums, a product's from the Gram of its rows'
+	// blocks -- integers, so "nobody carries both" is decided exactly
+	std::vector<int32_t> psum(products.size());
+	{
+		std::vector<size_t> order(products.size());
+		for (size_t i = 0; i < order.size(); i++) order[i] = i;
+		auto block = [&](size_t i) { return std::make_pair(products[i].a / kGramBlock, products[i].b / kGramBlock); };
+		std::sort(order.begin(), order.end(), [&](size_t x, size_t y) { return block(x) < block(y); });
+		std::vector<int32_t> C;
+		for (size_t at = 0; at < order.size();) {
+			// of the block only the rows between the lowest and the highest that its products name, each way
+			const auto blk = block(order[at]);
+			int a0 = h->rows, a1 = -1, b0 = h->rows, b1 = -1;
+			for (size_t e = at; e < order.size() && block(order[e]) == blk; e++) {
+				const Product &pr = products[order[e]];
+				a0 = std::min(a0, pr.a); a1 = std::max(a1, pr.a);
+				b0 = std::min(b0, pr.b); b1 = std::max(b1, pr.b);
+			}
+			const int na = a1 - a0 + 1, nb = b1 - b0 + 1;
+			C.resize((size_t)na * nb);
+			if (int rc = rows_gram(h, a0, na, b0, nb, C.data())) return rc;
+			for (; at < order.size() && block(order[at]) == blk; at++) {
+				const Product &pr = products[order[at]];
+				psum[order[at]] = C[(size_t)(pr.a - a0) * nb + (pr.b - b0)];
+			}
+		}
+	}
+	const std::vector<int32_t> &r = h->h_row_sum;
+	for (size_t i = 0; i < products.size(); i++)
+		if (psum[i] == 0) fits[products[i].fit].term[products[i].term][0] = -2;      // (marked; cleared below)
+	for (int t = 0; t < n_fits; t++) {
+		GlmTermsFit &f = fits[(size_t)t];
+		int left = 0, out = 0;
+		for (int j = 0; j < GLMT_TERMS; j++) {
+			int *tm = f.term[j];
+			if (tm[0] == -1) continue;
+			if (tm[0] == -2 || (tm[1] < 0 && r[(size_t)tm[0]] == 0)) { tm[0] = tm[1] = -1; out++; }
+			else left++;
+		}
+		f.fitted = left > 0;
+		f.flags0 = left > 0 ? (out ? GLM_FLAG_ALIASED : 0) : GLM_FLAG_RANK;
+	}
+	fits[(size_t)n_fits] = GlmTermsFit{{{-1, -1}, {-1, -1}, {-1, -1}}, 1, 0};
+
+	return call.run(GLM_SLOTS, fits.data(), sizeof(GlmTermsFit), n_fit,
+		[&](const double *d_cov, const double *d_w) {
+			hipLaunchKernelGGL(k_glm_image_terms, dim3((unsigned)(((size_t)kp * GLM_SLOTS + 255) / 256)), dim3(256), 0, h->st, d_cov, d_w, n, q,
+				kp, h->glm_img.as<double>(), h->glm_wt.as<double>());
+		},
+		[&](const GlmOut &O) {
+			hipLaunchKernelGGL(k_glm_fit_terms, dim3(n_fit), dim3(GLM_WAVES * 64), 0, h->st, h->glm_img.as<double>(), h->glm_wt.as<double>(),
+				h->y.as<int8_t>(), h->feat.as<int8_t>(), h->glm_fits.as<GlmTermsFit>(), n, kp, q, maxit, epsilon, O.coef, O.se, O.dev, O.it,
 				O.fl, O.df);
 		});
 }

@@ -38,7 +38,8 @@ extern "C" {
                                        + hibag_hip_test_layout_plan, _count, _get, _free (test entries): likewise;
                                        + the regression entries (hibag_hip_assoc_glm, _n_kept, _feature_rows): likewise;
                                        + the quantitative-trait entries (hibag_hip_assoc_quant_*): likewise;
-                                       + the set regression (hibag_hip_assoc_glm_sets, hibag_hip_assoc_row_sums): likewise */
+                                       + the set regression (hibag_hip_assoc_glm_sets, hibag_hip_assoc_row_sums): likewise;
+                                       + the term regression (hibag_hip_assoc_glm_terms, hibag_hip_assoc_row_gram): likewise */
 
 /* error codes */
 #define HIBAG_HIP_OK          0
@@ -377,6 +378,38 @@ int hibag_hip_assoc_glm_sets(hibag_hip_assoc *h, const int32_t *set_start, const
 
 /* The sums of the handle's feature rows over the kept samples: out int32 [rows], rows as hibag_hip_assoc_feature_rows. */
 int hibag_hip_assoc_row_sums(hibag_hip_assoc *h, int32_t *out);
+
+/* ---- pairwise interaction fits: hlaAssocInteract ------------
+ * The co-carriage sums of feature rows: out int32 [n_rows][n_rows], out[i][j] = the sum over the kept samples of
+ * feat[row0 + i][s] * feat[row0 + j][s], rows as hibag_hip_assoc_feature_rows numbers them.  Integer sums on the int8 Gram
+ * kernel, exact; the diagonal of a 0 / 1 row is its row sum.  EINVAL for a null pointer, rows outside the handle's, or
+ * n_rows > 8192. */
+int hibag_hip_assoc_row_gram(hibag_hip_assoc *h, int row0, int n_rows, int32_t *out);
+
+/* glm(y ~ t_1 + t_2 + t_3 + covariates, family = binomial) for every fit RECORD of up to three terms, and for the base model
+ * y ~ covariates: the fit of hibag_hip_assoc_glm with the aliased-column rule of
+ * hibag_hip_assoc_glm_sets, where a term is a feature row of the handle or the PRODUCT of two rows -- for two alleles of one
+ * locus the heterozygote a/b.  The product is formed per sample as an integer while the fit walks the samples; no product row
+ * exists in memory.  The definitions are DESIGN.md section 27.
+ *   terms       int32 [n_fits][3][2]: term j of a fit is (row_a, row_b): (-1, -1) unused, (a, -1) row a, (a, b) the product
+ *               of rows a and b; 0 <= n_fits <= 2^20
+ *   covar       float64 [n_covar][n_kept] (NULL with n_covar = 0); 0 <= n_covar <= HIBAG_HIP_GLM_TERMS_MAX_COVAR
+ *   weight, maxit, epsilon: as hibag_hip_assoc_glm
+ * Outputs for n_fits + 1 fits, fit n_fits the base model:
+ *   coef, se    float64 [n_fits + 1][16] by slot: 0 the intercept, 1 + j term j, 4 .. 3 + n_covar the covariates; every other
+ *               slot, every term left out and every dropped column NaN
+ *   deviance    float64, iterations int32, flags int32 (HIBAG_HIP_GLM_*) [n_fits + 1]
+ *   df_h        int32 [n_fits + 1]: the terms still in the fit at its last solve (0 where not fitted)
+ * The factorisation takes the columns in the order intercept, covariates, terms in slot order; a column whose pivot is
+ * <= 1e-11 A_jj is dropped (NaN, ALIASED).  Decided from integer sums before any fit: a term whose column sum is 0 is left out
+ * (its slot NaN, ALIASED); a fit with no term left, or with three unused terms, is not fitted (RANK, NaN, df_h 0).  The slot
+ * layout is fixed, so a fit's numbers depend on the kept samples, its own terms and the arguments -- not on the other fits.
+ * EINVAL as hibag_hip_assoc_glm, and for n_covar > 11, n_fits outside its range, null terms with fits to read, a row index
+ * outside the handle's rows, row_a = -1 with row_b >= 0, the same term twice in a fit (a product taken unordered). */
+#define HIBAG_HIP_GLM_TERMS_MAX_COVAR 11
+int hibag_hip_assoc_glm_terms(hibag_hip_assoc *h, const int32_t *terms, int n_fits, const double *covar, int n_covar,
+	const double *weight, int maxit, double epsilon, double *coef, double *se, double *deviance, int32_t *iterations,
+	int32_t *flags, int32_t *df_h);
 
 /* ---- a quantitative trait on the tests of a handle: hlaAssocQuant ------------
  * lm(y ~ h + covariates) for every test of the handle (R/Association.R:262-313, 368-376 with a continuous y), with max-T
