@@ -10,7 +10,8 @@ iteration as one 16 x 16 FP64 matrix-core tile.  The fit is R's ``glm.fit`` rest
 whole partition -- all residues of a position at once -- is ``hlaAssocOmnibus`` (assocomni.py).
 
 Not built: other ``family`` values (a quantitative trait with the t-test and ANOVA columns is ``hlaAssocQuant``,
-assocquant.py), permutation p-values for this regression, R's step halving, interaction terms, and ``fisher_p`` of the
+assocquant.py), permutation p-values for this regression (the family-wise p-value of the same tests is ``hlaAssocScore``,
+assocscore.py: score tests with multiplier resampling), R's step halving, interaction terms, and ``fisher_p`` of the
 genotype model."""
 
 from __future__ import annotations
@@ -192,7 +193,7 @@ def hlaAssocGlm(hla: HlaAlleleClass, y: Sequence, covariates=None, model: str = 
     and the base model converged.  A rank-deficient base model is a ValueError.
 
     Not built: other families (a quantitative trait: ``hlaAssocQuant``), permutation p-values for this
-    regression, R's step halving (with the clamps of section 23 the deviance is always finite), interaction terms, and
+    regression (``hlaAssocScore`` gives the family-wise p-value of the same tests), R's step halving (with the clamps of section 23 the deviance is always finite), interaction terms, and
     ``fisher_p`` of the genotype model.  (``_backend``: the tests' seam -- a class with the interface of ``_DeviceGlm`` that
     stands in for the device.)"""
     _check_model(model)

@@ -9,7 +9,8 @@ positions already found.  One test per partition of ``groups``; every fit runs o
 FP64 matrix-core blocks per four samples.  Aliased columns are dropped as R's ``glm.fit`` drops them and the degrees of
 freedom shrink with them.  The definitions are DESIGN.md section 26 (the fit itself: section 23).
 
-Not built: permutation p-values for these fits, the ``genotype`` coding, lumping of rare levels, designs beyond 31 columns,
+Not built: permutation p-values for these fits (``hlaAssocScore(..., omnibus=True)``, assocscore.py, has the family-wise p-value
+of the same design sets), the ``genotype`` coding, lumping of rare levels, designs beyond 31 columns,
 interactions, other families."""
 
 from __future__ import annotations

@@ -20,9 +20,11 @@
 // driver; hibag_hip_assoc_row_gram gives the exact co-carriage sums of feature rows from k_ld_gram<1>.
 //
 // hibag_hip_assoc_quant_* (hlaAssocQuant; kernels: hibag_k_quant.h) test a quantitative trait on the
-// same feature rows, through a handle of their own that borrows this one; they are at the end of the file.  The two
-// permutation sides share one panel driver (`panel_perms`, `check_perm_range`, `for_each_panel`, `PermOut`, `download_panels`),
-// and every function that enqueues work on host memory follows one drain rule (`enqueued`): the first namespace below.
+// same feature rows, through a handle of their own that borrows this one; hibag_hip_assoc_score_* (hlaAssocScore, DESIGN.md
+// section 28; kernels: hibag_k_score.h) run covariate-adjusted score tests with multiplier resampling the same way; both are
+// at the end of the file.  The permutation and resampling sides share one panel driver (`panel_perms`, `check_perm_range`,
+// `for_each_panel`, `PermOut`, `download_panels`), and every function that enqueues work on host memory follows one drain
+// rule (`enqueued`): the first namespace below.
 
 #include "hibag_internal.h"
 #include "hibag_k_assoc.h"
@@ -30,6 +32,7 @@
 #include "hibag_k_glmw.h"
 #include "hibag_k_glmt.h"
 #include "hibag_k_quant.h"
+#include "hibag_k_score.h"
 
 using hibag_detail::DevBuf;
 
@@ -92,23 +95,26 @@ template <class Make> int download_panels(hipStream_t st, int n, int pp, const v
 	});
 }
 
-// What a permutation call accumulates on the device: every permutation's largest statistic and, per test, the number of
-// permutations at or above the observed statistic.
+// What a permutation call accumulates on the device: every permutation's largest statistic (`width` of them for an entry that
+// keeps several maxima per permutation) and, per test, the number of permutations at or above the observed statistic.
 struct PermOut {
-	DevBuf max_stat, count;                      // double [n_perm]; uint64 [n_test]
+	DevBuf max_stat, count;                      // double [n_perm][width]; uint64 [n_test]
 
-	int reserve(int64_t n_perm, int T) { return max_stat.reserve(sizeof(double) * (size_t)n_perm) || count.reserve(sizeof(unsigned long long) * (size_t)T); }
+	int reserve(int64_t n_perm, int T, int width = 1)
+	{
+		return max_stat.reserve(sizeof(double) * (size_t)n_perm * std::max(width, 1)) || count.reserve(sizeof(unsigned long long) * (size_t)std::max(T, 1));
+	}
 	void release() { max_stat.release(); count.release(); }
 
 	// one call: the counts zeroed, panel(done, n_lab) for every panel of `pp`, both outputs on the host
-	template <class Panel> int run(hipStream_t st, int T, int64_t n_perm, int pp, double *h_max, int64_t *h_count, Panel panel)
+	template <class Panel> int run(hipStream_t st, int T, int64_t n_perm, int pp, double *h_max, int64_t *h_count, Panel panel, int width = 1)
 	{
 		static_assert(sizeof(unsigned long long) == sizeof(int64_t), "the counts are copied as they are");
 		return enqueued(st, [&]() -> int {
 			HIP_TRY(hipMemsetAsync(count.p, 0, sizeof(unsigned long long) * (size_t)T, st));
 			if (int rc = for_each_panel(n_perm, pp, panel)) return rc;
-			HIP_TRY(hipMemcpyAsync(h_max, max_stat.p, sizeof(double) * (size_t)n_perm, hipMemcpyDeviceToHost, st));
-			HIP_TRY(hipMemcpyAsync(h_count, count.p, sizeof(int64_t) * (size_t)T, hipMemcpyDeviceToHost, st));
+			if (width > 0) HIP_TRY(hipMemcpyAsync(h_max, max_stat.p, sizeof(double) * (size_t)n_perm * width, hipMemcpyDeviceToHost, st));
+			if (T > 0) HIP_TRY(hipMemcpyAsync(h_count, count.p, sizeof(int64_t) * (size_t)T, hipMemcpyDeviceToHost, st));
 			HIP_TRY(hipStreamSynchronize(st));
 			return 0;
 		});
@@ -761,9 +767,10 @@ int quant_enqueue_panel(hibag_hip_quant *q, uint64_t seed, uint64_t p0, int n_la
 	return 0;
 }
 
-// the basis: the constant, then the covariates, orthonormalised by modified Gram-Schmidt applied twice.  Returns the column
-// that is in the span of the earlier ones, or -1.
-int quant_orthonormalise(const double *covar, int n, int nb, std::vector<double> &Q)
+// the basis: the constant, then the covariates, orthonormalised by modified Gram-Schmidt applied twice -- under the inner
+// product sum_i (w_i a_i) b_i where `w` is given (hlaAssocScore), else the plain one.  Returns the column that is in the span
+// of the earlier ones, or -1.
+int quant_orthonormalise(const double *covar, int n, int nb, std::vector<double> &Q, const double *w = nullptr)
 {
 	Q.assign((size_t)nb * n, 0.0);
 	std::vector<double> v((size_t)n);
@@ -771,17 +778,17 @@ int quant_orthonormalise(const double *covar, int n, int nb, std::vector<double>
 		double zz = 0.0;
 		for (int i = 0; i < n; i++) {
 			v[i] = k == 0 ? 1.0 : covar[(size_t)(k - 1) * n + i];
-			zz += v[i] * v[i];
+			zz += w ? (w[i] * v[i]) * v[i] : v[i] * v[i];
 		}
 		for (int pass = 0; pass < 2; pass++)
 			for (int j = 0; j < k; j++) {
 				const double *qj = &Q[(size_t)j * n];
 				double c = 0.0;
-				for (int i = 0; i < n; i++) c += qj[i] * v[i];
+				for (int i = 0; i < n; i++) c += w ? (w[i] * qj[i]) * v[i] : qj[i] * v[i];
 				for (int i = 0; i < n; i++) v[i] -= c * qj[i];
 			}
 		double ss = 0.0;
-		for (int i = 0; i < n; i++) ss += v[i] * v[i];
+		for (int i = 0; i < n; i++) ss += w ? (w[i] * v[i]) * v[i] : v[i] * v[i];
 		const double s = sqrt(ss);
 		if (!(s > 1e-9 * sqrt(zz))) return k;
 		for (int i = 0; i < n; i++) Q[(size_t)k * n + i] = v[i] / s;
@@ -1016,6 +1023,377 @@ int hibag_hip_assoc_quant_gram_ms(const hibag_hip_quant *q, double *ms)
 {
 	if (!q || !ms) return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_quant_gram_ms: null argument");
 	*ms = q->gram_ms;
+	return 0;
+}
+
+} // extern "C"
+
+// ---- hlaAssocScore (kernels: hibag_k_score.h) ----------------------------------------------------
+// Score tests of a case / control trait under the base model y ~ covariates, on the tests or sets of rows of an association
+// handle.  hibag_hip_assoc_score_new fits the base model once with the regression driver above, takes the residuals, the
+// weights and the weighted basis on the host, uploads them and has the device project the feature rows.
+// hibag_hip_assoc_score_sets installs the sets: the device sums their weighted Grams, the host factorises them and uploads
+// the factors, and the observed residuals -- replicate 0, all signs +1 -- go through the kernels of the replicates.
+// hibag_hip_assoc_score_resample then works in panels of replicates with the panel driver of the permutation entries: the
+// residual panel from the signs (k_score_coef, k_score_project), the FP64 Gram (k_quant_gram, as it is), one pass over it (k_score_stat).
+
+struct hibag_hip_score {
+	hibag_hip_assoc *h = nullptr;                // borrowed; outlives this handle
+	int nb = 0, n_sets = -1, n_df = 0;           // basis rows; the installed sets (-1: none yet); their distinct degrees of freedom
+	double b_coef[GLM_SLOTS], b_se[GLM_SLOTS], b_dev = 0; // the base model's fit
+	int32_t b_it = 0, b_fl = 0;
+	double ms[3] = {0, 0, 0};                    // project, Gram, statistic of the last resampling call
+	DevBuf basis, e, w;                          // double [nb][kp], [kp], [kp]
+	DevBuf sets, rows, factor, stat_obs;         // ScoreSet [n_sets], int32 kept rows, double packed factors, double [n_sets]
+	DevBuf panel, gram, part;                    // per-call panel: double [pp / 16][kp / 4][64], [rows][pp], [segments][13][ldp]
+	size_t ldp = 0;
+	PermOut out;                                 // per resampling call
+	std::vector<double> h_proj, h_g, h_stat;     // [rows][nb], [rows], [n_sets]
+	std::vector<int32_t> h_df, h_flags;          // [n_sets]
+	std::vector<hipEvent_t> ev;                  // four per panel of the last resampling call
+
+	~hibag_hip_score()
+	{
+		if (!h) return;
+		(void)hipSetDevice(h->device);
+		if (h->st) (void)hipStreamSynchronize(h->st);
+		for (DevBuf *b : {&basis, &e, &w, &sets, &rows, &factor, &stat_obs, &panel, &gram, &part}) b->release();
+		out.release();
+		for (hipEvent_t x : ev) (void)hipEventDestroy(x);
+	}
+};
+
+namespace {
+
+int score_panel_perms(const hibag_hip_score *s, int64_t n)
+{
+	return panel_perms("HIBAG_SCORE_PANEL_PERMS", kQuantPanelBytes, sizeof(double) * (size_t)s->h->kp, QUANT_TILE, true, n);
+}
+
+int score_reserve_panel(hibag_hip_score *s, int pp)
+{
+	const hibag_hip_assoc *h = s->h;
+	const size_t ldp = ((size_t)pp + SCORE_BLOCK - 1) / SCORE_BLOCK * SCORE_BLOCK, n_seg = ((size_t)std::max(h->D.n, 1) + SCORE_SEG - 1) / SCORE_SEG;
+	if (s->panel.reserve(sizeof(double) * (size_t)pp * h->kp) || s->gram.reserve(sizeof(double) * (size_t)h->rows * pp) ||
+		s->part.reserve(sizeof(double) * n_seg * QUANT_MAX_BASIS * ldp))
+		return HIBAG_HIP_ENOMEM;
+	s->ldp = std::max(s->ldp, ldp);                          // (the row stride of what is reserved; it only grows)
+	return 0;
+}
+
+// replicates p0 .. p0 + n_lab - 1 (n_lab <= the reserved panel) through the three kernels; the Gram has row stride ldc;
+// ev: four events around them, or null
+int score_enqueue_panel(hibag_hip_score *s, uint64_t seed, uint64_t p0, int n_lab, size_t ldc, double *stat_out, double *max_out,
+	const double *stat_obs, unsigned long long *count, const hipEvent_t *ev)
+{
+	hibag_hip_assoc *h = s->h;
+	const int n = h->D.n, kp = h->kp, tiles = (n_lab + QUANT_TILE - 1) / QUANT_TILE;
+	if (ev) HIP_TRY(hipEventRecord(ev[0], h->st));
+	const unsigned n_blk = (unsigned)((n_lab + SCORE_BLOCK - 1) / SCORE_BLOCK);
+	hipLaunchKernelGGL(k_score_coef, dim3(n_blk, (n + SCORE_SEG - 1) / SCORE_SEG), dim3(SCORE_THREADS), 0, h->st, seed, p0, n_lab, n, kp,
+		s->e.as<double>(), s->w.as<double>(), s->basis.as<double>(), s->nb, s->part.as<double>(), s->ldp);
+	hipLaunchKernelGGL(k_score_project, dim3(n_blk, (kp + SCORE_SEG - 1) / SCORE_SEG), dim3(SCORE_THREADS), 0, h->st, seed, p0, n_lab, n, kp,
+		s->e.as<double>(), s->w.as<double>(), s->basis.as<double>(), s->nb, s->part.as<double>(), s->ldp, s->panel.as<double>());
+	if (ev) HIP_TRY(hipEventRecord(ev[1], h->st));
+	hipLaunchKernelGGL(k_quant_gram, dim3(tiles, (h->rows + QUANT_TILE - 1) / QUANT_TILE), dim3(QUANT_GRAM_WAVES * 64), 0, h->st,
+		h->feat.as<int8_t>(), h->rows, kp, s->panel.as<double>(), s->gram.as<double>(), ldc);
+	if (ev) HIP_TRY(hipEventRecord(ev[2], h->st));
+	hipLaunchKernelGGL(k_score_stat, dim3((n_lab + 63) / 64), dim3(64), 0, h->st, s->gram.as<double>(), ldc, n_lab, s->sets.as<ScoreSet>(),
+		s->n_sets, s->rows.as<int32_t>(), s->factor.as<double>(), s->n_df, stat_out, max_out, stat_obs, count);
+	if (ev) HIP_TRY(hipEventRecord(ev[3], h->st));
+	HIP_TRY(hipGetLastError());
+	return 0;
+}
+
+} // namespace
+
+extern "C" {
+
+hibag_hip_score *hibag_hip_assoc_score_new(hibag_hip_assoc *h, const double *covar, int n_covar, const double *weight, int maxit,
+	double epsilon)
+{
+	if (!h) { hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_score_new: null handle"); return nullptr; }
+	static_assert(QUANT_MAX_BASIS == HIBAG_HIP_GLM_MAX_COVAR + 1, "the constant and the covariates");
+	static_assert(SCORE_MAX_ROWS == HIBAG_HIP_SCORE_MAX_ROWS && SCORE_MAX_ROWS <= SCORE_SET_LD, "the header's set size");
+	hibag_hip_score *s = new (std::nothrow) hibag_hip_score;
+	if (!s) { hibag_fail(HIBAG_HIP_ENOMEM, "out of host memory"); return nullptr; }
+	s->h = h;
+	s->nb = n_covar + 1;
+	const int n = h->D.n, kp = h->kp, q = n_covar, nb = n_covar + 1, rows = h->rows;
+
+	// the base model: the d = 0 fit of section 23, one fit with the kernels of hibag_hip_assoc_glm
+	const GlmCall call{"hibag_hip_assoc_score_new", h, covar, n_covar, weight, maxit, epsilon, s->b_coef, s->b_se, &s->b_dev, &s->b_it, &s->b_fl,
+		nullptr};
+	const GlmFit base{-1, -1};
+	if (call.check_control(HIBAG_HIP_GLM_MAX_COVAR) || call.check_values() ||
+		call.run(GLM_SLOTS, &base, sizeof(GlmFit), 1,
+			[&](const double *d_cov, const double *d_w) {
+				hipLaunchKernelGGL(k_glm_image, dim3((unsigned)(((size_t)kp * GLM_SLOTS + 255) / 256)), dim3(256), 0, h->st, d_cov, d_w, n, q, kp,
+					h->glm_img.as<double>(), h->glm_wt.as<double>());
+			},
+			[&](const GlmOut &O) {
+				hipLaunchKernelGGL(k_glm_fit, dim3(1), dim3(GLM_WAVES * 64), 0, h->st, h->glm_img.as<double>(), h->glm_wt.as<double>(),
+					h->y.as<int8_t>(), h->feat.as<int8_t>(), h->glm_fits.as<GlmFit>(), n, kp, q, maxit, epsilon, O.coef, O.se, O.dev, O.it, O.fl);
+			})) {
+		delete s;
+		return nullptr;
+	}
+	if (s->b_fl & GLM_FLAG_RANK) {
+		hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_score_new: the covariates are collinear (the base model is rank-deficient)");
+		delete s;
+		return nullptr;
+	}
+
+	// residuals and weights from the base model's coefficients, in index order (section 28 item 2)
+	std::vector<int8_t> y((size_t)kp);
+	std::vector<double> img((size_t)(nb + 2) * kp, 0.0), Q;     // the padded rows: basis, e, w
+	double *e = &img[(size_t)nb * kp], *w = e + kp;
+	auto fail = [&]() { delete s; return (hibag_hip_score *)nullptr; };
+	if (hipSetDevice(h->device) != hipSuccess || enqueued(h->st, [&]() -> int {
+			HIP_TRY(hipMemcpyAsync(y.data(), h->y.p, (size_t)kp, hipMemcpyDeviceToHost, h->st));
+			HIP_TRY(hipStreamSynchronize(h->st));
+			return 0;
+		})) return fail();
+	for (int i = 0; i < n; i++) {
+		double eta = s->b_coef[0];
+		for (int k = 0; k < q; k++) eta += covar[(size_t)k * n + i] * s->b_coef[GLM_COV0 + k];
+		double t = exp(eta);
+		if (eta < -30.0) t = GLM_EPS;
+		if (eta > 30.0) t = 1.0 / GLM_EPS;
+		const double mu = t / (1.0 + t), v = mu * (1.0 - mu), wt = weight ? weight[i] : 1.0;
+		w[i] = wt * v;
+		e[i] = wt * ((y[i] ? 1.0 : 0.0) - mu);
+	}
+	const int bad = quant_orthonormalise(covar, n, nb, Q, w);
+	if (bad >= 0) {
+		hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_score_new: the covariates are collinear (column %d lies in the span of the constant "
+			"and the columns before it under the base model's weights)", bad - 1);
+		return fail();
+	}
+	for (int k = 0; k < nb; k++) std::copy(&Q[(size_t)k * n], &Q[(size_t)k * n] + n, &img[(size_t)k * kp]);
+
+	TempBuf d_proj;
+	s->h_proj.resize((size_t)rows * nb);
+	if (s->basis.reserve(sizeof(double) * (size_t)nb * kp) || s->e.reserve(sizeof(double) * (size_t)kp) || s->w.reserve(sizeof(double) * (size_t)kp) ||
+		d_proj.reserve(sizeof(double) * (size_t)rows * nb) || score_reserve_panel(s, QUANT_TILE))
+		return fail();
+	if (enqueued(h->st, [&]() -> int {
+			HIP_TRY(hipMemcpyAsync(s->basis.p, img.data(), sizeof(double) * (size_t)nb * kp, hipMemcpyHostToDevice, h->st));
+			HIP_TRY(hipMemcpyAsync(s->e.p, e, sizeof(double) * (size_t)kp, hipMemcpyHostToDevice, h->st));
+			HIP_TRY(hipMemcpyAsync(s->w.p, w, sizeof(double) * (size_t)kp, hipMemcpyHostToDevice, h->st));
+			hipLaunchKernelGGL(k_score_proj, dim3(rows), dim3(256), 0, h->st, h->feat.as<int8_t>(), kp, n, s->w.as<double>(), s->basis.as<double>(),
+				nb, d_proj.as<double>());
+			HIP_TRY(hipGetLastError());
+			HIP_TRY(hipMemcpyAsync(s->h_proj.data(), d_proj.p, sizeof(double) * (size_t)rows * nb, hipMemcpyDeviceToHost, h->st));
+			HIP_TRY(hipStreamSynchronize(h->st));
+			return 0;
+		})) return fail();
+	return s;
+}
+
+void hibag_hip_assoc_score_free(hibag_hip_score *s) { delete s; }
+
+int hibag_hip_assoc_score_base(hibag_hip_score *s, double *coef, double *se, double *deviance, int32_t *iterations, int32_t *flags)
+{
+	if (!s || !coef || !se || !deviance || !iterations || !flags) return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_score_base: null argument");
+	std::copy(s->b_coef, s->b_coef + GLM_SLOTS, coef);
+	std::copy(s->b_se, s->b_se + GLM_SLOTS, se);
+	*deviance = s->b_dev; *iterations = s->b_it; *flags = s->b_fl;
+	return 0;
+}
+
+int hibag_hip_assoc_score_sets(hibag_hip_score *s, const int32_t *set_start, const int32_t *set_rows, int n_sets, double *proj, double *S,
+	int32_t *kept)
+{
+	if (!s || !proj || (n_sets > 0 && (!S || !kept))) return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_score_sets: null argument");
+	if (n_sets < 0 || n_sets > kMaxTests || !set_start || set_start[0] != 0)
+		return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_score_sets: need 0 <= n_sets <= %d and set_start with set_start[0] = 0", kMaxTests);
+	hibag_hip_assoc *h = s->h;
+	std::vector<int> seen((size_t)h->rows, -1);
+	for (int t = 0; t < n_sets; t++) {
+		const int m = set_start[t + 1] - set_start[t];
+		if (m < 0) return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_score_sets: set_start is not monotone at set %d", t);
+		if (m > SCORE_MAX_ROWS) return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_score_sets: set %d has %d rows; at most %d", t, m, SCORE_MAX_ROWS);
+		if (m > 0 && !set_rows) return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_score_sets: set_rows is null");
+		for (int j = 0; j < m; j++) {
+			const int r = set_rows[set_start[t] + j];
+			if (r < 0 || r >= h->rows)
+				return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_score_sets: set %d names row %d, outside the handle's %d", t, r, h->rows);
+			if (seen[(size_t)r] == t) return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_score_sets: set %d names row %d twice", t, r);
+			seen[(size_t)r] = t;
+		}
+	}
+	const int nb = s->nb, kp = h->kp, total = set_start[n_sets], ns = std::max(n_sets, 1);
+	HIP_TRY(hipSetDevice(h->device));
+	TempBuf d_start, d_rows, d_S;
+	std::vector<double> S32((size_t)ns * SCORE_SET_LD * SCORE_SET_LD);
+	if (d_start.reserve(sizeof(int32_t) * (size_t)(n_sets + 1)) || d_rows.reserve(sizeof(int32_t) * (size_t)std::max(total, 1)) ||
+		d_S.reserve(sizeof(double) * S32.size()) || s->stat_obs.reserve(sizeof(double) * (size_t)ns))
+		return HIBAG_HIP_ENOMEM;
+	if (n_sets > 0)
+		if (int rc = enqueued(h->st, [&]() -> int {
+				HIP_TRY(hipMemcpyAsync(d_start.p, set_start, sizeof(int32_t) * (size_t)(n_sets + 1), hipMemcpyHostToDevice, h->st));
+				if (total) HIP_TRY(hipMemcpyAsync(d_rows.p, set_rows, sizeof(int32_t) * (size_t)total, hipMemcpyHostToDevice, h->st));
+				hipLaunchKernelGGL(k_score_setgram, dim3(n_sets), dim3(SCORE_GRAM_WAVES * 64), 0, h->st, h->feat.as<int8_t>(), kp, s->w.as<double>(),
+					d_start.as<int32_t>(), d_rows.as<int32_t>(), d_S.as<double>());
+				HIP_TRY(hipGetLastError());
+				HIP_TRY(hipMemcpyAsync(S32.data(), d_S.p, sizeof(double) * (size_t)n_sets * SCORE_SET_LD * SCORE_SET_LD, hipMemcpyDeviceToHost, h->st));
+				HIP_TRY(hipStreamSynchronize(h->st));
+				return 0;
+			})) return rc;
+
+	// per set: V = S - P P', its Cholesky factor in column order with aliased columns dropped (section 28 item 4)
+	std::vector<ScoreSet> sets((size_t)ns, ScoreSet{0, 0, 0, 0});
+	std::vector<int32_t> krows;
+	std::vector<double> factor;
+	s->h_df.assign((size_t)n_sets, 0);
+	s->h_flags.assign((size_t)n_sets, 0);
+	const std::vector<int32_t> &rsum = h->h_row_sum;
+	const bool base_failed = (s->b_fl & GLM_FLAG_MAXIT) != 0;
+	size_t s_at = 0;
+	for (int t = 0; t < n_sets; t++) {
+		const int m = set_start[t + 1] - set_start[t];
+		const int32_t *rw = set_rows + set_start[t];
+		const double *St = &S32[(size_t)t * SCORE_SET_LD * SCORE_SET_LD];
+		double V[SCORE_MAX_ROWS][SCORE_MAX_ROWS], L[SCORE_MAX_ROWS][SCORE_MAX_ROWS];
+		for (int a = 0; a < m; a++)
+			for (int b = 0; b <= a; b++) {
+				const double sab = St[a * SCORE_SET_LD + b];
+				double pp = 0.0;
+				for (int k = 0; k < nb; k++) pp += s->h_proj[(size_t)rw[a] * nb + k] * s->h_proj[(size_t)rw[b] * nb + k];
+				V[a][b] = V[b][a] = sab - pp;
+				S[s_at + (size_t)a * m + b] = S[s_at + (size_t)b * m + a] = sab;
+			}
+		s_at += (size_t)m * m;
+		int keep[SCORE_MAX_ROWS], d = 0, dropped = 0;             // the kept columns' positions in the set, in order
+		int32_t mask = 0;
+		for (int j = 0; j < m; j++) {
+			if (rsum[(size_t)rw[j]] == 0) { dropped++; continue; }       // nobody carries it: decided from the integer row sum
+			double piv = V[j][j];
+			for (int c = 0; c < d; c++) piv -= L[j][c] * L[j][c];
+			if (!(piv > 1e-11 * St[j * SCORE_SET_LD + j])) { dropped++; continue; }
+			L[j][d] = sqrt(piv);
+			for (int i = j + 1; i < m; i++) {
+				double v = V[i][j];
+				for (int c = 0; c < d; c++) v -= L[i][c] * L[j][c];
+				L[i][d] = v / L[j][d];
+			}
+			keep[d++] = j;
+			mask |= (int32_t)1 << j;
+		}
+		kept[t] = mask;
+		int32_t fl = d == 0 ? GLM_FLAG_RANK : dropped ? GLM_FLAG_ALIASED : 0;
+		if (base_failed) { fl |= GLM_FLAG_MAXIT; d = 0; }
+		s->h_flags[(size_t)t] = fl;
+		s->h_df[(size_t)t] = d;
+		sets[(size_t)t] = ScoreSet{(int)krows.size(), d, 0, (int)factor.size()};
+		for (int a = 0; a < d; a++) {
+			krows.push_back(rw[keep[a]]);
+			for (int b = 0; b <= a; b++) factor.push_back(L[keep[a]][b]);
+		}
+	}
+	// the slots of the distinct degrees of freedom, ascending
+	int slot_of[SCORE_MAX_ROWS + 1];
+	std::fill(slot_of, slot_of + SCORE_MAX_ROWS + 1, -1);
+	for (int t = 0; t < n_sets; t++) slot_of[s->h_df[(size_t)t]] = 0;
+	s->n_df = 0;
+	for (int d = 1; d <= SCORE_MAX_ROWS; d++)
+		if (slot_of[d] == 0) slot_of[d] = s->n_df++;
+	for (int t = 0; t < n_sets; t++) sets[(size_t)t].slot = std::max(slot_of[sets[(size_t)t].d], 0);
+	std::copy(s->h_proj.begin(), s->h_proj.end(), proj);
+
+	s->n_sets = n_sets;
+	s->h_g.assign((size_t)h->rows, 0.0);
+	s->h_stat.assign((size_t)n_sets, std::nan(""));
+	if (s->sets.reserve(sizeof(ScoreSet) * (size_t)ns) || s->rows.reserve(sizeof(int32_t) * std::max<size_t>(krows.size(), 1)) ||
+		s->factor.reserve(sizeof(double) * std::max<size_t>(factor.size(), 1)) || score_reserve_panel(s, QUANT_TILE))
+		return HIBAG_HIP_ENOMEM;
+	return enqueued(h->st, [&]() -> int {
+		HIP_TRY(hipMemcpyAsync(s->sets.p, sets.data(), sizeof(ScoreSet) * (size_t)ns, hipMemcpyHostToDevice, h->st));
+		if (!krows.empty()) HIP_TRY(hipMemcpyAsync(s->rows.p, krows.data(), sizeof(int32_t) * krows.size(), hipMemcpyHostToDevice, h->st));
+		if (!factor.empty()) HIP_TRY(hipMemcpyAsync(s->factor.p, factor.data(), sizeof(double) * factor.size(), hipMemcpyHostToDevice, h->st));
+		// the observed residuals: replicate 0, a panel of its own
+		if (int e = score_enqueue_panel(s, 0, 0, 1, QUANT_TILE, s->stat_obs.as<double>(), nullptr, nullptr, nullptr, nullptr)) return e;
+		HIP_TRY(hipMemcpy2DAsync(s->h_g.data(), sizeof(double), s->gram.p, sizeof(double) * QUANT_TILE, sizeof(double), (size_t)h->rows,
+			hipMemcpyDeviceToHost, h->st));
+		if (n_sets) HIP_TRY(hipMemcpyAsync(s->h_stat.data(), s->stat_obs.p, sizeof(double) * (size_t)n_sets, hipMemcpyDeviceToHost, h->st));
+		HIP_TRY(hipStreamSynchronize(h->st));
+		return 0;
+	});
+}
+
+int hibag_hip_assoc_score_observed(hibag_hip_score *s, double *g, double *stat, int32_t *df, int32_t *flags)
+{
+	if (!s || !g || !stat || !df || !flags) return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_score_observed: null argument");
+	if (s->n_sets < 0) return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_score_observed: no sets are installed (hibag_hip_assoc_score_sets)");
+	std::copy(s->h_g.begin(), s->h_g.end(), g);
+	std::copy(s->h_stat.begin(), s->h_stat.end(), stat);
+	std::copy(s->h_df.begin(), s->h_df.end(), df);
+	std::copy(s->h_flags.begin(), s->h_flags.end(), flags);
+	return 0;
+}
+
+int hibag_hip_assoc_score_n_df(const hibag_hip_score *s)
+{
+	if (!s || s->n_sets < 0) return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_score_n_df: null handle or no sets installed");
+	return s->n_df;
+}
+
+int hibag_hip_assoc_score_resample(hibag_hip_score *s, uint64_t seed, uint64_t p0, int64_t n_perm, double *max_stat, int64_t *count_point)
+{
+	if (!s || n_perm < 0 || !count_point || (n_perm > 0 && !max_stat))
+		return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_score_resample: null argument or n_perm < 0");
+	if (s->n_sets < 0) return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_score_resample: no sets are installed (hibag_hip_assoc_score_sets)");
+	if (int rc = check_perm_range("hibag_hip_assoc_score_resample", "residuals", p0, (uint64_t)n_perm)) return rc;
+	hibag_hip_assoc *h = s->h;
+	const int T = s->n_sets, n_df = s->n_df;
+	std::fill(count_point, count_point + T, (int64_t)0);
+	s->ms[0] = s->ms[1] = s->ms[2] = 0;
+	if (n_perm == 0 || T == 0) return 0;
+	HIP_TRY(hipSetDevice(h->device));
+	const int pp = score_panel_perms(s, n_perm);
+	const size_t n_panel = (size_t)((n_perm + pp - 1) / pp);
+	if (score_reserve_panel(s, pp) || s->out.reserve(n_perm, T, n_df)) return HIBAG_HIP_ENOMEM;
+	while (s->ev.size() < 4 * n_panel) {
+		hipEvent_t x;
+		HIP_TRY(hipEventCreate(&x));
+		s->ev.push_back(x);
+	}
+	int rc = s->out.run(h->st, T, n_perm, pp, max_stat, count_point, [&](int64_t done, int n_lab) -> int {
+		return score_enqueue_panel(s, seed, p0 + (uint64_t)done, n_lab, (size_t)pp, nullptr, s->out.max_stat.as<double>() + (size_t)done * n_df,
+			s->stat_obs.as<double>(), s->out.count.as<unsigned long long>(), &s->ev[4 * (size_t)(done / pp)]);
+	}, n_df);
+	if (rc) return rc;
+	for (size_t j = 0; j < n_panel; j++)
+		for (int k = 0; k < 3; k++) {
+			float ms = 0;
+			HIP_TRY(hipEventElapsedTime(&ms, s->ev[4 * j + k], s->ev[4 * j + k + 1]));
+			s->ms[k] += ms;
+		}
+	return 0;
+}
+
+int hibag_hip_assoc_score_signs(hibag_hip_score *s, uint64_t seed, uint64_t p0, int n, int8_t *out)
+{
+	if (!s || n < 0 || (n > 0 && !out)) return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_score_signs: null argument or n < 0");
+	if (int rc = check_perm_range("hibag_hip_assoc_score_signs", "residuals", p0, (uint64_t)n)) return rc;
+	hibag_hip_assoc *h = s->h;
+	if (n == 0 || h->D.n == 0) return 0;
+	HIP_TRY(hipSetDevice(h->device));
+	const int pp = score_panel_perms(s, n), kp = h->kp, ns = h->D.n;
+	if (s->panel.reserve(sizeof(double) * (size_t)pp * kp)) return HIBAG_HIP_ENOMEM;      // (the panel's room, as int8 [pp][kp])
+	return download_panels(h->st, n, pp, s->panel.p, (size_t)kp, (size_t)ns, out, [&](int64_t done, int n_lab) -> int {
+		hipLaunchKernelGGL(k_score_signs, dim3((ns + 255) / 256), dim3(256), 0, h->st, ns, (size_t)kp, seed, p0 + (uint64_t)done, n_lab,
+			s->panel.as<int8_t>());
+		HIP_TRY(hipGetLastError());
+		return 0;
+	});
+}
+
+int hibag_hip_assoc_score_ms(const hibag_hip_score *s, double *ms)
+{
+	if (!s || !ms) return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_score_ms: null argument");
+	std::copy(s->ms, s->ms + 3, ms);
 	return 0;
 }
 

@@ -39,7 +39,8 @@ extern "C" {
                                        + the regression entries (hibag_hip_assoc_glm, _n_kept, _feature_rows): likewise;
                                        + the quantitative-trait entries (hibag_hip_assoc_quant_*): likewise;
                                        + the set regression (hibag_hip_assoc_glm_sets, hibag_hip_assoc_row_sums): likewise;
-                                       + the term regression (hibag_hip_assoc_glm_terms, hibag_hip_assoc_row_gram): likewise */
+                                       + the term regression (hibag_hip_assoc_glm_terms, hibag_hip_assoc_row_gram): likewise;
+                                       + the score tests (hibag_hip_assoc_score_*): likewise */
 
 /* error codes */
 #define HIBAG_HIP_OK          0
@@ -455,6 +456,68 @@ int hibag_hip_assoc_quant_perm_rows(hibag_hip_quant *q, uint64_t seed, uint64_t 
 
 /* Event time of the Gram kernels of the last hibag_hip_assoc_quant_permute call, in ms (for measurements). */
 int hibag_hip_assoc_quant_gram_ms(const hibag_hip_quant *q, double *ms);
+
+/* ---- covariate-adjusted score tests with multiplier resampling: hlaAssocScore ------------
+ * Under the base model glm(y ~ covariates, family = binomial), fitted once, the score test of a SET of feature rows of the
+ * handle -- a single test's row, the two dummies of GENOTYPE, the residues of a position -- is T = U' V^-1 U with
+ * U = X~'(y - mu), X~ the rows projected off the covariates under the model's weights, chi-square with one degree of freedom
+ * per kept row.  Lin's multiplier resampling (Bioinformatics 21:781, 2005) replaces every sample's residual e_i by e_i s_i with
+ * independent signs; replicate 0 has all signs +1 and is the observed run.  All rows under all replicates of a panel are one
+ * real-valued Gram matrix, int8 feature rows x FP64 resampled residuals, on the FP64 matrix cores; no fit is repeated.  The
+ * definitions -- base fit, weighted basis, sign generator, orders of the sums, statistic -- are DESIGN.md section 28; results
+ * do not depend on the panel size, on the other sets or on how a run of replicates is split over calls. */
+typedef struct hibag_hip_score hibag_hip_score;          /* a base model and its sets on a hibag_hip_assoc, which it borrows */
+
+#define HIBAG_HIP_SCORE_MAX_ROWS 30   /* feature rows of a set */
+
+/* Fits the base model (the fit of hibag_hip_assoc_glm without an h column; covar, weight, maxit, epsilon as there), takes
+ * mu, the weights w = weight mu (1 - mu) and the residuals e = weight (y - mu) on the host, orthonormalises (1, covariates)
+ * under sum_i w_i a_i b_i by modified Gram-Schmidt applied twice, and projects every feature row of `h` on that basis on the
+ * device of `h`.  A base fit that did not converge (HIBAG_HIP_GLM_MAXIT in hibag_hip_assoc_score_base's flags) leaves a
+ * handle whose sets all carry that flag and NaN.  The handle is owned separately (hibag_hip_assoc_score_free) and must be
+ * freed before `h`; it uses the stream of `h`, so the two are used by one host thread at a time.  NULL on failure: EINVAL as
+ * hibag_hip_assoc_glm, and for a rank-deficient base fit or a column in the weighted span of the earlier ones (the message
+ * says "collinear"). */
+hibag_hip_score *hibag_hip_assoc_score_new(hibag_hip_assoc *h, const double *covar, int n_covar, const double *weight, int maxit,
+	double epsilon);
+void hibag_hip_assoc_score_free(hibag_hip_score *s);
+
+/* The base model's fit as hibag_hip_assoc_glm reports fit n_tests: coef, se float64 [16] by slot (0 the intercept,
+ * 3 .. 2 + n_covar the covariates, NaN elsewhere), *deviance, *iterations, *flags. */
+int hibag_hip_assoc_score_base(hibag_hip_score *s, double *coef, double *se, double *deviance, int32_t *iterations, int32_t *flags);
+
+/* Installs the sets (set_start, set_rows as hibag_hip_assoc_glm_sets takes them; a set has at most HIBAG_HIP_SCORE_MAX_ROWS
+ * rows) and runs the observed residuals through them.  Per set the device sums S[a][b] = sum_i w_i F[a][i] F[b][i]; the host
+ * forms V = S - P P' (P the set's rows of proj) and factorises it in column order.  A row with row sum 0, and a column whose
+ * pivot is <= 1e-11 S_jj, is dropped: its bit in `kept` is clear, the set has HIBAG_HIP_GLM_ALIASED and one degree of freedom
+ * less; a set left without columns (an empty one included) has HIBAG_HIP_GLM_RANK alone and NaN.
+ *   proj   float64 [rows][1 + n_covar]: feature row x basis column, every row of the handle
+ *   S      float64, set t's [m][m] (m its rows, symmetric) at the sum of the earlier sets' m^2
+ *   kept   int32 [n_sets]: bit j set = row j of the set is in its factor
+ * Installing sets again replaces the earlier ones.  EINVAL as hibag_hip_assoc_glm_sets, and for a set of more than 30 rows. */
+int hibag_hip_assoc_score_sets(hibag_hip_score *s, const int32_t *set_start, const int32_t *set_rows, int n_sets, double *proj, double *S,
+	int32_t *kept);
+
+/* The observed run: g float64 [rows] (every feature row's score), stat float64 [n_sets] (NaN where not fitted), df int32
+ * [n_sets] (the kept rows; 0 where not fitted), flags int32 [n_sets] (HIBAG_HIP_GLM_MAXIT: the base fit did not converge;
+ * _RANK; _ALIASED).  hibag_hip_assoc_score_n_df: the number of distinct values > 0 in df. */
+int hibag_hip_assoc_score_observed(hibag_hip_score *s, double *g, double *stat, int32_t *df, int32_t *flags);
+int hibag_hip_assoc_score_n_df(const hibag_hip_score *s);
+
+/* Replicates p0 .. p0 + n_perm - 1 (p0 >= 1; replicate p's signs depend on (seed, p) and the sample's index alone):
+ *   max_stat     float64 [n_perm][n_df]: per replicate and distinct df value (ascending) the largest non-NaN statistic over
+ *                the sets with that df, NaN if none
+ *   count_point  int64 [n_sets]: the replicates of THIS call with T >= the observed T (0 where that is NaN)
+ * A run may be split over calls: max_stat concatenates and the counts add.  The work goes in panels of replicates, in whole
+ * tiles of 16 (HIBAG_SCORE_PANEL_PERMS per panel if that is set, read per call; else about 256 MB of residuals). */
+int hibag_hip_assoc_score_resample(hibag_hip_score *s, uint64_t seed, uint64_t p0, int64_t n_perm, double *max_stat, int64_t *count_point);
+
+/* The signs themselves: out int8 [n][n_kept], row j = replicate p0 + j, +1 or -1 (for tests of the generator). */
+int hibag_hip_assoc_score_signs(hibag_hip_score *s, uint64_t seed, uint64_t p0, int n, int8_t *out);
+
+/* Event times of the last hibag_hip_assoc_score_resample call, in ms: ms[0] the residual panels (signs, projection, panel
+ * write), ms[1] the Gram, ms[2] the statistics (for measurements). */
+int hibag_hip_assoc_score_ms(const hibag_hip_score *s, double *ms);
 
 /* ---- several models of one locus, merged: hlaPredMerge on the device ----------
  * hlaPredMerge(hlaPredict(m1, type = "response+prob"), hlaPredict(m2, ...), ...) (R/HIBAG.R:825-1023 around HIBAG_SumList,
