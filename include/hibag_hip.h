@@ -519,6 +519,47 @@ int hibag_hip_assoc_score_signs(hibag_hip_score *s, uint64_t seed, uint64_t p0, 
  * write), ms[1] the Gram, ms[2] the statistics (for measurements). */
 int hibag_hip_assoc_score_ms(const hibag_hip_score *s, double *ms);
 
+/* ---- multi-locus haplotypes: hlaHaplotypes, an EM over imputed calls ---------
+ * Which alleles of 2 .. 6 loci sit together on a chromosome, and how often: an EM over the haplotype pairs that each
+ * sample's candidate allele pairs (hibag_hip_predict_topk's lists, or certain typing) allow.  The definitions -- candidate
+ * and state order, the haplotype key, the one summation rule, the iteration -- are DESIGN.md section 29; every number is
+ * made of IEEE FP64 adds, multiplies and divides in a fixed order and does not depend on launch shapes. */
+typedef struct hibag_hip_haplo hibag_hip_haplo;          /* the states and the dictionary of one cohort, resident on a device */
+
+#define HIBAG_HIP_HAPLO_MAX_LOCI   6
+#define HIBAG_HIP_HAPLO_MAX_ALLELE 1024   /* alleles of a locus: 10 bits of the key each */
+#define HIBAG_HIP_HAPLO_MAX_K      64     /* candidates per sample and locus */
+
+/* Builds the states, the haplotype dictionary and every haplotype's list on `device` (-1: the calling thread's).
+ *   h1 / h2 / prob  int32, int32, float64 [n_loci][n_samp][k]: per locus and sample the candidate pairs in rank order
+ *                   (0-based allele indices, the smaller first when stored) with their weights.  A rank with
+ *                   HIBAG_HIP_NA_INTEGER or weight 0 is no candidate; a sample without a candidate at some locus is left out.
+ *   max_states      the most states one sample may have (the caller trims its candidates beforehand)
+ * EINVAL: n_loci outside 2 .. 6, k outside 1 .. HIBAG_HIP_HAPLO_MAX_K, an allele index outside [0, 1024) and not NA, a
+ * weight that is negative or not finite, a sample with more than max_states states, more than 2^31 - 1 entries (two per
+ * state) in total, no sample used.  NULL on failure (hibag_hip_last_error says why). */
+hibag_hip_haplo *hibag_hip_haplo_new(int n_samp, int n_loci, int k, const int32_t *h1, const int32_t *h2, const double *prob,
+	int max_states, int device);
+void hibag_hip_haplo_free(hibag_hip_haplo *h);
+
+/* *n_hap: distinct haplotypes H; *n_states: states of all used samples; *n_used; used int32 [n_samp]: 1 = used; states
+ * int64 [n_samp]: states per sample (0 for one left out).  Every output may be NULL. */
+int hibag_hip_haplo_dims(const hibag_hip_haplo *h, int32_t *n_hap, int64_t *n_states, int32_t *n_used, int32_t *used, int64_t *states);
+
+/* The EM from f = 1 / H: at most maxit >= 1 iterations, stopping after the first with delta = max |f' - f| <= tol (tol >= 0).
+ *   freq float64 [H], keys uint64 [H]: the frequencies after the last iteration made and the haplotypes' keys (allele index
+ *   of locus l in bits 10 l .. 10 l + 9), ascending; *n_iter, *delta: iterations made and the last one's delta;
+ *   *n_zero: used samples whose states all have weight 0 under freq (their total is 0, their posteriors are 0, not NaN).
+ * A fit starts afresh: two fits on one handle give the same arrays. */
+int hibag_hip_haplo_fit(hibag_hip_haplo *h, int maxit, double tol, double *freq, uint64_t *keys, int32_t *n_iter, double *delta,
+	int32_t *n_zero);
+
+/* After a fit, under its frequencies: per sample the state with the largest posterior, the first of equals in state order:
+ * hapA / hapB int32 [n_samp][n_loci] (allele indices), prob float64 [n_samp] (that posterior), total float64 [n_samp] (the
+ * sample's likelihood, the sum of its states' weights).  A sample left out has HIBAG_HIP_NA_INTEGER and NaN.  ESTATE before
+ * a fit. */
+int hibag_hip_haplo_calls(hibag_hip_haplo *h, int32_t *hapA, int32_t *hapB, double *prob, double *total);
+
 /* ---- several models of one locus, merged: hlaPredMerge on the device ----------
  * hlaPredMerge(hlaPredict(m1, type = "response+prob"), hlaPredict(m2, ...), ...) (R/HIBAG.R:825-1023 around HIBAG_SumList,
  * HIBAG_UpdateAddProbW, HIBAG_NormalizeProb, src/HIBAG.cpp:1455-1547) without the k posterior matrices leaving the device,
