@@ -68,8 +68,9 @@ EXPORTS = [
     "hibag_hip_assoc_quant_permute", "hibag_hip_assoc_quant_perm_rows", "hibag_hip_assoc_quant_gram_ms",
     "hibag_hip_assoc_score_new", "hibag_hip_assoc_score_free", "hibag_hip_assoc_score_base", "hibag_hip_assoc_score_sets",
     "hibag_hip_assoc_score_observed", "hibag_hip_assoc_score_n_df", "hibag_hip_assoc_score_resample", "hibag_hip_assoc_score_signs",
-    "hibag_hip_assoc_score_ms",
+    "hibag_hip_assoc_score_ms", "hibag_hip_assoc_rscore_sets",
     "hibag_hip_haplo_new", "hibag_hip_haplo_free", "hibag_hip_haplo_dims", "hibag_hip_haplo_fit", "hibag_hip_haplo_calls",
+    "hibag_hip_haplo_dosage",
     "hibag_hip_oob_knock_variants", "hibag_hip_oob_knock",
     "hibag_hip_test_layout_plan", "hibag_hip_test_layout_count", "hibag_hip_test_layout_get", "hibag_hip_test_layout_free",
     "hibag_hip_test_set_chunking", "hibag_hip_test_last_launch", "hibag_hip_test_plan_total", "hibag_hip_test_plan_accum",
@@ -227,6 +228,8 @@ def lib() -> C.CDLL:
         L.hibag_hip_assoc_score_resample.argtypes = [vp, C.c_uint64, C.c_uint64, i64, vp, vp]
         L.hibag_hip_assoc_score_signs.argtypes = [vp, C.c_uint64, C.c_uint64, i32, vp]
         L.hibag_hip_assoc_score_ms.argtypes = [vp, vp]
+    if hasattr(L, "hibag_hip_assoc_rscore_sets"):
+        L.hibag_hip_assoc_rscore_sets.argtypes = [vp, vp, i32, vp, vp, i32, vp, vp, vp]
     if hasattr(L, "hibag_hip_haplo_new"):
         L.hibag_hip_haplo_new.argtypes = [i32, i32, i32, vp, vp, vp, i32, i32]
         L.hibag_hip_haplo_new.restype = vp
@@ -235,6 +238,8 @@ def lib() -> C.CDLL:
         L.hibag_hip_haplo_dims.argtypes = [vp, vp, vp, vp, vp, vp]
         L.hibag_hip_haplo_fit.argtypes = [vp, i32, dbl, vp, vp, vp, vp, vp]
         L.hibag_hip_haplo_calls.argtypes = [vp, vp, vp, vp, vp]
+    if hasattr(L, "hibag_hip_haplo_dosage"):
+        L.hibag_hip_haplo_dosage.argtypes = [vp, vp, i32, vp]
     if hasattr(L, "hibag_hip_cohort_new"):
         # (an older build selected with HIBAG_HIP_LIBRARY, e.g. the parent commit's for a baseline timing, lacks the cohort
         # entries: everything else still binds, and a call that needs them fails with AttributeError)

@@ -68,6 +68,7 @@ class _DeviceScore(_DeviceOmni):
     """The tests of one cohort on the device, with a base model and its score tests on them (``hibag_hip_score``)."""
 
     _s = None
+    n_score_rows = 0                    # rows of the last score_real_sets; 0: the handle's own rows are installed
 
     def score(self, covar: Optional[np.ndarray], weight: Optional[np.ndarray], maxit: int, epsilon: float) -> None:
         """The base model over the covariates [q, n_kept] and prior weights [n_kept]; ValueError for collinear covariates."""
@@ -108,7 +109,28 @@ class _DeviceScore(_DeviceOmni):
         S = np.empty(max(sum(len(s) ** 2 for s in sets), 1))
         kept = np.empty(max(len(sets), 1), np.int32)
         _lib.check(_lib.lib().hibag_hip_assoc_score_sets(self._s, _ptr(start), _ptr(rows), len(sets), _ptr(proj), _ptr(S), _ptr(kept)))
-        self.n_sets = len(sets)
+        self.n_sets, self.n_score_rows = len(sets), 0
+        out, at = [], 0
+        for s in sets:
+            out.append(S[at:at + len(s) ** 2].reshape(len(s), len(s)).copy())
+            at += len(s) ** 2
+        return proj, out, kept[:len(sets)]
+
+    def score_real_sets(self, rows: np.ndarray, sets: Sequence[Sequence[int]]):
+        """Installs sets over the real-valued rows [m, n_kept] in place of the handle's own; returns as ``score_sets``, proj
+        [m, n_basis].  ``score_observed`` and ``score_resample`` then run over these rows."""
+        rows = np.ascontiguousarray(rows, np.float64)
+        if rows.ndim != 2 or rows.shape[1] != self.n_kept:
+            raise ValueError("rows must be a [m, n_kept] array")
+        start = np.zeros(len(sets) + 1, np.int32)
+        start[1:] = np.cumsum([len(s) for s in sets])
+        idx = np.ascontiguousarray([r for s in sets for r in s] or [0], np.int32)
+        proj = np.empty((len(rows), self.n_basis))
+        S = np.empty(max(sum(len(s) ** 2 for s in sets), 1))
+        kept = np.empty(max(len(sets), 1), np.int32)
+        _lib.check(_lib.lib().hibag_hip_assoc_rscore_sets(self._s, _ptr(rows), len(rows), _ptr(start), _ptr(idx), len(sets), _ptr(proj),
+                                                              _ptr(S), _ptr(kept)))
+        self.n_sets, self.n_score_rows = len(sets), len(rows)
         out, at = [], 0
         for s in sets:
             out.append(S[at:at + len(s) ** 2].reshape(len(s), len(s)).copy())
@@ -116,8 +138,8 @@ class _DeviceScore(_DeviceOmni):
         return proj, out, kept[:len(sets)]
 
     def score_observed(self):
-        """(g [rows], stat [n_sets], df, flags int32 [n_sets])."""
-        g, stat = np.empty(self.n_rows), np.empty(self.n_sets)
+        """(g [rows], stat [n_sets], df, flags int32 [n_sets]); the rows are those of the last install."""
+        g, stat = np.empty(self.n_score_rows or self.n_rows), np.empty(self.n_sets)
         df, flags = np.empty(self.n_sets, np.int32), np.empty(self.n_sets, np.int32)
         _lib.check(_lib.lib().hibag_hip_assoc_score_observed(self._s, _ptr(g), _ptr(stat), _ptr(df), _ptr(flags)))
         return g, stat, df, flags

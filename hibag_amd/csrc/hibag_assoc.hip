@@ -33,6 +33,7 @@
 #include "hibag_k_glmt.h"
 #include "hibag_k_quant.h"
 #include "hibag_k_score.h"
+#include "hibag_k_rscore.h"
 
 using hibag_detail::DevBuf;
 
@@ -1036,6 +1037,8 @@ int hibag_hip_assoc_quant_gram_ms(const hibag_hip_quant *q, double *ms)
 // the factors, and the observed residuals -- replicate 0, all signs +1 -- go through the kernels of the replicates.
 // hibag_hip_assoc_score_resample then works in panels of replicates with the panel driver of the permutation entries: the
 // residual panel from the signs (k_score_coef, k_score_project), the FP64 Gram (k_quant_gram, as it is), one pass over it (k_score_stat).
+// hibag_hip_assoc_rscore_sets installs sets over real-valued rows of its own instead (hlaAssocHaplo, DESIGN.md section 30;
+// kernels: hibag_k_rscore.h): the same steps with k_rscore_proj, k_rscore_setgram and, per panel, k_rscore_gram.
 
 struct hibag_hip_score {
 	hibag_hip_assoc *h = nullptr;                // borrowed; outlives this handle
@@ -1046,9 +1049,13 @@ struct hibag_hip_score {
 	DevBuf basis, e, w;                          // double [nb][kp], [kp], [kp]
 	DevBuf sets, rows, factor, stat_obs;         // ScoreSet [n_sets], int32 kept rows, double packed factors, double [n_sets]
 	DevBuf panel, gram, part;                    // per-call panel: double [pp / 16][kp / 4][64], [rows][pp], [segments][13][ldp]
+	DevBuf X;                                    // hibag_hip_assoc_rscore_sets: double [x_rows][kp], zero on the padding samples
+	int x_rows = 0;
+	bool real = false;                           // the installed sets are over X, not over the handle's int8 rows
 	size_t ldp = 0;
 	PermOut out;                                 // per resampling call
 	std::vector<double> h_proj, h_g, h_stat;     // [rows][nb], [rows], [n_sets]
+	std::vector<double> h_xproj;                 // [x_rows][nb]: the projections of X
 	std::vector<int32_t> h_df, h_flags;          // [n_sets]
 	std::vector<hipEvent_t> ev;                  // four per panel of the last resampling call
 
@@ -1057,7 +1064,7 @@ struct hibag_hip_score {
 		if (!h) return;
 		(void)hipSetDevice(h->device);
 		if (h->st) (void)hipStreamSynchronize(h->st);
-		for (DevBuf *b : {&basis, &e, &w, &sets, &rows, &factor, &stat_obs, &panel, &gram, &part}) b->release();
+		for (DevBuf *b : {&basis, &e, &w, &sets, &rows, &factor, &stat_obs, &panel, &gram, &part, &X}) b->release();
 		out.release();
 		for (hipEvent_t x : ev) (void)hipEventDestroy(x);
 	}
@@ -1074,7 +1081,7 @@ int score_reserve_panel(hibag_hip_score *s, int pp)
 {
 	const hibag_hip_assoc *h = s->h;
 	const size_t ldp = ((size_t)pp + SCORE_BLOCK - 1) / SCORE_BLOCK * SCORE_BLOCK, n_seg = ((size_t)std::max(h->D.n, 1) + SCORE_SEG - 1) / SCORE_SEG;
-	if (s->panel.reserve(sizeof(double) * (size_t)pp * h->kp) || s->gram.reserve(sizeof(double) * (size_t)h->rows * pp) ||
+	if (s->panel.reserve(sizeof(double) * (size_t)pp * h->kp) || s->gram.reserve(sizeof(double) * (size_t)std::max(h->rows, s->x_rows) * pp) ||
 		s->part.reserve(sizeof(double) * n_seg * QUANT_MAX_BASIS * ldp))
 		return HIBAG_HIP_ENOMEM;
 	s->ldp = std::max(s->ldp, ldp);                          // (the row stride of what is reserved; it only grows)
@@ -1095,8 +1102,12 @@ int score_enqueue_panel(hibag_hip_score *s, uint64_t seed, uint64_t p0, int n_la
 	hipLaunchKernelGGL(k_score_project, dim3(n_blk, (kp + SCORE_SEG - 1) / SCORE_SEG), dim3(SCORE_THREADS), 0, h->st, seed, p0, n_lab, n, kp,
 		s->e.as<double>(), s->w.as<double>(), s->basis.as<double>(), s->nb, s->part.as<double>(), s->ldp, s->panel.as<double>());
 	if (ev) HIP_TRY(hipEventRecord(ev[1], h->st));
-	hipLaunchKernelGGL(k_quant_gram, dim3(tiles, (h->rows + QUANT_TILE - 1) / QUANT_TILE), dim3(QUANT_GRAM_WAVES * 64), 0, h->st,
-		h->feat.as<int8_t>(), h->rows, kp, s->panel.as<double>(), s->gram.as<double>(), ldc);
+	if (s->real)
+		hipLaunchKernelGGL(k_rscore_gram, dim3(tiles, (s->x_rows + QUANT_TILE - 1) / QUANT_TILE), dim3(QUANT_GRAM_WAVES * 64), 0, h->st,
+			s->X.as<double>(), s->x_rows, kp, s->panel.as<double>(), s->gram.as<double>(), ldc);
+	else
+		hipLaunchKernelGGL(k_quant_gram, dim3(tiles, (h->rows + QUANT_TILE - 1) / QUANT_TILE), dim3(QUANT_GRAM_WAVES * 64), 0, h->st,
+			h->feat.as<int8_t>(), h->rows, kp, s->panel.as<double>(), s->gram.as<double>(), ldc);
 	if (ev) HIP_TRY(hipEventRecord(ev[2], h->st));
 	hipLaunchKernelGGL(k_score_stat, dim3((n_lab + 63) / 64), dim3(64), 0, h->st, s->gram.as<double>(), ldc, n_lab, s->sets.as<ScoreSet>(),
 		s->n_sets, s->rows.as<int32_t>(), s->factor.as<double>(), s->n_df, stat_out, max_out, stat_obs, count);
@@ -1202,29 +1213,60 @@ int hibag_hip_assoc_score_base(hibag_hip_score *s, double *coef, double *se, dou
 	return 0;
 }
 
-int hibag_hip_assoc_score_sets(hibag_hip_score *s, const int32_t *set_start, const int32_t *set_rows, int n_sets, double *proj, double *S,
-	int32_t *kept)
+// hibag_hip_assoc_score_sets (X null: the sets name the handle's int8 rows) and hibag_hip_assoc_rscore_sets (X float64
+// [m][n_kept]: the sets name its rows)
+static int score_install(hibag_hip_score *s, const char *me, const double *X, int m_real, const int32_t *set_start, const int32_t *set_rows,
+	int n_sets, double *proj, double *S, int32_t *kept)
 {
-	if (!s || !proj || (n_sets > 0 && (!S || !kept))) return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_score_sets: null argument");
+	if (!s || !proj || (n_sets > 0 && (!S || !kept))) return hibag_fail(HIBAG_HIP_EINVAL, "%s: null argument", me);
 	if (n_sets < 0 || n_sets > kMaxTests || !set_start || set_start[0] != 0)
-		return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_score_sets: need 0 <= n_sets <= %d and set_start with set_start[0] = 0", kMaxTests);
+		return hibag_fail(HIBAG_HIP_EINVAL, "%s: need 0 <= n_sets <= %d and set_start with set_start[0] = 0", me, kMaxTests);
 	hibag_hip_assoc *h = s->h;
-	std::vector<int> seen((size_t)h->rows, -1);
+	const bool real = X != nullptr;
+	const int n_rows = real ? m_real : h->rows;
+	std::vector<int> seen((size_t)n_rows, -1);
 	for (int t = 0; t < n_sets; t++) {
 		const int m = set_start[t + 1] - set_start[t];
-		if (m < 0) return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_score_sets: set_start is not monotone at set %d", t);
-		if (m > SCORE_MAX_ROWS) return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_score_sets: set %d has %d rows; at most %d", t, m, SCORE_MAX_ROWS);
-		if (m > 0 && !set_rows) return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_score_sets: set_rows is null");
+		if (m < 0) return hibag_fail(HIBAG_HIP_EINVAL, "%s: set_start is not monotone at set %d", me, t);
+		if (m > SCORE_MAX_ROWS) return hibag_fail(HIBAG_HIP_EINVAL, "%s: set %d has %d rows; at most %d", me, t, m, SCORE_MAX_ROWS);
+		if (m > 0 && !set_rows) return hibag_fail(HIBAG_HIP_EINVAL, "%s: set_rows is null", me);
 		for (int j = 0; j < m; j++) {
 			const int r = set_rows[set_start[t] + j];
-			if (r < 0 || r >= h->rows)
-				return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_score_sets: set %d names row %d, outside the handle's %d", t, r, h->rows);
-			if (seen[(size_t)r] == t) return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_score_sets: set %d names row %d twice", t, r);
+			if (r < 0 || r >= n_rows)
+				return hibag_fail(HIBAG_HIP_EINVAL, "%s: set %d names row %d, outside the handle's %d", me, t, r, n_rows);
+			if (seen[(size_t)r] == t) return hibag_fail(HIBAG_HIP_EINVAL, "%s: set %d names row %d twice", me, t, r);
 			seen[(size_t)r] = t;
 		}
 	}
 	const int nb = s->nb, kp = h->kp, total = set_start[n_sets], ns = std::max(n_sets, 1);
 	HIP_TRY(hipSetDevice(h->device));
+	if (real) {
+		// the rows, zero-padded to [m][kp], and their projections on the basis
+		const int n = h->D.n;
+		std::vector<double> img((size_t)m_real * kp, 0.0);
+		for (int r = 0; r < m_real; r++)
+			for (int i = 0; i < n; i++) {
+				const double v = X[(size_t)r * n + i];
+				if (!std::isfinite(v)) return hibag_fail(HIBAG_HIP_EINVAL, "%s: row %d has the value %g at sample %d; finite values", me, r, v, i);
+				img[(size_t)r * kp + i] = v;
+			}
+		TempBuf d_proj;
+		if (s->X.reserve(sizeof(double) * img.size()) || d_proj.reserve(sizeof(double) * (size_t)m_real * nb)) return HIBAG_HIP_ENOMEM;
+		s->h_xproj.resize((size_t)m_real * nb);
+		if (int rc = enqueued(h->st, [&]() -> int {
+				HIP_TRY(hipMemcpyAsync(s->X.p, img.data(), sizeof(double) * img.size(), hipMemcpyHostToDevice, h->st));
+				hipLaunchKernelGGL(k_rscore_proj, dim3(m_real), dim3(256), 0, h->st, s->X.as<double>(), kp, n, s->w.as<double>(), s->basis.as<double>(),
+					nb, d_proj.as<double>());
+				HIP_TRY(hipGetLastError());
+				HIP_TRY(hipMemcpyAsync(s->h_xproj.data(), d_proj.p, sizeof(double) * (size_t)m_real * nb, hipMemcpyDeviceToHost, h->st));
+				HIP_TRY(hipStreamSynchronize(h->st));
+				return 0;
+			})) { s->n_sets = -1; return rc; }
+		s->x_rows = m_real;
+	}
+	s->real = real;
+	s->n_sets = -1;                                            // (until the new sets stand)
+	const std::vector<double> &h_proj = real ? s->h_xproj : s->h_proj;
 	TempBuf d_start, d_rows, d_S;
 	std::vector<double> S32((size_t)ns * SCORE_SET_LD * SCORE_SET_LD);
 	if (d_start.reserve(sizeof(int32_t) * (size_t)(n_sets + 1)) || d_rows.reserve(sizeof(int32_t) * (size_t)std::max(total, 1)) ||
@@ -1234,8 +1276,12 @@ int hibag_hip_assoc_score_sets(hibag_hip_score *s, const int32_t *set_start, con
 		if (int rc = enqueued(h->st, [&]() -> int {
 				HIP_TRY(hipMemcpyAsync(d_start.p, set_start, sizeof(int32_t) * (size_t)(n_sets + 1), hipMemcpyHostToDevice, h->st));
 				if (total) HIP_TRY(hipMemcpyAsync(d_rows.p, set_rows, sizeof(int32_t) * (size_t)total, hipMemcpyHostToDevice, h->st));
-				hipLaunchKernelGGL(k_score_setgram, dim3(n_sets), dim3(SCORE_GRAM_WAVES * 64), 0, h->st, h->feat.as<int8_t>(), kp, s->w.as<double>(),
-					d_start.as<int32_t>(), d_rows.as<int32_t>(), d_S.as<double>());
+				if (real)
+					hipLaunchKernelGGL(k_rscore_setgram, dim3(n_sets), dim3(SCORE_GRAM_WAVES * 64), 0, h->st, s->X.as<double>(), kp, s->w.as<double>(),
+						d_start.as<int32_t>(), d_rows.as<int32_t>(), d_S.as<double>());
+				else
+					hipLaunchKernelGGL(k_score_setgram, dim3(n_sets), dim3(SCORE_GRAM_WAVES * 64), 0, h->st, h->feat.as<int8_t>(), kp, s->w.as<double>(),
+						d_start.as<int32_t>(), d_rows.as<int32_t>(), d_S.as<double>());
 				HIP_TRY(hipGetLastError());
 				HIP_TRY(hipMemcpyAsync(S32.data(), d_S.p, sizeof(double) * (size_t)n_sets * SCORE_SET_LD * SCORE_SET_LD, hipMemcpyDeviceToHost, h->st));
 				HIP_TRY(hipStreamSynchronize(h->st));
@@ -1260,7 +1306,7 @@ int hibag_hip_assoc_score_sets(hibag_hip_score *s, const int32_t *set_start, con
 			for (int b = 0; b <= a; b++) {
 				const double sab = St[a * SCORE_SET_LD + b];
 				double pp = 0.0;
-				for (int k = 0; k < nb; k++) pp += s->h_proj[(size_t)rw[a] * nb + k] * s->h_proj[(size_t)rw[b] * nb + k];
+				for (int k = 0; k < nb; k++) pp += h_proj[(size_t)rw[a] * nb + k] * h_proj[(size_t)rw[b] * nb + k];
 				V[a][b] = V[b][a] = sab - pp;
 				S[s_at + (size_t)a * m + b] = S[s_at + (size_t)b * m + a] = sab;
 			}
@@ -1268,7 +1314,8 @@ int hibag_hip_assoc_score_sets(hibag_hip_score *s, const int32_t *set_start, con
 		int keep[SCORE_MAX_ROWS], d = 0, dropped = 0;             // the kept columns' positions in the set, in order
 		int32_t mask = 0;
 		for (int j = 0; j < m; j++) {
-			if (rsum[(size_t)rw[j]] == 0) { dropped++; continue; }       // nobody carries it: decided from the integer row sum
+			// nobody carries it: decided from the integer row sum, for real rows from S_jj == 0
+			if (real ? St[j * SCORE_SET_LD + j] == 0.0 : rsum[(size_t)rw[j]] == 0) { dropped++; continue; }
 			double piv = V[j][j];
 			for (int c = 0; c < d; c++) piv -= L[j][c] * L[j][c];
 			if (!(piv > 1e-11 * St[j * SCORE_SET_LD + j])) { dropped++; continue; }
@@ -1300,10 +1347,10 @@ int hibag_hip_assoc_score_sets(hibag_hip_score *s, const int32_t *set_start, con
 	for (int d = 1; d <= SCORE_MAX_ROWS; d++)
 		if (slot_of[d] == 0) slot_of[d] = s->n_df++;
 	for (int t = 0; t < n_sets; t++) sets[(size_t)t].slot = std::max(slot_of[sets[(size_t)t].d], 0);
-	std::copy(s->h_proj.begin(), s->h_proj.end(), proj);
+	std::copy(h_proj.begin(), h_proj.end(), proj);
 
 	s->n_sets = n_sets;
-	s->h_g.assign((size_t)h->rows, 0.0);
+	s->h_g.assign((size_t)n_rows, 0.0);
 	s->h_stat.assign((size_t)n_sets, std::nan(""));
 	if (s->sets.reserve(sizeof(ScoreSet) * (size_t)ns) || s->rows.reserve(sizeof(int32_t) * std::max<size_t>(krows.size(), 1)) ||
 		s->factor.reserve(sizeof(double) * std::max<size_t>(factor.size(), 1)) || score_reserve_panel(s, QUANT_TILE))
@@ -1314,12 +1361,27 @@ int hibag_hip_assoc_score_sets(hibag_hip_score *s, const int32_t *set_start, con
 		if (!factor.empty()) HIP_TRY(hipMemcpyAsync(s->factor.p, factor.data(), sizeof(double) * factor.size(), hipMemcpyHostToDevice, h->st));
 		// the observed residuals: replicate 0, a panel of its own
 		if (int e = score_enqueue_panel(s, 0, 0, 1, QUANT_TILE, s->stat_obs.as<double>(), nullptr, nullptr, nullptr, nullptr)) return e;
-		HIP_TRY(hipMemcpy2DAsync(s->h_g.data(), sizeof(double), s->gram.p, sizeof(double) * QUANT_TILE, sizeof(double), (size_t)h->rows,
+		HIP_TRY(hipMemcpy2DAsync(s->h_g.data(), sizeof(double), s->gram.p, sizeof(double) * QUANT_TILE, sizeof(double), (size_t)n_rows,
 			hipMemcpyDeviceToHost, h->st));
 		if (n_sets) HIP_TRY(hipMemcpyAsync(s->h_stat.data(), s->stat_obs.p, sizeof(double) * (size_t)n_sets, hipMemcpyDeviceToHost, h->st));
 		HIP_TRY(hipStreamSynchronize(h->st));
 		return 0;
 	});
+}
+
+int hibag_hip_assoc_score_sets(hibag_hip_score *s, const int32_t *set_start, const int32_t *set_rows, int n_sets, double *proj, double *S,
+	int32_t *kept)
+{
+	return score_install(s, "hibag_hip_assoc_score_sets", nullptr, 0, set_start, set_rows, n_sets, proj, S, kept);
+}
+
+int hibag_hip_assoc_rscore_sets(hibag_hip_score *s, const double *rows, int m, const int32_t *set_start, const int32_t *set_rows,
+	int n_sets, double *proj, double *S, int32_t *kept)
+{
+	const char *me = "hibag_hip_assoc_rscore_sets";
+	if (!s || !rows) return hibag_fail(HIBAG_HIP_EINVAL, "%s: null argument", me);
+	if (m < 1 || m > kMaxTests) return hibag_fail(HIBAG_HIP_EINVAL, "%s: m = %d; 1 .. %d rows", me, m, kMaxTests);
+	return score_install(s, me, rows, m, set_start, set_rows, n_sets, proj, S, kept);
 }
 
 int hibag_hip_assoc_score_observed(hibag_hip_score *s, double *g, double *stat, int32_t *df, int32_t *flags)

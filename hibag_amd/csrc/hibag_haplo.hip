@@ -6,7 +6,8 @@
 // with the entry number as payload, run heads, a scan), and the work lists -- samples by state count, haplotypes by list
 // length -- that decide the lane group an S64 sum gets.  hibag_hip_haplo_fit enqueues the iterations in batches; the kernels
 // of a batch test the device's `done` flag, so the frequencies are those of the first iteration with delta <= tol whatever
-// the batch size.  A handle has one stream and is used by one host thread at a time.
+// the batch size.  hibag_hip_haplo_dosage sums the last E step's posteriors per (haplotype, sample) (k_haplo_dosage).  A handle
+// has one stream and is used by one host thread at a time.
 
 #include <cstring>   // (rocprim's headers use memcpy without including it)
 #include <rocprim/rocprim.hpp>
@@ -36,12 +37,13 @@ struct hibag_hip_haplo {
 	DevBuf start, wc, keys, hidx, hstart, entries, q, tot, f0, f1, ctl;
 	DevBuf s16, s64, h8, h16, h64;               // the work lists, int32
 	DevBuf callA, callB, callP;                  // hibag_hip_haplo_calls
+	DevBuf dosHap, dosOut;                       // hibag_hip_haplo_dosage: int32 [rows], double [rows][n_used] of one chunk
 
 	~hibag_hip_haplo()
 	{
 		(void)hipSetDevice(device);
 		if (st) (void)hipStreamSynchronize(st);
-		for (DevBuf *b : {&start, &wc, &keys, &hidx, &hstart, &entries, &q, &tot, &f0, &f1, &ctl, &s16, &s64, &h8, &h16, &h64, &callA, &callB, &callP})
+		for (DevBuf *b : {&start, &wc, &keys, &hidx, &hstart, &entries, &q, &tot, &f0, &f1, &ctl, &s16, &s64, &h8, &h16, &h64, &callA, &callB, &callP, &dosHap, &dosOut})
 			b->release();
 		if (st) (void)hipStreamDestroy(st);
 	}
@@ -55,6 +57,7 @@ constexpr int kMaxK = 64;                        // candidates per sample and lo
 constexpr int kMaxAllele = 1 << HAPLO_KEY_BITS;
 constexpr long long kMaxEntries = 2147483647LL;
 constexpr int kBatch = 8;                        // iterations enqueued between two looks at the device's flag
+constexpr size_t kDosageChunk = (size_t)1 << 22; // cells of hibag_hip_haplo_dosage's device buffer (32 MB)
 
 // the drain rule of hibag_assoc.hip: what `body` enqueued is waited for before a frame it reads or writes goes away
 template <class Body> int enqueued(hipStream_t st, Body body)
@@ -368,6 +371,41 @@ int hibag_hip_haplo_calls(hibag_hip_haplo *h, int32_t *hapA, int32_t *hapB, doub
 		std::copy(&b[(size_t)u * L], &b[(size_t)u * L] + L, hapB + (size_t)s * L);
 		prob[s] = p[u];
 		total[s] = h->h_tot[u];
+	}
+	return 0;
+}
+
+int hibag_hip_haplo_dosage(hibag_hip_haplo *h, const int32_t *hap, int m, double *out)
+{
+	if (!h || !hap || !out) return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_haplo_dosage: null argument");
+	if (!h->fitted) return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_haplo_dosage: call hibag_hip_haplo_fit first");
+	if (m < 1) return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_haplo_dosage: m = %d; at least 1", m);
+	for (int j = 0; j < m; j++)
+		if (hap[j] < 0 || hap[j] >= h->H)
+			return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_haplo_dosage: hap[%d] = %d; haplotype indices are 0 .. %d", j, hap[j], h->H - 1);
+	HIP_TRY(hipSetDevice(h->device));
+	const int nu = h->n_used;
+	const int chunk = (int)std::min<size_t>((size_t)m, std::max<size_t>(kDosageChunk / (size_t)nu, 1));   // rows per launch
+	if (h->dosHap.reserve(sizeof(int32_t) * (size_t)chunk) || h->dosOut.reserve(sizeof(double) * (size_t)chunk * nu)) return HIBAG_HIP_ENOMEM;
+	std::vector<double> d((size_t)chunk * nu);
+	for (int j0 = 0; j0 < m; j0 += chunk) {
+		const int rows = std::min(chunk, m - j0);
+		if (int rc = enqueued(h->st, [&]() -> int {
+			HIP_TRY(hipMemcpyAsync(h->dosHap.p, hap + j0, sizeof(int32_t) * (size_t)rows, hipMemcpyHostToDevice, h->st));
+			HIP_TRY(hipMemsetAsync(h->dosOut.p, 0, sizeof(double) * (size_t)rows * nu, h->st));
+			hipLaunchKernelGGL(k_haplo_dosage, dim3(rows), dim3(256), 0, h->st, nu, h->dosHap.as<int32_t>(), h->start.as<long long>(),
+				h->hstart.as<uint32_t>(), h->entries.as<uint32_t>(), h->q.as<double>(), h->dosOut.as<double>());
+			HIP_TRY(hipGetLastError());
+			HIP_TRY(hipMemcpyAsync(d.data(), h->dosOut.p, sizeof(double) * (size_t)rows * nu, hipMemcpyDeviceToHost, h->st));
+			HIP_TRY(hipStreamSynchronize(h->st));
+			return 0;
+		})) return rc;
+		// the samples left out: NaN
+		for (int j = 0; j < rows; j++) {
+			double *o = out + (size_t)(j0 + j) * h->n_samp;
+			std::fill(o, o + h->n_samp, std::nan(""));
+			for (int u = 0; u < nu; u++) o[h->used[u]] = d[(size_t)j * nu + u];
+		}
 	}
 	return 0;
 }

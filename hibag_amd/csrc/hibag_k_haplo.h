@@ -251,4 +251,35 @@ __global__ void __launch_bounds__(256) k_haplo_call(int n_used, int L, const lon
 	if (j == 0) prob[u] = bq;
 }
 
+// k_haplo_dosage: the posterior dosages of the haplotypes hap[0 .. m): out [m][n_used], zeroed
+// by the host beforehand.  A haplotype's list is in ascending entry number and a sample's states are one range, so the list
+// falls into one segment per sample that has an entry.  One workgroup per selected haplotype; thread t looks at the positions
+// t, t + 256, ... of the list, finds the position's sample by bisection of `start`, and where the position before belongs
+// to another sample (a segment head) adds the segment's q in order from 0.0 -- an all-homozygous state has both its entries
+// here and adds its q twice -- and stores the sum.  Every cell has one writer.  Grid: m, 256 threads.
+__global__ void __launch_bounds__(256) k_haplo_dosage(int n_used, const int32_t *__restrict__ hap, const long long *__restrict__ start,
+	const uint32_t *__restrict__ hstart, const uint32_t *__restrict__ entries, const double *__restrict__ q, double *__restrict__ out)
+{
+	const int h = hap[blockIdx.x];
+	const uint32_t a = hstart[h], b = hstart[h + 1];
+	double *row = out + (size_t)blockIdx.x * n_used;
+	for (uint32_t i = a + threadIdx.x; i < b; i += 256) {
+		const long long s = entries[i] >> 1;
+		int lo = 0, hi = n_used;                     // start[lo] <= s < start[hi]
+		while (hi - lo > 1) {
+			const int mid = lo + ((hi - lo) >> 1);
+			if (start[mid] <= s) lo = mid; else hi = mid;
+		}
+		if (i > a && (long long)(entries[i - 1] >> 1) >= start[lo]) continue;   // not the head of its segment
+		const long long s_end = start[lo + 1];
+		double d = 0.0;
+		for (uint32_t k = i; k < b; k++) {
+			const long long t = entries[k] >> 1;
+			if (t >= s_end) break;
+			d = d + q[t];
+		}
+		row[lo] = d;
+	}
+}
+
 #endif

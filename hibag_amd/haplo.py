@@ -11,7 +11,7 @@ number is defined operation by operation in DESIGN.md section 29, and ``tests/ha
 
 Not built: division by the per-locus model prior; marginalising a sample's missing locus over all alleles (the sample is
 left out); more than 6 loci; progressive insertion or trimming of the dictionary; ``hlaPredictLoci(type="topk")`` as a
-source; association tests on haplotypes."""
+source.  (Association tests on haplotypes: ``hlaAssocHaplo``, from ``dosage`` or ``as_alleles`` of the result here.)"""
 
 from __future__ import annotations
 
@@ -191,6 +191,14 @@ class _DeviceHaplo:
         _lib.check(_lib.lib().hibag_hip_haplo_calls(self._h, _ptr(a), _ptr(b), _ptr(prob), _ptr(total)))
         return dict(hapA=a, hapB=b, prob=prob, total=total)
 
+    def dosage(self, hap: Sequence[int]) -> np.ndarray:
+        """float64 [m, n] under the last fit: every sample's expected copies of the haplotypes ``hap`` (indices into the fit's
+        ascending-key order), NaN for a sample left out."""
+        hap = np.ascontiguousarray(hap, np.int32)
+        out = np.empty((len(hap), self.n_samp), np.float64)
+        _lib.check(_lib.lib().hibag_hip_haplo_dosage(self._h, _ptr(hap), len(hap), _ptr(out)))
+        return out
+
 
 def decode_keys(keys: np.ndarray, n_loci: int) -> np.ndarray:
     """int32 [H, L]: the allele index of every locus of every key."""
@@ -206,7 +214,14 @@ class HlaHaplotypeResult:
     (the last iteration's largest frequency change), ``loglik`` (the sum of log ``total`` over the used samples with a
     total above 0; ``n_zero`` samples have total 0).  Per sample, in ``sample_id`` order: ``h1`` / ``h2`` int32 [n, L] (the two
     haplotypes of the most probable state, ``NA_INTEGER`` for a sample left out), ``prob`` (that state's posterior), ``used``,
-    ``total`` (the sample's likelihood), ``n_states``, ``n_trimmed`` (candidates the trimming dropped)."""
+    ``total`` (the sample's likelihood), ``n_states``, ``n_trimmed`` (candidates the trimming dropped).  With
+    ``dosage_min_freq``: ``dosage_index`` (the positions in ``haplotypes`` with ``freq >= dosage_min_freq``, in order) and
+    ``dosage`` float64 [m, n], every sample's expected number of copies of those haplotypes under its posterior over its
+    states (NaN for a sample left out); else both are ``None``."""
+
+    dosage_min_freq: Optional[float] = None
+    dosage_index: Optional[np.ndarray] = None
+    dosage: Optional[np.ndarray] = None
 
     def __init__(self, loci, levels, sample_id, haplotypes, freq, keys, n_iter, converged, delta, loglik, n_zero, h1, h2, prob, used,
                  total, n_states, n_trimmed, rank0):
@@ -244,6 +259,30 @@ class HlaHaplotypeResult:
         return HlaAlleleClass(locus=self.loci[l], sample_id=list(self.sample_id), h1=lo, h2=hi, levels=self.levels[l],
                               prob=self.prob.copy())
 
+    def as_alleles(self, min_freq: float = 0.0) -> HlaAlleleClass:
+        """The called haplotype pairs as an :class:`HlaAlleleClass` whose "alleles" are haplotypes: the levels are the names
+        of the haplotypes with ``freq >= min_freq``, in result order, and ``"rare"`` for every other one; NA for a sample left
+        out; ``prob`` is the called state's posterior.  With it the association entries run on best-guess haplotypes as they
+        are."""
+        if not (isinstance(min_freq, (int, float, np.floating)) and not isinstance(min_freq, bool) and 0 <= float(min_freq) <= 1):
+            raise ValueError("min_freq must be a number in [0, 1]")
+        sel = np.flatnonzero(self.freq >= float(min_freq))
+        levels = [self.names(int(i)) for i in sel] + ["rare"]
+        sel_keys = np.asarray(self.keys, np.uint64)[sel]
+        by_key = np.argsort(sel_keys, kind="stable")
+        shift = (KEY_BITS * np.arange(len(self.loci))).astype(np.uint64)
+        used = np.asarray(self.used, bool)
+
+        def index(h):
+            key = (np.where(used[:, None], h, 0).astype(np.uint64) << shift[None, :]).sum(axis=1, dtype=np.uint64)
+            pos = np.minimum(np.searchsorted(sel_keys[by_key], key), max(len(sel) - 1, 0))
+            hit = (sel_keys[by_key][pos] == key) if len(sel) else np.zeros(len(key), bool)
+            out = np.where(hit, by_key[pos] if len(sel) else 0, len(sel))
+            return np.where(used, out, NA_INTEGER).astype(np.int32)
+
+        return HlaAlleleClass(locus="~".join(self.loci), sample_id=list(self.sample_id), h1=index(self.h1), h2=index(self.h2), levels=levels,
+                              prob=self.prob.copy())
+
     @property
     def n_changed(self) -> np.ndarray:
         """Per locus: the used samples whose pair differs from their first candidate."""
@@ -259,7 +298,7 @@ class HlaHaplotypeResult:
 
 
 def hlaHaplotypes(calls: Union[Mapping, Sequence], max_states: int = 4096, min_prob: float = 0.01, maxit: int = 200,
-                  tol: float = 1e-8, verbose: bool = True) -> HlaHaplotypeResult:
+                  tol: float = 1e-8, verbose: bool = True, dosage_min_freq: Optional[float] = None) -> HlaHaplotypeResult:
     """Haplotype frequencies over the loci of ``calls`` and every sample's most probable haplotype pair.
 
     ``calls``: a mapping ``{locus: result}`` or a sequence of results, 2 .. 6 loci, each an :class:`HlaTopCalls` (k candidates
@@ -268,7 +307,11 @@ def hlaHaplotypes(calls: Union[Mapping, Sequence], max_states: int = 4096, min_p
     ``ValueError``.  A sample without a candidate at some locus is left out (``used`` False).  Candidates of rank >= 1 below
     ``min_prob`` are dropped, then the least probable ones until the sample has at most ``max_states`` states.  The EM starts
     from equal frequencies and stops after the first iteration whose largest frequency change is at most ``tol``, or after
-    ``maxit`` iterations."""
+    ``maxit`` iterations.  ``dosage_min_freq``: also return every sample's expected dosage of the haplotypes with at least
+    that frequency (``dosage_index``, ``dosage`` of the result) -- what ``hlaAssocHaplo`` tests."""
+    if dosage_min_freq is not None and not (isinstance(dosage_min_freq, (int, float, np.floating)) and not isinstance(dosage_min_freq, bool)
+                                            and 0 <= float(dosage_min_freq) <= 1):
+        raise ValueError("dosage_min_freq must be None or a number in [0, 1]")
     if not isinstance(max_states, (int, np.integer)) or isinstance(max_states, bool) or not (1 <= int(max_states) <= MAX_ENTRIES // 2):
         raise ValueError("max_states must be an integer between 1 and 2^30 - 1")
     if not isinstance(maxit, (int, np.integer)) or isinstance(maxit, bool) or int(maxit) < 1:
@@ -295,14 +338,21 @@ def hlaHaplotypes(calls: Union[Mapping, Sequence], max_states: int = 4096, min_p
         fit = dev.fit(int(maxit), float(tol))
         got = dev.calls()
         used, states = dev.used, dev.states
+        order = np.lexsort((fit["keys"], -fit["freq"]))                # frequency descending, then key ascending
+        dosage_index = dosage = None
+        if dosage_min_freq is not None:
+            dosage_index = np.flatnonzero(fit["freq"][order] >= float(dosage_min_freq))
+            dosage = dev.dosage(order[dosage_index]) if len(dosage_index) else np.zeros((0, len(ids)))
     converged = bool(fit["delta"] <= float(tol))
     tot = got["total"][used]
     loglik = float(sum(math.log(t) for t in tot if t > 0))
-    order = np.lexsort((fit["keys"], -fit["freq"]))                    # frequency descending, then key ascending
     if verbose:
         print(f"  {fit['n_iter']} iterations, delta = {fit['delta']:.3g}" + ("" if converged else " (not converged)") +
               f", log-likelihood {loglik:.6f}" + (f", {fit['n_zero']} samples with likelihood 0" if fit["n_zero"] else ""))
     n_trimmed = np.where(used, n_trimmed, 0).astype(np.int32)
-    return HlaHaplotypeResult(loci, levels, ids, decode_keys(fit["keys"][order], len(loci)), fit["freq"][order], fit["keys"][order],
-                              fit["n_iter"], converged, fit["delta"], loglik, fit["n_zero"], got["hapA"], got["hapB"], got["prob"],
-                              used, got["total"], states, n_trimmed, rank0)
+    res = HlaHaplotypeResult(loci, levels, ids, decode_keys(fit["keys"][order], len(loci)), fit["freq"][order], fit["keys"][order],
+                             fit["n_iter"], converged, fit["delta"], loglik, fit["n_zero"], got["hapA"], got["hapB"], got["prob"],
+                             used, got["total"], states, n_trimmed, rank0)
+    if dosage_min_freq is not None:
+        res.dosage_min_freq, res.dosage_index, res.dosage = float(dosage_min_freq), dosage_index, dosage
+    return res

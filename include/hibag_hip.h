@@ -498,6 +498,17 @@ int hibag_hip_assoc_score_base(hibag_hip_score *s, double *coef, double *se, dou
 int hibag_hip_assoc_score_sets(hibag_hip_score *s, const int32_t *set_start, const int32_t *set_rows, int n_sets, double *proj, double *S,
 	int32_t *kept);
 
+/* The same on REAL-VALUED feature rows (hlaAssocHaplo: expected haplotype dosages): `rows` is host
+ * float64 [m][n_kept] in the handle's kept-sample order, and set_rows names rows 0 .. m - 1 of it.  proj[row][k] =
+ * sum_i X[row][i] (w_i q_k[i]), S[a][b] = sum_i (w_i X[a][i]) X[b][i], g[row][p] = sum_i X[row][i] r_i: the definitions above
+ * with X in place of the int8 rows, every sum in the int8 kernels' order.  A row with S_jj == 0 is dropped (in place of
+ * "row sum 0"); the pivot rule, flags, df and kept masks are unchanged.  proj is float64 [m][1 + n_covar]; S and kept as
+ * above.  After this call hibag_hip_assoc_score_observed (g float64 [m]) and _resample run over these rows; after a later
+ * hibag_hip_assoc_score_sets call they run over the handle's int8 rows again.  EINVAL as hibag_hip_assoc_score_sets, and
+ * for m < 1, a null `rows`, a value that is NaN or infinite. */
+int hibag_hip_assoc_rscore_sets(hibag_hip_score *s, const double *rows, int m, const int32_t *set_start, const int32_t *set_rows,
+	int n_sets, double *proj, double *S, int32_t *kept);
+
 /* The observed run: g float64 [rows] (every feature row's score), stat float64 [n_sets] (NaN where not fitted), df int32
  * [n_sets] (the kept rows; 0 where not fitted), flags int32 [n_sets] (HIBAG_HIP_GLM_MAXIT: the base fit did not converge;
  * _RANK; _ALIASED).  hibag_hip_assoc_score_n_df: the number of distinct values > 0 in df. */
@@ -559,6 +570,14 @@ int hibag_hip_haplo_fit(hibag_hip_haplo *h, int maxit, double tol, double *freq,
  * sample's likelihood, the sum of its states' weights).  A sample left out has HIBAG_HIP_NA_INTEGER and NaN.  ESTATE before
  * a fit. */
 int hibag_hip_haplo_calls(hibag_hip_haplo *h, int32_t *hapA, int32_t *hapB, double *prob, double *total);
+
+/* After a fit, under its frequencies and the posteriors q of the same last E step as hibag_hip_haplo_calls: the expected
+ * number of copies of haplotype hap[j] (an index into the fit's ascending-key order, 0 .. H - 1) that sample i carries,
+ *   out  float64 [m][n_samp]: the sum of q over those entries of the haplotype's list that belong to sample i, from 0.0 in
+ *        ascending entry number with one rounding per addition (an all-homozygous state lists its haplotype twice and adds
+ *        its q twice); 0.0 where the list has no entry of the sample; NaN for a sample left out.
+ * EINVAL before a fit, for m < 1, an index outside 0 .. H - 1, a null pointer. */
+int hibag_hip_haplo_dosage(hibag_hip_haplo *h, const int32_t *hap, int m, double *out);
 
 /* ---- several models of one locus, merged: hlaPredMerge on the device ----------
  * hlaPredMerge(hlaPredict(m1, type = "response+prob"), hlaPredict(m2, ...), ...) (R/HIBAG.R:825-1023 around HIBAG_SumList,
