@@ -2,14 +2,20 @@
 references alone): the subnormal total gives a call with prob = inf, every 64-sample group of ``mixed-lanes`` holds lanes
 without a call, with a finite call and with prob = inf side by side -- in the ensemble for every curve size from 4 to 12, and
 per classifier for every classifier whose frequencies are scaled down --, a mask heals some poisoned lanes and leaves
-others, and a merge meets posterior columns that are NaN in some rows only.  These are conditions on the inputs: where a
-recipe misses one, the recipe changes (seed, rate, factor), never the condition."""
+others, and a merge meets posterior columns that are NaN in some rows only; for the entries with a finish of their own
+(top-k, draws, groups, given, family): rows with inf cells, with inf and NaN cells, all-NaN and healthy rows share a
+64-sample group, inf rows tie across top-k's segments, draws meet S = inf and S = NaN, allele sets move a call off an inf cell
+or leave it NaN cells only, and a pedigree pairs every kind of parent over two generations.  These are conditions on the
+inputs: where a recipe misses one, the recipe changes (seed, rate, factor), never the condition."""
 
 import numpy as np
 import pytest
 
+import draws_reference as DR
 import edge_corpus as EC
+import family_reference as FR
 import ref_cases as RC
+import topk_reference as TR
 from hibag_amd import NA_INTEGER
 
 GROUPS = [slice(0, 64), slice(64, 128), slice(128, 192)]
@@ -145,3 +151,195 @@ def test_every_reference_runs_on_every_case(name):
     for vote in (1, 2):
         assert EC.masked_want(name, vote)["postprob"].shape == (n, model.n_cell)
     assert EC.merge_want(name, True)["postprob"].shape[1] == n
+
+
+# ---- top-k, draws, groups, given, family: the entries whose finish is a kernel of its own -----------------------------------
+VOTES = (1, 2)
+
+
+def _inf_rows(name, vote=1):
+    return np.isposinf(EC.posterior(name, vote)[0]).any(axis=1)
+
+
+def test_inf_nan_and_healthy_rows_share_a_group_and_the_subnormal_inf_rows_tie():
+    pp, _ = EC.posterior("mixed-lanes", 1)
+    kind = EC.row_kinds("mixed-lanes")
+    both = np.isposinf(pp).any(axis=1) & np.isnan(pp).any(axis=1)
+    assert np.array_equal(both, kind == EC.INF) and np.isnan(pp[kind == EC.NAN]).all()       # inf comes with NaN; NaN rows are all NaN
+    full = [g for g in GROUPS if both[g].any() and (kind[g] == EC.NAN).any() and (kind[g] == EC.HEALTHY).any()]
+    assert full, [np.bincount(kind[g], minlength=4).tolist() for g in GROUPS]
+    assert both.sum() >= 5 and _inf_rows("mixed-lanes-each").any()
+    for vote in VOTES[1:]:                                    # the majority vote passes over a classifier without a call
+        for name in EC.CASES:
+            assert np.isfinite(EC.posterior(name, vote)[0]).all(), (name, vote)
+    # subnormal-lanes: inf in every cell, so every rank of the list is decided by cell order alone
+    pp, _ = EC.posterior("subnormal-lanes", 1)
+    rows = _inf_rows("subnormal-lanes")
+    assert rows.sum() >= 10 and np.isposinf(pp[rows]).all() and rows[:64].any() and rows[64:].any()
+    want = EC.topk_want("subnormal-lanes", 1, 16)
+    h1, h2 = TR.pair_of_cell(np.arange(pp.shape[1]), EC.n_hla("subnormal-lanes"))
+    assert (want["h1"][rows, :len(h1)] == h1).all() and (want["h2"][rows, :len(h1)] == h2).all()
+    assert np.isposinf(want["prob"][rows, :len(h1)]).all() and (want["h1"][rows, len(h1):] == NA_INTEGER).all()
+
+
+def test_topk_rank_0_on_inf_rows_is_the_oracles_call():
+    seen = 0
+    for name in EC.CASES:
+        rows = _inf_rows(name)
+        call = EC.plain_want(name, 1)
+        for k in EC.TOPK_K:
+            want = EC.topk_want(name, 1, k)
+            assert np.array_equal(want["h1"][rows, 0], call["h1"][rows]) and np.array_equal(want["h2"][rows, 0], call["h2"][rows]), (name, k)
+            assert np.isposinf(want["prob"][rows, 0]).all() and np.isposinf(call["prob"][rows]).all(), (name, k)
+        seen += int(rows.sum())
+    assert seen >= 20
+
+
+def test_select_and_select_fast_agree_on_every_corpus_posterior():
+    for name in EC.CASES:
+        for vote in VOTES:
+            pp, _ = EC.posterior(name, vote)
+            for k in (1, 4, 16):
+                TR.assert_topk_equal(TR.select_fast(pp, k, EC.n_hla(name)), EC.topk_want(name, vote, k) if k in EC.TOPK_K
+                                     else TR.select(pp, k, EC.n_hla(name)), f"{name}, vote {vote}, k {k}", keys=TR.KEYS)
+
+
+def test_draws_are_na_where_s_is_not_positive_and_nan_where_s_is_nan():
+    pinned = 0
+    for name in EC.CASES:
+        for vote in VOTES:
+            S = EC.draw_S(name, vote)
+            with np.errstate(invalid="ignore"):
+                none = ~(S > 0)
+            for sample0 in EC.DRAW_SAMPLE0:
+                want = EC.draws_all(name, vote, sample0)
+                assert np.array_equal(want["h1"] == NA_INTEGER, np.broadcast_to(none[:, None], want["h1"].shape)), (name, vote)
+                assert np.array_equal(want["h2"] == NA_INTEGER, want["h1"] == NA_INTEGER)
+                assert np.array_equal(np.isnan(want["prob"]), np.broadcast_to(np.isnan(S)[:, None], want["prob"].shape)), (name, vote)
+                assert (want["prob"][none & ~np.isnan(S)] == 0).all() and (want["prob"][~none] > 0).all()
+        # the contract as written: a row with inf and NaN cells has S = NaN and no draw, although the oracle calls it
+        pp, _ = EC.posterior(name, 1)
+        mixed = np.isposinf(pp).any(axis=1) & np.isnan(pp).any(axis=1)
+        assert np.isnan(EC.draw_S(name, 1)[mixed]).all() and (EC.plain_want(name, 1)["h1"][mixed] != NA_INTEGER).all()
+        pinned += int(mixed.sum())
+        # an all-inf row: S = inf, no threshold is passed, every draw is the last cell
+        allinf = np.isposinf(pp).all(axis=1)
+        assert (EC.draws_all(name, 1, 0)["h1"][allinf] == EC.n_hla(name) - 1).all()
+    assert pinned >= 5
+    # the first n of 64 draws are the call with n draws, and the two numberings draw differently
+    for name in ("subnormal-lanes", "mixed-lanes"):
+        pp, _ = EC.posterior(name, 1)
+        for sample0 in EC.DRAW_SAMPLE0:
+            direct = DR.draws_from_postprob(pp, 17, EC.DRAW_SEED, sample0, EC.n_hla(name))
+            DR.assert_draws_equal(EC.draws_want(name, 1, 17, sample0), direct, f"{name}, sample0 {sample0}", keys=DR.KEYS)
+    a, b = (EC.draws_all("subnormal-lanes", 1, s0)["h1"] for s0 in EC.DRAW_SAMPLE0)
+    assert not np.array_equal(a, b) and EC.DRAW_SAMPLE0[1] >> 32 and (EC.DRAW_SAMPLE0[1] + 64) >> 32 != EC.DRAW_SAMPLE0[1] >> 32
+
+
+def test_groups_partitions_are_what_they_are_called():
+    for name in EC.CASES:
+        parts = EC.partitions(name)
+        n = EC.n_hla(name)
+        assert np.array_equal(parts[EC.IDENTITY], np.arange(n)) and (parts[EC.SINGLE] == 0).all()
+        assert set(parts[EC.WITH_EMPTY]) == {0, 2} and np.bincount(parts[EC.COARSE]).max() == min(3, n)
+        for vote in VOTES:
+            want, call = EC.groups_want(name, vote), EC.plain_want(name, vote)
+            for key, mine in (("h1", want["g1"][:, 0]), ("h2", want["g2"][:, 0]), ("prob", want["prob"][:, 0]),
+                              ("dosage", want["dosage"][:, :n])):
+                assert np.array_equal(mine, call[key], equal_nan=True), (name, vote, key)
+    # inf + NaN loses, inf + inf wins: the single group's one bin
+    want = EC.groups_want("mixed-lanes", 1)
+    assert (want["g1"][EC.row_kinds("mixed-lanes") == EC.INF, EC.SINGLE] == NA_INTEGER).all()
+    want = EC.groups_want("subnormal-lanes", 1)
+    rows = _inf_rows("subnormal-lanes")
+    assert (want["g1"][rows, EC.SINGLE] == 0).all() and np.isposinf(want["prob"][rows, EC.SINGLE]).all()
+
+
+def test_given_sets_move_the_call_and_starve_it():
+    moved = starved = 0
+    for name in EC.CASES:
+        pp, _ = EC.posterior(name, 1)
+        call = EC.plain_want(name, 1)
+        full = EC.given_want(name, 1, "full")
+        for key in ("h1", "h2", "prob", "dosage"):
+            assert np.array_equal(full[key], call[key], equal_nan=True), (name, key)
+        assert np.array_equal(full["support"], EC.draw_S(name, 1), equal_nan=True), name
+        want = EC.given_want(name, 1, "moved")
+        for s in np.nonzero(_inf_rows(name))[0]:
+            # the consistent cells: all but (c1, c1), (c1, c2), (c2, c2)
+            c1, c2 = int(call["h1"][s]), int(call["h2"][s])
+            h1, h2 = FR.cell_pairs(EC.n_hla(name))
+            left = np.isposinf(pp[s]) & ~(np.isin(h1, (c1, c2)) & np.isin(h2, (c1, c2)))
+            if left.any():                                    # the next consistent inf cell
+                c = int(left.argmax())
+                assert (want["h1"][s], want["h2"][s]) == (h1[c], h2[c]) != (c1, c2) and np.isposinf(want["prob"][s]), (name, s)
+                moved += 1
+            else:
+                assert want["h1"][s] == NA_INTEGER and want["prob"][s] == 0 and np.isnan(want["support"][s]), (name, s)
+        want = EC.given_want(name, 1, "nan-only")
+        rows = np.isposinf(pp).any(axis=1) & np.isnan(pp).any(axis=1)
+        assert (want["h1"][rows] == NA_INTEGER).all() and (want["prob"][rows] == 0).all() and np.isnan(want["support"][rows]).all(), name
+        assert (EC.given_sets(name, "nan-only")[rows].sum(axis=2) == 1).all()
+        starved += int(rows.sum())
+        want = EC.given_want(name, 1, "empty")
+        assert (want["h1"] == NA_INTEGER).all() and (want["support"] == 0).all() and (want["dosage"] == 0).all(), name
+    assert moved >= 20 and starved >= 5, (moved, starved)
+    assert any(_inf_rows(n)[s] and np.isnan(EC.posterior(n, 1)[0][s]).any() and EC.given_want(n, 1, "moved")["h1"][s] != NA_INTEGER
+               for n in EC.LANE_CASES[1:] for s in range(200)), "no row with inf and NaN cells has a second inf cell"
+
+
+def test_family_pedigree_has_the_parent_kinds_and_depths():
+    for name in EC.CASES:
+        rows, ped = EC.family_case(name)
+        depth = FR.depths(ped)                                # (asserts that parents precede their children)
+        assert set(rows) == set(range(len(EC.case(name)[1]))) and (ped[:, 0] != ped[:, 1])[ped[:, 0] >= 0].all(), name
+        if name not in EC.LANE_CASES:
+            assert np.array_equal(depth, (np.arange(len(rows)) % 3 == 2).astype(int)) and np.array_equal(rows, np.arange(len(rows)))
+            continue
+        kind = EC.row_kinds(name)[rows]
+        have = sorted(set(kind))
+        pk = np.where(ped >= 0, kind[np.maximum(ped, 0)], EC.OUT)                    # the parents' kinds
+        first = (depth <= 1) & (depth[np.maximum(ped, 0)] == 0).all(axis=1)           # children of founders
+        for ka in [EC.OUT] + have:
+            for kb in [EC.OUT] + have:
+                for kc in set(have) & {EC.HEALTHY, EC.INF}:
+                    assert (first & (pk[:, 0] == ka) & (pk[:, 1] == kb) & (kind == kc)).any(), (name, ka, kb, kc)
+        has = ped >= 0
+        same = has & (ped // 64 == np.arange(len(ped))[:, None] // 64)
+        assert same.any() and (has & ~same).any(), name
+        assert np.count_nonzero(has.any(axis=1) & (np.arange(len(ped)) % 64 < 8)) >= 1
+        for with_prior in (True, False):
+            S = EC.family_want(name, 1, with_prior)["support"]
+            through = np.zeros((3, len(ped)), bool)           # a grandchild through an inf-row parent, a NaN-support one, an inf-support one
+            for k in (0, 1):
+                p = np.maximum(ped[:, k], 0)
+                mid = (ped[:, k] >= 0) & (depth[p] == 1) & (depth == 2)
+                through |= np.stack([mid & (kind[p] == EC.INF), mid & np.isnan(S[p]), mid & np.isposinf(S[p])])
+            assert through[0].any() and through[1].any(), (name, with_prior)
+            if name == "subnormal-lanes":
+                assert through[2].any(), with_prior
+        # an inf parent (D = inf, S = inf) leaves its child uncalled with NaN support; a NaN-support parent is unknown
+        want, none = EC.family_want(name, 1, True), EC.family_want(name, 1, False)
+        own = EC.posterior(name, 1)[0][rows]
+        for i in np.nonzero(first & (depth == 1))[0]:
+            Sp = [want["support"][p] if p >= 0 else 0.0 for p in ped[i]]
+            if any(np.isposinf(x) for x in Sp):
+                assert want["h1"][i] == NA_INTEGER and np.isnan(want["support"][i]) and np.isnan(want["dosage"][i]).all(), (name, i)
+            elif not any(x > 0 for x in Sp):                  # both unknown: the sample's own row
+                assert np.array_equal(want["support"][i], np.cumsum(own[i])[-1], equal_nan=True), (name, i)
+                assert want["h1"][i] == none["h1"][i]
+
+
+@pytest.mark.parametrize("name", EC.CASES)
+def test_every_finish_reference_runs_on_every_case(name):
+    n, nh = len(EC.case(name)[1]), EC.n_hla(name)
+    for vote in VOTES:
+        for k in EC.TOPK_K:
+            assert EC.topk_want(name, vote, k)["prob"].shape == (n, k)
+        for d in EC.DRAW_N:
+            assert EC.draws_want(name, vote, d, EC.DRAW_SAMPLE0[1])["h1"].shape == (n, d)
+        assert EC.groups_want(name, vote)["prob"].shape == (n, 5) and EC.groups_want(name, vote)["dosage"].shape == (n, EC.groups_offsets(name)[-1])
+        for which in EC.GIVEN_SETS:
+            assert EC.given_want(name, vote, which)["dosage"].shape == (n, nh)
+        for with_prior in (True, False):
+            assert EC.family_want(name, vote, with_prior)["dosage"].shape == (len(EC.family_case(name)[0]), nh)

@@ -1,7 +1,10 @@
 """The underflow and edge-case corpus (``ref_cases.PREDICT_CASES``: totals of 0 and below 1 / DBL_MAX, classifiers without
 haplotypes, zero frequencies, mirrored ties, genotype values outside 0..2, and 64-sample groups that mix healthy, inf, NaN
 and inactive lanes) through every entry that restates the accumulate / pick arithmetic in kernels of its own: the curve
-(k_prefix_accum), out of bag (k_oob_pick, k_oob_scan, k_oob_best_valu), the knock-out, the masked driver and the merge.
+(k_prefix_accum), out of bag (k_oob_pick, k_oob_scan, k_oob_best_valu), the knock-out, the masked driver and the merge; and
+through every entry that replaces the finish with kernels of its own: top-k (k_finish_topk), draws (k_finish_draw), groups
+(k_finish_groups, with and without LDS), given (k_finish_given, k_given_dosage) and family (k_family_ratios,
+k_finish_family, k_family_dosage).
 Every case, every sample, no tolerance: integers equal, floats the same 64 bits or NaN in both, against the references
 tests/edge_corpus.py builds from the oracle alone (tests/test_edge_corpus_host.py holds the inputs to what they are for)."""
 
@@ -12,6 +15,8 @@ import pytest
 
 import curve_reference as CR
 import edge_corpus as EC
+import family_reference as FR
+import given_reference as GR
 import hibag_amd as hb
 import importance_reference as IR
 import masked_reference as MR
@@ -225,3 +230,212 @@ def test_merge_device(name, use_matching, monkeypatch):
             _merge_equal(got, want, f"{name}, use_matching {use_matching}, chunk {chunk}")
     finally:
         L.hibag_hip_merge_plan_free(C.c_void_p(h))
+
+
+# ---- top-k, draws, groups, given, family: the finishes with kernels of their own ------------------------------------------------
+VOTES = pytest.mark.parametrize("vote", [1, 2])
+
+
+def _samples_equal(got, want, what, keys):
+    """Outputs whose first axis is the sample: integers equal, floats the same bits or NaN in both; names the first
+    differing sample with its group and lane."""
+    for k in keys:
+        a, b = np.ascontiguousarray(got[k]), np.ascontiguousarray(want[k])
+        assert a.shape == b.shape and a.dtype == b.dtype, (what, k, a.shape, b.shape, a.dtype, b.dtype)
+        if a.dtype.kind == "i":
+            bad = a != b
+        else:
+            bad = ~((a.view(np.uint64) == b.view(np.uint64)) | (np.isnan(a) & np.isnan(b)))
+        if bad.any():
+            at = np.argwhere(bad)
+            s = int(at[0][0])
+            raise AssertionError(f"{what} {k}: {len(at)} entries differ, the first at sample {s} (group {s // 64}, lane {s % 64})"
+                                 f"{'' if a.ndim == 1 else f', column {int(at[0][1])}'}: got {a[tuple(at[0])]!r}, "
+                                 f"reference {b[tuple(at[0])]!r}")
+
+
+def _clean(dev):
+    assert dev.status() == 0 and dev.handover_faults() == 0
+
+
+def _cohort_of(G):
+    n, S = G.shape
+    return hb.HlaSNPGeno(genotype=np.ascontiguousarray(G.T), sample_id=[f"S{i}" for i in range(n)], snp_id=[f"r{i}" for i in range(S)],
+                         snp_position=np.arange(S, dtype=np.float64), snp_allele=["A/G"] * S, assembly="hg19")
+
+
+LIST_KEYS = ("h1", "h2", "prob", "matching")
+
+
+@CASES
+@VOTES
+def test_topk(name, vote, device_model):
+    model, G = EC.case(name)
+    dev = device_model(model)
+    raw = dev.predict_raw(G, vote, want_dosage=False)
+    called = raw["h1"] != hb.NA_INTEGER
+    for k in EC.TOPK_K:
+        got = dev.predict_topk(G, k, vote)
+        _clean(dev)
+        _samples_equal(got, EC.topk_want(name, vote, k), f"{name}, vote {vote}, k {k}", LIST_KEYS)
+        _samples_equal({key: got[key][called, 0] for key in ("h1", "h2", "prob")}, {key: raw[key][called] for key in ("h1", "h2", "prob")},
+                       f"{name}, vote {vote}, k {k}: rank 0 against predict_raw", ("h1", "h2", "prob"))
+    if name in MIXED:
+        col = np.arange(G.shape[1], dtype=np.int32)
+        with hb.HlaDeviceCohort(_cohort_of(G)) as coh:
+            for k in EC.TOPK_K:
+                got = dev.predict_topk_cohort(coh, col, None, k, vote)
+                _clean(dev)
+                _samples_equal(got, EC.topk_want(name, vote, k), f"{name}, vote {vote}, k {k}, resident cohort", LIST_KEYS)
+
+
+@CASES
+@VOTES
+def test_draws(name, vote, device_model):
+    model, G = EC.case(name)
+    dev = device_model(model)
+    for sample0 in EC.DRAW_SAMPLE0:
+        for n in EC.DRAW_N:
+            got = dev.predict_draw(G, n, EC.DRAW_SEED, vote, sample0=sample0)
+            _clean(dev)
+            _samples_equal(got, EC.draws_want(name, vote, n, sample0), f"{name}, vote {vote}, n {n}, sample0 {sample0}", LIST_KEYS)
+    if name in MIXED:
+        col = np.arange(G.shape[1], dtype=np.int32)
+        with hb.HlaDeviceCohort(_cohort_of(G)) as coh:
+            for n in EC.DRAW_N:
+                got = dev.predict_draw_cohort(coh, col, None, n, EC.DRAW_SEED, vote, sample0=EC.DRAW_SAMPLE0[1])
+                _clean(dev)
+                _samples_equal(got, EC.draws_want(name, vote, n, EC.DRAW_SAMPLE0[1]), f"{name}, vote {vote}, n {n}, resident cohort", LIST_KEYS)
+
+
+GROUP_KEYS = ("g1", "g2", "prob", "matching", "dosage")
+
+
+@CASES
+@VOTES
+def test_groups(name, vote, device_model, monkeypatch):
+    model, G = EC.case(name)
+    want = EC.groups_want(name, vote)
+    nh = EC.n_hla(name)
+    dev = device_model(model)
+    raw = dev.predict_raw(G, vote, want_dosage=True)
+    with dev.groups_plan(EC.partitions(name)) as plan:
+        assert plan.tile()[1] is True
+        got = dev.predict_groups(G, plan, vote, want_dosage=True)
+        _clean(dev)
+        _samples_equal(got, want, f"{name}, vote {vote}", GROUP_KEYS)
+        lean = dev.predict_groups(G, plan, vote, want_dosage=False)
+        _samples_equal(lean, want, f"{name}, vote {vote}, no dosage", GROUP_KEYS[:4])
+        # the identity partition is the plain finish
+        mine = {"h1": got["g1"][:, EC.IDENTITY], "h2": got["g2"][:, EC.IDENTITY], "prob": got["prob"][:, EC.IDENTITY],
+                "dosage": got["dosage"][:, :nh]}
+        _samples_equal(mine, raw, f"{name}, vote {vote}: identity partition against predict_raw", ("h1", "h2", "prob", "dosage"))
+        if name in MIXED:
+            with monkeypatch.context() as mp:
+                mp.setenv("HIBAG_GROUPS_NO_LDS", "1")
+                assert plan.tile()[1] is False
+                got = dev.predict_groups(G, plan, vote, want_dosage=True)
+            _clean(dev)
+            _samples_equal(got, want, f"{name}, vote {vote}, without LDS", GROUP_KEYS)
+            col = np.arange(G.shape[1], dtype=np.int32)
+            with hb.HlaDeviceCohort(_cohort_of(G)) as coh:
+                got = dev.predict_groups_cohort(coh, col, None, plan, vote, want_dosage=True)
+            _clean(dev)
+            _samples_equal(got, want, f"{name}, vote {vote}, resident cohort", GROUP_KEYS)
+
+
+GIVEN_KEYS = ("h1", "h2", "prob", "support", "matching", "dosage")
+
+
+@CASES
+@VOTES
+def test_given(name, vote, device_model):
+    model, G = EC.case(name)
+    dev = device_model(model)
+    raw = dev.predict_raw(G, vote, want_dosage=True)
+    for which in EC.GIVEN_SETS:
+        allow = GR.pack(EC.given_sets(name, which))
+        got = dev.predict_given(G, allow, vote, want_dosage=True)
+        _clean(dev)
+        _samples_equal(got, EC.given_want(name, vote, which), f"{name}, vote {vote}, sets {which}", GIVEN_KEYS)
+        lean = dev.predict_given(G, allow, vote, want_dosage=False)
+        _samples_equal(lean, got, f"{name}, vote {vote}, sets {which}, no dosage", GIVEN_KEYS[:5])
+        if which == "full":                                   # the plain finish, and the draws' S
+            _samples_equal(got, raw, f"{name}, vote {vote}: full sets against predict_raw", ("h1", "h2", "prob", "dosage"))
+            _samples_equal(got, {"support": EC.draw_S(name, vote)}, f"{name}, vote {vote}: full sets against S", ("support",))
+    if name in MIXED:
+        col = np.arange(G.shape[1], dtype=np.int32)
+        with hb.HlaDeviceCohort(_cohort_of(G)) as coh:
+            for which in EC.GIVEN_SETS:
+                got = dev.predict_given_cohort(coh, col, None, GR.pack(EC.given_sets(name, which)), vote, want_dosage=True)
+                _clean(dev)
+                _samples_equal(got, EC.given_want(name, vote, which), f"{name}, vote {vote}, sets {which}, resident cohort", GIVEN_KEYS)
+
+
+@CASES
+@VOTES
+def test_family(name, vote, device_model, monkeypatch):
+    model, _ = EC.case(name)
+    G = EC.family_geno(name)
+    _, ped = EC.family_case(name)
+    dev = device_model(model)
+    raw = dev.predict_raw(G, vote, want_dosage=True)
+    S = EC.draw_S(name, vote)[EC.family_case(name)[0]]
+    for with_prior in (True, False):
+        prior = EC.family_prior(name, with_prior)
+        want = EC.family_want(name, vote, with_prior)
+        got = dev.predict_family(G, ped, prior, vote, want_dosage=True)
+        _clean(dev)
+        _samples_equal(got, want, f"{name}, vote {vote}, prior {with_prior}", GIVEN_KEYS)
+        lean = dev.predict_family(G, ped, prior, vote, want_dosage=False)
+        _samples_equal(lean, want, f"{name}, vote {vote}, prior {with_prior}, no dosage", GIVEN_KEYS[:5])
+        if name in MIXED:                                     # parents and children in different slices
+            with monkeypatch.context() as mp:
+                mp.setenv("HIBAG_STAGED_SLICE", "64")
+                got = dev.predict_family(G, ped, prior, vote, want_dosage=True)
+            _clean(dev)
+            _samples_equal(got, want, f"{name}, vote {vote}, prior {with_prior}, slices of 64", GIVEN_KEYS)
+        # founders only: the plain finish, and the draws' S
+        got = dev.predict_family(G, FR.founders_only(len(G)), prior, vote, want_dosage=True)
+        _clean(dev)
+        _samples_equal(got, raw, f"{name}, vote {vote}, prior {with_prior}: founders against predict_raw", ("h1", "h2", "prob", "dosage"))
+        _samples_equal(got, {"support": S}, f"{name}, vote {vote}, prior {with_prior}: founders against S", ("support",))
+
+
+def test_wrappers_hand_infinite_probabilities_through(device_model):
+    """hlaPredictTopK, hlaPredictDraws, hlaPredictGroups, hlaPredictGiven and hlaPredictFamily on subnormal-lanes: no
+    exception, and the inf probabilities as the device wrote them."""
+    import warnings
+    name = "subnormal-lanes"
+    model, G = EC.case(name)
+    dev = device_model(model)
+    snp = np.ascontiguousarray(G.T)
+    inf = np.isposinf(EC.plain_want(name, 1)["prob"])
+    assert inf.sum() >= 10
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")                       # ("No prediction output" for the samples that type nothing)
+        top = hb.hlaPredictTopK(dev, snp, k=5, verbose=False)
+        draws = hb.hlaPredictDraws(dev, snp, n=17, seed=EC.DRAW_SEED, verbose=False)
+        groups = hb.hlaPredictGroups(dev, snp, EC.partitions(name), verbose=False)
+        given = hb.hlaPredictGiven(dev, snp, EC.given_sets(name, "moved"), dosage=True, verbose=False)
+        fam_G = np.ascontiguousarray(EC.family_geno(name).T)
+        family = hb.hlaPredictFamily(dev, fam_G, EC.family_case(name)[1], prior="model", dosage=True, verbose=False)
+    _clean(dev)
+    _samples_equal({"h1": top.h1, "h2": top.h2, "prob": top.prob, "matching": top.matching}, EC.topk_want(name, 1, 5), "hlaPredictTopK", LIST_KEYS)
+    assert np.isposinf(top.prob[inf]).all() and np.isposinf(top.best().prob[inf]).all()
+    _samples_equal({"h1": draws.h1, "h2": draws.h2, "prob": draws.prob, "matching": draws.matching}, EC.draws_want(name, 1, 17, 0),
+                   "hlaPredictDraws", LIST_KEYS)
+    assert np.isposinf(draws.prob[inf]).all()
+    _samples_equal({"g1": groups.g1, "g2": groups.g2, "prob": groups.prob, "matching": groups.matching, "dosage": groups.dosage},
+                   EC.groups_want(name, 1), "hlaPredictGroups", GROUP_KEYS)
+    assert np.isposinf(groups.prob[inf]).all()
+    want = EC.given_want(name, 1, "moved")
+    _samples_equal({"h1": given.h1, "h2": given.h2, "prob": given.prob_joint, "support": given.support, "matching": given.matching},
+                   want, "hlaPredictGiven", GIVEN_KEYS[:5])
+    assert np.isposinf(given.prob_joint[inf]).all() and np.isposinf(given.support[inf]).all()
+    assert np.array_equal(given.prob, GR.conditional(want)["prob"], equal_nan=True)
+    want = EC.family_want(name, 1, True)
+    assert np.array_equal(hb.hlaModelAllelePrior(model), EC.family_prior(name, True))
+    _samples_equal({"h1": family.h1, "h2": family.h2, "prob": family.prob_joint, "support": family.support, "matching": family.matching},
+                   want, "hlaPredictFamily", GIVEN_KEYS[:5])
+    assert np.isposinf(want["prob"]).sum() >= 10 and np.array_equal(family.prob, FR.conditional(want)["prob"], equal_nan=True)

@@ -57,21 +57,23 @@ def select(postprob: np.ndarray, k: int, n_hla: int) -> dict:
 
 def select_fast(postprob: np.ndarray, k: int, n_hla: int) -> dict:
     """The same lists by ``np.argpartition`` and an ordered sort of the k survivors (descending value, equal values in
-    cell order).  A row whose k-th value is tied with a cell the partition left out is done by the definition."""
+    cell order).  A row whose k-th value is tied with a cell the partition left out is done by the definition.  +inf is a
+    value that qualifies like any other (a total below 1 / DBL_MAX makes such rows)."""
     pp = np.asarray(postprob, np.float64)
     n, P = pp.shape
     if P <= k or n == 0:
         return select(pp, k, n_hla)
     with np.errstate(invalid="ignore"):
-        c = np.where(pp > 0, pp, -np.inf)                    # zeros, negatives and NaN never qualify
+        c = np.where(pp > 0, pp, -np.inf)                    # zeros, negatives and NaN never qualify: -inf marks them
     cell = np.argpartition(-c, k - 1, axis=1)[:, :k]
     val = np.take_along_axis(c, cell, axis=1)
     order = np.lexsort((cell, -val), axis=1)
     cell, val = np.take_along_axis(cell, order, axis=1), np.take_along_axis(val, order, axis=1)
     thr = val[:, -1:]
-    cut = np.isfinite(thr[:, 0]) & ((c == thr).sum(axis=1) > (val == thr).sum(axis=1))      # a tie across the partition
-    cell = np.where(np.isfinite(val), cell, -1)
-    out = _finish(cell, np.where(np.isfinite(val), val, 0.0), k, n_hla)
+    listed = val != -np.inf                                  # only the marker drops out: +inf is a value like any other
+    cut = listed[:, -1] & ((c == thr).sum(axis=1) > (val == thr).sum(axis=1))               # a tie across the partition
+    cell = np.where(listed, cell, -1)
+    out = _finish(cell, np.where(listed, val, 0.0), k, n_hla)
     if cut.any():
         redo = select(pp[cut], k, n_hla)
         for key in KEYS:
