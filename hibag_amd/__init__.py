@@ -42,9 +42,10 @@ from .associnteract import HlaAssocInteractResult, hlaAssocInteract  # noqa: F40
 from .assocscore import HlaAssocScoreResult, hlaAssocScore  # noqa: F401
 from .haplo import HlaHaplotypeResult, hlaHaplotypes  # noqa: F401
 from .assochaplo import HlaAssocHaploResult, hlaAssocHaplo  # noqa: F401
+from .assocsurv import HlaAssocSurvResult, hlaAssocSurv  # noqa: F401
 from ._lib import HibagHipError  # noqa: F401
 
-__all__ = ["hlaAssocHaplo", "HlaAssocHaploResult", "hlaHaplotypes", "HlaHaplotypeResult", "hlaAssocScore", "HlaAssocScoreResult","hlaAssocInteract", "HlaAssocInteractResult", "hlaAssocOmnibus", "hlaAssocStepwise", "HlaAssocOmnibusResult", "HlaAssocStepwiseResult", "hlaAssocGlm", "HlaAssocGlmResult", "hlaAssocQuant", "HlaAssocQuantResult", "hlaSNPImportance", "HlaSNPImportance", "engine_kind", "engine_nkb", "engine_steps", "NA_INTEGER", "Classifier", "HlaAttrBagObj", "HlaSNPGeno", "load_geno", "load_model", "model_to_robj", "save_model",
+__all__ = ["hlaAssocSurv", "HlaAssocSurvResult", "hlaAssocHaplo", "HlaAssocHaploResult", "hlaHaplotypes", "HlaHaplotypeResult", "hlaAssocScore", "HlaAssocScoreResult","hlaAssocInteract", "HlaAssocInteractResult", "hlaAssocOmnibus", "hlaAssocStepwise", "HlaAssocOmnibusResult", "HlaAssocStepwiseResult", "hlaAssocGlm", "HlaAssocGlmResult", "hlaAssocQuant", "HlaAssocQuantResult", "hlaSNPImportance", "HlaSNPImportance", "engine_kind", "engine_nkb", "engine_steps", "NA_INTEGER", "Classifier", "HlaAttrBagObj", "HlaSNPGeno", "load_geno", "load_model", "model_to_robj", "save_model",
            "HlaAlleleClass", "HlaAttrBagClass", "hlaClose", "hlaModelFromObj", "hlaModelToObj",
            "hlaPredict", "hlaSetKernelTarget", "hlaGenoSwitchStrand", "hlaSNPID", "HibagHipError",
            "HlaBEDGeno", "hlaBED2Geno", "hlaLociInfo", "RRandom", "hlaAllele", "hlaAttrBagging", "hlaConcurrentAttrBagging", "hlaParallelAttrBagging", "hlaUniqueAllele", "hlaAlleleDigit", "hlaPredMerge", "hlaPredictMerge", "hlaAlleleSubset", "hlaCompareAllele", "hlaFlankingSNP", "hlaGenoSubset",

@@ -64,6 +64,7 @@ EXPORTS = [
     "hibag_hip_assoc_n_kept", "hibag_hip_assoc_feature_rows", "hibag_hip_assoc_glm",
     "hibag_hip_assoc_glm_sets", "hibag_hip_assoc_row_sums",
     "hibag_hip_assoc_glm_terms", "hibag_hip_assoc_row_gram",
+    "hibag_hip_assoc_cox", "hibag_hip_assoc_cox_segment",
     "hibag_hip_assoc_quant_new", "hibag_hip_assoc_quant_free", "hibag_hip_assoc_quant_classes", "hibag_hip_assoc_quant_observed",
     "hibag_hip_assoc_quant_permute", "hibag_hip_assoc_quant_perm_rows", "hibag_hip_assoc_quant_gram_ms",
     "hibag_hip_assoc_score_new", "hibag_hip_assoc_score_free", "hibag_hip_assoc_score_base", "hibag_hip_assoc_score_sets",
@@ -206,6 +207,9 @@ def lib() -> C.CDLL:
     if hasattr(L, "hibag_hip_assoc_glm_terms"):
         L.hibag_hip_assoc_glm_terms.argtypes = [vp, vp, i32, vp, i32, vp, i32, C.c_double, vp, vp, vp, vp, vp, vp]
         L.hibag_hip_assoc_row_gram.argtypes = [vp, i32, i32, vp]
+    if hasattr(L, "hibag_hip_assoc_cox"):
+        L.hibag_hip_assoc_cox.argtypes = [vp, vp, vp, i32, i32, i32, C.c_double, vp, vp, vp, vp, vp, vp, vp]
+        L.hibag_hip_assoc_cox_segment.argtypes = [i32, C.POINTER(i32), C.POINTER(i32)]
     if hasattr(L, "hibag_hip_assoc_quant_new"):
         L.hibag_hip_assoc_quant_new.argtypes = [vp, vp, vp, i32]
         L.hibag_hip_assoc_quant_new.restype = vp

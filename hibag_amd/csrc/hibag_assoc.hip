@@ -19,6 +19,10 @@
 // up to three TERMS -- a feature row, or the product of two, formed while the samples are walked -- on the same buffers and
 // driver; hibag_hip_assoc_row_gram gives the exact co-carriage sums of feature rows from k_ld_gram<1>.
 //
+// hibag_hip_assoc_cox (hlaAssocSurv; kernels: hibag_k_cox.h) fits one Cox regression per test on a handle
+// whose samples come in time order; it uses `GlmCall`'s argument checks and the regression buffers, with launches of its own
+// (the base model first, whose coefficients the tests start from).
+//
 // hibag_hip_assoc_quant_* (hlaAssocQuant; kernels: hibag_k_quant.h) test a quantitative trait on the
 // same feature rows, through a handle of their own that borrows this one; hibag_hip_assoc_score_* (hlaAssocScore, DESIGN.md
 // section 28; kernels: hibag_k_score.h) run covariate-adjusted score tests with multiplier resampling the same way; both are
@@ -31,6 +35,7 @@
 #include "hibag_k_glm.h"
 #include "hibag_k_glmw.h"
 #include "hibag_k_glmt.h"
+#include "hibag_k_cox.h"
 #include "hibag_k_quant.h"
 #include "hibag_k_score.h"
 #include "hibag_k_rscore.h"
@@ -134,6 +139,7 @@ struct hibag_hip_assoc {
 	PermOut out;                                 // per permutation call
 	DevBuf y;                                    // int8 [kp]: the kept samples' labels, zero padding (hibag_hip_assoc_glm)
 	DevBuf glm_in, glm_img, glm_wt, glm_fits, glm_out; // hibag_hip_assoc_glm: covariates and weights as given, the operand image, the padded weights, GlmFit [n_fit], the outputs
+	DevBuf cox_time, cox_tab, cox_scr;           // hibag_hip_assoc_cox: the times as given, the block table (int32 [5 kp + 1]), the fits' scratch (3 kp doubles each)
 	std::vector<int32_t> h_row_sum;              // the feature rows' sums [rows]
 	std::vector<double> h_stat;                  // the observed statistics and tables, made once by hibag_hip_assoc_new
 	std::vector<int64_t> h_table;
@@ -142,7 +148,7 @@ struct hibag_hip_assoc {
 	{
 		(void)hipSetDevice(device);
 		if (st) (void)hipStreamSynchronize(st);
-		for (DevBuf *b : {&feat, &row_sum, &stat_obs, &labels, &gram, &y, &glm_in, &glm_img, &glm_wt, &glm_fits, &glm_out}) b->release();
+		for (DevBuf *b : {&feat, &row_sum, &stat_obs, &labels, &gram, &y, &glm_in, &glm_img, &glm_wt, &glm_fits, &glm_out, &cox_time, &cox_tab, &cox_scr}) b->release();
 		out.release();
 		if (st) (void)hipStreamDestroy(st);
 	}
@@ -273,6 +279,7 @@ int rows_gram(hibag_hip_assoc *h, int a0, int na, int b0, int nb, int32_t *out)
 constexpr int kMaxGramRows = 8192;               // hibag_hip_assoc_row_gram: 256 MiB of int32 at most
 constexpr int kGramBlock = 2048;                 // hibag_hip_assoc_glm_terms: the products' sums come in blocks of rows x rows
 constexpr int kMaxTermFits = 1 << 20;
+constexpr size_t kCoxScratchBytes = (size_t)256 << 20; // hibag_hip_assoc_cox: the fits of one launch share this much scratch, one fit at least
 
 // what hibag_hip_assoc_new does on the device: features, then the observed labelling as a panel of one
 int build(hibag_hip_assoc *h, const std::vector<int32_t> &a1, const std::vector<int32_t> &a2, const std::vector<int8_t> &y,
@@ -522,6 +529,116 @@ int hibag_hip_assoc_row_sums(hibag_hip_assoc *h, int32_t *out)
 	if (!h || !out) return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_row_sums: null argument");
 	std::copy(h->h_row_sum.begin(), h->h_row_sum.end(), out);
 	return 0;
+}
+
+int hibag_hip_assoc_cox_segment(int n_kept, int *step, int *segment)
+{
+	if (n_kept <= 0 || n_kept > kMaxSamples || !step || !segment)
+		return hibag_fail(HIBAG_HIP_EINVAL, "hibag_hip_assoc_cox_segment: n_kept = %d outside 1 .. 2^24, or a null pointer", n_kept);
+	static_assert(HIBAG_LD_KPAD % (COX_STEP * COX_WAVES) == 0, "the segments of k_cox_fit are whole steps and equal");
+	*step = COX_STEP;
+	*segment = (int)(pad_to((size_t)n_kept, HIBAG_LD_KPAD) / COX_WAVES);
+	return 0;
+}
+
+int hibag_hip_assoc_cox(hibag_hip_assoc *h, const double *time, const double *covar, int n_covar, int ties, int maxit, double epsilon,
+	const double *start, double *coef, double *se, double *loglik, double *score, int32_t *iterations, int32_t *flags)
+{
+	const char *me = "hibag_hip_assoc_cox";
+	if (!h || !time || !coef || !se || !loglik || !score || !iterations || !flags) return hibag_fail(HIBAG_HIP_EINVAL, "%s: null argument", me);
+	static_assert(COX_COV0 + HIBAG_HIP_COX_MAX_COVAR < COX_ONE, "two h slots, the covariates, then the constant");
+	static_assert(sizeof(CoxFit) == 2 * sizeof(int), "CoxFit records are uploaded as they are");
+	const GlmCall call{me, h, covar, n_covar, nullptr, maxit, epsilon, coef, se, loglik, iterations, flags, nullptr};
+	if (int rc = call.check_control(HIBAG_HIP_COX_MAX_COVAR)) return rc;
+	if (ties != COX_TIES_EFRON && ties != COX_TIES_BRESLOW) return hibag_fail(HIBAG_HIP_EINVAL, "%s: ties = %d; 0 efron, 1 breslow", me, ties);
+	if (int rc = call.check_values()) return rc;
+	const int n = h->D.n, T = h->D.n_test, kp = h->kp, q = n_covar, n_fit = T + 1;
+	for (int i = 0; i < n; i++) {
+		if (!std::isfinite(time[i]) || time[i] < 0) return hibag_fail(HIBAG_HIP_EINVAL, "%s: time[%d] = %g; times are finite and >= 0", me, i, time[i]);
+		if (i > 0 && time[i] > time[i - 1])
+			return hibag_fail(HIBAG_HIP_EINVAL, "%s: time[%d] > time[%d]; the kept samples come in time order, latest first", me, i, i - 1);
+	}
+	std::vector<double> beta0((size_t)COX_SLOTS, 0.0), base((size_t)COX_SLOTS, 0.0);      // where the base model starts; where the tests do
+	if (start)
+		for (int j = 0; j < q; j++) {
+			if (!std::isfinite(start[j])) return hibag_fail(HIBAG_HIP_EINVAL, "%s: start[%d] is not finite", me, j);
+			beta0[(size_t)COX_COV0 + j] = start[j];
+		}
+
+	// the fits, the base model first: which feature rows stand behind slots 0 and 1
+	std::vector<CoxFit> fits((size_t)n_fit);
+	const std::vector<int32_t> &r = h->h_row_sum;
+	fits[0] = CoxFit{h->n_case > 0 ? -1 : -2, -1};
+	for (int t = 0; t < T; t++) {
+		CoxFit &f = fits[(size_t)t + 1];
+		if (h->D.model == ASSOC_GENOTYPE) {
+			const int64_t het = r[2 * t], hom = r[2 * t + 1];
+			f.row_a = het > 0 ? 2 * t : -1;
+			f.row_b = hom > 0 ? 2 * t + 1 : -1;
+			if ((het == 0 && hom == 0) || het + hom == n) f.row_a = -2;
+		} else {
+			const int64_t top = (int64_t)(h->D.model == ASSOC_ADDITIVE ? 2 : 1) * n;
+			f.row_a = (r[t] == 0 || r[t] == top) ? -2 : t;
+			f.row_b = -1;
+		}
+		if (h->n_case == 0) f.row_a = -2;
+	}
+
+	HIP_TRY(hipSetDevice(h->device));
+	const hipStream_t st = h->st;
+	const size_t nf = (size_t)n_fit, per_fit = sizeof(double) * 3 * (size_t)kp;
+	const int batch = (int)std::min<size_t>(nf, std::max<size_t>(kCoxScratchBytes / per_fit, 1));
+	if (h->glm_in.reserve(sizeof(double) * std::max<size_t>((size_t)q * n, 1)) || h->glm_img.reserve(sizeof(double) * COX_SLOTS * (size_t)kp) ||
+		h->glm_fits.reserve(sizeof(CoxFit) * nf) || h->glm_out.reserve(nf * ((2 * COX_SLOTS + 2) * sizeof(double) + 2 * sizeof(int32_t)) + sizeof(double) * COX_SLOTS) ||
+		h->cox_time.reserve(sizeof(double) * (size_t)n) || h->cox_tab.reserve(sizeof(int32_t) * (5 * (size_t)kp + 1)) ||
+		h->cox_scr.reserve(per_fit * (size_t)batch))
+		return HIBAG_HIP_ENOMEM;
+	double *d_cov = h->glm_in.as<double>(), *d_time = h->cox_time.as<double>(), *d_img = h->glm_img.as<double>();
+	double *o_coef = h->glm_out.as<double>(), *o_se = o_coef + nf * COX_SLOTS, *o_ll = o_se + nf * COX_SLOTS, *o_sc = o_ll + nf, *d_start = o_sc + nf;
+	int32_t *o_it = (int32_t *)(d_start + COX_SLOTS), *o_fl = o_it + nf;
+	int32_t *t_blk = h->cox_tab.as<int32_t>(), *t_first = t_blk + kp, *t_dk = t_first + kp + 1, *t_scan = t_dk + kp;
+	const CoxTable tab{t_blk, t_first, t_dk};
+	int32_t base_fl = 0;
+	const std::vector<CoxFit> none(nf, CoxFit{-2, -1});
+	auto launch_fits = [&](int f0, int count) {
+		hipLaunchKernelGGL(k_cox_fit, dim3(count), dim3(COX_WAVES * 64), 0, st, d_img, h->y.as<int8_t>(), h->feat.as<int8_t>(),
+			h->glm_fits.as<CoxFit>() + f0, tab, d_start, n, kp, q, ties, maxit, epsilon, h->cox_scr.as<double>(), o_coef + (size_t)f0 * COX_SLOTS,
+			o_se + (size_t)f0 * COX_SLOTS, o_ll + f0, o_sc + f0, o_it + f0, o_fl + f0);
+	};
+	return enqueued(st, [&]() -> int {
+		if (q) HIP_TRY(hipMemcpyAsync(d_cov, covar, sizeof(double) * (size_t)q * n, hipMemcpyHostToDevice, st));
+		HIP_TRY(hipMemcpyAsync(d_time, time, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, st));
+		HIP_TRY(hipMemcpyAsync(h->glm_fits.p, fits.data(), sizeof(CoxFit) * nf, hipMemcpyHostToDevice, st));
+		HIP_TRY(hipMemcpyAsync(d_start, beta0.data(), sizeof(double) * COX_SLOTS, hipMemcpyHostToDevice, st));
+		hipLaunchKernelGGL(k_cox_image, dim3((unsigned)(((size_t)kp * COX_SLOTS + 255) / 256) + 1), dim3(256), 0, st, d_cov, d_time,
+			h->y.as<int8_t>(), n, q, kp, d_img, t_blk, t_first, t_dk, t_scan);
+		HIP_TRY(hipGetLastError());
+		// the base model, whose coefficients the tests start from
+		launch_fits(0, 1);
+		if (hipGetLastError() != hipSuccess) return hibag_fail(HIBAG_HIP_ENODEV, "%s: a kernel launch failed", me);
+		HIP_TRY(hipMemcpyAsync(base.data(), o_coef, sizeof(double) * COX_SLOTS, hipMemcpyDeviceToHost, st));
+		HIP_TRY(hipMemcpyAsync(&base_fl, o_fl, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+		HIP_TRY(hipStreamSynchronize(st));
+		if (base_fl & COX_FLAG_RANK) {
+			// no base model, no start: every test is reported like it
+			HIP_TRY(hipMemcpyAsync(h->glm_fits.p, none.data(), sizeof(CoxFit) * nf, hipMemcpyHostToDevice, st));
+			HIP_TRY(hipStreamSynchronize(st));
+		}
+		for (double &v : base) if (std::isnan(v)) v = 0.0;
+		HIP_TRY(hipMemcpyAsync(d_start, base.data(), sizeof(double) * COX_SLOTS, hipMemcpyHostToDevice, st));
+		for (int f0 = 1; f0 < n_fit; f0 += batch) {
+			launch_fits(f0, std::min(batch, n_fit - f0));
+			if (hipGetLastError() != hipSuccess) return hibag_fail(HIBAG_HIP_ENODEV, "%s: a kernel launch failed", me);
+		}
+		HIP_TRY(hipMemcpyAsync(coef, o_coef, sizeof(double) * nf * COX_SLOTS, hipMemcpyDeviceToHost, st));
+		HIP_TRY(hipMemcpyAsync(se, o_se, sizeof(double) * nf * COX_SLOTS, hipMemcpyDeviceToHost, st));
+		HIP_TRY(hipMemcpyAsync(loglik, o_ll, sizeof(double) * nf, hipMemcpyDeviceToHost, st));
+		HIP_TRY(hipMemcpyAsync(score, o_sc, sizeof(double) * nf, hipMemcpyDeviceToHost, st));
+		HIP_TRY(hipMemcpyAsync(iterations, o_it, sizeof(int32_t) * nf, hipMemcpyDeviceToHost, st));
+		HIP_TRY(hipMemcpyAsync(flags, o_fl, sizeof(int32_t) * nf, hipMemcpyDeviceToHost, st));
+		HIP_TRY(hipStreamSynchronize(st));
+		return 0;
+	});
 }
 
 int hibag_hip_assoc_glm_sets(hibag_hip_assoc *h, const int32_t *set_start, const int32_t *set_rows, int n_sets, const double *covar,

@@ -40,7 +40,8 @@ extern "C" {
                                        + the quantitative-trait entries (hibag_hip_assoc_quant_*): likewise;
                                        + the set regression (hibag_hip_assoc_glm_sets, hibag_hip_assoc_row_sums): likewise;
                                        + the term regression (hibag_hip_assoc_glm_terms, hibag_hip_assoc_row_gram): likewise;
-                                       + the score tests (hibag_hip_assoc_score_*): likewise */
+                                       + the score tests (hibag_hip_assoc_score_*): likewise;
+                                       + the Cox regression (hibag_hip_assoc_cox, hibag_hip_assoc_cox_segment): likewise */
 
 /* error codes */
 #define HIBAG_HIP_OK          0
@@ -379,6 +380,42 @@ int hibag_hip_assoc_glm_sets(hibag_hip_assoc *h, const int32_t *set_start, const
 
 /* The sums of the handle's feature rows over the kept samples: out int32 [rows], rows as hibag_hip_assoc_feature_rows. */
 int hibag_hip_assoc_row_sums(hibag_hip_assoc *h, int32_t *out);
+
+/* ---- Cox regression per test for time-to-event traits: hlaAssocSurv ------------
+ * coxph(Surv(time, event) ~ h + covariates) for every test of the handle and for the base model Surv ~ covariates: Newton's
+ * method on the Efron or Breslow partial likelihood, no step halving.  The handle's kept samples must come in time order,
+ * LATEST FIRST, and its y is the event indicator.  The definitions are DESIGN.md section 31.  A fit's numbers depend on the
+ * kept samples, its own columns and the arguments below, not on the other tests of the handle.
+ *   time        float64 [n_kept], finite, >= 0, not increasing
+ *   covar       float64 [n_covar][n_kept], one row per covariate, centred by the caller (NULL with n_covar = 0);
+ *               0 <= n_covar <= HIBAG_HIP_COX_MAX_COVAR
+ *   ties        HIBAG_HIP_COX_EFRON or HIBAG_HIP_COX_BRESLOW
+ *   maxit       >= 1 iterations at most; epsilon > 0: converged when |1 - loglik_old / loglik_new| <= epsilon
+ *   start       float64 [n_covar] where the base model's coefficients start, or NULL for 0
+ * Outputs for 1 + n_tests fits, fit 0 the base model, fit 1 + t test t; a test starts from 0 for h and the base model's
+ * coefficients:
+ *   coef, se    float64 [1 + n_tests][16] by slot: 0 h (het for GENOTYPE), 1 hom (GENOTYPE only), 2 .. 1 + n_covar the
+ *               covariates; every other slot NaN
+ *   loglik      float64: the partial log-likelihood of the reported coefficients
+ *   score       float64: the score statistic of the h slots at the start (NaN for the base model)
+ *   iterations int32, flags int32 (HIBAG_HIP_COX_*)
+ * A test whose column is constant over the kept samples is not fitted (RANK, NaN), GENOTYPE as hibag_hip_assoc_glm; with
+ * no event among the kept samples, or a base model with RANK, no fit is.
+ * EINVAL for a null handle, time or output, n_covar outside its range, bad ties, maxit < 1, epsilon not > 0, a non-finite
+ * covariate or start value, a time that is not finite, negative or larger than its predecessor. */
+#define HIBAG_HIP_COX_MAX_COVAR 12
+#define HIBAG_HIP_COX_EFRON     0
+#define HIBAG_HIP_COX_BRESLOW   1
+#define HIBAG_HIP_COX_MAXIT     1   /* not converged within maxit: the last values are reported */
+#define HIBAG_HIP_COX_RANK      2   /* a pivot <= 1e-11 I_jj, a column that cannot be fitted, no event: the values are NaN */
+#define HIBAG_HIP_COX_CLAMP     4   /* a linear predictor outside [-200, 200] was clamped in some evaluation */
+#define HIBAG_HIP_COX_DECREASE  8   /* the log-likelihood decreased in an iteration that did not converge (no step halving) */
+int hibag_hip_assoc_cox(hibag_hip_assoc *h, const double *time, const double *covar, int n_covar, int ties, int maxit, double epsilon,
+	const double *start, double *coef, double *se, double *loglik, double *score, int32_t *iterations, int32_t *flags);
+
+/* The constants of the fit kernel's walk at n_kept samples: *step the samples of one matrix-core step, *segment the
+ * contiguous samples one wave owns (the tests place ties across the seams with them). */
+int hibag_hip_assoc_cox_segment(int n_kept, int *step, int *segment);
 
 /* ---- pairwise interaction fits: hlaAssocInteract ------------
  * The co-carriage sums of feature rows: out int32 [n_rows][n_rows], out[i][j] = the sum over the kept samples of
