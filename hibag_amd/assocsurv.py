@@ -134,7 +134,10 @@ def hlaAssocSurv(hla: HlaAlleleClass, time: Sequence, event: Sequence, covariate
     A test whose column is constant over the kept samples has flag bit 1 and NaN; the ``genotype`` model drops a dummy that
     nobody carries, as ``hlaAssocGlm``.  With no event among the kept samples every test has bit 1.  A column whose carriers
     (or non-carriers) have no event has a monotone likelihood: it is fitted as it comes and ends with bit 0 and / or bit 2,
-    or converged on the flat likelihood with a large estimate and a huge ``se``; its likelihood-ratio and score tests are valid.  A rank-deficient base model is a ValueError.  The likelihood-ratio
+    or converged on the flat likelihood with a large estimate and a huge ``se``; its likelihood-ratio and score tests are valid.
+    A column whose carriers are the earliest events can lose its information altogether after an overshooting first step
+    (their risk dominates every risk set): it has bit 1 and NaN, never a runaway estimate.  A rank-deficient base model is a
+    ValueError.  The likelihood-ratio
     columns are NaN only where the fit or the base model has bit 1.
 
     Not built: ``use_prob`` / case weights, strata, left truncation and time-varying covariates, robust variance, step

@@ -163,7 +163,7 @@ __device__ __forceinline__ void cox_block(double S, double D, int d, int ties, i
 // 3. the exclusive suffix over the segments' totals of a_k;
 // 4. backwards, sample by sample the running A; per step one MFMA with a = w x, b = x.
 // Then the waves' tiles are added in wave order and thread 0 tests convergence, factorises I = G - V over the used slots
-// (column order, pivot rule 1e-11 I_jj) and takes the Newton step.  The factor of the LAST solve stays in LDS; the standard
+// (column order, pivot rule 1e-11 G_jj) and takes the Newton step.  The factor of the LAST solve stays in LDS; the standard
 // errors come from it after the loop.  After the first factorisation thread 0 also forms the score statistic of the h slots.
 //
 // start [16] by slot: where the fit starts.  scr: 3 kp doubles per fit of the launch (r by sample; a, b by block).
@@ -176,6 +176,7 @@ __global__ void __launch_bounds__(COX_WAVES * 64) k_cox_fit(const double *__rest
 	__shared__ double s_G[COX_WAVES][256];      // the waves' tiles of sum w x x'
 	__shared__ double s_V[COX_WAVES][256];      // the waves' tiles of sum v v'
 	__shared__ double s_I[256];                 // G - V: rows / columns = slots
+	__shared__ double s_Gd[COX_SLOTS];          // the diagonal of G: the scale a pivot of G - V is judged against
 	__shared__ double s_T[COX_WAVES][COX_SLOTS]; // the segments' totals of r x
 	__shared__ double s_ex[COX_WAVES][COX_SLOTS]; // the segments' sums of the events' x
 	__shared__ double s_eta[COX_WAVES], s_phi[COX_WAVES], s_a[COX_WAVES];
@@ -331,6 +332,7 @@ __global__ void __launch_bounds__(COX_WAVES * 64) k_cox_fit(const double *__rest
 			double G = s_G[0][tid], V = s_V[0][tid];
 			for (int w = 1; w < COX_WAVES; w++) { G += s_G[w][tid]; V += s_V[w][tid]; }
 			s_I[tid] = G - V;
+			if ((tid >> 4) == (tid & 15)) s_Gd[tid >> 4] = G;
 			if ((tid & 15) == COX_ONE) {
 				const int i = tid >> 4;
 				double ex = s_ex[0][i];
@@ -364,10 +366,10 @@ __global__ void __launch_bounds__(COX_WAVES * 64) k_cox_fit(const double *__rest
 				bool ok = true;
 				for (int j = 0; j < p && ok; j++) {
 					const int sj = s_act[j];
-					const double ajj = s_I[sj * 16 + sj];
-					double dj = ajj;
+					double dj = s_I[sj * 16 + sj];
 					for (int m = 0; m < j; m++) dj -= s_L[j * 16 + m] * s_L[j * 16 + m];
-					if (!(dj > 1e-11 * ajj)) { ok = false; break; }
+					// against G_jj, what the subtraction cancelled: an information that is rounding noise fails in every precision
+					if (!(dj > 1e-11 * s_Gd[sj])) { ok = false; break; }
 					const double ljj = sqrt(dj);
 					s_L[j * 16 + j] = ljj;
 					for (int i = j + 1; i < p; i++) {

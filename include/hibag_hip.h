@@ -407,7 +407,7 @@ int hibag_hip_assoc_row_sums(hibag_hip_assoc *h, int32_t *out);
 #define HIBAG_HIP_COX_EFRON     0
 #define HIBAG_HIP_COX_BRESLOW   1
 #define HIBAG_HIP_COX_MAXIT     1   /* not converged within maxit: the last values are reported */
-#define HIBAG_HIP_COX_RANK      2   /* a pivot <= 1e-11 I_jj, a column that cannot be fitted, no event: the values are NaN */
+#define HIBAG_HIP_COX_RANK      2   /* a pivot of I = G - V <= 1e-11 G_jj, a column that cannot be fitted, no event: the values are NaN */
 #define HIBAG_HIP_COX_CLAMP     4   /* a linear predictor outside [-200, 200] was clamped in some evaluation */
 #define HIBAG_HIP_COX_DECREASE  8   /* the log-likelihood decreased in an iteration that did not converge (no step halving) */
 int hibag_hip_assoc_cox(hibag_hip_assoc *h, const double *time, const double *covar, int n_covar, int ties, int maxit, double epsilon,

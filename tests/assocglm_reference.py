@@ -18,15 +18,20 @@ SLOTS, COV0, MAX_COVAR = 16, 3, 12
 MAXIT_BIT, RANK_BIT, BOUNDARY_BIT = 1, 2, 4
 
 
-def cholesky(A, dtype):
-    """L (lower, L L' = A) column by column, or None where a pivot is <= 1e-11 A_jj."""
+def cholesky(A, dtype, scale=None, pivots=None):
+    """L (lower, L L' = A) column by column, or None where a pivot is <= 1e-11 scale_j; ``scale`` is the diagonal of A unless
+    given (the Cox fits give the diagonal before the cancellation).  ``pivots``: a list that receives every tested pivot as
+    (pivot, threshold) in float."""
     p = len(A)
     L = np.zeros((p, p), dtype)
     for j in range(p):
         d = A[j, j]
         for m in range(j):
             d = d - L[j, m] * L[j, m]
-        if not d > dtype(1e-11) * A[j, j]:
+        limit = dtype(1e-11) * (A[j, j] if scale is None else scale[j])
+        if pivots is not None:
+            pivots.append((float(d), float(limit)))
+        if not d > limit:
             return None
         L[j, j] = np.sqrt(d)
         for i in range(j + 1, p):
@@ -82,7 +87,8 @@ def _deviance(mu, y, wt):
 
 
 def fit(X, y, wt, maxit=25, epsilon=1e-8, dtype=np.float64):
-    """One fit of items 3-5: dict coef, se [p], deviance, iterations, flags, crit (every iteration's)."""
+    """One fit of items 3-5: dict coef, se [p], deviance, iterations, flags, crit (every iteration's), pivots (every tested
+    pivot with its threshold) and eta_max (the largest |eta| the weights of an iteration were taken at)."""
     X = np.asarray(X, dtype)
     y = np.asarray(y, dtype)
     wt = np.asarray(wt, dtype)
@@ -92,9 +98,10 @@ def fit(X, y, wt, maxit=25, epsilon=1e-8, dtype=np.float64):
     mu = (wt * y + dtype(0.5)) / (wt + 1)
     eta = np.log(mu / (1 - mu))
     devold = _deviance(mu, y, wt)
-    crits = []
+    crits, pivots, eta_max = [], [], 0.0
     flags = 0
     for k in range(1, maxit + 1):
+        eta_max = max(eta_max, float(np.abs(eta[wt > 0]).max(initial=0.0)))
         t, mu = _mean(eta, dtype)
         g = np.where(np.abs(eta) > 30, eps, t / ((1 + t) * (1 + t)))
         v = mu * (1 - mu)
@@ -102,9 +109,9 @@ def fit(X, y, wt, maxit=25, epsilon=1e-8, dtype=np.float64):
         W = wt * (g * g) / v
         A = X.T @ (X * W[:, None])
         b = X.T @ (W * z)
-        L = cholesky(A, dtype)
+        L = cholesky(A, dtype, pivots=pivots)
         if L is None:
-            return dict(coef=nan, se=nan, deviance=np.nan, iterations=k, flags=RANK_BIT, crit=crits)
+            return dict(coef=nan, se=nan, deviance=np.nan, iterations=k, flags=RANK_BIT, crit=crits, pivots=pivots, eta_max=eta_max)
         beta = solve(L, b, dtype)
         eta = X @ beta
         _, mu = _mean(eta, dtype)
@@ -118,7 +125,8 @@ def fit(X, y, wt, maxit=25, epsilon=1e-8, dtype=np.float64):
         flags |= MAXIT_BIT
     if ((mu < 10 * eps) | (mu > 1 - 10 * eps)).any():
         flags |= BOUNDARY_BIT
-    return dict(coef=beta, se=np.sqrt(inverse_diagonal(L, dtype)), deviance=dev, iterations=k, flags=flags, crit=crits)
+    return dict(coef=beta, se=np.sqrt(inverse_diagonal(L, dtype)), deviance=dev, iterations=k, flags=flags, crit=crits, pivots=pivots,
+                eta_max=eta_max)
 
 
 def fit_slots(F, rsum, model, n):
@@ -137,7 +145,8 @@ def fit_slots(F, rsum, model, n):
 
 def glm_rows(F, model, covar, weight, y, maxit=25, epsilon=1e-8, dtype=np.float64):
     """What hibag_hip_assoc_glm returns from the feature rows F [rows, n]: dict of coef, se [T + 1, 16] by slot (float64),
-    deviance, iterations, flags [T + 1], and crit, a list of every fit's criteria; fit T is the base model."""
+    deviance, iterations, flags [T + 1], and crit, pivots, eta_max, lists of every fit's criteria, tested pivots and largest
+    |eta|; fit T is the base model."""
     n = F.shape[1]
     covar = np.zeros((0, n)) if covar is None else np.asarray(covar, np.float64).reshape(-1, n)
     q = len(covar)
@@ -146,7 +155,8 @@ def glm_rows(F, model, covar, weight, y, maxit=25, epsilon=1e-8, dtype=np.float6
     slots = fit_slots(F, F.sum(axis=1), model, n) + [(-1, -1)]
     n_fit = len(slots)
     out = dict(coef=np.full((n_fit, SLOTS), np.nan), se=np.full((n_fit, SLOTS), np.nan), deviance=np.full(n_fit, np.nan),
-               iterations=np.zeros(n_fit, np.int32), flags=np.zeros(n_fit, np.int32), crit=[[] for _ in range(n_fit)])
+               iterations=np.zeros(n_fit, np.int32), flags=np.zeros(n_fit, np.int32), crit=[[] for _ in range(n_fit)],
+               pivots=[[] for _ in range(n_fit)], eta_max=[0.0] * n_fit)
     for f, rows in enumerate(slots):
         if rows is None:
             out["flags"][f] = RANK_BIT
@@ -158,6 +168,7 @@ def glm_rows(F, model, covar, weight, y, maxit=25, epsilon=1e-8, dtype=np.float6
         out["se"][f, used] = np.asarray(res["se"], np.float64)
         out["deviance"][f] = float(res["deviance"])
         out["iterations"][f], out["flags"][f], out["crit"][f] = res["iterations"], res["flags"], res["crit"]
+        out["pivots"][f], out["eta_max"][f] = res["pivots"], res["eta_max"]
     return out
 
 

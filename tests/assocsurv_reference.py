@@ -42,7 +42,7 @@ class Blocks:
 
 
 def evaluate(X, e, B, beta, ties="efron", dtype=np.float64):
-    """Item 4 at beta: (loglik, U [p], I [p, p], clamped)."""
+    """Item 4 at beta: (loglik, U [p], I [p, p], clamped, diag G [p]) with G = sum w x x', the Gram I = G - V is left of."""
     X = np.asarray(X, dtype)
     n, p = X.shape
     ev = np.asarray(e) != 0
@@ -70,8 +70,8 @@ def evaluate(X, e, B, beta, ties="efron", dtype=np.float64):
     w = r * (A[B.blk] - np.where(ev, b[B.blk], dtype(0)))
     loglik = np.where(ev, eta, dtype(0)).sum() - np.log(phi).sum()
     U = np.where(ev[:, None], X, dtype(0)).sum(axis=0) - (w[:, None] * X).sum(axis=0)
-    info = X.T @ (w[:, None] * X) - v.T @ v
-    return loglik, U, info, clamped
+    gram = X.T @ (w[:, None] * X)
+    return loglik, U, gram - v.T @ v, clamped, np.diag(gram)
 
 
 def inverse_block(L, d, dtype):
@@ -91,24 +91,24 @@ def inverse_block(L, d, dtype):
 
 def fit(X, e, B, start, d, ties="efron", maxit=20, epsilon=1e-9, dtype=np.float64):
     """One fit of items 5-6 from ``start``; the first ``d`` columns of X are the h columns.  dict coef, se [p], loglik,
-    score, iterations, flags, crit (every iteration's)."""
+    score, iterations, flags, crit (every iteration's), pivots (every tested pivot with its threshold)."""
     p = X.shape[1]
     nan = np.full(p, np.nan)
     beta = np.asarray(start, dtype).copy()
-    ll, U, info, clamped = evaluate(X, e, B, beta, ties, dtype)
+    ll, U, info, clamped, gdiag = evaluate(X, e, B, beta, ties, dtype)
     flags = CLAMP_BIT if clamped else 0
     if p == 0:
-        return dict(coef=nan, se=nan, loglik=ll, score=np.nan, iterations=0, flags=flags, crit=[])
-    score, crits, L = np.nan, [], None
+        return dict(coef=nan, se=nan, loglik=ll, score=np.nan, iterations=0, flags=flags, crit=[], pivots=[])
+    score, crits, pivots, L = np.nan, [], [], None
     for k in range(1, maxit + 1):
-        L = G.cholesky(info, dtype)
+        L = G.cholesky(info, dtype, scale=gdiag, pivots=pivots)          # a pivot is judged against G_jj (item 5)
         if L is None:
-            return dict(coef=nan, se=nan, loglik=np.nan, score=np.nan, iterations=k, flags=RANK_BIT, crit=crits)
+            return dict(coef=nan, se=nan, loglik=np.nan, score=np.nan, iterations=k, flags=RANK_BIT, crit=crits, pivots=pivots)
         if k == 1 and d > 0:
             M = inverse_block(L, d, dtype)
             score = sum(U[i] * M[i, j] * U[j] for i in range(d) for j in range(d))
         beta = beta + G.solve(L, U, dtype)
-        ll_new, U, info, clamped = evaluate(X, e, B, beta, ties, dtype)
+        ll_new, U, info, clamped, gdiag = evaluate(X, e, B, beta, ties, dtype)
         if clamped:
             flags |= CLAMP_BIT
         with np.errstate(divide="ignore", invalid="ignore"):
@@ -121,7 +121,8 @@ def fit(X, e, B, start, d, ties="efron", maxit=20, epsilon=1e-9, dtype=np.float6
             flags |= DECREASE_BIT
     else:
         flags |= MAXIT_BIT
-    return dict(coef=beta, se=np.sqrt(G.inverse_diagonal(L, dtype)), loglik=ll, score=score, iterations=k, flags=flags, crit=crits)
+    return dict(coef=beta, se=np.sqrt(G.inverse_diagonal(L, dtype)), loglik=ll, score=score, iterations=k, flags=flags, crit=crits,
+                pivots=pivots)
 
 
 def fit_slots(rsum, model, n):
@@ -131,7 +132,7 @@ def fit_slots(rsum, model, n):
 
 def cox_rows(F, model, time, covar, e, ties="efron", maxit=20, epsilon=1e-9, dtype=np.float64, start=None):
     """What hibag_hip_assoc_cox returns from the feature rows F [rows, n] in time order: dict of coef, se [1 + T, 16] by
-    slot (float64), loglik, score, iterations, flags [1 + T], and crit, a list of every fit's criteria; fit 0 is the base
+    slot (float64), loglik, score, iterations, flags [1 + T], and crit and pivots, lists of every fit's criteria and tested pivots; fit 0 is the base
     model.  covar [q, n] is taken as it is (the caller centres it)."""
     n = F.shape[1]
     covar = np.zeros((0, n)) if covar is None else np.asarray(covar, np.float64).reshape(-1, n)
@@ -145,7 +146,7 @@ def cox_rows(F, model, time, covar, e, ties="efron", maxit=20, epsilon=1e-9, dty
     n_fit = len(slots)
     out = dict(coef=np.full((n_fit, SLOTS), np.nan), se=np.full((n_fit, SLOTS), np.nan), loglik=np.full(n_fit, np.nan),
                score=np.full(n_fit, np.nan), iterations=np.zeros(n_fit, np.int32), flags=np.zeros(n_fit, np.int32),
-               crit=[[] for _ in range(n_fit)])
+               crit=[[] for _ in range(n_fit)], pivots=[[] for _ in range(n_fit)])
     base = np.zeros(q) if start is None else np.asarray(start, np.float64)
     for f, rows in enumerate(slots):
         if rows is None:
@@ -159,6 +160,7 @@ def cox_rows(F, model, time, covar, e, ties="efron", maxit=20, epsilon=1e-9, dty
         out["se"][f, used] = np.asarray(res["se"], np.float64)
         out["loglik"][f], out["score"][f] = float(res["loglik"]), float(res["score"])
         out["iterations"][f], out["flags"][f], out["crit"][f] = res["iterations"], res["flags"], res["crit"]
+        out["pivots"][f] = res["pivots"]
         if f == 0:
             if res["flags"] & RANK_BIT:                          # no base model, no start: every test is reported like it
                 out["flags"][1:] = RANK_BIT
